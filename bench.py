@@ -20,7 +20,11 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   value / ms_per_step   wall clock of K timed steps (barrier + synchronize on both sides, MAX over ranks); the timed call
                  passes `routing=` (the caller knows whether frame 3 is zero; no host sync).  `reference_call` times the same K
                  steps as the reference calls it, `forward(x)`: the routing test runs on the device and syncs once per call.
-  step_ms        median / p10 / p90 of the K per-step GPU durations (HIP events on the launch stream)
+  step_ms        median / p10 / p90 of the K per-step GPU durations (HIP events on the launch stream; with K <= --inflight no
+                 same-stream pair exists and it holds the wall-clock ms_per_step alone)
+  --dump-outputs DIR   writes what the LAST timed step returned to its caller (rank 0: the [B,3,H,W] frames) as DIR/output.npy,
+                 float32, at most 64 MB (a fixed seed-0 sample of flat indices beyond that, DIR/output_index.npy); the inputs are
+                 seeded, so two builds run with the same arguments can be compared output for output
   roofline       the largest kernel (fused correlation arg-max, 37 % of the path's algorithmic FLOPs, one launch per frame):
                  FLOPs per launch / its average duration (`achieved`: the flops the dispatched kernel EXECUTES — the diagonal-sliding
                  kernel of round 3 computes each row-against-row term once, a third of the bmm's count, so the algorithmic count /
@@ -55,6 +59,7 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -245,6 +250,28 @@ def family_records(fam_events: dict, n_frames: int, h: int, w: int, has_ref: boo
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write each tensor as out_dir/<name>.npy in float32.  Over DUMP_LIMIT_BYTES in all, each keeps a fixed sample instead: flat
+    indices drawn by a generator of seed 0, sorted and saved beside it as <name>_index.npy (int64), the same for every run of a shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    sampled = total > DUMP_LIMIT_BYTES
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if sampled:
+            keep = max(1, t.numel() * DUMP_LIMIT_BYTES // (3 * total))       # 4-byte values + 8-byte indices stay under the limit
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.reshape(-1)[idx]
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.numpy())
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+        shapes[name] = list(t.shape)
+    return {"dir": out_dir, "shapes": shapes, "sampled": sampled}
+
+
 def train_main(argv=None):
     """`bench.py --train ...`: training-step throughput (config 5), see the module docstring."""
     line = train_measure(argv)
@@ -399,7 +426,11 @@ def main():
     ap.add_argument("--knobs", default="", help='experiments: JSON of extra speinet_amd.ops.Ctx fields, e.g. \'{"stage": {"glue": {"precision": "bf16x3"}}}\'')
     ap.add_argument("--height", type=int, default=H)
     ap.add_argument("--width", type=int, default=W)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
 
     if "RANK" not in os.environ and args.gpus > 1:
         # one command for N GPUs: this parent never touches the GPU; it starts the N ranks (python -m torch.distributed.run ...
@@ -458,7 +489,7 @@ def main():
     lanes = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(device=dev) for _ in range(nfl - 1)]
 
     def run_steps(n, **kw):
-        gate = None
+        gate, out = None, None
         for i in range(n):
             with torch.cuda.stream(lanes[i % nfl]):
                 if gate is not None and nfl > 1 and gate_mode != "none":
@@ -472,6 +503,7 @@ def main():
                 checksums[i % nfl].add_(out.double().sum())
                 if pr is not None:
                     marks[i + 1].record()
+        return out
 
     with torch.no_grad():
         run_steps(max(args.warmup, nfl), routing=routing)
@@ -482,9 +514,11 @@ def main():
         barrier()
         t0 = time.perf_counter()
         marks[0].record()
-        run_steps(args.steps, routing=routing, profile=prof)
+        last_out = run_steps(args.steps, routing=routing, profile=prof)
         barrier()
         dt = time.perf_counter() - t0
+        dumped = dump_outputs(args.dump_outputs, {"output": last_out}) if args.dump_outputs and rank == 0 else None
+        del last_out
         checksum = sum(checksums)
         # ---- the same steps the way the reference calls forward: no routing hint (device test + one host sync per call) ----
         barrier()
@@ -507,6 +541,8 @@ def main():
             net.use_graph, net.streams = keep
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)] if nfl == 1 else \
               [marks[i].elapsed_time(marks[i + nfl]) / nfl for i in range(1, args.steps + 1 - nfl)]   # same-stream neighbours
+    if not step_ms:                     # steps <= frames in flight: no same-stream pair to time, only the wall clock of the region
+        step_ms = [1e3 * dt / args.steps]
     pairs = prof["corr_argmax"]
     corr_ms = sum(s.elapsed_time(e) for s, e in pairs) / max(1, len(pairs))
     assert len(pairs) == args.steps * nb, "the dominant kernel must be timed once per frame"
@@ -576,6 +612,8 @@ def main():
                          "path_hbm_frac": (path_hbm * fps / world / 8e12) if path_hbm else None},
             "checksum": float(gathered[:, 0].sum().item()),
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         extras = world == 1 and not args.no_extras and (h, w) == (H, W) and args.precision == "f16" and nb == 1
         if extras:
             # BASELINE.json configs[1] to the letter ("bf16 forward"): the same steps with bf16 operands (8-bit significands: 3e-3 dB)
