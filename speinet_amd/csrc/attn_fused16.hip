@@ -949,6 +949,8 @@ __global__ __launch_bounds__(512) void attn_pipe_kernel(const Attn4Params<LP> p,
         const int grpn = tnx - bq_ * p.groups, bmapn = tnx < ntiles ? bq_ : bmap;
         const int rotn = grpn & 15, rot4n = (grpn * 3) & 15;
         const size_t moff = (size_t)__builtin_amdgcn_readfirstlane(bmap) * HW * D, moffn = (size_t)__builtin_amdgcn_readfirstlane(bmapn) * HW * D;
+        // (int byte counts: HW <= 2^21 is a multiple of 25, so HW * 1024 <= 2^31 - 2048 and a row's offset never overflows; an absent row,
+        // entry -1, is -1024 + channel = beyond the range as an unsigned offset)
         const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + moff), 0, HW * (D * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(p.out + moff, 0, HW * (D * 4), 0x00020000);
         // fragment q of the tile's weight stream (q = 16 pass + step; q >= 64: the next tile's Q pass)
@@ -1136,7 +1138,7 @@ __global__ __launch_bounds__(512) void attn_pipe_kernel(const Attn4Params<LP> p,
                     const int en[4] = {ent.x, ent.y, ent.z, ent.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        accp[i][4 * k + e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsx, (en[e] << 10) + voff_ch, soff_w, 0));
+                        accp[i][4 * k + e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsx, en[e] * 1024 + voff_ch, soff_w, 0));
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
@@ -1160,7 +1162,7 @@ __global__ __launch_bounds__(512) void attn_pipe_kernel(const Attn4Params<LP> p,
                     const int en[4] = {ent.x, ent.y, ent.z, ent.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        accp[i][4 * k + e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsx, (en[e] << 10) + voff_ch, soff_w, 0));
+                        accp[i][4 * k + e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsx, en[e] * 1024 + voff_ch, soff_w, 0));
                     __builtin_amdgcn_sched_barrier(0);
                 }
         }
@@ -1200,7 +1202,7 @@ __global__ __launch_bounds__(512) void attn_pipe_kernel(const Attn4Params<LP> p,
                 const int en[4] = {ent.x, ent.y, ent.z, ent.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(accp[i][4 * k + e]), rso, (en[e] << 10) + voff_ch, soff_w, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(accp[i][4 * k + e]), rso, en[e] * 1024 + voff_ch, soff_w, 0);
                 __builtin_amdgcn_sched_barrier(0);    // group by group: 16 table reads in flight at once are 64 more live registers
             }
         lds_barrier();                                // slab X holds the next tile; slab Yc is free; the table after next is complete
@@ -1212,7 +1214,7 @@ __global__ __launch_bounds__(512) void attn_pipe_kernel(const Attn4Params<LP> p,
                 const int en[4] = {ent.x, ent.y, ent.z, ent.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(accp[i][4 * k + e]), rso, (en[e] << 10) + voff_ch, soff_w, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(accp[i][4 * k + e]), rso, en[e] * 1024 + voff_ch, soff_w, 0);
                 __builtin_amdgcn_sched_barrier(0);    // group by group: 16 table reads in flight at once are 64 more live registers
             }
         if (first) SPEI_STAMP(p.stamps, 6);

@@ -139,6 +139,7 @@ __global__ __launch_bounds__(512) void conv3_pipe_kernel(const C3Params<LP> p) {
         int bmap, y0, x0;
         tile_origin(tile, bmap, y0, x0);
         const size_t moff = (size_t)bmap * HW * C;
+        // (int byte counts: HW <= 2^21 is a multiple of 6 x 16, so HW * 1024 <= 2^31 - 32768 and no pixel offset overflows)
         const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(p.out + moff, 0, HW * (C * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res + moff : p.out + moff), 0,
                                                                              p.res ? HW * (C * 4) : 0, 0x00020000);

@@ -420,10 +420,12 @@ __global__ __launch_bounds__(512) void mlp_pipe_kernel(const MlpParams<LP> p, co
     SPEI_STAMP(p.stamps, 1); SPEI_STAMP_CLK(p.stamps, 8 + 1);
 
     // x and out through buffer descriptors whose range is the M rows: dword accesses in the accumulators' own layout (register 4 k + e of
-    // row tile i <-> row 32 i + 8 k + 4 fk + e, channel 32 wave + fr), out-of-range rows read 0 / are not written
-    const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.M * (D * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, p.M * (D * 4), 0x00020000);
-    const int voff_row = fk * 4096 + fr * 4;
+    // row tile i <-> row 32 i + 8 k + 4 fk + e, channel 32 wave + fr), out-of-range rows read 0 / are not written.  Range and row offsets
+    // are unsigned 32-bit byte counts: at M = 2^21 the range is 2^31 and the last tile's rows run past it, which in int is overflow
+    const unsigned range = (unsigned)p.M * (D * 4u);
+    const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)range, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)range, 0x00020000);
+    const unsigned voff_row = fk * 4096 + fr * 4;
     f32x16 acc2[RP3];                                       // fc2 accumulators; a tile's results are stored under the NEXT tile's P1
 #pragma unroll
     for (int i = 0; i < RP3; ++i)
@@ -496,8 +498,9 @@ __global__ __launch_bounds__(512) void mlp_pipe_kernel(const MlpParams<LP> p, co
         };
 
         // byte offsets of (row 4 fk of the tile, channel fr) for the previous tile's stores and this tile's residual loads; before the
-        // first tile the "previous" offset is negative = beyond any descriptor range (M <= 2^21 rows): those stores are dropped
-        const int vthis = voff_row + tile * (MP * 1024), vprev = vthis - (int)gridDim.x * (MP * 1024);
+        // first tile the "previous" offset wraps below zero to >= 2^32 - 2^25 = beyond any descriptor range (M <= 2^21 rows): those
+        // stores are dropped
+        const unsigned vthis = voff_row + (unsigned)tile * (MP * 1024u), vprev = vthis - gridDim.x * (MP * 1024u);
         f32x16 acc1a[RP3], acc1b[RP3];
         f32x16 res[RP3];                                    // this tile's residual rows, in the fc2 accumulators' layout
         init_rows(acc1a, bias1);
@@ -510,11 +513,11 @@ __global__ __launch_bounds__(512) void mlp_pipe_kernel(const MlpParams<LP> p, co
                 const int i = s >> 2, k = s & 3;
                 // the row lives in the VECTOR offset (the descriptor's range check covers vector offset + immediate only; the scalar
                 // offset carries the wave's 128-byte channel block, which never leaves the row)
-                const int vst = vprev + (i * 32 + 8 * k) * 1024, vld = vthis + (i * 32 + 8 * k) * 1024;
+                const unsigned vst = vprev + (i * 32 + 8 * k) * 1024u, vld = vthis + (i * 32 + 8 * k) * 1024u;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc2[i][4 * k + e]), rso, vst + e * 1024, wave * 128, 0);
-                    res[i][4 * k + e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsx, vld + e * 1024, wave * 128, 0));
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc2[i][4 * k + e]), rso, (int)(vst + e * 1024u), wave * 128, 0);
+                    res[i][4 * k + e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsx, (int)(vld + e * 1024u), wave * 128, 0));
                 }
             }
         });
@@ -558,7 +561,8 @@ __global__ __launch_bounds__(512) void mlp_pipe_kernel(const MlpParams<LP> p, co
 #pragma unroll
         for (int r = 0; r < 16; ++r)
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc2[i][r]), rso,
-                                                  voff_row + (tile - (int)gridDim.x) * (MP * 1024) + (i * 32 + 8 * (r >> 2) + (r & 3)) * 1024, wave * 128, 0);
+                                                  (int)(voff_row + (unsigned)(tile - (int)gridDim.x) * (MP * 1024u) +
+                                                        (i * 32 + 8 * (r >> 2) + (r & 3)) * 1024u), wave * 128, 0);
     SPEI_STAMP(p.stamps, 7); SPEI_STAMP_CLK(p.stamps, 8 + 7);
 }
 
