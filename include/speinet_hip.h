@@ -311,7 +311,8 @@ int spei_conv_wgrad_f32_batched(const float* x, int ldx, const float* dy, int ld
 /* Training: a weight in the reference's layout (Conv2d [N][K][ks][ks] / Linear [N][K], fp32) -> the split pair
  * hi = bf16(w), lo = bf16(w - hi) in the slab kernels' fragment order, one launch.  mode 0: the forward GEMM weight
  * [tap][N][K]; mode 1: the stride-1 data-gradient weight (taps reversed, channel axes swapped: [tap][K][N]).  The
- * weights of a training step change every optimizer step (trainer/trainer_swint.py:39-44). */
+ * weights of a training step change every optimizer step (trainer/trainer_swint.py:39-44).  frag_lo == NULL: only
+ * hi = bf16(w) (round to nearest even) is written — the single fragment of train_precision = "bf16". */
 int spei_pack_split16(const float* w, int N, int K, int ksize, int mode, void* frag_hi, void* frag_lo, spei_stream_t stream);
 
 /* The same weight / bias gradient with the products split on the 16-bit matrix pipe (a = ah + al in bf16: al*bh + ah*bl + ah*bh,
@@ -320,6 +321,23 @@ int spei_pack_split16(const float* w, int N, int K, int ksize, int mode, void* f
  * spei_conv_wgrad_f32_batched. */
 int spei_conv_wgrad_bf16x3_batched(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* ws, int Hin, int Win,
                                    int Hout, int Wout, int N, int K, int ksize, int stride, int pad, int batch, spei_stream_t stream);
+
+/* The same weight gradient in single products (speinet_amd/train.py `train_precision = "bf16"`, the arithmetic of the reference's
+ * main_SPEINet.py:12 `set_float32_matmul_precision('medium')`): dY and X rounded once to bf16 (round to nearest even), one
+ * v_mfma_f32_32x32x16_bf16 per 16 pixels, fp32 accumulation; the bias gradient stays an fp32 column sum.  Replaces the weight
+ * gradients of loss.backward() (trainer/trainer_swint.py:42) for every Conv2d / ConvTranspose2d / Linear.  Arguments, workspace,
+ * partial layout and fixed summation order as spei_conv_wgrad_bf16x3_batched (bitwise reproducible). */
+int spei_conv_wgrad_bf16_batched(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* ws, int Hin, int Win,
+                                 int Hout, int Wout, int N, int K, int ksize, int stride, int pad, int batch, spei_stream_t stream);
+
+/* Data gradient of a stride-2 Conv2d (k = 3 or 5, padding k / 2; model/recons_video_ori.py:40-56 encoder heads, whose
+ * loss.backward() it replaces) on the slab kernel: the adjoint (transposed) convolution of dY [batch][Hin][Win][k0] fp32, split
+ * into the four output-parity classes, each a stride-1 convolution over the dY grid with <= 9 taps, written with pixel stride 2
+ * into out [batch][2Hin][2Win][N] fp32 (the caller crops an odd input size).  wfrag4: the fragment-ordered bf16 weights of the
+ * classes (oy % 2, ox % 2) = 00, 01, 10, 11 (speinet_amd/train.py `_s2_adjoint_frags`): taps ky, kx with (p + pad - k) even,
+ * ky-major.  Operands rounded once to bf16, fp32 accumulation. */
+int spei_conv_s2_adjoint_slab16(const float* dy, int k0, const void* const* wfrag4, float* out, int N, int Hin, int Win, int ksize,
+                                int batch, spei_stream_t stream);
 
 /* ReLU backward on the output of a fused conv + ReLU: dz = dy where y > 0, else 0 (n floats, n % 4 == 0). */
 int spei_relu_bwd(const float* y, const float* dy, float* dz, int64_t n, spei_stream_t stream);
@@ -390,6 +408,18 @@ int spei_gelu_bwd(const float* pre, const float* dy, float* dpre, int64_t n, spe
  * equally sized maps stored one after the other are processed in one launch (dbias_part [batch][nwin][8][25][25]). */
 int spei_window_attention_bwd(const float* q, const float* kv, const float* relbias, const float* dout, float* dq, float* dkv,
                               float* dbias_part, int H, int W, int shift, int batch, spei_stream_t stream);
+
+/* Window attention for training in bf16 on the 16-bit matrix pipe (speinet_amd/train.py `train_precision = "bf16"`;
+ * model/swinir.py:115-149 under train() mode and loss.backward()).  Forward: q, kv fp32 in HBM, rounded once to bf16 while staged,
+ * S = Q K^T and O = P V each as two v_mfma_f32_32x32x16_bf16 per (window, head) (25 tokens padded to 32), softmax, relative bias and
+ * shift mask in fp32, P rounded to bf16 as the second product's operand, out fp32.  Backward: P recomputed from q / k (never
+ * stored); dP = dO V^T, dV = P^T dO, dQ = dS K, dK = dS^T Q on the same MFMA with P and dS rounded to bf16 as operands; dbias_part
+ * holds the fp32 dS.  Arguments, layouts, mask, shift and the dbias_part layout as spei_window_attention_batched /
+ * spei_window_attention_bwd. */
+int spei_window_attention16_train(const float* q, const float* kv, const float* relbias, float* out, int H, int W, int shift, int batch,
+                                  spei_stream_t stream);
+int spei_window_attention16_bwd(const float* q, const float* kv, const float* relbias, const float* dout, float* dq, float* dkv,
+                                float* dbias_part, int H, int W, int shift, int batch, spei_stream_t stream);
 
 /* out[m][n] = x[m][n] * rowscale[m] (the DropPath factor of model/swinir.py:278-279 applied to a branch gradient).  N % 4 == 0. */
 int spei_scale_rows(const float* x, const float* rowscale, float* out, int64_t M, int N, spei_stream_t stream);

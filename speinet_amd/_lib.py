@@ -68,6 +68,8 @@ SIGNATURES = {
     "spei_wgrad_ws_floats": (L, [I, I, I, I, I]),
     "spei_conv_wgrad_f32_batched": (I, [P, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
     "spei_conv_wgrad_bf16x3_batched": (I, [P, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
+    "spei_conv_wgrad_bf16_batched": (I, [P, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
+    "spei_conv_s2_adjoint_slab16": (I, [P, I, P, P, I, I, I, I, I, P]),
     "spei_conv_wgrad_f32": (I, [P, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "spei_relu_bwd": (I, [P, P, P, L, P]),
     "spei_plane_ws_floats": (L, [I, I, I]),
@@ -85,6 +87,8 @@ SIGNATURES = {
     "spei_gelu_fwd": (I, [P, P, L, P]),
     "spei_gelu_bwd": (I, [P, P, P, L, P]),
     "spei_window_attention_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
+    "spei_window_attention16_train": (I, [P, P, P, P, I, I, I, I, P]),
+    "spei_window_attention16_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     "spei_scale_rows": (I, [P, P, P, L, I, P]),
     "spei_corr_s_bwd_lr": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "spei_search_bwd_ref": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),

@@ -101,6 +101,9 @@ struct Wgrad16Params {
     int batch, nseg_row, nseg, chunk_seg;    // segments per output row, in all, per chunk (a multiple of 4)
 };
 
+// SPLIT = false (train_precision = "bf16"): each operand rounded once to bf16 (round to nearest even), ONE MFMA per 16 pixels; the
+// same work units, partial layout and two-stage sum, so the result is as reproducible as the split form's.
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void conv_wgrad16_kernel(const Wgrad16Params p) {
     typedef lpv<__bf16>::x8 bf8;
     __shared__ float red[4][16][64];
@@ -147,13 +150,17 @@ __global__ __launch_bounds__(256) void conv_wgrad16_kernel(const Wgrad16Params p
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             ah[j] = (__bf16)a[j];
-            al[j] = (__bf16)(a[j] - (float)ah[j]);
             bh[j] = (__bf16)b[j];
-            bl[j] = (__bf16)(b[j] - (float)bh[j]);
+            if (SPLIT) {
+                al[j] = (__bf16)(a[j] - (float)ah[j]);
+                bl[j] = (__bf16)(b[j] - (float)bh[j]);
+            }
             asum += a[j];
         }
-        acc = mfma16(al, bh, acc);
-        acc = mfma16(ah, bl, acc);
+        if (SPLIT) {
+            acc = mfma16(al, bh, acc);
+            acc = mfma16(ah, bl, acc);
+        }
         acc = mfma16(ah, bh, acc);
     }
     bred[wave][lane] = asum;
@@ -182,7 +189,7 @@ __global__ __launch_bounds__(256) void conv_wgrad16_kernel(const Wgrad16Params p
 // split once per segment for the KS taps, and the X values of the KS shifted windows are one run of 8 + KS - 1 pixels per lane,
 // gathered and split once: 3 KS MFMAs per ~(20 + 3 KS) gathers / conversions per lane instead of 3 per ~16 — the per-tap form above
 // was bound by those, not by the matrix pipe (conv_wgrad16: 193 us per layer at batch 20).
-template <int KS>
+template <int KS, bool SPLIT>
 __global__ __launch_bounds__(256) void conv_wgrad16_row_kernel(const Wgrad16Params p) {
     typedef lpv<__bf16>::x8 bf8;
     constexpr int NX = 8 + KS - 1;
@@ -229,26 +236,31 @@ __global__ __launch_bounds__(256) void conv_wgrad16_row_kernel(const Wgrad16Para
         for (int j = 0; j < NX; ++j) xx[j] = xn[j];
         if (sg + 1 < s1) load(sg + 1, an, xn);
         bf8 ah, al;
-        __bf16 xh[NX], xl[NX];
+        __bf16 xh[NX], xl[SPLIT ? NX : 1];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             ah[j] = (__bf16)a[j];
-            al[j] = (__bf16)(a[j] - (float)ah[j]);
+            if (SPLIT) al[j] = (__bf16)(a[j] - (float)ah[j]);
             asum += a[j];
         }
 #pragma unroll
         for (int j = 0; j < NX; ++j) {
             xh[j] = (__bf16)xx[j];
-            xl[j] = (__bf16)(xx[j] - (float)xh[j]);
+            if (SPLIT) xl[j] = (__bf16)(xx[j] - (float)xh[j]);
         }
         // pixels of the segment past the row's end carry dY = 0: their products vanish whatever X holds
 #pragma unroll
         for (int t = 0; t < KS; ++t) {
             bf8 bh, bl;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { bh[j] = xh[j + t]; bl[j] = xl[j + t]; }
-            acc[t] = mfma16(al, bh, acc[t]);
-            acc[t] = mfma16(ah, bl, acc[t]);
+            for (int j = 0; j < 8; ++j) {
+                bh[j] = xh[j + t];
+                if (SPLIT) bl[j] = xl[j + t];
+            }
+            if (SPLIT) {
+                acc[t] = mfma16(al, bh, acc[t]);
+                acc[t] = mfma16(ah, bl, acc[t]);
+            }
             acc[t] = mfma16(ah, bh, acc[t]);
         }
     }
@@ -281,6 +293,7 @@ __global__ __launch_bounds__(256) void conv_wgrad16_row_kernel(const Wgrad16Para
 
 // 1x1 layers (the Swin linears): no taps to share the gathers, so a workgroup takes a 64 x 64 tile (2 x 2 MFMA tiles): the dY values
 // of two channel tiles and the X values of two feed twelve MFMAs per 32 gathers per lane instead of three per 16.
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void conv_wgrad16_1x1_kernel(const Wgrad16Params p) {
     typedef lpv<__bf16>::x8 bf8;
     __shared__ float red[4][16][64];
@@ -329,17 +342,21 @@ __global__ __launch_bounds__(256) void conv_wgrad16_1x1_kernel(const Wgrad16Para
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 ah[i][j] = (__bf16)a[i][j];
-                al[i][j] = (__bf16)(a[i][j] - (float)ah[i][j]);
                 bh[i][j] = (__bf16)x[i][j];
-                bl[i][j] = (__bf16)(x[i][j] - (float)bh[i][j]);
+                if (SPLIT) {
+                    al[i][j] = (__bf16)(a[i][j] - (float)ah[i][j]);
+                    bl[i][j] = (__bf16)(x[i][j] - (float)bh[i][j]);
+                }
                 asum[i] += a[i][j];
             }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                acc[i][j] = mfma16(al[i], bh[j], acc[i][j]);
-                acc[i][j] = mfma16(ah[i], bl[j], acc[i][j]);
+                if (SPLIT) {
+                    acc[i][j] = mfma16(al[i], bh[j], acc[i][j]);
+                    acc[i][j] = mfma16(ah[i], bl[j], acc[i][j]);
+                }
                 acc[i][j] = mfma16(ah[i], bh[j], acc[i][j]);
             }
     }
@@ -573,7 +590,8 @@ extern "C" int64_t spei_wgrad_ws_floats(int Hout, int Wout, int N, int K, int ks
 }
 
 static int conv_wgrad_run(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* ws, int Hin, int Win,
-                          int Hout, int Wout, int N, int K, int ksize, int stride, int pad, int batch, spei_stream_t stream, bool split = false) {
+                          int Hout, int Wout, int N, int K, int ksize, int stride, int pad, int batch, spei_stream_t stream, int form = 0) {
+    // form: 0 fp32 (v_mfma_f32_32x32x2_f32), 1 split bf16x3, 2 single-product bf16
     SPEI_REQUIRE(x && dy && dw && ws, "spei_conv_wgrad_f32: null pointer");
     SPEI_REQUIRE(batch >= 1 && (int64_t)batch * Hout * Wout < (1ll << 30), "spei_conv_wgrad_f32: batch=%d", batch);
     SPEI_REQUIRE(N > 0 && K > 0 && N <= 256 && ldx >= K && ldy >= N, "spei_conv_wgrad_f32: N=%d K=%d ldx=%d ldy=%d", N, K, ldx, ldy);
@@ -584,7 +602,8 @@ static int conv_wgrad_run(const float* x, int ldx, const float* dy, int ldy, flo
                  "spei_conv_wgrad_f32: output size %dx%d inconsistent with input %dx%d k%d s%d p%d", Hout, Wout, Hin, Win, ksize, stride, pad);
     hipStream_t st = (hipStream_t)stream;
     const int M = Hout * Wout * batch, T = ksize * ksize;
-    if (split) {
+    if (form) {
+        const bool split = form == 1;
         Wgrad16Params q;
         q.x = x; q.dy = dy; q.part = ws; q.ldx = ldx; q.ldy = ldy; q.K = K; q.N = N; q.batch = batch;
         q.Hin = Hin; q.Win = Win; q.Hout = Hout; q.Wout = Wout; q.ks = ksize; q.stride = stride; q.pad = pad;
@@ -600,14 +619,22 @@ static int conv_wgrad_run(const float* x, int ldx, const float* dy, int ldy, flo
         const int nchunks = cdiv(q.nseg, chunk);
         float* bpart = ws + (size_t)wgrad_ws_slices(N, K, ksize) * T * N * K;
         q.bpart = dbias ? bpart : nullptr;
-        if (!rows) hipLaunchKernelGGL(conv_wgrad16_kernel, dim3(T * q.ntn * q.ntk, nchunks), dim3(256), 0, st, q);
-        else if (ksize == 5) hipLaunchKernelGGL(conv_wgrad16_row_kernel<5>, dim3(ksize * q.ntn * q.ntk, nchunks), dim3(256), 0, st, q);
-        else if (ksize == 3) hipLaunchKernelGGL(conv_wgrad16_row_kernel<3>, dim3(ksize * q.ntn * q.ntk, nchunks), dim3(256), 0, st, q);
-        else hipLaunchKernelGGL(conv_wgrad16_1x1_kernel, dim3(((q.ntn + 1) / 2) * ((q.ntk + 1) / 2), nchunks), dim3(256), 0, st, q);
+        const dim3 gt(T * q.ntn * q.ntk, nchunks), gr(ksize * q.ntn * q.ntk, nchunks), g1(((q.ntn + 1) / 2) * ((q.ntk + 1) / 2), nchunks);
+        if (split) {
+            if (!rows) hipLaunchKernelGGL(conv_wgrad16_kernel<true>, gt, dim3(256), 0, st, q);
+            else if (ksize == 5) hipLaunchKernelGGL((conv_wgrad16_row_kernel<5, true>), gr, dim3(256), 0, st, q);
+            else if (ksize == 3) hipLaunchKernelGGL((conv_wgrad16_row_kernel<3, true>), gr, dim3(256), 0, st, q);
+            else hipLaunchKernelGGL(conv_wgrad16_1x1_kernel<true>, g1, dim3(256), 0, st, q);
+        } else {
+            if (!rows) hipLaunchKernelGGL(conv_wgrad16_kernel<false>, gt, dim3(256), 0, st, q);
+            else if (ksize == 5) hipLaunchKernelGGL((conv_wgrad16_row_kernel<5, false>), gr, dim3(256), 0, st, q);
+            else if (ksize == 3) hipLaunchKernelGGL((conv_wgrad16_row_kernel<3, false>), gr, dim3(256), 0, st, q);
+            else hipLaunchKernelGGL(conv_wgrad16_1x1_kernel<false>, g1, dim3(256), 0, st, q);
+        }
         const int64_t count = (int64_t)T * N * K;
         hipLaunchKernelGGL(partial_sum_kernel, dim3(cdiv(count + (dbias ? N : 0), 256)), dim3(256), 0, st, ws, dw, count, nchunks,
                            dbias ? bpart : nullptr, dbias, dbias ? N : 0);
-        SPEI_CHECK_LAUNCH("spei_conv_wgrad_bf16x3");
+        SPEI_CHECK_LAUNCH(split ? "spei_conv_wgrad_bf16x3" : "spei_conv_wgrad_bf16");
         return 0;
     }
     WgradParams p;
@@ -644,7 +671,13 @@ extern "C" int spei_conv_wgrad_f32_batched(const float* x, int ldx, const float*
 extern "C" int spei_conv_wgrad_bf16x3_batched(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* ws, int Hin,
                                               int Win, int Hout, int Wout, int N, int K, int ksize, int stride, int pad, int batch,
                                               spei_stream_t stream) {
-    return conv_wgrad_run(x, ldx, dy, ldy, dw, dbias, ws, Hin, Win, Hout, Wout, N, K, ksize, stride, pad, batch, stream, true);
+    return conv_wgrad_run(x, ldx, dy, ldy, dw, dbias, ws, Hin, Win, Hout, Wout, N, K, ksize, stride, pad, batch, stream, 1);
+}
+
+extern "C" int spei_conv_wgrad_bf16_batched(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* ws, int Hin,
+                                            int Win, int Hout, int Wout, int N, int K, int ksize, int stride, int pad, int batch,
+                                            spei_stream_t stream) {
+    return conv_wgrad_run(x, ldx, dy, ldy, dw, dbias, ws, Hin, Win, Hout, Wout, N, K, ksize, stride, pad, batch, stream, 2);
 }
 
 extern "C" int spei_relu_bwd(const float* y, const float* dy, float* dz, int64_t n, spei_stream_t stream) {
@@ -761,12 +794,12 @@ __global__ __launch_bounds__(256) void pack_split16_kernel(const float* __restri
         lo[j] = (__bf16)(v - (float)h);
     }
     *reinterpret_cast<bf8*>(fhi + i * 8) = hi;
-    *reinterpret_cast<bf8*>(flo + i * 8) = lo;
+    if (flo) *reinterpret_cast<bf8*>(flo + i * 8) = lo;         // NULL: the single bf16 fragment (train_precision = "bf16")
 }
 }  // namespace
 
 extern "C" int spei_pack_split16(const float* w, int N, int K, int ksize, int mode, void* frag_hi, void* frag_lo, spei_stream_t stream) {
-    SPEI_REQUIRE(w && frag_hi && frag_lo, "spei_pack_split16: null pointer");
+    SPEI_REQUIRE(w && frag_hi, "spei_pack_split16: null pointer");
     SPEI_REQUIRE(N > 0 && K > 0 && N % 32 == 0 && K % 32 == 0 && ksize >= 1 && (mode == 0 || mode == 1), "spei_pack_split16: N=%d K=%d ksize=%d mode=%d", N, K, ksize, mode);
     SPEI_REQUIRE(((uintptr_t)frag_hi | (uintptr_t)frag_lo) % 16 == 0, "spei_pack_split16: 16-byte alignment required");
     const int T = ksize * ksize;

@@ -44,10 +44,11 @@ struct SlabParams {
     int iw_magic;            // ceil(2^20 / IW): pix / IW == (pix * iw_magic) >> 20 for pix < 2048
     int goff_bytes;          // bytes reserved for the group offset table (multiple of 16)
     int n_chunks;            // 32*WN*TN-column chunks looped inside the workgroup
-    // Tap list form (ntap > 0, used for the parity classes of a stride-2 transposed conv): the taps are the (dy, dx) >= 0
-    // offsets below instead of the ks x ks square, and output pixel (y, x) of the tile grid is written to pixel
-    // (y * o_mul + o_row_add, x * o_mul + o_col_add) of a map that is Wfull pixels wide.
-    int ntap, tap_dy[4], tap_dx[4];
+    // Tap list form (ntap > 0, used for the parity classes of a stride-2 transposed conv and of a stride-2 conv's adjoint): the taps
+    // are the (dy, dx) >= 0 offsets below (from the slab origin, which sits `pad` pixels before the tile) instead of the ks x ks
+    // square, and output pixel (y, x) of the tile grid is written to pixel (y * o_mul + o_row_add, x * o_mul + o_col_add) of a map
+    // that is Wfull pixels wide.
+    int ntap, tap_dy[9], tap_dx[9];
     int o_mul, o_row_add, o_col_add, Wfull;
     int64_t planes;          // > 0: write output channels 0..2 as three fp32 NCHW planes of this many pixels (last conv)
     int ln;                  // 1: LayerNorm(256) without affine is applied to every input row while it is staged
@@ -716,6 +717,52 @@ extern "C" int spei_convt2_slab16x3(const float* a0, int lda0, int k0, const voi
     const void* const wf[2][2] = {{whi4[0], whi4[1]}, {whi4[2], whi4[3]}};
     const void* const wl[2][2] = {{wlo4[0], wlo4[1]}, {wlo4[2], wlo4[3]}};
     return convt2_launch(SPEI_BF16, a0, lda0, k0, false, wf, wl, bias, out, ldo, false, Hin, Win, N, act, (hipStream_t)stream);
+}
+
+// Data gradient of a stride-2 Conv2d (k = 3 / 5, padding P = k / 2): dx[y] = sum over (o, t) with y = 2o - P + t of W[t]^T dY[o].  Output
+// row y = 2Y + p takes the taps t with (p + P - t) even, from dY row o = Y + (p + P - t) / 2: a stride-1 tap-list convolution over the dY
+// grid per parity class (up to 3 x 3 taps for k = 5), offsets shifted by P / 2 so they are >= 0 (the slab starts P / 2 pixels early,
+// zero outside the map).  Single bf16 products, fp32 maps in and out.
+extern "C" int spei_conv_s2_adjoint_slab16(const float* dy, int k0, const void* const* wfrag4, float* out, int N, int Hin, int Win, int ksize,
+                                           int batch, spei_stream_t stream) {
+    SPEI_REQUIRE(dy && wfrag4 && out, "spei_conv_s2_adjoint_slab16: null pointer");
+    for (int i = 0; i < 4; ++i)
+        SPEI_REQUIRE(wfrag4[i] && (uintptr_t)wfrag4[i] % 16 == 0, "spei_conv_s2_adjoint_slab16: class %d weights missing or unaligned", i);
+    SPEI_REQUIRE(ksize == 3 || ksize == 5, "spei_conv_s2_adjoint_slab16: ksize=%d (3 or 5)", ksize);
+    SPEI_REQUIRE(k0 > 0 && k0 % 32 == 0 && N > 0 && N % 32 == 0, "spei_conv_s2_adjoint_slab16: K=%d N=%d must be multiples of 32", k0, N);
+    SPEI_REQUIRE(batch >= 1 && batch <= 65535, "spei_conv_s2_adjoint_slab16: batch=%d", batch);
+    SPEI_REQUIRE(Hin > 0 && Win > 0 && (int64_t)Hin * Win * 4 * N < (1ll << 32) && (int64_t)Hin * Win < (1ll << 30),
+                 "spei_conv_s2_adjoint_slab16: bad map size");
+    SPEI_REQUIRE(((uintptr_t)dy | (uintptr_t)out) % 16 == 0, "spei_conv_s2_adjoint_slab16: operands must be 16-byte aligned");
+    const int P = ksize / 2, sh = P / 2;
+    for (int py = 0; py < 2; ++py)
+        for (int px = 0; px < 2; ++px) {
+            SlabParams p = {};
+            p.a0 = dy; p.a1 = nullptr; p.wh = wfrag4[py * 2 + px]; p.wl = nullptr; p.bias = nullptr; p.out = out;
+            p.res = nullptr; p.rowscale = nullptr;
+            p.lda0 = k0; p.lda1 = 0; p.k0 = k0; p.k1 = 0; p.ldo = N; p.ldr = 0;
+            p.N = N; p.K = k0;
+            p.Hin = Hin; p.Win = Win; p.Hout = Hin; p.Wout = Win;          // the tile grid is the dY grid
+            p.ks = 1; p.stride = 1; p.pad = sh; p.act = SPEI_ACT_NONE; p.ln = 0;
+            p.ntap = 0;
+            for (int ky = 0; ky < ksize; ++ky) {
+                if ((py + P - ky) & 1) continue;
+                for (int kx = 0; kx < ksize; ++kx) {
+                    if ((px + P - kx) & 1) continue;
+                    p.tap_dy[p.ntap] = (py + P - ky) / 2 + sh;             // (p + P - k) is even: exact halves, >= -sh
+                    p.tap_dx[p.ntap] = (px + P - kx) / 2 + sh;
+                    ++p.ntap;
+                }
+            }
+            p.o_mul = 2; p.o_row_add = py; p.o_col_add = px; p.Wfull = 2 * Win; p.planes = 0;
+            p.batch = batch;
+            p.a0_bs = (long long)Hin * Win * k0 * 4;
+            p.out_bs = (long long)4 * Hin * Win * N * 4;
+            p.res_bs = 0;
+            const int rc = dispatch_fmt(p, SPEI_BF16, false, false, false, (hipStream_t)stream);
+            if (rc) return rc;
+        }
+    return 0;
 }
 
 extern "C" int spei_convt2_slab16(int fmt, const void* a0, int lda0, int k0, int a_fmt, const void* wfrag00, const void* wfrag01,

@@ -19,9 +19,10 @@ Activations are NHWC pixel rows, the batch folded into the row index: [B * H * W
 loop over the samples (their kernels take one map); linears, LayerNorm, GELU take all rows at once.
 
 What runs where:
-  HIP    every pixel-sized operation: conv / transposed conv / linear forward and data gradient (spei_igemm_f32, spei_conv5_in),
-         weight + bias gradients (spei_conv_wgrad_f32), ReLU / GELU masks, LayerNorm forward and backward, window attention
-         forward and backward, the gates' plane statistics, the gated residual sum and its backward, DropPath row scaling,
+  HIP    every pixel-sized operation: conv / transposed conv / linear forward and data gradient (spei_igemm_f32, spei_conv5_in; in the
+         16-bit modes the slab kernels spei_conv_slab16[_batched], and for "bf16" also spei_convt2_slab16 and
+         spei_conv_s2_adjoint_slab16), weight + bias gradients (spei_conv_wgrad_f32 / _bf16x3 / _bf16), ReLU / GELU masks, LayerNorm
+         forward and backward, window attention forward and backward (fp32 MFMA; "bf16": spei_window_attention16_train / _bwd), the gates' plane statistics, the gated residual sum and its backward, DropPath row scaling,
          the Richardson-Lucy prior, SearchTransfer forward (exact f32 correlation arg-max, gathers) and backward, bicubic
          up-sampling and its adjoint, the `* weight_S` row scale and its gradient
   torch  parameter-sized or [H][C]-plane-sized work: the gate maps (SE MLP, two 2->1 convs, BatchNorm(1)) and their autograd,
@@ -49,19 +50,25 @@ def _ctx(device) -> Ctx:
     return Ctx("f32", "bf16x3", device=device)
 
 
-# Arithmetic of the step's forward and data-gradient GEMMs (`model.train_precision`): "f32" — v_mfma_f32_32x32x2_f32, the form
-# G20 - G22 pin to 1e-6; "bf16x3" — split products on the 16-bit matrix pipe (csrc/conv_slab16.hip, the inference kernels' SPLIT form:
-# 16-bit-significand operands, 2^-16 relative per product, fp32 accumulation): several times the rate, and still finer than the
-# arithmetic the reference trains in (main_SPEINet.py:12 `set_float32_matmul_precision('medium')`: TF32 / bf16 matmuls).  Weight
-# gradients, the stride-2 transposed forms, attention and everything pixel-sized stay fp32.  The choice is read when the graph is
-# built (a context variable around forward_swint / forward_speinet) and kept by every Function for its backward: the autograd
-# engine runs those on its own thread.
+# Arithmetic of the step's GEMMs (`model.train_precision`): "f32" — v_mfma_f32_32x32x2_f32, the form G20 - G22 pin to 1e-6;
+# "bf16x3" — split products on the 16-bit matrix pipe (csrc/conv_slab16.hip, the inference kernels' SPLIT form: 16-bit-significand
+# operands, 2^-16 relative per product, fp32 accumulation) for the forward, stride-1 data-gradient and weight-gradient GEMMs: several
+# times the rate, and still finer than the arithmetic the reference trains in (main_SPEINet.py:12
+# `set_float32_matmul_precision('medium')`: TF32 / bf16 matmuls); the stride-2 transposed forms and attention stay fp32;
+# "bf16" — that 'medium' arithmetic on the one reduced-precision matrix path gfx950 has: EVERY GEMM of the step, forward and backward
+# (convolutions at stride 1 / 2, the transposed convolutions, linears, window attention's four products and their gradients), rounds
+# each operand once to bf16 (round to nearest even), multiplies exactly and sums in fp32 — one v_mfma_f32_32x32x16_bf16 per product.
+# In every mode the bias gradients, LayerNorm, GELU, softmax, the gates and BatchNorm(1), the RL prior, bicubic, the SearchTransfer
+# arg-max (exact fp32: routing decisions do not move), the loss and Adam stay fp32, as do the weights (master copies), activations
+# and gradients in HBM; the 3-channel head conv (spei_conv5_in, not a GEMM of 32-channel tiles) stays fp32 forward.  The choice is
+# read when the graph is built (a context variable around forward_swint / forward_speinet) and kept by every Function for its
+# backward: the autograd engine runs those on its own thread.
 import contextvars
 
 _PREC = contextvars.ContextVar("speinet_train_precision", default="f32")
 
 
-def _split_frags(ctx: "Ctx", owner):
+def _split_frags(ctx: "Ctx", owner, single: bool = False):
     """(hi, lo) bf16 halves of a GEMM weight in MFMA fragment order, straight from the parameter in the reference's layout (ONE launch,
     spei_pack_split16).  `owner` = (parameter tensor, tag): tag "fwd" = the forward weight [tap][N][K], "dgrad" = the stride-1
     data-gradient weight (taps reversed, channel axes swapped).  The pair is kept ON the parameter object together with the `_version`
@@ -69,34 +76,71 @@ def _split_frags(ctx: "Ctx", owner):
     or be mistaken for another parameter (an address-keyed table can: a freed parameter's address is handed to the next model's).
     The stamp is (`_version`, storage address, device): `.to()` / `param.data = t` swap the storage without touching the counter.
     Edits THROUGH `.data` (`p.data.mul_()`) change neither: the model's `invalidate_packed()` — run at the top of every autograd
-    forward — drops the cache of every parameter (`drop_split_cache`), so a pair lives for one forward + backward at most."""
+    forward — drops the cache of every parameter (`drop_split_cache`), so a pair lives for one forward + backward at most.
+    single (train_precision "bf16"): (hi, None), hi = bf16(w) rounded to nearest even, cached under (tag, "bf16")."""
     weight, tag = owner
-    stamp = (weight._version, weight.data_ptr(), str(weight.device))
-    cache = getattr(weight, "_spei_split", None)
-    if cache is not None:
-        hit = cache.get(tag)
-        if hit is not None and hit[0] == stamp:
-            return hit[1]
+    key = (tag, "bf16") if single else tag
+    stamp, hit = _cache_get(weight, key)
+    if hit is not None:
+        return hit
     w = weight.detach()
     w = w if w.is_contiguous() else w.contiguous()
     assert w.dtype == torch.float32 and w.dim() in (2, 4) and (w.dim() == 2 or w.shape[2] == w.shape[3])
     n, k, ks = w.shape[0], w.shape[1], (w.shape[2] if w.dim() == 4 else 1)
     hi = torch.empty(w.numel(), device=w.device, dtype=torch.bfloat16)
-    lo = torch.empty_like(hi)
-    _lib.check(_lib.lib().spei_pack_split16(ctx._tp(w), n, k, ks, {"fwd": 0, "dgrad": 1}[tag], ctx._tp(hi), ctx._tp(lo), ctx._stream()),
-               "spei_pack_split16")
-    out = (hi, lo)
+    lo = None if single else torch.empty_like(hi)
+    _lib.check(_lib.lib().spei_pack_split16(ctx._tp(w), n, k, ks, {"fwd": 0, "dgrad": 1}[tag], ctx._tp(hi), _NULL if lo is None else ctx._tp(lo),
+                                            ctx._stream()), "spei_pack_split16")
+    return _cache_put(weight, key, stamp, (hi, lo))
+
+
+def _cache_put(weight: torch.Tensor, key, stamp, value):
     try:
+        cache = getattr(weight, "_spei_split", None)
         if cache is None:
             cache = weight._spei_split = {}
-        cache[tag] = (stamp, out)
+        cache[key] = (stamp, value)
     except AttributeError:
         pass
-    return out
+    return value
+
+
+def _cache_get(weight: torch.Tensor, key):
+    stamp = (weight._version, weight.data_ptr(), str(weight.device))
+    hit = (getattr(weight, "_spei_split", None) or {}).get(key)
+    return stamp, (hit[1] if hit is not None and hit[0] == stamp else None)
+
+
+def _class_frags_bf16(weight: torch.Tensor, kind: str):
+    """The four output-parity-class weights (bf16, fragment order, classes 00 01 10 11) of a stride-2 tap-list launch, and the device
+    array of their four pointers; cached on the parameter like `_split_frags`.  kind "convt": a ConvTranspose2d(3, stride 2) weight
+    [K][N][3][3] for spei_convt2_slab16 (pack.PackedW.convT_class_frags' tap order); "adj": a stride-2 Conv2d weight [N][K][k][k] for
+    the data gradient spei_conv_s2_adjoint_slab16 (taps (ky, kx) with (parity + k // 2 - k) even, ky-major), GEMM weight [tap][K][N]."""
+    from .pack import PackedW, _frag
+    stamp, hit = _cache_get(weight, (kind, "bf16"))
+    if hit is not None:
+        return hit
+    w = weight.detach()
+    if kind == "convt":
+        k, n = w.shape[0], w.shape[1]
+        cls = PackedW._class_frags(w.permute(2, 3, 1, 0).reshape(9, n, k).to(torch.bfloat16))
+        frags = [cls[c].reshape(-1) for c in ((0, 0), (0, 1), (1, 0), (1, 1))]
+    else:
+        ks = w.shape[2]
+        pad = ks // 2
+        wt = w.permute(2, 3, 1, 0).to(torch.bfloat16)                                            # [ky][kx][K][N]
+        frags = []
+        for py in (0, 1):
+            for px in (0, 1):
+                taps = [wt[ky, kx] for ky in range(ks) if (py + pad - ky) % 2 == 0 for kx in range(ks) if (px + pad - kx) % 2 == 0]
+                frags.append(_frag(torch.stack(taps).contiguous()).reshape(-1))
+    ptrs = (C.c_void_p * 4)(*[f.data_ptr() for f in frags])                                   # host array, read by the launcher
+    return _cache_put(weight, (kind, "bf16"), stamp, (frags, ptrs))
 
 
 def drop_split_cache(module) -> None:
-    """Forget the packed bf16 halves kept on the module's parameters (called by `invalidate_packed()`)."""
+    """Forget the packed bf16 weights (split halves, single fragments, class fragments) kept on the module's parameters (called by
+    `invalidate_packed()`)."""
     for p_ in module.parameters():
         if getattr(p_, "_spei_split", None):
             p_._spei_split = {}
@@ -130,19 +174,21 @@ def _igemm(ctx: Ctx, a: torch.Tensor, K: int, w_tnk: torch.Tensor, bias: Optiona
     assert a.shape == (batch * Hin * Win, K) and out.shape == (batch * Hout * Wout, N) and K % 32 == 0 and N % 32 == 0
     assert residual is None or (residual.is_contiguous() and residual.shape == out.shape)
     lib = _lib.lib()
-    if prec == "bf16x3" and mode == CONV and (rowscale is None or batch == 1):
+    if prec == "bf16" and not (mode == CONV and (rowscale is None or batch == 1)):
+        raise RuntimeError(f"train_precision 'bf16': no slab form for mode={mode}, rowscale with batch={batch}")
+    if prec in ("bf16x3", "bf16") and mode == CONV and (rowscale is None or batch == 1):
         from .pack import BF16, F32
-        fhi, flo = _split_frags(ctx, wkey)
+        fhi, flo = _split_frags(ctx, wkey, single=prec == "bf16")
         ldr = N if residual is not None else 0
         if batch == 1 or Wout == 1:
             rows = batch * Hin * Win
             dims = (rows, 1, batch * Hout * Wout, 1) if (ksize == 1 and stride == 1) else (Hin, Win, Hout, Wout)
             assert batch == 1 or (ksize == 1 and stride == 1)
-            _lib.check(lib.spei_conv_slab16(BF16, _p(ctx, a), K, K, _NULL, 0, 0, F32, ctx._tp(fhi), ctx._tp(flo), _p(ctx, bias), _p(ctx, out), N, F32,
+            _lib.check(lib.spei_conv_slab16(BF16, _p(ctx, a), K, K, _NULL, 0, 0, F32, ctx._tp(fhi), _NULL if flo is None else ctx._tp(flo), _p(ctx, bias), _p(ctx, out), N, F32,
                                             _p(ctx, residual), ldr, _p(ctx, rowscale), *dims, N, ksize, stride, ksize // 2, act, 0, ctx._stream()),
                        "spei_conv_slab16")
         else:
-            _lib.check(lib.spei_conv_slab16_batched(BF16, _p(ctx, a), K, F32, ctx._tp(fhi), ctx._tp(flo), _p(ctx, bias), _p(ctx, out), F32,
+            _lib.check(lib.spei_conv_slab16_batched(BF16, _p(ctx, a), K, F32, ctx._tp(fhi), _NULL if flo is None else ctx._tp(flo), _p(ctx, bias), _p(ctx, out), F32,
                                                     _p(ctx, residual), batch, Hin, Win, Hout, Wout, N, ksize, stride, ksize // 2, act,
                                                     ctx._stream()), "spei_conv_slab16_batched")
         return
@@ -168,7 +214,7 @@ def _wgrad(ctx: Ctx, x: torch.Tensor, K: int, dy: torch.Tensor, N: int, Hin: int
         ws = torch.empty(lib.spei_wgrad_ws_floats(Hout, Wout, nn_, K, ksize), device=dev)
         dyp = C.c_void_p(dy.data_ptr() + 4 * n0)
         assert dy.device == ctx.device and dy.is_contiguous() and dy.dtype == torch.float32
-        fn = lib.spei_conv_wgrad_bf16x3_batched if prec == "bf16x3" else lib.spei_conv_wgrad_f32_batched
+        fn = {"bf16x3": lib.spei_conv_wgrad_bf16x3_batched, "bf16": lib.spei_conv_wgrad_bf16_batched}.get(prec, lib.spei_conv_wgrad_f32_batched)
         _lib.check(fn(_p(ctx, x), K, dyp, N, _p(ctx, dwp), _p(ctx, dbp), _p(ctx, ws), Hin, Win, Hout, Wout, nn_,
                       K, ksize, stride, ksize // 2, batch, ctx._stream()), "spei_conv_wgrad_batched")
         if N > 256:
@@ -223,10 +269,15 @@ class _Conv2d(torch.autograd.Function):
             wt = lambda: _w_conv(weight).transpose(1, 2).contiguous()                      # [t][k][n]
             hf, wf = ho * stride, wo * stride
             dx = torch.empty(B * hf * wf, k, device=dy.device)
-            if fctx.prec == "bf16x3" and stride == 1:
+            if fctx.prec in ("bf16x3", "bf16") and stride == 1:
                 # stride 1: the transposed convolution IS the convolution with the taps reversed
                 _igemm(ctx, dz, n, lambda: wt().flip(0).contiguous(), None, dx, k, ho, wo, hf, wf, ksize, 1, CONV, ACT_NONE, batch=B,
-                       prec="bf16x3", wkey=_wkey(weight, "dgrad"))
+                       prec=fctx.prec, wkey=_wkey(weight, "dgrad"))
+            elif fctx.prec == "bf16":
+                # stride 2: the adjoint as four output-parity classes of stride-1 tap-list convolutions over the dZ grid
+                _, ptrs = _class_frags_bf16(weight, "adj")
+                _lib.check(_lib.lib().spei_conv_s2_adjoint_slab16(_p(ctx, dz), n, ptrs, _p(ctx, dx), k, ho, wo, ksize, B, ctx._stream()),
+                           "spei_conv_s2_adjoint_slab16")
             else:
                 _igemm(ctx, dz, n, wt, None, dx, k, ho, wo, hf, wf, ksize, stride, CONV_T, ACT_NONE, batch=B)
             if (hf, wf) != (H, W):        # odd input size under stride 2: the transposed conv made one row / column too many
@@ -244,12 +295,23 @@ class _ConvT2d(torch.autograd.Function):
         ctx = _ctx(x.device)
         k, n = weight.shape[0], weight.shape[1]
         x = x.contiguous()
-        w = weight.detach().permute(2, 3, 1, 0).reshape(9, n, k).contiguous()               # [tap][N][K]
         out = torch.empty(B * 4 * H * W, n, device=x.device)
         b = bias.detach().contiguous()
-        _igemm(ctx, x, k, w, b, out, n, H, W, 2 * H, 2 * W, 3, 2, CONV_T, ACT_RELU, batch=B)
+        prec = _PREC.get()
+        if prec == "bf16":
+            # the four output-parity classes on the slab kernel (1 / 2 / 2 / 4 taps), one launch per class and sample
+            (f00, f01, f10, f11), _ = _class_frags_bf16(weight, "convt")
+            from .pack import BF16, F32
+            for i in range(B):
+                _lib.check(_lib.lib().spei_convt2_slab16(BF16, _p(ctx, x[i * H * W:(i + 1) * H * W]), k, k, F32, ctx._tp(f00), ctx._tp(f01), ctx._tp(f10),
+                                                         ctx._tp(f11), _p(ctx, b), _p(ctx, out[i * 4 * H * W:(i + 1) * 4 * H * W]), n, F32, H, W, n,
+                                                         ACT_RELU, ctx._stream()), "spei_convt2_slab16")
+        else:
+            w = weight.detach().permute(2, 3, 1, 0).reshape(9, n, k).contiguous()           # [tap][N][K]
+            _igemm(ctx, x, k, w, b, out, n, H, W, 2 * H, 2 * W, 3, 2, CONV_T, ACT_RELU, batch=B)
         fctx.save_for_backward(x, weight, out)
         fctx.meta = (B, H, W)
+        fctx.prec = prec
         return out
 
     @staticmethod
@@ -259,10 +321,13 @@ class _ConvT2d(torch.autograd.Function):
         ctx = _ctx(dy.device)
         k, n = weight.shape[0], weight.shape[1]
         dz = _relu_mask(ctx, y, dy.contiguous())
-        wc = _w_conv(weight)                                                               # Conv2d view: [tap][out = K][in = N]
+        wc = lambda: _w_conv(weight)                                                       # Conv2d view: [tap][out = K][in = N]
         dx = torch.empty(B * H * W, k, device=dy.device)
-        _igemm(ctx, dz, n, wc, None, dx, k, 2 * H, 2 * W, H, W, 3, 2, CONV, ACT_NONE, batch=B)
-        dw, _ = _wgrad(ctx, dz, n, x, k, 2 * H, 2 * W, H, W, 3, 2, want_bias=False, batch=B)                            # [t][K][N]
+        # "bf16": the stride-2 Conv2d on the slab kernel, the same weight read as Conv2d [out = K][in = N] (pack "fwd"); the other modes
+        # keep their fp32 forms
+        prec = "bf16" if fctx.prec == "bf16" else "f32"
+        _igemm(ctx, dz, n, wc, None, dx, k, 2 * H, 2 * W, H, W, 3, 2, CONV, ACT_NONE, batch=B, prec=prec, wkey=_wkey(weight, "fwd"))
+        dw, _ = _wgrad(ctx, dz, n, x, k, 2 * H, 2 * W, H, W, 3, 2, want_bias=False, batch=B, prec=prec)                # [t][K][N]
         dweight = dw.view(3, 3, k, n).permute(2, 3, 0, 1).contiguous()
         return dx, dweight, dz.sum(dim=0), None, None, None
 
@@ -285,6 +350,7 @@ class _ConvIn(torch.autograd.Function):
                                          ctx._stream()), "spei_conv5_in")
         fctx.save_for_backward(frames.permute(0, 2, 3, 1).reshape(B * H * W, c).contiguous(), weight, out)
         fctx.meta = (B, H, W)
+        fctx.prec = _PREC.get()
         return out
 
     @staticmethod
@@ -294,7 +360,7 @@ class _ConvIn(torch.autograd.Function):
         ctx = _ctx(dy.device)
         n, k = weight.shape[0], weight.shape[1]
         dz = _relu_mask(ctx, y, dy.contiguous())
-        dw, db = _wgrad(ctx, x, k, dz, n, H, W, H, W, 5, 1, batch=B)
+        dw, db = _wgrad(ctx, x, k, dz, n, H, W, H, W, 5, 1, batch=B, prec="bf16" if fctx.prec == "bf16" else "f32")
         return None, dw.view(5, 5, n, k).permute(2, 3, 0, 1).contiguous(), db
 
 
@@ -395,11 +461,16 @@ class _WindowAttention(torch.autograd.Function):
         q, kv, rb = q.contiguous(), kv.contiguous(), relbias.detach().contiguous()
         out = torch.empty_like(q)
         lib = _lib.lib()
-        hw = H * W
-        _lib.check(lib.spei_window_attention_batched(_p(ctx, q), _p(ctx, kv), 0, _p(ctx, rb), _p(ctx, out), H, W, shift, B, ctx._stream()),
-                   "spei_window_attention_batched")
+        prec = _PREC.get()
+        if prec == "bf16":
+            _lib.check(lib.spei_window_attention16_train(_p(ctx, q), _p(ctx, kv), _p(ctx, rb), _p(ctx, out), H, W, shift, B, ctx._stream()),
+                       "spei_window_attention16_train")
+        else:
+            _lib.check(lib.spei_window_attention_batched(_p(ctx, q), _p(ctx, kv), 0, _p(ctx, rb), _p(ctx, out), H, W, shift, B, ctx._stream()),
+                       "spei_window_attention_batched")
         fctx.save_for_backward(q, kv, rb)
         fctx.meta = (B, H, W, shift)
+        fctx.prec = prec
         return out
 
     @staticmethod
@@ -412,9 +483,9 @@ class _WindowAttention(torch.autograd.Function):
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
         nwin = (H // 5) * (W // 5)
         part = torch.empty(B, nwin, 8, 25, 25, device=dout.device)
-        hw = H * W
-        _lib.check(lib.spei_window_attention_bwd(_p(ctx, q), _p(ctx, kv), _p(ctx, rb), _p(ctx, dout), _p(ctx, dq), _p(ctx, dkv), _p(ctx, part),
-                                                 H, W, shift, B, ctx._stream()), "spei_window_attention_bwd")
+        fn = lib.spei_window_attention16_bwd if fctx.prec == "bf16" else lib.spei_window_attention_bwd
+        _lib.check(fn(_p(ctx, q), _p(ctx, kv), _p(ctx, rb), _p(ctx, dout), _p(ctx, dq), _p(ctx, dkv), _p(ctx, part), H, W, shift, B, ctx._stream()),
+                   "spei_window_attention_bwd")
         return dq, dkv, part.sum(dim=(0, 1)), None, None, None, None
 
 
@@ -801,8 +872,8 @@ def forward_swint(model, x: torch.Tensor, scales: Optional[list] = None, bn_trai
 
 def _train_precision(model) -> str:
     p = getattr(model, "train_precision", "f32")
-    if p not in ("f32", "bf16x3"):
-        raise ValueError(f"train_precision {p!r}: 'f32' or 'bf16x3'")
+    if p not in ("f32", "bf16x3", "bf16"):
+        raise ValueError(f"train_precision {p!r}: 'f32', 'bf16x3' or 'bf16'")
     return p
 
 
