@@ -129,6 +129,16 @@ int spei_conv_slab16_fa(int fmt, const float* x, int K, const void* x1, const fl
 int spei_conv32_ws16(int fmt, const void* a, int a_fmt, const void* wfrag, const float* bias, void* out, int out_fmt, int batch,
                      int H, int W, int act, spei_stream_t stream);
 
+/* 64 -> 64 channel 5x5 convolution (stride 1, zero padding 2), weight-stationary (csrc/conv64_ws16.hip): the two convs of a ResBlock at
+ * half resolution (model/block.py:26-47,127-131) — the four waves of a workgroup hold the layer's 200 weight fragments between them
+ * (wave w: output channels [32 (w >> 1), +32), input-channel half w & 1) in registers for the whole launch, one persistent workgroup per CU
+ * walks over 6 x 32 pixel tiles of all `batch` maps, double-buffers the tiles' slabs in LDS and adds the two input-channel halves through
+ * LDS.  a: [batch][H*W][64] fp32 or `fmt`; wfrag: the layer's weights in fragment order (as spei_conv_slab16 takes them); bias [64] or
+ * NULL; out: [batch][H*W][64] `fmt` or fp32, must not be `a`; act: SPEI_ACT_NONE / SPEI_ACT_RELU.  Same operand rounding as
+ * spei_conv_slab16, fp32 sums in (tap, channel) order per input-channel half, then half 0 + half 1 + bias. */
+int spei_conv64_ws16(int fmt, const void* a, int a_fmt, const void* wfrag, const float* bias, void* out, int out_fmt, int batch,
+                     int H, int W, int act, spei_stream_t stream);
+
 /* Fused Swin MLP branch (model/swinir.py:12-29 Mlp.forward + the `x + mlp(norm2(x))` tail of :279), 16-bit matrix pipe:
  * out = x + fc2(GELU(fc1(LayerNorm256(x)))), LayerNorm affine folded into w1/b1 (pack.py); w*_frag in MFMA fragment
  * order; the normalised tokens and the 512-wide hidden activations live only in LDS.  x, out: [M][256] fp32, may alias. */

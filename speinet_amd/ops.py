@@ -261,6 +261,9 @@ class Ctx:
       conv32_ws       16-bit: the 32 -> 32 channel 5x5 convolutions (the ResBlock convs at full resolution: inBlock, outBlock) on the
                       weight-stationary persistent kernel (spei_conv32_ws16: the layer's 51 KB of weights live in each wave's registers, nothing
                       streams from L2 in the main loop).  Off: the slab kernel, which runs these layers at its weight intake
+      conv64_ws       16-bit: the 64 -> 64 channel 5x5 convolutions (the ResBlock convs at half resolution) on the weight-stationary
+                      persistent kernel (spei_conv64_ws16: the four waves of a workgroup hold the layer's 205 KB of weights between them).
+                      None (default): follow conv32_ws, so conv32_ws=False still puts every 5x5 layer on the slab kernel
       corr_bf16       "f16" with corr "top2": the candidate pass of the correlation runs on bf16 operands (True, default) instead of
                       f16.  The fp32 re-score decides the winner and S either way (G14: 16 more of 57600 positions differ, dPSNR
                       +1e-6 dB); bf16 operands let the chip hold a ~7 % higher MFMA clock on the slab kernel (tools/bench_corr.py); on the diagonal
@@ -277,7 +280,7 @@ class Ctx:
     ACT_NONE, ACT_RELU, ACT_GELU = ACT_NONE, ACT_RELU, ACT_GELU
     CONV, CONV_T = CONV, CONV_T
     _FIELDS = ("precision", "corr_precision", "device", "use_slab", "bf16_storage", "x1_bf16", "fuse_mlp", "fuse_attn",
-               "commute_upconv", "commute_any", "corr_bf16", "corr_diag", "fuse_apply", "split_decode", "batch_enc", "attn_win4", "conv32_ws", "conv3_pipe", "stage", "profile", "capture")
+               "commute_upconv", "commute_any", "corr_bf16", "corr_diag", "fuse_apply", "split_decode", "batch_enc", "attn_win4", "conv32_ws", "conv64_ws", "conv3_pipe", "stage", "profile", "capture")
     # stages of an f16 frame that run in split (bf16x3) arithmetic by default, see `split_decode`
     SPLIT_STAGES = ("glue", "dec2")
     __slots__ = _FIELDS
@@ -286,7 +289,8 @@ class Ctx:
                  bf16_storage: bool = True, x1_bf16: bool = True, fuse_mlp: bool = True, fuse_attn: bool = True,
                  commute_upconv: bool = True, commute_any: bool = False, corr_bf16: bool = True,
                  corr_diag: bool = True, fuse_apply: bool = False, split_decode: bool = True, batch_enc: bool = True,
-                 attn_win4: bool = True, conv32_ws: bool = True, conv3_pipe: bool = True, stage: Optional[dict] = None,
+                 attn_win4: bool = True, conv32_ws: bool = True, conv64_ws: Optional[bool] = None, conv3_pipe: bool = True,
+                 stage: Optional[dict] = None,
                  profile: Optional[dict] = None, capture: Optional[dict] = None):
         if precision not in PRECISIONS:
             raise ValueError(f"unknown precision {precision!r}")
@@ -308,6 +312,7 @@ class Ctx:
                      ("fuse_attn", fuse_attn), ("commute_upconv", commute_upconv), ("commute_any", commute_any),
                      ("corr_bf16", corr_bf16), ("corr_diag", corr_diag), ("fuse_apply", fuse_apply), ("split_decode", split_decode), ("batch_enc", batch_enc), ("attn_win4", attn_win4), ("conv32_ws", conv32_ws), ("conv3_pipe", conv3_pipe)):
             object.__setattr__(self, k, bool(v))
+        object.__setattr__(self, "conv64_ws", None if conv64_ws is None else bool(conv64_ws))
         object.__setattr__(self, "stage", dict(stage) if stage else {})
         object.__setattr__(self, "profile", profile)
         object.__setattr__(self, "capture", capture)
@@ -457,6 +462,12 @@ class Ctx:
             # the 32-channel 5x5 layers: weight-stationary persistent kernel (csrc/conv32_ws16.hip)
             _lib.check(lib.spei_conv32_ws16(self.fmt, fp(a0), a0.fmt, tp(w.frag(self.fmt)), tp(bias), fp(out), out.fmt, 1, a0.H, a0.W, act,
                                             self._stream()), "spei_conv32_ws16")
+        elif (self.conv64_ws_available() and mode == CONV and ksize == 5 and stride == 1 and k0 == 64 and N == 64 and a1 is None
+                and residual is None and rowscale is None and not ln_input and act in (ACT_NONE, ACT_RELU) and w.fhi is not None
+                and (a0.ld, a0.off, out.ld, out.off) == (64, 0, 64, 0) and a0.t.data_ptr() != out.t.data_ptr()):
+            # the 64-channel 5x5 layers: weight-stationary persistent kernel (csrc/conv64_ws16.hip)
+            _lib.check(lib.spei_conv64_ws16(self.fmt, fp(a0), a0.fmt, tp(w.frag(self.fmt)), tp(bias), fp(out), out.fmt, 1, a0.H, a0.W, act,
+                                            self._stream()), "spei_conv64_ws16")
         elif (mode == CONV_T and self.lp16 and self.use_slab and ksize == 3 and stride == 2 and a1 is None and residual is None
                 and rowscale is None and N % 32 == 0 and k0 % 32 == 0):
             # stride-2 transposed conv = four stride-1 convs (one per output parity) on the slab kernel
@@ -567,6 +578,10 @@ class Ctx:
         """The weight-stationary kernel for 32 -> 32 channel 5x5 layers (single-product 16-bit modes)."""
         return self.lp16 and self.use_slab and self.conv32_ws
 
+    def conv64_ws_available(self) -> bool:
+        """The weight-stationary kernel for 64 -> 64 channel 5x5 layers (single-product 16-bit modes; `conv64_ws` None follows `conv32_ws`)."""
+        return self.lp16 and self.use_slab and (self.conv32_ws if self.conv64_ws is None else self.conv64_ws)
+
     def batched_kernels(self) -> bool:
         """`igemm_batched` can run (what the batched Swin calls need; `batch_enc` only decides about the encoder passes)."""
         return self.lp16 and self.use_slab
@@ -596,6 +611,11 @@ class Ctx:
                 and act in (ACT_NONE, ACT_RELU)):
             _lib.check(_lib.lib().spei_conv32_ws16(self.fmt, tp(a.t), a.fmt, tp(w.frag(self.fmt)), tp(bias), tp(out.t), out.fmt, a.B, a.H, a.W,
                                                    act, self._stream()), "spei_conv32_ws16")
+            return out
+        if (self.conv64_ws_available() and ksize == 5 and stride == 1 and a.C == 64 and N == 64 and residual is None
+                and act in (ACT_NONE, ACT_RELU)):
+            _lib.check(_lib.lib().spei_conv64_ws16(self.fmt, tp(a.t), a.fmt, tp(w.frag(self.fmt)), tp(bias), tp(out.t), out.fmt, a.B, a.H, a.W,
+                                                   act, self._stream()), "spei_conv64_ws16")
             return out
         _lib.check(_lib.lib().spei_conv_slab16_batched(self.fmt, tp(a.t), a.C, a.fmt, tp(w.frag(self.fmt)), _vp(0), tp(bias), tp(out.t), out.fmt,
                                                        tp(residual.t) if residual is not None else _vp(0), a.B, a.H, a.W, ho, wo, N, ksize,
