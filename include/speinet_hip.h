@@ -463,6 +463,19 @@ int spei_det_gray(const float* rgb, float* gray, int N, int H, int W, spei_strea
 int64_t spei_det_ws_floats(int N, int H, int W, int k);
 int spei_det_features(const float* gray, float* out, float* ws, int N, int H, int W, int k, spei_stream_t stream);
 
+/* ---- frame I/O of the clip API (speinet_amd/video.py; reference inference_SPEINet.py:466-482 numpy2tensor / tensor2numpy) ---- */
+
+/* N uint8 [H][W][3] frames, frame_stride bytes apart (rows packed) -> dst fp32 [N][3][Hp][Wp], Hp / Wp = H / W rounded up to
+ * multiples of 20, values u * (float)(1/255); the bottom / right pad reflects (torch F.pad mode "reflect": row H + j reads row
+ * H - 2 - j), which needs Hp - H < H and Wp - W < W.  dst 16-byte aligned, or NULL.  gray (or NULL): [N][H][W], the detector's
+ * gray plane of the unpadded frames, bit-identical to spei_det_gray on the frames as fp32 0..255.  dst and gray may not both be NULL. */
+int spei_frames_u8_in(const unsigned char* src, int64_t frame_stride, float* dst, float* gray, int N, int H, int W, spei_stream_t stream);
+
+/* fp32 [3][Hp][Wp] -> dst uint8 [H][W][3], the top-left crop (H <= Hp, W <= Wp) as round_half_even(clamp(x * 255, 0, 255)),
+ * 0 for a non-finite value: the `out_hwc` of spei_frame_post.  nonfinite (or NULL): one int, cleared on the stream, then nonzero
+ * iff the crop held a NaN or an infinity. */
+int spei_frame_u8_out(const float* src, unsigned char* dst, int* nonfinite, int H, int W, int Hp, int Wp, spei_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,8 @@ SIGNATURES = {
     "spei_det_gray": (I, [P, P, I, I, I, P]),
     "spei_det_ws_floats": (L, [I, I, I, I]),
     "spei_det_features": (I, [P, P, P, I, I, I, I, P]),
+    "spei_frames_u8_in": (I, [P, L, P, P, I, I, I, P]),
+    "spei_frame_u8_out": (I, [P, P, P, I, I, I, I, P]),
 }
 
 

@@ -194,3 +194,11 @@ __device__ __forceinline__ void quad_transpose4(float& a0, float& a1, float& a2,
     s = b1 ? a1 : a3; r = dpp_quad<0x4E>(s);
     if (b1) a1 = r; else a3 = r;
 }
+
+// ITU-R 601 gray value in 0..1 of one pixel given as fp32 0..255 (torchvision Grayscale, then / 255: inference_SPEINet.py:182).  The LD
+// detector's gray plane (spei_det_gray) and the clip ingest's (spei_frames_u8_in) both use this one expression, with its roundings
+// spelled out: left to -ffp-contract=fast, the compiler contracted `0.2989f * r + 0.587f * g + 0.114f * b` two different ways in the two
+// versions of det_gray_kernel's grid-stride loop, so a pixel's last bit depended on its place in the launch.
+__device__ __forceinline__ float spei_gray_px(float r, float g, float b) {
+    return __fmaf_rn(0.114f, b, __fmaf_rn(0.2989f, r, 0.587f * g)) / 255.0f;
+}

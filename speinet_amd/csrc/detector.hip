@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void det_gray_kernel(const float* __restrict__
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t n = i / hw, p = i - n * hw;
         const float* f = rgb + n * 3 * hw + p;
-        gray[i] = (0.2989f * f[0] + 0.587f * f[hw] + 0.114f * f[2 * hw]) / 255.0f;
+        gray[i] = spei_gray_px(f[0], f[hw], f[2 * hw]);
     }
 }
 

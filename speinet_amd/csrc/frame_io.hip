@@ -1,0 +1,169 @@
+// Frame I/O of the clip API (speinet_amd/video.py): uint8 frames of any size in, uint8 frames of the same size out.
+//
+//   spei_frames_u8_in  — N uint8 [H][W][3] frames -> fp32 [N][3][Hp][Wp], Hp / Wp the next multiples of 20, values u * (float)(1/255)
+//                        (reference inference_SPEINet.py:466-475 numpy2tensor: float64 -> float32, then mul_(1/255) in float32);
+//                        the bottom / right pad reflects (torch F.pad mode "reflect", as SwinIR's check_image_size pads to window
+//                        multiples): padded row H + j reads row H - 2 - j, column W + j reads column W - 2 - j.  Optionally the
+//                        LD detector's gray plane [N][H][W] of the unpadded frame, bit-identical to spei_det_gray on the same frame
+//                        as fp32 0..255 (one shared expression, spei_gray_px).
+//   spei_frame_u8_out  — fp32 [3][Hp][Wp] -> the top-left H x W crop as uint8 [H][W][3], round_half_even(clamp(x * 255, 0, 255))
+//                        (reference :477-482 tensor2numpy); exactly the `out_hwc` of spei_frame_post (metrics.hip), a non-finite
+//                        value included (0).  Optionally a flag, nonzero iff the crop held a non-finite value: spei_frame_post's
+//                        `finite` result, which the clip API uses to recompute the window in bf16x3 as the harness does.
+//
+// Streaming kernels, one thread per group of 4 pixels of a row: 12 bytes of uint8 read (three dwords when the rows are 4-byte
+// aligned), one 16-byte store per plane.  The mirrored indices are computed in the pad band only.  HBM-bound: a 720p frame is
+// 2.8 MB in and 11 MB out.
+#include "common.h"
+
+namespace {
+
+constexpr int MULT = 20;                                   // two stride-2 stages, then 5x5 windows
+constexpr float INV255 = (float)(1.0 / 255.0);             // numpy2tensor's rgb_range / 255 (a Python float) as the float32 scalar
+constexpr int BLOCKS_MAX = 8192;
+
+__device__ __forceinline__ int byte_of(const uint32_t (&w)[3], int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xff; }
+
+__global__ __launch_bounds__(256) void frames_u8_in_kernel(const unsigned char* __restrict__ src, int64_t fstride, float* __restrict__ dst,
+                                                           float* __restrict__ gray, int H, int W, int Hp, int Wp, int64_t total,
+                                                           int aligned) {
+    const int gw = Wp >> 2;                                // groups per padded row (Wp % 20 == 0)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / gw;                        // n * Hp + y
+        const int x0 = (int)(i - row * gw) * 4;
+        const int n = (int)(row / Hp), y = (int)(row - (int64_t)n * Hp);
+        if (!dst && y >= H) continue;                      // gray only: the pad rows have nothing to write
+        const int sy = y < H ? y : 2 * H - 2 - y;
+        const unsigned char* s = src + n * fstride + (int64_t)sy * W * 3;
+        float v[3][4];
+        if (x0 + 4 <= W) {                                 // interior: 12 consecutive bytes
+            uint32_t w[3];
+            if (aligned) {
+                const uint32_t* p = reinterpret_cast<const uint32_t*>(s + x0 * 3);
+                w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
+            } else {
+                const unsigned char* p = s + x0 * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    w[k] = (uint32_t)p[4 * k] | ((uint32_t)p[4 * k + 1] << 8) | ((uint32_t)p[4 * k + 2] << 16) | ((uint32_t)p[4 * k + 3] << 24);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][k] = (float)byte_of(w, 3 * k + c);
+        } else {                                           // right edge and pad band: column W + j reads column W - 2 - j
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int x = x0 + k, sx = x < W ? x : 2 * W - 2 - x;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][k] = (float)s[sx * 3 + c];
+            }
+        }
+        if (gray && y < H) {
+            float* g = gray + ((int64_t)n * H + y) * W;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < W) g[x0 + k] = spei_gray_px(v[0][k], v[1][k], v[2][k]);
+        }
+        if (dst) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float4* d = reinterpret_cast<float4*>(dst + (((int64_t)n * 3 + c) * Hp + y) * Wp + x0);
+                *d = make_float4(v[c][0] * INV255, v[c][1] * INV255, v[c][2] * INV255, v[c][3] * INV255);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t to_u8(float v) {
+    const float q = rintf(fminf(fmaxf(v * 255.0f, 0.0f), 255.0f));     // mul(255).clamp(0, 255).round(): half to even, as torch
+    return isfinite(v) ? (uint32_t)q : 0u;                              // as spei_frame_post
+}
+
+__global__ __launch_bounds__(256) void frame_u8_out_kernel(const float* __restrict__ src, unsigned char* __restrict__ dst,
+                                                           int* __restrict__ nonfinite, int H, int W, int Wp, int64_t plane, int gw,
+                                                           int64_t total, int vec_in, int vec_out) {
+    int bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int y = (int)(i / gw), x0 = (int)(i - (int64_t)y * gw) * 4;
+        const float* s = src + (int64_t)y * Wp + x0;
+        uint32_t q[3][4];
+        if (vec_in) {                                      // Wp % 4 == 0: x0 + 4 <= Wp
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float4 f = *reinterpret_cast<const float4*>(s + c * plane);
+                const float e[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    q[c][k] = to_u8(e[k]);
+                    bad |= (x0 + k < W && !isfinite(e[k])) ? 1 : 0;     // columns W.. of the group are pad, not part of the crop
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float v = x0 + k < W ? s[c * plane + k] : 0.0f;
+                    q[c][k] = to_u8(v);
+                    bad |= isfinite(v) ? 0 : 1;
+                }
+        }
+        unsigned char* d = dst + ((int64_t)y * W + x0) * 3;
+        if (vec_out && x0 + 4 <= W) {                      // 12 bytes as three dwords
+            uint32_t w[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 12; ++j) w[j >> 2] |= q[j % 3][j / 3] << (8 * (j & 3));
+            uint32_t* p = reinterpret_cast<uint32_t*>(d);
+            p[0] = w[0]; p[1] = w[1]; p[2] = w[2];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < W)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) d[k * 3 + c] = (unsigned char)q[c][k];
+        }
+    }
+    if (nonfinite && bad) atomicOr(nonfinite, 1);           // rare: one atomic per thread that met a non-finite value
+}
+
+inline int grid_for(int64_t total) { return (int)((total + 255) / 256 < BLOCKS_MAX ? (total + 255) / 256 : BLOCKS_MAX); }
+
+}  // namespace
+
+extern "C" int spei_frames_u8_in(const unsigned char* src, int64_t frame_stride, float* dst, float* gray, int N, int H, int W,
+                                 spei_stream_t stream) {
+    SPEI_REQUIRE(src && (dst || gray), "spei_frames_u8_in: null pointer (src, and dst or gray, are required)");
+    SPEI_REQUIRE(N > 0 && H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), "spei_frames_u8_in: bad frame shape %d x %dx%d", N, H, W);
+    SPEI_REQUIRE(N == 1 || frame_stride >= (int64_t)H * W * 3, "spei_frames_u8_in: frame stride %lld < one %dx%d frame",
+                 (long long)frame_stride, H, W);
+    const int Hp = (H + MULT - 1) / MULT * MULT, Wp = (W + MULT - 1) / MULT * MULT;
+    SPEI_REQUIRE(Hp - H < H && Wp - W < W, "spei_frames_u8_in: a %dx%d frame cannot reflect-pad to %dx%d (the pad must be smaller "
+                 "than the frame)", H, W, Hp, Wp);
+    SPEI_REQUIRE(!dst || ((uintptr_t)dst & 15) == 0, "spei_frames_u8_in: dst must be 16-byte aligned");
+    const int aligned = ((uintptr_t)src & 3) == 0 && (N == 1 || (frame_stride & 3) == 0) && (W & 3) == 0;
+    const int64_t total = (int64_t)N * Hp * (Wp / 4);
+    hipLaunchKernelGGL(frames_u8_in_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, frame_stride, dst, gray, H, W,
+                       Hp, Wp, total, aligned);
+    SPEI_CHECK_LAUNCH("spei_frames_u8_in");
+    return 0;
+}
+
+extern "C" int spei_frame_u8_out(const float* src, unsigned char* dst, int* nonfinite, int H, int W, int Hp, int Wp,
+                                 spei_stream_t stream) {
+    SPEI_REQUIRE(src && dst, "spei_frame_u8_out: null pointer");
+    SPEI_REQUIRE(H > 0 && W > 0 && Hp >= H && Wp >= W && (int64_t)Hp * Wp < (1ll << 30),
+                 "spei_frame_u8_out: bad sizes (crop %dx%d of a %dx%d frame)", H, W, Hp, Wp);
+    const int gw = (W + 3) / 4;
+    const int vec_in = (Wp & 3) == 0 && ((uintptr_t)src & 15) == 0;
+    const int vec_out = (W & 3) == 0 && ((uintptr_t)dst & 3) == 0;
+    const int64_t total = (int64_t)H * gw;
+    if (nonfinite && hipMemsetAsync(nonfinite, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) {
+        spei_set_error("spei_frame_u8_out: clearing the non-finite flag failed");
+        return -2;
+    }
+    hipLaunchKernelGGL(frame_u8_out_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, dst, nonfinite, H, W, Wp,
+                       (int64_t)Hp * Wp, gw, total, vec_in, vec_out);
+    SPEI_CHECK_LAUNCH("spei_frame_u8_out");
+    return 0;
+}

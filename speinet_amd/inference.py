@@ -115,11 +115,13 @@ class FrameCache:
     however many windows share it (a frame is a neighbour twice, a middle frame once and often a reference).  Uploads go
     through a small ring of page-locked staging buffers allocated once: a copy from pageable memory makes the host wait for
     everything queued on the stream before it (one full GPU drain per window), and allocating page-locked memory per frame
-    synchronises the device.  Bounded LRUs (a 720p RGB frame is 2.8 MB)."""
+    synchronises the device.  Bounded LRUs (a 720p RGB frame is 2.8 MB).  `load(key)` decodes one frame (default: `key` is a
+    file path)."""
     RING = 8
 
-    def __init__(self, pool: ThreadPoolExecutor, capacity: int = 96, device=None):
+    def __init__(self, pool: ThreadPoolExecutor, capacity: int = 96, device=None, load=None):
         self.pool, self.capacity, self.device = pool, capacity, device
+        self.load = load or _imread
         self.items: "collections.OrderedDict[str, Future]" = collections.OrderedDict()
         self.dev: "collections.OrderedDict[str, torch.Tensor]" = collections.OrderedDict()
         self._ring, self._events, self._n = [], [], 0
@@ -129,7 +131,7 @@ class FrameCache:
             if p in self.items:
                 self.items.move_to_end(p)
             elif p not in self.dev:
-                self.items[p] = self.pool.submit(_imread, p)
+                self.items[p] = self.pool.submit(self.load, p)
         while len(self.items) > self.capacity:
             self.items.popitem(last=False)
 

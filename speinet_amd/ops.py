@@ -196,7 +196,57 @@ def frame_post(out_chw: torch.Tensor, gt_hwc: torch.Tensor, border: int = 4):
     return u8, res
 
 
-CORR_DIAG_WS_MAX = 8 << 30      # bytes of candidate pairs the diagonal correlation kernel may use before the slab kernel takes over
+def padded_size(n: int) -> int:
+    """The model's frame size for a frame dimension of n: the next multiple of 20 (two stride-2 stages, then 5x5 windows)."""
+    return -(-n // 20) * 20
+
+
+def frames_u8_in(u8: torch.Tensor, out: Optional[torch.Tensor] = None, gray: bool = False, planes: bool = True):
+    """uint8 frames [N,H,W,3] (or one [H,W,3]; each frame packed, any frame stride) on the device -> (fp32 [N,3,Hp,Wp] reflect-padded
+    to multiples of 20 with `numpy2tensor`'s values, or None when not `planes`; the detector's gray plane [N,H,W], or None when not
+    `gray`).  `out` (optional): the planes' destination, contiguous, N*3*Hp*Wp floats.  One launch on the current stream (csrc/frame_io.hip)."""
+    assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() in (3, 4) and (planes or gray)
+    fr = u8 if u8.dim() == 4 else u8.unsqueeze(0)
+    n, h, w, c = fr.shape
+    assert c == 3 and fr.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
+    hp, wp = padded_size(h), padded_size(w)
+    dev = u8.device
+    if planes:
+        if out is None:
+            out = torch.empty(n, 3, hp, wp, device=dev)
+        assert out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * 3 * hp * wp
+    else:
+        out = None
+    g = torch.empty(n, h, w, device=dev) if gray else None
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_frames_u8_in(_vp(fr.data_ptr()), fr.stride(0), _vp(out.data_ptr() if out is not None else 0),
+                                         _vp(g.data_ptr() if g is not None else 0), n, h, w, st), "spei_frames_u8_in")
+    return out, g
+
+
+def frame_u8_out(x: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None,
+                 nonfinite: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [3,Hp,Wp] on the device -> its top-left h x w crop as uint8 [h,w,3] (`tensor2numpy`'s values, the frame of `frame_post`).
+    `out` (optional): a packed uint8 [h,w,3] destination.  `nonfinite` (optional): an int32 device tensor whose first element becomes
+    nonzero iff the crop held a NaN or an infinity (`frame_post`'s finite flag, inverted).  Launches on the current stream
+    (csrc/frame_io.hip), no host sync."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 3 and x.is_contiguous()
+    hp, wp = x.shape[1:]
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=torch.uint8, device=x.device)
+    assert out.device == x.device and out.dtype == torch.uint8 and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
+    assert nonfinite is None or (nonfinite.device == x.device and nonfinite.dtype == torch.int32 and nonfinite.numel() >= 1)
+    lib = _lib.lib()
+    with torch.cuda.device(x.device):
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(lib.spei_frame_u8_out(_vp(x.data_ptr()), _vp(out.data_ptr()), _vp(nonfinite.data_ptr() if nonfinite is not None else 0),
+                                         h, w, hp, wp, st), "spei_frame_u8_out")
+    return out
+
+
+CORR_DIAG_WS_MAX = 8 << 30     # bytes of candidate pairs the diagonal correlation kernel may use before the slab kernel takes over
 
 
 class CorrPlan:

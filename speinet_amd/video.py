@@ -1,0 +1,446 @@
+"""Deblur a clip of the user's own footage: uint8 frames of any size (at least 20x20), with or without sharpness labels, no ground
+truth.  The library API is `deblur_clip`; the command line is
+
+    python -m speinet_amd.video --input <dir | glob> --output <dir> --model_path <checkpoint | synthetic> [--labels <file.npy>]
+
+It runs the harness's clip machinery (speinet_amd.inference) without the harness's dataset layout, metrics and crop:
+  * labels — given (0/1 per frame, 1 = sharp), or computed by the LD detector (speinet_amd.detector) in a first streaming pass over the
+    clip in batches of 16 frames: gray planes from the ingest kernel, focus measures, logistic regression;
+  * the window plan — `selection.assemble_windows` on the frame indices (a frame's number is its index in the clip): reflect-padded
+    clip, `blurry_indices`, references more than 7 frames away zeroed, routing by the zeroed reference;
+  * the windows — `forward_window` with a per-clip `EncoderCache`, `prefetch_window` one window ahead, windows alternating over two
+    launch streams, in whatever `precision` / `corr_precision` / `use_graph` / `streams` the caller set on the model;
+  * frames cross PCIe as uint8 from page-locked staging buffers (`inference.FrameCache`) and are decoded, for image paths, on worker
+    threads a few windows ahead.
+A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
+SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
+the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
+such sizes at all; at multiples of 20 the frames are bit-identical to the harness's.  Device memory is bounded by one window, the
+encoder cache and the windows in flight: it does not grow with the clip's length.
+"""
+from __future__ import annotations
+
+import argparse
+import collections
+import glob
+import os
+import time
+import warnings
+from concurrent.futures import ThreadPoolExecutor
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import detector, ops, selection
+from .inference import FrameCache, _imread, _imwrite
+from .speinet import EncoderCache
+
+ZERO = ("zero",)                 # window key of a zeroed reference frame
+MIN_SIZE = 20
+IMAGE_EXTS = (".png", ".jpg", ".jpeg", ".bmp")
+CORR_PRECISION = {"f32": "bf16x3", "bf16x3": "bf16x3", "bf16": "top2", "f16": "top2"}    # the harness's pairing (inference.Inference)
+DETECT_BATCH = 16                # frames per launch of the labelling pass (the harness's batch)
+PREFETCH = 4                     # windows decoded ahead of the GPU
+LANES = 2                        # launch streams the windows alternate over (inference.py --lanes)
+LAG = 2                          # windows enqueued after a frame before it is handed out
+FLAG_RING = 8                    # non-finite flags in flight (> LAG + 1)
+
+padded_size = ops.padded_size
+
+
+def reflect_index(n: int, n_pad: Optional[int] = None) -> np.ndarray:
+    """Source row (or column) of each of the n_pad padded rows of a dimension of n: i < n reads i, n + j reads n - 2 - j (torch F.pad
+    mode "reflect"; what spei_frames_u8_in computes in its pad band)."""
+    n_pad = padded_size(n) if n_pad is None else n_pad
+    if not n_pad - n < n:
+        raise ValueError(f"reflect padding of {n} to {n_pad} needs a pad smaller than {n}")
+    i = np.arange(n_pad)
+    return np.where(i < n, i, 2 * n - 2 - i)
+
+
+class _Frames:
+    """The clip behind one interface: frame i as a host uint8 [H,W,3] array (`host`) or a device tensor (`on_device`)."""
+
+    def __init__(self, items, T: int, H: int, W: int, paths: bool):
+        self.items, self.T, self.H, self.W, self.paths = items, T, H, W, paths
+
+    def on_device(self, i: int) -> bool:
+        f = self.items[i]
+        return torch.is_tensor(f) and f.is_cuda
+
+    def host(self, i: int) -> np.ndarray:
+        f = self.items[i]
+        if self.paths:
+            img = _imread(f)
+            if img.shape != (self.H, self.W, 3):
+                raise ValueError(f"frame {i} ({f}) is {img.shape[1]}x{img.shape[0]}, the clip is {self.W}x{self.H}")
+            return img
+        return f.numpy() if torch.is_tensor(f) else np.asarray(f)
+
+
+def _check_frame(i, shape, dtype) -> None:
+    if dtype not in (np.uint8, torch.uint8):
+        raise ValueError(f"frames must be uint8; frame {i} is {dtype}")
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"frames must be 3-channel HWC arrays [H,W,3]; frame {i} has shape {tuple(shape)}")
+    if shape[0] < MIN_SIZE or shape[1] < MIN_SIZE:
+        raise ValueError(f"frames must be at least {MIN_SIZE}x{MIN_SIZE}; frame {i} is {shape[1]}x{shape[0]}")
+
+
+def frames_of(frames) -> _Frames:
+    """Validate a clip: a uint8 [T,H,W,3] array or tensor (host or device), a list of uint8 [H,W,3] arrays / tensors, or a list of
+    image paths (only their headers are read here).  Raises ValueError with the reason."""
+    if isinstance(frames, (str, bytes)) or not hasattr(frames, "__len__") or not hasattr(frames, "__getitem__"):
+        raise ValueError(f"frames must be an indexable sequence of frames, got {type(frames).__name__}")
+    T = len(frames)
+    if T < 2:
+        raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {T}")
+    if isinstance(frames, (np.ndarray, torch.Tensor)):
+        if frames.ndim != 4:
+            raise ValueError(f"a frame array must be [T,H,W,3]; got shape {tuple(frames.shape)}")
+        _check_frame(0, tuple(frames.shape[1:]), frames.dtype)
+        return _Frames(frames, T, int(frames.shape[1]), int(frames.shape[2]), paths=False)
+    items = list(frames)
+    is_path = [isinstance(f, (str, os.PathLike)) for f in items]
+    if any(is_path) and not all(is_path):
+        raise ValueError("frames mixes image paths and arrays")
+    if all(is_path):
+        from PIL import Image
+        sizes = []
+        for p in items:
+            with Image.open(p) as im:           # the header only: decoding happens later, on worker threads
+                sizes.append((im.size[1], im.size[0]))
+        for i, (h, w) in enumerate(sizes):
+            _check_frame(i, (h, w, 3), np.uint8)
+            if (h, w) != sizes[0]:
+                raise ValueError(f"mixed frame sizes: frame 0 is {sizes[0][1]}x{sizes[0][0]}, frame {i} ({items[i]}) is {w}x{h}")
+        return _Frames([os.fspath(p) for p in items], T, sizes[0][0], sizes[0][1], paths=True)
+    for i, f in enumerate(items):
+        if not isinstance(f, (np.ndarray, torch.Tensor)):
+            raise ValueError(f"frame {i} is a {type(f).__name__}, not an array, tensor or image path")
+        _check_frame(i, tuple(f.shape), f.dtype)
+        if tuple(f.shape) != tuple(items[0].shape):
+            raise ValueError(f"mixed frame sizes: frame 0 is {items[0].shape[1]}x{items[0].shape[0]}, frame {i} is {f.shape[1]}x{f.shape[0]}")
+    return _Frames(items, T, int(items[0].shape[0]), int(items[0].shape[1]), paths=False)
+
+
+def labels_of(labels, T: int) -> np.ndarray:
+    lab = np.asarray(labels).reshape(-1)
+    if lab.size != T:
+        raise ValueError(f"labels has {lab.size} entries for a clip of {T} frames")
+    if not np.isin(lab, (0, 1)).all():
+        raise ValueError("labels must be 0 (blurry) or 1 (sharp) per frame")
+    return lab.astype(np.int64)
+
+
+def window_plan(labels, n_seq: int = 3) -> list:
+    """The harness's window plan for a clip labelled `labels` (inference.Inference.infer): one entry per output frame with the n_seq
+    window frames, the two reference frames, whether each reference is zeroed (`zero_pre` is the routing: True = no-reference branch)
+    and the n_seq + 2 `forward_window` keys (frame indices, `ZERO` for a zeroed reference)."""
+    T = len(labels)
+    wins = selection.assemble_windows([str(i) for i in range(T)], labels, n_seq, True, number=int)
+    plan = []
+    for k, w in enumerate(wins):
+        win, pre, sub = [int(f) for f in w["window"]], int(w["pre"]), int(w["sub"])
+        plan.append({"index": k, "window": win, "pre": pre, "sub": sub, "zero_pre": bool(w["zero_pre"]), "zero_sub": bool(w["zero_sub"]),
+                     "keys": win + [ZERO if w["zero_pre"] else pre, ZERO if w["zero_sub"] else sub]})
+    return plan
+
+
+def _lanes(model, device, n: int) -> list:
+    """The launch streams of the windows, one set per model and device: `forward_window` captures one graph per launch stream, so
+    fresh streams per clip would capture fresh graphs per clip."""
+    key = ("video_lanes", device.index, n)
+    if key not in model._side_streams:
+        model._side_streams[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
+    return model._side_streams[key]
+
+
+class ClipRun:
+    """Iterator of (index, uint8 [H,W,3] device tensor) in frame order; see `deblur_clip`.  `labels` (0/1 per frame; computed on first
+    access when the caller gave none) and `plan` (`window_plan(labels)`) describe what runs; `recomputed` lists the frames that were
+    recomputed in bf16x3 because their 16-bit pass left a non-finite value."""
+
+    def __init__(self, model, frames: _Frames, labels, out):
+        self.model, self.frames = model, frames
+        params = list(model.parameters())
+        self.device = params[0].device if params else torch.device("cpu")
+        if self.device.type != "cuda":
+            raise RuntimeError("speinet_amd runs on MI355X only (HIP kernels): move the model to a ROCm device first")
+        self._labels = labels
+        if out is not None and out.device != self.device:
+            raise ValueError(f"out is on {out.device}, the model on {self.device}")
+        self.out = out
+        self.recomputed = []         # frames whose 16-bit pass left a non-finite value and that were recomputed in bf16x3
+        self._plan = None
+        self._it = None
+
+    @property
+    def labels(self) -> np.ndarray:
+        if self._labels is None:
+            self._labels = self._detect()
+        return self._labels
+
+    @property
+    def plan(self) -> list:
+        if self._plan is None:
+            self._plan = window_plan(self.labels)
+        return self._plan
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._it is None:
+            self._it = self._run()
+        return next(self._it)
+
+    def _detect(self) -> np.ndarray:
+        """The LD detector's labels, DETECT_BATCH frames at a time: uint8 upload, gray planes (spei_frames_u8_in), focus measures."""
+        fr, dev, B = self.frames, self.device, DETECT_BATCH
+        T, H, W = fr.T, fr.H, fr.W
+        feats = []
+        with torch.no_grad(), torch.cuda.device(dev), ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as pool:
+            futs = {}
+
+            def want(upto):
+                for i in range(min(upto, T)):
+                    if i not in futs and not fr.on_device(i):
+                        futs[i] = pool.submit(fr.host, i)
+
+            stage = [torch.empty(B, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            events = [None, None]
+            batch = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+            for b, i0 in enumerate(range(0, T, B)):
+                n = min(B, T - i0)
+                want(i0 + 2 * B)
+                st = stage[b % 2]
+                if events[b % 2] is not None:
+                    events[b % 2].synchronize()           # the upload issued two batches ago
+                host = [i for i in range(i0, i0 + n) if not fr.on_device(i)]
+                for i in host:
+                    st[i - i0].numpy()[...] = futs.pop(i).result()
+                if host:
+                    batch[:n].copy_(st[:n], non_blocking=True)
+                    events[b % 2] = torch.cuda.Event()
+                    events[b % 2].record()
+                for i in range(i0, i0 + n):
+                    if fr.on_device(i):
+                        batch[i - i0].copy_(fr.items[i])
+                _, gray = ops.frames_u8_in(batch[:n], gray=True, planes=False)
+                feats.append(detector.gray_focus_measures(gray, 11))
+        return detector.predict(torch.cat(feats))
+
+    def _run(self):
+        m, dev, fr = self.model, self.device, self.frames
+        T, H, W = fr.T, fr.H, fr.W
+        Hp, Wp = padded_size(H), padded_size(W)
+        plan = self.plan
+        n = m.n_sequence
+        pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
+        cache = FrameCache(pool, capacity=16, device=dev, load=fr.host)     # uint8 frames, decoded and uploaded once each
+        enc = EncoderCache()
+        inflight, ready = collections.deque(), collections.deque()
+        # the stream current at the first `next` assembles the inputs; the windows run on the lanes; a frame handed out is ordered
+        # before later work on whatever stream is current at that `next`
+        home = torch.cuda.current_stream(dev)
+        lanes = _lanes(m, dev, LANES)
+        # per window: the egress kernel's non-finite flag, copied to page-locked memory behind the window (read once the window is done)
+        flags = torch.zeros(FLAG_RING, dtype=torch.int32, device=dev)
+        flags_host = torch.zeros(FLAG_RING, dtype=torch.int32, pin_memory=True)
+
+        def frame(i):
+            return fr.items[i].to(dev).contiguous() if fr.on_device(i) else cache.get_dev(i)
+
+        def prepare(k):
+            """Window k's input [1, n + 2, 3, Hp, Wp] on the home stream."""
+            for ahead in plan[k:k + 1 + PREFETCH]:
+                cache.request([i for i in ahead["keys"] if i is not ZERO and not fr.on_device(i)])
+            x = torch.empty(1, n + 2, 3, Hp, Wp, device=dev)
+            for j, key in enumerate(plan[k]["keys"]):
+                if key is ZERO:
+                    x[0, j].zero_()
+                else:
+                    ops.frames_u8_in(frame(key), out=x[0, j])
+            return x
+
+        def enqueue(k, x, nxt):
+            """Window k on its lane (and window k + 1's encoder passes on the model's prefetch stream)."""
+            if len(inflight) >= max(2, len(lanes)):
+                inflight.popleft().synchronize()           # the host stays at most two windows ahead of the GPU
+            w = plan[k]
+            dst = self.out[k] if self.out is not None else torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+            lane = lanes[k % len(lanes)]
+            lane.wait_stream(home)                         # the window's input was assembled on the home stream
+            slot = k % FLAG_RING
+            with torch.cuda.stream(lane):
+                x.record_stream(lane)
+                dst.record_stream(lane)
+                if nxt is not None:
+                    nxt.record_stream(lane)
+                    m.prefetch_window(nxt, plan[k + 1]["keys"], enc, zero_ref=plan[k + 1]["zero_pre"])
+                y = m.forward_window(x, w["keys"], enc, zero_ref=w["zero_pre"])
+                ops.frame_u8_out(y[0], H, W, out=dst, nonfinite=flags[slot:slot + 1])
+                flags_host[slot:slot + 1].copy_(flags[slot:slot + 1], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+            inflight.append(ev)
+            ready.append((k, dst, ev, x))
+
+        def redo(k, x, dst):
+            """Window k again in split-bf16 arithmetic (fp32 exponent range), eagerly, on the home stream: a 16-bit pass left a NaN or an
+            infinity in the frame (half operands do not saturate).  As the harness does (inference.Inference._redo_window)."""
+            keep = (m.precision, m.corr_precision, m.use_graph)
+            m.precision, m.corr_precision, m.use_graph = "bf16x3", "bf16x3", False
+            try:
+                y = m(x, routing=[plan[k]["zero_pre"]])
+            finally:
+                m.precision, m.corr_precision, m.use_graph = keep
+            slot = k % FLAG_RING
+            ops.frame_u8_out(y[0], H, W, out=dst, nonfinite=flags[slot:slot + 1])
+            if int(flags[slot].item()):
+                raise FloatingPointError(f"non-finite values in deblurred frame {k} in bf16x3 arithmetic as well: the input or the "
+                                         "checkpoint is at fault")
+            self.recomputed.append(k)
+            warnings.warn(f"speinet_amd.video: frame {k} had a non-finite value in {keep[0]} arithmetic and was recomputed in bf16x3",
+                          RuntimeWarning, stacklevel=3)
+
+        def hand_out():
+            k, t, e, x = ready.popleft()
+            e.synchronize()                                # done already: the limiter in `enqueue` waited for it (not so while draining)
+            cur = torch.cuda.current_stream(dev)
+            if int(flags_host[k % FLAG_RING]):
+                with torch.cuda.stream(home):
+                    home.wait_event(e)
+                    redo(k, x, t)
+                cur.wait_stream(home)
+            else:
+                cur.wait_event(e)
+            if cur != home:
+                t.record_stream(cur)
+            return k, t
+
+        # grad mode and the current device are set around each step, not across a `yield`: they are the caller's while it holds a frame
+        try:
+            with torch.no_grad(), torch.cuda.device(dev), torch.cuda.stream(home):
+                nxt = prepare(0)
+            for k in range(T):
+                with torch.no_grad(), torch.cuda.device(dev):
+                    with torch.cuda.stream(home):
+                        x = nxt
+                        nxt = prepare(k + 1) if k + 1 < T else None
+                        enqueue(k, x, nxt)
+                    # frames are handed out LAG windows behind: by then the limiter has waited for that window, so its non-finite flag
+                    # is on the host without a stall, and the windows after it keep running
+                    got = hand_out() if len(ready) > LAG else None
+                if got is not None:
+                    yield got
+            while ready:
+                with torch.no_grad(), torch.cuda.device(dev):
+                    got = hand_out()
+                yield got
+        finally:
+            pool.shutdown(wait=False, cancel_futures=True)
+
+
+def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None) -> ClipRun:
+    """Deblur a clip: an iterator of (index, uint8 [H,W,3] frame on the model's device), in frame order, one per input frame.
+
+    model  — an eval() `SPEINet` on a ROCm device; its `precision`, `corr_precision`, `use_graph` and `streams` are used as set.
+    frames — T >= 2 frames of one size, at least 20x20: a uint8 [T,H,W,3] numpy array or torch tensor (host or device), a list of
+             uint8 [H,W,3] arrays / tensors, or a list of image paths (decoded to RGB on worker threads, a few windows ahead).
+    labels — optional 0/1 per frame (1 = sharp); None: the LD detector labels the clip in a first streaming pass.
+    out    — optional contiguous uint8 [T,H,W,3] tensor on the model's device: frame i is written to out[i] and that view is yielded.
+
+    The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
+    complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
+    holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
+    to `ClipRun.recomputed` with a RuntimeWarning, and FloatingPointError is raised if the frame is still not finite."""
+    fr = frames_of(frames)
+    lab = None if labels is None else labels_of(labels, fr.T)
+    shape = (fr.T, fr.H, fr.W, 3)
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 [{fr.T},{fr.H},{fr.W},3] tensor")
+    return ClipRun(model, fr, lab, out)
+
+
+def _inputs(spec: str) -> list:
+    files = [os.path.join(spec, f) for f in os.listdir(spec)] if os.path.isdir(spec) else glob.glob(spec)
+    return sorted(f for f in files if f.lower().endswith(IMAGE_EXTS) and os.path.isfile(f))
+
+
+def load_model(model_path: str, device, precision: str = "f16", graph: bool = True):
+    """A SPEINet in eval() on `device` with the harness's arithmetic pairing for `precision` (`synthetic`: the seed-0 test weights)."""
+    from . import checkpoint
+    from .speinet import SPEINet, default_args
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    net = SPEINet(in_channels=3, n_sequence=3, out_channels=3, n_resblock=3, n_feat=32, device=str(device), args=default_args())
+    if model_path == "synthetic":
+        from .synth import state_dict_template, synth_state_dict
+        net.load_state_dict(synth_state_dict(state_dict_template(), seed=0))
+    else:
+        checkpoint.load_into(net, model_path, strict=True)
+    net = net.to(device).eval()
+    net.precision, net.corr_precision = precision, CORR_PRECISION[precision]
+    net.use_graph = graph
+    net.streams = 1
+    return net
+
+
+def main(argv=None) -> None:
+    p = argparse.ArgumentParser(description="Deblur a clip of image files of any size (at least 20x20) on an MI355X: one PNG per input frame")
+    p.add_argument("--input", required=True, help="a directory of frames, or a glob (PNG / JPG / BMP); frames in file-name order")
+    p.add_argument("--output", required=True, help="directory for the deblurred PNGs (input file name, .png)")
+    p.add_argument("--labels", default=None, help="0/1 per frame (1 = sharp) as a .npy file; default: the LD detector labels the clip")
+    p.add_argument("--model_path", required=True, help="checkpoint in the reference layout, or 'synthetic' (seed-0 test weights)")
+    p.add_argument("--precision", choices=sorted(CORR_PRECISION), default="f16",
+                   help="arithmetic of the GEMM-shaped kernels (default f16 with the top2 correlation: the throughput configuration)")
+    p.add_argument("--device", default="cuda")
+    p.add_argument("--no_graph", dest="graph", action="store_false", default=True, help="launch kernels eagerly (no hipGraph replay)")
+    a = p.parse_args(argv)
+    files = _inputs(a.input)
+    if len(files) < 2:
+        raise SystemExit(f"--input {a.input}: {len(files)} image file(s) found, a clip needs at least 2")
+    names = [os.path.splitext(os.path.basename(f))[0] + ".png" for f in files]
+    if len(set(names)) != len(names):
+        raise SystemExit(f"--input {a.input}: two frames share a file name stem (the outputs are <stem>.png)")
+    labels = np.load(a.labels) if a.labels else None
+    net = load_model(a.model_path, a.device, a.precision, a.graph)
+    run = deblur_clip(net, files, labels)
+    os.makedirs(a.output, exist_ok=True)
+    H, W = run.frames.H, run.frames.W
+    slots = [{"buf": torch.empty(H, W, 3, dtype=torch.uint8, pin_memory=True), "fut": None} for _ in range(8)]
+
+    def write(buf, ev, path):
+        ev.synchronize()
+        _imwrite(path, buf.numpy())
+
+    t0 = t_prev = time.time()
+    with ThreadPoolExecutor(max_workers=4, thread_name_prefix="speinet-png") as writers:
+        for i, frame in run:
+            sl = slots[i % len(slots)]
+            if sl["fut"] is not None:
+                sl["fut"].result()
+            sl["buf"].copy_(frame, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            sl["fut"] = writers.submit(write, sl["buf"], ev, os.path.join(a.output, names[i]))
+            now = time.time()
+            branch = "no-reference" if run.plan[i]["zero_pre"] else "reference"
+            print(f"> {names[i]} {branch} {now - t_prev:.3f}s", flush=True)
+            if run.recomputed and run.recomputed[-1] == i:
+                print(f"# {names[i]}: non-finite value in the {a.precision} frame, recomputed in bf16x3 ({len(run.recomputed)} so far)",
+                      flush=True)
+            t_prev = now
+        for sl in slots:
+            if sl["fut"] is not None:
+                sl["fut"].result()
+    dt = time.time() - t0
+    print(f"# {len(files)} frames {W}x{H} in {dt:.2f}s: {len(files) / dt:.2f} frames/s ({a.precision})", flush=True)
+
+
+if __name__ == "__main__":
+    main()
