@@ -353,29 +353,32 @@ int spei_conv_s2_adjoint_slab16(const float* dy, int k0, const void* const* wfra
 int spei_relu_bwd(const float* y, const float* dy, float* dz, int64_t n, spei_stream_t stream);
 
 /* Plane statistics of the ResBlock gates, training form (model/block.py:71-73 ZPool over W and over H, :8-24 SE pooling):
- * prod == 0: rowmax, rowmean [H][C] (over x), colmax, colmean [W][C] (over y), mean [C] of a [H][W][C];
- * prod == 1: the plain sums of a * b over x, over y and over the map into rowmean / colmean / mean (rowmax = colmax = NULL):
- * with a = dOut and b = x1 these are the gradients of g1, g2 and s of out = x + x1 * (s + g1 + g2).
+ * prod == 0: rowmax, rowmean [H][C] (over x), colmax, colmean [W][C] (over y), mean [C] of a [H][W][C], and the int32 arg-max of
+ * each maximum: rowarg [H][C] the LOWEST x, colarg [W][C] the LOWEST y among the maximal elements (torch.max(dim)'s index, which
+ * receives the maximum's whole gradient however many elements tie);
+ * prod == 1: the plain sums of a * b over x, over y and over the map into rowmean / colmean / mean (rowmax = colmax = rowarg =
+ * colarg = NULL): with a = dOut and b = x1 these are the gradients of g1, g2 and s of out = x + x1 * (s + g1 + g2).
  * ws: spei_plane_ws_floats(H, W, C) floats.  C in {32, 64, 128}. */
 int64_t spei_plane_ws_floats(int H, int W, int C);
-int spei_plane_stats(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, float* rowmean, float* colmax,
-                     float* colmean, float* mean, float* ws, spei_stream_t stream);
+int spei_plane_stats(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, int* rowarg, float* rowmean,
+                     float* colmax, int* colarg, float* colmean, float* mean, float* ws, spei_stream_t stream);
 
 /* The same for `batch` equally sized maps stored one after the other (a, b: batch * H*W rows; outputs [batch][H][C], [batch][W][C],
  * [batch][C]); ws: batch * spei_plane_ws_floats(H, W, C) floats. */
-int spei_plane_stats_batched(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, float* rowmean, float* colmax,
-                             float* colmean, float* mean, float* ws, int batch, spei_stream_t stream);
+int spei_plane_stats_batched(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, int* rowarg, float* rowmean,
+                             float* colmax, int* colarg, float* colmean, float* mean, float* ws, int batch, spei_stream_t stream);
 
 /* Backward of the gated residual sum through x1 (model/block.py:136-140): dx1 = dOut * (s + g1 + g2) + the pooled statistics'
- * gradients routed back (means spread evenly, maxima to the arg-max element).  dx = dOut needs no kernel. */
-int spei_resblock_apply_bwd(const float* dout, const float* x1, const float* s, const float* g1, const float* g2, const float* rowmax,
-                            const float* colmax, const float* d_rowmax, const float* d_rowmean, const float* d_colmax,
-                            const float* d_colmean, const float* d_mean, float* dx1, int H, int W, int C, spei_stream_t stream);
+ * gradients routed back (means spread evenly, each maximum's to its ONE arg-max element rowarg / colarg of spei_plane_stats).
+ * dx = dOut needs no kernel. */
+int spei_resblock_apply_bwd(const float* dout, const float* s, const float* g1, const float* g2, const int* rowarg, const int* colarg,
+                            const float* d_rowmax, const float* d_rowmean, const float* d_colmax, const float* d_colmean,
+                            const float* d_mean, float* dx1, int H, int W, int C, spei_stream_t stream);
 /* The same for `batch` dense maps stored one after the other (and their statistics / gate maps likewise) in one launch. */
-int spei_resblock_apply_bwd_batched(const float* dout, const float* x1, const float* s, const float* g1, const float* g2,
-                                    const float* rowmax, const float* colmax, const float* d_rowmax, const float* d_rowmean,
-                                    const float* d_colmax, const float* d_colmean, const float* d_mean, float* dx1, int batch, int H,
-                                    int W, int C, spei_stream_t stream);
+int spei_resblock_apply_bwd_batched(const float* dout, const float* s, const float* g1, const float* g2, const int* rowarg,
+                                    const int* colarg, const float* d_rowmax, const float* d_rowmean, const float* d_colmax,
+                                    const float* d_colmean, const float* d_mean, float* dx1, int batch, int H, int W, int C,
+                                    spei_stream_t stream);
 
 /* The gate maps of a ResBlock from its plane statistics, forward and backward, for the training step (model/block.py:8-24 SEBlock,
  * :49-68 BasicConv1 = 2->1 conv + BatchNorm2d(1), :75-96 AttentionGate1/2, :116-119 TripletAttention) — BatchNorm on batch statistics

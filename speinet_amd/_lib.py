@@ -74,10 +74,10 @@ SIGNATURES = {
     "spei_conv_wgrad_f32": (I, [P, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "spei_relu_bwd": (I, [P, P, P, L, P]),
     "spei_plane_ws_floats": (L, [I, I, I]),
-    "spei_plane_stats": (I, [P, P, I, I, I, I, P, P, P, P, P, P, P]),
-    "spei_plane_stats_batched": (I, [P, P, I, I, I, I, P, P, P, P, P, P, I, P]),
-    "spei_resblock_apply_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P]),
-    "spei_resblock_apply_bwd_batched": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "spei_plane_stats": (I, [P, P, I, I, I, I, P, P, P, P, P, P, P, P, P]),
+    "spei_plane_stats_batched": (I, [P, P, I, I, I, I, P, P, P, P, P, P, P, P, I, P]),
+    "spei_resblock_apply_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P]),
+    "spei_resblock_apply_bwd_batched": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "spei_gate_train_saved_floats": (L, [I, I, I, I, I]),
     "spei_gate_train_ws_floats": (L, [I, I, I, I, I]),
     "spei_gate_train_nparams": (I, [I]),

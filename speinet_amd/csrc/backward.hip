@@ -420,25 +420,35 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------------------------------------
 // ResBlock gate statistics for training (model/block.py:71-73 ZPool, :8-24 SE pooling), and the sums its backward needs.
 //   stats:   rowmax / rowmean [H][C] over x, colmax / colmean [W][C] over y, mean [C] of a = x1              (PROD = false)
+//            with the arg-max of each maximum: rowarg [H][C] the lowest x, colarg [W][C] the lowest y among the maximal elements —
+//            torch.max(dim) hands the gradient of a maximum to that one element (its first index), however many elements tie
 //   bwd:     rowsum [H][C], colsum [W][C], total [C] of a * b  (a = dOut, b = x1: the gradients of g1, g2 and s)  (PROD = true)
 // Stage 1: a block owns an R x 64-pixel... tile of TR rows x TC columns, threads = channels x columns; stage 2 combines the tile
 // partials in a fixed order.  C <= 128, C % 4 == 0.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int GT = 16;        // tile rows = tile columns (16: a 200x200 training crop still gives 169 workgroups)
 
+// (m, a) <- the larger of (m, a) and (v, i); of equal values the lower index
+__device__ __forceinline__ void argmax_merge(float& m, int& a, float v, int i) {
+    if (v > m || (v == m && i < a)) { m = v; a = i; }
+}
+
 template <bool PROD>
 __global__ __launch_bounds__(256) void plane_stats_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W, int C,
                                                           float* __restrict__ rowp_max, float* __restrict__ rowp_sum,
-                                                          float* __restrict__ colp_max, float* __restrict__ colp_sum, int ntx, int nty) {
+                                                          float* __restrict__ colp_max, float* __restrict__ colp_sum,
+                                                          int* __restrict__ rowp_arg, int* __restrict__ colp_arg, int ntx, int nty) {
     {   // blockIdx.y = sample of a batch of equally sized maps: inputs and partial buffers move by one sample's extent
         const size_t z = blockIdx.y;
         a += z * H * W * C;
         if (PROD) b += z * H * W * C;
-        const size_t pstride = 2 * ((size_t)ntx * H * C + (size_t)nty * W * C);
+        const size_t pstride = 3 * ((size_t)ntx * H * C + (size_t)nty * W * C);
         if (rowp_max) rowp_max += z * pstride;
         rowp_sum += z * pstride;
         if (colp_max) colp_max += z * pstride;
         colp_sum += z * pstride;
+        if (rowp_arg) rowp_arg += z * pstride;
+        if (colp_arg) colp_arg += z * pstride;
     }
     // thread -> (channel c, column group): with C channels, 256 / C columns are processed side by side
     const int tid = threadIdx.x;
@@ -446,63 +456,84 @@ __global__ __launch_bounds__(256) void plane_stats_kernel(const float* __restric
     const int tx = blockIdx.x % ntx, ty = blockIdx.x / ntx;
     const int x0 = tx * GT, y0 = ty * GT;
     __shared__ float smax[256], ssum[256];
+    __shared__ int sarg[256];
     // column partials: each thread owns columns x0 + cg, x0 + cg + ncg, ... ; row partials need a cross-thread combine per row
     for (int xx = cg; xx < GT; xx += ncg) {
         const int x = x0 + xx;
         float cm = -INFINITY, cs = 0.f;
+        int ca = INT_MAX;
         if (x < W)
             for (int yy = 0; yy < GT && y0 + yy < H; ++yy) {
                 const size_t o = ((size_t)(y0 + yy) * W + x) * C + c;
                 const float v = PROD ? a[o] * b[o] : a[o];
-                cm = fmaxf(cm, v);
+                if (!PROD) argmax_merge(cm, ca, v, y0 + yy);
                 cs += v;
             }
         if (x < W) {
-            if (!PROD) colp_max[((size_t)ty * W + x) * C + c] = cm;
+            if (!PROD) {
+                colp_max[((size_t)ty * W + x) * C + c] = cm;
+                colp_arg[((size_t)ty * W + x) * C + c] = ca;
+            }
             colp_sum[((size_t)ty * W + x) * C + c] = cs;
         }
     }
     for (int yy = 0; yy < GT; ++yy) {
         const int y = y0 + yy;
         float rm = -INFINITY, rs = 0.f;
+        int ra = INT_MAX;
         if (y < H)
             for (int xx = cg; xx < GT && x0 + xx < W; xx += ncg) {
                 const size_t o = ((size_t)y * W + x0 + xx) * C + c;
                 const float v = PROD ? a[o] * b[o] : a[o];
-                rm = fmaxf(rm, v);
+                if (!PROD) argmax_merge(rm, ra, v, x0 + xx);
                 rs += v;
             }
         smax[tid] = rm;
         ssum[tid] = rs;
+        sarg[tid] = ra;
         __syncthreads();
         if (cg == 0 && y < H) {
             float m = smax[c], s = ssum[c];
-            for (int j = 1; j < ncg; ++j) { m = fmaxf(m, smax[j * C + c]); s += ssum[j * C + c]; }
-            if (!PROD) rowp_max[((size_t)tx * H + y) * C + c] = m;
+            int ar = sarg[c];
+            for (int j = 1; j < ncg; ++j) {     // thread j's columns interleave with the others': ties go to the lowest x
+                if (!PROD) argmax_merge(m, ar, smax[j * C + c], sarg[j * C + c]);
+                s += ssum[j * C + c];
+            }
+            if (!PROD) {
+                rowp_max[((size_t)tx * H + y) * C + c] = m;
+                rowp_arg[((size_t)tx * H + y) * C + c] = ar;
+            }
             rowp_sum[((size_t)tx * H + y) * C + c] = s;
         }
         __syncthreads();
     }
 }
 
-// stage 2: lines [L][C] from `nt` partials [nt][L][C]; scale applied to the sum (1/W for a mean, 1 for a plain sum)
-__global__ __launch_bounds__(256) void plane_combine_kernel(const float* __restrict__ pmax, const float* __restrict__ psum, int nt, int64_t LC,
-                                                            float scale, float* __restrict__ omax, float* __restrict__ osum, int64_t pstride) {
+// stage 2: lines [L][C] from `nt` partials [nt][L][C]; scale applied to the sum (1/W for a mean, 1 for a plain sum); with pmax, the
+// maximum and (parg) its arg-max, ties to the lower index
+__global__ __launch_bounds__(256) void plane_combine_kernel(const float* __restrict__ pmax, const float* __restrict__ psum,
+                                                            const int* __restrict__ parg, int nt, int64_t LC, float scale,
+                                                            float* __restrict__ omax, float* __restrict__ osum, int* __restrict__ oarg,
+                                                            int64_t pstride) {
     {   // blockIdx.y = sample: partials move by pstride floats, outputs by LC
         const int64_t z = blockIdx.y;
         if (pmax) pmax += z * pstride;
+        if (parg) parg += z * pstride;
         psum += z * pstride;
         if (omax) omax += z * LC;
+        if (oarg) oarg += z * LC;
         osum += z * LC;
     }
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= LC) return;
     float m = -INFINITY, s = 0.f;
+    int a = INT_MAX;
     for (int k = 0; k < nt; ++k) {
-        if (pmax) m = fmaxf(m, pmax[(size_t)k * LC + i]);
+        if (pmax) argmax_merge(m, a, pmax[(size_t)k * LC + i], parg[(size_t)k * LC + i]);
         s += psum[(size_t)k * LC + i];
     }
     if (omax) omax[i] = m;
+    if (oarg) oarg[i] = a;
     osum[i] = s * scale;
 }
 
@@ -527,11 +558,14 @@ __global__ __launch_bounds__(256) void lines_total_kernel(const float* __restric
 // gated residual sum backward:  out = x + x1 * (s[c] + g1[y][c] + g2[x][c])
 //   dx1 = dOut * (s + g1 + g2)
 //       + d_rowmean[y][c] / W + d_colmean[x][c] / H + d_mean[c] / (H W)                       (mean pools)
-//       + d_rowmax[y][c] [x1 == rowmax[y][c]] + d_colmax[x][c] [x1 == colmax[x][c]]           (max pools: the arg-max element)
+//       + d_rowmax[y][c] [x == rowarg[y][c]] + d_colmax[x][c] [y == colarg[x][c]]            (max pools: the arg-max element)
+// The arg-max is the FIRST maximal element (spei_plane_stats: lowest x of a row, lowest y of a column), as torch.max(dim) routes it:
+// comparing x1 with the maximum instead would hand d_rowmax to every tied element (W of them on a constant row).
 // (dx = dOut is the caller's tensor itself.)
 // ---------------------------------------------------------------------------------------------------------------------
 struct ApplyBwdParams {
-    const float *dout, *x1, *s, *g1, *g2, *rowmax, *colmax, *d_rowmax, *d_rowmean, *d_colmax, *d_colmean, *d_mean;
+    const float *dout, *s, *g1, *g2, *d_rowmax, *d_rowmean, *d_colmax, *d_colmean, *d_mean;
+    const int *rowarg, *colarg;
     float* dx1;
     int H, W, C;
 };
@@ -548,17 +582,20 @@ __global__ __launch_bounds__(256) void resblock_apply_bwd_kernel(const ApplyBwdP
         const int64_t pix = i / cg;
         const int x = (int)(pix % p.W), y = (int)(pix / p.W);
         const size_t o = mo + pix * p.C + c, ro = mr + (size_t)y * p.C + c, co = mc + (size_t)x * p.C + c;
-        const f32x4 d = *reinterpret_cast<const f32x4*>(p.dout + o), v = *reinterpret_cast<const f32x4*>(p.x1 + o);
+        const f32x4 d = *reinterpret_cast<const f32x4*>(p.dout + o);
         const f32x4 gate = *reinterpret_cast<const f32x4*>(p.s + mm + c) + (*reinterpret_cast<const f32x4*>(p.g1 + ro) + *reinterpret_cast<const f32x4*>(p.g2 + co));
         f32x4 r = d * gate + *reinterpret_cast<const f32x4*>(p.d_rowmean + ro) * iw + *reinterpret_cast<const f32x4*>(p.d_colmean + co) * ih +
                   *reinterpret_cast<const f32x4*>(p.d_mean + mm + c) * ihw;
-        const f32x4 rm = *reinterpret_cast<const f32x4*>(p.rowmax + ro), cm = *reinterpret_cast<const f32x4*>(p.colmax + co);
+        const int4 ra = *reinterpret_cast<const int4*>(p.rowarg + ro), ca = *reinterpret_cast<const int4*>(p.colarg + co);
         const f32x4 drm = *reinterpret_cast<const f32x4*>(p.d_rowmax + ro), dcm = *reinterpret_cast<const f32x4*>(p.d_colmax + co);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (v[e] == rm[e]) r[e] += drm[e];
-            if (v[e] == cm[e]) r[e] += dcm[e];
-        }
+        if (ra.x == x) r[0] += drm[0];
+        if (ra.y == x) r[1] += drm[1];
+        if (ra.z == x) r[2] += drm[2];
+        if (ra.w == x) r[3] += drm[3];
+        if (ca.x == y) r[0] += dcm[0];
+        if (ca.y == y) r[1] += dcm[1];
+        if (ca.z == y) r[2] += dcm[2];
+        if (ca.w == y) r[3] += dcm[3];
         *reinterpret_cast<f32x4*>(p.dx1 + o) = r;
     }
 }
@@ -689,57 +726,61 @@ extern "C" int spei_relu_bwd(const float* y, const float* dy, float* dz, int64_t
 
 extern "C" int64_t spei_plane_ws_floats(int H, int W, int C) {
     const int64_t ntx = (W + GT - 1) / GT, nty = (H + GT - 1) / GT;
-    return 2 * (ntx * H * C + nty * W * C);
+    return 3 * (ntx * H * C + nty * W * C);           // maxima, sums and (int32) arg-maxima of the tile partials
 }
 
-// prod == 0: rowmax, rowmean [H][C], colmax, colmean [W][C], mean [C] of a.   prod == 1: rowmax = colmax = NULL; rowmean / colmean /
-// mean receive the plain SUMS of a * b over x, over y and over the map.
-static int plane_stats_run(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, float* rowmean, float* colmax,
-                           float* colmean, float* mean, float* ws, int batch, spei_stream_t stream) {
-    SPEI_REQUIRE(a && rowmean && colmean && mean && ws && (!prod || b) && (prod || (rowmax && colmax)), "spei_plane_stats: null pointer");
+// prod == 0: rowmax, rowarg, rowmean [H][C], colmax, colarg, colmean [W][C], mean [C] of a.   prod == 1: rowmax = colmax = rowarg =
+// colarg = NULL; rowmean / colmean / mean receive the plain SUMS of a * b over x, over y and over the map.
+static int plane_stats_run(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, int* rowarg, float* rowmean,
+                           float* colmax, int* colarg, float* colmean, float* mean, float* ws, int batch, spei_stream_t stream) {
+    SPEI_REQUIRE(a && rowmean && colmean && mean && ws && (!prod || b) && (prod || (rowmax && colmax && rowarg && colarg)),
+                 "spei_plane_stats: null pointer");
     SPEI_REQUIRE((C == 32 || C == 64 || C == 128) && H > 0 && W > 0, "spei_plane_stats: C=%d (32/64/128 built)", C);
     SPEI_REQUIRE(batch >= 1 && batch <= 65535, "spei_plane_stats: batch=%d", batch);
     hipStream_t st = (hipStream_t)stream;
     const int ntx = (W + GT - 1) / GT, nty = (H + GT - 1) / GT;
-    const int64_t pstride = 2 * ((int64_t)ntx * H * C + (int64_t)nty * W * C);          // partial floats per sample
+    const int64_t pstride = 3 * ((int64_t)ntx * H * C + (int64_t)nty * W * C);          // partial words per sample
     float* rpm = ws;
     float* rps = rpm + (size_t)ntx * H * C;
     float* cpm = rps + (size_t)ntx * H * C;
     float* cps = cpm + (size_t)nty * W * C;
+    int* rpa = reinterpret_cast<int*>(cps + (size_t)nty * W * C);
+    int* cpa = rpa + (size_t)ntx * H * C;
     const dim3 g1(ntx * nty, batch);
-    if (prod) hipLaunchKernelGGL(plane_stats_kernel<true>, g1, dim3(256), 0, st, a, b, H, W, C, rpm, rps, cpm, cps, ntx, nty);
-    else hipLaunchKernelGGL(plane_stats_kernel<false>, g1, dim3(256), 0, st, a, b, H, W, C, rpm, rps, cpm, cps, ntx, nty);
+    if (prod) hipLaunchKernelGGL(plane_stats_kernel<true>, g1, dim3(256), 0, st, a, b, H, W, C, rpm, rps, cpm, cps, nullptr, nullptr, ntx, nty);
+    else hipLaunchKernelGGL(plane_stats_kernel<false>, g1, dim3(256), 0, st, a, b, H, W, C, rpm, rps, cpm, cps, rpa, cpa, ntx, nty);
     const int64_t hc = (int64_t)H * C, wc = (int64_t)W * C;
     // rows: plain sums first (the channel total is the sum of the row sums), then scaled to means when asked for
-    hipLaunchKernelGGL(plane_combine_kernel, dim3(cdiv(hc, 256), batch), dim3(256), 0, st, prod ? nullptr : rpm, rps, ntx, hc, 1.0f,
-                       prod ? nullptr : rowmax, rowmean, pstride);
+    hipLaunchKernelGGL(plane_combine_kernel, dim3(cdiv(hc, 256), batch), dim3(256), 0, st, prod ? nullptr : rpm, rps, prod ? nullptr : rpa, ntx,
+                       hc, 1.0f, prod ? nullptr : rowmax, rowmean, prod ? nullptr : rowarg, pstride);
     hipLaunchKernelGGL(lines_total_kernel, dim3(batch), dim3(256), 0, st, rowmean, H, C, prod ? 1.0f : 1.0f / ((float)H * (float)W), mean);
-    if (!prod) hipLaunchKernelGGL(plane_combine_kernel, dim3(cdiv(hc, 256), batch), dim3(256), 0, st, nullptr, rps, ntx, hc, 1.0f / (float)W, nullptr,
-                                  rowmean, pstride);
-    hipLaunchKernelGGL(plane_combine_kernel, dim3(cdiv(wc, 256), batch), dim3(256), 0, st, prod ? nullptr : cpm, cps, nty, wc,
-                       prod ? 1.0f : 1.0f / (float)H, prod ? nullptr : colmax, colmean, pstride);
+    if (!prod) hipLaunchKernelGGL(plane_combine_kernel, dim3(cdiv(hc, 256), batch), dim3(256), 0, st, nullptr, rps, nullptr, ntx, hc,
+                                  1.0f / (float)W, nullptr, rowmean, nullptr, pstride);
+    hipLaunchKernelGGL(plane_combine_kernel, dim3(cdiv(wc, 256), batch), dim3(256), 0, st, prod ? nullptr : cpm, cps, prod ? nullptr : cpa, nty,
+                       wc, prod ? 1.0f : 1.0f / (float)H, prod ? nullptr : colmax, colmean, prod ? nullptr : colarg, pstride);
     SPEI_CHECK_LAUNCH("spei_plane_stats");
     return 0;
 }
 
-extern "C" int spei_plane_stats(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, float* rowmean, float* colmax,
-                                float* colmean, float* mean, float* ws, spei_stream_t stream) {
-    return plane_stats_run(a, b, prod, H, W, C, rowmax, rowmean, colmax, colmean, mean, ws, 1, stream);
+extern "C" int spei_plane_stats(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, int* rowarg, float* rowmean,
+                                float* colmax, int* colarg, float* colmean, float* mean, float* ws, spei_stream_t stream) {
+    return plane_stats_run(a, b, prod, H, W, C, rowmax, rowarg, rowmean, colmax, colarg, colmean, mean, ws, 1, stream);
 }
 
-extern "C" int spei_plane_stats_batched(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, float* rowmean,
-                                        float* colmax, float* colmean, float* mean, float* ws, int batch, spei_stream_t stream) {
-    return plane_stats_run(a, b, prod, H, W, C, rowmax, rowmean, colmax, colmean, mean, ws, batch, stream);
+extern "C" int spei_plane_stats_batched(const float* a, const float* b, int prod, int H, int W, int C, float* rowmax, int* rowarg,
+                                        float* rowmean, float* colmax, int* colarg, float* colmean, float* mean, float* ws, int batch,
+                                        spei_stream_t stream) {
+    return plane_stats_run(a, b, prod, H, W, C, rowmax, rowarg, rowmean, colmax, colarg, colmean, mean, ws, batch, stream);
 }
 
-static int resblock_apply_bwd_run(const float* dout, const float* x1, const float* s, const float* g1, const float* g2, const float* rowmax,
-                                  const float* colmax, const float* d_rowmax, const float* d_rowmean, const float* d_colmax,
-                                  const float* d_colmean, const float* d_mean, float* dx1, int batch, int H, int W, int C, spei_stream_t stream) {
-    SPEI_REQUIRE(dout && x1 && s && g1 && g2 && rowmax && colmax && d_rowmax && d_rowmean && d_colmax && d_colmean && d_mean && dx1,
+static int resblock_apply_bwd_run(const float* dout, const float* s, const float* g1, const float* g2, const int* rowarg, const int* colarg,
+                                  const float* d_rowmax, const float* d_rowmean, const float* d_colmax, const float* d_colmean,
+                                  const float* d_mean, float* dx1, int batch, int H, int W, int C, spei_stream_t stream) {
+    SPEI_REQUIRE(dout && s && g1 && g2 && rowarg && colarg && d_rowmax && d_rowmean && d_colmax && d_colmean && d_mean && dx1,
                  "spei_resblock_apply_bwd: null pointer");
     SPEI_REQUIRE(C % 4 == 0 && H > 0 && W > 0 && batch >= 1 && batch <= 65535, "spei_resblock_apply_bwd: bad shape");
     ApplyBwdParams p;
-    p.dout = dout; p.x1 = x1; p.s = s; p.g1 = g1; p.g2 = g2; p.rowmax = rowmax; p.colmax = colmax; p.d_rowmax = d_rowmax;
+    p.dout = dout; p.s = s; p.g1 = g1; p.g2 = g2; p.rowarg = rowarg; p.colarg = colarg; p.d_rowmax = d_rowmax;
     p.d_rowmean = d_rowmean; p.d_colmax = d_colmax; p.d_colmean = d_colmean; p.d_mean = d_mean; p.dx1 = dx1; p.H = H; p.W = W; p.C = C;
     const int64_t total = (int64_t)H * W * (C / 4);
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
@@ -748,17 +789,17 @@ static int resblock_apply_bwd_run(const float* dout, const float* x1, const floa
     return 0;
 }
 
-extern "C" int spei_resblock_apply_bwd(const float* dout, const float* x1, const float* s, const float* g1, const float* g2, const float* rowmax,
-                                       const float* colmax, const float* d_rowmax, const float* d_rowmean, const float* d_colmax,
-                                       const float* d_colmean, const float* d_mean, float* dx1, int H, int W, int C, spei_stream_t stream) {
-    return resblock_apply_bwd_run(dout, x1, s, g1, g2, rowmax, colmax, d_rowmax, d_rowmean, d_colmax, d_colmean, d_mean, dx1, 1, H, W, C, stream);
+extern "C" int spei_resblock_apply_bwd(const float* dout, const float* s, const float* g1, const float* g2, const int* rowarg, const int* colarg,
+                                       const float* d_rowmax, const float* d_rowmean, const float* d_colmax, const float* d_colmean,
+                                       const float* d_mean, float* dx1, int H, int W, int C, spei_stream_t stream) {
+    return resblock_apply_bwd_run(dout, s, g1, g2, rowarg, colarg, d_rowmax, d_rowmean, d_colmax, d_colmean, d_mean, dx1, 1, H, W, C, stream);
 }
 
-extern "C" int spei_resblock_apply_bwd_batched(const float* dout, const float* x1, const float* s, const float* g1, const float* g2,
-                                               const float* rowmax, const float* colmax, const float* d_rowmax, const float* d_rowmean,
-                                               const float* d_colmax, const float* d_colmean, const float* d_mean, float* dx1, int batch, int H,
-                                               int W, int C, spei_stream_t stream) {
-    return resblock_apply_bwd_run(dout, x1, s, g1, g2, rowmax, colmax, d_rowmax, d_rowmean, d_colmax, d_colmean, d_mean, dx1, batch, H, W, C, stream);
+extern "C" int spei_resblock_apply_bwd_batched(const float* dout, const float* s, const float* g1, const float* g2, const int* rowarg,
+                                               const int* colarg, const float* d_rowmax, const float* d_rowmean, const float* d_colmax,
+                                               const float* d_colmean, const float* d_mean, float* dx1, int batch, int H, int W, int C,
+                                               spei_stream_t stream) {
+    return resblock_apply_bwd_run(dout, s, g1, g2, rowarg, colarg, d_rowmax, d_rowmean, d_colmax, d_colmean, d_mean, dx1, batch, H, W, C, stream);
 }
 
 // ---- training: a weight in the reference's layout -> the split (hi, lo) bf16 pair in MFMA fragment order, ONE launch -----------------

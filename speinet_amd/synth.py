@@ -168,3 +168,29 @@ def synth_frames_edges(b: int, h: int, w: int, seed: int = 1700, zero_ref: tuple
         if bi in zero_ref:
             x[bi, 3] = 0.0
     return torch.from_numpy(x), torch.from_numpy(gt)
+
+
+def synth_frames_flat(b: int, h: int, w: int, seed: int = 2300, zero_ref: tuple = (), bar: int | None = None) -> torch.Tensor:
+    """Flat content, the third content class: ``synth_frames`` windows with what real footage has and smooth fields lack — exactly
+    equal pixels over whole regions.  Every sample gets black letterbox bars (``bar`` rows, default h // 4, at the top and the bottom of every frame)
+    and a saturated disc (a clipped highlight, 1.0 in all channels, following the frames' motion); sample 0 is faded to near-black
+    (x 0.03, its bars still exact zeros).  Samples in ``zero_ref`` get frame 3 zeroed (the no-reference route) as in
+    ``synth_frames``.  The feature maps of such input hold many bit-identical values, so the row and column maxima of the
+    ResBlock gates (ZPool) tie."""
+    x = synth_frames(b, h, w, seed=seed).numpy().copy()
+    r = np.random.RandomState(seed + 1)
+    yy, xx = np.meshgrid(np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32), indexing="ij")
+    bar = max(h // 4, 1) if bar is None else bar
+    for bi in range(b):
+        cy, cx = r.uniform(0.35 * h, 0.65 * h), r.uniform(0.25 * w, 0.75 * w)
+        rad = r.uniform(0.12, 0.2) * min(h, w)
+        for f in range(5):
+            disc = (yy - (cy + f - 2)) ** 2 + (xx - (cx + 2 - f)) ** 2 < rad * rad
+            x[bi, f][:, disc] = 1.0
+            x[bi, f, :, :bar] = 0.0
+            x[bi, f, :, h - bar:] = 0.0
+        if bi == 0:
+            x[bi] *= np.float32(0.03)
+        if bi in zero_ref:
+            x[bi, 3] = 0.0
+    return torch.from_numpy(x)

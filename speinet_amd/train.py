@@ -157,6 +157,11 @@ def _p(ctx: Ctx, t: Optional[torch.Tensor]):
     return ctx._tp(t)
 
 
+def _pi(ctx: Ctx, t: torch.Tensor):
+    assert t.dtype == torch.int32
+    return ctx._tp(t)
+
+
 # ---- the GEMM family on raw tensors (no packing objects: the weights change every step) ---------------------------------------
 def _w_conv(weight: torch.Tensor) -> torch.Tensor:
     """Conv2d [N, K, kh, kw] -> [tap][N][K]."""
@@ -654,10 +659,13 @@ class _GatedSum(torch.autograd.Function):
         x, x1 = x.contiguous(), x1.contiguous()
         rowmax, rowmean = torch.empty(B, H, c, device=dev), torch.empty(B, H, c, device=dev)
         colmax, colmean = torch.empty(B, W, c, device=dev), torch.empty(B, W, c, device=dev)
+        # the ZPool arg-max (lowest x of a row, lowest y of a column among the maxima): the backward routes each maximum's gradient to it
+        rowarg, colarg = torch.empty(B, H, c, device=dev, dtype=torch.int32), torch.empty(B, W, c, device=dev, dtype=torch.int32)
         mean = torch.empty(B, c, device=dev)
         ws = torch.empty(B * lib.spei_plane_ws_floats(H, W, c), device=dev)
-        _lib.check(lib.spei_plane_stats_batched(_p(ctx, x1), _NULL, 0, H, W, c, _p(ctx, rowmax), _p(ctx, rowmean), _p(ctx, colmax),
-                                                _p(ctx, colmean), _p(ctx, mean), _p(ctx, ws), B, ctx._stream()), "spei_plane_stats_batched")
+        _lib.check(lib.spei_plane_stats_batched(_p(ctx, x1), _NULL, 0, H, W, c, _p(ctx, rowmax), _pi(ctx, rowarg), _p(ctx, rowmean),
+                                                _p(ctx, colmax), _pi(ctx, colarg), _p(ctx, colmean), _p(ctx, mean), _p(ctx, ws), B,
+                                                ctx._stream()), "spei_plane_stats_batched")
         prm, run, keep_alive = _gate_ptrs(ctx, params)
         s, g1, g2 = torch.empty(B, c, device=dev), torch.empty(B, H, c, device=dev), torch.empty(B, W, c, device=dev)
         saved = torch.empty(lib.spei_gate_train_saved_floats(B, groups, H, W, c), device=dev)
@@ -670,13 +678,13 @@ class _GatedSum(torch.autograd.Function):
                                                    ctx._stream()), "spei_resblock_apply_batched")
         # the backward reads the SAVED batch statistics (train) / the running statistics as they were (eval: copied into `saved` by the
         # forward), never the running buffers, which move again when the same block runs on the next frame
-        fctx.save_for_backward(x1, rowmax, rowmean, colmax, colmean, mean, s, g1, g2, saved, *params)
+        fctx.save_for_backward(x1, rowarg, colarg, rowmax, rowmean, colmax, colmean, mean, s, g1, g2, saved, *params)
         fctx.meta = (B, H, W, bn_train, groups)
         return out
 
     @staticmethod
     def backward(fctx, dout):
-        x1, rowmax, rowmean, colmax, colmean, mean, s, g1, g2, saved, *params = fctx.saved_tensors
+        x1, rowarg, colarg, rowmax, rowmean, colmax, colmean, mean, s, g1, g2, saved, *params = fctx.saved_tensors
         B, H, W, bn_train, groups = fctx.meta
         ctx = _ctx(dout.device)
         lib = _lib.lib()
@@ -686,8 +694,8 @@ class _GatedSum(torch.autograd.Function):
         # gradients of the gates: sums of dOut * x1 over x, over y, over the map
         dg1, dg2, ds = torch.empty(B, H, c, device=dev), torch.empty(B, W, c, device=dev), torch.empty(B, c, device=dev)
         ws = torch.empty(B * lib.spei_plane_ws_floats(H, W, c), device=dev)
-        _lib.check(lib.spei_plane_stats_batched(_p(ctx, dout), _p(ctx, x1), 1, H, W, c, _NULL, _p(ctx, dg1), _NULL, _p(ctx, dg2), _p(ctx, ds),
-                                                _p(ctx, ws), B, ctx._stream()), "spei_plane_stats_batched")
+        _lib.check(lib.spei_plane_stats_batched(_p(ctx, dout), _p(ctx, x1), 1, H, W, c, _NULL, _NULL, _p(ctx, dg1), _NULL, _NULL, _p(ctx, dg2),
+                                                _p(ctx, ds), _p(ctx, ws), B, ctx._stream()), "spei_plane_stats_batched")
         # ... through the gate maps: statistics and parameters are the leaves
         prm, run, keep_alive = _gate_ptrs(ctx, params)
         d_stats = [torch.empty_like(t) for t in (rowmax, rowmean, colmax, colmean, mean)]
@@ -699,8 +707,8 @@ class _GatedSum(torch.autograd.Function):
                                           *[_p(ctx, t) for t in d_stats], _p(ctx, dprm), C.c_void_p(gws.data_ptr()), ctx._stream()),
                    "spei_gate_maps_bwd")
         dx1 = torch.empty_like(x1)
-        _lib.check(lib.spei_resblock_apply_bwd_batched(_p(ctx, dout), _p(ctx, x1), _p(ctx, s), _p(ctx, g1), _p(ctx, g2), _p(ctx, rowmax),
-                                                       _p(ctx, colmax), _p(ctx, d_stats[0]), _p(ctx, d_stats[1]), _p(ctx, d_stats[2]),
+        _lib.check(lib.spei_resblock_apply_bwd_batched(_p(ctx, dout), _p(ctx, s), _p(ctx, g1), _p(ctx, g2), _pi(ctx, rowarg), _pi(ctx, colarg),
+                                                       _p(ctx, d_stats[0]), _p(ctx, d_stats[1]), _p(ctx, d_stats[2]),
                                                        _p(ctx, d_stats[3]), _p(ctx, d_stats[4]), _p(ctx, dx1), B, H, W, c, ctx._stream()),
                    "spei_resblock_apply_bwd_batched")
         # dprm: se_w1 | se_b1 | se_w2 | se_b2 | cw_w | cw_g | cw_b | hc_w | hc_g | hc_b  -> the parameters' shapes (views of one buffer)

@@ -9,13 +9,16 @@ Synthetic name-keyed weights (seed 0), seeded inputs and targets.
 its published algorithm (per call: new_empty((B,1,1)).bernoulli_(keep) / keep) and RECORDS every draw, so the fixture carries
 the factors the reference actually used; speinet_amd.train.drop_path_scales draws the same stream from the same seed.
 
-Committed per case: the full output and the loss terms, the DropPath draws, per-parameter gradient L2 norms and every 97th
-element of each gradient, the BatchNorm running buffers after the step, and every 97th element of every 25th parameter after
-the Adam step.  The same step is then repeated in FLOAT64 (same weights, inputs, DropPath factors, HEM shuffle): `sub64/*`
+Committed per case: the full output and the loss terms, the DropPath draws, per-parameter gradient L2 norms and every `stride`-th
+element of each gradient (97; 997 for G23, which keeps the fixture small), the BatchNorm running buffers after the step, and every
+`stride`-th element of every 25th parameter after the Adam step.  G23 is written in the packed form of oracle/fixtures.py (one
+array per family instead of one archive entry per parameter); tests read every fixture through oracle.fixtures.load_train_fixture.  The same step is then repeated in FLOAT64 (same weights, inputs, DropPath factors, HEM shuffle): `sub64/*`
 holds the same gradient elements from that run, so a test can tell fp32 summation noise (how far the reference's own fp32
 gradients sit from the fp64 ones) from an arithmetic difference.
 
-Run:  python tests/golden/make_golden_train.py      (needs /root/reference; writes tests/golden/g20_train_*.npz)
+G23: the G21 step on flat content (speinet_amd.synth.synth_frames_flat), where the gates' row / column maxima tie.
+
+Run:  python tests/golden/make_golden_train.py [swint] [speinet] [curve] [flat]     (needs the reference; writes tests/golden/g2*_*.npz)
 """
 import importlib.util
 import os
@@ -54,7 +57,7 @@ class DropPath(torch.nn.Module):
         return x * rt
 
 
-def run_case(name, build, x, gt, hem_mod, seed):
+def run_case(name, build, x, gt, hem_mod, seed, stride=STRIDE, packed=False):
     """One training step of `build()` in fp32 (recorded DropPath draws) and again in float64 (replayed draws); writes the fixture."""
     torch.manual_seed(0)
     net = build()
@@ -72,7 +75,7 @@ def run_case(name, build, x, gt, hem_mod, seed):
     loss.backward()
     res = {"seed": seed, "b": x.shape[0], "h": x.shape[-2], "w": x.shape[-1], "out": out.detach().numpy(), "loss": loss.item(),
            "l1": l1.item(), "hem": lh.item(), "draws": np.stack([np.pad(d.numpy(), (0, x.shape[0] - d.numel())) for d in DRAWS]),
-           "draw_len": np.asarray([d.numel() for d in DRAWS])}
+           "draw_len": np.asarray([d.numel() for d in DRAWS]), "stride": stride}
     n, unused = 0, []
     for k, p in net.named_parameters():
         if p.grad is None:
@@ -80,13 +83,13 @@ def run_case(name, build, x, gt, hem_mod, seed):
             continue
         g = p.grad.reshape(-1)
         res["norm/" + k] = g.norm().item()
-        res["sub/" + k] = g[::STRIDE].clone().numpy()
+        res["sub/" + k] = g[::stride].clone().numpy()
         n += 1
     res["unused"] = np.asarray(unused)
     opt.step()
     for i, (k, p) in enumerate(net.named_parameters()):
         if i % 25 == 0:
-            res["adam/" + k] = p.detach().reshape(-1)[::STRIDE].clone().numpy()
+            res["adam/" + k] = p.detach().reshape(-1)[::stride].clone().numpy()
     for k, v in net.state_dict().items():
         if "running_" in k or "num_batches_tracked" in k:
             res["bn/" + k] = v.clone().numpy()
@@ -116,8 +119,11 @@ def run_case(name, build, x, gt, hem_mod, seed):
             continue
         g = p.grad.reshape(-1)
         res["norm64/" + k] = g.norm().item()
-        res["sub64/" + k] = g[::STRIDE].clone().numpy().astype(np.float32)
+        res["sub64/" + k] = g[::stride].clone().numpy().astype(np.float32)
         worst = max(worst, float(np.linalg.norm(res["sub/" + k] - res["sub64/" + k]) / max(res["norm64/" + k], 1e-12)))
+    if packed:
+        from oracle.fixtures import pack_train_fixture
+        res = pack_train_fixture(res)
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **res)
     print(f"{name}: loss {loss.item():.6f} (L1 {l1.item():.6f}, HEM {lh.item():.6f}), {n} parameter gradients ({len(unused)} parameters unused), "
           f"{len(DRAWS)} DropPath draws, {os.path.getsize(os.path.join(HERE, name + '.npz')) / 1024:.0f} KB; float64 re-run: loss {loss64.item():.8f}, "
@@ -134,7 +140,7 @@ def main():
     hem_mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(hem_mod)
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["swint", "speinet", "curve"]
+    which = sys.argv[1:] or ["swint", "speinet", "curve", "flat"]
     if "swint" in which:
         for name, seed, n_seq, b, h, w in (("g20_train_swint_40x40", 201, 3, 2, 40, 40), ("g20_train_swint_n1_40x60", 202, 1, 1, 40, 60)):
             args = template_args()
@@ -214,6 +220,20 @@ def main():
             x = synth_frames(b, h, w, seed=seed, zero_ref=zero).contiguous()
             gt = synth_frames(b, h, w, seed=seed + 500)[:, 1].contiguous()
             run_case(name, build, x, gt, hem_mod, seed)
+    if "flat" in which:
+        # G23: the G21 step on flat content (synth_frames_flat: letterbox bars, a clipped highlight, sample 0 faded to near-black,
+        # sample 1 without a reference): feature maps with exact ties at the gates' row / column maxima
+        from speinet_amd.synth import synth_frames_flat
+        for name, seed, b, h, w, zero in (("g23_train_speinet_flat_40x40", 231, 3, 40, 40, (1,)),):
+            args = template_args()
+
+            def build():
+                net = ms.SPEINet(in_channels=3, n_sequence=3, out_channels=3, n_resblock=3, n_feat=32, device="cpu", args=args)
+                net.load_state_dict(synth_state_dict(net.state_dict(), seed=0), strict=True)
+                return net
+            x = synth_frames_flat(b, h, w, seed=seed, zero_ref=zero).contiguous()
+            gt = synth_frames_flat(b, h, w, seed=seed + 500)[:, 1].contiguous()
+            run_case(name, build, x, gt, hem_mod, seed, stride=997, packed=True)
 
 
 if __name__ == "__main__":

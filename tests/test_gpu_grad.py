@@ -315,3 +315,294 @@ def test_encoder_gradients_vs_reference(golden_dir, synth_sd, name, h, w):
           + ", ".join(f"{k[11:]} {e:.1e}" for e, k in sorted(errs, reverse=True)[:6]))
     loss2, grads2 = run()
     assert loss2 == loss and all(torch.equal(grads[k], grads2[k]) for k in grads), "gradients are not bitwise reproducible"
+
+
+# ---- ZPool ties: the gated sum's backward on planes with exact ties at the row / column maxima ---------------------------------------
+# torch.max(dim) hands the gradient of a maximum to ONE element, the first maximal index (lowest x of a row, lowest y of a column);
+# flat content (letterbox bars, clipped highlights, fades to black) gives x1 planes with many bit-identical maxima.
+def _tie_planes(b, h, w, c, seed):
+    """x1 [b, h, w, c] float32 with exact ties built in, channel pattern (c + sample) % 8: 0 whole constant rows (k = W, and ties down
+    the columns), 1 whole constant columns (k = H), 2 a constant rectangle above everything else (row AND column maxima), 3 the same
+    rectangle below everything (ties, none at a maximum), 4 two equal row maxima at xa < xb (different 16-wide tiles when W > 70),
+    5 equal row maxima at x = 0 and x = W-1, 6 two equal column maxima at ya < yb, 7 at y = 0 and y = H-1.  Channels with
+    (c // 8) odd are shifted by -20: all-negative planes with the same ties.  Returns x1 and the checks (pattern -> mask of the
+    lines that must hold a tie at their maximum)."""
+    r = np.random.RandomState(seed)
+    x1 = r.randn(b, h, w, c).astype(np.float32)
+    xa, xb = (10, 70) if w > 70 else (1, w - 3)
+    ya, yb = (10, 70) if h > 70 else (1, h - 3)
+    r0, r1, q0, q1 = h // 4, max(h // 2, h // 4 + 2), w // 3, max(2 * w // 3, w // 3 + 2)
+    for bi in range(b):
+        for ch in range(c):
+            p = x1[bi, :, :, ch]
+            k = (ch + bi) % 8
+            if k == 0:
+                p[1::4, :] = 6.0
+            elif k == 1:
+                p[:, 2::5] = 6.0
+            elif k == 2:
+                p[r0:r1, q0:q1] = 6.0
+            elif k == 3:
+                p[r0:r1, q0:q1] = -6.0
+            elif k in (4, 5):
+                m = (6.0 + r.rand(h)).astype(np.float32)
+                p[:, xa if k == 4 else 0] = m
+                p[:, xb if k == 4 else w - 1] = m
+            else:
+                m = (6.0 + r.rand(w)).astype(np.float32)
+                p[ya if k == 6 else 0, :] = m
+                p[yb if k == 6 else h - 1, :] = m
+            if (ch // 8) % 2 == 1:
+                p -= np.float32(20.0)
+    return torch.from_numpy(x1), (xa, xb, ya, yb)
+
+
+def _assert_ties(x1, pos):
+    """Every constructed tie is present in x1 (so the test cannot pass on planes without them): per pattern, the lines whose maximum
+    is shared."""
+    b, h, w, c = x1.shape
+    xa, xb, ya, yb = pos
+    rmax, cmax = x1.amax(dim=2), x1.amax(dim=1)                   # [b, h, c], [b, w, c]
+    rk, ck = (x1 == rmax[:, :, None]).sum(2), (x1 == cmax[:, None]).sum(1)   # number of maxima per row / per column
+    n = 0
+    for bi in range(b):
+        for ch in range(c):
+            k = (ch + bi) % 8
+            if k == 0:
+                assert (rk[bi, 1::4, ch] == w).all() and (ck[bi, :, ch] == len(range(1, h, 4))).all(), (bi, ch)
+            elif k == 1:
+                assert (ck[bi, 2::5, ch] == h).all() and (rk[bi, :, ch] == len(range(2, w, 5))).all(), (bi, ch)
+            elif k == 2:
+                r0, r1, q0, q1 = h // 4, max(h // 2, h // 4 + 2), w // 3, max(2 * w // 3, w // 3 + 2)
+                assert (rk[bi, r0:r1, ch] == q1 - q0).all() and (ck[bi, q0:q1, ch] == r1 - r0).all(), (bi, ch)
+            elif k == 3:
+                assert (rk[bi, :, ch] == 1).all() and (ck[bi, :, ch] == 1).all(), (bi, ch)
+            elif k in (4, 5):
+                a, z = (xa, xb) if k == 4 else (0, w - 1)
+                assert (x1[bi, :, a, ch] == rmax[bi, :, ch]).all() and (x1[bi, :, z, ch] == rmax[bi, :, ch]).all() and (rk[bi, :, ch] == 2).all()
+            else:
+                a, z = (ya, yb) if k == 6 else (0, h - 1)
+                assert (x1[bi, a, :, ch] == cmax[bi, :, ch]).all() and (x1[bi, z, :, ch] == cmax[bi, :, ch]).all() and (ck[bi, :, ch] == 2).all()
+            n += 1
+    assert n == b * c and (x1[..., 8:16] < 0).all()
+    return int((rk > 1).sum()), int((ck > 1).sum())
+
+
+def _gate_params(c, seed):
+    g = torch.Generator().manual_seed(seed)
+    rn = lambda *s, sc=1.0: torch.randn(*s, generator=g) * sc
+    r = c // 4
+    return [rn(r, c, sc=0.2), rn(r, sc=0.1), rn(c, r, sc=0.3), rn(c, sc=0.1), rn(1, 2, 7, 7, sc=0.15), rn(1).abs() + 0.5, rn(1, sc=0.1),
+            rn(1, sc=0.1), rn(1).abs() + 0.7, rn(1, 2, 5, 5, sc=0.2), rn(1).abs() + 0.5, rn(1, sc=0.1), rn(1, sc=0.1), rn(1).abs() + 0.6]
+
+
+def _gated_sum_torch(x, x1, prm, groups, bn_train):
+    """float64 statement of the gated sum on [B, H, W, C] maps: ZPool by torch.max(dim)[0] (first maximal index gets the gradient)."""
+    stats = [x1.max(dim=2)[0], x1.mean(dim=2), x1.max(dim=1)[0], x1.mean(dim=1), x1.mean(dim=(1, 2))]
+    bs = x1.shape[0] // groups
+    outs = [[], [], []]
+    for gi in range(groups):
+        sl = slice(gi * bs, (gi + 1) * bs)
+        o = gate_maps_torch(*[t[sl] for t in stats], prm, bn_train, update_running=bn_train)
+        for k in range(3):
+            outs[k].append(o[k])
+    s, g1, g2 = (torch.cat(o) for o in outs)
+    return x + x1 * (s[:, None, None, :] + g1[:, :, None, :] + g2[:, None, :, :]), stats, (s, g1, g2)
+
+
+TIE_CASES = [(32, 37, 130, 2, 1), (64, 130, 23, 3, 1), (128, 19, 29, 4, 2), (32, 200, 200, 2, 1), (64, 45, 75, 6, 3), (128, 75, 130, 2, 2)]
+
+
+@pytest.mark.parametrize("bn_train", [True, False])
+@pytest.mark.parametrize("c,h,w,b,groups", TIE_CASES)
+def test_gated_sum_backward_with_tied_maxima(c, h, w, b, groups, bn_train):
+    """train._GatedSum (spei_plane_stats_batched -> spei_gate_maps_fwd / _bwd -> spei_resblock_apply_bwd_batched) on x1 planes with
+    exact ties at the row and column maxima (_tie_planes), x1 a leaf so both sides see the same values and the same ties: output,
+    dx, dx1, every gate-parameter gradient and the running buffers against float64 autograd of the reference's statement, whose
+    ZPool is torch.max(dim)[0].  The gradient of a tied maximum belongs to the FIRST maximal element; handing it to every tied
+    element multiplies it by the number of ties (W on a constant row)."""
+    x1, pos = _tie_planes(b, h, w, c, seed=c + h + w)
+    nr, nc = _assert_ties(x1, pos)
+    x = rnd(300 + c, b, h, w, c)
+    dout = rnd(400 + c, b, h, w, c)
+    prm = _gate_params(c, c * 10 + w)
+    # float64
+    x64, x164 = x.double().requires_grad_(True), x1.double().requires_grad_(True)
+    p64 = [t.double().requires_grad_(i not in (7, 8, 12, 13)) for i, t in enumerate(prm)]
+    out64 = _gated_sum_torch(x64, x164, p64, groups, bn_train)[0]
+    leaves = [x64, x164] + [t for t in p64 if t.requires_grad]
+    grads = torch.autograd.grad(out64, leaves, dout.double())
+    # HIP
+    flat = lambda t: t.reshape(-1, c).contiguous().to(DEV)
+    xg, x1g = flat(x).requires_grad_(True), flat(x1).requires_grad_(True)
+    pd = [t.clone().to(DEV).requires_grad_(i not in (7, 8, 12, 13)) for i, t in enumerate(prm)]
+    out = T._GatedSum.apply(xg, x1g, b, h, w, bn_train, groups, *pd)
+    assert rel(out, out64.detach().reshape(-1, c)) < 2e-6, "output"
+    out.backward(flat(dout))
+    assert torch.equal(xg.grad.cpu(), dout.reshape(-1, c)), "dx"
+    e_dx1 = rel(x1g.grad, grads[1].reshape(-1, c))
+    errs = [e_dx1]
+    names = ("se_w1", "se_b1", "se_w2", "se_b2", "cw_w", "cw_g", "cw_b", "hc_w", "hc_g", "hc_b")
+    gp = grads[2:]
+    gscale = max(gq.norm().item() for gq in gp)
+    got_p = [t.grad for i, t in enumerate(pd) if i not in (7, 8, 12, 13)]
+    for got, ref, nm in zip(got_p, gp, names):
+        e = (got.cpu().double() - ref).norm().item() / max(ref.norm().item(), 1e-3 * gscale)
+        errs.append(e)
+        assert e < 2e-5, (nm, e)
+    for i in (7, 8, 12, 13):
+        assert (pd[i].detach().cpu() - p64[i].detach().float()).abs().max().item() < 1e-6, i
+    print(f"C={c} {h}x{w} B={b} groups={groups} bn_train={bn_train}: {nr} rows / {nc} columns with tied maxima; dx1 {e_dx1:.1e} "
+          f"(bound 5e-6), worst parameter gradient {max(errs[1:]):.1e} (bound 2e-5)")
+    assert e_dx1 < 5e-6, ("dx1", e_dx1)
+
+
+@pytest.mark.parametrize("c,h,w", [(32, 37, 130), (64, 130, 23), (128, 75, 130), (32, 200, 200)])
+def test_plane_stats_argmax_and_apply_bwd_single_map(c, h, w):
+    """The one-map entry points on tied planes: spei_plane_stats returns the maxima bit-exactly and their arg-max as torch.max(dim)
+    does (lowest x of a row, lowest y of a column — also when the equal maxima lie in different 16-wide tiles), and
+    spei_resblock_apply_bwd, given the float64 statement's gates and statistic gradients, returns its dx1."""
+    import ctypes as C
+    from speinet_amd import _lib
+    x1, pos = _tie_planes(1, h, w, c, seed=7 * c + h)
+    _assert_ties(x1, pos)
+    dout = rnd(500 + c, 1, h, w, c)
+    prm = _gate_params(c, c + 3 * h)
+    x164 = x1.double().requires_grad_(True)
+    p64 = [t.double() for t in prm]
+    out64, stats, gates = _gated_sum_torch(torch.zeros_like(x164), x164, p64, 1, False)
+    d_stats = torch.autograd.grad(out64, stats, dout.double(), retain_graph=True)
+    dx1_64 = torch.autograd.grad(out64, x164, dout.double())[0]
+    ctx = T._ctx(torch.device(DEV))
+    lib = _lib.lib()
+    P = lambda t: T._p(ctx, t)
+    dv = lambda t: t.float().contiguous().to(DEV)
+    a = dv(x1.reshape(-1, c))
+    rowmax, rowmean, colmax, colmean, mean = (torch.empty(n, c, device=DEV) for n in (h, h, w, w, 1))
+    rowarg, colarg = torch.full((h, c), -1, dtype=torch.int32, device=DEV), torch.full((w, c), -1, dtype=torch.int32, device=DEV)
+    ws = torch.empty(lib.spei_plane_ws_floats(h, w, c), device=DEV)
+    with torch.cuda.device(DEV):
+        _lib.check(lib.spei_plane_stats(P(a), T._NULL, 0, h, w, c, P(rowmax), T._pi(ctx, rowarg), P(rowmean), P(colmax), T._pi(ctx, colarg),
+                                        P(colmean), P(mean), P(ws), ctx._stream()), "spei_plane_stats")
+        ref_rm, ref_ra = x1[0].max(dim=1)                       # [h, c] over x
+        ref_cm, ref_ca = x1[0].max(dim=0)                       # [w, c] over y
+        assert torch.equal(rowmax.cpu(), ref_rm) and torch.equal(colmax.cpu(), ref_cm), "maxima"
+        bad_r, bad_c = int((rowarg.cpu() != ref_ra).sum()), int((colarg.cpu() != ref_ca).sum())
+        assert bad_r == 0 and bad_c == 0, f"{bad_r} row / {bad_c} column arg-maxima differ from torch's first index"
+        assert rel(rowmean, x1[0].double().mean(1)) < 1e-6 and rel(colmean, x1[0].double().mean(0)) < 1e-6
+        s, g1, g2 = (dv(t.detach()[0]) for t in gates)
+        dd = [dv(t[0]) for t in d_stats]
+        dx1 = torch.empty_like(a)
+        _lib.check(lib.spei_resblock_apply_bwd(P(dv(dout.reshape(-1, c))), P(s), P(g1), P(g2), T._pi(ctx, rowarg), T._pi(ctx, colarg),
+                                               *[P(t) for t in dd], P(dx1), h, w, c, ctx._stream()), "spei_resblock_apply_bwd")
+    e = rel(dx1, dx1_64.reshape(-1, c))
+    print(f"C={c} {h}x{w}: arg-maxima exact; dx1 {e:.1e} (bound 5e-6)")
+    assert e < 5e-6, e
+
+
+def _flat_frame(kind, h, w):
+    """One [1, 3, h, w] frame of flat content: 'letterbox' (black bars of h // 4 rows at the top and bottom) or 'highlight' (clipped
+    at 1.0 in all channels: a blown-out band over the top h // 4 rows and a disc), over a synth_frames field."""
+    f = synth_frames(1, h, w, seed=61)[0, 1].clone()
+    if kind == "letterbox":
+        f[:, :h // 4] = 0.0
+        f[:, h - h // 4:] = 0.0
+    else:
+        yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+        f[:, (yy - 0.6 * h) ** 2 + (xx - 0.55 * w) ** 2 < (0.25 * min(h, w)) ** 2] = 1.0
+        f[:, :h // 4] = 1.0
+    return f[None]
+
+
+@pytest.mark.parametrize("kind,h,w", [("letterbox", 40, 60), ("highlight", 37, 53), ("letterbox", 64, 130)])
+def test_resblock_backward_flat_content_vs_torch(synth_sd, kind, h, w):
+    """The ResBlock of test_resblock_backward_vs_torch (inBlock.1, 32 channels, eval-mode gates) on conv_in features of flat content,
+    where whole rows / columns of x1 are bit-identical.  The float64 statement takes the HIP forward's decisions, as
+    test_conv_forward_backward does: its ReLU mask, and its ZPool arg-max — the FIRST exact maximum of HIP's fp32 x1 of each row /
+    column, taken with gather — so only the arithmetic is compared, at the f32 bounds 1e-5 / 5e-5 / 1e-4."""
+    net = SPEINet(args=default_args())
+    net.load_state_dict(synth_sd, strict=True)
+    rn = net.recons_net.to(DEV)
+    blk = rn.inBlock[1]
+    c = 32
+    with torch.no_grad():
+        x = T._ConvIn.apply(_flat_frame(kind, h, w).to(DEV), rn.inBlock[0][0].weight, rn.inBlock[0][0].bias)
+        t_h = T._Conv2d.apply(x, blk.main[0].main[0].weight, blk.main[0].main[0].bias, None, 1, h, w, 5, 1, True)
+        x1_h = T._Conv2d.apply(t_h, blk.main[1].main[0].weight, blk.main[1].main[0].bias, None, 1, h, w, 5, 1, False)
+    x1_h = x1_h.cpu().view(1, h, w, c)
+    mask = (t_h.cpu() > 0).view(1, h, w, c).permute(0, 3, 1, 2)
+    ridx, cidx = x1_h.max(dim=2)[1], x1_h.max(dim=1)[1]                # first exact maxima: [1, h, c] over x, [1, w, c] over y
+    ties_r = int(((x1_h == x1_h.amax(dim=2, keepdim=True)).sum(2) > 1).sum())
+    ties_c = int(((x1_h == x1_h.amax(dim=1, keepdim=True)).sum(1) > 1).sum())
+    assert ties_r + ties_c > 0, "no tied maxima in HIP's x1: the case does not test ties"
+    # float64 statement with HIP's decisions
+    sd = {k: v.detach().cpu().double().requires_grad_(v.requires_grad) for k, v in
+          list(blk.named_parameters()) + [(k, b) for k, b in blk.named_buffers() if "running_" in k]}
+    xd = x.cpu().double().view(1, h, w, c).permute(0, 3, 1, 2).requires_grad_(True)
+    t = F.conv2d(xd, sd["main.0.main.0.weight"], sd["main.0.main.0.bias"], padding=2) * mask
+    x1 = F.conv2d(t, sd["main.1.main.0.weight"], sd["main.1.main.0.bias"], padding=2).permute(0, 2, 3, 1)   # [1, h, w, c]
+    stats = [x1.gather(2, ridx[:, :, None, :]).squeeze(2), x1.mean(dim=2), x1.gather(1, cidx[:, None]).squeeze(1), x1.mean(dim=1),
+             x1.mean(dim=(1, 2))]
+    names = ("se.fc.0.weight", "se.fc.0.bias", "se.fc.2.weight", "se.fc.2.bias", "te.cw.conv.conv.weight", "te.cw.conv.bn.weight",
+             "te.cw.conv.bn.bias", "te.cw.conv.bn.running_mean", "te.cw.conv.bn.running_var", "te.hc.conv.conv.weight",
+             "te.hc.conv.bn.weight", "te.hc.conv.bn.bias", "te.hc.conv.bn.running_mean", "te.hc.conv.bn.running_var")
+    s, g1, g2 = gate_maps_torch(*stats, [sd[k].reshape(-1) if "running_" in k else sd[k] for k in names], False, False)
+    out_ref = xd.permute(0, 2, 3, 1) + x1 * (s[:, None, None, :] + g1[:, :, None, :] + g2[:, None, :, :])
+    g = rnd(70 + h, 1, h, w, c)
+    out_ref.backward(g.double())
+    # HIP
+    xg = x.detach().clone().requires_grad_(True)
+    out = T.resblock(xg, blk, 1, h, w, False)
+    eo = rel(out, out_ref.detach().reshape(-1, c))
+    out.backward(g.reshape(-1, c).to(DEV))
+    ed = rel(xg.grad, xd.grad.permute(0, 2, 3, 1).reshape(-1, c))
+    ep = {k: rel(p.grad, sd[k].grad) for k, p in blk.named_parameters()}
+    worst = max(ep.items(), key=lambda kv: kv[1])
+    print(f"{kind} {h}x{w}: x1 rows / columns with tied maxima {ties_r} / {ties_c}; output {eo:.1e} (1e-5), data gradient {ed:.1e} (5e-5), "
+          f"worst parameter gradient {worst[1]:.1e} ({worst[0]}, 1e-4)")
+    assert eo < 1e-5 and ed < 5e-5, (eo, ed)
+    for k, e in ep.items():
+        assert e < 1e-4, (k, e)
+
+
+@pytest.mark.parametrize("content", ["natural", "flat"])
+def test_encoder_groups_equal_separate_passes(synth_sd, content):
+    """train.encoder(frames, groups=n) — n encoder passes of the reference in ONE set of launches, BatchNorm(1) statistics of the
+    gates per group — against n separate train.encoder calls on a second copy of the model: the pyramid outputs, every parameter
+    gradient and every BatchNorm running buffer within 1e-6 (train-mode gates, where the groups matter)."""
+    from speinet_amd.synth import synth_frames_flat
+    n, bs, h, w = 3, 2, 24, 36
+    frames = (synth_frames(n * bs, h, w, seed=81) if content == "natural" else synth_frames_flat(n * bs, h, w, seed=82))[:, 1].contiguous().to(DEV)
+    nets = []
+    for _ in range(2):
+        net = SPEINet(args=default_args())
+        net.load_state_dict(synth_sd, strict=True)
+        nets.append(net.to(DEV).train())
+    g = torch.Generator().manual_seed(83)
+    r = [torch.randn(n * bs * hh * ww, cc, generator=g).to(DEV) for cc, hh, ww in ((32, h, w), (64, h // 2, w // 2), (128, h // 4, w // 4))]
+
+    def loss_of(levels):
+        return sum((lv * rr).sum() * 0.5 ** i for i, (lv, rr) in enumerate(zip(levels, r)))
+
+    lv_g = T.encoder(frames, nets[0].recons_net, True, pyramid=True, groups=n)
+    loss_of(lv_g).backward()
+    per = [T.encoder(frames[i * bs:(i + 1) * bs], nets[1].recons_net, True, pyramid=True) for i in range(n)]
+    lv_s = [torch.cat([p[k].view(bs, -1, p[k].shape[1]) for p in per]).view(-1, per[0][k].shape[1]) for k in range(3)]
+    loss_of(lv_s).backward()
+    eo = max(rel(a, b.detach().cpu()) for a, b in zip(lv_g, lv_s))
+    pa, pb = dict(nets[0].recons_net.named_parameters()), dict(nets[1].recons_net.named_parameters())
+    errs = []
+    for k, p in pa.items():
+        if p.grad is None:
+            assert pb[k].grad is None, k
+            continue
+        scale = pb[k].grad.norm().item()
+        if ".bn." in k:                                   # a one-number, cancelling sum: against its gate's convolution weight
+            scale = max(scale, pb[k.rsplit(".bn.", 1)[0] + ".conv.weight"].grad.norm().item())
+        errs.append(((p.grad - pb[k].grad).norm().item() / max(scale, 1e-30), k))
+    ba, bb = dict(nets[0].recons_net.named_buffers()), dict(nets[1].recons_net.named_buffers())
+    eb = max((ba[k].double() - bb[k].double()).abs().max().item() / max(1.0, bb[k].double().abs().max().item()) for k in ba)
+    worst = max(errs)
+    print(f"{content}: encoder groups={n} vs {n} passes: outputs {eo:.1e}, {len(errs)} gradients worst {worst[0]:.1e} ({worst[1]}), "
+          f"running buffers {eb:.1e}")
+    assert len(errs) == 132 and eo < 1e-6 and worst[0] < 1e-6 and eb < 1e-6, (eo, worst, eb)

@@ -243,9 +243,10 @@ def test_window_attention_bf16_contract(shift):
         _check(what, rr[i] + (got["bf16"][i].detach().double().cpu() - rr[i]).sign() * d, rr[i], re[i], got["f32"][i], bound=ATTN)
 
 
-def _net(which, b, h, w, seed_x):
+def _net(which, b, h, w, seed_x, content="smooth"):
     from speinet_amd.speinet import default_args
-    from speinet_amd.synth import synth_frames, synth_state_dict
+    from speinet_amd.synth import synth_frames as smooth_frames, synth_frames_flat, synth_state_dict
+    synth_frames = smooth_frames if content == "smooth" else synth_frames_flat
     from speinet_amd import train as T
     args = default_args()
     args.n_sequence = 3
@@ -274,8 +275,9 @@ def _step(net, x, gt, scales, loss_fn, prec):
     return out.detach().clone(), loss.item(), {k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None}
 
 
-@pytest.mark.parametrize("which", ["swint", "speinet"])
-def test_training_step_bf16_vs_f32(which):
+@pytest.mark.parametrize("which,content", [pytest.param("swint", "smooth", id="swint"), pytest.param("speinet", "smooth", id="speinet"),
+                                           pytest.param("speinet", "flat", id="speinet-flat")])
+def test_training_step_bf16_vs_f32(which, content):
     """The bf16 step against the f32 step on the batch of test_training_step_bf16x3_vs_f32 (B = 3 at 60x40, the full model's last
     sample reference-less, the same DropPath factors and HEM seed).  Output within 1.5e-2 of its range (the inference bf16 bound),
     loss within 5e-3 relative.  Gradients, relative L2 per parameter: median <= 1.2e-1, worst <= 3e-1.
@@ -286,11 +288,12 @@ def test_training_step_bf16_vs_f32(which):
     activations again, and swint's gradient crosses the encoder, 2 x 6 Swin blocks and the decoder, so the parameters far from the
     loss sit furthest from the f32 gradient (outBlock 1.5e-2, encoder / Swin 8e-2 to 9e-2); the largest are the relative-position
     bias tables, sums of dS over every window, where P (dP - r_q) cancels.  bf16x3 (2^-16 products) measures 2.7e-3 / 8e-3 on the
-    same batch.  Bounds: measured x 1.5."""
+    same batch.  Bounds: measured x 1.5.  content "flat": the full model on synth_frames_flat (letterbox bars, a clipped highlight,
+    one sample faded to near-black: tied maxima in the gates, which use the same kernels in both modes), under the same bounds."""
     from speinet_amd.loss import Loss
     from speinet_amd.synth import synth_frames
     b, h, w = 3, 60, 40
-    net, x, scales = _net(which, b, h, w, 91 if which == "swint" else 92)
+    net, x, scales = _net(which, b, h, w, 91 if which == "swint" else 92, content)
     gt = synth_frames(b, h, w, seed=93)[:, 1].contiguous().to(DEV)
     loss_fn = Loss("1*L1+2*HEM", device=DEV)
     o32, l32, g32 = _step(net, x, gt, scales, loss_fn, "f32")

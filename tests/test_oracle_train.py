@@ -65,16 +65,29 @@ def test_oracle_train_mode_vs_reference_training_step(golden_dir):
 def test_oracle_train_mode_full_model_vs_reference(golden_dir):
     """The same for `model/speinet.py` (G21: three 40x40 windows, the second without a reference): SearchTransfer's max / gather and
     SelfTransfer under autograd, the cross-scale decoder, BatchNorm statistics per routing class — float64 against float64."""
+    _full_model_pin(golden_dir, "g21_train_speinet_40x40", synth_frames)
+
+
+def test_oracle_train_mode_full_model_flat_vs_reference(golden_dir):
+    """G23: the same step on flat content (synth_frames_flat: letterbox bars, a clipped highlight, one sample faded to near-black),
+    whose feature maps tie at the gates' row / column maxima — the float64 gradients of the reference, where torch.max(dim) gives
+    each tied maximum's gradient to its first index, and of the restatement agree as on G21."""
+    from speinet_amd.synth import synth_frames_flat
+    _full_model_pin(golden_dir, "g23_train_speinet_flat_40x40", synth_frames_flat)
+
+
+def _full_model_pin(golden_dir, name, frames):
+    from oracle.fixtures import load_train_fixture
     torch.set_num_threads(8)
-    d = np.load(os.path.join(golden_dir, "g21_train_speinet_40x40.npz"))
+    d = load_train_fixture(os.path.join(golden_dir, name + ".npz"))
     seed, b, h, w = (int(d[k]) for k in ("seed", "b", "h", "w"))
     from speinet_amd.speinet import SPEINet, default_args
     from speinet_amd.train import drop_path_rates
     net = SPEINet(args=default_args())
     sd = {k: (v.double() if v.is_floating_point() else v) for k, v in synth_state_dict(net.state_dict(), seed=0).items()}
     cfg = O.Cfg(n_sequence=3)
-    x = synth_frames(b, h, w, seed=seed, zero_ref=(1,)).contiguous().double()
-    gt = synth_frames(b, h, w, seed=seed + 500)[:, 1].contiguous().double()
+    x = frames(b, h, w, seed=seed, zero_ref=(1,)).contiguous().double()
+    gt = frames(b, h, w, seed=seed + 500)[:, 1].contiguous().double()
     it = iter(zip(d["draws"], d["draw_len"]))
     calls = []
     for _ in range(4):                                   # 2 swin calls of the no-reference sub-batch (1 sample), then 2 of the other (2)
@@ -93,12 +106,13 @@ def test_oracle_train_mode_full_model_vs_reference(golden_dir):
     assert abs(loss - float(d["loss64"])) < 1e-7
     gmax = max(float(d[k]) for k in d.files if k.startswith("norm64/"))
     worst = (0.0, "")
+    st = int(d["stride"]) if "stride" in d.files else 97          # the fixture's gradient subsample stride
     for k in (f[7:] for f in d.files if f.startswith("norm64/")):
         g = grads[k].reshape(-1)
         scale = max(float(d["norm64/" + k]), 1e-5 * gmax)
-        e = max((g[::97].float() - torch.from_numpy(d["sub64/" + k])).norm().item(), abs(g.norm().item() - float(d["norm64/" + k]))) / scale
+        e = max((g[::st].float() - torch.from_numpy(d["sub64/" + k])).norm().item(), abs(g.norm().item() - float(d["norm64/" + k]))) / scale
         worst = max(worst, (e, k))
     params = {k for k, _ in net.named_parameters()}
     assert set(str(u) for u in d["unused"]) == {k for k in params if k not in grads}          # search23, connect, SearchTransfer's convs
-    print(f"oracle (float64) full-model training gradients vs the reference's float64 run: worst deviation {worst[0]:.1e} ({worst[1]})")
+    print(f"{name}: oracle (float64) full-model training gradients vs the reference's float64 run: worst deviation {worst[0]:.1e} ({worst[1]})")
     assert worst[0] < 1e-4          # (the 1e-8 prior difference above, amplified on the cancelling BatchNorm scalars: 1.4e-5 measured)
