@@ -16,10 +16,15 @@ pipe BASELINE.json names, 11-bit instead of 8-bit significands) with the exact r
 output stays within 1e-3 dB PSNR of the reference (tests/test_gpu_bf16.py asserts it against the reference's own 720p
 outputs).  `--precision bf16` is configs[1] to the letter (3e-3 dB).
 
+A plain run sets up, warms up, times the K steps, dumps the outputs if asked and prints its line: everything in it comes from
+the timed region itself.  `--full` adds every measurement that needs runs of its own (marked [full] below; each still obeys its
+--no-* / --cpu-baseline option): `reference_call`, `roofline.families`, `bf16_letter`, `f32_grade`, `harness`, `train` and
+`cpu_baseline`, about a minute and a half more.
+
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   value / ms_per_step   wall clock of K timed steps (barrier + synchronize on both sides, MAX over ranks); the timed call
-                 passes `routing=` (the caller knows whether frame 3 is zero; no host sync).  `reference_call` times the same K
-                 steps as the reference calls it, `forward(x)`: the routing test runs on the device and syncs once per call.
+                 passes `routing=` (the caller knows whether frame 3 is zero; no host sync).  [full] `reference_call` times the same
+                 K steps as the reference calls it, `forward(x)`: the routing test runs on the device and syncs once per call.
   step_ms        median / p10 / p90 of the K per-step GPU durations (HIP events on the launch stream; with K <= --inflight no
                  same-stream pair exists and it holds the wall-clock ms_per_step alone)
   --dump-outputs DIR   writes what the LAST timed step returned to its caller (rank 0: the [B,3,H,W] frames) as DIR/output.npy,
@@ -35,15 +40,17 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                  (F = 20.64 TFLOP) against the same peak.  `traffic` / `path_hbm_bytes_per_frame`: HBM bytes from
                  rocprofv3 PMC passes made OFFLINE with tools/pmc_traffic.py (FETCH_SIZE doubled as the guide prescribes for
                  wide coalesced reads on gfx950) and read from profiles/ — `traffic_source` names the file, null if absent.
+                 [full] `families`: kernel time per family from 3 eager single-stream frames after the timed region; the
+                 top-level fields then describe the family with the most kernel time (null in a plain run).
   --train        a second measurement, BASELINE.json configs[4] (trainer/trainer_swint.py on 200x200 crops, option/template.py:6-22):
                  `python bench.py --train [--model swint|speinet] [--batch 20] [--steps 5] [--warmup 2] [--cpu-baseline]` prints ONE
                  JSON line of its own — training crops/s (forward in train() mode, 1*L1+2*HEM, backward, Adam; N ranks under
                  torch.distributed.run average gradients over RCCL, weak scaling), the per-phase split by HIP events, and with
                  --cpu-baseline the oracle's train-mode graph under torch autograd on the host cores (2 crops)
-  harness        (N = 1, unless --no-harness) end-to-end frames/s of the inference harness (speinet_amd.inference, the counterpart of
+  harness        [full] (N = 1, unless --no-harness) end-to-end frames/s of the inference harness (speinet_amd.inference, the counterpart of
                  inference_SPEINet.py) on a synthetic 720p clip ON DISK: PNG decode, selection, upload, forward with cross-window
                  encoder reuse, uint8, PSNR / SSIM, PNG encode — what a user of the reference's script gets per frame.
-  cpu_baseline   the oracle (CPU restatement of the reference, PyTorch fp32) timed on this host's cores, rank 0, N = 1: one untimed
+  cpu_baseline   [full] the oracle (CPU restatement of the reference, PyTorch fp32) timed on this host's cores, rank 0, N = 1: one untimed
                  and two timed 360x640 frames (threads, allocator, oneDNN primitives warm), then ONE 720p frame (the value).  Threads =
                  the physical cores of one socket, capped by the CPUs the process may use (affinity / cgroup quota); both numbers are
                  in the record.  If the probe predicts more than --cpu-budget seconds for the 720p frame the probe itself is
@@ -397,6 +404,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other measurement (reference_call, per-family kernel times, bf16 to the "
+                         "letter, f32-grade, harness, training step, CPU baseline), each unless its own option below skips it")
     ap.add_argument("--cpu-baseline", choices=["720p", "sample", "none"], default="720p")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="same as --cpu-baseline none")
     ap.add_argument("--cpu-budget", type=float, default=240.0, help="seconds the 720p oracle frame may take (else: extrapolated probe)")
@@ -416,9 +426,9 @@ def main():
                     help="frames in flight: consecutive steps alternate over this many launch streams (each its own captured graph instance), "
                          "so that the kernels of one frame fill the tails and launch gaps of the others (1: one frame at a time).  Round 4: three, "
                          "ungated (--gate none) — with the frame's Swin calls batched on one stream there is no second in-frame stream to fill the "
-                         "chip any more, and three free-running frames measured +2.8 % over round 3's two gated ones (same box)")
+                         "chip any more, and three free-running frames measured +2.8 %% over round 3's two gated ones (same box)")
     ap.add_argument("--no-families", action="store_true", help="skip the per-family kernel-time pass (3 eager frames with HIP events around every launch)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the bf16-to-the-letter and training sub-records of the default line")
+    ap.add_argument("--no-extras", action="store_true", help="skip the bf16-to-the-letter, f32-grade and training sub-records of the --full line")
     ap.add_argument("--free-overlap", action="store_true", help="(= --gate none, the default since round 4)")
     ap.add_argument("--gate", choices=["corr_end", "corr_start", "none"], default=None,
                     help="with --inflight > 1, when step i + 1 may start: after step i's correlation kernel (corr_end, round 3), when it starts "
@@ -520,16 +530,18 @@ def main():
         dumped = dump_outputs(args.dump_outputs, {"output": last_out}) if args.dump_outputs and rank == 0 else None
         del last_out
         checksum = sum(checksums)
-        # ---- the same steps the way the reference calls forward: no routing hint (device test + one host sync per call) ----
-        barrier()
-        t1 = time.perf_counter()
-        run_steps(args.steps)
-        barrier()
-        dt_ref_call = time.perf_counter() - t1
-        # ---- per-family kernel time: the same frames once more, eager on ONE stream with a HIP event pair around every launch of the
+        # ---- [full] the same steps the way the reference calls forward: no routing hint (device test + one host sync per call) ----
+        dt_ref_call = None
+        if args.full:
+            barrier()
+            t1 = time.perf_counter()
+            run_steps(args.steps)
+            barrier()
+            dt_ref_call = time.perf_counter() - t1
+        # ---- [full] per-family kernel time: the same frames once more, eager on ONE stream with a HIP event pair around every launch of the
         # conv / swin / correlation / streaming kernels (exclusive times: nothing overlaps; not part of the timed region) ----------------
         fam_prof, fam_frames = {"families": {}}, 0
-        if rank == 0 and not args.no_families:
+        if rank == 0 and args.full and not args.no_families:
             keep = (net.use_graph, net.streams)
             net.use_graph, net.streams = False, 1
             net(frames[0], routing=routing)                       # eager warm-up (allocator)
@@ -549,7 +561,7 @@ def main():
 
     from speinet_amd.dist import gather_metrics, max_over_ranks
     tmax = max_over_ranks(dt, dev, dist)
-    tmax_ref = max_over_ranks(dt_ref_call, dev, dist)
+    tmax_ref = max_over_ranks(dt_ref_call, dev, dist) if args.full else None
     # the only payload that crosses xGMI: one [checksum, frames] row per rank
     gathered = gather_metrics(torch.cat((checksum, torch.tensor([float(args.steps)], device=dev, dtype=torch.float64))), dist)
     assert torch.isfinite(gathered).all(), "non-finite output"
@@ -584,8 +596,6 @@ def main():
                                                                      "corr_start": " (step i + 1 starts with step i's correlation kernel)",
                                                                      "none": " on their own streams, ungated"}[gate_mode] if nfl > 1 else "")},
             "step_ms": {"median": statistics.median(step_ms), "p10": qs[0], "p90": qs[8], "min": min(step_ms), "max": max(step_ms)},
-            "reference_call": {"value": world * args.steps * nb / tmax_ref, "unit": "frames/s", "ms_per_step": 1e3 * tmax_ref / args.steps,
-                               "note": "forward(x) without the routing hint: the frame-3 test runs on the device, one host sync per call"},
             # the family with the most kernel time per frame; every family is in `families`, the correlation kernel —
             # the one launch per frame that can be bracketed live inside the timed region — keeps its own record
             "roofline": {**({"bound": families[top]["bound"], "kernel": f"{top} family: {families[top]['kernels']}",
@@ -614,7 +624,10 @@ def main():
         }
         if dumped is not None:
             line["dump_outputs"] = dumped
-        extras = world == 1 and not args.no_extras and (h, w) == (H, W) and args.precision == "f16" and nb == 1
+        if tmax_ref is not None:
+            line["reference_call"] = {"value": world * args.steps * nb / tmax_ref, "unit": "frames/s", "ms_per_step": 1e3 * tmax_ref / args.steps,
+                                      "note": "forward(x) without the routing hint: the frame-3 test runs on the device, one host sync per call"}
+        extras = args.full and world == 1 and not args.no_extras and (h, w) == (H, W) and args.precision == "f16" and nb == 1
         if extras:
             # BASELINE.json configs[1] to the letter ("bf16 forward"): the same steps with bf16 operands (8-bit significands: 3e-3 dB)
             net.precision = "bf16"
@@ -647,7 +660,7 @@ def main():
                                  "dtype": "bf16x3 (split products, f32-grade; correlation bf16x3)",
                                  "parity": "|dPSNR| vs the reference <= 1e-3 dB, max |err| < 1e-3 (tests/test_gpu_parity.py, test_gpu_bf16.py)"}
             net.precision, net.corr_precision = args.precision, args.corr_precision
-        if world == 1 and not args.no_harness and (h, w) == (H, W) and args.precision != "f32" and nb == 1:
+        if args.full and world == 1 and not args.no_harness and (h, w) == (H, W) and args.precision != "f32" and nb == 1:
             from speinet_amd.inference import harness_throughput
             del net, frames
             torch.cuda.empty_cache()
@@ -659,7 +672,7 @@ def main():
             tr = train_measure(["--batch", "20", "--steps", "3", "--warmup", "1"])
             line["train"] = {k: tr[k] for k in ("metric", "value", "unit", "batch_per_gpu", "patch", "ms_per_step", "ms", "dtype")}
         mode = "none" if args.no_cpu_baseline else args.cpu_baseline
-        if world == 1 and mode != "none":
+        if args.full and world == 1 and mode != "none":
             line["cpu_baseline"] = cpu_baseline(1234, mode, args.cpu_budget)
         print(json.dumps(line), flush=True)
     if dist is not None:
