@@ -191,15 +191,14 @@ int spei_attn_win4_16(int fmt, const float* x, float* out, const void* yhat, con
                       const void* wkv_frag, const float* bkv, const void* wproj_frag, const float* bproj,
                       const float* relbias, int batch, int H, int W, int shift, spei_stream_t stream);
 
-/* Harness post-processing of one deblurred frame (inference_SPEINet.py:477-482 tensor2numpy, :484-500 calc_PSNR, :502-543 calc_SSIM):
- * out_chw [3][H][W] fp32 (the model's output, unclamped) -> out_hwc [H][W][3] uint8 = round(clamp(255 x, 0, 255)) (half to even), and
- * result[0] = 1 if every value of out_chw was finite else 0, result[1] = PSNR, result[2] = SSIM of out_hwc against gt_hwc ([H][W][3]
- * uint8) on the region cropped by `border` pixels on every side (the reference crops 4).  PSNR from the exact integer squared error
- * (inf for identical frames); SSIM: 11x11 Gaussian window (sigma 1.5), valid region, float64 sums, mean over channels and positions.
- * ws: spei_frame_post_ws_doubles(H, W, border) doubles (-1: the cropped frame is smaller than the window). */
-int64_t spei_frame_post_ws_doubles(int H, int W, int border);
-int spei_frame_post(const float* out_chw, const unsigned char* gt_hwc, unsigned char* out_hwc, int H, int W, int border,
-                    double* ws, double* result, spei_stream_t stream);
+/* Harness metrics of one deblurred frame (inference_SPEINet.py:484-500 calc_PSNR, :502-543 calc_SSIM): result[0] = PSNR, result[1] =
+ * SSIM of out_hwc (the uint8 frame of spei_frame_u8_out) against gt_hwc, both [H][W][3] uint8, on the region cropped by `border` pixels
+ * on every side (the reference crops 4).  PSNR from the exact integer squared error (inf for identical frames); SSIM: 11x11 Gaussian
+ * window (sigma 1.5), valid region, float64 sums, mean over channels and positions.
+ * ws: spei_frame_metrics_ws_doubles(H, W, border) doubles (-1: the cropped frame is smaller than the window). */
+int64_t spei_frame_metrics_ws_doubles(int H, int W, int border);
+int spei_frame_metrics(const unsigned char* out_hwc, const unsigned char* gt_hwc, int H, int W, int border, double* ws, double* result,
+                       spei_stream_t stream);
 
 /* K3 — ResBlock gates (model/block.py:8-24 SE, 71-96 ZPool+AttentionGate1/2, 108-124 TripletAttention).
  * x1: conv2 output [H][W][C] stored as x1_fmt (SPEI_F32 / SPEI_BF16 / SPEI_F16).  Workspace `ws` floats: spei_gate_ws_floats(H,W,C).
@@ -475,8 +474,8 @@ int spei_det_features(const float* gray, float* out, float* ws, int N, int H, in
 int spei_frames_u8_in(const unsigned char* src, int64_t frame_stride, float* dst, float* gray, int N, int H, int W, spei_stream_t stream);
 
 /* fp32 [3][Hp][Wp] -> dst uint8 [H][W][3], the top-left crop (H <= Hp, W <= Wp) as round_half_even(clamp(x * 255, 0, 255)),
- * 0 for a non-finite value: the `out_hwc` of spei_frame_post.  nonfinite (or NULL): one int, cleared on the stream, then nonzero
- * iff the crop held a NaN or an infinity. */
+ * 0 for a non-finite value (reference inference_SPEINet.py:477-482 tensor2numpy).  nonfinite (or NULL): one int, cleared on the
+ * stream, then nonzero iff the crop held a NaN or an infinity. */
 int spei_frame_u8_out(const float* src, unsigned char* dst, int* nonfinite, int H, int W, int Hp, int Wp, spei_stream_t stream);
 
 #ifdef __cplusplus

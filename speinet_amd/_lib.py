@@ -95,8 +95,8 @@ SIGNATURES = {
     "spei_search_bwd_ref": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "spei_upsample_bicubic_bwd": (I, [P, P, I, I, I, I, P]),
     "spei_rowdot": (I, [P, P, P, L, I, P]),
-    "spei_frame_post_ws_doubles": (L, [I, I, I]),
-    "spei_frame_post": (I, [P, P, P, I, I, I, P, P, P]),
+    "spei_frame_metrics_ws_doubles": (L, [I, I, I]),
+    "spei_frame_metrics": (I, [P, P, I, I, I, P, P, P]),
     "spei_det_gray": (I, [P, P, I, I, I, P]),
     "spei_det_ws_floats": (L, [I, I, I, I]),
     "spei_det_features": (I, [P, P, P, I, I, I, I, P]),

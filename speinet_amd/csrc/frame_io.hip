@@ -7,9 +7,9 @@
 //                        LD detector's gray plane [N][H][W] of the unpadded frame, bit-identical to spei_det_gray on the same frame
 //                        as fp32 0..255 (one shared expression, spei_gray_px).
 //   spei_frame_u8_out  — fp32 [3][Hp][Wp] -> the top-left H x W crop as uint8 [H][W][3], round_half_even(clamp(x * 255, 0, 255))
-//                        (reference :477-482 tensor2numpy); exactly the `out_hwc` of spei_frame_post (metrics.hip), a non-finite
-//                        value included (0).  Optionally a flag, nonzero iff the crop held a non-finite value: spei_frame_post's
-//                        `finite` result, which the clip API uses to recompute the window in bf16x3 as the harness does.
+//                        (reference :477-482 tensor2numpy), 0 for a non-finite value: the frame that is written to disk and that
+//                        the harness scores (spei_frame_metrics, metrics.hip).  Optionally a flag, nonzero iff the crop held a
+//                        non-finite value, on which the clip API recomputes the window in bf16x3.
 //
 // Streaming kernels, one thread per group of 4 pixels of a row: 12 bytes of uint8 read (three dwords when the rows are 4-byte
 // aligned), one 16-byte store per plane.  The mirrored indices are computed in the pad band only.  HBM-bound: a 720p frame is
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void frames_u8_in_kernel(const unsigned char* 
 
 __device__ __forceinline__ uint32_t to_u8(float v) {
     const float q = rintf(fminf(fmaxf(v * 255.0f, 0.0f), 255.0f));     // mul(255).clamp(0, 255).round(): half to even, as torch
-    return isfinite(v) ? (uint32_t)q : 0u;                              // as spei_frame_post
+    return isfinite(v) ? (uint32_t)q : 0u;
 }
 
 __global__ __launch_bounds__(256) void frame_u8_out_kernel(const float* __restrict__ src, unsigned char* __restrict__ dst,

@@ -1,55 +1,37 @@
-// Harness post-processing of one deblurred frame on the device (reference inference_SPEINet.py:477-482 tensor2numpy, :484-500
-// calc_PSNR, :502-543 calc_SSIM): the model's fp32 [3][H][W] output -> the uint8 [H][W][3] frame that is written to disk, whether any
-// value was non-finite, and PSNR / SSIM of that frame against the ground-truth frame on the border-cropped region — three small
-// launches instead of the ~45 torch kernels of round 3 (float64 band-matrix GEMMs for the Gaussian window: 0.95 ms of rocBLAS per
-// window, 2.2 ms in all; profiles/r04_harness_*).  Arithmetic: integers where the reference has integers (squared differences are
-// exact), float64 for the SSIM window sums and the means, as numpy does it.  SSIM: 11x11 Gaussian (sigma 1.5) = outer(k, k) applied
-// as a row pass and a column pass, valid region only; per channel; the mean over all channels and positions (the reference averages
-// the same 3-channel value three times).  HBM-bound: each frame is read once per kernel (2.8 MB).
+// Harness metrics of one deblurred frame on the device (reference inference_SPEINet.py:484-500 calc_PSNR, :502-543 calc_SSIM): PSNR and
+// SSIM of the uint8 [H][W][3] frame that is written to disk (spei_frame_u8_out, frame_io.hip) against the ground-truth frame on the
+// border-cropped region — three small launches instead of the ~45 torch kernels of round 3 (float64 band-matrix GEMMs for the Gaussian
+// window: 0.95 ms of rocBLAS per window, 2.2 ms in all; profiles/r04_harness_*).  Arithmetic: integers where the reference has
+// integers (the squared differences, summed exactly in float64), float64 for the SSIM window sums and the means, as numpy does it.
+// SSIM: 11x11 Gaussian (sigma 1.5) = outer(k, k) applied as a row pass and a column pass, valid region only; per channel; the mean over
+// all channels and positions (the reference averages the same 3-channel value three times).  HBM-bound: each frame is read once per
+// kernel (2.8 MB).
 #include "common.h"
 
 namespace {
 
 constexpr int TW = 32, TH = 8, R = 5, KS = 2 * R + 1;     // output tile, window radius
 
-__global__ __launch_bounds__(256) void frame_to_u8_kernel(const float* __restrict__ chw, unsigned char* __restrict__ hwc,
-                                                           const unsigned char* __restrict__ gt, int H, int W, int border,
-                                                           double* __restrict__ part) {
-    // one thread = one pixel (3 channels): planes read coalesced, 3 bytes written per thread
-    const int n = H * W;
+__global__ __launch_bounds__(256) void sq_diff_kernel(const unsigned char* __restrict__ a, const unsigned char* __restrict__ b, int H,
+                                                       int W, int border, double* __restrict__ part) {
+    // one thread = one byte: sum of (a - b)^2 over the cropped region
+    const int n = H * W * 3;
     long long sq = 0;
-    int bad = 0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const int y = i / W, x = i - y * W;
-        const bool in = y >= border && y < H - border && x >= border && x < W - border;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = chw[(size_t)c * n + i];
-            bad += !isfinite(v);
-            const float q = rintf(fminf(fmaxf(v * 255.0f, 0.0f), 255.0f));      // mul(255).clamp(0, 255).round(): half to even, as torch
-            const int u = isfinite(v) ? (int)q : 0;
-            hwc[(size_t)i * 3 + c] = (unsigned char)u;
-            if (in) {
-                const int d = u - (int)gt[(size_t)i * 3 + c];
-                sq += d * d;
-            }
+        const int p = i / 3, y = p / W, x = p - y * W;
+        if (y >= border && y < H - border && x >= border && x < W - border) {
+            const int d = (int)a[i] - (int)b[i];
+            sq += d * d;
         }
     }
-    // block reduction (fixed order): lanes, then waves
+    // block reduction (fixed order): lanes, then waves; every partial is an integer below 2^53, so the sums are exact
     __shared__ double s_sq[4];
-    __shared__ int s_bad[4];
     double dsq = (double)sq;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        dsq += __shfl_xor(dsq, o, 64);
-        bad += __shfl_xor(bad, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { s_sq[threadIdx.x >> 6] = dsq; s_bad[threadIdx.x >> 6] = bad; }
+    for (int o = 32; o > 0; o >>= 1) dsq += __shfl_xor(dsq, o, 64);
+    if ((threadIdx.x & 63) == 0) s_sq[threadIdx.x >> 6] = dsq;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = (s_sq[0] + s_sq[1]) + (s_sq[2] + s_sq[3]);
-        part[2 * blockIdx.x + 1] = (double)((s_bad[0] + s_bad[1]) + (s_bad[2] + s_bad[3]));
-    }
+    if (threadIdx.x == 0) part[blockIdx.x] = (s_sq[0] + s_sq[1]) + (s_sq[2] + s_sq[3]);
 }
 
 struct Gauss { double k[KS]; };
@@ -105,43 +87,41 @@ __global__ __launch_bounds__(256) void ssim_kernel(const unsigned char* __restri
     if (threadIdx.x == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = (s_acc[0] + s_acc[1]) + (s_acc[2] + s_acc[3]);
 }
 
-__global__ __launch_bounds__(256) void metrics_final_kernel(const double* __restrict__ part_u8, int n_u8, const double* __restrict__ part_ssim,
+__global__ __launch_bounds__(256) void metrics_final_kernel(const double* __restrict__ part_sq, int n_sq, const double* __restrict__ part_ssim,
                                                              int n_ssim, double n_px, double n_ssim_px, double* __restrict__ result) {
-    __shared__ double s[3][4];
-    double sq = 0, bad = 0, ss = 0;
-    for (int i = threadIdx.x; i < n_u8; i += 256) { sq += part_u8[2 * i]; bad += part_u8[2 * i + 1]; }
+    __shared__ double s[2][4];
+    double sq = 0, ss = 0;
+    for (int i = threadIdx.x; i < n_sq; i += 256) sq += part_sq[i];
     for (int i = threadIdx.x; i < n_ssim; i += 256) ss += part_ssim[i];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        sq += __shfl_xor(sq, o, 64); bad += __shfl_xor(bad, o, 64); ss += __shfl_xor(ss, o, 64);
+        sq += __shfl_xor(sq, o, 64); ss += __shfl_xor(ss, o, 64);
     }
-    if ((threadIdx.x & 63) == 0) { s[0][threadIdx.x >> 6] = sq; s[1][threadIdx.x >> 6] = bad; s[2][threadIdx.x >> 6] = ss; }
+    if ((threadIdx.x & 63) == 0) { s[0][threadIdx.x >> 6] = sq; s[1][threadIdx.x >> 6] = ss; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double tsq = (s[0][0] + s[0][1]) + (s[0][2] + s[0][3]), tbad = (s[1][0] + s[1][1]) + (s[1][2] + s[1][3]);
-        const double tss = (s[2][0] + s[2][1]) + (s[2][2] + s[2][3]);
+        const double tsq = (s[0][0] + s[0][1]) + (s[0][2] + s[0][3]), tss = (s[1][0] + s[1][1]) + (s[1][2] + s[1][3]);
         const double mse = tsq / n_px;
-        result[0] = tbad == 0.0 ? 1.0 : 0.0;                                     // every value finite
-        result[1] = mse == 0.0 ? INFINITY : 20.0 * log10(255.0 / sqrt(mse));     // calc_PSNR (inf on identical frames)
-        result[2] = tss / n_ssim_px;
+        result[0] = mse == 0.0 ? INFINITY : 20.0 * log10(255.0 / sqrt(mse));     // calc_PSNR (inf on identical frames)
+        result[1] = tss / n_ssim_px;
     }
 }
 
-constexpr int U8_BLOCKS = 512;
+constexpr int SQ_BLOCKS = 512;
 
 }  // namespace
 
-extern "C" int64_t spei_frame_post_ws_doubles(int H, int W, int border) {
+extern "C" int64_t spei_frame_metrics_ws_doubles(int H, int W, int border) {
     const int oh = H - 2 * border - 2 * R, ow = W - 2 * border - 2 * R;
     if (oh <= 0 || ow <= 0) return -1;
-    return 2 * (int64_t)U8_BLOCKS + (int64_t)cdiv(ow, TW) * cdiv(oh, TH);
+    return (int64_t)SQ_BLOCKS + (int64_t)cdiv(ow, TW) * cdiv(oh, TH);
 }
 
-extern "C" int spei_frame_post(const float* out_chw, const unsigned char* gt_hwc, unsigned char* out_hwc, int H, int W, int border,
-                               double* ws, double* result, spei_stream_t stream) {
-    SPEI_REQUIRE(out_chw && gt_hwc && out_hwc && ws && result, "spei_frame_post: null pointer");
-    SPEI_REQUIRE(border >= 0 && H - 2 * border - 2 * R > 0 && W - 2 * border - 2 * R > 0 && (int64_t)H * W < (1ll << 30),
-                 "spei_frame_post: %dx%d with border %d leaves no valid SSIM window", H, W, border);
+extern "C" int spei_frame_metrics(const unsigned char* out_hwc, const unsigned char* gt_hwc, int H, int W, int border, double* ws,
+                                  double* result, spei_stream_t stream) {
+    SPEI_REQUIRE(out_hwc && gt_hwc && ws && result, "spei_frame_metrics: null pointer");
+    SPEI_REQUIRE(border >= 0 && H - 2 * border - 2 * R > 0 && W - 2 * border - 2 * R > 0 && (int64_t)H * W < (1ll << 29),
+                 "spei_frame_metrics: %dx%d with border %d leaves no valid SSIM window", H, W, border);
     hipStream_t st = (hipStream_t)stream;
     Gauss g;
     double sum = 0;
@@ -149,11 +129,11 @@ extern "C" int spei_frame_post(const float* out_chw, const unsigned char* gt_hwc
     for (int i = 0; i < KS; ++i) g.k[i] /= sum;
     const int oh = H - 2 * border - 2 * R, ow = W - 2 * border - 2 * R;
     const dim3 tiles(cdiv(ow, TW), cdiv(oh, TH));
-    double* part_ssim = ws + 2 * U8_BLOCKS;
-    hipLaunchKernelGGL(frame_to_u8_kernel, dim3(U8_BLOCKS), dim3(256), 0, st, out_chw, out_hwc, gt_hwc, H, W, border, ws);
+    double* part_ssim = ws + SQ_BLOCKS;
+    hipLaunchKernelGGL(sq_diff_kernel, dim3(SQ_BLOCKS), dim3(256), 0, st, out_hwc, gt_hwc, H, W, border, ws);
     hipLaunchKernelGGL(ssim_kernel, tiles, dim3(256), 0, st, out_hwc, gt_hwc, H, W, border, g, part_ssim);
-    hipLaunchKernelGGL(metrics_final_kernel, dim3(1), dim3(256), 0, st, ws, U8_BLOCKS, part_ssim, (int)(tiles.x * tiles.y),
+    hipLaunchKernelGGL(metrics_final_kernel, dim3(1), dim3(256), 0, st, ws, SQ_BLOCKS, part_ssim, (int)(tiles.x * tiles.y),
                        (double)(H - 2 * border) * (W - 2 * border) * 3.0, (double)oh * ow * 3.0, result);
-    SPEI_CHECK_LAUNCH("spei_frame_post");
+    SPEI_CHECK_LAUNCH("spei_frame_metrics");
     return 0;
 }

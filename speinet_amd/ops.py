@@ -174,26 +174,25 @@ def _family(name: str):
     return deco
 
 
-def frame_post(out_chw: torch.Tensor, gt_hwc: torch.Tensor, border: int = 4):
-    """Harness post-processing of one frame on the device (csrc/metrics.hip; reference inference_SPEINet.py:477-543): out_chw [3,H,W]
-    fp32 -> (uint8 [H,W,3] frame, float64 [finite, PSNR, SSIM] against gt_hwc on the border-cropped region), three launches on the
-    current stream of the tensors' device, no host sync."""
-    assert out_chw.is_cuda and out_chw.dtype == torch.float32 and out_chw.dim() == 3 and out_chw.shape[0] == 3 and out_chw.is_contiguous()
-    h, w = out_chw.shape[1:]
-    assert gt_hwc.shape == (h, w, 3) and gt_hwc.dtype == torch.uint8 and gt_hwc.device == out_chw.device and gt_hwc.is_contiguous()
+def frame_metrics(u8: torch.Tensor, gt_hwc: torch.Tensor, border: int = 4) -> torch.Tensor:
+    """Harness metrics of one frame on the device (csrc/metrics.hip; reference inference_SPEINet.py:484-543): float64 [PSNR, SSIM] of
+    the uint8 [H,W,3] frame `u8` (`frame_u8_out`'s) against gt_hwc on the border-cropped region, three launches on the current stream
+    of the tensors' device, no host sync."""
+    assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[2] == 3 and u8.is_contiguous()
+    h, w = u8.shape[:2]
+    assert gt_hwc.shape == u8.shape and gt_hwc.dtype == torch.uint8 and gt_hwc.device == u8.device and gt_hwc.is_contiguous()
     lib = _lib.lib()
-    n = lib.spei_frame_post_ws_doubles(h, w, border)
+    n = lib.spei_frame_metrics_ws_doubles(h, w, border)
     if n < 0:
         raise ValueError(f"frame {w}x{h} with border {border} is smaller than the 11x11 SSIM window")
-    dev = out_chw.device
-    u8 = torch.empty(h, w, 3, dtype=torch.uint8, device=dev)
+    dev = u8.device
     ws = torch.empty(n, dtype=torch.float64, device=dev)
-    res = torch.empty(3, dtype=torch.float64, device=dev)
+    res = torch.empty(2, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_frame_post(_vp(out_chw.data_ptr()), _vp(gt_hwc.data_ptr()), _vp(u8.data_ptr()), h, w, border, _vp(ws.data_ptr()),
-                                       _vp(res.data_ptr()), st), "spei_frame_post")
-    return u8, res
+        _lib.check(lib.spei_frame_metrics(_vp(u8.data_ptr()), _vp(gt_hwc.data_ptr()), h, w, border, _vp(ws.data_ptr()), _vp(res.data_ptr()),
+                                          st), "spei_frame_metrics")
+    return res
 
 
 def padded_size(n: int) -> int:
@@ -228,10 +227,9 @@ def frames_u8_in(u8: torch.Tensor, out: Optional[torch.Tensor] = None, gray: boo
 
 def frame_u8_out(x: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None,
                  nonfinite: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp32 [3,Hp,Wp] on the device -> its top-left h x w crop as uint8 [h,w,3] (`tensor2numpy`'s values, the frame of `frame_post`).
+    """fp32 [3,Hp,Wp] on the device -> its top-left h x w crop as uint8 [h,w,3] (`tensor2numpy`'s values, 0 for a non-finite value).
     `out` (optional): a packed uint8 [h,w,3] destination.  `nonfinite` (optional): an int32 device tensor whose first element becomes
-    nonzero iff the crop held a NaN or an infinity (`frame_post`'s finite flag, inverted).  Launches on the current stream
-    (csrc/frame_io.hip), no host sync."""
+    nonzero iff the crop held a NaN or an infinity.  Launches on the current stream (csrc/frame_io.hip), no host sync."""
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 3 and x.is_contiguous()
     hp, wp = x.shape[1:]
     if out is None:

@@ -1,22 +1,23 @@
-"""Deblur a clip of the user's own footage: uint8 frames of any size (at least 20x20), with or without sharpness labels, no ground
-truth.  The library API is `deblur_clip`; the command line is
+"""The clip loop: deblur a clip of uint8 frames of any size (at least 20x20), with or without sharpness labels.  The library API is
+`deblur_clip`; the command line, for the user's own footage (no ground truth), is
 
     python -m speinet_amd.video --input <dir | glob> --output <dir> --model_path <checkpoint | synthetic> [--labels <file.npy>]
 
-It runs the harness's clip machinery (speinet_amd.inference) without the harness's dataset layout, metrics and crop:
+and the dataset harness (speinet_amd.inference) runs every clip through `deblur_clip` as well, adding its ground truth and metrics.
   * labels — given (0/1 per frame, 1 = sharp), or computed by the LD detector (speinet_amd.detector) in a first streaming pass over the
     clip in batches of 16 frames: gray planes from the ingest kernel, focus measures, logistic regression;
-  * the window plan — `selection.assemble_windows` on the frame indices (a frame's number is its index in the clip): reflect-padded
-    clip, `blurry_indices`, references more than 7 frames away zeroed, routing by the zeroed reference;
+  * the window plan — `selection.assemble_windows` on the frame numbers (by default a frame's number is its index in the clip; the
+    harness passes the numbers in its file names): reflect-padded clip, `blurry_indices`, references more than 7 frames away zeroed,
+    routing by the zeroed reference;
   * the windows — `forward_window` with a per-clip `EncoderCache`, `prefetch_window` one window ahead, windows alternating over two
-    launch streams, in whatever `precision` / `corr_precision` / `use_graph` / `streams` the caller set on the model;
-  * frames cross PCIe as uint8 from page-locked staging buffers (`inference.FrameCache`) and are decoded, for image paths, on worker
-    threads a few windows ahead.
+    launch streams that the model keeps, in whatever `precision` / `corr_precision` / `use_graph` / `streams` the caller set on it;
+  * frames cross PCIe as uint8 from page-locked staging buffers (`FrameCache`) and are decoded, for image paths, on worker threads a
+    few windows ahead; a window whose 16-bit pass left a non-finite value is recomputed in bf16x3.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
-such sizes at all; at multiples of 20 the frames are bit-identical to the harness's.  Device memory is bounded by one window, the
-encoder cache and the windows in flight: it does not grow with the clip's length.
+such sizes at all; its harness crops the frames to multiples of 20 instead, which `crop=True` does (on the host, as each frame is
+loaded).  Device memory is bounded by one window, the encoder cache and the windows in flight: it does not grow with the clip's length.
 """
 from __future__ import annotations
 
@@ -26,27 +27,126 @@ import glob
 import os
 import time
 import warnings
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import Future, ThreadPoolExecutor
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import detector, ops, selection
-from .inference import FrameCache, _imread, _imwrite
 from .speinet import EncoderCache
 
 ZERO = ("zero",)                 # window key of a zeroed reference frame
 MIN_SIZE = 20
 IMAGE_EXTS = (".png", ".jpg", ".jpeg", ".bmp")
-CORR_PRECISION = {"f32": "bf16x3", "bf16x3": "bf16x3", "bf16": "top2", "f16": "top2"}    # the harness's pairing (inference.Inference)
+CORR_PRECISION = {"f32": "bf16x3", "bf16x3": "bf16x3", "bf16": "top2", "f16": "top2"}    # correlation arithmetic per precision
 DETECT_BATCH = 16                # frames per launch of the labelling pass (the harness's batch)
 PREFETCH = 4                     # windows decoded ahead of the GPU
-LANES = 2                        # launch streams the windows alternate over (inference.py --lanes)
+LANES = 2                        # launch streams the windows alternate over (3 and 4 measured 8-25 % slower than 2 on 720p)
 LAG = 2                          # windows enqueued after a frame before it is handed out
 FLAG_RING = 8                    # non-finite flags in flight (> LAG + 1)
 
 padded_size = ops.padded_size
+
+
+def _imread(path: str) -> np.ndarray:
+    from PIL import Image
+    return np.asarray(Image.open(path).convert("RGB"))
+
+
+def _imwrite(path: str, img: np.ndarray) -> None:
+    """Lossless PNG at zlib level 1: the reference writes with cv2.imwrite's default, OpenCV's "best speed" PNG setting
+    (inference_SPEINet.py:415-417); PIL's own default (level 6) costs twice the encode time for 10 % smaller files."""
+    from PIL import Image
+    Image.fromarray(img).save(path, compress_level=1)
+
+
+class FrameCache:
+    """Decode-once, upload-once cache of frames: `load(key)` decodes one (host uint8 [H,W,3]).  `request(keys)` schedules decodes on
+    the thread pool; `get_dev(key)` returns the frame on the device, uploaded once however many windows share it (a frame is a
+    neighbour twice, a middle frame once and often a reference).  Uploads go through a small ring of page-locked staging buffers
+    allocated once: a copy from pageable memory makes the host wait for everything queued on the stream before it (one full GPU drain
+    per window), and allocating page-locked memory per frame synchronises the device.  Bounded LRUs (a 720p RGB frame is 2.8 MB)."""
+    RING = 8
+
+    def __init__(self, pool: ThreadPoolExecutor, load, device, capacity: int = 16):
+        self.pool, self.load, self.device, self.capacity = pool, load, device, capacity
+        self.items: "collections.OrderedDict[object, Future]" = collections.OrderedDict()
+        self.dev: "collections.OrderedDict[object, torch.Tensor]" = collections.OrderedDict()
+        self._ring, self._events, self._n = [], [], 0
+
+    def request(self, keys) -> None:
+        for p in keys:
+            if p in self.items:
+                self.items.move_to_end(p)
+            elif p not in self.dev:
+                self.items[p] = self.pool.submit(self.load, p)
+        while len(self.items) > self.capacity:
+            self.items.popitem(last=False)
+
+    def _upload(self, arr: np.ndarray) -> torch.Tensor:
+        n = arr.size
+        if not self._ring or self._ring[0].numel() < n:
+            self._ring = [torch.empty(n, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
+            self._events = [None] * self.RING
+        i = self._n % self.RING
+        self._n += 1
+        if self._events[i] is not None:
+            self._events[i].synchronize()                 # the copy issued RING uploads ago: long finished
+        stage = self._ring[i][:n].view(arr.shape)
+        stage.numpy()[...] = arr
+        t = stage.to(self.device, non_blocking=True)
+        self._events[i] = torch.cuda.Event()
+        self._events[i].record()
+        return t
+
+    def get_dev(self, key) -> torch.Tensor:
+        t = self.dev.get(key)
+        if t is None:
+            self.request([key])
+            t = self.dev[key] = self._upload(self.items.pop(key).result())
+            while len(self.dev) > self.capacity:
+                self.dev.popitem(last=False)
+        else:
+            self.dev.move_to_end(key)
+        return t
+
+
+class HostRing:
+    """Finished frames landed in page-locked memory for worker threads: `land(fn, *tensors)` queues the device->host copies of the
+    tensors on the current stream, behind whatever produced them, and returns the future of `fn(*host_tensors)`, which runs on the
+    pool once those copies are done.  A worker waits on its own copies only: a `.cpu()` from a worker thread is a synchronous copy on
+    the stream and would wait for every window queued after its own as well.  `n` slots in turn, a slot reused once its last worker
+    has finished; the buffers are allocated once per set of shapes (allocating page-locked memory synchronises the device)."""
+
+    def __init__(self, pool: ThreadPoolExecutor, n: int = 8):
+        self.pool, self.n, self.k = pool, n, 0
+        self.bufs, self.futs = [], [None] * n
+
+    def land(self, fn, *tensors) -> Future:
+        if not self.bufs or [(b.shape, b.dtype) for b in self.bufs[0]] != [(t.shape, t.dtype) for t in tensors]:
+            self.drain()
+            self.bufs = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors] for _ in range(self.n)]
+        i = self.k % self.n
+        self.k += 1
+        if self.futs[i] is not None:
+            self.futs[i].result()
+        for b, t in zip(self.bufs[i], tensors):
+            b.copy_(t, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.futs[i] = self.pool.submit(self._work, fn, ev, self.bufs[i])
+        return self.futs[i]
+
+    @staticmethod
+    def _work(fn, ev, bufs):
+        ev.synchronize()
+        return fn(*bufs)
+
+    def drain(self) -> None:
+        for f in self.futs:
+            if f is not None:
+                f.result()
 
 
 def reflect_index(n: int, n_pad: Optional[int] = None) -> np.ndarray:
@@ -60,23 +160,29 @@ def reflect_index(n: int, n_pad: Optional[int] = None) -> np.ndarray:
 
 
 class _Frames:
-    """The clip behind one interface: frame i as a host uint8 [H,W,3] array (`host`) or a device tensor (`on_device`)."""
+    """The clip behind one interface: frame i as a host uint8 [H,W,3] array (`host`) or a device tensor (`device`), cropped at the
+    bottom and right to H x W (`crop`: the source size rounded down to multiples of 20; otherwise the source size)."""
 
-    def __init__(self, items, T: int, H: int, W: int, paths: bool):
-        self.items, self.T, self.H, self.W, self.paths = items, T, H, W, paths
+    def __init__(self, items, T: int, H: int, W: int, paths: bool, crop: bool = False):
+        self.items, self.T, self.paths, self.src = items, T, paths, (H, W)
+        self.H, self.W = (H - H % 20, W - W % 20) if crop else (H, W)
 
     def on_device(self, i: int) -> bool:
         f = self.items[i]
         return torch.is_tensor(f) and f.is_cuda
 
+    def device(self, i: int) -> torch.Tensor:
+        return self.items[i][:self.H, :self.W]
+
     def host(self, i: int) -> np.ndarray:
         f = self.items[i]
         if self.paths:
             img = _imread(f)
-            if img.shape != (self.H, self.W, 3):
-                raise ValueError(f"frame {i} ({f}) is {img.shape[1]}x{img.shape[0]}, the clip is {self.W}x{self.H}")
-            return img
-        return f.numpy() if torch.is_tensor(f) else np.asarray(f)
+            if img.shape[:2] != self.src:
+                raise ValueError(f"frame {i} ({f}) is {img.shape[1]}x{img.shape[0]}, the clip is {self.src[1]}x{self.src[0]}")
+        else:
+            img = f.numpy() if torch.is_tensor(f) else np.asarray(f)
+        return img[:self.H, :self.W]
 
 
 def _check_frame(i, shape, dtype) -> None:
@@ -88,7 +194,7 @@ def _check_frame(i, shape, dtype) -> None:
         raise ValueError(f"frames must be at least {MIN_SIZE}x{MIN_SIZE}; frame {i} is {shape[1]}x{shape[0]}")
 
 
-def frames_of(frames) -> _Frames:
+def frames_of(frames, crop: bool = False) -> _Frames:
     """Validate a clip: a uint8 [T,H,W,3] array or tensor (host or device), a list of uint8 [H,W,3] arrays / tensors, or a list of
     image paths (only their headers are read here).  Raises ValueError with the reason."""
     if isinstance(frames, (str, bytes)) or not hasattr(frames, "__len__") or not hasattr(frames, "__getitem__"):
@@ -100,7 +206,7 @@ def frames_of(frames) -> _Frames:
         if frames.ndim != 4:
             raise ValueError(f"a frame array must be [T,H,W,3]; got shape {tuple(frames.shape)}")
         _check_frame(0, tuple(frames.shape[1:]), frames.dtype)
-        return _Frames(frames, T, int(frames.shape[1]), int(frames.shape[2]), paths=False)
+        return _Frames(frames, T, int(frames.shape[1]), int(frames.shape[2]), paths=False, crop=crop)
     items = list(frames)
     is_path = [isinstance(f, (str, os.PathLike)) for f in items]
     if any(is_path) and not all(is_path):
@@ -115,14 +221,14 @@ def frames_of(frames) -> _Frames:
             _check_frame(i, (h, w, 3), np.uint8)
             if (h, w) != sizes[0]:
                 raise ValueError(f"mixed frame sizes: frame 0 is {sizes[0][1]}x{sizes[0][0]}, frame {i} ({items[i]}) is {w}x{h}")
-        return _Frames([os.fspath(p) for p in items], T, sizes[0][0], sizes[0][1], paths=True)
+        return _Frames([os.fspath(p) for p in items], T, sizes[0][0], sizes[0][1], paths=True, crop=crop)
     for i, f in enumerate(items):
         if not isinstance(f, (np.ndarray, torch.Tensor)):
             raise ValueError(f"frame {i} is a {type(f).__name__}, not an array, tensor or image path")
         _check_frame(i, tuple(f.shape), f.dtype)
         if tuple(f.shape) != tuple(items[0].shape):
             raise ValueError(f"mixed frame sizes: frame 0 is {items[0].shape[1]}x{items[0].shape[0]}, frame {i} is {f.shape[1]}x{f.shape[0]}")
-    return _Frames(items, T, int(items[0].shape[0]), int(items[0].shape[1]), paths=False)
+    return _Frames(items, T, int(items[0].shape[0]), int(items[0].shape[1]), paths=False, crop=crop)
 
 
 def labels_of(labels, T: int) -> np.ndarray:
@@ -134,12 +240,14 @@ def labels_of(labels, T: int) -> np.ndarray:
     return lab.astype(np.int64)
 
 
-def window_plan(labels, n_seq: int = 3) -> list:
-    """The harness's window plan for a clip labelled `labels` (inference.Inference.infer): one entry per output frame with the n_seq
-    window frames, the two reference frames, whether each reference is zeroed (`zero_pre` is the routing: True = no-reference branch)
-    and the n_seq + 2 `forward_window` keys (frame indices, `ZERO` for a zeroed reference)."""
+def window_plan(labels, n_seq: int = 3, numbers=None) -> list:
+    """The window plan for a clip labelled `labels`: one entry per output frame with the n_seq window frames, the two reference frames
+    (frame indices), whether each reference is zeroed (more than 7 frame numbers from the last window frame; `zero_pre` is the
+    routing: True = no-reference branch) and the n_seq + 2 `forward_window` keys (frame indices, `ZERO` for a zeroed reference).
+    `numbers`: the frame numbers the reference gap is measured in (the harness's come from its file names); default: the indices."""
     T = len(labels)
-    wins = selection.assemble_windows([str(i) for i in range(T)], labels, n_seq, True, number=int)
+    number = int if numbers is None else (lambda i: int(numbers[int(i)]))
+    wins = selection.assemble_windows([str(i) for i in range(T)], labels, n_seq, True, number=number)
     plan = []
     for k, w in enumerate(wins):
         win, pre, sub = [int(f) for f in w["window"]], int(w["pre"]), int(w["sub"])
@@ -159,10 +267,11 @@ def _lanes(model, device, n: int) -> list:
 
 class ClipRun:
     """Iterator of (index, uint8 [H,W,3] device tensor) in frame order; see `deblur_clip`.  `labels` (0/1 per frame; computed on first
-    access when the caller gave none) and `plan` (`window_plan(labels)`) describe what runs; `recomputed` lists the frames that were
-    recomputed in bf16x3 because their 16-bit pass left a non-finite value."""
+    access when the caller gave none) and `plan` (`window_plan(labels, numbers=numbers)`) describe what runs; `recomputed` lists the
+    frames that were recomputed in bf16x3 because their 16-bit pass left a non-finite value; `seconds[k]` is window k's host time
+    [assembling its input, enqueueing it] (the wait for a free launch slot excluded)."""
 
-    def __init__(self, model, frames: _Frames, labels, out):
+    def __init__(self, model, frames: _Frames, labels, out, numbers=None):
         self.model, self.frames = model, frames
         params = list(model.parameters())
         self.device = params[0].device if params else torch.device("cpu")
@@ -173,6 +282,8 @@ class ClipRun:
             raise ValueError(f"out is on {out.device}, the model on {self.device}")
         self.out = out
         self.recomputed = []         # frames whose 16-bit pass left a non-finite value and that were recomputed in bf16x3
+        self.seconds = []
+        self.numbers = numbers
         self._plan = None
         self._it = None
 
@@ -185,7 +296,7 @@ class ClipRun:
     @property
     def plan(self) -> list:
         if self._plan is None:
-            self._plan = window_plan(self.labels)
+            self._plan = window_plan(self.labels, numbers=self.numbers)
         return self._plan
 
     def __iter__(self):
@@ -227,7 +338,7 @@ class ClipRun:
                     events[b % 2].record()
                 for i in range(i0, i0 + n):
                     if fr.on_device(i):
-                        batch[i - i0].copy_(fr.items[i])
+                        batch[i - i0].copy_(fr.device(i))
                 _, gray = ops.frames_u8_in(batch[:n], gray=True, planes=False)
                 feats.append(detector.gray_focus_measures(gray, 11))
         return detector.predict(torch.cat(feats))
@@ -239,7 +350,7 @@ class ClipRun:
         plan = self.plan
         n = m.n_sequence
         pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
-        cache = FrameCache(pool, capacity=16, device=dev, load=fr.host)     # uint8 frames, decoded and uploaded once each
+        cache = FrameCache(pool, fr.host, dev)             # uint8 frames, decoded and uploaded once each
         enc = EncoderCache()
         inflight, ready = collections.deque(), collections.deque()
         # the stream current at the first `next` assembles the inputs; the windows run on the lanes; a frame handed out is ordered
@@ -251,10 +362,11 @@ class ClipRun:
         flags_host = torch.zeros(FLAG_RING, dtype=torch.int32, pin_memory=True)
 
         def frame(i):
-            return fr.items[i].to(dev).contiguous() if fr.on_device(i) else cache.get_dev(i)
+            return fr.device(i).to(dev).contiguous() if fr.on_device(i) else cache.get_dev(i)
 
         def prepare(k):
             """Window k's input [1, n + 2, 3, Hp, Wp] on the home stream."""
+            t0 = time.time()
             for ahead in plan[k:k + 1 + PREFETCH]:
                 cache.request([i for i in ahead["keys"] if i is not ZERO and not fr.on_device(i)])
             x = torch.empty(1, n + 2, 3, Hp, Wp, device=dev)
@@ -263,12 +375,14 @@ class ClipRun:
                     x[0, j].zero_()
                 else:
                     ops.frames_u8_in(frame(key), out=x[0, j])
+            self.seconds.append([time.time() - t0, 0.0])
             return x
 
         def enqueue(k, x, nxt):
             """Window k on its lane (and window k + 1's encoder passes on the model's prefetch stream)."""
             if len(inflight) >= max(2, len(lanes)):
                 inflight.popleft().synchronize()           # the host stays at most two windows ahead of the GPU
+            t0 = time.time()
             w = plan[k]
             dst = self.out[k] if self.out is not None else torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
             lane = lanes[k % len(lanes)]
@@ -287,10 +401,11 @@ class ClipRun:
                 ev.record()
             inflight.append(ev)
             ready.append((k, dst, ev, x))
+            self.seconds[k][1] = time.time() - t0
 
         def redo(k, x, dst):
             """Window k again in split-bf16 arithmetic (fp32 exponent range), eagerly, on the home stream: a 16-bit pass left a NaN or an
-            infinity in the frame (half operands do not saturate).  As the harness does (inference.Inference._redo_window)."""
+            infinity in the frame (half operands do not saturate)."""
             keep = (m.precision, m.corr_precision, m.use_graph)
             m.precision, m.corr_precision, m.use_graph = "bf16x3", "bf16x3", False
             try:
@@ -344,7 +459,7 @@ class ClipRun:
             pool.shutdown(wait=False, cancel_futures=True)
 
 
-def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None) -> ClipRun:
+def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None) -> ClipRun:
     """Deblur a clip: an iterator of (index, uint8 [H,W,3] frame on the model's device), in frame order, one per input frame.
 
     model  — an eval() `SPEINet` on a ROCm device; its `precision`, `corr_precision`, `use_graph` and `streams` are used as set.
@@ -352,17 +467,22 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              uint8 [H,W,3] arrays / tensors, or a list of image paths (decoded to RGB on worker threads, a few windows ahead).
     labels — optional 0/1 per frame (1 = sharp); None: the LD detector labels the clip in a first streaming pass.
     out    — optional contiguous uint8 [T,H,W,3] tensor on the model's device: frame i is written to out[i] and that view is yielded.
+    crop   — crop every frame at the bottom and right to multiples of 20 as it is loaded, as the reference's harness does, instead of
+             padding it (H and W are then the cropped size).
+    numbers — optional frame number per frame, in which the distance to a reference frame is measured (default: the indices).
 
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
     to `ClipRun.recomputed` with a RuntimeWarning, and FloatingPointError is raised if the frame is still not finite."""
-    fr = frames_of(frames)
+    fr = frames_of(frames, crop)
     lab = None if labels is None else labels_of(labels, fr.T)
+    if numbers is not None and len(numbers) != fr.T:
+        raise ValueError(f"numbers has {len(numbers)} entries for a clip of {fr.T} frames")
     shape = (fr.T, fr.H, fr.W, 3)
     if out is not None and not (torch.is_tensor(out) and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
         raise ValueError(f"out must be a contiguous uint8 [{fr.T},{fr.H},{fr.W},3] tensor")
-    return ClipRun(model, fr, lab, out)
+    return ClipRun(model, fr, lab, out, numbers)
 
 
 def _inputs(spec: str) -> list:
@@ -412,22 +532,11 @@ def main(argv=None) -> None:
     run = deblur_clip(net, files, labels)
     os.makedirs(a.output, exist_ok=True)
     H, W = run.frames.H, run.frames.W
-    slots = [{"buf": torch.empty(H, W, 3, dtype=torch.uint8, pin_memory=True), "fut": None} for _ in range(8)]
-
-    def write(buf, ev, path):
-        ev.synchronize()
-        _imwrite(path, buf.numpy())
-
     t0 = t_prev = time.time()
     with ThreadPoolExecutor(max_workers=4, thread_name_prefix="speinet-png") as writers:
+        ring = HostRing(writers)
         for i, frame in run:
-            sl = slots[i % len(slots)]
-            if sl["fut"] is not None:
-                sl["fut"].result()
-            sl["buf"].copy_(frame, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            sl["fut"] = writers.submit(write, sl["buf"], ev, os.path.join(a.output, names[i]))
+            ring.land(lambda buf, path=os.path.join(a.output, names[i]): _imwrite(path, buf.numpy()), frame)
             now = time.time()
             branch = "no-reference" if run.plan[i]["zero_pre"] else "reference"
             print(f"> {names[i]} {branch} {now - t_prev:.3f}s", flush=True)
@@ -435,9 +544,7 @@ def main(argv=None) -> None:
                 print(f"# {names[i]}: non-finite value in the {a.precision} frame, recomputed in bf16x3 ({len(run.recomputed)} so far)",
                       flush=True)
             t_prev = now
-        for sl in slots:
-            if sl["fut"] is not None:
-                sl["fut"].result()
+        ring.drain()
     dt = time.time() - t0
     print(f"# {len(files)} frames {W}x{H} in {dt:.2f}s: {len(files) / dt:.2f} frames/s ({a.precision})", flush=True)
 

@@ -137,29 +137,86 @@ def test_forward_window_reuse_bit_identical(graph):
 
 
 @pytest.mark.parametrize("h,w", [(720, 1280), (60, 100), (45, 77), (19, 51)])
-def test_frame_post_vs_numpy(h, w):
-    """csrc/metrics.hip (uint8 conversion + finite flag + PSNR + SSIM in three launches) against the host restatements of the
-    reference's functions: `selection.tensor2numpy` (inference_SPEINet.py:477-482), `selection.calc_psnr` (:484-500) and
-    `inference.calc_ssim` (:502-543, numpy float64; SSIM itself is parity-unpinned: cv2 is absent) on the 4-pixel-cropped frames."""
+def test_frame_metrics_vs_numpy(h, w):
+    """The harness's per-frame kernels — csrc/frame_io.hip's uint8 conversion with its non-finite flag, then csrc/metrics.hip's PSNR and
+    SSIM — against the host restatements of the reference's functions: `selection.tensor2numpy` (inference_SPEINet.py:477-482),
+    `selection.calc_psnr` (:484-500) and `inference.calc_ssim` (:502-543, numpy float64; SSIM itself is parity-unpinned: cv2 is absent)
+    on the 4-pixel-cropped frames."""
     from speinet_amd import ops
     g = torch.Generator().manual_seed(h * 1000 + w)
     gt = (torch.rand(h, w, 3, generator=g) * 255).round().to(torch.uint8)
     out = (gt.permute(2, 0, 1).float() / 255 + 0.08 * torch.randn(3, h, w, generator=g)).contiguous()     # leaves [0, 1] in places
     out[0, 5, 7] = 0.5 / 255                                                                               # a tie: rounds to even (0)
     out[1, 6, 8] = 1.5 / 255                                                                               # ... (2)
-    u8, res = ops.frame_post(out.to("cuda:0"), gt.to("cuda:0"), 4)
+    gt_d = gt.to("cuda:0")
+    flag = torch.full((1,), 7, dtype=torch.int32, device="cuda:0")
+    u8 = ops.frame_u8_out(out.to("cuda:0"), h, w, nonfinite=flag)
+    res = ops.frame_metrics(u8, gt_d, 4)
     ref_u8 = selection.tensor2numpy(out[None])
     assert np.array_equal(u8.cpu().numpy(), ref_u8)
-    fin, psnr, ssim = res.tolist()
-    assert fin == 1.0
+    psnr, ssim = res.tolist()
+    assert int(flag.item()) == 0
     a, b = ref_u8[4:-4, 4:-4], gt.numpy()[4:-4, 4:-4]
     assert abs(psnr - selection.calc_psnr(a, b)) < 1e-9
     assert abs(ssim - inference.calc_ssim(a, b)) < 1e-10
     # identical frames: PSNR inf, SSIM 1; a non-finite value is reported and does not poison the uint8 frame
     same = (gt.permute(2, 0, 1).float() / 255).contiguous()
-    _, res = ops.frame_post(same.to("cuda:0"), gt.to("cuda:0"), 4)
-    assert res[0].item() == 1.0 and res[1].item() == float("inf") and abs(res[2].item() - 1.0) < 1e-12
+    res = ops.frame_metrics(ops.frame_u8_out(same.to("cuda:0"), h, w), gt_d, 4)
+    assert res[0].item() == float("inf") and abs(res[1].item() - 1.0) < 1e-12
     same[2, 3, 3] = float("nan")
     same[0, 9, 9] = float("inf")
-    u8, res = ops.frame_post(same.to("cuda:0"), gt.to("cuda:0"), 4)
-    assert res[0].item() == 0.0 and u8.cpu()[3, 3, 2] == 0
+    u8 = ops.frame_u8_out(same.to("cuda:0"), h, w, nonfinite=flag)
+    assert int(flag.item()) != 0 and u8.cpu()[3, 3, 2] == 0
+
+
+def _window_graphs(net) -> set:
+    return {k for k in net._graphs if k[0] == "window"}
+
+
+def test_harness_keeps_window_graphs_across_clips(tmp_path):
+    """Two clips of one shape through one Inference: the second clip replays the window graphs the first one captured (they are keyed
+    by launch stream, and the launch streams are the model's, not the clip's)."""
+    root, res = str(tmp_path / "data"), str(tmp_path / "res")
+    _make_clip(root, "clipA", 6, 40, 60, 1, labels=[1, 0, 0, 0, 1, 0])
+    _make_clip(root, "clipB", 6, 40, 60, 2, labels=[1, 0, 0, 0, 1, 0])
+    a = inference.build_args(["--data_path", root, "--model_path", "synthetic", "--result_path", res, "--precision", "f16"])
+    inf = inference.Inference(a)
+    inf.logger.echo = False
+    assert inf.net.use_graph
+    seen = []                                   # the window graphs at the start of each clip (labels_for runs first, once per clip)
+    labels_of_clip = inf.labels_for
+
+    def labels_for(clip, frames):
+        seen.append(_window_graphs(inf.net))
+        return labels_of_clip(clip, frames)
+
+    inf.labels_for = labels_for
+    tot = inf.infer()
+    assert int(tot[2].item()) == 12 and len(seen) == 2
+    assert not seen[0] and seen[1]              # clip A captured its window graphs ...
+    assert _window_graphs(inf.net) == seen[1]   # ... and clip B captured none
+
+
+def test_harness_crops_to_multiples_of_20(tmp_path):
+    """A 45x67 clip: the harness crops every frame (and the ground truth) to 40x60, as the reference does, and writes the model's output
+    on the cropped window."""
+    root, res = str(tmp_path / "data"), str(tmp_path / "res")
+    labels = [1, 0, 0, 0, 1]
+    _make_clip(root, "clipA", 5, 45, 67, 6, labels=labels)
+    a = inference.build_args(["--data_path", root, "--model_path", "synthetic", "--result_path", res, "--precision", "f32"])
+    inf = inference.Inference(a)
+    inf.logger.echo = False
+    tot = inf.infer()
+    assert int(tot[2].item()) == 5
+    blur = sorted(os.path.join(root, "blur", "clipA", f) for f in os.listdir(os.path.join(root, "blur", "clipA")))
+    for w in selection.assemble_windows(blur, np.asarray(labels)):
+        imgs = [inference._imread(p)[:40, :60] for p in w["window"] + [w["pre"], w["sub"]]]
+        if w["zero_pre"]:
+            imgs[-2] = np.zeros_like(imgs[-2])
+        if w["zero_sub"]:
+            imgs[-1] = np.zeros_like(imgs[-1])
+        with torch.no_grad():
+            out = inf.net(selection.numpy2tensor(imgs).cuda(), routing=[bool(w["zero_pre"])])
+        saved = inference._imread(os.path.join(res, "clipA", w["name"] + ".png"))
+        assert saved.shape == (40, 60, 3)
+        assert np.array_equal(selection.tensor2numpy(out), saved), w["name"]

@@ -94,7 +94,9 @@ def _ties() -> np.ndarray:
 
 
 @pytest.mark.parametrize("h, w, hp, wp", [(37, 53, 40, 60), (40, 60, 40, 60), (37, 53, 37, 53), (720, 1280, 720, 1280)])
-def test_egress_kernel(h, w, hp, wp):
+def test_egress_kernel_vs_numpy(h, w, hp, wp):
+    """spei_frame_u8_out against `selection.tensor2numpy` (ties, values far outside [0, 1], the crop of a padded frame), its non-finite
+    flag, and spei_frame_metrics on its frames against `selection.calc_psnr`: there is one fp32 -> uint8 kernel, the harness's too."""
     rng = np.random.default_rng(hp * wp)
     x = rng.uniform(-0.5, 1.5, (3, hp, wp)).astype(np.float32)
     ties = _ties()
@@ -109,26 +111,27 @@ def test_egress_kernel(h, w, hp, wp):
     assert got.shape == (h, w, 3)
     assert np.array_equal(got, selection.tensor2numpy(xt[None, :, :h, :w]))
     assert int((np.abs(x[:, :h, :w] * 255 - np.round(x[:, :h, :w] * 255)) == 0.5).sum()) >= len(ties)
-    u8, met = ops.frame_post(xt[:, :h, :w].contiguous().to(DEV), torch.zeros(h, w, 3, dtype=torch.uint8, device=DEV), 4)
-    assert np.array_equal(got, u8.cpu().numpy())
     flag = torch.full((1,), 7, dtype=torch.int32, device=DEV)                     # cleared by the call
     ops.frame_u8_out(xt.to(DEV), h, w, nonfinite=flag)
-    assert int(flag.item()) == 0 and met[0].item() == 1.0
+    assert int(flag.item()) == 0
     if wp > w:                                                  # a NaN in the pad columns is not part of the crop
         xp = x.copy()
         xp[1, h - 1, w] = np.nan
         ops.frame_u8_out(torch.from_numpy(xp).to(DEV), h, w, nonfinite=flag)
         assert int(flag.item()) == 0
-    # non-finite values: as spei_frame_post (0), and the flag is its `finite` result inverted
+    # non-finite values: 0 in the frame, the flag set, and the metrics of the frame those of the numpy frame
+    zeros = torch.zeros(h, w, 3, dtype=torch.uint8, device=DEV)
     for nf in ([(0, 1, 2, np.nan)], [(2, h - 1, w - 1, np.inf)], [(0, 1, 2, np.nan), (1, 3, 4, np.inf), (2, 5, 6, -np.inf)]):
         xn = x.copy()
         for c_, y_, x_, v in nf:
             xn[c_, y_, x_] = v
-        xt = torch.from_numpy(xn)
-        got = ops.frame_u8_out(xt.to(DEV), h, w, nonfinite=flag)
-        u8, met = ops.frame_post(xt[:, :h, :w].contiguous().to(DEV), torch.zeros(h, w, 3, dtype=torch.uint8, device=DEV), 4)
-        assert torch.equal(got, u8)
-        assert int(flag.item()) != 0 and met[0].item() == 0.0
+        got = ops.frame_u8_out(torch.from_numpy(xn).to(DEV), h, w, nonfinite=flag)
+        xz = np.where(np.isfinite(xn), xn, np.float32(0))
+        ref = selection.tensor2numpy(torch.from_numpy(xz)[None, :, :h, :w])
+        assert np.array_equal(got.cpu().numpy(), ref)
+        assert int(flag.item()) != 0
+        psnr = ops.frame_metrics(got, zeros, 4)[0].item()
+        assert abs(psnr - selection.calc_psnr(ref[4:-4, 4:-4], np.zeros_like(ref[4:-4, 4:-4]))) < 1e-9
 
 
 # ---- 3. multiples of 20: the harness's PNGs ----------------------------------------------------------------------------------------

@@ -66,10 +66,11 @@ def test_validation_of_image_files(tmp_path):
         V.deblur_clip(None, _u8(3, 30, 30, 3), out=torch.empty(3, 30, 30, 3))
 
 
-def _harness_plan(labels):
-    """What inference.Inference.infer runs per window (its `prepare`): routing, zeroed references and forward_window keys, with the
-    frame files named by their index."""
-    frames = [f"clip/{i:06d}.png" for i in range(len(labels))]
+def _harness_plan(labels, numbers=None):
+    """The harness's selection run directly (selection.assemble_windows on frame files whose names carry `numbers`, default the
+    indices): routing, zeroed references and the frames of each window, as frame numbers."""
+    numbers = list(range(len(labels))) if numbers is None else numbers
+    frames = [f"clip/{n:06d}.png" for n in numbers]
     out = []
     for w in selection.assemble_windows(frames, np.asarray(labels)):
         keys = list(w["window"]) + [("zero", 0, 0) if w["zero_pre"] else w["pre"], ("zero", 0, 0) if w["zero_sub"] else w["sub"]]
@@ -81,7 +82,7 @@ def _harness_plan(labels):
 def test_window_plan_equals_harness_plan(golden_dir):
     g11 = json.load(open(os.path.join(golden_dir, "g11_selection.json")))
     assert len(g11) >= 5
-    routed = set()
+    routed, renumbered = set(), 0
     for name, d in g11.items():
         plan = V.window_plan(d["labels"])
         mine = [(p["index"], p["zero_pre"], p["zero_sub"], [None if k is V.ZERO else k for k in p["keys"]]) for p in plan]
@@ -91,7 +92,14 @@ def test_window_plan_equals_harness_plan(golden_dir):
             assert p["keys"][:3] == p["window"] and p["window"][1] == p["index"]
             assert (p["keys"][3] is V.ZERO) == p["zero_pre"] and (p["keys"][4] is V.ZERO) == p["zero_sub"]
             routed.add(p["zero_pre"])
+        # frame numbers that are not the indices (gaps, an offset): the references are zeroed by the numbers, the keys stay indices
+        numbers = [100 + 2 * i + (i // 5) * 3 for i in range(len(d["labels"]))]
+        plan_n = V.window_plan(d["labels"], numbers=numbers)
+        mine_n = [(numbers[p["index"]], p["zero_pre"], p["zero_sub"], [None if k is V.ZERO else numbers[k] for k in p["keys"]]) for p in plan_n]
+        assert mine_n == _harness_plan(d["labels"], numbers), name
+        renumbered += [(p["zero_pre"], p["zero_sub"]) for p in plan_n] != [(p["zero_pre"], p["zero_sub"]) for p in plan]
     assert routed == {True, False}
+    assert renumbered > 0          # the numbering changed which references are zeroed in some case
 
 
 def test_header_declares_frame_io():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """End-to-end harness throughput on a synthetic 720p clip on disk (PNG decode -> selection -> forward -> uint8 -> PSNR/SSIM ->
-PNG encode): python tools/harness_bench.py [frames] [precision] [harness flags, e.g. --lanes 1]      (the same measurement bench.py --full
+PNG encode): python tools/harness_bench.py [frames] [precision] [harness flags, e.g. --streams 2]      (the same measurement bench.py --full
 reports as "harness")"""
 import json
 import os
