@@ -194,7 +194,7 @@ def _attn_ref(q, kv, rb, g, B, H, W, shift, rnd):
     s = rnd(qh) @ rnd(kh).transpose(-2, -1) + rb.unsqueeze(0)
     if shift:
         from speinet_amd.speinet import _shift_mask
-        mask = _shift_mask(H, W, ws, shift).double()
+        mask = _shift_mask(H, W, ws, shift).double().to(s.device)
         s = (s.view(B, -1, heads, 25, 25) + mask.unsqueeze(1).unsqueeze(0)).view(-1, heads, 25, 25)
     p = s.softmax(-1)
     o = rnd(p) @ rnd(vh)
