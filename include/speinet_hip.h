@@ -79,20 +79,14 @@ int spei_igemm_f32_batched(const float* a0, int lda0, int k0, const float* a1, i
                            const float* rowscale, int Hin, int Win, int Hout, int Wout, int N, int ksize, int stride,
                            int pad, int mode, int act, int batch, spei_stream_t stream);
 
-/* Same contract on the bf16 matrix pipe (v_mfma_f32_32x32x16_bf16, fp32 accumulate, fp32 activations in HBM rounded to
- * bf16 while staged to LDS).  w_hi/w_lo: [tap][N][K] bf16.  w_lo == NULL: one bf16 product per MAC ("bf16");
- * w_lo != NULL: split product al*wh + ah*wl + ah*wh ("bf16x3", f32-grade at 3/16 of the f32 MFMA cost). */
-int spei_igemm_bf16(const float* a0, int lda0, int k0, const float* a1, int lda1, int k1, const void* w_hi,
-                    const void* w_lo, const float* bias, float* out, int ldo, const float* residual, int ldr,
-                    const float* rowscale, int Hin, int Win, int Hout, int Wout, int N, int ksize, int stride,
-                    int pad, int mode, int act, spei_stream_t stream);
-
-/* Slab-resident variant of spei_igemm_bf16 for SPEI_CONV (stride 1/2) and linears, bf16 or half operands (`fmt`): the
+/* Same contract for SPEI_CONV (stride 1/2) and linears on the 16-bit matrix pipe (v_mfma_f32_32x32x16_bf16 / _f16, fp32
+ * accumulate), bf16 or half operands (`fmt`), slab-resident: the
  * input tile + halo is staged once into LDS as 16-bit and the weights stream from HBM/L2 in MFMA fragment order
  * (wfrag: [N/32][tap][K/16][64][8] 16-bit, see speinet_amd/pack.py).  Linears: pass Hin = Hout = M, Win = Wout = 1.
  * a_fmt / out_fmt: the activations (both sources) / the output are stored as fp32 or as `fmt` in HBM — 16-bit for
  * tensors that only feed the next GEMM or the attention kernel; residual, rowscale and bias stay fp32.
- * wfrag_lo != NULL: the split "bf16x3" product (SPEI_BF16 with fp32 activations only).
+ * wfrag_lo == NULL: one 16-bit product per MAC ("bf16" / "f16"); wfrag_lo != NULL: the split product al*wh + ah*wl + ah*wh
+ * ("bf16x3", f32-grade at 3/16 of the f32 MFMA cost; SPEI_BF16 with fp32 activations only).
  * ln_input: LayerNorm(256) without affine (model/swinir.py:244, affine folded into the weights) is applied to each
  * 256-wide fp32 input row while it is staged, so the normalised tokens never exist in HBM. */
 int spei_conv_slab16(int fmt, const void* a0, int lda0, int k0, const void* a1, int lda1, int k1, int a_fmt,
@@ -109,16 +103,6 @@ int spei_conv_slab16(int fmt, const void* a0, int lda0, int k0, const void* a1, 
 int spei_conv_slab16_batched(int fmt, const void* a0, int k0, int a_fmt, const void* wfrag, const void* wfrag_lo, const float* bias,
                              void* out, int out_fmt, const float* residual, int batch, int Hin, int Win, int Hout, int Wout, int N,
                              int ksize, int stride, int pad, int act, spei_stream_t stream);
-
-/* The same convolution (stride 1, pad k/2, one dense fp32 input map, single-product arithmetic) with the PREVIOUS ResBlock's gated
- * residual sum folded into its staging (model/block.py:136-140 feeding the next block's first conv, :127-131):
- *     x'[p][c] = x[p][c] + x1[p][c] * (s[c] + g1[y][c] + g2[x][c]),    out = act(conv(x', w) + bias)
- * x' is what spei_resblock_apply would have written; every pixel of it is also stored to x_out (fp32 [H*W][K], must not alias x)
- * by the workgroup that owns it: the residual stream of the next block.  x1: 16-bit (fmt) [H*W][K]; s [K], g1 [H][K], g2 [W][K]
- * from spei_resblock_gates.  K in {32, 64, 128, 256}. */
-int spei_conv_slab16_fa(int fmt, const float* x, int K, const void* x1, const float* s, const float* g1, const float* g2,
-                        float* x_out, const void* wfrag, const float* bias, void* out, int ldo, int out_fmt, int H, int W, int N,
-                        int ksize, int act, spei_stream_t stream);
 
 /* 32 -> 32 channel 5x5 convolution (stride 1, zero padding 2), weight-stationary (round 4, csrc/conv32_ws16.hip): the two convs of a
  * ResBlock at full resolution (model/block.py:26-47,127-131 in model/recons_video_ori.py:26-43 inBlock and :72-75 outBlock) — every wave

@@ -10,6 +10,7 @@ calls `forward` from one Python thread per device, model/__init__.py:19-20; SURV
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from typing import Optional
 
 import torch
@@ -274,104 +275,99 @@ class CorrPlan:
             ctx.profile["families"].setdefault("correlation", []).append((f0, f1))
 
 
+@dataclasses.dataclass(frozen=True, slots=True, eq=False)
 class Ctx:
-    """Everything one forward call needs to know besides its tensors.  Immutable; `replace` derives a variant.
-
-    precision / corr_precision   see PRECISIONS / CORR_PRECISIONS above
-    device                       the ROCm device every tensor of the call lives on; kernels are launched on torch's current
-                                 stream OF THAT DEVICE, and every pointer handed to the C-ABI is checked against it
-    knobs (all default True; parity ablations switch them off one at a time, tools/ablate_parity.py; "16-bit" = the
-    single-product modes "bf16" / "f16"):
-      use_slab        slab-resident conv / linear kernel (conv_slab16.hip) instead of igemm_bf16.hip (bf16 / bf16x3 only)
-      bf16_storage    16-bit: tensors that ONLY feed the next GEMM / the attention kernel live in HBM as 16-bit
-      x1_bf16         16-bit: the ResBlock's conv2 output (read by the gate statistics and the apply pass) is 16-bit
-      fuse_mlp        16-bit: LayerNorm -> fc1 -> GELU -> fc2 -> +x in one kernel (mlp_fused16.hip)
-      fuse_attn       16-bit: LayerNorm -> q/kv GEMMs -> window attention -> proj -> +x in one kernel (attn_fused16.hip)
-      commute_upconv  16-bit: relu(conv1x1(bicubic_up(x))) evaluated as relu(bicubic_up(conv1x1(x)))
-      commute_any     (default OFF) the same in every arithmetic mode: set by stage overrides that run single layers of a 16-bit
-                      frame in split arithmetic (the f32-grade MODES keep the reference's order of operations)
-      fuse_apply      (default OFF) 16-bit: the gated residual sum of a ResBlock (all but the last of a stack) is computed inside the next
-                      block's first conv while that stages its input (spei_conv_slab16_fa) instead of by spei_resblock_apply.
-                      Bit-identical frames; measured no faster: 30.3 vs 30.15 ms per 720p frame
-      split_decode    "f16": decoder_second (3 ResBlocks at H/4, 128 channels) and the 1x1 / 3x3 glue convolutions of `_decode`
-                      (conv_lv*, search*: model/speinet.py:92-119) run in split arithmetic (bf16x3, f32-grade).  They are 2.4 % of the
-                      frame's FLOPs and where the half-operand error weighs most on the `_forwardb` branch: |dPSNR| against the
-                      reference on that branch 0.9-1.07e-3 dB -> 1.4-4.6e-4 (every golden <= 4.6e-4; profiles/r03_parity_ablation.txt),
-                      for 1.35 ms of a 30.3 ms frame.  Off: round 2's arithmetic (tests then hold 1e-3 dB with no margin on that branch)
-      batch_enc       16-bit: the frame's 7 encoder passes (6 without a sharp reference) go through every layer of the three encoder
-                      stages in ONE launch per layer (gridDim.y = pass; engine.enc_batched) instead of one launch per pass and layer:
-                      bit-identical frames, ~1000 fewer launches per frame, and at H/4 a launch has 3150 workgroups instead of 450
-                      (three resident rounds instead of half of one).  Off: round 2's per-pass launches on two streams
-      conv3_pipe      16-bit: the 256 -> 256 channel 3x3 convolutions of the Swin body (RSTB tail, conv_after_body) on fp32 token maps whose
-                      height is a multiple of 6 and width a multiple of 16 as a persistent pipelined kernel (spei_conv3x3_256_pipe16)
-      attn_win4       16-bit, with fuse_attn: the fused attention branch with four windows per workgroup and a batch of maps per launch
-                      (spei_attn_win4_16).  Off: round 2's two-window kernel, one map per launch (spei_attn_fused16)
-      conv32_ws       16-bit: the 32 -> 32 channel 5x5 convolutions (the ResBlock convs at full resolution: inBlock, outBlock) on the
-                      weight-stationary persistent kernel (spei_conv32_ws16: the layer's 51 KB of weights live in each wave's registers, nothing
-                      streams from L2 in the main loop).  Off: the slab kernel, which runs these layers at its weight intake
-      conv64_ws       16-bit: the 64 -> 64 channel 5x5 convolutions (the ResBlock convs at half resolution) on the weight-stationary
-                      persistent kernel (spei_conv64_ws16: the four waves of a workgroup hold the layer's 205 KB of weights between them).
-                      None (default): follow conv32_ws, so conv32_ws=False still puts every 5x5 layer on the slab kernel
-      corr_bf16       "f16" with corr "top2": the candidate pass of the correlation runs on bf16 operands (True, default) instead of
-                      f16.  The fp32 re-score decides the winner and S either way (G14: 16 more of 57600 positions differ, dPSNR
-                      +1e-6 dB); bf16 operands let the chip hold a ~7 % higher MFMA clock on the slab kernel (tools/bench_corr.py); on the diagonal
-                      kernel, which is not limited by the matrix pipe, the difference is 1-5 % (2.60-2.73 vs 2.73-2.76 ms)
-      corr_diag       corr "top2", reference map at least as high as the query map (SearchTransfer's maps of one size, SelfTransfer's
-                      rotated landscape map): the candidate pass is the diagonal-sliding kernel (corr_diag16.hip): each row-against-row term of the 3x3-patch score is computed once and
-                      shared by the three patch rows that use it — a third of the bmm's flops, same fp32 sums.  Off: the slab kernel
-    stage        {stage name: {field: value}} overrides applied by `for_stage` (engine: "enc", "swin", "search", "decode", and inside
-                 "decode" the stacks "dec2" (decoder_second), "dec1" (decoder_first), "out" (outBlock) and its final conv "tail")
-    profile      None, or {op name: [(start_event, end_event), ...]} filled on the launch stream (bench.py)
-    capture      None, or a dict that receives intermediate device tensors by name ("arg", "s": what SearchTransfer
-                 decided) for the parity tests; eager launches only
-    """
+    """Everything one forward call needs to know besides its tensors.  Immutable; `replace` derives a variant.  The knobs default to the
+    shipping configuration; parity ablations switch them off one at a time (tools/ablate_parity.py).  "16-bit" below = the
+    single-product modes "bf16" / "f16"."""
     ACT_NONE, ACT_RELU, ACT_GELU = ACT_NONE, ACT_RELU, ACT_GELU
     CONV, CONV_T = CONV, CONV_T
-    _FIELDS = ("precision", "corr_precision", "device", "use_slab", "bf16_storage", "x1_bf16", "fuse_mlp", "fuse_attn",
-               "commute_upconv", "commute_any", "corr_bf16", "corr_diag", "fuse_apply", "split_decode", "batch_enc", "attn_win4", "conv32_ws", "conv64_ws", "conv3_pipe", "stage", "profile", "capture")
     # stages of an f16 frame that run in split (bf16x3) arithmetic by default, see `split_decode`
     SPLIT_STAGES = ("glue", "dec2")
-    __slots__ = _FIELDS
 
-    def __init__(self, precision: str = "f32", corr_precision: str = "bf16x3", device=None, use_slab: bool = True,
-                 bf16_storage: bool = True, x1_bf16: bool = True, fuse_mlp: bool = True, fuse_attn: bool = True,
-                 commute_upconv: bool = True, commute_any: bool = False, corr_bf16: bool = True,
-                 corr_diag: bool = True, fuse_apply: bool = False, split_decode: bool = True, batch_enc: bool = True,
-                 attn_win4: bool = True, conv32_ws: bool = True, conv64_ws: Optional[bool] = None, conv3_pipe: bool = True,
-                 stage: Optional[dict] = None,
-                 profile: Optional[dict] = None, capture: Optional[dict] = None):
-        if precision not in PRECISIONS:
-            raise ValueError(f"unknown precision {precision!r}")
-        corr_precision = _CORR_ALIASES.get(corr_precision, corr_precision)
-        if corr_precision not in CORR_PRECISIONS:
-            raise ValueError(f"unknown correlation precision {corr_precision!r}")
+    # see PRECISIONS / CORR_PRECISIONS above
+    precision: str = "f32"
+    corr_precision: str = "bf16x3"
+    # the ROCm device every tensor of the call lives on; kernels are launched on torch's current stream OF THAT DEVICE, and every
+    # pointer handed to the C-ABI is checked against it.  None: the current device
+    device: Optional[torch.device] = None
+    # 16-bit: tensors that ONLY feed the next GEMM / the attention kernel live in HBM as 16-bit
+    bf16_storage: bool = True
+    # 16-bit: the ResBlock's conv2 output (read by the gate statistics and the apply pass) is 16-bit
+    x1_bf16: bool = True
+    # 16-bit: LayerNorm -> fc1 -> GELU -> fc2 -> +x in one kernel (mlp_fused16.hip)
+    fuse_mlp: bool = True
+    # 16-bit: LayerNorm -> q/kv GEMMs -> window attention -> proj -> +x in one kernel (attn_fused16.hip)
+    fuse_attn: bool = True
+    # 16-bit: relu(conv1x1(bicubic_up(x))) evaluated as relu(bicubic_up(conv1x1(x)))
+    commute_upconv: bool = True
+    # the same in every arithmetic mode: set by stage overrides that run single layers of a 16-bit frame in split arithmetic (the
+    # f32-grade MODES keep the reference's order of operations)
+    commute_any: bool = False
+    # "f16" with corr "top2": the candidate pass of the correlation runs on bf16 operands (True) instead of f16.  The fp32 re-score
+    # decides the winner and S either way (G14: 16 more of 57600 positions differ, dPSNR +1e-6 dB); bf16 operands let the chip hold a
+    # ~7 % higher MFMA clock on the slab kernel (tools/bench_corr.py); on the diagonal kernel, which is not limited by the matrix pipe,
+    # the difference is 1-5 % (2.60-2.73 vs 2.73-2.76 ms)
+    corr_bf16: bool = True
+    # corr "top2", reference map at least as high as the query map (SearchTransfer's maps of one size, SelfTransfer's rotated landscape
+    # map): the candidate pass is the diagonal-sliding kernel (corr_diag16.hip): each row-against-row term of the 3x3-patch score is
+    # computed once and shared by the three patch rows that use it — a third of the bmm's flops, same fp32 sums.  Off: the slab kernel
+    corr_diag: bool = True
+    # "f16": decoder_second (3 ResBlocks at H/4, 128 channels) and the 1x1 / 3x3 glue convolutions of `_decode` (conv_lv*, search*:
+    # model/speinet.py:92-119) run in split arithmetic (bf16x3, f32-grade).  They are 2.4 % of the frame's FLOPs and where the
+    # half-operand error weighs most on the `_forwardb` branch: |dPSNR| against the reference on that branch 0.9-1.07e-3 dB ->
+    # 1.4-4.6e-4 (every golden <= 4.6e-4; profiles/r03_parity_ablation.txt), for 1.35 ms of a 30.3 ms frame.  Off: round 2's arithmetic
+    # (tests then hold 1e-3 dB with no margin on that branch)
+    split_decode: bool = True
+    # 16-bit: the frame's 7 encoder passes (6 without a sharp reference) go through every layer of the three encoder stages in ONE launch
+    # per layer (gridDim.y = pass; engine.enc_batched) instead of one launch per pass and layer: bit-identical frames, ~1000 fewer
+    # launches per frame, and at H/4 a launch has 3150 workgroups instead of 450 (three resident rounds instead of half of one).
+    # Off: round 2's per-pass launches on two streams
+    batch_enc: bool = True
+    # 16-bit, with fuse_attn: the fused attention branch with four windows per workgroup and a batch of maps per launch
+    # (spei_attn_win4_16).  Off: round 2's two-window kernel, one map per launch (spei_attn_fused16)
+    attn_win4: bool = True
+    # 16-bit: the 32 -> 32 channel 5x5 convolutions (the ResBlock convs at full resolution: inBlock, outBlock) on the weight-stationary
+    # persistent kernel (spei_conv32_ws16: the layer's 51 KB of weights live in each wave's registers, nothing streams from L2 in the
+    # main loop).  Off: the slab kernel, which runs these layers at its weight intake
+    conv32_ws: bool = True
+    # 16-bit: the 64 -> 64 channel 5x5 convolutions (the ResBlock convs at half resolution) on the weight-stationary persistent kernel
+    # (spei_conv64_ws16: the four waves of a workgroup hold the layer's 205 KB of weights between them).  None: follow conv32_ws, so
+    # conv32_ws=False still puts every 5x5 layer on the slab kernel
+    conv64_ws: Optional[bool] = None
+    # 16-bit: the 256 -> 256 channel 3x3 convolutions of the Swin body (RSTB tail, conv_after_body) on fp32 token maps whose height is a
+    # multiple of 6 and width a multiple of 16 as a persistent pipelined kernel (spei_conv3x3_256_pipe16)
+    conv3_pipe: bool = True
+    # {stage name: {field: value}} overrides applied by `for_stage` (engine: "enc", "swin", "search", "decode", and inside "decode" the
+    # stacks "dec2" (decoder_second), "dec1" (decoder_first), "out" (outBlock) and its final conv "tail")
+    stage: Optional[dict] = None
+    # None, or {op name: [(start_event, end_event), ...]} filled on the launch stream (bench.py)
+    profile: Optional[dict] = None
+    # None, or a dict that receives intermediate device tensors by name ("arg", "s": what SearchTransfer decided) for the parity
+    # tests; eager launches only
+    capture: Optional[dict] = None
+
+    def __post_init__(self):
+        put = object.__setattr__
+        if self.precision not in PRECISIONS:
+            raise ValueError(f"unknown precision {self.precision!r}")
+        put(self, "corr_precision", _CORR_ALIASES.get(self.corr_precision, self.corr_precision))
+        if self.corr_precision not in CORR_PRECISIONS:
+            raise ValueError(f"unknown correlation precision {self.corr_precision!r}")
         cur = torch.cuda.current_device() if torch.cuda.is_available() else 0
-        device = torch.device("cuda", cur) if device is None else torch.device(device)
-        if precision == "f16" and not use_slab:
-            raise ValueError("the f16 mode is built on the slab kernels only")
+        device = torch.device("cuda", cur) if self.device is None else torch.device(self.device)
         if device.type != "cuda":
             raise RuntimeError("speinet_amd runs on MI355X only (HIP kernels); there is no CPU path")
-        if device.index is None:
-            device = torch.device("cuda", cur)
-        object.__setattr__(self, "precision", precision)
-        object.__setattr__(self, "corr_precision", corr_precision)
-        object.__setattr__(self, "device", device)
-        for k, v in (("use_slab", use_slab), ("bf16_storage", bf16_storage), ("x1_bf16", x1_bf16), ("fuse_mlp", fuse_mlp),
-                     ("fuse_attn", fuse_attn), ("commute_upconv", commute_upconv), ("commute_any", commute_any),
-                     ("corr_bf16", corr_bf16), ("corr_diag", corr_diag), ("fuse_apply", fuse_apply), ("split_decode", split_decode), ("batch_enc", batch_enc), ("attn_win4", attn_win4), ("conv32_ws", conv32_ws), ("conv3_pipe", conv3_pipe)):
-            object.__setattr__(self, k, bool(v))
-        object.__setattr__(self, "conv64_ws", None if conv64_ws is None else bool(conv64_ws))
-        object.__setattr__(self, "stage", dict(stage) if stage else {})
-        object.__setattr__(self, "profile", profile)
-        object.__setattr__(self, "capture", capture)
-
-    def __setattr__(self, k, v):
-        raise AttributeError("Ctx is immutable; use replace()")
+        put(self, "device", torch.device("cuda", cur) if device.index is None else device)
+        for k in _BOOL_KNOBS:
+            if type(getattr(self, k)) is not bool:
+                put(self, k, bool(getattr(self, k)))
+        if self.conv64_ws is not None:
+            put(self, "conv64_ws", bool(self.conv64_ws))
+        put(self, "stage", dict(self.stage) if self.stage else {})
 
     def replace(self, **kw) -> "Ctx":
-        d = {k: getattr(self, k) for k in self._FIELDS}
-        d.update(kw)
-        return Ctx(**d)
+        return dataclasses.replace(self, **kw)
 
     def for_stage(self, name: str) -> "Ctx":
         o = self.stage.get(name)
@@ -412,7 +408,7 @@ class Ctx:
 
     def inter_dtype(self) -> torch.dtype:
         """Storage type of GEMM-only intermediates (x-hat, q, kv, attention output, MLP hidden, ResBlock conv1 output)."""
-        return LP_DTYPE[self.fmt] if (self.lp16 and self.use_slab and self.bf16_storage) else torch.float32
+        return LP_DTYPE[self.fmt] if (self.lp16 and self.bf16_storage) else torch.float32
 
     # ---- K15 / K1 / first and last conv ------------------------------------------------------------------------
     def any_nonzero(self, x: torch.Tensor, flag: torch.Tensor) -> None:
@@ -444,7 +440,7 @@ class Ctx:
         """Last conv, NHWC 32 channels -> three NCHW planes.  w32 / b32 (weights zero-padded to 32 output channels,
         packed): the 16-bit modes run the layer on the slab kernel."""
         assert out.shape == (3, f.H, f.W) and out.is_contiguous() and out.dtype == torch.float32
-        if self.lp16 and self.use_slab and w32 is not None and f.C == 32:
+        if self.lp16 and w32 is not None and f.C == 32:
             _lib.check(_lib.lib().spei_conv5_out_slab16(self.fmt, self._fp(f), f.ld, f.fmt, self._tp(w32.frag(self.fmt)), self._tp(b32),
                                                        self._tp(out), f.H, f.W, self._stream()), "spei_conv5_out_slab16")
             return out
@@ -457,12 +453,38 @@ class Ctx:
     # ---- the GEMM family ---------------------------------------------------------------------------------------
     def _conv3_pipe_ok(self, a, w, N: int, ksize: int, stride: int, act: int, residual, out) -> bool:
         """The persistent 3x3 / 256-channel kernel takes the call: dense fp32 maps, 6 x 16 pixel tiles cover the map, 16-bit single products."""
-        return (self.conv3_pipe and self.lp16 and self.use_slab and ksize == 3 and stride == 1 and N == 256 and a.C == 256 and act == ACT_NONE
+        return (self.conv3_pipe and self.lp16 and ksize == 3 and stride == 1 and N == 256 and a.C == 256 and act == ACT_NONE
                 and a.H % 6 == 0 and a.W % 16 == 0 and a.H * a.W <= (1 << 21) and a.t.dtype == torch.float32 and getattr(a, "ld", 256) == 256
                 and getattr(a, "off", 0) == 0 and getattr(w, "fhi", None) is not None and tuple(w.shape) == (9, 256, 256)
                 and (out is None or (out.t.dtype == torch.float32 and getattr(out, "ld", 256) == 256 and getattr(out, "off", 0) == 0
                                      and out.t.data_ptr() != a.t.data_ptr()))
                 and (residual is None or (residual.t.dtype == torch.float32 and getattr(residual, "ld", 256) == 256 and getattr(residual, "off", 0) == 0)))
+
+    def _persistent_conv(self, a, w, bias, N: int, ksize: int, stride: int, act: int, residual, out, batch: int) -> bool:
+        """Launch the persistent kernel that takes this conv layer, if one does: the pipelined 3x3 / 256-channel kernel or the
+        weight-stationary 5x5 kernels for 32 / 64 channels.  a, out, residual: FMaps (batch 1) or BMaps of `batch` maps, each spanning
+        its whole buffer, `out` not `a`; the caller has a one-source conv without row scale or LayerNorm staging.  False: nothing
+        launched, the slab kernel runs the layer."""
+        tp, lib, f = self._tp, _lib.lib(), self.fmt
+        if self._conv3_pipe_ok(a, w, N, ksize, stride, act, residual, out):
+            _lib.check(lib.spei_conv3x3_256_pipe16(f, tp(a.t), tp(w.frag(f)), tp(bias), tp(residual.t) if residual is not None else _vp(0),
+                                                   tp(out.t), batch, a.H, a.W, self._stream()), "spei_conv3x3_256_pipe16")
+            return True
+        if not (ksize == 5 and stride == 1 and a.C == N and residual is None and act in (ACT_NONE, ACT_RELU) and w.fhi is not None
+                and (getattr(a, "ld", N), getattr(a, "off", 0), getattr(out, "ld", N), getattr(out, "off", 0)) == (N, 0, N, 0)
+                and a.t.data_ptr() != out.t.data_ptr()):
+            return False
+        if N == 32 and self.conv32_ws_available():
+            # the 32-channel 5x5 layers: weight-stationary persistent kernel (csrc/conv32_ws16.hip)
+            _lib.check(lib.spei_conv32_ws16(f, tp(a.t), a.fmt, tp(w.frag(f)), tp(bias), tp(out.t), out.fmt, batch, a.H, a.W, act,
+                                            self._stream()), "spei_conv32_ws16")
+            return True
+        if N == 64 and self.conv64_ws_available():
+            # the 64-channel 5x5 layers: weight-stationary persistent kernel (csrc/conv64_ws16.hip)
+            _lib.check(lib.spei_conv64_ws16(f, tp(a.t), a.fmt, tp(w.frag(f)), tp(bias), tp(out.t), out.fmt, batch, a.H, a.W, act,
+                                            self._stream()), "spei_conv64_ws16")
+            return True
+        return False
 
     @_family("conv")
     def igemm(self, a0: FMap, w, bias: Optional[torch.Tensor], N: int, ksize: int = 1, stride: int = 1,
@@ -479,8 +501,8 @@ class Ctx:
             out = FMap.empty(ho, wo, N, a0.t.device, out_dtype)
         assert out.H == ho and out.W == wo and out.C == N
         k0, k1 = a0.C, (a1.C if a1 is not None else 0)
-        slab = prec != "f32" and self.use_slab and mode == CONV
-        assert slab or (mode == CONV_T and self.lp16 and self.use_slab) or not (a0.lp or out.lp), \
+        slab = prec != "f32" and mode == CONV
+        assert slab or (mode == CONV_T and self.lp16) or not (a0.lp or out.lp), \
             "16-bit activations are only supported by the slab kernel"
         assert a1 is None or a1.t.dtype == a0.t.dtype
         assert residual is None or not residual.lp
@@ -496,34 +518,19 @@ class Ctx:
         if rowscale is not None:
             assert rowscale.numel() == ho * wo
         tp, fp = self._tp, self._fp
-        common = (fp(out), out.ld, fp(residual), residual.ld if residual is not None else 0, tp(rowscale), a0.H, a0.W, ho, wo, N,
-                  ksize, stride, pad, mode, act, self._stream())
         srcs = (fp(a0), a0.ld, k0, fp(a1), a1.ld if a1 is not None else 0, k1)
         lib = _lib.lib()
-        if (mode == CONV and a1 is None and rowscale is None and not ln_input and out_dtype == torch.float32
-                and self._conv3_pipe_ok(a0, w, N, ksize, stride, act, residual, out)):
-            _lib.check(lib.spei_conv3x3_256_pipe16(self.fmt, fp(a0), tp(w.frag(self.fmt)), tp(bias), fp(residual), fp(out), 1, a0.H, a0.W,
-                                                   self._stream()), "spei_conv3x3_256_pipe16")
-        elif (self.conv32_ws_available() and mode == CONV and ksize == 5 and stride == 1 and k0 == 32 and N == 32 and a1 is None
-                and residual is None and rowscale is None and not ln_input and act in (ACT_NONE, ACT_RELU) and w.fhi is not None
-                and (a0.ld, a0.off, out.ld, out.off) == (32, 0, 32, 0) and a0.t.data_ptr() != out.t.data_ptr()):
-            # the 32-channel 5x5 layers: weight-stationary persistent kernel (csrc/conv32_ws16.hip)
-            _lib.check(lib.spei_conv32_ws16(self.fmt, fp(a0), a0.fmt, tp(w.frag(self.fmt)), tp(bias), fp(out), out.fmt, 1, a0.H, a0.W, act,
-                                            self._stream()), "spei_conv32_ws16")
-        elif (self.conv64_ws_available() and mode == CONV and ksize == 5 and stride == 1 and k0 == 64 and N == 64 and a1 is None
-                and residual is None and rowscale is None and not ln_input and act in (ACT_NONE, ACT_RELU) and w.fhi is not None
-                and (a0.ld, a0.off, out.ld, out.off) == (64, 0, 64, 0) and a0.t.data_ptr() != out.t.data_ptr()):
-            # the 64-channel 5x5 layers: weight-stationary persistent kernel (csrc/conv64_ws16.hip)
-            _lib.check(lib.spei_conv64_ws16(self.fmt, fp(a0), a0.fmt, tp(w.frag(self.fmt)), tp(bias), fp(out), out.fmt, 1, a0.H, a0.W, act,
-                                            self._stream()), "spei_conv64_ws16")
-        elif (mode == CONV_T and self.lp16 and self.use_slab and ksize == 3 and stride == 2 and a1 is None and residual is None
+        if (mode == CONV and a1 is None and rowscale is None and not ln_input
+                and self._persistent_conv(a0, w, bias, N, ksize, stride, act, residual, out, 1)):
+            return out
+        if (mode == CONV_T and self.lp16 and ksize == 3 and stride == 2 and a1 is None and residual is None
                 and rowscale is None and N % 32 == 0 and k0 % 32 == 0):
             # stride-2 transposed conv = four stride-1 convs (one per output parity) on the slab kernel
             cf = w.convT_class_frags(self.fmt)
             _lib.check(lib.spei_convt2_slab16(self.fmt, fp(a0), a0.ld, k0, a0.fmt, tp(cf[(0, 0)]), tp(cf[(0, 1)]), tp(cf[(1, 0)]),
                                               tp(cf[(1, 1)]), tp(bias), fp(out), out.ld, out.fmt, a0.H, a0.W, N, act,
                                               self._stream()), "spei_convt2_slab16")
-        elif (mode == CONV_T and prec == "bf16x3" and self.use_slab and ksize == 3 and stride == 2 and a1 is None and residual is None
+        elif (mode == CONV_T and prec == "bf16x3" and ksize == 3 and stride == 2 and a1 is None and residual is None
                 and rowscale is None and N % 32 == 0 and k0 % 32 == 0 and not a0.lp and not out.lp):
             # the same in split arithmetic (the transposed conv that ends decoder_second inside an f16 frame's split stages; round 1's igemm
             # kernel took 327 us for it)
@@ -531,7 +538,8 @@ class Ctx:
             _lib.check(lib.spei_convt2_slab16x3(fp(a0), a0.ld, k0, ph, pl, tp(bias), fp(out), out.ld, a0.H, a0.W, N, act, self._stream()),
                        "spei_convt2_slab16x3")
         elif prec == "f32":
-            _lib.check(lib.spei_igemm_f32(*srcs, tp(w.f32), tp(bias), *common), "spei_igemm_f32")
+            _lib.check(lib.spei_igemm_f32(*srcs, tp(w.f32), tp(bias), fp(out), out.ld, fp(residual), residual.ld if residual is not None else 0,
+                                          tp(rowscale), a0.H, a0.W, ho, wo, N, ksize, stride, pad, mode, act, self._stream()), "spei_igemm_f32")
         elif slab and w.fhi is not None:
             dims = (a0.H * a0.W, 1, ho * wo, 1) if (ksize == 1 and stride == 1) else (a0.H, a0.W, ho, wo)
             _lib.check(lib.spei_conv_slab16(
@@ -539,9 +547,8 @@ class Ctx:
                 out.fmt, fp(residual), residual.ld if residual is not None else 0,
                 tp(rowscale), *dims, N, ksize, stride, pad, act, int(ln_input), self._stream()), "spei_conv_slab16")
         else:
-            assert prec != "f16", "f16: N and K must be multiples of 32 (slab kernel)"
-            _lib.check(lib.spei_igemm_bf16(*srcs, tp(w.hi), tp(w.lo) if prec == "bf16x3" else _vp(0), tp(bias), *common),
-                       "spei_igemm_bf16")
+            raise ValueError(f"no {prec} kernel for N={N} K={k0 + k1} ksize={ksize} stride={stride} mode={mode}: N and K must be multiples "
+                             "of 32; transposed convs 3x3 stride 2")
         return out
 
     def linear(self, x: torch.Tensor, w, b: Optional[torch.Tensor], act: int = ACT_NONE,
@@ -574,36 +581,14 @@ class Ctx:
                                            tp(s), tp(g1), tp(g2), tp(ws), self._stream()), "spei_resblock_gates")
         return s, g1, g2
 
-    def apply_fused_available(self, c: int) -> bool:
-        """The gated residual sum of a ResBlock can ride in the NEXT block's first conv (spei_conv_slab16_fa): 16-bit modes on the
-        slab kernel with a 16-bit x1."""
-        return self.lp16 and self.use_slab and self.x1_bf16 and self.fuse_apply and c in (32, 64, 128, 256)
-
-    def resblock(self, x, pk: dict, extra: Optional[FMap] = None, out: Optional[FMap] = None, defer: bool = False):
-        """x + SE(x1) + TE(x1), x1 = conv5(relu(conv5(x)))  (reference model/block.py:127-140).
-
-        `x` is a map, or the deferred tail of the previous block — a tuple (x, x1, s, g1, g2): then this block's first conv computes
-        that block's output while it stages its input (one kernel fewer, one fp32 map round trip fewer) and writes it back as the
-        residual stream.  `defer=True` returns this block's own tail instead of applying it (the caller passes it to the next)."""
+    def resblock(self, x: FMap, pk: dict, extra: Optional[FMap] = None, out: Optional[FMap] = None) -> FMap:
+        """x + SE(x1) + TE(x1), x1 = conv5(relu(conv5(x)))  (reference model/block.py:127-140)."""
         idt = self.inter_dtype()
-        if isinstance(x, tuple):
-            px, px1, ps, pg1, pg2 = x
-            c = px.C
-            xn = FMap.empty(px.H, px.W, c, px.t.device)
-            t = FMap.empty(px.H, px.W, c, px.t.device, idt)
-            w1 = pk["w1"] if not torch.is_tensor(pk["w1"]) else PackedW(pk["w1"], px.t.device)
-            _lib.check(_lib.lib().spei_conv_slab16_fa(self.fmt, self._fp(px), c, self._fp(px1), self._tp(ps), self._tp(pg1), self._tp(pg2),
-                                                      self._fp(xn), self._tp(w1.frag(self.fmt)), self._tp(pk["b1"]), self._fp(t), t.ld, t.fmt,
-                                                      px.H, px.W, c, 5, ACT_RELU, self._stream()), "spei_conv_slab16_fa")
-            x = xn
-        else:
-            c = x.C
-            assert x.off == 0 and x.ld == c
-            t = self.igemm(x, pk["w1"], pk["b1"], c, ksize=5, act=ACT_RELU, out_dtype=idt)   # only conv2 reads it
+        c = x.C
+        assert x.off == 0 and x.ld == c
+        t = self.igemm(x, pk["w1"], pk["b1"], c, ksize=5, act=ACT_RELU, out_dtype=idt)   # only conv2 reads it
         x1 = self.igemm(t, pk["w2"], pk["b2"], c, ksize=5, out_dtype=idt if self.x1_bf16 else torch.float32)
         s, g1, g2 = self.resblock_gates(x1, pk)
-        if defer:
-            return (x, x1, s, g1, g2)
         if out is None:
             out = FMap.empty(x.H, x.W, c, x.t.device)
         if extra is not None:
@@ -620,19 +605,19 @@ class Ctx:
     # ---- the same stacks on several maps per launch (the frame's encoder passes) -------------------------------------------------
     def batched_available(self) -> bool:
         """One launch per layer for all maps of a BMap (the frame's encoder passes): the single-product 16-bit modes on the slab kernel."""
-        return self.batched_kernels() and self.x1_bf16 and self.bf16_storage and not self.fuse_apply and self.batch_enc
+        return self.batched_kernels() and self.x1_bf16 and self.bf16_storage and self.batch_enc
 
     def conv32_ws_available(self) -> bool:
         """The weight-stationary kernel for 32 -> 32 channel 5x5 layers (single-product 16-bit modes)."""
-        return self.lp16 and self.use_slab and self.conv32_ws
+        return self.lp16 and self.conv32_ws
 
     def conv64_ws_available(self) -> bool:
         """The weight-stationary kernel for 64 -> 64 channel 5x5 layers (single-product 16-bit modes; `conv64_ws` None follows `conv32_ws`)."""
-        return self.lp16 and self.use_slab and (self.conv32_ws if self.conv64_ws is None else self.conv64_ws)
+        return self.lp16 and (self.conv32_ws if self.conv64_ws is None else self.conv64_ws)
 
     def batched_kernels(self) -> bool:
         """`igemm_batched` can run (what the batched Swin calls need; `batch_enc` only decides about the encoder passes)."""
-        return self.lp16 and self.use_slab
+        return self.lp16
 
     @_family("conv")
     def igemm_batched(self, a: BMap, w, bias: torch.Tensor, N: int, ksize: int, stride: int = 1, act: int = ACT_NONE,
@@ -650,20 +635,7 @@ class Ctx:
             assert (residual.B, residual.H, residual.W, residual.C) == (a.B, ho, wo, N) and residual.t.dtype == torch.float32
             assert residual.t.data_ptr() != a.t.data_ptr()
         tp = self._tp
-        if out_dtype == torch.float32 and self._conv3_pipe_ok(a, w, N, ksize, stride, act, residual, out):
-            _lib.check(_lib.lib().spei_conv3x3_256_pipe16(self.fmt, tp(a.t), tp(w.frag(self.fmt)), tp(bias),
-                                                          tp(residual.t) if residual is not None else _vp(0), tp(out.t), a.B, a.H, a.W,
-                                                          self._stream()), "spei_conv3x3_256_pipe16")
-            return out
-        if (self.conv32_ws_available() and ksize == 5 and stride == 1 and a.C == 32 and N == 32 and residual is None
-                and act in (ACT_NONE, ACT_RELU)):
-            _lib.check(_lib.lib().spei_conv32_ws16(self.fmt, tp(a.t), a.fmt, tp(w.frag(self.fmt)), tp(bias), tp(out.t), out.fmt, a.B, a.H, a.W,
-                                                   act, self._stream()), "spei_conv32_ws16")
-            return out
-        if (self.conv64_ws_available() and ksize == 5 and stride == 1 and a.C == 64 and N == 64 and residual is None
-                and act in (ACT_NONE, ACT_RELU)):
-            _lib.check(_lib.lib().spei_conv64_ws16(self.fmt, tp(a.t), a.fmt, tp(w.frag(self.fmt)), tp(bias), tp(out.t), out.fmt, a.B, a.H, a.W,
-                                                   act, self._stream()), "spei_conv64_ws16")
+        if self._persistent_conv(a, w, bias, N, ksize, stride, act, residual, out, a.B):
             return out
         _lib.check(_lib.lib().spei_conv_slab16_batched(self.fmt, tp(a.t), a.C, a.fmt, tp(w.frag(self.fmt)), _vp(0), tp(bias), tp(out.t), out.fmt,
                                                        tp(residual.t) if residual is not None else _vp(0), a.B, a.H, a.W, ho, wo, N, ksize,
@@ -702,13 +674,13 @@ class Ctx:
     # ---- Swin (K6-K9) ------------------------------------------------------------------------------------------
     def ln_fused_available(self) -> bool:
         """LayerNorm folded into the staging of the following 256-wide linear (slab kernel, every mode but f32)."""
-        return self.precision != "f32" and self.use_slab
+        return self.precision != "f32"
 
     def attn_fused_available(self) -> bool:
-        return self.lp16 and self.use_slab and self.fuse_attn and self.bf16_storage
+        return self.lp16 and self.fuse_attn and self.bf16_storage
 
     def mlp_fused_available(self) -> bool:
-        return self.lp16 and self.use_slab and self.fuse_mlp
+        return self.lp16 and self.fuse_mlp
 
     def swin_multi_available(self) -> bool:
         """The Swin calls of a frame as one batch over stacked maps (engine.swin_multi): needs the batched attention kernel."""
@@ -784,7 +756,7 @@ class Ctx:
         s = torch.empty(n, device=dev)
         arg = torch.empty(n, device=dev, dtype=torch.int32)
         dims = (lr.H, lr.W, ref.H, ref.W, lr.C)
-        rescore = self.precision != "f32" and self.corr_precision == "top2" and self.use_slab and lr.C == 128
+        rescore = self.precision != "f32" and self.corr_precision == "top2" and lr.C == 128
         # the diagonal kernel keeps one candidate pair per (query, diagonal, reference tile): 415 MB at 720p, ~34 GB at 4K — beyond the
         # budget (a quarter of the device's free memory, at most 8 GiB) the slab kernel takes over (its workspace is per query only)
         diag, diag_floats = False, 0
@@ -798,7 +770,7 @@ class Ctx:
                             (lr, ref, inv_lr, inv_ref, ws))
         split = self.corr_precision == "bf16x3"
         f16 = BF16 if (rescore and self.corr_bf16) else self.fmt
-        assert f16 == BF16 or (not split and self.use_slab and lr.C == 128), "f16 correlation: slab kernel, single / top2"
+        assert f16 == BF16 or (not split and lr.C == 128), "f16 correlation: slab kernel, single / top2"
         parts = []
         for f in (lr, ref):
             hi = torch.empty(f.H * f.W, f.C, device=dev, dtype=LP_DTYPE[f16])
@@ -820,7 +792,7 @@ class Ctx:
             return CorrPlan(self, s, arg, f"corr_{'diag' if diag else 'slab'}_kernel<top2, {fname}>", [main], [post],
                             (lr, ref, inv_lr, inv_ref, ws, parts, s2, arg2))
         args = (tp(parts[0]), tp(parts[1]), tp(parts[2]), tp(parts[3]), tp(inv_lr), tp(inv_ref), *dims, tp(s), tp(arg), tp(ws))
-        if self.use_slab and lr.C == 128:
+        if lr.C == 128:
             main = (lib.spei_corr_slab16, "spei_corr_slab16", (f16, *args))
             kname = f"corr_slab_kernel<{'bf16x3' if split else 'top1, ' + fname}>"
         else:
@@ -866,3 +838,6 @@ class Ctx:
         assert out.shape == a.shape == b.shape and out.dtype == a.dtype == torch.float32
         _lib.check(_lib.lib().spei_add(self._tp(a), self._tp(b), self._tp(out), a.numel(), self._stream()), "spei_add")
         return out
+
+
+_BOOL_KNOBS = tuple(f.name for f in dataclasses.fields(Ctx) if f.type in (bool, "bool"))      # Ctx.__post_init__ coerces these to bool

@@ -42,21 +42,26 @@ def _frag(w: torch.Tensor) -> torch.Tensor:
     return w.view(t, n // 32, 32, k // 16, 2, 8).permute(1, 0, 3, 4, 2, 5).contiguous()
 
 
+def _split_bf16(w: torch.Tensor):
+    """fp32 -> (hi, lo) bf16 with lo = bf16(w - hi): the two weight operands of the split "bf16x3" product."""
+    hi = w.to(torch.bfloat16)
+    return hi, (w - hi.float()).to(torch.bfloat16)
+
+
 class PackedW:
-    """Device copies of one GEMM weight: f32 for the exact path; bf16 hi / lo (= bf16(w - hi)) plain and in fragment
-    order for the bf16 / bf16x3 modes; half in fragment order for the f16 mode (`frag(fmt)`)."""
-    __slots__ = ("f32", "hi", "lo", "shape", "fhi", "flo", "fh16", "_ct")
+    """Device copies of one GEMM weight: f32 for the exact path; in fragment order, when N and K are multiples of 32, bf16 hi / lo
+    (= bf16(w - hi)) for the bf16 / bf16x3 modes and half for the f16 mode (`frag(fmt)`)."""
+    __slots__ = ("f32", "shape", "fhi", "flo", "fh16", "_ct")
 
     def __init__(self, t: torch.Tensor, device):
         self.f32 = t.detach().to(device=device, dtype=torch.float32).contiguous()
-        self.hi = self.f32.to(torch.bfloat16)
-        self.lo = (self.f32 - self.hi.float()).to(torch.bfloat16)
         self.shape = tuple(self.f32.shape)
         t, n, k = self.shape
         self.fhi = self.flo = self.fh16 = None
         self._ct = {}
         if n % 32 == 0 and k % 32 == 0:
-            self.fhi, self.flo = _frag(self.hi), _frag(self.lo)
+            hi, lo = _split_bf16(self.f32)
+            self.fhi, self.flo = _frag(hi), _frag(lo)
             self.fh16 = _frag(self.f32.to(torch.float16))
 
     def frag(self, fmt: int):
@@ -84,7 +89,7 @@ class PackedW:
         """(hi, lo) class fragments for the split (bf16x3) form, spei_convt2_slab16x3, + the two device arrays of four pointers it takes."""
         if "split" not in self._ct:
             assert self.shape[0] == 9
-            hi, lo = self._class_frags(self.hi), self._class_frags(self.lo)
+            hi, lo = (self._class_frags(w) for w in _split_bf16(self.f32))
             order = [(0, 0), (0, 1), (1, 0), (1, 1)]
             import ctypes as C
             ph = (C.c_void_p * 4)(*[hi[k].data_ptr() for k in order])

@@ -3,6 +3,7 @@ import ctypes
 
 import numpy as np
 import os
+import re
 
 import pytest
 import torch
@@ -29,6 +30,35 @@ def test_library_exports_every_declared_symbol(lib_path):
     assert sorted(_lib.SIGNATURES) == declared, "ctypes signature table and header disagree"
     assert _lib.lib().spei_arch() == b"gfx950"
     assert _lib.lib().spei_version() >= 100
+
+
+def test_ctypes_signatures_follow_the_header():
+    """`_lib.SIGNATURES` is parsed from include/speinet_hip.h: literal pins for every type case, the argument count of every entry
+    against the declaration as written, and a refusal to guess at a type the parser does not know."""
+    P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    pins = {
+        "spei_version": (I, []),
+        "spei_last_error": (ctypes.c_char_p, []),
+        "spei_arch": (ctypes.c_char_p, []),
+        "spei_any_nonzero": (I, [P, L, P, P]),
+        "spei_rl_prior": (I, [P, P, P, I, I, I, I, F, P]),
+        "spei_ln_bwd_blocks": (L, [L]),
+        "spei_frame_metrics_ws_doubles": (L, [I, I, I]),
+        "spei_convt2_slab16x3": (I, [P, I, I, P, P, P, P, I, I, I, I, I, P]),      # `const void* const*` parameters
+        "spei_frames_u8_in": (I, [P, L, P, P, I, I, I, P]),
+    }
+    for name, sig in pins.items():
+        assert _lib.SIGNATURES[name] == sig, name
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+    for name, (_res, args) in _lib.SIGNATURES.items():
+        decls = re.findall(r"\b%s\s*\(([^)]*)\)\s*;" % name, text)
+        assert len(decls) == 1, name
+        written = decls[0].strip()
+        assert len(args) == (0 if written in ("", "void") else written.count(",") + 1), name
+    for bad in ("int spei_x(unsigned n, spei_stream_t stream);", "double spei_x(int n);", "int spei_x(long long n);", "float* spei_x(void);"):
+        with pytest.raises(ValueError):
+            _lib.parse_header(bad)
+    assert _lib.parse_header("int64_t spei_x(const float* a, int32_t n, float f, spei_stream_t s);") == {"spei_x": (L, [P, I, F, P])}
 
 
 def test_state_dict_layout_matches_reference_inventory():
