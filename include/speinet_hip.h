@@ -462,6 +462,38 @@ int spei_frames_u8_in(const unsigned char* src, int64_t frame_stride, float* dst
  * stream, then nonzero iff the crop held a NaN or an infinity. */
 int spei_frame_u8_out(const float* src, unsigned char* dst, int* nonfinite, int H, int W, int Hp, int Wp, spei_stream_t stream);
 
+/* ---- training on a dataset (speinet_amd/data.py, speinet_amd/fit.py) ---- */
+
+/* One output frame of a training batch: a P x P rectangle of one uint8 [H][W][3] frame on the device. */
+#define SPEI_CROP_HFLIP 1 /* [:, ::-1] */
+#define SPEI_CROP_VFLIP 2 /* [::-1, :] */
+#define SPEI_CROP_ROT90 4 /* np.rot90: counter-clockwise, out[i][j] = in[j][P-1-i] */
+#define SPEI_CROP_ZERO 8  /* the frame is all zeros; nothing is read */
+typedef struct {
+    uint64_t src;  /* device address of the frame's first byte */
+    int32_t pitch; /* bytes from one row to the next (>= 3 W) */
+    int32_t y0, x0; /* top-left corner of the rectangle */
+    int32_t flags; /* SPEI_CROP_* */
+    int32_t H, W;  /* the frame's size: the rectangle is checked against it on the host */
+} spei_crop_record;
+
+/* The batch the reference's loader builds per sample on its workers (util/utils.py:8-65 get_patch, np2Tensor, data_augment;
+ * data/videodata_nfs.py:180-207 __getitem__), in one launch: record r < n_in -> input [n_in][3][P][P], record n_in + r -> gt
+ * [n_gt][3][P][P], both fp32 and 16-byte aligned.  Value (float)u * (float)(rgb_range / 255), bit-identical to np2Tensor; geometry
+ * in the reference's order: crop, hflip, vflip, rot90.  P % 4 == 0 (the reference's size_must_mode = 4 crop is then the identity).
+ * table: n_in + n_gt records on the device; table_host: the same records in HOST memory, against which every rectangle is checked
+ * before anything is launched (a record that leaves its frame is an error, never a kernel's fault). */
+int spei_train_batch_u8(const spei_crop_record* table, const spei_crop_record* table_host, int n_in, int n_gt, float* input, float* gt,
+                        int P, float rgb_range, spei_stream_t stream);
+
+/* The reference's validation metric (util/utils.py:81-92 calc_psnr, trainer/trainer_swint_hsa_nsf.py:73) on the model's FLOAT output,
+ * unclamped and unquantised: a, b fp32 [3][H][W]; d = a / rgb_range - b / rgb_range in fp32 over rows and columns [shave, size - shave);
+ * result[0] = the sum of d * d in float64 (fixed order), result[1] = the number of terms.  PSNR = 100 if the sum is 0, else
+ * 20 log10(1 / sqrt(sum / count)).  ws: SPEI_PSNR_WS_DOUBLES doubles. */
+#define SPEI_PSNR_WS_DOUBLES 256
+int spei_psnr_f32(const float* a, const float* b, int H, int W, int shave, float rgb_range, double* ws, double* result,
+                  spei_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

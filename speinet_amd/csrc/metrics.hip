@@ -109,7 +109,57 @@ __global__ __launch_bounds__(256) void metrics_final_kernel(const double* __rest
 
 constexpr int SQ_BLOCKS = 512;
 
+// calc_psnr of the training loop (util/utils.py:81-92): the float frames themselves, shaved; d in fp32 as numpy computes it, d * d exact
+// in float64, summed in a fixed order (lanes, waves, then the blocks' partials in the second launch)
+__global__ __launch_bounds__(256) void psnr_f32_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W, int shave,
+                                                        float rgb_range, double* __restrict__ part) {
+    const int ch = H - 2 * shave, cw = W - 2 * shave;
+    const int64_t n = (int64_t)3 * ch * cw;
+    double sq = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / cw;                         // c * ch + y
+        const int x = (int)(i - row * cw), c = (int)(row / ch), y = (int)(row - (int64_t)c * ch);
+        const int64_t o = ((int64_t)c * H + y + shave) * W + x + shave;
+        const float d = __fsub_rn(__fdiv_rn(a[o], rgb_range), __fdiv_rn(b[o], rgb_range));
+        sq += (double)d * (double)d;
+    }
+    __shared__ double s_sq[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    if ((threadIdx.x & 63) == 0) s_sq[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (s_sq[0] + s_sq[1]) + (s_sq[2] + s_sq[3]);
+}
+
+__global__ __launch_bounds__(256) void psnr_f32_final_kernel(const double* __restrict__ part, double count, double* __restrict__ result) {
+    __shared__ double s[4];
+    double sq = part[threadIdx.x];                         // SPEI_PSNR_WS_DOUBLES == 256 partials
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        result[0] = (s[0] + s[1]) + (s[2] + s[3]);
+        result[1] = count;
+    }
+}
+
+static_assert(SPEI_PSNR_WS_DOUBLES == 256, "psnr_f32_final_kernel reads one partial per thread");
+
 }  // namespace
+
+extern "C" int spei_psnr_f32(const float* a, const float* b, int H, int W, int shave, float rgb_range, double* ws, double* result,
+                             spei_stream_t stream) {
+    SPEI_REQUIRE(a && b && ws && result, "spei_psnr_f32: null pointer");
+    SPEI_REQUIRE(shave >= 0 && H - 2 * shave > 0 && W - 2 * shave > 0 && (int64_t)H * W < (1ll << 29),
+                 "spei_psnr_f32: %dx%d shaved by %d leaves nothing to score", H, W, shave);
+    SPEI_REQUIRE(rgb_range > 0.0f, "spei_psnr_f32: rgb_range %g must be positive", (double)rgb_range);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(psnr_f32_kernel, dim3(SPEI_PSNR_WS_DOUBLES), dim3(256), 0, st, a, b, H, W, shave, rgb_range, ws);
+    hipLaunchKernelGGL(psnr_f32_final_kernel, dim3(1), dim3(256), 0, st, ws, 3.0 * (H - 2 * shave) * (double)(W - 2 * shave), result);
+    SPEI_CHECK_LAUNCH("spei_psnr_f32");
+    return 0;
+}
 
 extern "C" int64_t spei_frame_metrics_ws_doubles(int H, int W, int border) {
     const int oh = H - 2 * border - 2 * R, ow = W - 2 * border - 2 * R;

@@ -1,0 +1,108 @@
+// The training batch of the dataset loop (speinet_amd/data.py): one launch turns a table of uint8 crop rectangles into the fp32 tensors
+// the trainers take — what the reference builds per sample on DataLoader workers (util/utils.py:8-65 get_patch / np2Tensor /
+// data_augment, data/videodata_nfs.py:180-207 __getitem__):
+//
+//   input  fp32 [n_in][3][P][P]   (n_in = B * (n_seq + 2), or B * n_seq without references)
+//   gt     fp32 [n_gt][3][P][P]   (n_gt = B: the middle frame's ground truth)
+//
+// One record per output frame: the address of a uint8 [H][W][3] frame, its row pitch in bytes, the crop origin (y0, x0) and the flags
+// {hflip, vflip, rot90, zero}.  Value: (float)u * (float)(rgb_range / 255) (np2Tensor: float64 -> float32, then mul_ by a Python
+// scalar in float32), bit-identical to the reference's tensors.  Geometry in the reference's order — crop, [:, ::-1] if hflip,
+// [::-1, :] if vflip, np.rot90 (counter-clockwise) if rot90 — which for output pixel (i, j) of the P x P patch reads crop pixel
+//     no rot90:  ( vflip ? P-1-i : i ,  hflip ? P-1-j : j )
+//     rot90:     ( vflip ? P-1-j : j ,  hflip ? i : P-1-i )
+// so a 32 x 32 output tile always reads one 32 x 32 source tile, transposed and / or mirrored.  A workgroup stages that tile through
+// LDS: thread t reads 4 pixels (12 bytes: three dwords where the row addresses are 4-byte aligned, bytes otherwise) of source row
+// t / 8, so a wave reads 8 source rows of 96 contiguous bytes each; then thread t writes 4 pixels of output row t / 8 as one 16-byte
+// store per plane, whatever the flags.  LDS pitch 33 dwords (one packed pixel per dword): a 32-lane half of a ds_write_b32 /
+// ds_read_b32 holds 4 rows x 8 groups and touches bank (row + 4 * group + k) % 32 in either orientation — all distinct.
+// `zero` records write zeros and read nothing.  Plain vector stores only.
+#include "common.h"
+
+namespace {
+
+constexpr int TILE = 32, PITCH = TILE + 1;
+constexpr int F_HFLIP = 1, F_VFLIP = 2, F_ROT90 = 4, F_ZERO = 8;
+
+__global__ __launch_bounds__(256) void train_batch_kernel(const spei_crop_record* __restrict__ table, int n_in, float* __restrict__ input,
+                                                          float* __restrict__ gt, int P, int tiles, float scale) {
+    __shared__ uint32_t lds[TILE * PITCH];
+    const int r = blockIdx.y;
+    const spei_crop_record rec = table[r];
+    const int oi0 = (blockIdx.x / tiles) * TILE, oj0 = (blockIdx.x % tiles) * TILE;
+    const int nI = min(TILE, P - oi0), nJ = min(TILE, P - oj0);          // multiples of 4 (P % 4 == 0)
+    const int row = threadIdx.x >> 3, g4 = (threadIdx.x & 7) * 4;
+    const bool hf = rec.flags & F_HFLIP, vf = rec.flags & F_VFLIP, rot = rec.flags & F_ROT90, zero = rec.flags & F_ZERO;
+    // the source tile inside the crop: rows [cy_lo, cy_lo + nR), columns [cx_lo, cx_lo + nC); cx_lo % 4 == 0
+    const int nR = rot ? nJ : nI, nC = rot ? nI : nJ;
+    const int cy_lo = rot ? (vf ? P - oj0 - nJ : oj0) : (vf ? P - oi0 - nI : oi0);
+    const int cx_lo = rot ? (hf ? oi0 : P - oi0 - nI) : (hf ? P - oj0 - nJ : oj0);
+    if (!zero) {
+        if (row < nR && g4 < nC) {
+            const unsigned char* s = reinterpret_cast<const unsigned char*>(rec.src) + (int64_t)(rec.y0 + cy_lo + row) * rec.pitch +
+                                     (int64_t)(rec.x0 + cx_lo + g4) * 3;
+            uint32_t w[3];
+            if ((((uintptr_t)rec.src + (int64_t)rec.x0 * 3) & 3) == 0 && (rec.pitch & 3) == 0) {      // every row of the crop starts on a dword
+                const uint32_t* p = reinterpret_cast<const uint32_t*>(s);
+                w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    w[k] = (uint32_t)s[4 * k] | ((uint32_t)s[4 * k + 1] << 8) | ((uint32_t)s[4 * k + 2] << 16) | ((uint32_t)s[4 * k + 3] << 24);
+            }
+            // 12 bytes = 4 pixels: pixel k is bytes 3k .. 3k+2 -> one dword 0x00BBGGRR each
+            const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32), hi = (uint64_t)w[1] | ((uint64_t)w[2] << 32);
+            uint32_t* d = lds + row * PITCH + g4;
+            d[0] = (uint32_t)lo & 0xffffffu;
+            d[1] = (uint32_t)(lo >> 24) & 0xffffffu;
+            d[2] = (uint32_t)(hi >> 16) & 0xffffffu;
+            d[3] = (uint32_t)(hi >> 40) & 0xffffffu;
+        }
+        __syncthreads();
+    }
+    if (row >= nI || g4 >= nJ) return;
+    const int i = oi0 + row;
+    float v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = oj0 + g4 + k;
+        const int cy = rot ? (vf ? P - 1 - j : j) : (vf ? P - 1 - i : i);
+        const int cx = rot ? (hf ? i : P - 1 - i) : (hf ? P - 1 - j : j);
+        const uint32_t px = zero ? 0u : lds[(cy - cy_lo) * PITCH + (cx - cx_lo)];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = (float)((px >> (8 * c)) & 0xffu) * scale;
+    }
+    float* base = r < n_in ? input + (int64_t)r * 3 * P * P : gt + (int64_t)(r - n_in) * 3 * P * P;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        *reinterpret_cast<float4*>(base + ((int64_t)c * P + i) * P + oj0 + g4) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+}
+
+}  // namespace
+
+extern "C" int spei_train_batch_u8(const spei_crop_record* table, const spei_crop_record* table_host, int n_in, int n_gt, float* input,
+                                   float* gt, int P, float rgb_range, spei_stream_t stream) {
+    SPEI_REQUIRE(table && table_host, "spei_train_batch_u8: null record table (the device table and its host copy are both required)");
+    SPEI_REQUIRE(n_in >= 0 && n_gt >= 0 && n_in + n_gt > 0 && n_in + n_gt <= 65535, "spei_train_batch_u8: bad record counts %d + %d", n_in, n_gt);
+    SPEI_REQUIRE((n_in == 0 || input) && (n_gt == 0 || gt), "spei_train_batch_u8: null dst");
+    SPEI_REQUIRE(((uintptr_t)input & 15) == 0 && ((uintptr_t)gt & 15) == 0, "spei_train_batch_u8: dst must be 16-byte aligned");
+    SPEI_REQUIRE(P > 0 && P % 4 == 0 && P <= 4096, "spei_train_batch_u8: patch size %d must be a positive multiple of 4 (at most 4096)", P);
+    SPEI_REQUIRE(rgb_range > 0.0f, "spei_train_batch_u8: rgb_range %g must be positive", (double)rgb_range);
+    // the rectangles are checked HERE, on the host copy: the kernel never meets a record that leaves its frame
+    for (int r = 0; r < n_in + n_gt; ++r) {
+        const spei_crop_record& c = table_host[r];
+        SPEI_REQUIRE((c.flags & ~15) == 0, "spei_train_batch_u8: record %d has unknown flag bits 0x%x", r, (unsigned)c.flags);
+        if (c.flags & F_ZERO) continue;
+        SPEI_REQUIRE(c.src != 0, "spei_train_batch_u8: record %d has a null frame address", r);
+        SPEI_REQUIRE(c.H > 0 && c.W > 0 && c.W <= (1 << 24) && c.pitch >= c.W * 3, "spei_train_batch_u8: record %d: frame %dx%d with a row pitch of %d bytes",
+                     r, c.W, c.H, c.pitch);
+        SPEI_REQUIRE(c.y0 >= 0 && c.x0 >= 0 && (int64_t)c.y0 + P <= c.H && (int64_t)c.x0 + P <= c.W,
+                     "spei_train_batch_u8: record %d: the %dx%d rectangle at (y %d, x %d) leaves its %dx%d frame", r, P, P, c.y0, c.x0, c.W, c.H);
+    }
+    const int tiles = cdiv(P, TILE);
+    const float scale = (float)((double)rgb_range / 255.0);
+    hipLaunchKernelGGL(train_batch_kernel, dim3(tiles * tiles, n_in + n_gt), dim3(256), 0, (hipStream_t)stream, table, n_in, input, gt, P,
+                       tiles, scale);
+    SPEI_CHECK_LAUNCH("spei_train_batch_u8");
+    return 0;
+}

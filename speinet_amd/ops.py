@@ -245,6 +245,33 @@ def frame_u8_out(x: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = 
     return out
 
 
+def psnr_f32(a: torch.Tensor, b: torch.Tensor, shave: int = 4, rgb_range: float = 1.0) -> torch.Tensor:
+    """The reference's validation metric on float frames (csrc/metrics.hip spei_psnr_f32; util/utils.py:81-92 calc_psnr): a, b fp32
+    [3,H,W] on the device -> float64 [2] = (sum of squared differences over [shave:-shave] in float64, number of terms).  Two launches on
+    the current stream, no host sync; `psnr_of` turns the pair into dB on the host."""
+    assert a.is_cuda and a.dtype == torch.float32 and a.dim() == 3 and a.shape[0] == 3 and a.is_contiguous()
+    assert b.shape == a.shape and b.dtype == torch.float32 and b.device == a.device and b.is_contiguous()
+    lib = _lib.lib()
+    dev = a.device
+    ws = torch.empty(PSNR_WS_DOUBLES, dtype=torch.float64, device=dev)
+    res = torch.empty(2, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_psnr_f32(_vp(a.data_ptr()), _vp(b.data_ptr()), a.shape[1], a.shape[2], shave, float(rgb_range), _vp(ws.data_ptr()),
+                                     _vp(res.data_ptr()), st), "spei_psnr_f32")
+    return res
+
+
+PSNR_WS_DOUBLES = 256          # SPEI_PSNR_WS_DOUBLES
+
+
+def psnr_of(sq_sum: float, count: float) -> float:
+    """calc_psnr's last lines (util/utils.py:88-92): 100 for identical frames, else 20 log10(1 / sqrt(mse))."""
+    import math
+    mse = sq_sum / count
+    return 100.0 if mse == 0 else 20 * math.log10(1.0 / math.sqrt(mse))
+
+
 CORR_DIAG_WS_MAX = 8 << 30     # bytes of candidate pairs the diagonal correlation kernel may use before the slab kernel takes over
 
 
@@ -413,6 +440,19 @@ class Ctx:
     # ---- K15 / K1 / first and last conv ------------------------------------------------------------------------
     def any_nonzero(self, x: torch.Tensor, flag: torch.Tensor) -> None:
         _lib.check(_lib.lib().spei_any_nonzero(self._tp(x), x.numel(), self._tp(flag), self._stream()), "spei_any_nonzero")
+
+    def train_batch(self, table: torch.Tensor, table_host: torch.Tensor, n_in: int, n_gt: int, input: torch.Tensor, gt: torch.Tensor,
+                    patch: int, rgb_range: float = 1.0) -> None:
+        """One training batch from a table of crop records (csrc/train_batch.hip; speinet_amd.data.RECORD): `table` the records on the
+        device, `table_host` the same bytes in host memory (every rectangle is checked against its frame there, before the launch);
+        input fp32 [n_in,3,P,P] and gt fp32 [n_gt,3,P,P] (any leading shape) are written on the current stream."""
+        nb = (n_in + n_gt) * 32
+        assert table.dtype == torch.uint8 and table.numel() >= nb and not table_host.is_cuda and table_host.dtype == torch.uint8 \
+            and table_host.is_contiguous() and table_host.numel() >= nb
+        assert input.dtype == torch.float32 and input.numel() == n_in * 3 * patch * patch
+        assert gt.dtype == torch.float32 and gt.numel() == n_gt * 3 * patch * patch
+        _lib.check(_lib.lib().spei_train_batch_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(input), self._tp(gt),
+                                                  patch, float(rgb_range), self._stream()), "spei_train_batch_u8")
 
     def rl_prior(self, img: torch.Tensor, iters: int, lam: float = 0.01) -> torch.Tensor:
         """img [3,H,W] -> [3,H,W]."""
