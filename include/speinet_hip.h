@@ -444,7 +444,8 @@ int spei_rowdot(const float* a, const float* b, float* out, int64_t M, int N, sp
 
 /* Row a11 — LD sharpness detector features (inference_SPEINet.py:54-189).  spei_det_gray: [N][3][H][W] fp32 0..255 ->
  * gray [N][H][W] in 0..1 (ITU-R 601 weights).  spei_det_features: gray -> out [N][6] = LAP1, MIS3, WAV1, GRA7, STA3, DCT3
- * with window size k (odd; the reference uses 11).  ws: spei_det_ws_floats(N,H,W,k) floats. */
+ * with window size k (odd; the reference uses 11 and sweeps 3..201).  ws: spei_det_ws_floats(N,H,W,k) floats.  k <= 11 sums each
+ * k x k box of GRA7 / STA3 directly; k >= 13 takes running column sums and row prefix sums (cost independent of k). */
 int spei_det_gray(const float* rgb, float* gray, int N, int H, int W, spei_stream_t stream);
 int64_t spei_det_ws_floats(int N, int H, int W, int k);
 int spei_det_features(const float* gray, float* out, float* ws, int N, int H, int W, int k, spei_stream_t stream);
@@ -493,6 +494,17 @@ int spei_train_batch_u8(const spei_crop_record* table, const spei_crop_record* t
 #define SPEI_PSNR_WS_DOUBLES 256
 int spei_psnr_f32(const float* a, const float* b, int H, int W, int shave, float rgb_range, double* ws, double* result,
                   spei_stream_t stream);
+
+/* ---- making a data set from sharp footage (speinet_amd/blurset.py) ---- */
+
+/* The reference's blur synthesis (LD_detector/mix_choice_dataset.py:46-71, :99-108; sharp_detector_params_estimation_parallel.py:50-76)
+ * in one launch: src = T packed uint8 [H][W][3] frames, frame_stride bytes apart; runs = M pairs (start, length) of int32 on the
+ * device, 1 <= length <= 15, start + length <= T; runs_host: the same pairs in HOST memory, checked before anything is launched.
+ * Per run m: blur[m] = floor(sum of the run's frames / length) per byte (== np.mean -> float32 -> astype(uint8)), gt[m] = frame
+ * start + length / 2, both uint8 [M][H][W][3] packed; gray (or NULL): [M][H][W] fp32, the detector's gray plane of blur[m],
+ * bit-identical to spei_frames_u8_in's.  16-byte accesses when H * W % 16 == 0 and every pointer and the stride are 16-byte aligned. */
+int spei_window_mean_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
+                        unsigned char* blur, unsigned char* gt, float* gray, int H, int W, spei_stream_t stream);
 
 #ifdef __cplusplus
 }

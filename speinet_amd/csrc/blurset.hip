@@ -1,0 +1,129 @@
+// Data-set synthesis (speinet_amd/blurset.py): the reference makes its GoProS-style sets from sharp high-frame-rate footage by
+// averaging runs of 1..15 consecutive frames (LD_detector/mix_choice_dataset.py:46-71 _generate_blurry_sequence_, :99-108 the uint8
+// frames it writes; sharp_detector_params_estimation_parallel.py:50-76 generate_blurry_sequence).
+//
+//   spei_window_mean_u8 — T packed uint8 [H][W][3] frames on the device and a table of M runs (start, length), 1 <= length <= 15.
+//                         Per run m:  blur[m] = floor(sum_{t < length} frame[start + t] / length) per byte, in integer arithmetic
+//                         (== np.mean(window, axis=0) -> float32 -> astype(uint8), :61 and :104: a non-integer quotient with
+//                         length <= 15 lies at least 1/15 from an integer, far more than float32 rounding at 255);
+//                                     gt[m]   = frame[start + length / 2]  (:62);
+//                                     gray[m] = the detector's gray plane of blur[m] (spei_gray_px, as spei_frames_u8_in writes it).
+//
+// One launch for all runs.  HBM-bound by construction: every source frame of a run is read once (the gt frame a second time, from
+// cache) and two frames are written per run, so a clip of T frames in M runs moves (T + 2 M) * H*W*3 bytes plus 4 * M * H*W for the
+// gray planes: 720p, T = 480 in M = 80 runs: 1.77 GB + 0.29 GB.  Vector path (H*W a multiple of 16, pointers and frame stride
+// 16-byte aligned): one thread per 16 pixels, three 16-byte loads per source frame, three 16-byte stores per output frame, four per
+// gray plane.  Otherwise one thread per pixel with byte accesses.  The quotient is a multiply and a shift: with m = ceil(2^16 / n),
+// (s * m) >> 16 == s / n for every s <= 15 * 255 and n <= 15 (the error term s * (m n - 2^16) stays below 2^16).
+#include "common.h"
+
+namespace {
+
+constexpr int MAX_RUN = 15;
+
+__device__ __forceinline__ uint32_t quot(uint32_t s, uint32_t magic) { return (s * magic) >> 16; }
+
+__global__ __launch_bounds__(256) void window_mean_vec_kernel(const unsigned char* __restrict__ src, int64_t fstride, const int* __restrict__ runs,
+                                                              unsigned char* __restrict__ blur, unsigned char* __restrict__ gt,
+                                                              float* __restrict__ gray, int64_t hw) {
+    const int m = blockIdx.y;
+    const int start = runs[2 * m], len = runs[2 * m + 1];
+    const uint32_t magic = (65536u + len - 1) / len;
+    const int64_t groups = hw >> 4;                        // 16 pixels = 48 bytes per thread
+    const int64_t nb = hw * 3;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < groups; i += (int64_t)gridDim.x * 256) {
+        uint32_t acc[48];
+#pragma unroll
+        for (int j = 0; j < 48; ++j) acc[j] = 0u;
+        uint4 mid[3];
+        for (int t = 0; t < len; ++t) {
+            const uint4* p = reinterpret_cast<const uint4*>(src + (start + t) * fstride + i * 48);
+            const uint4 q[3] = {p[0], p[1], p[2]};
+            if (t == len / 2) { mid[0] = q[0]; mid[1] = q[1]; mid[2] = q[2]; }
+#pragma unroll
+            for (int v = 0; v < 3; ++v) {
+                const uint32_t w[4] = {q[v].x, q[v].y, q[v].z, q[v].w};
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[16 * v + j] += (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 48; ++j) acc[j] = quot(acc[j], magic);
+        uint4* b = reinterpret_cast<uint4*>(blur + m * nb + i * 48);
+        uint4* g = reinterpret_cast<uint4*>(gt + m * nb + i * 48);
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 16; ++j) w[j >> 2] |= acc[16 * v + j] << (8 * (j & 3));
+            b[v] = make_uint4(w[0], w[1], w[2], w[3]);
+            g[v] = mid[v];
+        }
+        if (gray) {
+            float4* y = reinterpret_cast<float4*>(gray + m * hw + i * 16);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                float e[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int px = 4 * v + j;
+                    e[j] = spei_gray_px((float)acc[3 * px], (float)acc[3 * px + 1], (float)acc[3 * px + 2]);
+                }
+                y[v] = make_float4(e[0], e[1], e[2], e[3]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void window_mean_px_kernel(const unsigned char* __restrict__ src, int64_t fstride, const int* __restrict__ runs,
+                                                             unsigned char* __restrict__ blur, unsigned char* __restrict__ gt,
+                                                             float* __restrict__ gray, int64_t hw) {
+    const int m = blockIdx.y;
+    const int start = runs[2 * m], len = runs[2 * m + 1];
+    const uint32_t magic = (65536u + len - 1) / len;
+    const int64_t nb = hw * 3;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (int64_t)gridDim.x * 256) {
+        uint32_t acc[3] = {0u, 0u, 0u};
+        for (int t = 0; t < len; ++t) {
+            const unsigned char* p = src + (start + t) * fstride + i * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += p[c];
+        }
+        const unsigned char* p = src + (start + len / 2) * fstride + i * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            acc[c] = quot(acc[c], magic);
+            blur[m * nb + i * 3 + c] = (unsigned char)acc[c];
+            gt[m * nb + i * 3 + c] = p[c];
+        }
+        if (gray) gray[m * hw + i] = spei_gray_px((float)acc[0], (float)acc[1], (float)acc[2]);
+    }
+}
+
+}  // namespace
+
+extern "C" int spei_window_mean_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
+                                   unsigned char* blur, unsigned char* gt, float* gray, int H, int W, spei_stream_t stream) {
+    SPEI_REQUIRE(src && runs && runs_host && blur && gt, "spei_window_mean_u8: null pointer (src, runs, runs_host, blur and gt are required)");
+    SPEI_REQUIRE(T > 0 && M > 0 && M <= 65535 && H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31),
+                 "spei_window_mean_u8: bad sizes (%d frames of %dx%d, %d runs; at most 65535 runs per launch)", T, H, W, M);
+    const int64_t hw = (int64_t)H * W;
+    SPEI_REQUIRE(T == 1 || frame_stride >= hw * 3, "spei_window_mean_u8: frame stride %lld < one %dx%d frame", (long long)frame_stride, H, W);
+    for (int m = 0; m < M; ++m) {
+        const int start = runs_host[2 * m], len = runs_host[2 * m + 1];
+        SPEI_REQUIRE(len >= 1 && len <= MAX_RUN, "spei_window_mean_u8: run %d has length %d (1..%d)", m, len, MAX_RUN);
+        SPEI_REQUIRE(start >= 0 && start <= T - len, "spei_window_mean_u8: run %d = frames %d..%d leaves the clip of %d frames", m, start,
+                     start + len - 1, T);
+    }
+    const bool vec = (hw & 15) == 0 && (((uintptr_t)src | (uintptr_t)blur | (uintptr_t)gt | (uintptr_t)gray) & 15) == 0 &&
+                     (T == 1 || (frame_stride & 15) == 0);
+    const int64_t items = vec ? hw >> 4 : hw;
+    const int64_t bx = (items + 255) / 256;
+    const dim3 grid((unsigned)(bx < 4096 ? bx : 4096), (unsigned)M);
+    if (vec)
+        hipLaunchKernelGGL(window_mean_vec_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, blur, gt, gray, hw);
+    else
+        hipLaunchKernelGGL(window_mean_px_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, blur, gt, gray, hw);
+    SPEI_CHECK_LAUNCH("spei_window_mean_u8");
+    return 0;
+}

@@ -1,7 +1,8 @@
 // Row a11 — LD sharpness detector at inference time: six focus measures per frame
 // (reference inference_SPEINet.py:54-189: sobel :54, laplacian :68, mask :79, focus_measure_mis3 :118, _gra7 :134,
 // _lap1 :144, _wave1 :152, _sta3 :161, _dct3 :169, generate_vars :177-189).  HBM-bound stencils + reductions; every
-// reduction goes block partials -> one fixed-order final sum per frame (bitwise reproducible).
+// reduction goes block partials -> one fixed-order final sum per frame (bitwise reproducible).  The training side of the detector
+// (LD_detector/sharp_detector_params_estimation_parallel.py:126-213, run_detector.sh: k in 3..201) computes the same six measures.
 //
 //   LAP1 = mean_win sum_win lap8(g)^2                  lap8 = [[1,1,1],[1,-8,1],[1,1,1]], zero pad
 //   MIS3 = mean_win sum_win sum_{8 nbrs} |g(p)-g(q)|   zero pad
@@ -15,6 +16,7 @@
 namespace {
 
 constexpr int TB = 16;     // 16 x 16 pixel tile per 256-thread block
+constexpr int BOX_SCAN_K = 13;     // GRA7 / STA3 box sums: k < 13 direct (det_boxdev_kernel), k >= 13 running sums
 
 __device__ __forceinline__ float gat(const float* g, int H, int W, int y, int x) {
     return (y >= 0 && y < H && x >= 0 && x < W) ? g[(size_t)y * W + x] : 0.0f;
@@ -97,6 +99,81 @@ __global__ __launch_bounds__(256) void det_boxdev_kernel(const float* __restrict
         }
         const float inv = 1.0f / (float)(k * k);
         const float eg = g[(size_t)y * W + x] - ag * inv, es = s[(size_t)y * W + x] - as * inv;
+        dg = eg * eg;
+        ds = es * es;
+    }
+    const int blk = blockIdx.y * gridDim.x + blockIdx.x;
+    const float s0 = block_sum(ds, red), s1 = block_sum(dg, red);
+    if (threadIdx.x == 0) {
+        part[((size_t)n * 6 + 3) * pb + blk] = s0;     // GRA7
+        part[((size_t)n * 6 + 4) * pb + blk] = s1;     // STA3
+    }
+}
+
+// pass 2 for k >= 13, three launches whose loads per pixel do not grow with k (the brute-force box above reads 2 k^2 values per pixel:
+// 8e4 at k = 201).  All sums fp32 in a fixed order, so the result is bitwise reproducible; k <= 11 keeps det_boxdev_kernel and its bits.
+//   a) column sums  c[y][x] = sum_{|a| <= k/2} v[y + a][x]  (zero pad): one thread per column and segment of `seg` rows, the first row
+//      summed directly (k loads, ascending rows), every further row by one add and one subtract; seg >= k / 2, so at most 4 loads per
+//      pixel, coalesced along x.  The running sum restarts every segment: its rounding does not build up over the frame.
+//   b) row prefix   p[y][x] = sum_{x' <= x} c[y][x'], in place: one wave per row, 64 columns per step (wave scan plus the carry).
+//   c) box_k(v)[y][x] = (p[y][min(x + k/2, W - 1)] - p[y][x - k/2 - 1]) / k^2, the deviation squared, block partials as above.
+// v = gray (plane 0) and v = sobel magnitude (plane 1); c / p: [N][2][H][W].
+__global__ __launch_bounds__(256) void det_colsum_kernel(const float* __restrict__ gray, const float* __restrict__ sob, float* __restrict__ col,
+                                                         int H, int W, int k, int seg) {
+    const int plane = blockIdx.z & 1, n = blockIdx.z >> 1;
+    const float* v = (plane ? sob : gray) + (size_t)n * H * W;
+    float* o = col + ((size_t)n * 2 + plane) * H * W;
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= W) return;
+    const int h = k / 2, y0 = blockIdx.y * seg, y1 = y0 + seg < H ? y0 + seg : H;
+    const int lo = y0 - h > 0 ? y0 - h : 0, hi = y0 + h < H - 1 ? y0 + h : H - 1;
+    float acc = 0.f;
+    for (int yy = lo; yy <= hi; ++yy) acc += v[(size_t)yy * W + x];
+    o[(size_t)y0 * W + x] = acc;
+    for (int y = y0 + 1; y < y1; ++y) {
+        if (y + h < H) acc += v[(size_t)(y + h) * W + x];
+        if (y - h - 1 >= 0) acc -= v[(size_t)(y - h - 1) * W + x];
+        o[(size_t)y * W + x] = acc;
+    }
+}
+
+__global__ __launch_bounds__(256) void det_rowscan_kernel(float* __restrict__ col, int W, int64_t rows) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    float* p = col + row * W;
+    float carry = 0.f;
+    for (int x0 = 0; x0 < W; x0 += 64) {
+        const int x = x0 + lane;
+        float v = x < W ? p[x] : 0.f;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const float t = __shfl_up(v, d, 64);
+            if (lane >= d) v += t;
+        }
+        v += carry;
+        if (x < W) p[x] = v;
+        carry = __shfl(v, 63, 64);
+    }
+}
+
+__global__ __launch_bounds__(256) void det_boxdev_scan_kernel(const float* __restrict__ gray, const float* __restrict__ sob,
+                                                              const float* __restrict__ pre, float* __restrict__ part, int H, int W, int k, int pb) {
+    __shared__ float red[4];
+    const int n = blockIdx.z;
+    const float* g = gray + (size_t)n * H * W;
+    const float* s = sob + (size_t)n * H * W;
+    const float* pg = pre + (size_t)n * 2 * H * W;
+    const float* ps = pg + (size_t)H * W;
+    const int x = blockIdx.x * TB + (threadIdx.x & 15), y = blockIdx.y * TB + (threadIdx.x >> 4);
+    const int ch = (H / k) * k, cw = (W / k) * k, h = k / 2;
+    float dg = 0.f, ds = 0.f;
+    if (y < ch && x < cw) {
+        const size_t r = (size_t)y * W;
+        const int hi = x + h < W - 1 ? x + h : W - 1, lo = x - h - 1;
+        const float ag = pg[r + hi] - (lo >= 0 ? pg[r + lo] : 0.f), as = ps[r + hi] - (lo >= 0 ? ps[r + lo] : 0.f);
+        const float inv = 1.0f / (float)(k * k);
+        const float eg = g[r + x] - ag * inv, es = s[r + x] - as * inv;
         dg = eg * eg;
         ds = es * es;
     }
@@ -210,18 +287,28 @@ extern "C" int spei_det_gray(const float* rgb, float* gray, int N, int H, int W,
 extern "C" int64_t spei_det_ws_floats(int N, int H, int W, int k) {
     if (N <= 0 || H < 4 || W < 4 || k < 1) return 0;
     const DetDims d = dims(H, W, k);
-    return (int64_t)N * H * W + (int64_t)N * 6 * d.pb;
+    return (int64_t)N * H * W * (k >= BOX_SCAN_K ? 3 : 1) + (int64_t)N * 6 * d.pb;      // sobel map (+ two planes of box sums), partials
 }
 
 extern "C" int spei_det_features(const float* gray, float* out, float* ws, int N, int H, int W, int k, spei_stream_t stream) {
     SPEI_REQUIRE(gray && out && ws && N > 0, "spei_det_features: bad arguments");
     SPEI_REQUIRE(k >= 1 && (k & 1) && H >= k + 3 && W >= k + 3, "spei_det_features: k=%d must be odd and fit the %dx%d frame", k, H, W);
+    SPEI_REQUIRE(k < BOX_SCAN_K || N <= 32767, "spei_det_features: at most 32767 frames per call for k >= 13 (got %d)", N);
     const DetDims d = dims(H, W, k);
     float* sob = ws;
     float* part = ws + (size_t)N * H * W;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(det_point_kernel, dim3(d.tiles_x, d.tiles_y, N), dim3(256), 0, st, gray, sob, part, H, W, k, d.pb);
-    hipLaunchKernelGGL(det_boxdev_kernel, dim3(d.tiles_x, d.tiles_y, N), dim3(256), 0, st, gray, sob, part, H, W, k, d.pb);
+    if (k < BOX_SCAN_K) {
+        hipLaunchKernelGGL(det_boxdev_kernel, dim3(d.tiles_x, d.tiles_y, N), dim3(256), 0, st, gray, sob, part, H, W, k, d.pb);
+    } else {
+        float* col = part + (size_t)N * 6 * d.pb;
+        const int seg = k / 2 + 1 > 32 ? k / 2 + 1 : 32;
+        hipLaunchKernelGGL(det_colsum_kernel, dim3(cdiv(W, 256), cdiv(H, seg), 2 * N), dim3(256), 0, st, gray, sob, col, H, W, k, seg);
+        const int64_t rows = (int64_t)N * 2 * H;
+        hipLaunchKernelGGL(det_rowscan_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, col, W, rows);
+        hipLaunchKernelGGL(det_boxdev_scan_kernel, dim3(d.tiles_x, d.tiles_y, N), dim3(256), 0, st, gray, sob, col, part, H, W, k, d.pb);
+    }
     hipLaunchKernelGGL(det_dct_kernel, dim3(d.nb_dct, N), dim3(256), 0, st, gray, part, H, W, k, d.pb);
     hipLaunchKernelGGL(det_wav_kernel, dim3(d.nb_wav, N), dim3(256), 0, st, gray, part, H, W, d.pb);
     const float nwin = (float)((H / k) * (W / k)), nwin_dct = (float)(((H - 3) / k) * ((W - 3) / k));

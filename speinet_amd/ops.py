@@ -13,6 +13,7 @@ import ctypes as C
 import dataclasses
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -224,6 +225,34 @@ def frames_u8_in(u8: torch.Tensor, out: Optional[torch.Tensor] = None, gray: boo
         _lib.check(lib.spei_frames_u8_in(_vp(fr.data_ptr()), fr.stride(0), _vp(out.data_ptr() if out is not None else 0),
                                          _vp(g.data_ptr() if g is not None else 0), n, h, w, st), "spei_frames_u8_in")
     return out, g
+
+
+def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: Optional[torch.Tensor] = None,
+                   gt: Optional[torch.Tensor] = None):
+    """The reference's blur synthesis on resident frames (csrc/blurset.hip): uint8 frames [T,H,W,3] on the device (each frame packed,
+    any frame stride) and M runs `starts[m]`, `lengths[m]` (1..15 frames, inside the clip) -> (blur uint8 [M,H,W,3] = the per-byte
+    integer mean of each run, gt uint8 [M,H,W,3] = the run's middle frame `start + length // 2`, the detector's gray plane [M,H,W] of
+    the blurry frames or None when not `gray`).  `blur` / `gt` (optional): contiguous destinations.  One launch on the current stream;
+    the runs are checked on the host before it."""
+    assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4
+    t, h, w, c = u8.shape
+    assert c == 3 and u8.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
+    runs_host = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(starts), np.asarray(lengths)], axis=1).astype(np.int32)))
+    m = runs_host.shape[0]
+    dev = u8.device
+    for name, buf in (("blur", blur), ("gt", gt)):
+        assert buf is None or (buf.device == dev and buf.dtype == torch.uint8 and tuple(buf.shape) == (m, h, w, 3) and buf.is_contiguous()), name
+    blur = torch.empty(m, h, w, 3, dtype=torch.uint8, device=dev) if blur is None else blur
+    gt = torch.empty(m, h, w, 3, dtype=torch.uint8, device=dev) if gt is None else gt
+    g = torch.empty(m, h, w, device=dev) if gray else None
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        runs = runs_host.to(dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_window_mean_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
+                                           _vp(blur.data_ptr()), _vp(gt.data_ptr()), _vp(g.data_ptr() if g is not None else 0), h, w, st),
+                   "spei_window_mean_u8")
+    return blur, gt, g
 
 
 def frame_u8_out(x: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None,

@@ -2,6 +2,7 @@
 `deblur_clip`; the command line, for the user's own footage (no ground truth), is
 
     python -m speinet_amd.video --input <dir | glob> --output <dir> --model_path <checkpoint | synthetic> [--labels <file.npy>]
+                                [--detector <detector.json>]
 
 and the dataset harness (speinet_amd.inference) runs every clip through `deblur_clip` as well, adding its ground truth and metrics.
   * labels — given (0/1 per frame, 1 = sharp), or computed by the LD detector (speinet_amd.detector) in a first streaming pass over the
@@ -271,8 +272,9 @@ class ClipRun:
     frames that were recomputed in bf16x3 because their 16-bit pass left a non-finite value; `seconds[k]` is window k's host time
     [assembling its input, enqueueing it] (the wait for a free launch slot excluded)."""
 
-    def __init__(self, model, frames: _Frames, labels, out, numbers=None):
+    def __init__(self, model, frames: _Frames, labels, out, numbers=None, detector_params=None):
         self.model, self.frames = model, frames
+        self.detector = detector.DEFAULT if detector_params is None else detector_params
         params = list(model.parameters())
         self.device = params[0].device if params else torch.device("cpu")
         if self.device.type != "cuda":
@@ -309,39 +311,8 @@ class ClipRun:
 
     def _detect(self) -> np.ndarray:
         """The LD detector's labels, DETECT_BATCH frames at a time: uint8 upload, gray planes (spei_frames_u8_in), focus measures."""
-        fr, dev, B = self.frames, self.device, DETECT_BATCH
-        T, H, W = fr.T, fr.H, fr.W
-        feats = []
-        with torch.no_grad(), torch.cuda.device(dev), ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as pool:
-            futs = {}
-
-            def want(upto):
-                for i in range(min(upto, T)):
-                    if i not in futs and not fr.on_device(i):
-                        futs[i] = pool.submit(fr.host, i)
-
-            stage = [torch.empty(B, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-            events = [None, None]
-            batch = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
-            for b, i0 in enumerate(range(0, T, B)):
-                n = min(B, T - i0)
-                want(i0 + 2 * B)
-                st = stage[b % 2]
-                if events[b % 2] is not None:
-                    events[b % 2].synchronize()           # the upload issued two batches ago
-                host = [i for i in range(i0, i0 + n) if not fr.on_device(i)]
-                for i in host:
-                    st[i - i0].numpy()[...] = futs.pop(i).result()
-                if host:
-                    batch[:n].copy_(st[:n], non_blocking=True)
-                    events[b % 2] = torch.cuda.Event()
-                    events[b % 2].record()
-                for i in range(i0, i0 + n):
-                    if fr.on_device(i):
-                        batch[i - i0].copy_(fr.device(i))
-                _, gray = ops.frames_u8_in(batch[:n], gray=True, planes=False)
-                feats.append(detector.gray_focus_measures(gray, 11))
-        return detector.predict(torch.cat(feats))
+        p = self.detector
+        return detector.predict(detector.clip_features(self.frames, self.device, p.kernel_size, DETECT_BATCH), p)
 
     def _run(self):
         m, dev, fr = self.model, self.device, self.frames
@@ -459,7 +430,8 @@ class ClipRun:
             pool.shutdown(wait=False, cancel_futures=True)
 
 
-def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None) -> ClipRun:
+def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
+                detector=None) -> ClipRun:
     """Deblur a clip: an iterator of (index, uint8 [H,W,3] frame on the model's device), in frame order, one per input frame.
 
     model  — an eval() `SPEINet` on a ROCm device; its `precision`, `corr_precision`, `use_graph` and `streams` are used as set.
@@ -470,6 +442,8 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     crop   — crop every frame at the bottom and right to multiples of 20 as it is loaded, as the reference's harness does, instead of
              padding it (H and W are then the cropped size).
     numbers — optional frame number per frame, in which the distance to a reference frame is measured (default: the indices).
+    detector — optional `detector.DetectorParams` (a model fitted by `python -m speinet_amd.detector fit`) that labels the clip when
+             `labels` is None; None: the reference's GoPro model (`detector.DEFAULT`).
 
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
@@ -482,7 +456,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     shape = (fr.T, fr.H, fr.W, 3)
     if out is not None and not (torch.is_tensor(out) and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
         raise ValueError(f"out must be a contiguous uint8 [{fr.T},{fr.H},{fr.W},3] tensor")
-    return ClipRun(model, fr, lab, out, numbers)
+    return ClipRun(model, fr, lab, out, numbers, detector)
 
 
 def _inputs(spec: str) -> list:
@@ -515,6 +489,8 @@ def main(argv=None) -> None:
     p.add_argument("--input", required=True, help="a directory of frames, or a glob (PNG / JPG / BMP); frames in file-name order")
     p.add_argument("--output", required=True, help="directory for the deblurred PNGs (input file name, .png)")
     p.add_argument("--labels", default=None, help="0/1 per frame (1 = sharp) as a .npy file; default: the LD detector labels the clip")
+    p.add_argument("--detector", default=None, help="a detector JSON file of `python -m speinet_amd.detector fit` (default: the reference's "
+                   "GoPro model)")
     p.add_argument("--model_path", required=True, help="checkpoint in the reference layout, or 'synthetic' (seed-0 test weights)")
     p.add_argument("--precision", choices=sorted(CORR_PRECISION), default="f16",
                    help="arithmetic of the GEMM-shaped kernels (default f16 with the top2 correlation: the throughput configuration)")
@@ -529,7 +505,7 @@ def main(argv=None) -> None:
         raise SystemExit(f"--input {a.input}: two frames share a file name stem (the outputs are <stem>.png)")
     labels = np.load(a.labels) if a.labels else None
     net = load_model(a.model_path, a.device, a.precision, a.graph)
-    run = deblur_clip(net, files, labels)
+    run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None)
     os.makedirs(a.output, exist_ok=True)
     H, W = run.frames.H, run.frames.W
     t0 = t_prev = time.time()
