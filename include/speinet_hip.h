@@ -463,6 +463,15 @@ int spei_frames_u8_in(const unsigned char* src, int64_t frame_stride, float* dst
  * stream, then nonzero iff the crop held a NaN or an infinity. */
 int spei_frame_u8_out(const float* src, unsigned char* dst, int* nonfinite, int H, int W, int Hp, int Wp, spei_stream_t stream);
 
+/* Pair statistics of consecutive frames, for the clip API's scene-cut rule (video.find_cuts; an extension beyond the reference): src =
+ * N >= 1 uint8 [H][W][3] frames, frame_stride bytes apart (rows packed; the frame-size bound of spei_frames_u8_in); prev (or NULL): one
+ * more packed frame, the one before frame 0.  On the integer luma Y = (77 R + 150 G + 29 B + 128) >> 8:
+ * hist[n][64] = the number of pixels of frame n with Y >> 2 == b (each row sums to H * W); sad[p] = the sum over pixels of
+ * |Y_a - Y_b| of consecutive pair p: N - 1 pairs, or N with prev, pair 0 then being (prev, frame 0).  N == 1 needs prev.  Both are
+ * cleared on the stream first.  Integer arithmetic only: the result is exact, whatever the launch shape and the order of the sums. */
+int spei_frame_pair_stats(const unsigned char* src, int64_t frame_stride, const unsigned char* prev, int N, int H, int W, int* hist,
+                          int64_t* sad, spei_stream_t stream);
+
 /* ---- training on a dataset (speinet_amd/data.py, speinet_amd/fit.py) ---- */
 
 /* One output frame of a training batch: a P x P rectangle of one uint8 [H][W][3] frame on the device. */

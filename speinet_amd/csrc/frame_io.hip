@@ -11,6 +11,11 @@
 //                        the harness scores (spei_frame_metrics, metrics.hip).  Optionally a flag, nonzero iff the crop held a
 //                        non-finite value, on which the clip API recomputes the window in bf16x3.
 //
+//   spei_frame_pair_stats — N uint8 [H][W][3] frames (and optionally the frame before them) -> the 64-bin histogram of every frame's
+//                        integer luma Y = (77 R + 150 G + 29 B + 128) >> 8 and the sum of |Y_a - Y_b| over every consecutive pair:
+//                        the statistics of the clip API's scene-cut rule (video.find_cuts; an extension, the reference has no such
+//                        pass).  Integers throughout: the result does not depend on the launch shape or on the order of the sums.
+//
 // Streaming kernels, one thread per group of 4 pixels of a row: 12 bytes of uint8 read (three dwords when the rows are 4-byte
 // aligned), one 16-byte store per plane.  The mirrored indices are computed in the pad band only.  HBM-bound: a 720p frame is
 // 2.8 MB in and 11 MB out.
@@ -127,6 +132,73 @@ __global__ __launch_bounds__(256) void frame_u8_out_kernel(const float* __restri
     if (nonfinite && bad) atomicOr(nonfinite, 1);           // rare: one atomic per thread that met a non-finite value
 }
 
+// ---- pair statistics -----------------------------------------------------------------------------------------------------------
+// grid (x, n): the blocks of column n stream frame n (member b of its pair: its histogram) beside the frame before it (member a:
+// frame n - 1, or `prev` for n = 0, or none), so a frame is read twice at most.  Rows are packed, so a frame is one run of H * W
+// pixels: 12-byte groups of 4 pixels as three dwords when both frames start on a 4-byte boundary, bytes otherwise and in the last,
+// partial group.  Histogram counts go to one LDS copy per wave; SAD partials are summed per wave, then per block; each block then
+// issues one integer atomic per non-empty bin and one 64-bit atomic for its SAD (Guideline 12: integer adds commute exactly).
+constexpr int PAIR_BLOCKS = 256;                           // blocks per frame
+constexpr int PAIR_BINS = 64;
+// A thread adds at most 4 * 255 per group, and a frame holds fewer than 2^31 / 12 groups (the bound of spei_frames_u8_in), so with
+// PAIR_BLOCKS blocks of 256 threads even a whole block's SAD fits 32 bits: the partials are widened once, at the global atomic.
+static_assert((((1ll << 31) / 12) / (256ll * PAIR_BLOCKS) + 1) * 256 * 4 * 255 < (1ll << 32), "pair SAD: a block's sum must fit 32 bits");
+
+__device__ __forceinline__ void load_group(const unsigned char* __restrict__ p, int valid, bool aligned, uint32_t (&w)[3]) {
+    if (valid == 4 && aligned) {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+        w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
+    } else {
+        w[0] = w[1] = w[2] = 0u;
+#pragma unroll
+        for (int j = 0; j < 12; ++j)
+            if (j < 3 * valid) w[j >> 2] |= (uint32_t)p[j] << (8 * (j & 3));
+    }
+}
+
+__device__ __forceinline__ int luma_of(const uint32_t (&w)[3], int k) {
+    return (77 * byte_of(w, 3 * k) + 150 * byte_of(w, 3 * k + 1) + 29 * byte_of(w, 3 * k + 2) + 128) >> 8;
+}
+
+__global__ __launch_bounds__(256) void frame_pair_stats_kernel(const unsigned char* __restrict__ src, int64_t fstride,
+                                                               const unsigned char* __restrict__ prev, int* __restrict__ hist,
+                                                               unsigned long long* __restrict__ sad, int64_t pixels) {
+    __shared__ unsigned int bins[4][PAIR_BINS];
+    __shared__ unsigned int block_sad;
+    const int n = blockIdx.y, wave = threadIdx.x >> 6;
+    const unsigned char* b = src + n * fstride;
+    const unsigned char* a = n > 0 ? b - fstride : prev;   // null: frame 0 of a call without `prev` has no pair
+    const bool aligned = (((uintptr_t)b | (uintptr_t)a) & 3) == 0;
+    (&bins[0][0])[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) block_sad = 0u;
+    __syncthreads();
+    const int64_t groups = (pixels + 3) >> 2, full = pixels >> 2;
+    unsigned int part = 0u;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+        const int valid = g < full ? 4 : (int)(pixels - 4 * g);
+        uint32_t wb[3], wa[3];
+        load_group(b + 12 * g, valid, aligned, wb);
+        if (a) load_group(a + 12 * g, valid, aligned, wa);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < valid) {
+                const int yb = luma_of(wb, k);
+                atomicAdd(&bins[wave][yb >> 2], 1u);
+                if (a) part += (unsigned int)abs(luma_of(wa, k) - yb);
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) part += __shfl_xor(part, m);
+    if (a && (threadIdx.x & 63) == 0) atomicAdd(&block_sad, part);
+    __syncthreads();
+    if (threadIdx.x < PAIR_BINS) {
+        const unsigned int c = bins[0][threadIdx.x] + bins[1][threadIdx.x] + bins[2][threadIdx.x] + bins[3][threadIdx.x];
+        if (c) atomicAdd(&hist[n * PAIR_BINS + threadIdx.x], (int)c);
+    }
+    if (a && threadIdx.x == 0) atomicAdd(&sad[prev ? n : n - 1], (unsigned long long)block_sad);
+}
+
 inline int grid_for(int64_t total) { return (int)((total + 255) / 256 < BLOCKS_MAX ? (total + 255) / 256 : BLOCKS_MAX); }
 
 }  // namespace
@@ -165,5 +237,26 @@ extern "C" int spei_frame_u8_out(const float* src, unsigned char* dst, int* nonf
     hipLaunchKernelGGL(frame_u8_out_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, dst, nonfinite, H, W, Wp,
                        (int64_t)Hp * Wp, gw, total, vec_in, vec_out);
     SPEI_CHECK_LAUNCH("spei_frame_u8_out");
+    return 0;
+}
+
+extern "C" int spei_frame_pair_stats(const unsigned char* src, int64_t frame_stride, const unsigned char* prev, int N, int H, int W,
+                                     int* hist, int64_t* sad, spei_stream_t stream) {
+    SPEI_REQUIRE(src && hist && sad, "spei_frame_pair_stats: null pointer (src, hist and sad are required)");
+    SPEI_REQUIRE(N >= 1 && N <= 65535, "spei_frame_pair_stats: %d frames (1..65535 per call)", N);
+    SPEI_REQUIRE(N > 1 || prev, "spei_frame_pair_stats: one frame and no prev make no pair");
+    SPEI_REQUIRE(H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), "spei_frame_pair_stats: bad frame shape %dx%d", H, W);
+    SPEI_REQUIRE(N == 1 || frame_stride >= (int64_t)H * W * 3, "spei_frame_pair_stats: frame stride %lld < one %dx%d frame",
+                 (long long)frame_stride, H, W);
+    const int64_t pixels = (int64_t)H * W, blocks = ((pixels + 3) / 4 + 255) / 256;
+    const int pairs = prev ? N : N - 1;
+    if (hipMemsetAsync(hist, 0, sizeof(int) * PAIR_BINS * N, (hipStream_t)stream) != hipSuccess ||
+        hipMemsetAsync(sad, 0, sizeof(int64_t) * pairs, (hipStream_t)stream) != hipSuccess) {
+        spei_set_error("spei_frame_pair_stats: clearing the results failed");
+        return -2;
+    }
+    hipLaunchKernelGGL(frame_pair_stats_kernel, dim3((int)(blocks < PAIR_BLOCKS ? blocks : PAIR_BLOCKS), N), dim3(256), 0,
+                       (hipStream_t)stream, src, frame_stride, prev, hist, reinterpret_cast<unsigned long long*>(sad), pixels);
+    SPEI_CHECK_LAUNCH("spei_frame_pair_stats");
     return 0;
 }

@@ -110,15 +110,14 @@ def predict(features, params: Optional[DetectorParams] = None) -> np.ndarray:
     return ((f @ np.asarray(p.coef) + p.intercept) > 0).astype(np.int64)
 
 
-def clip_features(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH) -> torch.Tensor:
-    """The six measures of every frame of a clip (`video.frames_of`'s result), `batch` frames at a time: uint8 upload from two
-    page-locked staging buffers, gray planes (spei_frames_u8_in), focus measures.  Image paths are decoded on worker threads two
-    batches ahead.  [T,6] float32 on `device`; device memory is bounded by one batch."""
-    from . import ops
+def clip_batches(fr, device, batch: int = DETECT_BATCH):
+    """One streaming pass over a clip (`video.frames_of`'s result): yields (first frame index, uint8 [n,H,W,3] device view) for every
+    `batch` frames in turn, on the current stream of `device`.  Host frames are uploaded from two page-locked staging buffers (image
+    paths decoded on worker threads two batches ahead), device-resident frames copied on the device.  The view is of ONE buffer that
+    the next batch overwrites: device memory is bounded by one batch.  The consumer sets grad mode and the current device."""
     dev, B = torch.device(device), batch
     T, H, W = fr.T, fr.H, fr.W
-    feats = []
-    with torch.no_grad(), torch.cuda.device(dev), ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as pool:
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as pool:
         futs = {}
 
         def want(upto):
@@ -145,9 +144,39 @@ def clip_features(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH) 
             for i in range(i0, i0 + n):
                 if fr.on_device(i):
                     dev_batch[i - i0].copy_(fr.device(i))
-            _, gray = ops.frames_u8_in(dev_batch[:n], gray=True, planes=False)
-            feats.append(gray_focus_measures(gray, kernel_size))
-    return torch.cat(feats)
+            yield i0, dev_batch[:n]
+
+
+def clip_pass(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, features: bool = True, pair_stats: bool = False):
+    """One `clip_batches` pass over a clip that yields the six focus measures of every frame ([T,6] float32, or None when not
+    `features`), the pair statistics of `ops.frame_pair_stats` over the whole clip ((sad int64 [T-1], hist int64 [T,64]), or None when
+    not `pair_stats`), or both, all on `device`.  The last frame of a batch is kept as `prev` of the next, so a pair that straddles two
+    batches is counted like any other: device memory is bounded by one batch plus one frame."""
+    from . import ops
+    dev = torch.device(device)
+    if pair_stats and batch < 2:
+        raise ValueError("pair statistics need batches of at least 2 frames (the first batch has no frame before it)")
+    feats, sads, hists, prev = [], [], [], None
+    with torch.no_grad(), torch.cuda.device(dev):
+        for i0, frames in clip_batches(fr, dev, batch):
+            if features:
+                _, gray = ops.frames_u8_in(frames, gray=True, planes=False)
+                feats.append(gray_focus_measures(gray, kernel_size))
+            if pair_stats:
+                sad, hist = ops.frame_pair_stats(frames, prev if i0 else None)
+                sads.append(sad)
+                hists.append(hist)
+                if i0 + len(frames) < fr.T:
+                    prev = torch.empty_like(frames[-1]) if prev is None else prev
+                    prev.copy_(frames[-1])
+    return (torch.cat(feats) if features else None), ((torch.cat(sads), torch.cat(hists)) if pair_stats else None)
+
+
+def clip_features(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH) -> torch.Tensor:
+    """The six measures of every frame of a clip (`video.frames_of`'s result), `batch` frames at a time: uint8 upload from two
+    page-locked staging buffers, gray planes (spei_frames_u8_in), focus measures.  Image paths are decoded on worker threads two
+    batches ahead.  [T,6] float32 on `device`; device memory is bounded by one batch."""
+    return clip_pass(fr, device, kernel_size, batch)[0]
 
 
 def _clips(dir_data: str) -> list:

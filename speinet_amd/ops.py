@@ -227,6 +227,27 @@ def frames_u8_in(u8: torch.Tensor, out: Optional[torch.Tensor] = None, gray: boo
     return out, g
 
 
+def frame_pair_stats(u8: torch.Tensor, prev: Optional[torch.Tensor] = None):
+    """Pair statistics of consecutive uint8 frames [N,H,W,3] on the device (each frame packed, any frame stride), optionally with the
+    packed frame `prev` [H,W,3] before them, on the integer luma Y = (77 R + 150 G + 29 B + 128) >> 8 (csrc/frame_io.hip) ->
+    (sad int64 [N-1], or [N] with `prev` (pair 0 is then (prev, frame 0)): the sum over pixels of |Y_a - Y_b| per consecutive pair;
+    hist int64 [N,64]: pixels per value of Y >> 2).  Exact integers.  One launch on the current stream, no host sync."""
+    assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4
+    n, h, w, c = u8.shape
+    assert c == 3 and u8.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
+    dev = u8.device
+    assert prev is None or (prev.device == dev and prev.dtype == torch.uint8 and tuple(prev.shape) == (h, w, 3) and prev.is_contiguous())
+    pairs = n if prev is not None else n - 1
+    hist = torch.empty(n, 64, dtype=torch.int32, device=dev)
+    sad = torch.empty(pairs, dtype=torch.int64, device=dev)
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_frame_pair_stats(_vp(u8.data_ptr()), u8.stride(0), _vp(prev.data_ptr() if prev is not None else 0), n, h, w,
+                                             _vp(hist.data_ptr()), _vp(sad.data_ptr()), st), "spei_frame_pair_stats")
+    return sad, hist.long()
+
+
 def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: Optional[torch.Tensor] = None,
                    gt: Optional[torch.Tensor] = None):
     """The reference's blur synthesis on resident frames (csrc/blurset.hip): uint8 frames [T,H,W,3] on the device (each frame packed,

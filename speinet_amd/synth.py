@@ -170,6 +170,20 @@ def synth_frames_edges(b: int, h: int, w: int, seed: int = 1700, zero_ref: tuple
     return torch.from_numpy(x), torch.from_numpy(gt)
 
 
+def synth_scene_u8(t: int, h: int, w: int, seed: int, step: int = 1) -> np.ndarray:
+    """One shot as uint8 [t,h,w,3]: the sharp reference frame of ``synth_frames_edges(1, h, w, seed)`` rolled by (step i, -step i)
+    pixels for frame i, scaled to 0..255, plus integer noise in [-3, 3] from RandomState(seed).  Shots of different seeds differ in
+    their tonal distribution (the smooth ``synth_frames`` fields do not: their luma histograms are nearly equal), so a concatenation of
+    such shots has hard cuts a histogram rule can find."""
+    ref = synth_frames_edges(1, h, w, seed)[0][0, 4].numpy()
+    r = np.random.RandomState(seed)
+    out = np.empty((t, h, w, 3), dtype=np.uint8)
+    for i in range(t):
+        f = np.roll(ref, (step * i, -step * i), axis=(1, 2)).transpose(1, 2, 0)
+        out[i] = np.clip(np.round(f * 255).astype(np.int64) + r.randint(-3, 4, size=f.shape), 0, 255)
+    return out
+
+
 def synth_frames_flat(b: int, h: int, w: int, seed: int = 2300, zero_ref: tuple = (), bar: int | None = None) -> torch.Tensor:
     """Flat content, the third content class: ``synth_frames`` windows with what real footage has and smooth fields lack — exactly
     equal pixels over whole regions.  Every sample gets black letterbox bars (``bar`` rows, default h // 4, at the top and the bottom of every frame)

@@ -2,14 +2,16 @@
 `deblur_clip`; the command line, for the user's own footage (no ground truth), is
 
     python -m speinet_amd.video --input <dir | glob> --output <dir> --model_path <checkpoint | synthetic> [--labels <file.npy>]
-                                [--detector <detector.json>]
+                                [--detector <detector.json>] [--cuts none|auto|<file>]
 
 and the dataset harness (speinet_amd.inference) runs every clip through `deblur_clip` as well, adding its ground truth and metrics.
   * labels — given (0/1 per frame, 1 = sharp), or computed by the LD detector (speinet_amd.detector) in a first streaming pass over the
     clip in batches of 16 frames: gray planes from the ingest kernel, focus measures, logistic regression;
   * the window plan — `selection.assemble_windows` on the frame numbers (by default a frame's number is its index in the clip; the
     harness passes the numbers in its file names): reflect-padded clip, `blurry_indices`, references more than 7 frames away zeroed,
-    routing by the zeroed reference;
+    routing by the zeroed reference; with scene cuts (`cuts`: given, or found by `scene_stats` + `find_cuts` in the labelling pass),
+    every scene is planned as a clip of its own, so no window and no reference frame crosses a cut (an extension: the reference's
+    data sets are one folder per shot);
   * the windows — `forward_window` with a per-clip `EncoderCache`, `prefetch_window` one window ahead, windows alternating over two
     launch streams that the model keeps, in whatever `precision` / `corr_precision` / `use_graph` / `streams` the caller set on it;
   * frames cross PCIe as uint8 from page-locked staging buffers (`FrameCache`) and are decoded, for image paths, on worker threads a
@@ -241,11 +243,66 @@ def labels_of(labels, T: int) -> np.ndarray:
     return lab.astype(np.int64)
 
 
-def window_plan(labels, n_seq: int = 3, numbers=None) -> list:
-    """The window plan for a clip labelled `labels`: one entry per output frame with the n_seq window frames, the two reference frames
-    (frame indices), whether each reference is zeroed (more than 7 frame numbers from the last window frame; `zero_pre` is the
-    routing: True = no-reference branch) and the n_seq + 2 `forward_window` keys (frame indices, `ZERO` for a zeroed reference).
-    `numbers`: the frame numbers the reference gap is measured in (the harness's come from its file names); default: the indices."""
+def cuts_of(cuts, T: int) -> list:
+    """Validate scene cuts for a clip of T frames: a strictly increasing sequence of first-frame-of-scene indices in 1..T-1 (None: no
+    cuts).  Raises ValueError with the reason."""
+    if cuts is None:
+        return []
+    if isinstance(cuts, (str, bytes)) or not hasattr(cuts, "__iter__"):
+        raise ValueError(f"cuts must be a sequence of frame indices, got {cuts!r}")
+    arr = np.asarray(list(cuts))
+    whole = arr.size == 0 or arr.dtype.kind in "iu" or (arr.dtype.kind == "f" and (arr == np.floor(arr)).all())
+    if arr.ndim != 1 or not whole:
+        raise ValueError(f"cuts must be a flat sequence of whole frame indices, got {cuts!r}")
+    out = [int(c) for c in arr]
+    for c in out:
+        if not 1 <= c <= T - 1:
+            raise ValueError(f"cut {c} is outside 1..{T - 1}: a cut is the index of a scene's first frame in a clip of {T} frames")
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"cuts must be strictly increasing, got {out}")
+    return out
+
+
+def find_cuts(sad, hist, pixels: int, *, hist_min: float = 0.25, ratio: float = 3.0, min_delta: float = 8.0, window: int = 2) -> list:
+    """Hard scene cuts from the pair statistics of a clip (`scene_stats`): sad [T-1], hist [T,64], `pixels` = H * W.  With
+    g[i] = sum_b |hist[i+1][b] - hist[i][b]| / (2 pixels) (the share of pixels that changed luma bin, 0..1) and d[i] = sad[i] / pixels
+    (mean absolute luma difference), there is a cut before frame i + 1 iff
+      g[i] >= hist_min,  d[i] >= min_delta,  and  g[i] >= ratio * max(g[j]) over the other pairs j with |j - i| <= window
+    (vacuously true when there are none).  The histogram term is blind to motion; the SAD term vetoes small global brightness steps;
+    the neighbourhood term makes a one-frame flash no cut, because its two pairs veto each other.  Returns the sorted list of
+    first-frame-of-scene indices.
+
+    Blind spots: a cut between two shots of the same tonal distribution has g near 0 and is missed; dissolves and fades are not hard
+    cuts and are not looked for; two cuts within `window` frames of each other veto each other.  The four defaults are design
+    parameters, not measurements: ratio 3 over a window of 2 is borrowed from common adaptive cut detectors, and nobody has tuned any
+    of them on real footage.  An extension beyond the reference, whose data sets hold one shot per folder."""
+    hist = np.asarray(hist, dtype=np.int64)
+    sad = np.asarray(sad, dtype=np.float64).reshape(-1)
+    if hist.ndim != 2 or hist.shape[0] < 2 or sad.size != hist.shape[0] - 1:
+        raise ValueError(f"find_cuts needs hist [T,bins] of T >= 2 frames and sad [T-1]; got {hist.shape} and {sad.shape}")
+    if pixels <= 0 or window < 0:
+        raise ValueError(f"find_cuts: pixels must be positive and window >= 0; got {pixels} and {window}")
+    g = np.abs(np.diff(hist, axis=0)).sum(axis=1) / (2.0 * pixels)
+    d = sad / pixels
+    cuts = []
+    for i in range(g.size):
+        others = np.concatenate([g[max(0, i - window):i], g[i + 1:i + 1 + window]])
+        if g[i] >= hist_min and d[i] >= min_delta and (others.size == 0 or g[i] >= ratio * others.max()):
+            cuts.append(i + 1)
+    return cuts
+
+
+def scene_stats(frames, device):
+    """The pair statistics of a clip (anything `frames_of` accepts) in one streaming pass of DETECT_BATCH frames at a time on `device`
+    (`detector.clip_pass`: the labelling pass's uploader; `ops.frame_pair_stats` per batch, the last frame of a batch carried over as
+    `prev` of the next): (sad int64 [T-1], hist int64 [T,64]) as numpy arrays, the input of `find_cuts`."""
+    fr = frames if isinstance(frames, _Frames) else frames_of(frames)
+    sad, hist = detector.clip_pass(fr, device, batch=DETECT_BATCH, features=False, pair_stats=True)[1]
+    return sad.cpu().numpy(), hist.cpu().numpy()
+
+
+def _scene_plan(labels, n_seq: int, numbers) -> list:
+    """The plan of one continuous scene: `selection.assemble_windows` on its frames."""
     T = len(labels)
     number = int if numbers is None else (lambda i: int(numbers[int(i)]))
     wins = selection.assemble_windows([str(i) for i in range(T)], labels, n_seq, True, number=number)
@@ -254,6 +311,30 @@ def window_plan(labels, n_seq: int = 3, numbers=None) -> list:
         win, pre, sub = [int(f) for f in w["window"]], int(w["pre"]), int(w["sub"])
         plan.append({"index": k, "window": win, "pre": pre, "sub": sub, "zero_pre": bool(w["zero_pre"]), "zero_sub": bool(w["zero_sub"]),
                      "keys": win + [ZERO if w["zero_pre"] else pre, ZERO if w["zero_sub"] else sub]})
+    return plan
+
+
+def window_plan(labels, n_seq: int = 3, numbers=None, cuts=None) -> list:
+    """The window plan for a clip labelled `labels`: one entry per output frame with the n_seq window frames, the two reference frames
+    (frame indices), whether each reference is zeroed (more than 7 frame numbers from the last window frame; `zero_pre` is the
+    routing: True = no-reference branch) and the n_seq + 2 `forward_window` keys (frame indices, `ZERO` for a zeroed reference).
+    `numbers`: the frame numbers the reference gap is measured in (the harness's come from its file names); default: the indices.
+    `cuts` (`cuts_of`): the first frame of every scene after the first.  Each scene [a, b) is planned as a clip of its own, on
+    labels[a:b] and numbers[a:b], with every frame index shifted by a (`index` stays the output frame's index in the whole clip): the
+    windows reflect at the scene's ends and the references come from the scene.  A one-frame scene {i} is planned as the first entry of
+    the two-frame clip [i, i] with labels [l_i, l_i] and numbers [n_i, n_i]."""
+    T = len(labels)
+    cuts = cuts_of(cuts, T)
+    if not cuts:
+        return _scene_plan(labels, n_seq, numbers)
+    plan = []
+    for a, b in zip([0] + cuts, cuts + [T]):
+        at = [a, a] if b - a == 1 else list(range(a, b))           # the scene's frames: a one-frame scene twice
+        scene = _scene_plan([labels[i] for i in at], n_seq, [i if numbers is None else numbers[i] for i in at])[:b - a]
+        for p in scene:
+            q = dict(p, index=a + p["index"], window=[at[i] for i in p["window"]], pre=at[p["pre"]], sub=at[p["sub"]])
+            q["keys"] = [k if k is ZERO else at[k] for k in p["keys"]]
+            plan.append(q)
     return plan
 
 
@@ -268,11 +349,12 @@ def _lanes(model, device, n: int) -> list:
 
 class ClipRun:
     """Iterator of (index, uint8 [H,W,3] device tensor) in frame order; see `deblur_clip`.  `labels` (0/1 per frame; computed on first
-    access when the caller gave none) and `plan` (`window_plan(labels, numbers=numbers)`) describe what runs; `recomputed` lists the
+    access when the caller gave none), `cuts` (the scene cuts in use; found on first access when the caller asked for "auto", in the
+    labelling pass when that runs too) and `plan` (`window_plan(labels, numbers=numbers, cuts=cuts)`) describe what runs; `recomputed` lists the
     frames that were recomputed in bf16x3 because their 16-bit pass left a non-finite value; `seconds[k]` is window k's host time
     [assembling its input, enqueueing it] (the wait for a free launch slot excluded)."""
 
-    def __init__(self, model, frames: _Frames, labels, out, numbers=None, detector_params=None):
+    def __init__(self, model, frames: _Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None):
         self.model, self.frames = model, frames
         self.detector = detector.DEFAULT if detector_params is None else detector_params
         params = list(model.parameters())
@@ -280,6 +362,8 @@ class ClipRun:
         if self.device.type != "cuda":
             raise RuntimeError("speinet_amd runs on MI355X only (HIP kernels): move the model to a ROCm device first")
         self._labels = labels
+        self._cuts = cuts                # a list, or None while "auto" has not run
+        self.cut_params = dict(cut_params or {})
         if out is not None and out.device != self.device:
             raise ValueError(f"out is on {out.device}, the model on {self.device}")
         self.out = out
@@ -292,13 +376,19 @@ class ClipRun:
     @property
     def labels(self) -> np.ndarray:
         if self._labels is None:
-            self._labels = self._detect()
+            self._analyse()
         return self._labels
+
+    @property
+    def cuts(self) -> list:
+        if self._cuts is None:
+            self._analyse()
+        return self._cuts
 
     @property
     def plan(self) -> list:
         if self._plan is None:
-            self._plan = window_plan(self.labels, numbers=self.numbers)
+            self._plan = window_plan(self.labels, numbers=self.numbers, cuts=self.cuts)
         return self._plan
 
     def __iter__(self):
@@ -309,10 +399,16 @@ class ClipRun:
             self._it = self._run()
         return next(self._it)
 
-    def _detect(self) -> np.ndarray:
-        """The LD detector's labels, DETECT_BATCH frames at a time: uint8 upload, gray planes (spei_frames_u8_in), focus measures."""
-        p = self.detector
-        return detector.predict(detector.clip_features(self.frames, self.device, p.kernel_size, DETECT_BATCH), p)
+    def _analyse(self) -> None:
+        """Whatever is missing of the LD detector's labels and the scene cuts, in ONE pass over the clip, DETECT_BATCH frames at a time:
+        uint8 upload, then gray planes (spei_frames_u8_in) and focus measures, pair statistics (spei_frame_pair_stats), or both."""
+        p, fr = self.detector, self.frames
+        feats, stats = detector.clip_pass(fr, self.device, p.kernel_size, DETECT_BATCH, features=self._labels is None,
+                                          pair_stats=self._cuts is None)
+        if feats is not None:
+            self._labels = detector.predict(feats, p)
+        if stats is not None:
+            self._cuts = find_cuts(stats[0].cpu().numpy(), stats[1].cpu().numpy(), fr.H * fr.W, **self.cut_params)
 
     def _run(self):
         m, dev, fr = self.model, self.device, self.frames
@@ -431,7 +527,7 @@ class ClipRun:
 
 
 def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
-                detector=None) -> ClipRun:
+                detector=None, cuts=None, cut_params: Optional[dict] = None) -> ClipRun:
     """Deblur a clip: an iterator of (index, uint8 [H,W,3] frame on the model's device), in frame order, one per input frame.
 
     model  — an eval() `SPEINet` on a ROCm device; its `precision`, `corr_precision`, `use_graph` and `streams` are used as set.
@@ -444,6 +540,11 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     numbers — optional frame number per frame, in which the distance to a reference frame is measured (default: the indices).
     detector — optional `detector.DetectorParams` (a model fitted by `python -m speinet_amd.detector fit`) that labels the clip when
              `labels` is None; None: the reference's GoPro model (`detector.DEFAULT`).
+    cuts   — scene cuts: None (the default) plans the clip as one continuous scene; a strictly increasing sequence of
+             first-frame-of-scene indices in 1..T-1 is used as given; "auto" finds hard cuts with `scene_stats` and `find_cuts` (in
+             the labelling pass when `labels` is None: the clip is uploaded once).  Every scene is planned as a clip of its own
+             (`window_plan`), so no window and no reference frame crosses a cut.  `ClipRun.cuts` holds the list in use.
+    cut_params — optional keyword arguments of `find_cuts` for "auto" (hist_min, ratio, min_delta, window: untuned defaults).
 
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
@@ -456,12 +557,29 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     shape = (fr.T, fr.H, fr.W, 3)
     if out is not None and not (torch.is_tensor(out) and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
         raise ValueError(f"out must be a contiguous uint8 [{fr.T},{fr.H},{fr.W},3] tensor")
-    return ClipRun(model, fr, lab, out, numbers, detector)
+    if isinstance(cuts, str):
+        if cuts != "auto":
+            raise ValueError(f"cuts must be None, \"auto\" or a sequence of frame indices, got {cuts!r}")
+        cuts = None
+    else:
+        cuts = cuts_of(cuts, fr.T)
+    if cut_params is not None and set(cut_params) - {"hist_min", "ratio", "min_delta", "window"}:
+        raise ValueError(f"cut_params holds {sorted(set(cut_params) - {'hist_min', 'ratio', 'min_delta', 'window'})}: "
+                         "find_cuts takes hist_min, ratio, min_delta and window")
+    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params)
 
 
 def _inputs(spec: str) -> list:
     files = [os.path.join(spec, f) for f in os.listdir(spec)] if os.path.isdir(spec) else glob.glob(spec)
     return sorted(f for f in files if f.lower().endswith(IMAGE_EXTS) and os.path.isfile(f))
+
+
+def read_cuts(path: str) -> list:
+    """Scene cuts from a file: a .npy array, or a text file of whitespace-separated first-frame-of-scene indices."""
+    if path.lower().endswith(".npy"):
+        return np.asarray(np.load(path)).reshape(-1).tolist()
+    with open(path) as f:
+        return [int(tok) for tok in f.read().split()]
 
 
 def load_model(model_path: str, device, precision: str = "f16", graph: bool = True):
@@ -491,6 +609,8 @@ def main(argv=None) -> None:
     p.add_argument("--labels", default=None, help="0/1 per frame (1 = sharp) as a .npy file; default: the LD detector labels the clip")
     p.add_argument("--detector", default=None, help="a detector JSON file of `python -m speinet_amd.detector fit` (default: the reference's "
                    "GoPro model)")
+    p.add_argument("--cuts", default="none", help="scene cuts: 'none' (one continuous scene, the default), 'auto' (hard cuts found from "
+                   "luma histograms and frame differences), or a .npy / text file of first-frame-of-scene indices")
     p.add_argument("--model_path", required=True, help="checkpoint in the reference layout, or 'synthetic' (seed-0 test weights)")
     p.add_argument("--precision", choices=sorted(CORR_PRECISION), default="f16",
                    help="arithmetic of the GEMM-shaped kernels (default f16 with the top2 correlation: the throughput configuration)")
@@ -505,8 +625,11 @@ def main(argv=None) -> None:
         raise SystemExit(f"--input {a.input}: two frames share a file name stem (the outputs are <stem>.png)")
     labels = np.load(a.labels) if a.labels else None
     net = load_model(a.model_path, a.device, a.precision, a.graph)
-    run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None)
+    cuts = {"none": None, "auto": "auto"}[a.cuts] if a.cuts in ("none", "auto") else read_cuts(a.cuts)
+    run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts)
     os.makedirs(a.output, exist_ok=True)
+    for c in run.cuts:
+        print(f"# cut before {names[c]}", flush=True)
     H, W = run.frames.H, run.frames.W
     t0 = t_prev = time.time()
     with ThreadPoolExecutor(max_workers=4, thread_name_prefix="speinet-png") as writers:
