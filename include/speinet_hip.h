@@ -472,6 +472,40 @@ int spei_frame_u8_out(const float* src, unsigned char* dst, int* nonfinite, int 
 int spei_frame_pair_stats(const unsigned char* src, int64_t frame_stride, const unsigned char* prev, int N, int H, int W, int* hist,
                           int64_t* sad, spei_stream_t stream);
 
+/* ---- planar YUV frames of the clip API (speinet_amd/y4m.py, speinet_amd/video.py; an extension beyond the reference) ---- */
+
+#define SPEI_YUV_420_CENTER 0 /* 4:2:0, chroma sample at the centre of its 2x2 block (y4m C420jpeg, and bare C420) */
+#define SPEI_YUV_420_LEFT 1   /* 4:2:0, chroma co-sited with the even column, between the two rows (y4m C420mpeg2) */
+#define SPEI_YUV_444 2        /* 4:4:4 (y4m C444) */
+#define SPEI_YUV_BT601 0
+#define SPEI_YUV_BT709 1
+#define SPEI_YUV_FULL 0    /* Y, U, V in 0..255 */
+#define SPEI_YUV_LIMITED 1 /* Y in 16..235, U and V in 16..240 */
+
+/* A planar frame is the Y plane [H][W], then U, then V: [ceil(H/2)][ceil(W/2)] each for 4:2:0, [H][W] each for 4:4:4; uint8, packed,
+ * as in a y4m FRAME payload; H and W may be odd.  An RGB frame is packed uint8 [H][W][3] (what spei_frames_u8_in takes).
+ * Integer arithmetic only, so the result is defined bit for bit.  Q14 coefficients, round(c * 16384), per (matrix, range):
+ *                 yr    yg    yb |    ur    ug   ub |   vr    vg    vb | yo |    cy |    rv |    gu     gv |    bu
+ *   601 full    4899  9617  1868 | -2765 -5427 8192 | 8192 -6860 -1332 |  0 | 16384 | 22970 | -5638 -11700 | 29032
+ *   601 limited 4207  8260  1604 | -2428 -4768 7196 | 7196 -6026 -1170 | 16 | 19077 | 26149 | -6419 -13320 | 33050
+ *   709 full    3483 11718  1183 | -1877 -6315 8192 | 8192 -7441  -751 |  0 | 16384 | 25802 | -3069  -7670 | 30402
+ *   709 limited 2991 10064  1016 | -1649 -5547 7196 | 7196 -6536  -660 | 16 | 19077 | 29372 | -3494  -8731 | 34610
+ * `>>` floors.  Clipping: RGB and full range to [0,255], limited range to [16,235] (Y) and [16,240] (U, V).
+ *
+ * spei_yuv_to_rgb_u8: src = N planar frames, frame_stride bytes apart -> dst = N packed RGB frames.  The chroma of a pixel is formed
+ * times 16, U16 and V16, neighbour indices clamped to the plane: 4:4:4: 16 U[y][x].  4:2:0 rows, both sitings: j = y >> 1 and the
+ * other row j - 1 (y even) or j + 1 (y odd), weights 3 : 1.  Columns, CENTER: the same with i = x >> 1.  Columns, LEFT: 4 : 0 at even
+ * x, 2 : 2 of columns i and i + 1 at odd x.  With yy = cy * 16 * (Y - yo), u = U16 - 2048, v = V16 - 2048:
+ *   R = clip((yy + rv v + 2^17) >> 18), G = clip((yy + gu u + gv v + 2^17) >> 18), B = clip((yy + bu u + 2^17) >> 18).
+ * spei_rgb_u8_to_yuv: one packed RGB frame -> one planar frame.  Y = clip(((yr R + yg G + yb B + 2^13) >> 14) + yo) per pixel.
+ * 4:4:4: U = clip(((ur R + ug G + ub B + 2^13) >> 14) + 128), V likewise.  4:2:0 CENTER: the same on the channel sums over rows 2j,
+ * 2j + 1 and columns 2i, 2i + 1, with 2^15 and >> 16.  4:2:0 LEFT: on the sums over rows 2j, 2j + 1 of c[2i-1] + 2 c[2i] + c[2i+1],
+ * with 2^16 and >> 17.  Indices clamped to the frame.  The 4:2:0 resampling is this project's own definition. */
+int spei_yuv_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W, int layout, int matrix,
+                       int range, spei_stream_t stream);
+int spei_rgb_u8_to_yuv(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
+                       spei_stream_t stream);
+
 /* ---- training on a dataset (speinet_amd/data.py, speinet_amd/fit.py) ---- */
 
 /* One output frame of a training batch: a P x P rectangle of one uint8 [H][W][3] frame on the device. */

@@ -113,8 +113,9 @@ def predict(features, params: Optional[DetectorParams] = None) -> np.ndarray:
 def clip_batches(fr, device, batch: int = DETECT_BATCH):
     """One streaming pass over a clip (`video.frames_of`'s result): yields (first frame index, uint8 [n,H,W,3] device view) for every
     `batch` frames in turn, on the current stream of `device`.  Host frames are uploaded from two page-locked staging buffers (image
-    paths decoded on worker threads two batches ahead), device-resident frames copied on the device.  The view is of ONE buffer that
-    the next batch overwrites: device memory is bounded by one batch.  The consumer sets grad mode and the current device."""
+    paths decoded on worker threads two batches ahead), device-resident frames copied on the device.  The frames of a y4m clip are
+    staged and uploaded as their planar bytes and made RGB on the device (`fr.rgb`: ops.yuv_to_rgb_u8).  The view is of ONE buffer
+    that the next batch overwrites: device memory is bounded by one batch.  The consumer sets grad mode and the current device."""
     dev, B = torch.device(device), batch
     T, H, W = fr.T, fr.H, fr.W
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as pool:
@@ -125,9 +126,11 @@ def clip_batches(fr, device, batch: int = DETECT_BATCH):
                 if i not in futs and not fr.on_device(i):
                     futs[i] = pool.submit(fr.host, i)
 
-        stage = [torch.empty(B, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        shape = (B, H, W, 3) if fr.yuv is None else (B, fr.items.frame_bytes)
+        stage = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         events = [None, None]
         dev_batch = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+        dev_planar = None if fr.yuv is None else torch.empty(shape, dtype=torch.uint8, device=dev)
         for b, i0 in enumerate(range(0, T, B)):
             n = min(B, T - i0)
             want(i0 + 2 * B)
@@ -138,7 +141,11 @@ def clip_batches(fr, device, batch: int = DETECT_BATCH):
             for i in host:
                 st[i - i0].numpy()[...] = futs.pop(i).result()
             if host:
-                dev_batch[:n].copy_(st[:n], non_blocking=True)
+                if dev_planar is None:
+                    dev_batch[:n].copy_(st[:n], non_blocking=True)
+                else:
+                    dev_planar[:n].copy_(st[:n], non_blocking=True)
+                    fr.rgb(dev_planar[:n], out=dev_batch[:n])
                 events[b % 2] = torch.cuda.Event()
                 events[b % 2].record()
             for i in range(i0, i0 + n):

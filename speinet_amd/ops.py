@@ -16,7 +16,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, y4m
 from .pack import BF16, F16, F32, LP_DTYPE, PackedW, fmt_of
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
@@ -292,6 +292,52 @@ def frame_u8_out(x: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = 
         st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         _lib.check(lib.spei_frame_u8_out(_vp(x.data_ptr()), _vp(out.data_ptr()), _vp(nonfinite.data_ptr() if nonfinite is not None else 0),
                                          h, w, hp, wp, st), "spei_frame_u8_out")
+    return out
+
+
+def yuv_frame_bytes(h: int, w: int, layout: int) -> int:
+    """Bytes of one planar YUV frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0, [h][w] each for 4:4:4."""
+    return y4m.frame_bytes(h, w, layout)
+
+
+def yuv_to_rgb_u8(planar: torch.Tensor, h: int, w: int, layout: int, matrix: int, range: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Planar uint8 YUV frames on the device, [N, frame_bytes] (rows any stride apart) or one [frame_bytes], as in a y4m FRAME payload
+    -> packed RGB uint8 [N,h,w,3] (csrc/yuv_io.hip: integer arithmetic, defined bit for bit in include/speinet_hip.h).  `layout`,
+    `matrix`, `range`: the constants of speinet_amd.y4m (SPEI_YUV_*).  `out` (optional): a contiguous uint8 [N,h,w,3] destination.
+    One launch on the current stream, no host sync."""
+    assert planar.is_cuda and planar.dtype == torch.uint8 and planar.dim() in (1, 2)
+    fr = planar if planar.dim() == 2 else planar.unsqueeze(0)
+    n, nb = fr.shape
+    assert nb == yuv_frame_bytes(h, w, layout) and fr.stride(1) == 1, "frames must be packed planar frames (any frame stride)"
+    dev = planar.device
+    if out is None:
+        out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    assert out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (n, h, w, 3) and out.is_contiguous()
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_yuv_to_rgb_u8(_vp(fr.data_ptr()), fr.stride(0), _vp(out.data_ptr()), n, h, w, layout, matrix, range, st),
+                   "spei_yuv_to_rgb_u8")
+    return out
+
+
+def rgb_u8_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One packed RGB uint8 frame [h,w,3] on the device -> its planar YUV frame, uint8 [frame_bytes], a y4m FRAME payload
+    (csrc/yuv_io.hip; the inverse definition of `yuv_to_rgb_u8`).  `out` (optional): a contiguous uint8 [frame_bytes] destination.
+    One launch on the current stream, no host sync."""
+    assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.is_contiguous()
+    h, w = rgb.shape[:2]
+    nb = yuv_frame_bytes(h, w, layout)
+    dev = rgb.device
+    if out is None:
+        out = torch.empty(nb, dtype=torch.uint8, device=dev)
+    assert out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (nb,) and out.is_contiguous()
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_rgb_u8_to_yuv(_vp(rgb.data_ptr()), _vp(out.data_ptr()), h, w, layout, matrix, range, st),
+                   "spei_rgb_u8_to_yuv")
     return out
 
 

@@ -1,8 +1,12 @@
 """The clip loop: deblur a clip of uint8 frames of any size (at least 20x20), with or without sharpness labels.  The library API is
 `deblur_clip`; the command line, for the user's own footage (no ground truth), is
 
-    python -m speinet_amd.video --input <dir | glob> --output <dir> --model_path <checkpoint | synthetic> [--labels <file.npy>]
-                                [--detector <detector.json>] [--cuts none|auto|<file>]
+    python -m speinet_amd.video --input <dir | glob | clip.y4m | -> --output <dir | out.y4m | -> --model_path <checkpoint | synthetic>
+                                [--labels <file.npy>] [--detector <detector.json>] [--cuts none|auto|<file>]
+                                [--matrix bt601|bt709] [--range full|limited] [--fps num:den] [--chroma 420jpeg|420mpeg2|444]
+
+(`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; stdin is spooled to a temporary file
+on disk before the first frame is deblurred, see `main`)
 
 and the dataset harness (speinet_amd.inference) runs every clip through `deblur_clip` as well, adding its ground truth and metrics.
   * labels — given (0/1 per frame, 1 = sharp), or computed by the LD detector (speinet_amd.detector) in a first streaming pass over the
@@ -15,7 +19,9 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
   * the windows — `forward_window` with a per-clip `EncoderCache`, `prefetch_window` one window ahead, windows alternating over two
     launch streams that the model keeps, in whatever `precision` / `corr_precision` / `use_graph` / `streams` the caller set on it;
   * frames cross PCIe as uint8 from page-locked staging buffers (`FrameCache`) and are decoded, for image paths, on worker threads a
-    few windows ahead; a window whose 16-bit pass left a non-finite value is recomputed in bf16x3.
+    few windows ahead; a window whose 16-bit pass left a non-finite value is recomputed in bf16x3;
+  * a y4m clip (speinet_amd.y4m) crosses PCIe as its planar bytes, 1.5 per pixel for 4:2:0, and becomes packed RGB on the device
+    (csrc/yuv_io.hip, integer arithmetic); a y4m output is made there from the deblurred frame the same way.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -28,6 +34,7 @@ import argparse
 import collections
 import glob
 import os
+import sys
 import time
 import warnings
 from concurrent.futures import Future, ThreadPoolExecutor
@@ -36,7 +43,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import detector, ops, selection
+from . import detector, ops, selection, y4m
 from .speinet import EncoderCache
 
 ZERO = ("zero",)                 # window key of a zeroed reference frame
@@ -72,8 +79,9 @@ class FrameCache:
     per window), and allocating page-locked memory per frame synchronises the device.  Bounded LRUs (a 720p RGB frame is 2.8 MB)."""
     RING = 8
 
-    def __init__(self, pool: ThreadPoolExecutor, load, device, capacity: int = 16):
+    def __init__(self, pool: ThreadPoolExecutor, load, device, capacity: int = 16, convert=None):
         self.pool, self.load, self.device, self.capacity = pool, load, device, capacity
+        self.convert = convert           # uploaded bytes -> the frame that is kept (planar YUV -> packed RGB, on the device)
         self.items: "collections.OrderedDict[object, Future]" = collections.OrderedDict()
         self.dev: "collections.OrderedDict[object, torch.Tensor]" = collections.OrderedDict()
         self._ring, self._events, self._n = [], [], 0
@@ -107,7 +115,8 @@ class FrameCache:
         t = self.dev.get(key)
         if t is None:
             self.request([key])
-            t = self.dev[key] = self._upload(self.items.pop(key).result())
+            t = self._upload(self.items.pop(key).result())
+            t = self.dev[key] = t if self.convert is None else self.convert(t)
             while len(self.dev) > self.capacity:
                 self.dev.popitem(last=False)
         else:
@@ -164,20 +173,34 @@ def reflect_index(n: int, n_pad: Optional[int] = None) -> np.ndarray:
 
 class _Frames:
     """The clip behind one interface: frame i as a host uint8 [H,W,3] array (`host`) or a device tensor (`device`), cropped at the
-    bottom and right to H x W (`crop`: the source size rounded down to multiples of 20; otherwise the source size)."""
+    bottom and right to H x W (`crop`: the source size rounded down to multiples of 20; otherwise the source size).  A y4m clip
+    (`yuv`: its (layout, matrix, range); `items` the `Y4MReader`) is the exception: `host` returns the frame's planar bytes as they
+    are in the file, and `rgb` turns uploaded planar frames into the cropped RGB frames on the device."""
 
-    def __init__(self, items, T: int, H: int, W: int, paths: bool, crop: bool = False):
-        self.items, self.T, self.paths, self.src = items, T, paths, (H, W)
+    def __init__(self, items, T: int, H: int, W: int, paths: bool, crop: bool = False, yuv=None):
+        self.items, self.T, self.paths, self.src, self.yuv = items, T, paths, (H, W), yuv
         self.H, self.W = (H - H % 20, W - W % 20) if crop else (H, W)
 
     def on_device(self, i: int) -> bool:
+        if self.yuv is not None:
+            return False
         f = self.items[i]
         return torch.is_tensor(f) and f.is_cuda
+
+    def rgb(self, planar: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Planar frames [N, frame_bytes] of a y4m clip on the device -> uint8 [N,H,W,3] there (`ops.yuv_to_rgb_u8`; cropped after
+        the conversion), into the contiguous `out` if given."""
+        if (self.H, self.W) == self.src:
+            return ops.yuv_to_rgb_u8(planar, self.H, self.W, *self.yuv, out=out)
+        full = ops.yuv_to_rgb_u8(planar, *self.src, *self.yuv)[:, :self.H, :self.W]
+        return full.contiguous() if out is None else out.copy_(full)
 
     def device(self, i: int) -> torch.Tensor:
         return self.items[i][:self.H, :self.W]
 
     def host(self, i: int) -> np.ndarray:
+        if self.yuv is not None:
+            return self.items.raw(i)
         f = self.items[i]
         if self.paths:
             img = _imread(f)
@@ -197,9 +220,20 @@ def _check_frame(i, shape, dtype) -> None:
         raise ValueError(f"frames must be at least {MIN_SIZE}x{MIN_SIZE}; frame {i} is {shape[1]}x{shape[0]}")
 
 
-def frames_of(frames, crop: bool = False) -> _Frames:
-    """Validate a clip: a uint8 [T,H,W,3] array or tensor (host or device), a list of uint8 [H,W,3] arrays / tensors, or a list of
-    image paths (only their headers are read here).  Raises ValueError with the reason."""
+def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None) -> _Frames:
+    """Validate a clip: a uint8 [T,H,W,3] array or tensor (host or device), a list of uint8 [H,W,3] arrays / tensors, a list of
+    image paths (only their headers are read here), or a `y4m.Y4MReader` (`yuv`: optional `matrix` / `range` in place of the
+    reader's).  Raises ValueError with the reason."""
+    if isinstance(frames, y4m.Y4MReader):
+        if set(yuv or {}) - {"matrix", "range"}:
+            raise ValueError(f"yuv holds {sorted(set(yuv) - {'matrix', 'range'})}: it takes matrix and range")
+        if len(frames) < 2:
+            raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {len(frames)}")
+        _check_frame(0, (frames.height, frames.width, 3), np.uint8)
+        how = (frames.layout, y4m.matrix_of((yuv or {}).get("matrix", frames.matrix)), y4m.range_of((yuv or {}).get("range", frames.range)))
+        return _Frames(frames, len(frames), frames.height, frames.width, paths=False, crop=crop, yuv=how)
+    if yuv is not None:
+        raise ValueError("yuv= applies to y4m clips only")
     if isinstance(frames, (str, bytes)) or not hasattr(frames, "__len__") or not hasattr(frames, "__getitem__"):
         raise ValueError(f"frames must be an indexable sequence of frames, got {type(frames).__name__}")
     T = len(frames)
@@ -417,7 +451,8 @@ class ClipRun:
         plan = self.plan
         n = m.n_sequence
         pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
-        cache = FrameCache(pool, fr.host, dev)             # uint8 frames, decoded and uploaded once each
+        # uint8 frames, decoded and uploaded once each; a y4m clip's as planar bytes, made RGB on the device
+        cache = FrameCache(pool, fr.host, dev, convert=None if fr.yuv is None else (lambda planar: fr.rgb(planar)[0]))
         enc = EncoderCache()
         inflight, ready = collections.deque(), collections.deque()
         # the stream current at the first `next` assembles the inputs; the windows run on the lanes; a frame handed out is ordered
@@ -527,12 +562,14 @@ class ClipRun:
 
 
 def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
-                detector=None, cuts=None, cut_params: Optional[dict] = None) -> ClipRun:
+                detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None) -> ClipRun:
     """Deblur a clip: an iterator of (index, uint8 [H,W,3] frame on the model's device), in frame order, one per input frame.
 
     model  — an eval() `SPEINet` on a ROCm device; its `precision`, `corr_precision`, `use_graph` and `streams` are used as set.
     frames — T >= 2 frames of one size, at least 20x20: a uint8 [T,H,W,3] numpy array or torch tensor (host or device), a list of
-             uint8 [H,W,3] arrays / tensors, or a list of image paths (decoded to RGB on worker threads, a few windows ahead).
+             uint8 [H,W,3] arrays / tensors, a list of image paths (decoded to RGB on worker threads, a few windows ahead), or a
+             y4m clip: a `y4m.Y4MReader`, or the path of a `.y4m` file (opened here).  A y4m frame is uploaded
+             as its planar bytes (1.5 bytes per pixel for 4:2:0) and becomes packed RGB on the device (`ops.yuv_to_rgb_u8`).
     labels — optional 0/1 per frame (1 = sharp); None: the LD detector labels the clip in a first streaming pass.
     out    — optional contiguous uint8 [T,H,W,3] tensor on the model's device: frame i is written to out[i] and that view is yielded.
     crop   — crop every frame at the bottom and right to multiples of 20 as it is loaded, as the reference's harness does, instead of
@@ -545,12 +582,16 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              the labelling pass when `labels` is None: the clip is uploaded once).  Every scene is planned as a clip of its own
              (`window_plan`), so no window and no reference frame crosses a cut.  `ClipRun.cuts` holds the list in use.
     cut_params — optional keyword arguments of `find_cuts` for "auto" (hist_min, ratio, min_delta, window: untuned defaults).
+    yuv    — for a y4m clip, optional `dict(matrix="bt601" | "bt709", range="full" | "limited")` (either or both) in place of what
+             the reader derived: y4m carries no matrix tag and often no range tag.
 
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
     to `ClipRun.recomputed` with a RuntimeWarning, and FloatingPointError is raised if the frame is still not finite."""
-    fr = frames_of(frames, crop)
+    if isinstance(frames, (str, os.PathLike)) and os.fspath(frames).lower().endswith(".y4m"):
+        frames = y4m.Y4MReader(frames)
+    fr = frames_of(frames, crop, yuv)
     lab = None if labels is None else labels_of(labels, fr.T)
     if numbers is not None and len(numbers) != fr.T:
         raise ValueError(f"numbers has {len(numbers)} entries for a clip of {fr.T} frames")
@@ -602,10 +643,38 @@ def load_model(model_path: str, device, precision: str = "f16", graph: bool = Tr
     return net
 
 
+def _fps(text: str):
+    num, _, den = text.replace("/", ":").partition(":")
+    return int(num), int(den or 1)
+
+
+def _spool(stream, spool_dir: Optional[str]):
+    """Copy a pipe to an unnamed temporary file (in `spool_dir`, default: the system's) and return that file."""
+    import shutil
+    import tempfile
+    f = tempfile.TemporaryFile(dir=spool_dir)
+    shutil.copyfileobj(stream, f, 1 << 22)
+    f.flush()
+    return f
+
+
 def main(argv=None) -> None:
-    p = argparse.ArgumentParser(description="Deblur a clip of image files of any size (at least 20x20) on an MI355X: one PNG per input frame")
-    p.add_argument("--input", required=True, help="a directory of frames, or a glob (PNG / JPG / BMP); frames in file-name order")
-    p.add_argument("--output", required=True, help="directory for the deblurred PNGs (input file name, .png)")
+    """The command line.  `--input` is a directory or glob of image files, a `.y4m` file, or `-` for a y4m stream on stdin; `--output`
+    a directory (one PNG per frame), a `.y4m` file, or `-` for a y4m stream on stdout (every log line then goes to stderr), so the
+    tool sits between two ffmpeg processes:
+
+        ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe - | python -m speinet_amd.video --input - --output - --model_path ... \
+            | ffmpeg -f yuv4mpegpipe -i - out.mp4
+
+    A pipe on stdin is SPOOLED TO DISK first, to an unnamed temporary file (`--spool_dir`), all of it before the first frame is
+    deblurred: the window plan needs the clip's length and its labels before the first window.  The y4m output is written by one
+    thread, in frame order."""
+    p = argparse.ArgumentParser(description="Deblur a clip of any size (at least 20x20) on an MI355X: image files or a YUV4MPEG2 stream in, "
+                                "one PNG per frame or a YUV4MPEG2 stream out")
+    p.add_argument("--input", required=True, help="a directory of frames, or a glob (PNG / JPG / BMP); frames in file-name order; or a "
+                   ".y4m file; or '-': a y4m stream on stdin (spooled to a temporary file first)")
+    p.add_argument("--output", required=True, help="directory for the deblurred PNGs (input file name, .png; 000000.png ... for y4m "
+                   "input); or a .y4m file; or '-': a y4m stream on stdout")
     p.add_argument("--labels", default=None, help="0/1 per frame (1 = sharp) as a .npy file; default: the LD detector labels the clip")
     p.add_argument("--detector", default=None, help="a detector JSON file of `python -m speinet_amd.detector fit` (default: the reference's "
                    "GoPro model)")
@@ -616,36 +685,80 @@ def main(argv=None) -> None:
                    help="arithmetic of the GEMM-shaped kernels (default f16 with the top2 correlation: the throughput configuration)")
     p.add_argument("--device", default="cuda")
     p.add_argument("--no_graph", dest="graph", action="store_false", default=True, help="launch kernels eagerly (no hipGraph replay)")
+    p.add_argument("--matrix", choices=sorted(y4m.MATRIX_NAMES), default=None, help="YUV matrix of y4m input and output (default: bt709 "
+                   "for 720 rows and more, bt601 below: y4m has no matrix tag)")
+    p.add_argument("--range", choices=sorted(y4m.RANGE_NAMES), default=None, help="YUV range of y4m input and output (default: the "
+                   "input's XCOLORRANGE tag, limited without one; full for image input)")
+    p.add_argument("--fps", type=_fps, default=None, help="frame rate of y4m output as num:den (default: the y4m input's; 25:1 for image input)")
+    p.add_argument("--chroma", choices=sorted(y4m.TAG_OF_LAYOUT.values()), default=None, help="chroma layout of y4m output from image "
+                   "input (default 420jpeg; y4m input keeps its own)")
+    p.add_argument("--spool_dir", default=None, help="directory of the temporary file that '--input -' is copied to (default: the system's)")
     a = p.parse_args(argv)
-    files = _inputs(a.input)
-    if len(files) < 2:
-        raise SystemExit(f"--input {a.input}: {len(files)} image file(s) found, a clip needs at least 2")
-    names = [os.path.splitext(os.path.basename(f))[0] + ".png" for f in files]
-    if len(set(names)) != len(names):
-        raise SystemExit(f"--input {a.input}: two frames share a file name stem (the outputs are <stem>.png)")
+    to_stdout = a.output == "-"
+    to_y4m = to_stdout or a.output.lower().endswith(".y4m")
+    log = sys.stderr if to_stdout else sys.stdout
+
+    def say(text: str) -> None:
+        print(text, file=log, flush=True)
+
+    reader = None
+    if a.input == "-":
+        reader = y4m.Y4MReader(_spool(sys.stdin.buffer, a.spool_dir))
+    elif a.input.lower().endswith(".y4m") and os.path.isfile(a.input):
+        reader = y4m.Y4MReader(a.input)
+    if reader is not None:
+        if len(reader) < 2:
+            raise SystemExit(f"--input {a.input}: {len(reader)} frame(s) found, a clip needs at least 2")
+        files, stems = reader, [f"{i:06d}" for i in range(len(reader))]
+    else:
+        files = _inputs(a.input)
+        if len(files) < 2:
+            raise SystemExit(f"--input {a.input}: {len(files)} image file(s) found, a clip needs at least 2")
+        stems = [os.path.splitext(os.path.basename(f))[0] for f in files]
+        if len(set(stems)) != len(stems):
+            raise SystemExit(f"--input {a.input}: two frames share a file name stem (the outputs are <stem>.png)")
+    names = [s if to_y4m else s + ".png" for s in stems]
     labels = np.load(a.labels) if a.labels else None
     net = load_model(a.model_path, a.device, a.precision, a.graph)
     cuts = {"none": None, "auto": "auto"}[a.cuts] if a.cuts in ("none", "auto") else read_cuts(a.cuts)
-    run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts)
-    os.makedirs(a.output, exist_ok=True)
-    for c in run.cuts:
-        print(f"# cut before {names[c]}", flush=True)
+    yuv = {k: v for k, v in (("matrix", a.matrix), ("range", a.range)) if v is not None} if reader is not None else None
+    run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
+                      yuv=yuv or None)
     H, W = run.frames.H, run.frames.W
+    writer = None
+    if to_y4m:
+        if reader is not None:
+            layout, matrix, rng = run.frames.yuv
+            fps, aspect = a.fps or reader.fps, reader.aspect
+        else:
+            layout, rng = y4m.layout_of(a.chroma or "420jpeg"), y4m.range_of(a.range or "full")
+            matrix = y4m.matrix_of(a.matrix) if a.matrix else (y4m.BT709 if H >= 720 else y4m.BT601)
+            fps, aspect = a.fps or (25, 1), None
+        writer = y4m.Y4MWriter(sys.stdout.buffer if to_stdout else a.output, W, H, fps, layout, rng, aspect)
+    else:
+        os.makedirs(a.output, exist_ok=True)
+    for c in run.cuts:
+        say(f"# cut before {names[c]}")
     t0 = t_prev = time.time()
-    with ThreadPoolExecutor(max_workers=4, thread_name_prefix="speinet-png") as writers:
+    # PNGs are encoded on four threads; a y4m stream is written by ONE, so its frames land in the order they were queued
+    with ThreadPoolExecutor(max_workers=1 if to_y4m else 4, thread_name_prefix="speinet-y4m" if to_y4m else "speinet-png") as writers:
         ring = HostRing(writers)
         for i, frame in run:
-            ring.land(lambda buf, path=os.path.join(a.output, names[i]): _imwrite(path, buf.numpy()), frame)
+            if to_y4m:
+                ring.land(lambda buf: writer.write(buf.numpy()), ops.rgb_u8_to_yuv(frame, layout, matrix, rng))
+            else:
+                ring.land(lambda buf, path=os.path.join(a.output, names[i]): _imwrite(path, buf.numpy()), frame)
             now = time.time()
             branch = "no-reference" if run.plan[i]["zero_pre"] else "reference"
-            print(f"> {names[i]} {branch} {now - t_prev:.3f}s", flush=True)
+            say(f"> {names[i]} {branch} {now - t_prev:.3f}s")
             if run.recomputed and run.recomputed[-1] == i:
-                print(f"# {names[i]}: non-finite value in the {a.precision} frame, recomputed in bf16x3 ({len(run.recomputed)} so far)",
-                      flush=True)
+                say(f"# {names[i]}: non-finite value in the {a.precision} frame, recomputed in bf16x3 ({len(run.recomputed)} so far)")
             t_prev = now
         ring.drain()
+    if writer is not None:
+        writer.close()
     dt = time.time() - t0
-    print(f"# {len(files)} frames {W}x{H} in {dt:.2f}s: {len(files) / dt:.2f} frames/s ({a.precision})", flush=True)
+    say(f"# {len(names)} frames {W}x{H} in {dt:.2f}s: {len(names) / dt:.2f} frames/s ({a.precision})")
 
 
 if __name__ == "__main__":

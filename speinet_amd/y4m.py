@@ -1,0 +1,239 @@
+"""YUV4MPEG2 ("y4m") streams: decoded video as `ffmpeg -f yuv4mpegpipe` writes and reads it, a text header line and then one
+`FRAME` line plus raw planar bytes per frame.  Host side only (numpy, no torch): the planar bytes go to the device as they are and
+become packed RGB there (csrc/yuv_io.hip, `ops.yuv_to_rgb_u8`), and come back the same way (`ops.rgb_u8_to_yuv`).
+
+Supported: progressive 8-bit 4:2:0 (`C420jpeg`, bare `C420`, `C420mpeg2`) and 4:4:4 (`C444`).  Not supported: interlaced streams,
+more than 8 bits, 4:2:2, 4:1:1, mono, `C420paldv`."""
+from __future__ import annotations
+
+import os
+import re
+import threading
+
+import numpy as np
+
+CENTER, LEFT, P444 = 0, 1, 2           # SPEI_YUV_420_CENTER, SPEI_YUV_420_LEFT, SPEI_YUV_444 (include/speinet_hip.h)
+BT601, BT709 = 0, 1                    # SPEI_YUV_BT601, SPEI_YUV_BT709
+FULL, LIMITED = 0, 1                   # SPEI_YUV_FULL, SPEI_YUV_LIMITED
+
+MAGIC = b"YUV4MPEG2"
+LAYOUT_OF_TAG = {"420jpeg": CENTER, "420": CENTER, "420mpeg2": LEFT, "444": P444}
+TAG_OF_LAYOUT = {CENTER: "420jpeg", LEFT: "420mpeg2", P444: "444"}
+MATRIX_NAMES = {"bt601": BT601, "bt709": BT709}
+RANGE_NAMES = {"full": FULL, "limited": LIMITED}
+HINT = "convert it with `ffmpeg -i <in> -pix_fmt yuv420p -f yuv4mpegpipe <out.y4m>`"
+MAX_HEADER = 4096
+
+
+def _named(value, names: dict, what: str) -> int:
+    if isinstance(value, str) and value.lower() in names:
+        return names[value.lower()]
+    if not isinstance(value, (str, bool)) and value in names.values():
+        return int(value)
+    raise ValueError(f"{what} must be one of {sorted(names)}, got {value!r}")
+
+
+def matrix_of(value) -> int:
+    """BT601 / BT709 from the constant or from "bt601" / "bt709"."""
+    return _named(value, MATRIX_NAMES, "matrix")
+
+
+def range_of(value) -> int:
+    """FULL / LIMITED from the constant or from "full" / "limited"."""
+    return _named(value, RANGE_NAMES, "range")
+
+
+def layout_of(value) -> int:
+    """CENTER / LEFT / P444 from the constant or from a y4m chroma tag ("420jpeg", "420", "420mpeg2", "444")."""
+    return _named(value, LAYOUT_OF_TAG, "chroma layout")
+
+
+def frame_bytes(h: int, w: int, layout: int) -> int:
+    """Bytes of one planar frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0 and [h][w] each for 4:4:4."""
+    if layout not in TAG_OF_LAYOUT:
+        raise ValueError(f"unknown chroma layout {layout!r}")
+    return h * w + 2 * (h * w if layout == P444 else ((h + 1) // 2) * ((w + 1) // 2))
+
+
+def _ratio(tag: str, text: str):
+    try:
+        a, b = text.split(":")
+        return int(a), int(b)
+    except ValueError:
+        raise ValueError(f"y4m header: tag {tag}{text} is not <int>:<int>") from None
+
+
+class Y4MReader:
+    """A y4m file as an indexable sequence of frames: `len(r)`, and `r.raw(i)` = the `frame_bytes` planar bytes of frame i as a uint8
+    numpy array, read at its offset with `readinto` (callable from several threads).  `path_or_file`: a path, or a seekable binary
+    file object (a pipe has no length: the command line spools it to a file first).
+
+    Only the header line and the first `FRAME` line are scanned.  `FRAME` lines may carry parameters, but every one must be as long
+    as the first: T is then the payload size divided by the record size, and a later line that differs raises ValueError when its
+    frame is read.  A file that ends inside a frame raises ValueError here.
+
+    Attributes: `width`, `height`, `fps` and `aspect` ((num, den); 25:1 and None when absent), `layout` (CENTER / LEFT / P444),
+    `chroma` (the C tag's text), `range` (from XCOLORRANGE=FULL|LIMITED; LIMITED when absent), `matrix`, `frame_bytes`.  y4m carries
+    no matrix tag: `matrix` is BT709 when height >= 720 and BT601 otherwise, which is ffmpeg's usual guess for untagged video;
+    assign `matrix` / `range`, or pass `yuv=dict(matrix=..., range=...)` to `deblur_clip`, to override.
+
+    Interlaced streams, more than 8 bits per sample, C420paldv, C422, C411 and Cmono are rejected with a ValueError that names the
+    tag."""
+
+    def __init__(self, path_or_file):
+        self._own = isinstance(path_or_file, (str, bytes, os.PathLike))
+        self._f = open(path_or_file, "rb") if self._own else path_or_file
+        self.name = os.fspath(path_or_file) if self._own else getattr(path_or_file, "name", "<file>")
+        self._lock = threading.Lock()
+        try:
+            self._parse()
+        except Exception:
+            self.close()
+            raise
+
+    def _fail(self, text: str):
+        raise ValueError(f"{self.name}: {text}; {HINT}")
+
+    def _parse(self) -> None:
+        f = self._f
+        f.seek(0)
+        head = f.read(MAX_HEADER)
+        end = head.find(b"\n")
+        if not head.startswith(MAGIC) or end < 0:
+            raise ValueError(f"{self.name}: not a YUV4MPEG2 stream (no '{MAGIC.decode()} ...' header line)")
+        tags = head[len(MAGIC):end].decode("ascii", "replace").split()
+        self.width = self.height = None
+        self.fps, self.aspect, self.chroma, self.range = (25, 1), None, "420jpeg", LIMITED
+        for t in tags:
+            key, val = t[0], t[1:]
+            if key == "W":
+                self.width = int(val)
+            elif key == "H":
+                self.height = int(val)
+            elif key == "F":
+                self.fps = _ratio(key, val)
+            elif key == "A":
+                self.aspect = _ratio(key, val)
+            elif key == "I":
+                if val not in ("p", "?"):
+                    self._fail(f"tag I{val}: interlaced streams are not supported (progressive Ip only)")
+            elif key == "C":
+                self.chroma = val
+            elif key == "X" and val.upper().startswith("COLORRANGE="):
+                name = val.split("=", 1)[1].lower()
+                if name not in RANGE_NAMES:
+                    self._fail(f"tag X{val}: the colour range must be FULL or LIMITED")
+                self.range = RANGE_NAMES[name]
+        for key, val in (("W", self.width), ("H", self.height)):
+            if val is None:
+                self._fail(f"the header has no {key} tag")
+            if val < 1:
+                self._fail(f"tag {key}{val}: the size must be positive")
+        c = self.chroma
+        if c not in LAYOUT_OF_TAG:
+            deep = re.fullmatch(r"(?:(?:420|422|444)p|mono)(\d+)", c)
+            if deep:
+                why = f"{deep.group(1)} bits per sample (8 only)"
+            elif c.startswith(("422", "411", "mono")) or c == "420paldv":
+                why = "only 4:2:0 (C420jpeg, C420, C420mpeg2) and 4:4:4 (C444) are supported"
+            else:
+                why = "unknown chroma format"
+            self._fail(f"tag C{c}: {why}")
+        self.layout = LAYOUT_OF_TAG[c]
+        self.matrix = BT709 if self.height >= 720 else BT601
+        self.frame_bytes = frame_bytes(self.height, self.width, self.layout)
+        self._data = end + 1
+        size = f.seek(0, os.SEEK_END)
+        if size == self._data:
+            self._line, self._T = b"FRAME\n", 0
+            return
+        f.seek(self._data)
+        first = f.read(MAX_HEADER)
+        end = first.find(b"\n")
+        self._line = first[:end + 1]
+        if end < 0 or not self._is_frame_line(self._line):
+            raise ValueError(f"{self.name}: no FRAME line after the header")
+        record = len(self._line) + self.frame_bytes
+        self._T, rest = divmod(size - self._data, record)
+        if rest:
+            raise ValueError(f"{self.name}: truncated: {size - self._data} bytes after the header are {self._T} frames of "
+                             f"{record} bytes ({len(self._line)} of FRAME line, {self.frame_bytes} of {self.width}x{self.height} "
+                             f"C{c}) and {rest} bytes more (a cut last frame, or FRAME lines of different lengths)")
+
+    @staticmethod
+    def _is_frame_line(line: bytes) -> bool:
+        return line[:5] == b"FRAME" and line[5:6] in (b" ", b"\n") and line.find(b"\n") == len(line) - 1
+
+    def __len__(self) -> int:
+        return self._T
+
+    def raw(self, i: int) -> np.ndarray:
+        """The planar bytes of frame i: a fresh uint8 array of `frame_bytes`."""
+        if not 0 <= i < self._T:
+            raise IndexError(f"frame {i} of a y4m clip of {self._T} frames")
+        n = len(self._line)
+        line, buf = bytearray(n), np.empty(self.frame_bytes, dtype=np.uint8)
+        with self._lock:
+            self._f.seek(self._data + i * (n + self.frame_bytes))
+            got = self._f.readinto(line), self._f.readinto(memoryview(buf))
+        if got != (n, self.frame_bytes):
+            raise ValueError(f"{self.name}: frame {i} is cut short")
+        if not self._is_frame_line(bytes(line)):
+            raise ValueError(f"{self.name}: frame {i} does not start with a FRAME line of {n} bytes like the first frame's "
+                             f"({bytes(self._line)!r}): FRAME lines of different lengths are not supported")
+        return buf
+
+    def __getitem__(self, i: int) -> np.ndarray:
+        return self.raw(i + self._T if isinstance(i, int) and i < 0 else i)
+
+    def close(self) -> None:
+        if self._own:
+            self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Y4MWriter:
+    """Write a progressive 8-bit y4m stream: the header once, then `write(planar bytes)` per frame (`frame_bytes` bytes: a bytes-like
+    object or a contiguous uint8 numpy array).  `path_or_file`: a path, or a binary file object (a pipe will do), which `close`
+    flushes and leaves open."""
+
+    def __init__(self, path_or_file, w: int, h: int, fps=(25, 1), layout: int = CENTER, range: int = LIMITED, aspect=None):
+        self.width, self.height, self.fps, self.aspect = int(w), int(h), (int(fps[0]), int(fps[1])), aspect
+        self.layout, self.range = layout_of(layout), range_of(range)
+        self.frame_bytes = frame_bytes(self.height, self.width, self.layout)
+        if self.width < 1 or self.height < 1 or self.fps[0] < 1 or self.fps[1] < 1:
+            raise ValueError(f"y4m: bad size {w}x{h} or frame rate {fps}")
+        self._own = isinstance(path_or_file, (str, bytes, os.PathLike))
+        self._f = open(path_or_file, "wb") if self._own else path_or_file
+        tags = [f"W{self.width}", f"H{self.height}", f"F{self.fps[0]}:{self.fps[1]}", "Ip"]
+        if aspect is not None:
+            tags.append(f"A{int(aspect[0])}:{int(aspect[1])}")
+        tags += [f"C{TAG_OF_LAYOUT[self.layout]}", "XCOLORRANGE=" + ("FULL" if self.range == FULL else "LIMITED")]
+        self._f.write(MAGIC + b" " + " ".join(tags).encode("ascii") + b"\n")
+        self.frames = 0
+
+    def write(self, planar) -> None:
+        data = memoryview(planar).cast("B")
+        if data.nbytes != self.frame_bytes:
+            raise ValueError(f"y4m: a {self.width}x{self.height} C{TAG_OF_LAYOUT[self.layout]} frame is {self.frame_bytes} bytes, "
+                             f"got {data.nbytes}")
+        self._f.write(b"FRAME\n")
+        self._f.write(data)
+        self.frames += 1
+
+    def close(self) -> None:
+        if self._own:
+            self._f.close()
+        else:
+            self._f.flush()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
