@@ -6,6 +6,9 @@ concatenations are never materialised (two-source GEMM operands, strided output 
 """
 from __future__ import annotations
 
+import contextlib
+from functools import partial
+
 import torch
 
 from .ops import ACT_GELU, ACT_RELU, CONV_T, BMap, Ctx, FMap
@@ -256,8 +259,51 @@ def decode(ctx: Ctx, ff: FMap, s: torch.Tensor, t3: FMap, t2: FMap, t1: FMap, P:
 # before the `fusion` conv).  Every kernel of the path leaves CUs idle in its last partial round of workgroups and in its
 # load / store phases; a second stream's kernels fill those.  Captured into the frame's hipGraph as parallel branches.
 # `sides`: the side streams (owned by the calling model, per device); the current stream of ctx.device is the main lane.
+def model_streams(model, key: tuple, device, n: int) -> list:
+    """`model._side_streams[key]`: n HIP streams on `device`, created on first use and kept as long as the model (captured graphs are
+    keyed by launch stream and replay on the streams they were captured with)."""
+    if key not in model._side_streams:
+        model._side_streams[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
+    return model._side_streams[key]
+
+
+def side_streams(model, device) -> list:
+    """The side lanes of `model.streams` lanes on `device` (the main lane is the caller's current stream)."""
+    n = max(1, int(model.streams)) - 1
+    return model_streams(model, (torch.device(device).index, n), device, n)
+
+
 def _lanes(ctx: Ctx, sides) -> list:
     return [torch.cuda.current_stream(ctx.device)] + list(sides or ())
+
+
+@contextlib.contextmanager
+def _side_lanes(lanes: list, fork: bool = True):
+    """Fork and join around the block that issues work on the lanes: the side lanes wait for the main lane (lanes[0]) before it — unless
+    the block orders them behind main with an event of its own (`fork=False`) — and the main lane waits for the side lanes after it."""
+    main = lanes[0]
+    for s_ in lanes[1:] if fork else ():
+        s_.wait_stream(main)
+    yield
+    for s_ in lanes[1:]:
+        main.wait_stream(s_)
+
+
+def _swin_calls(ctx: Ctx, f_mid: FMap, ys: list, P: dict, cat: FMap, lanes: list) -> None:
+    """Every swin call of a frame, one per lane, round-robin: call k fuses ys[k] — the y map, or a zero-argument producer of it, which
+    runs on the call's lane and needs nothing from the middle frame — into channel block k + 1 of `cat`.  Only the call itself needs
+    f_mid and conv_first(f_mid): a side lane waits for them (`ready`) right before it."""
+    main = lanes[0]
+    sx = SwinX(ctx, f_mid, P["swin"])
+    ready = torch.cuda.Event()
+    ready.record(main)
+    for slot, y in enumerate(ys, start=1):
+        lane = lanes[(slot - 1) % len(lanes)]
+        with torch.cuda.stream(lane):
+            feat = y() if callable(y) else y
+            if lane is not main:
+                lane.wait_event(ready)
+            swin(ctx, sx, feat, P["swin"], out=cat.view(128 * slot, 128))
 
 
 def forward_sample(ctx: Ctx, x: torch.Tensor, P: dict, n_seq: int, has_ref: bool, out: torch.Tensor, sides=()) -> torch.Tensor:
@@ -281,48 +327,37 @@ def forward_sample_steps(ctx: Ctx, x: torch.Tensor, P: dict, n_seq: int, has_ref
     h3, w3 = h // 4, w // 4
     dev = x.device
     lanes = _lanes(ctx, sides)
-    main = lanes[0]
     if ctx.for_stage("enc").batched_available():
         yield from forward_batch_steps(ctx, x[None], P, n_seq, [not has_ref], out[None], sides)
         return
-    for s_ in lanes[1:]:
-        s_.wait_stream(main)                      # fork: the input frames (and anything before them) are ready
-    lv = None
-    if has_ref:                                   # sharp-reference pyramid: last lane, ahead of its neighbour frames
-        with torch.cuda.stream(lanes[-1]):
-            lv = reference_pyramid(ctx, x[n_seq + 1], P)
-    cat = FMap(torch.empty(h3 * w3, 128 * n_seq, device=dev), h3, w3, 128 * n_seq)
-    mid = x[n_seq // 2]
-    e0 = enc(ctx, mid, P)
-    f_mid = enc(ctx, ctx.rl_prior(mid, 5, 0.01), P, extra=e0, out=cat.view(0, 128))
-    others = [i for i in range(n_seq) if i != n_seq // 2]
-    if ctx.for_stage("swin").swin_multi_available():
-        # the neighbour frames' encoder passes on the lanes, then ALL their swin calls as one batch (swin_multi)
-        fb = BMap.empty(len(others), h3, w3, 128, dev)
-        for k, i in enumerate(others):
-            with torch.cuda.stream(lanes[k % len(lanes)]):
-                e = enc(ctx, x[i], P)
-                enc(ctx, ctx.rl_prior(x[i], 1, 0.01), P, extra=e, out=fb.map(k))
-                del e
-        for s_ in lanes[1:]:
-            main.wait_stream(s_)                  # join
+    multi = ctx.for_stage("swin").swin_multi_available()
+    with _side_lanes(lanes):                      # fork: the input frames (and anything before them) are ready
+        lv = None
+        if has_ref:                               # sharp-reference pyramid: last lane, ahead of its neighbour frames
+            with torch.cuda.stream(lanes[-1]):
+                lv = reference_pyramid(ctx, x[n_seq + 1], P)
+        cat = FMap(torch.empty(h3 * w3, 128 * n_seq, device=dev), h3, w3, 128 * n_seq)
+        mid = x[n_seq // 2]
+        e0 = enc(ctx, mid, P)
+        f_mid = enc(ctx, ctx.rl_prior(mid, 5, 0.01), P, extra=e0, out=cat.view(0, 128))
+        others = [i for i in range(n_seq) if i != n_seq // 2]
+
+        def neighbour(i, out=None):               # enc(RL_1(x_i)) + enc(x_i): needs nothing from the middle frame
+            e = enc(ctx, x[i], P)
+            return enc(ctx, ctx.rl_prior(x[i], 1, 0.01), P, extra=e, out=out)
+
+        if multi:
+            # the neighbour frames' encoder passes on the lanes, then ALL their swin calls as one batch (swin_multi)
+            fb = BMap.empty(len(others), h3, w3, 128, dev)
+            for k, i in enumerate(others):
+                with torch.cuda.stream(lanes[k % len(lanes)]):
+                    neighbour(i, fb.map(k))
+        else:
+            _swin_calls(ctx, f_mid, [partial(neighbour, i) for i in others], P, cat, lanes)
+    if multi:
         yield from _fuse_tail(ctx, f_mid, fb, cat, lv, P, out, lanes)
-        return
-    sx = SwinX(ctx, f_mid, P["swin"])
-    ready = torch.cuda.Event()
-    ready.record(main)
-    for slot, i in enumerate(others, start=1):
-        lane = lanes[(slot - 1) % len(lanes)]
-        with torch.cuda.stream(lane):
-            e = enc(ctx, x[i], P)                      # the neighbour frame's own passes need nothing from the middle frame:
-            feat = enc(ctx, ctx.rl_prior(x[i], 1, 0.01), P, extra=e)
-            if lane is not main:
-                lane.wait_event(ready)                 # ... only its swin call does (f_mid, conv_first(f_mid))
-            swin(ctx, sx, feat, P["swin"], out=cat.view(128 * slot, 128))
-            del e, feat
-    for s_ in lanes[1:]:
-        main.wait_stream(s_)                      # join
-    yield from _tail(ctx, cat, lv, P, out)
+    else:
+        yield from _tail(ctx, cat, lv, P, out)
 
 
 def forward_batch_steps(ctx: Ctx, x: torch.Tensor, P: dict, n_seq: int, zero_ref: list, out: torch.Tensor, sides=(), max_maps: int = 16):
@@ -335,7 +370,6 @@ def forward_batch_steps(ctx: Ctx, x: torch.Tensor, P: dict, n_seq: int, zero_ref
     h3, w3 = h // 4, w // 4
     dev = x.device
     lanes = _lanes(ctx, sides)
-    main = lanes[0]
     others = [i for i in range(n_seq) if i != n_seq // 2]
     b0 = 0
     while b0 < B:
@@ -375,21 +409,11 @@ def forward_batch_steps(ctx: Ctx, x: torch.Tensor, P: dict, n_seq: int, zero_ref
 def _fuse_tail(ctx: Ctx, f_mid: FMap, fb: BMap, cat: FMap, lv, P: dict, out: torch.Tensor, lanes: list):
     """The neighbour-frame fusions into `cat` (its first 128 channels already hold f_mid), then `_tail`.  One batched pass over the
     stacked y maps where the mode has the batched kernels (swin_multi), else one swin call per neighbour frame on the side lanes."""
-    main = lanes[0]
-    sx = SwinX(ctx, f_mid, P["swin"])
     if ctx.for_stage("swin").swin_multi_available():
-        swin_multi(ctx, sx, fb, P["swin"], [cat.view(128 * slot, 128) for slot in range(1, fb.B + 1)])
+        swin_multi(ctx, SwinX(ctx, f_mid, P["swin"]), fb, P["swin"], [cat.view(128 * slot, 128) for slot in range(1, fb.B + 1)])
     else:
-        ready = torch.cuda.Event()
-        ready.record(main)
-        for slot in range(1, fb.B + 1):
-            lane = lanes[(slot - 1) % len(lanes)]
-            if lane is not main:
-                lane.wait_event(ready)
-            with torch.cuda.stream(lane):
-                swin(ctx, sx, fb.map(slot - 1), P["swin"], out=cat.view(128 * slot, 128))
-        for s_ in lanes[1:]:
-            main.wait_stream(s_)                  # join
+        with _side_lanes(lanes, fork=False):      # the side lanes start at the swin calls: `ready` is their fork
+            _swin_calls(ctx, f_mid, [fb.map(k) for k in range(fb.B)], P, cat, lanes)
     yield from _tail(ctx, cat, lv, P, out)
 
 
@@ -436,7 +460,6 @@ def fuse_and_decode_steps(ctx: Ctx, f_mid: FMap, feats: list, lv, P: dict, n_seq
     h3, w3 = f_mid.H, f_mid.W
     dev = f_mid.t.device
     lanes = _lanes(ctx, sides)
-    main = lanes[0]
     cat = FMap(torch.empty(h3 * w3, 128 * n_seq, device=dev), h3, w3, 128 * n_seq)
     cat.t[:, :128].copy_(f_mid.t)
     fb = BMap(torch.cat([f.t for f in feats]), len(feats), h3, w3, 128)
@@ -450,28 +473,16 @@ def forward_swint(ctx: Ctx, x: torch.Tensor, P: dict, n_seq: int, out: torch.Ten
     h, w = x.shape[-2:]
     h3, w3 = h // 4, w // 4
     dev = x.device
-    lanes = _lanes(ctx, sides)
-    main = lanes[0]
-    for s_ in lanes[1:]:
-        s_.wait_stream(main)
-    cat = FMap(torch.empty(h3 * w3, 128 * n_seq, device=dev), h3, w3, 128 * n_seq)
-    f_mid = enc(ctx, x[n_seq // 2], P, out=cat.view(0, 128))
-    sx = SwinX(ctx, f_mid, P["swin"])
-    if n_seq == 1:
-        f_trans = FMap.empty(h3, w3, 128, dev)
-        swin(ctx, sx, f_mid, P["swin"], out=f_trans)
-        cat = FMap(ctx.add(f_mid.t, f_trans.t), h3, w3, 128)
-    else:
-        ready = torch.cuda.Event()
-        ready.record(main)
-        for slot, i in enumerate([i for i in range(n_seq) if i != n_seq // 2], start=1):
-            lane = lanes[(slot - 1) % len(lanes)]
-            if lane is not main:
-                lane.wait_event(ready)
-            with torch.cuda.stream(lane):
-                swin(ctx, sx, enc(ctx, x[i], P), P["swin"], out=cat.view(128 * slot, 128))
-        for s_ in lanes[1:]:
-            main.wait_stream(s_)
+    lanes = _lanes(ctx, sides if n_seq > 1 else ())       # a single frame has nothing for the side lanes
+    with _side_lanes(lanes):
+        cat = FMap(torch.empty(h3 * w3, 128 * n_seq, device=dev), h3, w3, 128 * n_seq)
+        f_mid = enc(ctx, x[n_seq // 2], P, out=cat.view(0, 128))
+        if n_seq == 1:
+            f_trans = FMap.empty(h3, w3, 128, dev)
+            swin(ctx, SwinX(ctx, f_mid, P["swin"]), f_mid, P["swin"], out=f_trans)
+            cat = FMap(ctx.add(f_mid.t, f_trans.t), h3, w3, 128)
+        else:
+            _swin_calls(ctx, f_mid, [partial(enc, ctx, x[i], P) for i in range(n_seq) if i != n_seq // 2], P, cat, lanes)
     fw = P["conv"]
     ff = ctx.igemm(cat, fw["w"], fw["b"], 128)
     dctx = ctx.for_stage("decode")

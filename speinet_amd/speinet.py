@@ -12,6 +12,7 @@ raises.  The CPU restatement lives in oracle/ and is test infrastructure only.
 """
 from __future__ import annotations
 
+import inspect
 import os
 from types import SimpleNamespace
 from typing import Optional, Sequence
@@ -266,11 +267,7 @@ class SPEINet(nn.Module):
         return ops.Ctx(self.precision, self.corr_precision, device=device, profile=profile, capture=capture, **self.knobs)
 
     def _sides(self, device) -> list:
-        n = max(1, int(self.streams)) - 1
-        key = (torch.device(device).index, n)
-        if key not in self._side_streams:
-            self._side_streams[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
-        return self._side_streams[key]
+        return engine.side_streams(self, device)
 
     def _mode_key(self, device):
         return (self.precision, self.corr_precision, int(self.streams), str(device), self._generation, repr(sorted(self.knobs.items())))
@@ -351,10 +348,7 @@ class SPEINet(nn.Module):
             return self._forward_window(x, keys, cache, zero_ref)
 
     def _prefetch_stream(self, device) -> "torch.cuda.Stream":
-        key = ("prefetch", torch.device(device).index)
-        if key not in self._side_streams:
-            self._side_streams[key] = torch.cuda.Stream(device=device)
-        return self._side_streams[key]
+        return engine.model_streams(self, ("prefetch", torch.device(device).index), device, 1)[0]
 
     def prefetch_window(self, x: torch.Tensor, keys: Sequence, cache: "EncoderCache", zero_ref: bool) -> None:
         """Start the encoder passes a later `forward_window(x, keys, cache, zero_ref)` will need, on the prefetch stream: called for
@@ -431,38 +425,16 @@ class SPEINet(nn.Module):
         gkey = ("window", h, w, bool(zero_ref), torch.cuda.current_stream(x.device).cuda_stream) + self._mode_key(x.device)
         g = self._graphs.get(gkey)
         if g is None:
-            from .ops import FMap
-            clone = lambda f: FMap(f.t.clone(), f.H, f.W, f.C)
+            clone = lambda f: ops.FMap(f.t.clone(), f.H, f.W, f.C)
             s_mid, s_feats = clone(f_mid), [clone(f) for f in feats]
             s_lv = tuple(clone(f) for f in lv) if lv is not None else None
             s_out = torch.empty_like(out)
-            side = torch.cuda.Stream(device=x.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):           # warm-up off the capture
-                engine.fuse_and_decode(ctx, s_mid, s_feats, s_lv, P, n, s_out[0], sides)
-            torch.cuda.current_stream().wait_stream(side)
-            steps = engine.fuse_and_decode_steps(ctx, s_mid, s_feats, s_lv, P, n, s_out[0], sides)
-            g1 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g1):
-                plan = next(steps)
-            plan.launch()
-            g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2, pool=g1.pool()):
-                for _ in steps:
-                    raise RuntimeError("fuse_and_decode_steps yielded twice")
-            self._trim_graphs()
-            self._graph_devices.add(str(x.device))
-            g = self._graphs[gkey] = ((g1, plan, g2), s_mid, s_feats, s_lv, s_out)
-        (g1, plan, g2), s_mid, s_feats, s_lv, s_out = g
-        s_mid.t.copy_(f_mid.t)
-        for d, f in zip(s_feats, feats):
+            g = self._capture(gkey, x.device, ([s_mid] + s_feats + list(s_lv or ()), s_out),
+                              lambda: engine.fuse_and_decode_steps(ctx, s_mid, s_feats, s_lv, P, n, s_out[0], sides))
+        s_in, s_out = g.statics
+        for d, f in zip(s_in, [f_mid] + feats + list(lv or ())):
             d.t.copy_(f.t)
-        if lv is not None:
-            for d, f in zip(s_lv, lv):
-                d.t.copy_(f.t)
-        g1.replay()
-        plan.launch()
-        g2.replay()
+        g.replay()
         return s_out.clone()
 
     def _window_pieces_batched(self, ctx, x, keys, cache, zero_ref, P, tag, G, pf, used):
@@ -529,84 +501,96 @@ class SPEINet(nn.Module):
         lv = None if zero_ref else have[(tag, keys[n + 1], "ref")]
         return f_mid, feats, lv
 
-    def _trim_graphs(self, limit: int = 24) -> None:
-        if len(self._graphs) >= limit:
+    GRAPH_LIMIT = 24                   # captured instances a model keeps (frame, window and piece graphs together)
+
+    def _trim_graphs(self) -> None:
+        if len(self._graphs) >= self.GRAPH_LIMIT:
             torch.cuda.synchronize()           # a replay of one of them may still be running (other stream, earlier window)
             self._graphs.clear()
+
+    def _capture(self, key: tuple, device, statics, run) -> "_Graphed":
+        """Capture `run()` — a piece of the forward pass on the caller's static buffers `statics` — as hipGraphs and keep it as
+        `self._graphs[key]`.  `run` is a plain function that returns its outputs, or a generator that yields prepared correlation launches
+        (ops.CorrPlan) and may return outputs.  n plans give n + 1 graph segments in one memory pool, [g_0] plan_0 [g_1] ... plan_{n-1} [g_n]:
+        the plans are launched directly between the replays, so a caller can bracket the path's dominant kernel with HIP events on the
+        launch stream (`profile`, bench.py) inside the very run it times."""
+        def steps():
+            r = run()
+            return (yield from r) if inspect.isgenerator(r) else r
+
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):           # warm-up off the capture: sets kernel attributes, fills the allocator
+            for plan in steps():
+                plan.launch()
+        torch.cuda.current_stream().wait_stream(side)
+        segs, pool, it, result = [], None, steps(), None
+        while True:
+            gseg = torch.cuda.CUDAGraph()
+            plan = None
+            with torch.cuda.graph(gseg, pool=pool):
+                try:
+                    plan = next(it)
+                except StopIteration as end:
+                    result = end.value
+            pool = gseg.pool()
+            segs.append((gseg, plan))
+            if plan is None:
+                break
+            plan.launch()                       # once, eagerly: the next segment is captured behind real data
+        self._trim_graphs()
+        self._graph_devices.add(str(device))
+        g = self._graphs[key] = _Graphed(segs, statics, result)
+        return g
 
     def _graphed(self, name: tuple, inputs: list, fn) -> list:
         """`fn(*inputs) -> [FMap, ...]` through a hipGraph captured once per (name, mode): inputs (tensors or FMaps) are copied
         into the graph's static buffers, the outputs are returned as fresh copies (they go into the caller's cache)."""
-        from .ops import FMap
-        dev = inputs[0].device if torch.is_tensor(inputs[0]) else inputs[0].t.device
-        key = ("piece",) + name + self._mode_key(dev)
+        FMap = ops.FMap
         buf = lambda v: v if torch.is_tensor(v) else v.t
+        dev = buf(inputs[0]).device
+        key = ("piece",) + name + self._mode_key(dev)
         g = self._graphs.get(key)
         if g is None:
-            clone = lambda v: v.clone() if torch.is_tensor(v) else FMap(v.t.clone(), v.H, v.W, v.C, v.off)
-            s_in = [clone(v) for v in inputs]
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):           # warm-up off the capture
-                fn(*s_in)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                s_out = fn(*s_in)
-            self._trim_graphs()
-            self._graph_devices.add(str(dev))
-            g = self._graphs[key] = (graph, s_in, s_out)
-        graph, s_in, s_out = g
-        for d, v in zip(s_in, inputs):
+            s_in = [v.clone() if torch.is_tensor(v) else FMap(v.t.clone(), v.H, v.W, v.C, v.off) for v in inputs]
+            g = self._capture(key, dev, s_in, lambda: fn(*s_in))
+        for d, v in zip(g.statics, inputs):
             buf(d).copy_(buf(v))
-        graph.replay()
-        return [FMap(f.t.clone(), f.H, f.W, f.C, f.off) for f in s_out]
+        return [FMap(f.t.clone(), f.H, f.W, f.C, f.off) for f in g.replay()]
 
     def _forward_graph(self, ctx: ops.Ctx, x: torch.Tensor, P: dict, zero_ref: list, profile: Optional[dict] = None) -> torch.Tensor:
         """Replay the ~1500 launches of a frame as hipGraphs (captured once per shape / routing / precision): the per-launch
-        host cost (ctypes + hipLaunch, ~10 us each) otherwise leaves the GPU idle ~15 % of a frame.  A frame is TWO graph
-        segments around the correlation arg-max kernel, which is launched directly between them: that costs two extra
-        launches per frame and lets a caller bracket the path's dominant kernel with HIP events on the launch stream
-        (`profile`, bench.py) inside the very run it times."""
+        host cost (ctypes + hipLaunch, ~10 us each) otherwise leaves the GPU idle ~15 % of a frame.  A batch of B frames is B + 1 graph
+        segments around the B correlation arg-max launches (`_capture`)."""
         # one captured instance per launch stream: a caller that keeps two frames in flight (bench.py --inflight 2: frame i + 1's
         # encoder passes under frame i's correlation / decoder) calls forward from two streams, and each needs its own static buffers
         key = (tuple(x.shape), tuple(zero_ref), torch.cuda.current_stream(x.device).cuda_stream) + self._mode_key(x.device)
         g = self._graphs.get(key)
         if g is None:
-            sides = self._sides(x.device)
-            cctx = ctx.replace(profile=None)
             static_x = x.clone()
             static_out = torch.empty(x.shape[0], 3, x.shape[-2], x.shape[-1], device=x.device, dtype=torch.float32)
-            side = torch.cuda.Stream(device=x.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):       # warm-up off the capture: sets kernel attributes, fills the allocator
-                for plan in self._steps(cctx, static_x, P, zero_ref, static_out, sides):
-                    plan.launch()
-            torch.cuda.current_stream().wait_stream(side)
-            # graph segments between the correlation launches: [g_0] plan_0 [g_1] plan_1 ... plan_{B-1} [g_B]; each plan is launched
-            # once, eagerly, so that the next segment is captured behind real data
-            segs, pool = [], None
-            steps = self._steps(cctx, static_x, P, zero_ref, static_out, sides)
-            while True:
-                gseg = torch.cuda.CUDAGraph()
-                plan = None
-                with torch.cuda.graph(gseg, pool=pool):
-                    plan = next(steps, None)
-                pool = gseg.pool()
-                segs.append((gseg, plan))
-                if plan is None:
-                    break
-                plan.launch()
-            self._trim_graphs()
-            self._graph_devices.add(str(x.device))
-            g = self._graphs[key] = (segs, static_x, static_out)
-        segs, static_x, static_out = g
+            sides, cctx = self._sides(x.device), ctx.replace(profile=None)
+            g = self._capture(key, x.device, (static_x, static_out), lambda: self._steps(cctx, static_x, P, zero_ref, static_out, sides))
+        static_x, static_out = g.statics
         static_x.copy_(x)
-        for gseg, plan in segs:
+        g.replay(profile)
+        return static_out.clone()
+
+
+class _Graphed:
+    """One captured instance (`SPEINet._capture`): the graph segments, each with the correlation launch that follows it (None after the
+    last), the caller's static buffers and what the captured piece returned."""
+    __slots__ = ("segs", "statics", "result")
+
+    def __init__(self, segs, statics, result):
+        self.segs, self.statics, self.result = segs, statics, result
+
+    def replay(self, profile: Optional[dict] = None):
+        for gseg, plan in self.segs:
             gseg.replay()
             if plan is not None:
                 plan.launch(profile)
-        return static_out.clone()
+        return self.result
 
 
 def _wants_autograd(model: nn.Module, x: torch.Tensor) -> bool:

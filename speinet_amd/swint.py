@@ -101,13 +101,10 @@ class SPEINet(nn.Module):
             ctx = ops.Ctx(self.precision, "top2", device=x.device, profile=profile, **self.knobs)
             x = x.contiguous().float()
             P = self._pack(x.device)
-            n = max(1, int(self.streams)) - 1
-            key = (x.device.index, n)
-            if key not in self._side_streams:
-                self._side_streams[key] = [torch.cuda.Stream(device=x.device) for _ in range(n)]
+            sides = engine.side_streams(self, x.device)
             out = torch.empty(x.shape[0], 3, h, w, device=x.device, dtype=torch.float32)
             for b in range(x.shape[0]):
-                engine.forward_swint(ctx, x[b], P, self.n_sequence, out[b], self._side_streams[key])
+                engine.forward_swint(ctx, x[b], P, self.n_sequence, out[b], sides)
             return out
 
 

@@ -43,7 +43,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import detector, ops, selection, y4m
+from . import detector, engine, ops, selection, y4m
 from .speinet import EncoderCache
 
 ZERO = ("zero",)                 # window key of a zeroed reference frame
@@ -375,10 +375,7 @@ def window_plan(labels, n_seq: int = 3, numbers=None, cuts=None) -> list:
 def _lanes(model, device, n: int) -> list:
     """The launch streams of the windows, one set per model and device: `forward_window` captures one graph per launch stream, so
     fresh streams per clip would capture fresh graphs per clip."""
-    key = ("video_lanes", device.index, n)
-    if key not in model._side_streams:
-        model._side_streams[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
-    return model._side_streams[key]
+    return engine.model_streams(model, ("video_lanes", device.index, n), device, n)
 
 
 class ClipRun:

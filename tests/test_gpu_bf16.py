@@ -348,6 +348,27 @@ def test_streams_bit_identical(net, mode, graph):
         assert torch.equal(o, outs[0])
 
 
+def test_graph_trim_recapture_bit_identical(net):
+    """More frame shapes than the model keeps graphs for (`GRAPH_LIMIT`, lowered to 2 on this instance): the graphs are dropped and
+    captured again as the shapes come round, and every call — capture, replay, replay after a trim — gives the bits of the eager call."""
+    shapes = [(20, 20), (20, 40), (40, 40)]
+    xs = [synth_frames(1, h, w, seed=90 + i).to(DEV) for i, (h, w) in enumerate(shapes)]
+    net.precision, net.corr_precision, net.streams, net.GRAPH_LIMIT = "f16", "top2", 2, 2
+    try:
+        with torch.no_grad():
+            refs = [net(x).clone() for x in xs]
+            net.use_graph = True
+            for i in (0, 0, 1, 1, 2, 2, 0):                 # the third shape's capture trims; then the first shape is captured again
+                out = net(xs[i])
+                assert len(net._graphs) <= 2
+                assert torch.equal(out, refs[i]), shapes[i]
+    finally:
+        net.streams, net.use_graph, net.precision, net.corr_precision = 1, False, "f32", "bf16x3"
+        del net.GRAPH_LIMIT
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(r).all() for r in refs)
+
+
 @pytest.mark.parametrize("h,w,b,zero_ref", [(480, 640, 2, (1,)), (720, 1280, 1, ())])
 def test_forward_large_sizes_modes_agree(net, h, w, b, zero_ref):
     """480x640 (the BSD frame size, BASELINE.json configs[3]; 768 windows, lv3 map 120x160 -> partial tiles in every tiled

@@ -108,16 +108,18 @@ def test_harness_recomputes_non_finite_frames(tmp_path):
 
 
 @pytest.mark.parametrize("graph", [False, True])
-def test_forward_window_reuse_bit_identical(graph):
+@pytest.mark.parametrize("mode", [("bf16", "bf16"), ("bf16x3", "bf16x3")], ids=["bf16", "bf16x3"])
+def test_forward_window_reuse_bit_identical(mode, graph):
     """Cross-window reuse of the per-frame encoder passes (SURVEY.md plan step 8): sliding windows over a clip through
     `forward_window` give exactly the bits of the stateless `forward`, with most encoder passes served from the cache;
-    both routing branches, a zeroed reference frame, eager and hipGraph tails."""
+    both routing branches, a zeroed reference frame, eager and hipGraph tails.  bf16 batches the missing passes of a window
+    (`_window_pieces_batched`); the f32-grade bf16x3 runs them one at a time (`raw`, `sum`, `pyr`: with `graph`, one-segment graphs)."""
     from speinet_amd.speinet import EncoderCache, SPEINet, default_args
     from speinet_amd.synth import state_dict_template, synth_state_dict
     net = SPEINet(args=default_args())
     net.load_state_dict(synth_state_dict(state_dict_template(), seed=0))
     net = net.cuda().eval()
-    net.precision, net.corr_precision, net.streams, net.use_graph = "bf16", "bf16", 2, graph
+    (net.precision, net.corr_precision), net.streams, net.use_graph = mode, 2, graph
     frames = synth_frames(2, 60, 80, seed=11).reshape(10, 3, 60, 80)[:8].cuda()       # an 8-frame "clip"
     zero = torch.zeros_like(frames[0])
     cache = EncoderCache()
