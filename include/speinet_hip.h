@@ -530,6 +530,28 @@ typedef struct {
 int spei_train_batch_u8(const spei_crop_record* table, const spei_crop_record* table_host, int n_in, int n_gt, float* input, float* gt,
                         int P, float rgb_range, spei_stream_t stream);
 
+/* One output frame of a training batch made from SHARP footage (speinet_amd.data.SharpTrainLoader; an extension beyond the reference,
+ * which precomputes its blurry sets): the P x P rectangle of the per-byte mean of `length` consecutive uint8 [H][W][3] frames.
+ * sizeof(spei_run_record) == 48. */
+typedef struct {
+    uint64_t src;         /* device address of the first byte of the run's FIRST frame */
+    int64_t frame_stride; /* bytes from one frame to the next (>= H * pitch unless length == 1) */
+    int32_t pitch;        /* bytes from one row to the next (>= 3 W) */
+    int32_t y0, x0;       /* top-left corner of the rectangle */
+    int32_t flags;        /* SPEI_CROP_* */
+    int32_t H, W;         /* the frames' size: the rectangle is checked against it on the host */
+    int32_t length;       /* frames in the run, 1..15 */
+    int32_t avail;        /* frames from src to the end of its clip (>= length) */
+} spei_run_record;
+
+/* spei_train_batch_u8 on runs: per byte of the rectangle u = floor(sum of that byte over the run's frames / length) in integer
+ * arithmetic — the bytes of spei_window_mean_u8's blur[m] — then (float)u * (float)(rgb_range / 255); geometry, the zero flag, the
+ * output layout and the arguments as spei_train_batch_u8.  A ground-truth record is a run of length 1 at the run's middle frame
+ * (start + length / 2).  Every record is checked on table_host before anything is launched: flag bits, the rectangle inside its
+ * frame, pitch, frame stride, 1 <= length <= 15, length <= avail. */
+int spei_train_batch_runs_u8(const spei_run_record* table, const spei_run_record* table_host, int n_in, int n_gt, float* input, float* gt,
+                             int P, float rgb_range, spei_stream_t stream);
+
 /* The reference's validation metric (util/utils.py:81-92 calc_psnr, trainer/trainer_swint_hsa_nsf.py:73) on the model's FLOAT output,
  * unclamped and unquantised: a, b fp32 [3][H][W]; d = a / rgb_range - b / rgb_range in fp32 over rows and columns [shave, size - shave);
  * result[0] = the sum of d * d in float64 (fixed order), result[1] = the number of terms.  PSNR = 100 if the sum is 0, else

@@ -11,6 +11,7 @@ frames and labels by sorted file name (as the reference's do, data/videodata_nfs
 123.png` do not sort in frame order.
 
   * `plan_runs`   — the reference's draw sequence on a `random.Random` of the caller's (no global state): runs and labels;
+  * `plan_dataset` — that sequence for every clip of a directory on one `random.Random(seed)` (also data.SharpClipSet's, per epoch);
   * `synthesize`  — the averaging on the GPU (csrc/blurset.hip, one launch per chunk of the clip): frames cross PCIe once as uint8,
                     device memory is bounded by the chunk;
   * `write_dataset` — every clip folder of a directory, PNGs encoded on worker threads behind `video.HostRing`.
@@ -160,29 +161,42 @@ def clip_folders(src_dir: str) -> list:
     return clips
 
 
-def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int = 0, threshold: int = 5, window_range=(1, 15),
-                  device="cuda", chunk_frames: int = CHUNK_FRAMES, log=None) -> list:
-    """For every clip folder under src_dir write out_dir/blur/<clip>/<i>.png, out_dir/gt/<clip>/<i>.png and out_dir/label/<clip>.npy
-    (reference process_dataset, mix_choice_dataset.py:78-117).  `ratio`: the share of sharp runs; `ratios`: several, one drawn per
-    clip (:79) from the same `random.Random(seed)` that then draws the clip's runs.  -> one dict per clip (name, ratio, frames, labels)."""
-    ratios = [ratio] if ratios is None else list(ratios)
+def plan_dataset(clip_lengths, ratios, seed: int = 0, threshold: int = 5, window_range=(1, 15)) -> list:
+    """The draws of a whole directory on ONE `random.Random(seed)` (reference process_dataset, mix_choice_dataset.py:78-117): for every
+    clip, in the clips' sorted order (`clip_lengths`: their frame counts in that order), `rng.choice(ratios)` — drawn only when there
+    are several ratios (:79) — then the clip's `plan_runs`.  -> one (ratio, (starts, lengths, labels)) per clip."""
+    ratios = list(ratios)
     if not ratios:
         raise ValueError("give ratio or ratios")
     for r in ratios:
         check_arguments(r, threshold, window_range)
     rng = random.Random(seed)
+    plans = []
+    for n_frames in clip_lengths:
+        r = rng.choice(ratios) if len(ratios) > 1 else ratios[0]
+        plans.append((r, plan_runs(int(n_frames), r, threshold, window_range, rng)))
+    return plans
+
+
+def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int = 0, threshold: int = 5, window_range=(1, 15),
+                  device="cuda", chunk_frames: int = CHUNK_FRAMES, log=None) -> list:
+    """For every clip folder under src_dir write out_dir/blur/<clip>/<i>.png, out_dir/gt/<clip>/<i>.png and out_dir/label/<clip>.npy
+    (reference process_dataset, mix_choice_dataset.py:78-117).  `ratio`: the share of sharp runs; `ratios`: several, one drawn per
+    clip (:79) from the same `random.Random(seed)` that then draws the clip's runs (`plan_dataset`).  -> one dict per clip (name, ratio,
+    frames, labels)."""
+    clips = []
+    for name, files in clip_folders(src_dir):
+        try:
+            clips.append((name, frames_of(files)))
+        except ValueError as e:
+            raise ValueError(f"clip {name}: {e}") from None
+    plans = plan_dataset([fr.T for _, fr in clips], [ratio] if ratios is None else ratios, seed, threshold, window_range)
     dev = torch.device(device)
     done = []
     os.makedirs(os.path.join(out_dir, "label"), exist_ok=True)
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-png") as writers, torch.cuda.device(dev):
         ring = HostRing(writers, n=16)
-        for name, files in clip_folders(src_dir):
-            r = rng.choice(ratios) if len(ratios) > 1 else ratios[0]
-            try:
-                fr = frames_of(files)
-            except ValueError as e:
-                raise ValueError(f"clip {name}: {e}") from None
-            starts, lengths, labels = plan_runs(fr.T, r, threshold, window_range, rng)
+        for (name, fr), (r, (starts, lengths, labels)) in zip(clips, plans):
             bdir, gdir = os.path.join(out_dir, "blur", name), os.path.join(out_dir, "gt", name)
             os.makedirs(bdir, exist_ok=True)
             os.makedirs(gdir, exist_ok=True)

@@ -17,18 +17,42 @@
 // store per plane, whatever the flags.  LDS pitch 33 dwords (one packed pixel per dword): a 32-lane half of a ds_write_b32 /
 // ds_read_b32 holds 4 rows x 8 groups and touches bank (row + 4 * group + k) % 32 in either orientation — all distinct.
 // `zero` records write zeros and read nothing.  Plain vector stores only.
+//
+// spei_train_batch_runs_u8 (data.SharpTrainLoader: training from sharp footage, the blur synthesised per batch) is the same kernel on
+// spei_run_record: the record's frame is the per-byte integer mean of a run of 1..15 consecutive frames, u = floor(sum / length) —
+// the bytes of spei_window_mean_u8's blur[m] (csrc/blurset.hip) — formed in the load phase: thread t sums its 12 bytes over the run's
+// frames in registers (two bytes per dword, 16 bits each: a sum is at most 15 * 255 = 3825), up to four frames' loads in flight
+// before the first add, divides (blurset.hip's multiply and shift) and packs the four pixels into LDS as above.  Everything after
+// the barrier is shared.  A ground-truth record is a run of length 1 at the run's middle frame.
 #include "common.h"
+
+#include <type_traits>
 
 namespace {
 
 constexpr int TILE = 32, PITCH = TILE + 1;
 constexpr int F_HFLIP = 1, F_VFLIP = 2, F_ROT90 = 4, F_ZERO = 8;
+constexpr int MAX_RUN = 15, RUN_LOADS = 4;                               // RUN_LOADS frames' loads are issued before their adds
 
-__global__ __launch_bounds__(256) void train_batch_kernel(const spei_crop_record* __restrict__ table, int n_in, float* __restrict__ input,
+// 12 bytes = 4 pixels of one source row, as three dwords
+__device__ __forceinline__ void load12(const unsigned char* s, bool dwords, uint32_t w[3]) {
+    if (dwords) {
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(s);
+        w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            w[k] = (uint32_t)s[4 * k] | ((uint32_t)s[4 * k + 1] << 8) | ((uint32_t)s[4 * k + 2] << 16) | ((uint32_t)s[4 * k + 3] << 24);
+    }
+}
+
+template <typename Rec>
+__global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict__ table, int n_in, float* __restrict__ input,
                                                           float* __restrict__ gt, int P, int tiles, float scale) {
+    constexpr bool RUNS = std::is_same<Rec, spei_run_record>::value;
     __shared__ uint32_t lds[TILE * PITCH];
     const int r = blockIdx.y;
-    const spei_crop_record rec = table[r];
+    const Rec rec = table[r];
     const int oi0 = (blockIdx.x / tiles) * TILE, oj0 = (blockIdx.x % tiles) * TILE;
     const int nI = min(TILE, P - oi0), nJ = min(TILE, P - oj0);          // multiples of 4 (P % 4 == 0)
     const int row = threadIdx.x >> 3, g4 = (threadIdx.x & 7) * 4;
@@ -41,14 +65,36 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const spei_crop_record
         if (row < nR && g4 < nC) {
             const unsigned char* s = reinterpret_cast<const unsigned char*>(rec.src) + (int64_t)(rec.y0 + cy_lo + row) * rec.pitch +
                                      (int64_t)(rec.x0 + cx_lo + g4) * 3;
+            bool dwords = (((uintptr_t)rec.src + (int64_t)rec.x0 * 3) & 3) == 0 && (rec.pitch & 3) == 0;      // every row of the crop starts on a dword
             uint32_t w[3];
-            if ((((uintptr_t)rec.src + (int64_t)rec.x0 * 3) & 3) == 0 && (rec.pitch & 3) == 0) {      // every row of the crop starts on a dword
-                const uint32_t* p = reinterpret_cast<const uint32_t*>(s);
-                w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
-            } else {
+            if constexpr (RUNS) {
+                const int len = rec.length;
+                dwords = dwords && (len == 1 || (rec.frame_stride & 3) == 0);                                  // ... in every frame of the run
+                // even[k] holds the sums of bytes 0 and 2 of dword k in its two halves, odd[k] those of bytes 1 and 3
+                uint32_t even[3] = {0u, 0u, 0u}, odd[3] = {0u, 0u, 0u};
+                for (int t0 = 0; t0 < len; t0 += RUN_LOADS) {
+                    uint32_t q[RUN_LOADS][3];
+#pragma unroll
+                    for (int u = 0; u < RUN_LOADS; ++u) {
+                        q[u][0] = q[u][1] = q[u][2] = 0u;
+                        if (t0 + u < len) load12(s + (int64_t)(t0 + u) * rec.frame_stride, dwords, q[u]);
+                    }
+#pragma unroll
+                    for (int u = 0; u < RUN_LOADS; ++u)
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            even[k] += q[u][k] & 0x00ff00ffu;
+                            odd[k] += (q[u][k] >> 8) & 0x00ff00ffu;
+                        }
+                }
+                // (sum * m) >> 16 == sum / len with m = ceil(2^16 / len), for every sum <= 15 * 255 and len <= 15 (csrc/blurset.hip)
+                const uint32_t magic = (65536u + len - 1) / len;
 #pragma unroll
                 for (int k = 0; k < 3; ++k)
-                    w[k] = (uint32_t)s[4 * k] | ((uint32_t)s[4 * k + 1] << 8) | ((uint32_t)s[4 * k + 2] << 16) | ((uint32_t)s[4 * k + 3] << 24);
+                    w[k] = (((even[k] & 0xffffu) * magic) >> 16) | ((((odd[k] & 0xffffu) * magic) >> 16) << 8) |
+                           ((((even[k] >> 16) * magic) >> 16) << 16) | ((((odd[k] >> 16) * magic) >> 16) << 24);
+            } else {
+                load12(s, dwords, w);
             }
             // 12 bytes = 4 pixels: pixel k is bytes 3k .. 3k+2 -> one dword 0x00BBGGRR each
             const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32), hi = (uint64_t)w[1] | ((uint64_t)w[2] << 32);
@@ -78,31 +124,49 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const spei_crop_record
         *reinterpret_cast<float4*>(base + ((int64_t)c * P + i) * P + oj0 + g4) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
 }
 
+// Every record is checked HERE, on the host copy: the kernel never meets a record that leaves its frame or its clip
+template <typename Rec>
+int train_batch(const char* name, const Rec* table, const Rec* table_host, int n_in, int n_gt, float* input, float* gt, int P, float rgb_range,
+                spei_stream_t stream) {
+    SPEI_REQUIRE(table && table_host, "%s: null record table (the device table and its host copy are both required)", name);
+    SPEI_REQUIRE(n_in >= 0 && n_gt >= 0 && n_in + n_gt > 0 && n_in + n_gt <= 65535, "%s: bad record counts %d + %d", name, n_in, n_gt);
+    SPEI_REQUIRE((n_in == 0 || input) && (n_gt == 0 || gt), "%s: null dst", name);
+    SPEI_REQUIRE(((uintptr_t)input & 15) == 0 && ((uintptr_t)gt & 15) == 0, "%s: dst must be 16-byte aligned", name);
+    SPEI_REQUIRE(P > 0 && P % 4 == 0 && P <= 4096, "%s: patch size %d must be a positive multiple of 4 (at most 4096)", name, P);
+    SPEI_REQUIRE(rgb_range > 0.0f, "%s: rgb_range %g must be positive", name, (double)rgb_range);
+    for (int r = 0; r < n_in + n_gt; ++r) {
+        const Rec& c = table_host[r];
+        SPEI_REQUIRE((c.flags & ~15) == 0, "%s: record %d has unknown flag bits 0x%x", name, r, (unsigned)c.flags);
+        if (c.flags & F_ZERO) continue;
+        SPEI_REQUIRE(c.src != 0, "%s: record %d has a null frame address", name, r);
+        SPEI_REQUIRE(c.H > 0 && c.W > 0 && c.W <= (1 << 24) && c.pitch >= c.W * 3, "%s: record %d: frame %dx%d with a row pitch of %d bytes", name,
+                     r, c.W, c.H, c.pitch);
+        SPEI_REQUIRE(c.y0 >= 0 && c.x0 >= 0 && (int64_t)c.y0 + P <= c.H && (int64_t)c.x0 + P <= c.W,
+                     "%s: record %d: the %dx%d rectangle at (y %d, x %d) leaves its %dx%d frame", name, r, P, P, c.y0, c.x0, c.W, c.H);
+        if constexpr (std::is_same<Rec, spei_run_record>::value) {
+            SPEI_REQUIRE(c.length >= 1 && c.length <= MAX_RUN, "%s: record %d has a run of length %d (1..%d)", name, r, c.length, MAX_RUN);
+            SPEI_REQUIRE(c.length <= c.avail, "%s: record %d: a run of %d frames where %d are left of its clip", name, r, c.length, c.avail);
+            SPEI_REQUIRE(c.length == 1 || c.frame_stride >= (int64_t)c.H * c.pitch,
+                         "%s: record %d: frame stride %lld < one %dx%d frame with a row pitch of %d bytes", name, r, (long long)c.frame_stride, c.W,
+                         c.H, c.pitch);
+        }
+    }
+    const int tiles = cdiv(P, TILE);
+    const float scale = (float)((double)rgb_range / 255.0);
+    hipLaunchKernelGGL(train_batch_kernel<Rec>, dim3(tiles * tiles, n_in + n_gt), dim3(256), 0, (hipStream_t)stream, table, n_in, input, gt, P,
+                       tiles, scale);
+    SPEI_CHECK_LAUNCH(name);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int spei_train_batch_u8(const spei_crop_record* table, const spei_crop_record* table_host, int n_in, int n_gt, float* input,
                                    float* gt, int P, float rgb_range, spei_stream_t stream) {
-    SPEI_REQUIRE(table && table_host, "spei_train_batch_u8: null record table (the device table and its host copy are both required)");
-    SPEI_REQUIRE(n_in >= 0 && n_gt >= 0 && n_in + n_gt > 0 && n_in + n_gt <= 65535, "spei_train_batch_u8: bad record counts %d + %d", n_in, n_gt);
-    SPEI_REQUIRE((n_in == 0 || input) && (n_gt == 0 || gt), "spei_train_batch_u8: null dst");
-    SPEI_REQUIRE(((uintptr_t)input & 15) == 0 && ((uintptr_t)gt & 15) == 0, "spei_train_batch_u8: dst must be 16-byte aligned");
-    SPEI_REQUIRE(P > 0 && P % 4 == 0 && P <= 4096, "spei_train_batch_u8: patch size %d must be a positive multiple of 4 (at most 4096)", P);
-    SPEI_REQUIRE(rgb_range > 0.0f, "spei_train_batch_u8: rgb_range %g must be positive", (double)rgb_range);
-    // the rectangles are checked HERE, on the host copy: the kernel never meets a record that leaves its frame
-    for (int r = 0; r < n_in + n_gt; ++r) {
-        const spei_crop_record& c = table_host[r];
-        SPEI_REQUIRE((c.flags & ~15) == 0, "spei_train_batch_u8: record %d has unknown flag bits 0x%x", r, (unsigned)c.flags);
-        if (c.flags & F_ZERO) continue;
-        SPEI_REQUIRE(c.src != 0, "spei_train_batch_u8: record %d has a null frame address", r);
-        SPEI_REQUIRE(c.H > 0 && c.W > 0 && c.W <= (1 << 24) && c.pitch >= c.W * 3, "spei_train_batch_u8: record %d: frame %dx%d with a row pitch of %d bytes",
-                     r, c.W, c.H, c.pitch);
-        SPEI_REQUIRE(c.y0 >= 0 && c.x0 >= 0 && (int64_t)c.y0 + P <= c.H && (int64_t)c.x0 + P <= c.W,
-                     "spei_train_batch_u8: record %d: the %dx%d rectangle at (y %d, x %d) leaves its %dx%d frame", r, P, P, c.y0, c.x0, c.W, c.H);
-    }
-    const int tiles = cdiv(P, TILE);
-    const float scale = (float)((double)rgb_range / 255.0);
-    hipLaunchKernelGGL(train_batch_kernel, dim3(tiles * tiles, n_in + n_gt), dim3(256), 0, (hipStream_t)stream, table, n_in, input, gt, P,
-                       tiles, scale);
-    SPEI_CHECK_LAUNCH("spei_train_batch_u8");
-    return 0;
+    return train_batch("spei_train_batch_u8", table, table_host, n_in, n_gt, input, gt, P, rgb_range, stream);
+}
+
+extern "C" int spei_train_batch_runs_u8(const spei_run_record* table, const spei_run_record* table_host, int n_in, int n_gt, float* input,
+                                        float* gt, int P, float rgb_range, spei_stream_t stream) {
+    return train_batch("spei_train_batch_runs_u8", table, table_host, n_in, n_gt, input, gt, P, rgb_range, stream);
 }

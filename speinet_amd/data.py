@@ -6,6 +6,14 @@
     Sampler      the order of an epoch, its batches and their draws (host only; splits the batches over the ranks)
     TrainLoader  iterates (input, gt) device tensors: spei_train_batch_u8 (csrc/train_batch.hip) one batch ahead on a side stream
 
+and, beyond the reference (which precomputes its blurry sets), the same loop fed from SHARP footage, the blur synthesised per batch:
+
+    SharpClipSet      folders of sharp frames cut into runs as blurset.write_dataset cuts them, re-drawn for every epoch: epoch e is the
+                      set write_dataset(seed = seed + e) would write, as ClipSet would scan it — but nothing is written
+    SharpStore        the sharp frames, decoded once, uint8 [T,H,W,3] per clip on the device
+    run_records       one batch as spei_run_record: an input frame is a run of sharp frames, the ground truth the run's middle frame
+    SharpTrainLoader  TrainLoader on that table and spei_train_batch_runs_u8, which averages each crop's run in its load phase
+
 The reference decodes the five input frames and the ground truth of every sample again for every sample, on DataLoader workers
 (`_load_file`).  Here a frame is decoded once; a batch costs the host one small record table and the device one launch.
 
@@ -42,6 +50,10 @@ F_HFLIP, F_VFLIP, F_ROT90, F_ZERO = 1, 2, 4, 8                        # SPEI_CRO
 # spei_crop_record
 RECORD = np.dtype([("src", "<u8"), ("pitch", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("flags", "<i4"), ("H", "<i4"), ("W", "<i4")])
 assert RECORD.itemsize == 32
+# spei_run_record
+RUN_RECORD = np.dtype([("src", "<u8"), ("frame_stride", "<i8"), ("pitch", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("flags", "<i4"),
+                       ("H", "<i4"), ("W", "<i4"), ("length", "<i4"), ("avail", "<i4")])
+assert RUN_RECORD.itemsize == 48
 
 Sample = namedtuple("Sample", "clip frames pre sub zero_pre names")
 Draw = namedtuple("Draw", "ix iy hflip vflip rot90")
@@ -52,7 +64,47 @@ def _number(name: str) -> int:
     return int(name.split(".")[-1])
 
 
-class ClipSet:
+class Windows:
+    """The sample arithmetic of the reference's loader over `self.clips` (dicts with T, names and, with references, pre and sub), given
+    `self.train`, `self.n_seq` and `self.references`: what ClipSet scans from a written set and SharpClipSet plans share."""
+
+    def _count(self, what: str) -> None:
+        self.n_frames_video = [c["T"] for c in self.clips]
+        # videodata_nfs.py:29
+        self.num_frame = sum(self.n_frames_video) - (self.n_seq - 1) * len(self.clips)
+        if len(self) <= 0:
+            raise ValueError(f"{what}: {self.num_frame} windows give no {'training' if self.train else 'evaluation'} sample")
+
+    def __len__(self) -> int:
+        return self.num_frame * 2 if self.train else self.num_frame - 2     # videodata_nfs.py:209-213
+
+    def _find_video_num(self, idx: int):
+        for i, t in enumerate(self.n_frames_video):                         # videodata_nfs.py:221-226, :231
+            n = t - self.n_seq + 1
+            if idx < n:
+                return i, idx
+            idx -= n
+        raise IndexError("sample index beyond the last clip")
+
+    def sample(self, idx: int) -> Sample:
+        if not 0 <= idx < len(self):
+            raise IndexError(f"sample {idx} of {len(self)}")
+        if self.train:
+            idx %= self.num_frame                                           # videodata_nfs.py:215-217
+        v, f = self._find_video_num(idx)
+        clip = self.clips[v]
+        frames = list(range(f, f + self.n_seq))
+        if not self.references:
+            return Sample(v, frames, None, None, False, [clip["names"][i] for i in frames])
+        # videodata_nfs.py:237-238: the references of the window's FIRST frame
+        pre, sub = clip["pre"][f], clip["sub"][f]
+        names = [clip["names"][i] for i in frames + [pre, sub]]
+        # videodata_nfs.py:254-257: frame_numbers[2] (the window's last frame when n_seq = 3) against the pre reference only
+        zero_pre = abs(_number(names[2]) - _number(names[3])) > MAX_GAP
+        return Sample(v, frames, pre, sub, zero_pre, names)
+
+
+class ClipSet(Windows):
     """The scan of `dir_data` (blur/<clip>/*, gt/<clip>/*, label/<clip>.npy) and the samples the reference's loader makes of it.
 
     train                 training: clips truncated to n_frames_per_video, `len` = 2 * num_frame, idx taken modulo num_frame
@@ -112,43 +164,68 @@ class ClipSet:
                 # videodata_nfs.py:154: return_BlurryIndices on the clip's own labels, NOT reflect-padded
                 clip["pre"], clip["sub"] = selection.blurry_indices(clip["labels"])
             self.clips.append(clip)
-        self.n_frames_video = [c["T"] for c in self.clips]
-        # videodata_nfs.py:29
-        self.num_frame = sum(self.n_frames_video) - (self.n_seq - 1) * len(self.clips)
-        if len(self) <= 0:
-            raise ValueError(f"{dir_data}: {self.num_frame} windows give no {'training' if self.train else 'evaluation'} sample")
-
-    def __len__(self) -> int:
-        return self.num_frame * 2 if self.train else self.num_frame - 2     # videodata_nfs.py:209-213
+        self._count(dir_data)
 
     def nbytes(self) -> int:
         """Bytes of every blur and gt frame as uint8 RGB (from the image headers)."""
         return sum(2 * c["T"] * c["H"] * c["W"] * 3 for c in self.clips)
 
-    def _find_video_num(self, idx: int):
-        for i, t in enumerate(self.n_frames_video):                         # videodata_nfs.py:221-226, :231
-            n = t - self.n_seq + 1
-            if idx < n:
-                return i, idx
-            idx -= n
-        raise IndexError("sample index beyond the last clip")
 
-    def sample(self, idx: int) -> Sample:
-        if not 0 <= idx < len(self):
-            raise IndexError(f"sample {idx} of {len(self)}")
-        if self.train:
-            idx %= self.num_frame                                           # videodata_nfs.py:215-217
-        v, f = self._find_video_num(idx)
-        clip = self.clips[v]
-        frames = list(range(f, f + self.n_seq))
-        if not self.references:
-            return Sample(v, frames, None, None, False, [clip["names"][i] for i in frames])
-        # videodata_nfs.py:237-238: the references of the window's FIRST frame
-        pre, sub = clip["pre"][f], clip["sub"][f]
-        names = [clip["names"][i] for i in frames + [pre, sub]]
-        # videodata_nfs.py:254-257: frame_numbers[2] (the window's last frame when n_seq = 3) against the pre reference only
-        zero_pre = abs(_number(names[2]) - _number(names[3])) > MAX_GAP
-        return Sample(v, frames, pre, sub, zero_pre, names)
+class SharpClipSet(Windows):
+    """Folders of sharp frames (`dir_sharp/<clip>/*`, as `python -m speinet_amd.blurset --input` takes them) as a training set whose
+    blurry frames are never written.  `plan(epoch)` sets `clips` to what `blurset.write_dataset(dir_sharp, out, ratios=ratios,
+    seed=seed + epoch, ...)` followed by `ClipSet(out, True, ...)` would give — per source clip the runs of `blurset.plan_dataset`,
+    label 1 for a run of at most `threshold` frames, names `<clip>.<run index, six digits>`, truncated to n_frames_per_video RUNS,
+    pre / sub from the truncated labels — so `len()` and `sample(idx)` are ClipSet's on that set.  A virtual clip also carries `starts`
+    and `lengths` (the runs' sharp frames) and `source` (its index in `sharp`, the scanned folders).  The constructor plans epoch 0."""
+
+    def __init__(self, dir_sharp: str, ratios=(0.5,), threshold: int = 5, window_range=(1, 15), seed: int = 0, n_sequence: int = 3,
+                 n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None):
+        from .blurset import clip_folders
+        from .video import frames_of
+        self.dir_data, self.train, self.n_seq, self.references = dir_sharp, True, int(n_sequence), bool(references)
+        if self.references and self.n_seq != 3:
+            raise ValueError("samples with references are windows of 3 frames (the reference's zeroing test reads names 2 and 3: videodata_nfs.py:254)")
+        self.ratios, self.threshold, self.window_range = list(ratios), int(threshold), tuple(window_range)    # checked by plan_dataset
+        self.seed, self.n_frames_per_video = int(seed), int(n_frames_per_video)
+        self.sharp = []
+        for name, files in clip_folders(dir_sharp):
+            try:
+                fr = frames_of(files)                                        # headers only; mixed sizes inside a clip raise here
+            except ValueError as e:
+                raise ValueError(f"clip {name}: {e}") from None
+            if patch is not None and (fr.H < patch or fr.W < patch):
+                raise ValueError(f"clip {name}: frames are {fr.W}x{fr.H}, smaller than the {patch}x{patch} patch")
+            self.sharp.append({"name": name, "files": files, "T": fr.T, "H": fr.H, "W": fr.W})
+        self.plan(0)
+
+    def plan(self, epoch: int) -> None:
+        from .blurset import plan_dataset
+        plans = plan_dataset([c["T"] for c in self.sharp], self.ratios, self.seed + epoch, self.threshold, self.window_range)
+        clips = []
+        for k, (src, (ratio, (starts, lengths, labels))) in enumerate(zip(self.sharp, plans)):
+            cut = slice(0, self.n_frames_per_video)
+            starts, lengths, labels = starts[cut], lengths[cut], [int(v) for v in labels[cut]]
+            if len(labels) < self.n_seq:
+                raise ValueError(f"clip {src['name']}: the plan of epoch {epoch} cuts its {src['T']} frames into {len(labels)} runs, fewer "
+                                 f"than one window of {self.n_seq}")
+            clip = {"name": src["name"], "source": k, "ratio": ratio, "T": len(labels), "H": src["H"], "W": src["W"], "starts": starts,
+                    "lengths": lengths, "labels": labels, "pre": None, "sub": None,
+                    "names": [f"{src['name']}.{m:06d}" for m in range(len(labels))]}
+            if self.references:
+                clip["pre"], clip["sub"] = selection.blurry_indices(labels)
+            clips.append(clip)
+        self.clips, self.epoch = clips, epoch
+        self._count(f"{self.dir_data} (epoch {epoch})")
+
+    def summary(self) -> str:
+        """One line on the current plan: its runs and how many are labelled sharp."""
+        runs, sharp = sum(c["T"] for c in self.clips), sum(sum(c["labels"]) for c in self.clips)
+        return f"Plan {self.epoch} of {self.dir_data}: {runs} runs of {sum(c['T'] for c in self.sharp)} sharp frames, {sharp} labelled sharp"
+
+    def nbytes(self) -> int:
+        """Bytes of every sharp frame as uint8 RGB (from the image headers)."""
+        return sum(c["T"] * c["H"] * c["W"] * 3 for c in self.sharp)
 
 
 def draw(rng: random.Random, ih: int, iw: int, patch: int, augment: bool = True) -> Draw:
@@ -190,11 +267,7 @@ class ClipStore:
         self.clipset, self.residency, self.device = clipset, residency, torch.device(device)
         self.nbytes = clipset.nbytes()
         if residency == "device":
-            if budget_bytes is None:
-                budget_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
-            if self.nbytes > budget_bytes:
-                raise MemoryError(f"{clipset.dir_data}: the clips are {self.nbytes} bytes as uint8, the budget for device residency is "
-                                  f"{budget_bytes} bytes; use residency='host' (page-locked host memory, patches uploaded per batch)")
+            self._admit(budget_bytes, "use residency='host' (page-locked host memory, patches uploaded per batch)")
         self.blur, self.gt = [], []
         with ThreadPoolExecutor(max_workers=usable_cpus()) as pool:
             for clip in clipset.clips:
@@ -203,6 +276,13 @@ class ClipStore:
         if log is not None:
             log(f"ClipStore: {len(clipset.clips)} clips, {sum(c['T'] for c in clipset.clips)} blur/gt pairs, {self.nbytes} bytes, "
                 f"residency {residency}")
+
+    def _admit(self, budget_bytes: Optional[int], otherwise: str) -> None:
+        if budget_bytes is None:
+            budget_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
+        if self.nbytes > budget_bytes:
+            raise MemoryError(f"{self.clipset.dir_data}: the clips are {self.nbytes} bytes as uint8, the budget for device residency is "
+                              f"{budget_bytes} bytes; {otherwise}")
 
     def _load(self, pool, clip, paths) -> torch.Tensor:
         from .video import _imread
@@ -217,6 +297,22 @@ class ClipStore:
             arr[i] = img
         list(pool.map(one, range(T)))
         return host if self.residency == "host" else host.to(self.device)
+
+
+class SharpStore(ClipStore):
+    """Every sharp frame of a SharpClipSet decoded once and kept as one uint8 [T,H,W,3] device tensor per source clip (`frames`, in the
+    order of `clipset.sharp`), under ClipStore's budget rule.  Device residency only: a record reads up to 15 rectangles."""
+
+    def __init__(self, clipset: "SharpClipSet", device="cuda:0", budget_bytes: Optional[int] = None, log=print):
+        self.clipset, self.residency, self.device = clipset, "device", torch.device(device)
+        self.nbytes = clipset.nbytes()
+        self._admit(budget_bytes, "a set that does not fit is trained from disk: write it once with `python -m speinet_amd.blurset` and "
+                                  "pass `--dir_data` (host residency is built for written sets only)")
+        with ThreadPoolExecutor(max_workers=usable_cpus()) as pool:
+            self.frames = [self._load(pool, clip, clip["files"]) for clip in clipset.sharp]
+        if log is not None:
+            log(f"SharpStore: {len(clipset.sharp)} clips, {sum(c['T'] for c in clipset.sharp)} sharp frames, {self.nbytes} bytes, "
+                f"residency device")
 
 
 class Sampler:
@@ -256,7 +352,28 @@ class Sampler:
             c = cs.clips[s.clip]
             items.append((idx, s, draw(self.rng, c["H"], c["W"], self.patch, self.augment)))
         batches = [items[i:i + self.batch] for i in range(0, len(items), self.batch)]
-        return batches[self.rank::self.world]
+        return batches[:self.n_batches()][self.rank::self.world]
+
+
+class SharpSampler(Sampler):
+    """Sampler over a SharpClipSet: `epoch()` number e (0, 1, ...) first makes the set `plan(e)` (`replan=False`: plan 0 every time), then
+    draws order and crops as Sampler does, so calling `epoch()` once per finished epoch — Fit's resume loop — lands on the right plan.
+    The number of runs changes with the plan: with `world` > 1 an epoch is cut to the largest number of batches that divides by `world`
+    (all ranks still consume the same draws), and `n_batches()` reports that number for the plan in force."""
+
+    def __init__(self, clipset: "SharpClipSet", batch: int, patch: int = 200, seed: int = 1, augment: bool = True,
+                 rank: Optional[int] = None, world: Optional[int] = None, replan: bool = True):
+        super().__init__(clipset, batch, patch, seed, augment, rank, world)
+        self.replan, self.epochs = replan, 0
+
+    def n_batches(self) -> int:
+        n = super().n_batches()
+        return n - n % self.world
+
+    def epoch(self) -> list:
+        self.clipset.plan(self.epochs if self.replan else 0)
+        self.epochs += 1
+        return super().epoch()
 
 
 def batch_records(clipset: ClipSet, store: ClipStore, items, patch: int) -> np.ndarray:
@@ -289,6 +406,34 @@ def batch_records(clipset: ClipSet, store: ClipStore, items, patch: int) -> np.n
     return rec
 
 
+def run_records(clipset: SharpClipSet, store: SharpStore, items) -> np.ndarray:
+    """`batch_records` for a SharpClipSet under its CURRENT plan, as spei_run_record: B * F input records — the window's runs and, with
+    references, the pre and sub runs (only pre may carry the zero flag) — then B gt records: a run of length 1 at the middle run's middle
+    frame, start + length // 2.  `avail` counts the sharp frames from the record's first frame to the end of its clip."""
+    n_seq, refs = clipset.n_seq, clipset.references
+    F = n_seq + (2 if refs else 0)
+    B = len(items)
+    rec = np.zeros(B * F + B, dtype=RUN_RECORD)
+    inp, gt = rec[:B * F].reshape(B, F), rec[B * F:]
+    for b, (_idx, s, d) in enumerate(items):
+        c = clipset.clips[s.clip]
+        sharp = store.frames[c["source"]]                   # uint8 [T,H,W,3]
+        T, H, W, _ = sharp.shape
+        runs = np.asarray(list(s.frames) + ([s.pre, s.sub] if refs else []), dtype=np.int64)
+        start, length = c["starts"][runs], c["lengths"][runs]
+        mid = start[n_seq // 2] + length[n_seq // 2] // 2
+        flags = (F_HFLIP if d.hflip else 0) | (F_VFLIP if d.vflip else 0) | (F_ROT90 if d.rot90 else 0)
+        base, fstride = sharp.data_ptr(), sharp.stride(0)
+        for part in (inp[b], gt[b:b + 1]):
+            part["frame_stride"], part["pitch"], part["y0"], part["x0"], part["flags"] = fstride, sharp.stride(1), d.iy, d.ix, flags
+            part["H"], part["W"] = H, W
+        inp[b]["src"], inp[b]["length"], inp[b]["avail"] = (base + start * fstride).astype(np.uint64), length, T - start
+        gt[b]["src"], gt[b]["length"], gt[b]["avail"] = base + int(mid) * fstride, 1, T - mid
+        if refs and s.zero_pre:
+            inp[b]["flags"][n_seq] |= F_ZERO
+    return rec
+
+
 class TrainLoader:
     """Iterates (input [B,F,3,P,P], gt [B,3,P,P]) fp32 device tensors of one epoch per `iter()`.
 
@@ -302,14 +447,15 @@ class TrainLoader:
     row range by row range, into the slot's page-locked staging buffer and uploaded with one asynchronous copy; the records then point
     into the uploaded rectangles (offsets rebased to 0) and go through the same kernel, so the results are bit-identical."""
     RING = 3
+    RECORD = RECORD                  # the table's record type; SharpTrainLoader's is RUN_RECORD
 
     def __init__(self, clipset: ClipSet, store: ClipStore, batch: int, patch: int = 200, seed: int = 1, augment: bool = True,
-                 rgb_range: float = 1, prefetch: bool = True, rank: Optional[int] = None, world: Optional[int] = None):
+                 rgb_range: float = 1, prefetch: bool = True, rank: Optional[int] = None, world: Optional[int] = None, sampler=None):
         from . import ops
         if store.clipset is not clipset:
             raise ValueError("the ClipStore was loaded from another ClipSet")
         self.clipset, self.store, self.batch, self.patch, self.rgb_range, self.prefetch = clipset, store, batch, patch, float(rgb_range), prefetch
-        self.sampler = Sampler(clipset, batch, patch, seed, augment, rank, world)
+        self.sampler = Sampler(clipset, batch, patch, seed, augment, rank, world) if sampler is None else sampler
         self.device = store.device
         self.F = clipset.n_seq + (2 if clipset.references else 0)
         self.ctx = ops.Ctx(device=self.device)
@@ -318,8 +464,8 @@ class TrainLoader:
             self.side = torch.cuda.Stream(device=self.device)
             self.slots = []
             for _ in range(self.RING):
-                slot = {"host": torch.empty(n_rec * RECORD.itemsize, dtype=torch.uint8, pin_memory=True),
-                        "dev": torch.empty(n_rec * RECORD.itemsize, dtype=torch.uint8, device=self.device), "event": None}
+                slot = {"host": torch.empty(n_rec * self.RECORD.itemsize, dtype=torch.uint8, pin_memory=True),
+                        "dev": torch.empty(n_rec * self.RECORD.itemsize, dtype=torch.uint8, device=self.device), "event": None}
                 if store.residency == "host":
                     slot["stage"] = torch.empty((n_rec, patch, patch, 3), dtype=torch.uint8, pin_memory=True)
                     slot["stage_dev"] = torch.empty((n_rec, patch, patch, 3), dtype=torch.uint8, device=self.device)
@@ -330,6 +476,12 @@ class TrainLoader:
     def __len__(self) -> int:
         return len(self.sampler)
 
+    def _records(self, items) -> np.ndarray:
+        return batch_records(self.clipset, self.store, items, self.patch)
+
+    def _build(self, *args) -> None:
+        self.ctx.train_batch(*args)
+
     def _launch(self, items):
         """Build one batch on the side stream (from whichever thread calls); returns (input, gt, event)."""
         P, F, B = self.patch, self.F, len(items)
@@ -338,7 +490,7 @@ class TrainLoader:
             self.launched += 1
             if slot["event"] is not None:
                 slot["event"].synchronize()                   # the launch issued RING batches ago: long finished
-            rec = batch_records(self.clipset, self.store, items, P)
+            rec = self._records(items)
             n = rec.size
             inp = torch.empty((B, F, 3, P, P), device=self.device)         # blocks of the side stream: see __iter__
             gt = torch.empty((B, 3, P, P), device=self.device)
@@ -360,11 +512,11 @@ class TrainLoader:
                 base = slot["stage_dev"].data_ptr()
                 rec["src"] = np.uint64(base) + np.arange(n, dtype=np.uint64) * np.uint64(P * P * 3)
                 rec["pitch"], rec["y0"], rec["x0"], rec["H"], rec["W"] = P * 3, 0, 0, P, P
-            host = slot["host"][:n * RECORD.itemsize]
+            host = slot["host"][:n * self.RECORD.itemsize]
             host.numpy()[...] = rec.view(np.uint8).reshape(-1)
-            dev = slot["dev"][:n * RECORD.itemsize]
+            dev = slot["dev"][:n * self.RECORD.itemsize]
             dev.copy_(host, non_blocking=True)
-            self.ctx.train_batch(dev, host, B * F, B, inp, gt, P, self.rgb_range)
+            self._build(dev, host, B * F, B, inp, gt, P, self.rgb_range)
             ev = torch.cuda.Event()
             ev.record(self.side)
             slot["event"] = ev
@@ -390,3 +542,21 @@ class TrainLoader:
         finally:
             if pending is not None:                           # an abandoned epoch: let the launch in flight finish before the ring moves on
                 pending.result()
+
+
+class SharpTrainLoader(TrainLoader):
+    """TrainLoader fed from sharp footage: the table is `run_records`, the launch spei_train_batch_runs_u8, which averages the run of
+    every crop in its load phase; ring, side stream and prefetch thread are TrainLoader's.  Every `iter()` is one epoch under its own
+    plan (SharpSampler; `replan=False`: plan 0 throughout).  All launches of an epoch are issued before the next one is planned."""
+    RECORD = RUN_RECORD
+
+    def __init__(self, clipset: SharpClipSet, store: SharpStore, batch: int, patch: int = 200, seed: int = 1, augment: bool = True,
+                 rgb_range: float = 1, prefetch: bool = True, rank: Optional[int] = None, world: Optional[int] = None, replan: bool = True):
+        super().__init__(clipset, store, batch, patch, seed, augment, rgb_range, prefetch, rank, world,
+                         sampler=SharpSampler(clipset, batch, patch, seed, augment, rank, world, replan))
+
+    def _records(self, items) -> np.ndarray:
+        return run_records(self.clipset, self.store, items)
+
+    def _build(self, *args) -> None:
+        self.ctx.train_batch_runs(*args)

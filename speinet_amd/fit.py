@@ -5,7 +5,14 @@ speinet_amd.trainer.Trainer, fed by speinet_amd.data.TrainLoader.
         [--batch_size 20 --patch_size 200 --lr 1e-4 --lr_decay 150 --gamma 0.5 --epochs 500 --print_every 100
          --n_frames_per_video 200 --no_augment --pre_train <ckpt> --resume --train_precision bf16x3|bf16 --residency device|host --seed 1]
 
-Both directories hold blur/<clip>/*, gt/<clip>/* and (model speinet) label/<clip>.npy.  Names and defaults are those of the reference's
+Both directories hold blur/<clip>/*, gt/<clip>/* and (model speinet) label/<clip>.npy.  In place of `--dir_data`,
+
+        --dir_sharp <dir of folders of sharp frames> [--blur_ratio 0.1 0.3 0.5 --blur_threshold 5 --no_replan]
+
+trains from sharp high-frame-rate footage directly (an extension beyond the reference, which precomputes its sets): the frames stay on
+the device as uint8, every epoch e trains on the set `python -m speinet_amd.blurset --seed <seed + e>` would write — runs, labels and
+references re-drawn, nothing written — and every batch is averaged, cropped and augmented by one launch (data.SharpTrainLoader);
+`--no_replan` keeps epoch 0's set.  The validation set stays a written one.  Names and defaults are those of the reference's
 option/__init__.py and its SPEINet template.  Per epoch, in the reference's order: `scheduler.step()`, one `Trainer.step` per batch,
 a log line every `print_every` batches, then `evaluate()` — eval mode, one full-size validation sample at a time through the model's
 inference path in its configured `precision`, the reference's PSNR of the float output (spei_psnr_f32) — and the files of the
@@ -95,7 +102,8 @@ def load_weights(model: torch.nn.Module, path: str) -> None:
 
 
 class Fit:
-    """The epoch loop.  `model` on its device, `loss` a speinet_amd.loss.Loss, `train_loader` a data.TrainLoader; `val_set` a
+    """The epoch loop.  `model` on its device, `loss` a speinet_amd.loss.Loss, `train_loader` a data.TrainLoader (or SharpTrainLoader,
+    whose set is planned anew by every epoch: its plan is logged with the epoch's first batch); `val_set` a
     data.ClipSet(train=False) (or None: no evaluation, PSNR 0 is logged) with `val_store` its ClipStore (default: loaded here with the
     training store's residency)."""
 
@@ -144,10 +152,11 @@ class Fit:
         epoch, lr = self.schedule.begin_epoch()
         self.log("Epoch {:3d} with Lr {:.2e}".format(epoch, lr))
         total, n_batches = 0.0, 0
-        n_samples = len(self.loader.clipset)
         terms_log = getattr(self.loss, "log", None)          # speinet_amd.loss.Loss: one list of per-term values per call
         mark = len(terms_log) if terms_log is not None else 0
         for batch, (inp, gt) in enumerate(self.loader):
+            if batch == 0 and hasattr(self.loader.clipset, "summary"):
+                self.log(self.loader.clipset.summary())      # a SharpClipSet: this epoch's runs
             total += self.trainer.step(inp, gt)
             n_batches += 1
             if (batch + 1) % self.print_every == 0:
@@ -158,7 +167,7 @@ class Fit:
                     means = [sum(row[i] for row in seen) / len(seen) for i in range(len(self.loss.terms))]
                     terms = "".join("[{}: {:.4f}]".format(kind, v) for (_w, kind, _f), v in zip(self.loss.terms, means))
                 # trainer_swint_hsa_nsf.py:43-49 (its `mid` term is a constant 0)
-                self.log("[{}/{}]\tLoss : [total: {:.4f}]{}[mid: {:.4f}]".format((batch + 1) * self.loader.batch, n_samples, total / (batch + 1),
+                self.log("[{}/{}]\tLoss : [total: {:.4f}]{}[mid: {:.4f}]".format((batch + 1) * self.loader.batch, len(self.loader.clipset), total / (batch + 1),
                                                                                 terms, 0.0))
         mean = total / max(n_batches, 1)
         self.loss_log.append(mean)
@@ -241,10 +250,16 @@ def build_model(name: str, device, pre_train: Optional[str] = None, train_precis
 
 
 def main(argv=None) -> None:
-    from .data import ClipSet, ClipStore, TrainLoader
+    from .data import ClipSet, ClipStore, SharpClipSet, SharpStore, SharpTrainLoader, TrainLoader
     from .loss import Loss
-    ap = argparse.ArgumentParser(description="Train SPEINet (or its swint sub-model) on blur / gt / label folders, on one MI355X")
-    ap.add_argument("--dir_data", required=True)
+    ap = argparse.ArgumentParser(description="Train SPEINet (or its swint sub-model) on blur / gt / label folders, or on folders of sharp "
+                                             "frames blurred per batch, on one MI355X")
+    source = ap.add_mutually_exclusive_group(required=True)
+    source.add_argument("--dir_data", help="a written training set: blur/<clip>/, gt/<clip>/ and label/<clip>.npy")
+    source.add_argument("--dir_sharp", help="one folder of sharp high-frame-rate frames per clip; the blur is synthesised per batch")
+    ap.add_argument("--blur_ratio", type=float, nargs="+", default=[0.5], help="--dir_sharp: share of sharp runs; several: one is drawn per clip")
+    ap.add_argument("--blur_threshold", type=int, default=5, help="--dir_sharp: a run of at most this many frames is a sharp frame (label 1)")
+    ap.add_argument("--no_replan", action="store_true", help="--dir_sharp: keep epoch 0's runs for every epoch")
     ap.add_argument("--dir_data_test", required=True)
     ap.add_argument("--save", required=True)
     ap.add_argument("--model", default="speinet", choices=("speinet", "swint"))
@@ -266,11 +281,22 @@ def main(argv=None) -> None:
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     refs = a.model == "speinet"
-    train_set = ClipSet(a.dir_data, True, 3, a.n_frames_per_video, references=refs, patch=a.patch_size)
+    if a.dir_sharp and a.residency != "device":
+        ap.error("--dir_sharp keeps the sharp frames on the device (--residency device); a set that does not fit is written with "
+                 "`python -m speinet_amd.blurset` and trained with --dir_data")
+    if a.dir_sharp:
+        train_set = SharpClipSet(a.dir_sharp, a.blur_ratio, a.blur_threshold, seed=a.seed, n_frames_per_video=a.n_frames_per_video,
+                                 references=refs, patch=a.patch_size)
+    else:
+        train_set = ClipSet(a.dir_data, True, 3, a.n_frames_per_video, references=refs, patch=a.patch_size)
     val_set = ClipSet(a.dir_data_test, False, 3, a.n_frames_per_video, references=refs)
     net = build_model(a.model, a.device, a.pre_train, a.train_precision)
-    store = ClipStore(train_set, residency=a.residency, device=a.device)
-    loader = TrainLoader(train_set, store, a.batch_size, a.patch_size, seed=a.seed, augment=not a.no_augment)
+    if a.dir_sharp:
+        store = SharpStore(train_set, device=a.device)
+        loader = SharpTrainLoader(train_set, store, a.batch_size, a.patch_size, seed=a.seed, augment=not a.no_augment, replan=not a.no_replan)
+    else:
+        store = ClipStore(train_set, residency=a.residency, device=a.device)
+        loader = TrainLoader(train_set, store, a.batch_size, a.patch_size, seed=a.seed, augment=not a.no_augment)
     Fit(net, Loss(a.loss, device=a.device), loader, val_set, save=a.save, lr=a.lr, lr_decay=a.lr_decay, gamma=a.gamma, epochs=a.epochs,
         print_every=a.print_every, resume=a.resume, seed=a.seed).run()
 

@@ -550,6 +550,18 @@ class Ctx:
         _lib.check(_lib.lib().spei_train_batch_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(input), self._tp(gt),
                                                   patch, float(rgb_range), self._stream()), "spei_train_batch_u8")
 
+    def train_batch_runs(self, table: torch.Tensor, table_host: torch.Tensor, n_in: int, n_gt: int, input: torch.Tensor,
+                         gt: torch.Tensor, patch: int, rgb_range: float = 1.0) -> None:
+        """`train_batch` on run records (speinet_amd.data.RUN_RECORD, 48 bytes each): every output frame is the crop of the per-byte
+        integer mean of a run of 1..15 consecutive resident frames — spei_window_mean_u8's bytes, never written to memory."""
+        nb = (n_in + n_gt) * 48
+        assert table.dtype == torch.uint8 and table.numel() >= nb and not table_host.is_cuda and table_host.dtype == torch.uint8 \
+            and table_host.is_contiguous() and table_host.numel() >= nb
+        assert input.dtype == torch.float32 and input.numel() == n_in * 3 * patch * patch
+        assert gt.dtype == torch.float32 and gt.numel() == n_gt * 3 * patch * patch
+        _lib.check(_lib.lib().spei_train_batch_runs_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(input),
+                                                       self._tp(gt), patch, float(rgb_range), self._stream()), "spei_train_batch_runs_u8")
+
     def rl_prior(self, img: torch.Tensor, iters: int, lam: float = 0.01) -> torch.Tensor:
         """img [3,H,W] -> [3,H,W]."""
         c, h, w = img.shape
