@@ -472,6 +472,21 @@ int spei_frame_u8_out(const float* src, unsigned char* dst, int* nonfinite, int 
 int spei_frame_pair_stats(const unsigned char* src, int64_t frame_stride, const unsigned char* prev, int N, int H, int W, int* hist,
                           int64_t* sad, spei_stream_t stream);
 
+/* Deep frames: `depth` d = 10 or 12 bits per sample in little-endian 16-bit words, D = 2^d - 1; a word above D is read as D, so the
+ * result is defined for all 65536 words.  frame_stride stays in BYTES and must be even; every uint16 pointer 2-byte aligned.
+ * spei_frames_u16_in: as spei_frames_u8_in on N packed uint16 [H][W][3] frames, values (float)v * (float)(1.0 / D) (one float32
+ *   multiply), the same reflect pad; gray (or NULL) is bit-identical to spei_det_gray on the frames as fp32 (float)v * (float)(255.0 / D):
+ *   the focus measures see the usual 0..255 scale with the extra bits kept.
+ * spei_frame_u16_out: as spei_frame_u8_out, dst packed uint16 [H][W][3] = round_half_even(clamp(x * D, 0, D)) in float32, 0 for a
+ *   non-finite value; the same optional flag.
+ * spei_frame_pair_stats_u16: as spei_frame_pair_stats on the d-bit luma Yd = (77 R + 150 G + 29 B + 128) >> 8: hist bin Yd >> (d - 6)
+ *   (64 bins), sad over Yd (2^(d-8) times the 8-bit unit).  Integers throughout. */
+int spei_frames_u16_in(const uint16_t* src, int64_t frame_stride, float* dst, float* gray, int N, int H, int W, int depth,
+                       spei_stream_t stream);
+int spei_frame_u16_out(const float* src, uint16_t* dst, int* nonfinite, int H, int W, int Hp, int Wp, int depth, spei_stream_t stream);
+int spei_frame_pair_stats_u16(const uint16_t* src, int64_t frame_stride, const uint16_t* prev, int N, int H, int W, int depth, int* hist,
+                              int64_t* sad, spei_stream_t stream);
+
 /* ---- planar YUV frames of the clip API (speinet_amd/y4m.py, speinet_amd/video.py; an extension beyond the reference) ---- */
 
 #define SPEI_YUV_420_CENTER 0 /* 4:2:0, chroma sample at the centre of its 2x2 block (y4m C420jpeg, and bare C420) */
@@ -505,6 +520,33 @@ int spei_yuv_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned 
                        int range, spei_stream_t stream);
 int spei_rgb_u8_to_yuv(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
                        spei_stream_t stream);
+
+/* The same two conversions on deep samples: `depth` d = 10 or 12, s = d - 8, D = 2^d - 1, samples in little-endian 16-bit words (a
+ * word above D is read as D); a planar frame and a packed RGB frame are laid out as above with uint16 elements, frame_stride in BYTES
+ * (even), every pointer 2-byte aligned.  The rule that makes every row, exact rationals rounded to nearest (no value is an exact
+ * half; at d = 8 it gives the table above): Kr, Kb = 0.299, 0.114 (BT.601) or 0.2126, 0.0722 (BT.709), Kg = 1 - Kr - Kb; full range
+ * ly = lc = 1, yo = 0; limited range ly = 219 2^s / D, lc = 224 2^s / D, yo = 16 2^s; the chroma zero is 128 2^s in both ranges;
+ *   yr = rnd(16384 Kr ly), yb = rnd(16384 Kb ly), yg = rnd(16384 ly) - yr - yb
+ *   ub = vr = rnd(16384 lc / 2), ur = -rnd(16384 lc Kr / (2 (1 - Kb))), ug = -ub - ur, vb = -rnd(16384 lc Kb / (2 (1 - Kr))), vg = -vr - vb
+ *   cy = rnd(16384 / ly), rv = rnd(16384 2 (1 - Kr) / lc), bu = rnd(16384 2 (1 - Kb) / lc),
+ *   gu = -rnd(16384 2 Kb (1 - Kb) / (Kg lc)), gv = -rnd(16384 2 Kr (1 - Kr) / (Kg lc)).
+ * Full range therefore reuses the 8-bit full rows at every depth.  Limited range:
+ *                    yr    yg    yb |    ur    ug   ub |   vr    vg    vb |  yo |    cy |    rv |    gu     gv |    bu
+ *   d 10 601 limited 4195  8236  1599 | -2421 -4754 7175 | 7175 -6008 -1167 |  64 | 19133 | 26226 | -6438 -13359 | 33148
+ *   d 10 709 limited 2983 10034  1013 | -1644 -5531 7175 | 7175 -6517  -658 |  64 | 19133 | 29459 | -3504  -8757 | 34711
+ *   d 12 601 limited 4192  8229  1598 | -2420 -4750 7170 | 7170 -6004 -1166 | 256 | 19147 | 26245 | -6442 -13369 | 33172
+ *   d 12 709 limited 2981 10026  1012 | -1643 -5527 7170 | 7170 -6513  -657 | 256 | 19147 | 29480 | -3507  -8763 | 34737
+ * Chroma up- and down-sampling are those of the 8-bit entries (3 : 1 rows, the CENTER and LEFT column rules, clamped indices, the
+ * 16-fold U16 / V16, the box and [1 2 1] sums with their shifts).
+ * spei_yuv_to_rgb_u16: yy = cy * 16 * (Y - yo), u = U16 - (2048 << s), v = V16 - (2048 << s),
+ *   R = clip((yy + rv v + 2^17) >> 18, 0, D), G = clip((yy + gu u + gv v + 2^17) >> 18, 0, D), B = clip((yy + bu u + 2^17) >> 18, 0, D).
+ *   These sums do NOT fit int32 at 12-bit limited range (|yy + rv v| reaches 2.3e9): they are taken in 64 bits.
+ * spei_rgb_u16_to_yuv: the 8-bit expressions with `+ yo` and `+ (128 << s)` (the sums stay below 2.7e8); full range clips to [0, D],
+ *   limited range to [16 2^s, 235 2^s] (Y) and [16 2^s, 240 2^s] (U, V). */
+int spei_yuv_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout, int matrix, int range,
+                        int depth, spei_stream_t stream);
+int spei_rgb_u16_to_yuv(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
+                        spei_stream_t stream);
 
 /* ---- training on a dataset (speinet_amd/data.py, speinet_amd/fit.py) ---- */
 

@@ -225,6 +225,202 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const unsigned char* __
     }
 }
 
+// ---- deep samples (10 and 12 bits in little-endian 16-bit words) ------------------------------------------------------------------
+// The same two kernels on uint16 samples, depth d = 8 + s, D = 2^d - 1; a word above D reads as D.  Full range uses the rows of
+// COEF; limited range has rows of its own per depth (the rule is in include/speinet_hip.h).  One thread per group of 4 pixels as
+// above: 8-byte accesses of Y / U / V rows and three of them per 24-byte RGB group where base, stride and W allow, elements
+// otherwise and at the right edge.  Every product fits int32; the YUV -> RGB sums are taken in 64 bits (2.3e9 at 12-bit limited).
+constexpr Coef COEF_DEEP[2][2] = {
+    // [depth 10, 12][matrix], limited range
+    {/* 10 601 */ {4195, 8236, 1599, -2421, -4754, 7175, 7175, -6008, -1167, 64, 19133, 26226, -6438, -13359, 33148},
+     /* 10 709 */ {2983, 10034, 1013, -1644, -5531, 7175, 7175, -6517, -658, 64, 19133, 29459, -3504, -8757, 34711}},
+    {/* 12 601 */ {4192, 8229, 1598, -2420, -4750, 7170, 7170, -6004, -1166, 256, 19147, 26245, -6442, -13369, 33172},
+     /* 12 709 */ {2981, 10026, 1012, -1643, -5527, 7170, 7170, -6513, -657, 256, 19147, 29480, -3507, -8763, 34737}},
+};
+
+__device__ __forceinline__ int half_at(const uint2& w, int j) { return ((j < 2 ? w.x : w.y) >> (16 * (j & 1))) & 0xffff; }
+__device__ __forceinline__ uint2 pack4(int a, int b, int c, int d) {
+    return make_uint2((uint32_t)a | ((uint32_t)b << 16), (uint32_t)c | ((uint32_t)d << 16));
+}
+
+// 4 samples of a plane row from column x0, each at most D: one 8-byte load, or elements with the column clamped to the row
+__device__ __forceinline__ void load4(const uint16_t* __restrict__ row, int x0, int W, bool wide, int D, int (&v)[4]) {
+    if (wide) {
+        const uint2 w = *reinterpret_cast<const uint2*>(row + x0);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) v[p] = min(half_at(w, p), D);
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) v[p] = min((int)row[min(x0 + p, W - 1)], D);
+    }
+}
+
+__device__ __forceinline__ void store4(uint16_t* __restrict__ row, int x0, int W, bool wide, const int (&v)[4]) {
+    if (wide) {
+        *reinterpret_cast<uint2*>(row + x0) = pack4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if (x0 + p < W) row[x0 + p] = (uint16_t)v[p];
+    }
+}
+
+// 12 samples (R G B of 4 pixels) from p, each at most D: three 8-byte loads, or elements (pixel x0 + t / 3 clamped to column W - 1)
+__device__ __forceinline__ void load_rgb4(const uint16_t* __restrict__ row, int x0, int W, bool wide, int D, int (&c)[12]) {
+    if (wide) {
+        const uint2* p = reinterpret_cast<const uint2*>(row + x0 * 3);
+        const uint2 w[3] = {p[0], p[1], p[2]};
+#pragma unroll
+        for (int t = 0; t < 12; ++t) c[t] = min(half_at(w[t >> 2], t & 3), D);
+    } else {
+#pragma unroll
+        for (int t = 0; t < 12; ++t) c[t] = min((int)row[min(x0 + t / 3, W - 1) * 3 + t % 3], D);
+    }
+}
+
+__device__ __forceinline__ int clip_deep(int64_t v, int D) { return (int)min(max(v, (int64_t)0), (int64_t)D); }
+
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void yuv_to_rgb_u16_kernel(const uint16_t* __restrict__ src, int64_t fstride,
+                                                             uint16_t* __restrict__ dst, int H, int W, int64_t total, Coef k, int s,
+                                                             int aligned) {
+    const int gw = (W + 3) >> 2, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1, D = (256 << s) - 1;
+    const int64_t ysize = (int64_t)H * W, csize = LAYOUT == SPEI_YUV_444 ? ysize : (int64_t)Hc * Wc;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / gw;                        // n * H + y
+        const int x0 = (int)(i - row * gw) * 4;
+        const int n = (int)(row / H), y = (int)(row - (int64_t)n * H);
+        const uint16_t* f = src + n * fstride;             // fstride in samples
+        const uint16_t* up = f + ysize;
+        const uint16_t* vp = up + csize;
+        const bool wide = aligned && x0 + 4 <= W;
+        int Y[4], U16[4], V16[4];
+        load4(f + (int64_t)y * W, x0, W, wide, D, Y);
+        if (LAYOUT == SPEI_YUV_444) {
+            load4(up + (int64_t)y * W, x0, W, wide, D, U16);
+            load4(vp + (int64_t)y * W, x0, W, wide, D, V16);
+#pragma unroll
+            for (int p = 0; p < 4; ++p) { U16[p] *= 16; V16[p] *= 16; }
+        } else {
+            const int j = y >> 1, jo = clip((y & 1) ? j + 1 : j - 1, 0, Hc - 1), i0 = x0 >> 1;
+            const int64_t rj = (int64_t)j * Wc, ro = (int64_t)jo * Wc;
+            int u[4], v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = clip(i0 - 1 + q, 0, Wc - 1);
+                u[q] = 3 * min((int)up[rj + c], D) + min((int)up[ro + c], D);
+                v[q] = 3 * min((int)vp[rj + c], D) + min((int)vp[ro + c], D);
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int a = 1 + (p >> 1);                // column i = x >> 1
+                if (LAYOUT == SPEI_YUV_420_CENTER) {
+                    const int b = (p & 1) ? a + 1 : a - 1;
+                    U16[p] = 3 * u[a] + u[b];
+                    V16[p] = 3 * v[a] + v[b];
+                } else {
+                    U16[p] = (p & 1) ? 2 * (u[a] + u[a + 1]) : 4 * u[a];
+                    V16[p] = (p & 1) ? 2 * (v[a] + v[a + 1]) : 4 * v[a];
+                }
+            }
+        }
+        int q[12];                                         // R G B of 4 pixels
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            // int32 products (at most 1.3e9), 64-bit sums
+            const int u = U16[p] - (2048 << s), v = V16[p] - (2048 << s);
+            const int64_t yy = (int64_t)(k.cy * 16 * (Y[p] - k.yo)) + (1 << 17);
+            q[3 * p + 0] = clip_deep((yy + k.rv * v) >> 18, D);
+            q[3 * p + 1] = clip_deep((yy + (k.gu * u + k.gv * v)) >> 18, D);
+            q[3 * p + 2] = clip_deep((yy + k.bu * u) >> 18, D);
+        }
+        uint16_t* d = dst + (row * W + x0) * 3;
+        if (wide) {                                        // 24 bytes as three 8-byte stores
+            uint2* o = reinterpret_cast<uint2*>(d);
+            o[0] = pack4(q[0], q[1], q[2], q[3]);
+            o[1] = pack4(q[4], q[5], q[6], q[7]);
+            o[2] = pack4(q[8], q[9], q[10], q[11]);
+        } else {
+#pragma unroll
+            for (int t = 0; t < 12; ++t)
+                if (x0 + t / 3 < W) d[t] = (uint16_t)q[t];
+        }
+    }
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void rgb_u16_to_yuv_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, int H, int W,
+                                                             int64_t total, Coef k, int limited, int s, int al_src, int al_y, int al_c) {
+    const int gw = (W + 3) >> 2, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1, D = (256 << s) - 1, mid = 128 << s;
+    const int64_t ysize = (int64_t)H * W, csize = LAYOUT == SPEI_YUV_444 ? ysize : (int64_t)Hc * Wc;
+    const int ylo = limited ? 16 << s : 0, yhi = limited ? 235 << s : D, clo = ylo, chi = limited ? 240 << s : D;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int y = (int)(i / gw), g = (int)(i - (int64_t)y * gw), x0 = g * 4;
+        const uint16_t* r0 = src + (int64_t)y * W * 3;
+        int c[12];                                         // R G B of 4 pixels
+        load_rgb4(r0, x0, W, al_src && x0 + 4 <= W, D, c);
+        int Y[4], U[4], V[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int R = c[3 * p], G = c[3 * p + 1], B = c[3 * p + 2];
+            Y[p] = clip(((k.yr * R + k.yg * G + k.yb * B + (1 << 13)) >> 14) + k.yo, ylo, yhi);
+            if (LAYOUT == SPEI_YUV_444) {
+                U[p] = clip(((k.ur * R + k.ug * G + k.ub * B + (1 << 13)) >> 14) + mid, clo, chi);
+                V[p] = clip(((k.vr * R + k.vg * G + k.vb * B + (1 << 13)) >> 14) + mid, clo, chi);
+            }
+        }
+        const bool wide = al_y && x0 + 4 <= W;
+        store4(dst + (int64_t)y * W, x0, W, wide, Y);
+        if (LAYOUT == SPEI_YUV_444) {
+            store4(dst + ysize + (int64_t)y * W, x0, W, wide, U);
+            store4(dst + 2 * ysize + (int64_t)y * W, x0, W, wide, V);
+        } else if (!(y & 1) && !(g & 1)) {
+            // chroma samples (j, i0 .. i0 + 3) of rows y, y + 1 and columns x0 .. x0 + 7: sm[ch][q] is the sum over the two rows of
+            // channel ch at column x0 - 1 + q, rows and columns clamped to the frame (q = 0 is LEFT's left neighbour)
+            const int j = y >> 1, i0 = x0 >> 1;
+            const uint16_t* r1 = src + (int64_t)min(y + 1, H - 1) * W * 3;
+            int sm[3][9];
+            if (al_src && x0 + 8 <= W) {
+                int a[12], b[12];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    load_rgb4(r0, x0 + 4 * h, W, true, D, a);
+                    load_rgb4(r1, x0 + 4 * h, W, true, D, b);
+#pragma unroll
+                    for (int t = 0; t < 12; ++t) sm[t % 3][1 + 4 * h + t / 3] = a[t] + b[t];
+                }
+                const int xl = max(x0 - 1, 0) * 3;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch)
+                    sm[ch][0] = LAYOUT == SPEI_YUV_420_LEFT ? min((int)r0[xl + ch], D) + min((int)r1[xl + ch], D) : 0;
+            } else {
+#pragma unroll
+                for (int q = 0; q < 9; ++q) {
+                    const int x = clip(x0 - 1 + q, 0, W - 1) * 3;
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) sm[ch][q] = min((int)r0[x + ch], D) + min((int)r1[x + ch], D);
+                }
+            }
+            int Uc[4], Vc[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                int S[3];
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch)
+                    S[ch] = LAYOUT == SPEI_YUV_420_CENTER ? sm[ch][1 + 2 * m] + sm[ch][2 + 2 * m]
+                                                          : sm[ch][2 * m] + 2 * sm[ch][1 + 2 * m] + sm[ch][2 + 2 * m];
+                constexpr int SH = LAYOUT == SPEI_YUV_420_CENTER ? 16 : 17;
+                Uc[m] = clip(((k.ur * S[0] + k.ug * S[1] + k.ub * S[2] + (1 << (SH - 1))) >> SH) + mid, clo, chi);
+                Vc[m] = clip(((k.vr * S[0] + k.vg * S[1] + k.vb * S[2] + (1 << (SH - 1))) >> SH) + mid, clo, chi);
+            }
+            uint16_t* uo = dst + ysize + (int64_t)j * Wc;
+            const bool cwide = al_c && i0 + 4 <= Wc;
+            store4(uo, i0, Wc, cwide, Uc);
+            store4(uo + csize, i0, Wc, cwide, Vc);
+        }
+    }
+}
+
 inline int grid_for(int64_t total) { return (int)((total + 255) / 256 < BLOCKS_MAX ? (total + 255) / 256 : BLOCKS_MAX); }
 
 inline int64_t planar_bytes(int H, int W, int layout) {
@@ -235,6 +431,10 @@ inline int64_t planar_bytes(int H, int W, int layout) {
 inline bool known(int layout, int matrix, int range) {
     return (layout == SPEI_YUV_420_CENTER || layout == SPEI_YUV_420_LEFT || layout == SPEI_YUV_444) &&
            (matrix == SPEI_YUV_BT601 || matrix == SPEI_YUV_BT709) && (range == SPEI_YUV_FULL || range == SPEI_YUV_LIMITED);
+}
+
+inline Coef deep_coef(int depth, int matrix, int range) {
+    return range == SPEI_YUV_FULL ? COEF[matrix][0] : COEF_DEEP[depth == 12][matrix];
 }
 
 }  // namespace
@@ -289,5 +489,65 @@ extern "C" int spei_rgb_u8_to_yuv(const unsigned char* src, unsigned char* dst, 
         hipLaunchKernelGGL(rgb_to_yuv_kernel<SPEI_YUV_444>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k, limited, al_src,
                            al_y, al_c);
     SPEI_CHECK_LAUNCH("spei_rgb_u8_to_yuv");
+    return 0;
+}
+
+extern "C" int spei_yuv_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout, int matrix,
+                                   int range, int depth, spei_stream_t stream) {
+    SPEI_REQUIRE(src && dst, "spei_yuv_to_rgb_u16: null pointer");
+    SPEI_REQUIRE(N >= 1 && H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "spei_yuv_to_rgb_u16: bad frame shape %d x %dx%d", N, H, W);
+    SPEI_REQUIRE(known(layout, matrix, range), "spei_yuv_to_rgb_u16: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", layout, matrix,
+                 range);
+    SPEI_REQUIRE(depth == 10 || depth == 12, "spei_yuv_to_rgb_u16: unknown depth %d (10 or 12)", depth);
+    SPEI_REQUIRE(N == 1 || frame_stride >= 2 * planar_bytes(H, W, layout), "spei_yuv_to_rgb_u16: frame stride %lld < one %dx%d planar "
+                 "frame of %lld bytes", (long long)frame_stride, H, W, (long long)(2 * planar_bytes(H, W, layout)));
+    SPEI_REQUIRE(N == 1 || (frame_stride & 1) == 0, "spei_yuv_to_rgb_u16: odd frame stride %lld (bytes, a multiple of 2)",
+                 (long long)frame_stride);
+    SPEI_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 1) == 0, "spei_yuv_to_rgb_u16: src and dst must be 2-byte aligned");
+    const int aligned = (((uintptr_t)src | (uintptr_t)dst) & 7) == 0 && (N == 1 || (frame_stride & 7) == 0) && (W & 3) == 0;
+    const int64_t total = (int64_t)N * H * ((W + 3) / 4), fstride = N == 1 ? 0 : frame_stride / 2;
+    const Coef k = deep_coef(depth, matrix, range);
+    const int s = depth - 8;
+    const dim3 grid(grid_for(total)), block(256);
+    if (layout == SPEI_YUV_420_CENTER)
+        hipLaunchKernelGGL(yuv_to_rgb_u16_kernel<SPEI_YUV_420_CENTER>, grid, block, 0, (hipStream_t)stream, src, fstride, dst, H, W, total,
+                           k, s, aligned);
+    else if (layout == SPEI_YUV_420_LEFT)
+        hipLaunchKernelGGL(yuv_to_rgb_u16_kernel<SPEI_YUV_420_LEFT>, grid, block, 0, (hipStream_t)stream, src, fstride, dst, H, W, total, k,
+                           s, aligned);
+    else
+        hipLaunchKernelGGL(yuv_to_rgb_u16_kernel<SPEI_YUV_444>, grid, block, 0, (hipStream_t)stream, src, fstride, dst, H, W, total, k, s,
+                           aligned);
+    SPEI_CHECK_LAUNCH("spei_yuv_to_rgb_u16");
+    return 0;
+}
+
+extern "C" int spei_rgb_u16_to_yuv(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
+                                   spei_stream_t stream) {
+    SPEI_REQUIRE(src && dst, "spei_rgb_u16_to_yuv: null pointer");
+    SPEI_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "spei_rgb_u16_to_yuv: bad frame shape %dx%d", H, W);
+    SPEI_REQUIRE(known(layout, matrix, range), "spei_rgb_u16_to_yuv: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", layout, matrix,
+                 range);
+    SPEI_REQUIRE(depth == 10 || depth == 12, "spei_rgb_u16_to_yuv: unknown depth %d (10 or 12)", depth);
+    SPEI_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 1) == 0, "spei_rgb_u16_to_yuv: src and dst must be 2-byte aligned");
+    // rows of 6 W, 2 W and 2 ceil(W/2) bytes: 8-byte aligned when W % 4 == 0 (RGB, Y, and the 4:4:4 planes) and, for the 4:2:0 chroma
+    // planes, when W % 8 == 0
+    const int al_src = ((uintptr_t)src & 7) == 0 && (W & 3) == 0;
+    const int al_y = ((uintptr_t)dst & 7) == 0 && (W & 3) == 0;
+    const int al_c = ((uintptr_t)dst & 7) == 0 && (W & 7) == 0;
+    const int64_t total = (int64_t)H * ((W + 3) / 4);
+    const Coef k = deep_coef(depth, matrix, range);
+    const int limited = range == SPEI_YUV_LIMITED, s = depth - 8;
+    const dim3 grid(grid_for(total)), block(256);
+    if (layout == SPEI_YUV_420_CENTER)
+        hipLaunchKernelGGL(rgb_u16_to_yuv_kernel<SPEI_YUV_420_CENTER>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k,
+                           limited, s, al_src, al_y, al_c);
+    else if (layout == SPEI_YUV_420_LEFT)
+        hipLaunchKernelGGL(rgb_u16_to_yuv_kernel<SPEI_YUV_420_LEFT>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k, limited,
+                           s, al_src, al_y, al_c);
+    else
+        hipLaunchKernelGGL(rgb_u16_to_yuv_kernel<SPEI_YUV_444>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k, limited, s,
+                           al_src, al_y, al_c);
+    SPEI_CHECK_LAUNCH("spei_rgb_u16_to_yuv");
     return 0;
 }

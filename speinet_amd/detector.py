@@ -114,8 +114,9 @@ def clip_batches(fr, device, batch: int = DETECT_BATCH):
     """One streaming pass over a clip (`video.frames_of`'s result): yields (first frame index, uint8 [n,H,W,3] device view) for every
     `batch` frames in turn, on the current stream of `device`.  Host frames are uploaded from two page-locked staging buffers (image
     paths decoded on worker threads two batches ahead), device-resident frames copied on the device.  The frames of a y4m clip are
-    staged and uploaded as their planar bytes and made RGB on the device (`fr.rgb`: ops.yuv_to_rgb_u8).  The view is of ONE buffer
-    that the next batch overwrites: device memory is bounded by one batch.  The consumer sets grad mode and the current device."""
+    staged and uploaded as their planar bytes and made RGB on the device (`fr.rgb`: ops.yuv_to_rgb_u8, or ops.yuv_to_rgb_u16 for a
+    deep clip).  A deep clip (`fr.depth` 10 or 12) yields uint16 frames: its samples never pass through 8 bits.  The view is of ONE
+    buffer that the next batch overwrites: device memory is bounded by one batch.  The consumer sets grad mode and the current device."""
     dev, B = torch.device(device), batch
     T, H, W = fr.T, fr.H, fr.W
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as pool:
@@ -127,9 +128,9 @@ def clip_batches(fr, device, batch: int = DETECT_BATCH):
                     futs[i] = pool.submit(fr.host, i)
 
         shape = (B, H, W, 3) if fr.yuv is None else (B, fr.items.frame_bytes)
-        stage = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        stage = [torch.empty(shape, dtype=fr.dtype if fr.yuv is None else torch.uint8, pin_memory=True) for _ in range(2)]
         events = [None, None]
-        dev_batch = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+        dev_batch = torch.empty(B, H, W, 3, dtype=fr.dtype, device=dev)
         dev_planar = None if fr.yuv is None else torch.empty(shape, dtype=torch.uint8, device=dev)
         for b, i0 in enumerate(range(0, T, B)):
             n = min(B, T - i0)
@@ -157,7 +158,8 @@ def clip_batches(fr, device, batch: int = DETECT_BATCH):
 def clip_pass(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, features: bool = True, pair_stats: bool = False):
     """One `clip_batches` pass over a clip that yields the six focus measures of every frame ([T,6] float32, or None when not
     `features`), the pair statistics of `ops.frame_pair_stats` over the whole clip ((sad int64 [T-1], hist int64 [T,64]), or None when
-    not `pair_stats`), or both, all on `device`.  The last frame of a batch is kept as `prev` of the next, so a pair that straddles two
+    not `pair_stats`), or both, all on `device`.  A deep clip goes through `ops.frames_u16_in` and `ops.frame_pair_stats_u16` (its
+    sad is in units of the clip's own depth).  The last frame of a batch is kept as `prev` of the next, so a pair that straddles two
     batches is counted like any other: device memory is bounded by one batch plus one frame."""
     from . import ops
     dev = torch.device(device)
@@ -167,10 +169,16 @@ def clip_pass(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, feat
     with torch.no_grad(), torch.cuda.device(dev):
         for i0, frames in clip_batches(fr, dev, batch):
             if features:
-                _, gray = ops.frames_u8_in(frames, gray=True, planes=False)
+                if fr.depth == 8:
+                    _, gray = ops.frames_u8_in(frames, gray=True, planes=False)
+                else:
+                    _, gray = ops.frames_u16_in(frames, fr.depth, gray=True, planes=False)
                 feats.append(gray_focus_measures(gray, kernel_size))
             if pair_stats:
-                sad, hist = ops.frame_pair_stats(frames, prev if i0 else None)
+                if fr.depth == 8:
+                    sad, hist = ops.frame_pair_stats(frames, prev if i0 else None)
+                else:
+                    sad, hist = ops.frame_pair_stats_u16(frames, fr.depth, prev if i0 else None)
                 sads.append(sad)
                 hists.append(hist)
                 if i0 + len(frames) < fr.T:

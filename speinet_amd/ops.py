@@ -248,6 +248,61 @@ def frame_pair_stats(u8: torch.Tensor, prev: Optional[torch.Tensor] = None):
     return sad, hist.long()
 
 
+def _depth(depth: int) -> int:
+    if depth not in (10, 12):
+        raise ValueError(f"depth must be 10 or 12 (bits per sample in uint16 words), got {depth!r}")
+    return int(depth)
+
+
+def frames_u16_in(u16: torch.Tensor, depth: int, out: Optional[torch.Tensor] = None, gray: bool = False, planes: bool = True):
+    """`frames_u8_in` for deep frames: uint16 [N,H,W,3] (or one [H,W,3]; each frame packed, any frame stride) of `depth` 10 or 12 bits,
+    D = 2^depth - 1 (a word above D reads as D) -> (fp32 [N,3,Hp,Wp] = v * float32(1 / D), reflect-padded, or None when not `planes`;
+    the detector's gray plane [N,H,W] of the frames as fp32 v * float32(255 / D), or None when not `gray`).  One launch on the
+    current stream (csrc/frame_io.hip)."""
+    assert u16.is_cuda and u16.dtype == torch.uint16 and u16.dim() in (3, 4) and (planes or gray)
+    depth = _depth(depth)
+    fr = u16 if u16.dim() == 4 else u16.unsqueeze(0)
+    n, h, w, c = fr.shape
+    assert c == 3 and fr.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
+    hp, wp = padded_size(h), padded_size(w)
+    dev = u16.device
+    if planes:
+        if out is None:
+            out = torch.empty(n, 3, hp, wp, device=dev)
+        assert out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * 3 * hp * wp
+    else:
+        out = None
+    g = torch.empty(n, h, w, device=dev) if gray else None
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_frames_u16_in(_vp(fr.data_ptr()), 2 * fr.stride(0), _vp(out.data_ptr() if out is not None else 0),
+                                          _vp(g.data_ptr() if g is not None else 0), n, h, w, depth, st), "spei_frames_u16_in")
+    return out, g
+
+
+def frame_pair_stats_u16(u16: torch.Tensor, depth: int, prev: Optional[torch.Tensor] = None):
+    """`frame_pair_stats` for deep frames: uint16 [N,H,W,3] of `depth` 10 or 12 bits (and optionally the packed frame `prev` before
+    them), on the depth-bit luma Yd = (77 R + 150 G + 29 B + 128) >> 8 -> (sad int64 over Yd, 2^(depth-8) times the 8-bit unit;
+    hist int64 [N,64]: pixels per value of Yd >> (depth - 6)).  Exact integers.  One launch on the current stream, no host sync."""
+    assert u16.is_cuda and u16.dtype == torch.uint16 and u16.dim() == 4
+    depth = _depth(depth)
+    n, h, w, c = u16.shape
+    assert c == 3 and u16.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
+    dev = u16.device
+    assert prev is None or (prev.device == dev and prev.dtype == torch.uint16 and tuple(prev.shape) == (h, w, 3) and prev.is_contiguous())
+    pairs = n if prev is not None else n - 1
+    hist = torch.empty(n, 64, dtype=torch.int32, device=dev)
+    sad = torch.empty(pairs, dtype=torch.int64, device=dev)
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_frame_pair_stats_u16(_vp(u16.data_ptr()), 2 * u16.stride(0), _vp(prev.data_ptr() if prev is not None else 0),
+                                                 n, h, w, depth, _vp(hist.data_ptr()), _vp(sad.data_ptr()), st),
+                   "spei_frame_pair_stats_u16")
+    return sad, hist.long()
+
+
 def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: Optional[torch.Tensor] = None,
                    gt: Optional[torch.Tensor] = None):
     """The reference's blur synthesis on resident frames (csrc/blurset.hip): uint8 frames [T,H,W,3] on the device (each frame packed,
@@ -295,6 +350,26 @@ def frame_u8_out(x: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = 
     return out
 
 
+def frame_u16_out(x: torch.Tensor, h: int, w: int, depth: int, out: Optional[torch.Tensor] = None,
+                  nonfinite: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`frame_u8_out` for deep frames: fp32 [3,Hp,Wp] on the device -> its top-left h x w crop as uint16 [h,w,3] of `depth` 10 or 12
+    bits, round_half_even(clamp(x * D, 0, D)) with D = 2^depth - 1, 0 for a non-finite value.  `out` (optional): a packed uint16
+    [h,w,3] destination.  `nonfinite`: as in `frame_u8_out`.  Launches on the current stream (csrc/frame_io.hip), no host sync."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 3 and x.is_contiguous()
+    depth = _depth(depth)
+    hp, wp = x.shape[1:]
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=torch.uint16, device=x.device)
+    assert out.device == x.device and out.dtype == torch.uint16 and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
+    assert nonfinite is None or (nonfinite.device == x.device and nonfinite.dtype == torch.int32 and nonfinite.numel() >= 1)
+    lib = _lib.lib()
+    with torch.cuda.device(x.device):
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(lib.spei_frame_u16_out(_vp(x.data_ptr()), _vp(out.data_ptr()), _vp(nonfinite.data_ptr() if nonfinite is not None else 0),
+                                          h, w, hp, wp, depth, st), "spei_frame_u16_out")
+    return out
+
+
 def yuv_frame_bytes(h: int, w: int, layout: int) -> int:
     """Bytes of one planar YUV frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0, [h][w] each for 4:4:4."""
     return y4m.frame_bytes(h, w, layout)
@@ -338,6 +413,49 @@ def rgb_u8_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, out: 
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(lib.spei_rgb_u8_to_yuv(_vp(rgb.data_ptr()), _vp(out.data_ptr()), h, w, layout, matrix, range, st),
                    "spei_rgb_u8_to_yuv")
+    return out
+
+
+def yuv_to_rgb_u16(planar: torch.Tensor, h: int, w: int, layout: int, matrix: int, range: int, depth: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`yuv_to_rgb_u8` for deep frames: planar uint16 YUV frames of `depth` 10 or 12 bits on the device, [N, frame samples] (rows any
+    stride apart) or one [frame samples] (`yuv_frame_bytes(h, w, layout)` samples: a deep y4m FRAME payload viewed as uint16) ->
+    packed RGB uint16 [N,h,w,3] (csrc/yuv_io.hip; the deep rule of include/speinet_hip.h).  `out` (optional): a contiguous uint16
+    [N,h,w,3] destination.  One launch on the current stream, no host sync."""
+    assert planar.is_cuda and planar.dtype == torch.uint16 and planar.dim() in (1, 2)
+    depth = _depth(depth)
+    fr = planar if planar.dim() == 2 else planar.unsqueeze(0)
+    n, ns = fr.shape
+    assert ns == yuv_frame_bytes(h, w, layout) and fr.stride(1) == 1, "frames must be packed planar frames (any frame stride)"
+    dev = planar.device
+    if out is None:
+        out = torch.empty(n, h, w, 3, dtype=torch.uint16, device=dev)
+    assert out.device == dev and out.dtype == torch.uint16 and tuple(out.shape) == (n, h, w, 3) and out.is_contiguous()
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_yuv_to_rgb_u16(_vp(fr.data_ptr()), 2 * fr.stride(0), _vp(out.data_ptr()), n, h, w, layout, matrix, range, depth,
+                                           st), "spei_yuv_to_rgb_u16")
+    return out
+
+
+def rgb_u16_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, depth: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`rgb_u8_to_yuv` for deep frames: one packed RGB uint16 frame [h,w,3] of `depth` 10 or 12 bits on the device -> its planar YUV
+    frame, uint16 [frame samples], whose bytes are a deep y4m FRAME payload.  `out` (optional): a contiguous uint16 destination.
+    One launch on the current stream, no host sync."""
+    assert rgb.is_cuda and rgb.dtype == torch.uint16 and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.is_contiguous()
+    depth = _depth(depth)
+    h, w = rgb.shape[:2]
+    ns = yuv_frame_bytes(h, w, layout)
+    dev = rgb.device
+    if out is None:
+        out = torch.empty(ns, dtype=torch.uint16, device=dev)
+    assert out.device == dev and out.dtype == torch.uint16 and tuple(out.shape) == (ns,) and out.is_contiguous()
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_rgb_u16_to_yuv(_vp(rgb.data_ptr()), _vp(out.data_ptr()), h, w, layout, matrix, range, depth, st),
+                   "spei_rgb_u16_to_yuv")
     return out
 
 

@@ -1,9 +1,10 @@
-"""The clip loop: deblur a clip of uint8 frames of any size (at least 20x20), with or without sharpness labels.  The library API is
+"""The clip loop: deblur a clip of uint8 (or 10- / 12-bit uint16) frames of any size (at least 20x20), with or without sharpness labels.  The library API is
 `deblur_clip`; the command line, for the user's own footage (no ground truth), is
 
     python -m speinet_amd.video --input <dir | glob | clip.y4m | -> --output <dir | out.y4m | -> --model_path <checkpoint | synthetic>
                                 [--labels <file.npy>] [--detector <detector.json>] [--cuts none|auto|<file>]
                                 [--matrix bt601|bt709] [--range full|limited] [--fps num:den] [--chroma 420jpeg|420mpeg2|444]
+                                [--out_depth 8|10|12]
 
 (`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; stdin is spooled to a temporary file
 on disk before the first frame is deblurred, see `main`)
@@ -21,7 +22,11 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
   * frames cross PCIe as uint8 from page-locked staging buffers (`FrameCache`) and are decoded, for image paths, on worker threads a
     few windows ahead; a window whose 16-bit pass left a non-finite value is recomputed in bf16x3;
   * a y4m clip (speinet_amd.y4m) crosses PCIe as its planar bytes, 1.5 per pixel for 4:2:0, and becomes packed RGB on the device
-    (csrc/yuv_io.hip, integer arithmetic); a y4m output is made there from the deblurred frame the same way.
+    (csrc/yuv_io.hip, integer arithmetic); a y4m output is made there from the deblurred frame the same way;
+  * a deep clip (10 or 12 bits per sample: a `C420p10` ... `C444p12` y4m stream, or uint16 frames with `depth=`) never passes through
+    8 bits: its bytes cross PCIe through the same page-locked rings, the labelling pass, the scene statistics and the window loop
+    read uint16 frames (`ops.frames_u16_in`, `ops.frame_pair_stats_u16`), and the deblurred frame is quantised once, to `out_depth`
+    (`ops.frame_u16_out`).  Image files stay 8-bit.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -96,7 +101,7 @@ class FrameCache:
             self.items.popitem(last=False)
 
     def _upload(self, arr: np.ndarray) -> torch.Tensor:
-        n = arr.size
+        n = arr.nbytes
         if not self._ring or self._ring[0].numel() < n:
             self._ring = [torch.empty(n, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
             self._events = [None] * self.RING
@@ -104,7 +109,10 @@ class FrameCache:
         self._n += 1
         if self._events[i] is not None:
             self._events[i].synchronize()                 # the copy issued RING uploads ago: long finished
-        stage = self._ring[i][:n].view(arr.shape)
+        stage = self._ring[i][:n]
+        if arr.dtype == np.uint16:                        # a deep frame crosses as its bytes
+            stage = stage.view(torch.uint16)
+        stage = stage.view(arr.shape)
         stage.numpy()[...] = arr
         t = stage.to(self.device, non_blocking=True)
         self._events[i] = torch.cuda.Event()
@@ -175,10 +183,12 @@ class _Frames:
     """The clip behind one interface: frame i as a host uint8 [H,W,3] array (`host`) or a device tensor (`device`), cropped at the
     bottom and right to H x W (`crop`: the source size rounded down to multiples of 20; otherwise the source size).  A y4m clip
     (`yuv`: its (layout, matrix, range); `items` the `Y4MReader`) is the exception: `host` returns the frame's planar bytes as they
-    are in the file, and `rgb` turns uploaded planar frames into the cropped RGB frames on the device."""
+    are in the file, and `rgb` turns uploaded planar frames into the cropped RGB frames on the device.  `depth`: 8 (uint8 frames), or
+    10 / 12 (uint16 frames: `dtype`; the planar bytes of a deep y4m clip are still uint8, two per sample)."""
 
-    def __init__(self, items, T: int, H: int, W: int, paths: bool, crop: bool = False, yuv=None):
-        self.items, self.T, self.paths, self.src, self.yuv = items, T, paths, (H, W), yuv
+    def __init__(self, items, T: int, H: int, W: int, paths: bool, crop: bool = False, yuv=None, depth: int = 8):
+        self.items, self.T, self.paths, self.src, self.yuv, self.depth = items, T, paths, (H, W), yuv, depth
+        self.dtype = torch.uint8 if depth == 8 else torch.uint16
         self.H, self.W = (H - H % 20, W - W % 20) if crop else (H, W)
 
     def on_device(self, i: int) -> bool:
@@ -188,11 +198,19 @@ class _Frames:
         return torch.is_tensor(f) and f.is_cuda
 
     def rgb(self, planar: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Planar frames [N, frame_bytes] of a y4m clip on the device -> uint8 [N,H,W,3] there (`ops.yuv_to_rgb_u8`; cropped after
-        the conversion), into the contiguous `out` if given."""
+        """Planar frames [N, frame_bytes] (uint8: the file's bytes) of a y4m clip on the device -> uint8 [N,H,W,3] there
+        (`ops.yuv_to_rgb_u8`), or uint16 for a deep clip (`ops.yuv_to_rgb_u16` on the bytes viewed as words); cropped after the
+        conversion, into the contiguous `out` if given."""
+        if self.depth == 8:
+            convert = ops.yuv_to_rgb_u8
+        else:
+            planar = planar.view(torch.uint16)
+
+            def convert(p, h, w, *how, out=None):
+                return ops.yuv_to_rgb_u16(p, h, w, *how, self.depth, out=out)
         if (self.H, self.W) == self.src:
-            return ops.yuv_to_rgb_u8(planar, self.H, self.W, *self.yuv, out=out)
-        full = ops.yuv_to_rgb_u8(planar, *self.src, *self.yuv)[:, :self.H, :self.W]
+            return convert(planar, self.H, self.W, *self.yuv, out=out)
+        full = convert(planar, *self.src, *self.yuv)[:, :self.H, :self.W]
         return full.contiguous() if out is None else out.copy_(full)
 
     def device(self, i: int) -> torch.Tensor:
@@ -211,27 +229,38 @@ class _Frames:
         return img[:self.H, :self.W]
 
 
-def _check_frame(i, shape, dtype) -> None:
-    if dtype not in (np.uint8, torch.uint8):
-        raise ValueError(f"frames must be uint8; frame {i} is {dtype}")
+def _check_frame(i, shape, dtype, depth=None) -> None:
+    if dtype in (np.uint16, torch.uint16):
+        if depth is None:
+            raise ValueError(f"uint16 frames need depth=10 or depth=12 (bits per sample); frame {i} is {dtype}")
+    elif depth is not None:
+        raise ValueError(f"depth= applies to uint16 frames only; frame {i} is {dtype}")
+    elif dtype not in (np.uint8, torch.uint8):
+        raise ValueError(f"frames must be uint8, or uint16 with depth=; frame {i} is {dtype}")
     if len(shape) != 3 or shape[2] != 3:
         raise ValueError(f"frames must be 3-channel HWC arrays [H,W,3]; frame {i} has shape {tuple(shape)}")
     if shape[0] < MIN_SIZE or shape[1] < MIN_SIZE:
         raise ValueError(f"frames must be at least {MIN_SIZE}x{MIN_SIZE}; frame {i} is {shape[1]}x{shape[0]}")
 
 
-def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None) -> _Frames:
+def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None, depth: Optional[int] = None) -> _Frames:
     """Validate a clip: a uint8 [T,H,W,3] array or tensor (host or device), a list of uint8 [H,W,3] arrays / tensors, a list of
     image paths (only their headers are read here), or a `y4m.Y4MReader` (`yuv`: optional `matrix` / `range` in place of the
-    reader's).  Raises ValueError with the reason."""
+    reader's; a reader opened with `depths=(8, 10, 12)` may hold a deep clip).  uint16 arrays, tensors or lists of them are deep
+    frames and need `depth` = 10 or 12 (bits per sample; a word above 2^depth - 1 reads as that); `depth` with anything else is an
+    error.  Raises ValueError with the reason."""
+    if depth is not None and (isinstance(depth, bool) or depth not in (10, 12)):
+        raise ValueError(f"depth must be 10 or 12, got {depth!r}")
     if isinstance(frames, y4m.Y4MReader):
+        if depth is not None:
+            raise ValueError("depth= applies to uint16 frames only: a y4m clip carries its own")
         if set(yuv or {}) - {"matrix", "range"}:
             raise ValueError(f"yuv holds {sorted(set(yuv) - {'matrix', 'range'})}: it takes matrix and range")
         if len(frames) < 2:
             raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {len(frames)}")
         _check_frame(0, (frames.height, frames.width, 3), np.uint8)
         how = (frames.layout, y4m.matrix_of((yuv or {}).get("matrix", frames.matrix)), y4m.range_of((yuv or {}).get("range", frames.range)))
-        return _Frames(frames, len(frames), frames.height, frames.width, paths=False, crop=crop, yuv=how)
+        return _Frames(frames, len(frames), frames.height, frames.width, paths=False, crop=crop, yuv=how, depth=frames.depth)
     if yuv is not None:
         raise ValueError("yuv= applies to y4m clips only")
     if isinstance(frames, (str, bytes)) or not hasattr(frames, "__len__") or not hasattr(frames, "__getitem__"):
@@ -242,13 +271,15 @@ def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None) -> _Frames
     if isinstance(frames, (np.ndarray, torch.Tensor)):
         if frames.ndim != 4:
             raise ValueError(f"a frame array must be [T,H,W,3]; got shape {tuple(frames.shape)}")
-        _check_frame(0, tuple(frames.shape[1:]), frames.dtype)
-        return _Frames(frames, T, int(frames.shape[1]), int(frames.shape[2]), paths=False, crop=crop)
+        _check_frame(0, tuple(frames.shape[1:]), frames.dtype, depth)
+        return _Frames(frames, T, int(frames.shape[1]), int(frames.shape[2]), paths=False, crop=crop, depth=depth or 8)
     items = list(frames)
     is_path = [isinstance(f, (str, os.PathLike)) for f in items]
     if any(is_path) and not all(is_path):
         raise ValueError("frames mixes image paths and arrays")
     if all(is_path):
+        if depth is not None:
+            raise ValueError("depth= applies to uint16 frames only: image files are read as 8-bit")
         from PIL import Image
         sizes = []
         for p in items:
@@ -262,10 +293,10 @@ def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None) -> _Frames
     for i, f in enumerate(items):
         if not isinstance(f, (np.ndarray, torch.Tensor)):
             raise ValueError(f"frame {i} is a {type(f).__name__}, not an array, tensor or image path")
-        _check_frame(i, tuple(f.shape), f.dtype)
+        _check_frame(i, tuple(f.shape), f.dtype, depth)
         if tuple(f.shape) != tuple(items[0].shape):
             raise ValueError(f"mixed frame sizes: frame 0 is {items[0].shape[1]}x{items[0].shape[0]}, frame {i} is {f.shape[1]}x{f.shape[0]}")
-    return _Frames(items, T, int(items[0].shape[0]), int(items[0].shape[1]), paths=False, crop=crop)
+    return _Frames(items, T, int(items[0].shape[0]), int(items[0].shape[1]), paths=False, crop=crop, depth=depth or 8)
 
 
 def labels_of(labels, T: int) -> np.ndarray:
@@ -329,10 +360,17 @@ def find_cuts(sad, hist, pixels: int, *, hist_min: float = 0.25, ratio: float = 
 def scene_stats(frames, device):
     """The pair statistics of a clip (anything `frames_of` accepts) in one streaming pass of DETECT_BATCH frames at a time on `device`
     (`detector.clip_pass`: the labelling pass's uploader; `ops.frame_pair_stats` per batch, the last frame of a batch carried over as
-    `prev` of the next): (sad int64 [T-1], hist int64 [T,64]) as numpy arrays, the input of `find_cuts`."""
+    `prev` of the next): (sad int64 [T-1], hist int64 [T,64]) as numpy arrays, the input of `find_cuts`.  A deep clip (a `_Frames`
+    of `frames_of(..., depth=)`, or a deep y4m reader) goes through `ops.frame_pair_stats_u16`, and its sad comes back divided by
+    2^(depth-8), as float64, so that `find_cuts`' `min_delta` keeps its 8-bit unit."""
     fr = frames if isinstance(frames, _Frames) else frames_of(frames)
     sad, hist = detector.clip_pass(fr, device, batch=DETECT_BATCH, features=False, pair_stats=True)[1]
-    return sad.cpu().numpy(), hist.cpu().numpy()
+    return _sad_8bit(sad.cpu().numpy(), fr.depth), hist.cpu().numpy()
+
+
+def _sad_8bit(sad: np.ndarray, depth: int) -> np.ndarray:
+    """The pair SAD of a clip of `depth` bits in the 8-bit unit of `find_cuts`' `min_delta` (an exact division by a power of 2)."""
+    return sad if depth == 8 else sad / float(1 << (depth - 8))
 
 
 def _scene_plan(labels, n_seq: int, numbers) -> list:
@@ -379,14 +417,18 @@ def _lanes(model, device, n: int) -> list:
 
 
 class ClipRun:
-    """Iterator of (index, uint8 [H,W,3] device tensor) in frame order; see `deblur_clip`.  `labels` (0/1 per frame; computed on first
+    """Iterator of (index, [H,W,3] device tensor) in frame order, uint8 for `out_depth` 8 and uint16 for 10 and 12; see `deblur_clip`.
+    `depth` is the clip's sample depth (8, 10 or 12), `out_depth` that of the frames handed out.  `labels` (0/1 per frame; computed on first
     access when the caller gave none), `cuts` (the scene cuts in use; found on first access when the caller asked for "auto", in the
     labelling pass when that runs too) and `plan` (`window_plan(labels, numbers=numbers, cuts=cuts)`) describe what runs; `recomputed` lists the
     frames that were recomputed in bf16x3 because their 16-bit pass left a non-finite value; `seconds[k]` is window k's host time
     [assembling its input, enqueueing it] (the wait for a free launch slot excluded)."""
 
-    def __init__(self, model, frames: _Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None):
+    def __init__(self, model, frames: _Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
+                 out_depth: Optional[int] = None):
         self.model, self.frames = model, frames
+        self.depth = frames.depth
+        self.out_depth = frames.depth if out_depth is None else out_depth
         self.detector = detector.DEFAULT if detector_params is None else detector_params
         params = list(model.parameters())
         self.device = params[0].device if params else torch.device("cpu")
@@ -432,14 +474,15 @@ class ClipRun:
 
     def _analyse(self) -> None:
         """Whatever is missing of the LD detector's labels and the scene cuts, in ONE pass over the clip, DETECT_BATCH frames at a time:
-        uint8 upload, then gray planes (spei_frames_u8_in) and focus measures, pair statistics (spei_frame_pair_stats), or both."""
+        upload, then gray planes (spei_frames_u8_in / spei_frames_u16_in) and focus measures, pair statistics (spei_frame_pair_stats /
+        spei_frame_pair_stats_u16), or both.  A deep clip stays deep throughout."""
         p, fr = self.detector, self.frames
         feats, stats = detector.clip_pass(fr, self.device, p.kernel_size, DETECT_BATCH, features=self._labels is None,
                                           pair_stats=self._cuts is None)
         if feats is not None:
             self._labels = detector.predict(feats, p)
         if stats is not None:
-            self._cuts = find_cuts(stats[0].cpu().numpy(), stats[1].cpu().numpy(), fr.H * fr.W, **self.cut_params)
+            self._cuts = find_cuts(_sad_8bit(stats[0].cpu().numpy(), fr.depth), stats[1].cpu().numpy(), fr.H * fr.W, **self.cut_params)
 
     def _run(self):
         m, dev, fr = self.model, self.device, self.frames
@@ -448,7 +491,7 @@ class ClipRun:
         plan = self.plan
         n = m.n_sequence
         pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
-        # uint8 frames, decoded and uploaded once each; a y4m clip's as planar bytes, made RGB on the device
+        # frames (uint8, or uint16 for a deep clip), decoded and uploaded once each; a y4m clip's as planar bytes, made RGB on the device
         cache = FrameCache(pool, fr.host, dev, convert=None if fr.yuv is None else (lambda planar: fr.rgb(planar)[0]))
         enc = EncoderCache()
         inflight, ready = collections.deque(), collections.deque()
@@ -459,6 +502,17 @@ class ClipRun:
         # per window: the egress kernel's non-finite flag, copied to page-locked memory behind the window (read once the window is done)
         flags = torch.zeros(FLAG_RING, dtype=torch.int32, device=dev)
         flags_host = torch.zeros(FLAG_RING, dtype=torch.int32, pin_memory=True)
+        # ingest and egress by depth: a deep clip is read as uint16, and the frame is quantised once, to out_depth
+        depth, out_depth = self.depth, self.out_depth
+        out_dtype = torch.uint8 if out_depth == 8 else torch.uint16
+
+        def ingest(f, dst):
+            return ops.frames_u8_in(f, out=dst) if depth == 8 else ops.frames_u16_in(f, depth, out=dst)
+
+        def egress(y, dst, flag):
+            if out_depth == 8:
+                return ops.frame_u8_out(y, H, W, out=dst, nonfinite=flag)
+            return ops.frame_u16_out(y, H, W, out_depth, out=dst, nonfinite=flag)
 
         def frame(i):
             return fr.device(i).to(dev).contiguous() if fr.on_device(i) else cache.get_dev(i)
@@ -473,7 +527,7 @@ class ClipRun:
                 if key is ZERO:
                     x[0, j].zero_()
                 else:
-                    ops.frames_u8_in(frame(key), out=x[0, j])
+                    ingest(frame(key), x[0, j])
             self.seconds.append([time.time() - t0, 0.0])
             return x
 
@@ -483,7 +537,7 @@ class ClipRun:
                 inflight.popleft().synchronize()           # the host stays at most two windows ahead of the GPU
             t0 = time.time()
             w = plan[k]
-            dst = self.out[k] if self.out is not None else torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+            dst = self.out[k] if self.out is not None else torch.empty(H, W, 3, dtype=out_dtype, device=dev)
             lane = lanes[k % len(lanes)]
             lane.wait_stream(home)                         # the window's input was assembled on the home stream
             slot = k % FLAG_RING
@@ -494,7 +548,7 @@ class ClipRun:
                     nxt.record_stream(lane)
                     m.prefetch_window(nxt, plan[k + 1]["keys"], enc, zero_ref=plan[k + 1]["zero_pre"])
                 y = m.forward_window(x, w["keys"], enc, zero_ref=w["zero_pre"])
-                ops.frame_u8_out(y[0], H, W, out=dst, nonfinite=flags[slot:slot + 1])
+                egress(y[0], dst, flags[slot:slot + 1])
                 flags_host[slot:slot + 1].copy_(flags[slot:slot + 1], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
@@ -512,7 +566,7 @@ class ClipRun:
             finally:
                 m.precision, m.corr_precision, m.use_graph = keep
             slot = k % FLAG_RING
-            ops.frame_u8_out(y[0], H, W, out=dst, nonfinite=flags[slot:slot + 1])
+            egress(y[0], dst, flags[slot:slot + 1])
             if int(flags[slot].item()):
                 raise FloatingPointError(f"non-finite values in deblurred frame {k} in bf16x3 arithmetic as well: the input or the "
                                          "checkpoint is at fault")
@@ -559,16 +613,22 @@ class ClipRun:
 
 
 def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
-                detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None) -> ClipRun:
-    """Deblur a clip: an iterator of (index, uint8 [H,W,3] frame on the model's device), in frame order, one per input frame.
+                detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None,
+                depth: Optional[int] = None, out_depth: Optional[int] = None) -> ClipRun:
+    """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
+    or uint16 frames when `out_depth` is 10 or 12.
 
     model  — an eval() `SPEINet` on a ROCm device; its `precision`, `corr_precision`, `use_graph` and `streams` are used as set.
     frames — T >= 2 frames of one size, at least 20x20: a uint8 [T,H,W,3] numpy array or torch tensor (host or device), a list of
              uint8 [H,W,3] arrays / tensors, a list of image paths (decoded to RGB on worker threads, a few windows ahead), or a
              y4m clip: a `y4m.Y4MReader`, or the path of a `.y4m` file (opened here).  A y4m frame is uploaded
              as its planar bytes (1.5 bytes per pixel for 4:2:0) and becomes packed RGB on the device (`ops.yuv_to_rgb_u8`).
+             Deep clips: a 10- or 12-bit y4m stream (`C420p10` ... `C444p12`; a path, or a reader opened with
+             `depths=(8, 10, 12)`; deep 4:2:0 has no siting tag, the reader's `layout` says LEFT unless the caller sets it), or uint16
+             frames ([T,H,W,3], or a list of [H,W,3]) with `depth`.  A deep clip never passes through 8 bits.
     labels — optional 0/1 per frame (1 = sharp); None: the LD detector labels the clip in a first streaming pass.
-    out    — optional contiguous uint8 [T,H,W,3] tensor on the model's device: frame i is written to out[i] and that view is yielded.
+    out    — optional contiguous [T,H,W,3] tensor on the model's device, uint8 for `out_depth` 8 and uint16 for 10 and 12: frame i is
+             written to out[i] and that view is yielded.
     crop   — crop every frame at the bottom and right to multiples of 20 as it is loaded, as the reference's harness does, instead of
              padding it (H and W are then the cropped size).
     numbers — optional frame number per frame, in which the distance to a reference frame is measured (default: the indices).
@@ -582,19 +642,30 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     yuv    — for a y4m clip, optional `dict(matrix="bt601" | "bt709", range="full" | "limited")` (either or both) in place of what
              the reader derived: y4m carries no matrix tag and often no range tag.
 
+    depth  — 10 or 12: the bits per sample of uint16 frames (a word above 2^depth - 1 reads as that).  Required for uint16 input, an
+             error for anything else.
+    out_depth — 8, 10 or 12: the depth of the frames handed out, round_half_even(clamp(x * (2^out_depth - 1))) of the model's float
+             output; None: the input's depth.  An 8-bit clip with `out_depth=10` is allowed and useful: the model's output carries
+             more than 8 bits.
+
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
     to `ClipRun.recomputed` with a RuntimeWarning, and FloatingPointError is raised if the frame is still not finite."""
     if isinstance(frames, (str, os.PathLike)) and os.fspath(frames).lower().endswith(".y4m"):
-        frames = y4m.Y4MReader(frames)
-    fr = frames_of(frames, crop, yuv)
+        frames = y4m.Y4MReader(frames, depths=y4m.DEPTHS)
+    fr = frames_of(frames, crop, yuv, depth)
+    if out_depth is not None and (isinstance(out_depth, bool) or out_depth not in y4m.DEPTHS):
+        raise ValueError(f"out_depth must be None, 8, 10 or 12, got {out_depth!r}")
+    out_depth = fr.depth if out_depth is None else int(out_depth)
+    out_dtype = torch.uint8 if out_depth == 8 else torch.uint16
     lab = None if labels is None else labels_of(labels, fr.T)
     if numbers is not None and len(numbers) != fr.T:
         raise ValueError(f"numbers has {len(numbers)} entries for a clip of {fr.T} frames")
     shape = (fr.T, fr.H, fr.W, 3)
-    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous uint8 [{fr.T},{fr.H},{fr.W},3] tensor")
+    if out is not None and not (torch.is_tensor(out) and out.dtype == out_dtype and tuple(out.shape) == shape and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {str(out_dtype).split('.')[-1]} [{fr.T},{fr.H},{fr.W},3] tensor "
+                         f"(out_depth {out_depth})")
     if isinstance(cuts, str):
         if cuts != "auto":
             raise ValueError(f"cuts must be None, \"auto\" or a sequence of frame indices, got {cuts!r}")
@@ -604,7 +675,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     if cut_params is not None and set(cut_params) - {"hist_min", "ratio", "min_delta", "window"}:
         raise ValueError(f"cut_params holds {sorted(set(cut_params) - {'hist_min', 'ratio', 'min_delta', 'window'})}: "
                          "find_cuts takes hist_min, ratio, min_delta and window")
-    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params)
+    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth)
 
 
 def _inputs(spec: str) -> list:
@@ -688,22 +759,29 @@ def main(argv=None) -> None:
                    "input's XCOLORRANGE tag, limited without one; full for image input)")
     p.add_argument("--fps", type=_fps, default=None, help="frame rate of y4m output as num:den (default: the y4m input's; 25:1 for image input)")
     p.add_argument("--chroma", choices=sorted(y4m.TAG_OF_LAYOUT.values()), default=None, help="chroma layout of y4m output from image "
-                   "input (default 420jpeg; y4m input keeps its own)")
+                   "input (default 420jpeg; y4m input keeps its own); 420jpeg | 420mpeg2 also select the chroma siting of a 10- or "
+                   "12-bit 4:2:0 y4m input, whose tag carries none (default 420mpeg2: co-sited with the even column)")
+    p.add_argument("--out_depth", type=int, choices=y4m.DEPTHS, default=None, help="bits per sample of the output (default: the "
+                   "input's for y4m output; a PNG directory always gets 8-bit files)")
     p.add_argument("--spool_dir", default=None, help="directory of the temporary file that '--input -' is copied to (default: the system's)")
     a = p.parse_args(argv)
     to_stdout = a.output == "-"
     to_y4m = to_stdout or a.output.lower().endswith(".y4m")
     log = sys.stderr if to_stdout else sys.stdout
+    if not to_y4m and a.out_depth not in (None, 8):
+        raise SystemExit(f"--out_depth {a.out_depth}: a PNG directory gets 8-bit files; write a .y4m file or '-' for a deep output")
 
     def say(text: str) -> None:
         print(text, file=log, flush=True)
 
     reader = None
     if a.input == "-":
-        reader = y4m.Y4MReader(_spool(sys.stdin.buffer, a.spool_dir))
+        reader = y4m.Y4MReader(_spool(sys.stdin.buffer, a.spool_dir), depths=y4m.DEPTHS)
     elif a.input.lower().endswith(".y4m") and os.path.isfile(a.input):
-        reader = y4m.Y4MReader(a.input)
+        reader = y4m.Y4MReader(a.input, depths=y4m.DEPTHS)
     if reader is not None:
+        if reader.depth > 8 and reader.layout != y4m.P444 and a.chroma in ("420jpeg", "420mpeg2"):
+            reader.layout = y4m.layout_of(a.chroma)
         if len(reader) < 2:
             raise SystemExit(f"--input {a.input}: {len(reader)} frame(s) found, a clip needs at least 2")
         files, stems = reader, [f"{i:06d}" for i in range(len(reader))]
@@ -719,8 +797,14 @@ def main(argv=None) -> None:
     net = load_model(a.model_path, a.device, a.precision, a.graph)
     cuts = {"none": None, "auto": "auto"}[a.cuts] if a.cuts in ("none", "auto") else read_cuts(a.cuts)
     yuv = {k: v for k, v in (("matrix", a.matrix), ("range", a.range)) if v is not None} if reader is not None else None
+    out_depth = a.out_depth
+    if not to_y4m:
+        if reader is not None and reader.depth > 8:
+            say(f"# {reader.depth}-bit input, PNG output: the frames are written with 8 bits per sample (out_depth 8)")
+        out_depth = 8
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
-                      yuv=yuv or None)
+                      yuv=yuv or None, out_depth=out_depth)
+    out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
     if to_y4m:
@@ -731,7 +815,7 @@ def main(argv=None) -> None:
             layout, rng = y4m.layout_of(a.chroma or "420jpeg"), y4m.range_of(a.range or "full")
             matrix = y4m.matrix_of(a.matrix) if a.matrix else (y4m.BT709 if H >= 720 else y4m.BT601)
             fps, aspect = a.fps or (25, 1), None
-        writer = y4m.Y4MWriter(sys.stdout.buffer if to_stdout else a.output, W, H, fps, layout, rng, aspect)
+        writer = y4m.Y4MWriter(sys.stdout.buffer if to_stdout else a.output, W, H, fps, layout, rng, aspect, depth=out_depth)
     else:
         os.makedirs(a.output, exist_ok=True)
     for c in run.cuts:
@@ -742,7 +826,9 @@ def main(argv=None) -> None:
         ring = HostRing(writers)
         for i, frame in run:
             if to_y4m:
-                ring.land(lambda buf: writer.write(buf.numpy()), ops.rgb_u8_to_yuv(frame, layout, matrix, rng))
+                planar = (ops.rgb_u8_to_yuv(frame, layout, matrix, rng) if out_depth == 8 else
+                          ops.rgb_u16_to_yuv(frame, layout, matrix, rng, out_depth))
+                ring.land(lambda buf: writer.write(buf.numpy()), planar)
             else:
                 ring.land(lambda buf, path=os.path.join(a.output, names[i]): _imwrite(path, buf.numpy()), frame)
             now = time.time()

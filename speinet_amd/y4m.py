@@ -2,8 +2,10 @@
 `FRAME` line plus raw planar bytes per frame.  Host side only (numpy, no torch): the planar bytes go to the device as they are and
 become packed RGB there (csrc/yuv_io.hip, `ops.yuv_to_rgb_u8`), and come back the same way (`ops.rgb_u8_to_yuv`).
 
-Supported: progressive 8-bit 4:2:0 (`C420jpeg`, bare `C420`, `C420mpeg2`) and 4:4:4 (`C444`).  Not supported: interlaced streams,
-more than 8 bits, 4:2:2, 4:1:1, mono, `C420paldv`."""
+Supported: progressive 8-bit 4:2:0 (`C420jpeg`, bare `C420`, `C420mpeg2`) and 4:4:4 (`C444`), and, for a reader opened with
+`depths=(8, 10, 12)`, 10- and 12-bit 4:2:0 and 4:4:4 (`C420p10`, `C420p12`, `C444p10`, `C444p12`: little-endian 16-bit samples, which
+`ops.yuv_to_rgb_u16` / `ops.rgb_u16_to_yuv` convert).  Not supported: interlaced streams, other depths, 4:2:2, 4:1:1, mono,
+`C420paldv`."""
 from __future__ import annotations
 
 import os
@@ -18,6 +20,8 @@ FULL, LIMITED = 0, 1                   # SPEI_YUV_FULL, SPEI_YUV_LIMITED
 
 MAGIC = b"YUV4MPEG2"
 LAYOUT_OF_TAG = {"420jpeg": CENTER, "420": CENTER, "420mpeg2": LEFT, "444": P444}
+DEEP_TAGS = {"420p10": (LEFT, 10), "420p12": (LEFT, 12), "444p10": (P444, 10), "444p12": (P444, 12)}     # tag -> (layout, depth)
+DEPTHS = (8, 10, 12)
 TAG_OF_LAYOUT = {CENTER: "420jpeg", LEFT: "420mpeg2", P444: "444"}
 MATRIX_NAMES = {"bt601": BT601, "bt709": BT709}
 RANGE_NAMES = {"full": FULL, "limited": LIMITED}
@@ -48,11 +52,28 @@ def layout_of(value) -> int:
     return _named(value, LAYOUT_OF_TAG, "chroma layout")
 
 
-def frame_bytes(h: int, w: int, layout: int) -> int:
-    """Bytes of one planar frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0 and [h][w] each for 4:4:4."""
+def depth_of(depth) -> int:
+    """8, 10 or 12 bits per sample."""
+    if isinstance(depth, bool) or depth not in DEPTHS:
+        raise ValueError(f"depth must be one of {DEPTHS}, got {depth!r}")
+    return int(depth)
+
+
+def frame_bytes(h: int, w: int, layout: int, depth: int = 8) -> int:
+    """Bytes of one planar frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0 and [h][w] each for 4:4:4; one byte
+    per sample at `depth` 8, two (a little-endian word) at 10 and 12."""
     if layout not in TAG_OF_LAYOUT:
         raise ValueError(f"unknown chroma layout {layout!r}")
-    return h * w + 2 * (h * w if layout == P444 else ((h + 1) // 2) * ((w + 1) // 2))
+    samples = h * w + 2 * (h * w if layout == P444 else ((h + 1) // 2) * ((w + 1) // 2))
+    return samples * (1 if depth_of(depth) == 8 else 2)
+
+
+def chroma_tag(layout: int, depth: int = 8) -> str:
+    """The C tag's text of a layout at a depth: "420jpeg", "420mpeg2", "444"; "420p10", "444p12" and the like for deep streams (which
+    carry no siting)."""
+    if depth_of(depth) == 8:
+        return TAG_OF_LAYOUT[layout]
+    return f"{'444' if layout == P444 else '420'}p{depth}"
 
 
 def _ratio(tag: str, text: str):
@@ -72,15 +93,22 @@ class Y4MReader:
     as the first: T is then the payload size divided by the record size, and a later line that differs raises ValueError when its
     frame is read.  A file that ends inside a frame raises ValueError here.
 
+    `depths`: the sample depths the caller can take.  The default, (8,), refuses deep streams, as every caller that indexes the
+    payload as bytes needs; with (8, 10, 12) the reader also accepts `C420p10`, `C420p12`, `C444p10` and `C444p12`.  `raw(i)` still
+    returns the payload's bytes as uint8 (`frame_bytes` of them, two per sample, little-endian).  A deep 4:2:0 tag carries no
+    siting: `layout` is then LEFT, the MPEG-2 siting of the codecs such streams come from; it is a plain attribute that the caller
+    may set to CENTER before the clip is used.
+
     Attributes: `width`, `height`, `fps` and `aspect` ((num, den); 25:1 and None when absent), `layout` (CENTER / LEFT / P444),
-    `chroma` (the C tag's text), `range` (from XCOLORRANGE=FULL|LIMITED; LIMITED when absent), `matrix`, `frame_bytes`.  y4m carries
+    `depth` (8, 10 or 12), `chroma` (the C tag's text), `range` (from XCOLORRANGE=FULL|LIMITED; LIMITED when absent), `matrix`, `frame_bytes`.  y4m carries
     no matrix tag: `matrix` is BT709 when height >= 720 and BT601 otherwise, which is ffmpeg's usual guess for untagged video;
     assign `matrix` / `range`, or pass `yuv=dict(matrix=..., range=...)` to `deblur_clip`, to override.
 
-    Interlaced streams, more than 8 bits per sample, C420paldv, C422, C411 and Cmono are rejected with a ValueError that names the
-    tag."""
+    Interlaced streams, depths outside `depths` (9, 14 and 16 bits always), C420paldv, C422, C411 and Cmono at any depth are
+    rejected with a ValueError that names the tag."""
 
-    def __init__(self, path_or_file):
+    def __init__(self, path_or_file, depths=(8,)):
+        self.depths = tuple(depth_of(d) for d in depths)
         self._own = isinstance(path_or_file, (str, bytes, os.PathLike))
         self._f = open(path_or_file, "rb") if self._own else path_or_file
         self.name = os.fspath(path_or_file) if self._own else getattr(path_or_file, "name", "<file>")
@@ -130,18 +158,25 @@ class Y4MReader:
             if val < 1:
                 self._fail(f"tag {key}{val}: the size must be positive")
         c = self.chroma
-        if c not in LAYOUT_OF_TAG:
+        if c in DEEP_TAGS and DEEP_TAGS[c][1] in self.depths:
+            self.layout, self.depth = DEEP_TAGS[c]
+        elif c in LAYOUT_OF_TAG and 8 in self.depths:
+            self.layout, self.depth = LAYOUT_OF_TAG[c], 8
+        else:
             deep = re.fullmatch(r"(?:(?:420|422|444)p|mono)(\d+)", c)
-            if deep:
-                why = f"{deep.group(1)} bits per sample (8 only)"
+            if c in LAYOUT_OF_TAG:
+                why = f"8 bits per sample ({', '.join(map(str, self.depths))} only)"
+            elif deep and self.depths != (8,) and int(deep.group(1)) in self.depths:     # C422p10, Cmono12: not the depth's fault
+                why = "only 4:2:0 and 4:4:4 are supported"
+            elif deep:
+                why = f"{deep.group(1)} bits per sample ({', '.join(map(str, self.depths))} only)"
             elif c.startswith(("422", "411", "mono")) or c == "420paldv":
                 why = "only 4:2:0 (C420jpeg, C420, C420mpeg2) and 4:4:4 (C444) are supported"
             else:
                 why = "unknown chroma format"
             self._fail(f"tag C{c}: {why}")
-        self.layout = LAYOUT_OF_TAG[c]
         self.matrix = BT709 if self.height >= 720 else BT601
-        self.frame_bytes = frame_bytes(self.height, self.width, self.layout)
+        self.frame_bytes = frame_bytes(self.height, self.width, self.layout, self.depth)
         self._data = end + 1
         size = f.seek(0, os.SEEK_END)
         if size == self._data:
@@ -198,14 +233,17 @@ class Y4MReader:
 
 
 class Y4MWriter:
-    """Write a progressive 8-bit y4m stream: the header once, then `write(planar bytes)` per frame (`frame_bytes` bytes: a bytes-like
-    object or a contiguous uint8 numpy array).  `path_or_file`: a path, or a binary file object (a pipe will do), which `close`
-    flushes and leaves open."""
+    """Write a progressive y4m stream: the header once, then `write(planar bytes)` per frame (`frame_bytes` bytes: a bytes-like
+    object or a contiguous numpy array, uint8, or uint16 for a deep stream).  `path_or_file`: a path, or a binary file object (a pipe
+    will do), which `close` flushes and leaves open.  `depth` 10 or 12 writes `C420p10`, `C444p12` and the like (little-endian words;
+    the tag carries no siting, whatever `layout` says) and adds `XYSCSS=420P10` and the like, as ffmpeg does."""
 
-    def __init__(self, path_or_file, w: int, h: int, fps=(25, 1), layout: int = CENTER, range: int = LIMITED, aspect=None):
+    def __init__(self, path_or_file, w: int, h: int, fps=(25, 1), layout: int = CENTER, range: int = LIMITED, aspect=None,
+                 depth: int = 8):
         self.width, self.height, self.fps, self.aspect = int(w), int(h), (int(fps[0]), int(fps[1])), aspect
-        self.layout, self.range = layout_of(layout), range_of(range)
-        self.frame_bytes = frame_bytes(self.height, self.width, self.layout)
+        self.layout, self.range, self.depth = layout_of(layout), range_of(range), depth_of(depth)
+        self.chroma = chroma_tag(self.layout, self.depth)
+        self.frame_bytes = frame_bytes(self.height, self.width, self.layout, self.depth)
         if self.width < 1 or self.height < 1 or self.fps[0] < 1 or self.fps[1] < 1:
             raise ValueError(f"y4m: bad size {w}x{h} or frame rate {fps}")
         self._own = isinstance(path_or_file, (str, bytes, os.PathLike))
@@ -213,14 +251,15 @@ class Y4MWriter:
         tags = [f"W{self.width}", f"H{self.height}", f"F{self.fps[0]}:{self.fps[1]}", "Ip"]
         if aspect is not None:
             tags.append(f"A{int(aspect[0])}:{int(aspect[1])}")
-        tags += [f"C{TAG_OF_LAYOUT[self.layout]}", "XCOLORRANGE=" + ("FULL" if self.range == FULL else "LIMITED")]
+        tags += [f"C{self.chroma}"] + ([] if self.depth == 8 else [f"XYSCSS={self.chroma.upper()}"])
+        tags += ["XCOLORRANGE=" + ("FULL" if self.range == FULL else "LIMITED")]
         self._f.write(MAGIC + b" " + " ".join(tags).encode("ascii") + b"\n")
         self.frames = 0
 
     def write(self, planar) -> None:
         data = memoryview(planar).cast("B")
         if data.nbytes != self.frame_bytes:
-            raise ValueError(f"y4m: a {self.width}x{self.height} C{TAG_OF_LAYOUT[self.layout]} frame is {self.frame_bytes} bytes, "
+            raise ValueError(f"y4m: a {self.width}x{self.height} C{self.chroma} frame is {self.frame_bytes} bytes, "
                              f"got {data.nbytes}")
         self._f.write(b"FRAME\n")
         self._f.write(data)
