@@ -613,6 +613,31 @@ int spei_psnr_f32(const float* a, const float* b, int H, int W, int shave, float
 int spei_window_mean_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
                         unsigned char* blur, unsigned char* gt, float* gray, int H, int W, spei_stream_t stream);
 
+/* ---- blur synthesis in linear light (speinet_amd/light.py; an extension beyond the reference, whose scripts average code values) ---- */
+
+/* A sensor integrates light and applies its transfer curve afterwards; the two entries below average a run in LINEAR light, in integer
+ * arithmetic.  A light is 512 uint32 words, `tables` on the device and `tables_host` the same words in HOST memory: lin[256], then
+ * thr[256], made once on the host in float64 from the light's forward transfer f with S = 2^24 - 1:
+ *   lin[c] = rint(S f(c / 255))            the linear value of code c
+ *   thr[c] = rint(S f((c - 0.5) / 255))    the linear value of the boundary between codes c - 1 and c (c >= 1; thr[0] is never read)
+ * Valid iff lin[0] == 0, lin[255] <= S and lin[c-1] < thr[c] <= lin[c] for c = 1..255; then both tables increase strictly and
+ * encode(lin[c]) == c.  Validity is checked on tables_host before anything is launched: a kernel never meets a table that could make
+ * it misbehave.  Per byte position of a run of `length` frames:
+ *   L    = floor(sum of lin[byte] over the run / length)     (the sum is at most 15 S < 2^28)
+ *   blur = #{ c in 1..255 : thr[c] <= L }                     (the largest code whose lower boundary is at or below L)
+ * A run of length 1 returns its bytes (encode(lin[c]) == c).  Everything else — gt, the gray plane of the ENCODED bytes, the checks of
+ * runs_host, the access paths — is spei_window_mean_u8's. */
+int spei_window_mean_light_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
+                              const uint32_t* tables, const uint32_t* tables_host, unsigned char* blur, unsigned char* gt, float* gray,
+                              int H, int W, spei_stream_t stream);
+
+/* spei_train_batch_runs_u8 with the run averaged in linear light: u = the blur byte defined above — the bytes of
+ * spei_window_mean_light_u8's blur[m] — then (float)u * (float)(rgb_range / 255).  Records, geometry, the zero flag, the output
+ * layout and every check of table_host as spei_train_batch_runs_u8; tables / tables_host as above. */
+int spei_train_batch_runs_light_u8(const spei_run_record* table, const spei_run_record* table_host, int n_in, int n_gt,
+                                   const uint32_t* tables, const uint32_t* tables_host, float* input, float* gt, int P, float rgb_range,
+                                   spei_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

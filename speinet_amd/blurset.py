@@ -4,11 +4,13 @@ middle frame is the ground truth (reference LD_detector/mix_choice_dataset.py:46
 38-76).
 
     python -m speinet_amd.blurset --input <dir of clip folders> --output <dir> [--ratio 0.1 0.3 0.5] [--threshold 5] [--seed N]
+                                  [--light code|srgb|gamma:<g>]
 
 writes `<output>/blur/<clip>/<i>.png`, `<output>/gt/<clip>/<i>.png` and `<output>/label/<clip>.npy`: the layout `data.ClipSet`,
 `speinet_amd.fit` and `python -m speinet_amd.detector fit` read.  The frame files are numbered with six digits: the loaders pair
 frames and labels by sorted file name (as the reference's do, data/videodata_nfs.py:127-162), and the reference's own `0.png ..
-123.png` do not sort in frame order.
+123.png` do not sort in frame order.  `--light` (default `code`: the reference's average of code values, byte for byte) averages in
+linear light instead, as an exposure does: speinet_amd.light has the integer arithmetic; the ground truth, labels and layout are the same.
 
   * `plan_runs`   — the reference's draw sequence on a `random.Random` of the caller's (no global state): runs and labels;
   * `plan_dataset` — that sequence for every clip of a directory on one `random.Random(seed)` (also data.SharpClipSet's, per epoch);
@@ -27,6 +29,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from . import light as _light
 from . import ops
 from .video import IMAGE_EXTS, HostRing, _imwrite, frames_of
 
@@ -81,9 +84,11 @@ def _chunks(starts, lengths, chunk_frames: int):
         i = j
 
 
-def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES):
+def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code"):
     """Generator of (first run, blur uint8 [m,H,W,3], gt uint8 [m,H,W,3], gray [m,H,W] or None) on `device`, one item per chunk of
     consecutive runs; see `synthesize`."""
+    if not _light.is_code(light):
+        _light.tables(light)                              # a light without valid tables is refused before anything is read
     fr = frames if hasattr(frames, "on_device") else frames_of(frames)
     starts, lengths = (np.asarray(a, np.int64).reshape(-1) for a in runs[:2])
     if starts.size != lengths.size or starts.size == 0:
@@ -132,17 +137,18 @@ def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_fra
                     if fr.on_device(t):
                         src_buf[t - lo].copy_(fr.device(t))
                 src = src_buf[:hi - lo]
-            blur, gt, g = ops.window_mean_u8(src, starts[i:j] - lo, lengths[i:j], gray=gray)
+            blur, gt, g = ops.window_mean_u8(src, starts[i:j] - lo, lengths[i:j], gray=gray, light=light)
             yield i, blur, gt, g
 
 
-def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES):
+def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code"):
     """Average the runs of a clip on the GPU: `frames` in any form `video.frames_of` accepts (uint8 [T,H,W,3] array or tensor on the
     host or the device, a list of frames, a list of image paths), `runs` = (starts, lengths[, labels]) as `plan_runs` returns them
     -> (blur uint8 [M,H,W,3], gt uint8 [M,H,W,3]) on `device`, and the detector's gray planes [M,H,W] as a third item when `gray`.
     blur[m] is the per-byte floor of the run's mean (the bytes the reference writes), gt[m] the run's middle frame.  The source
-    frames are uploaded `chunk_frames` at a time; only the result is as long as the clip."""
-    parts = list(synthesize_chunks(frames, runs, device, gray, chunk_frames))
+    frames are uploaded `chunk_frames` at a time; only the result is as long as the clip.  `light`: "srgb" or "gamma:<g>" averages in
+    linear light (speinet_amd.light) instead; gt is unchanged and the gray planes are those of the encoded blur bytes."""
+    parts = list(synthesize_chunks(frames, runs, device, gray, chunk_frames, light))
     out = (torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]))
     return out + (torch.cat([p[3] for p in parts]),) if gray else out
 
@@ -179,11 +185,15 @@ def plan_dataset(clip_lengths, ratios, seed: int = 0, threshold: int = 5, window
 
 
 def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int = 0, threshold: int = 5, window_range=(1, 15),
-                  device="cuda", chunk_frames: int = CHUNK_FRAMES, log=None) -> list:
+                  device="cuda", chunk_frames: int = CHUNK_FRAMES, log=None, light="code") -> list:
     """For every clip folder under src_dir write out_dir/blur/<clip>/<i>.png, out_dir/gt/<clip>/<i>.png and out_dir/label/<clip>.npy
     (reference process_dataset, mix_choice_dataset.py:78-117).  `ratio`: the share of sharp runs; `ratios`: several, one drawn per
-    clip (:79) from the same `random.Random(seed)` that then draws the clip's runs (`plan_dataset`).  -> one dict per clip (name, ratio,
-    frames, labels)."""
+    clip (:79) from the same `random.Random(seed)` that then draws the clip's runs (`plan_dataset`).  `light`: the light the runs are
+    averaged in (speinet_amd.light; it changes the blur frames only, and is not recorded in the set).  -> one dict per clip (name,
+    ratio, frames, labels)."""
+    light = _light.name(light)
+    if light != _light.CODE:
+        _light.tables(light)
     clips = []
     for name, files in clip_folders(src_dir):
         try:
@@ -205,7 +215,7 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
                 _imwrite(pb, b.numpy())
                 _imwrite(pg, g.numpy())
 
-            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths), dev, False, chunk_frames):
+            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths), dev, False, chunk_frames, light):
                 for m in range(blur.shape[0]):
                     fn = f"{i0 + m:06d}.png"
                     ring.land(lambda b, g, pb=os.path.join(bdir, fn), pg=os.path.join(gdir, fn): save(b, g, pb, pg), blur[m], gt[m])
@@ -213,24 +223,37 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
             np.save(os.path.join(out_dir, "label", name + ".npy"), labels)
             done.append({"name": name, "ratio": r, "source_frames": fr.T, "frames": int(labels.size), "labels": labels})
             if log:
-                log(f"> {name}: {fr.T} sharp frames -> {labels.size} frames, {int(labels.sum())} labelled sharp (ratio {r})")
+                log(f"> {name}: {fr.T} sharp frames -> {labels.size} frames, {int(labels.sum())} labelled sharp (ratio {r}, light {light})")
     return done
 
 
-def main(argv=None) -> None:
+def parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Make a blur / gt / label training set from folders of sharp high-frame-rate frames on an MI355X")
     p.add_argument("--input", required=True, help="a directory with one folder of sharp frames per clip (PNG / JPG / BMP, file-name order)")
     p.add_argument("--output", required=True, help="directory for blur/<clip>/, gt/<clip>/ and label/<clip>.npy")
     p.add_argument("--ratio", type=float, nargs="+", default=[0.5], help="share of sharp runs; several: one is drawn per clip")
     p.add_argument("--threshold", type=int, default=5, help="a run of at most this many frames is a sharp frame (label 1)")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--light", default="code", help="the light the runs are averaged in: code (code values, the reference's sets), srgb or "
+                                                   "gamma:<g> (linear light, as an exposure)")
     p.add_argument("--device", default="cuda")
+    return p
+
+
+def main(argv=None) -> None:
+    p = parser()
     a = p.parse_args(argv)
+    try:
+        light = _light.name(a.light)
+        if light != _light.CODE:
+            _light.tables(light)
+    except ValueError as e:
+        p.error(f"--light: {e}")
     t0 = time.time()
     done = write_dataset(a.input, a.output, ratios=a.ratio, seed=a.seed, threshold=a.threshold, device=a.device,
-                         log=lambda s: print(s, flush=True))
+                         log=lambda s: print(s, flush=True), light=light)
     n_src, n_out = sum(d["source_frames"] for d in done), sum(d["frames"] for d in done)
-    print(f"# {len(done)} clips, {n_src} sharp frames -> {n_out} frames in {time.time() - t0:.2f}s", flush=True)
+    print(f"# {len(done)} clips, {n_src} sharp frames -> {n_out} frames in {time.time() - t0:.2f}s, light {light}", flush=True)
 
 
 if __name__ == "__main__":

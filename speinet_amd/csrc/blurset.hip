@@ -15,7 +15,15 @@
 // 16-byte aligned): one thread per 16 pixels, three 16-byte loads per source frame, three 16-byte stores per output frame, four per
 // gray plane.  Otherwise one thread per pixel with byte accesses.  The quotient is a multiply and a shift: with m = ceil(2^16 / n),
 // (s * m) >> 16 == s / n for every s <= 15 * 255 and n <= 15 (the error term s * (m n - 2^16) stays below 2^16).
+//
+//   spei_window_mean_light_u8 — the same launch with the run averaged in LINEAR light (csrc/light.h; an extension beyond the reference):
+//                         every source byte is decoded through lin[] (one LDS read), the sums are 32-bit, the quotient is light.h's
+//                         multiply-high and the result is encoded by a binary search over thr[] (eight LDS reads per output byte);
+//                         gt and the gray plane of the ENCODED bytes as above.  Both kernels are the templates below with LIGHT set: the
+//                         tables are staged by the workgroup before its first item, and a run of length 1 copies its bytes
+//                         (encode(lin[c]) == c) without touching them.  Same traffic as the code-value launch.
 #include "common.h"
+#include "light.h"
 
 namespace {
 
@@ -23,12 +31,26 @@ constexpr int MAX_RUN = 15;
 
 __device__ __forceinline__ uint32_t quot(uint32_t s, uint32_t magic) { return (s * magic) >> 16; }
 
+template <bool LIGHT>
+__device__ __forceinline__ uint32_t mean_of(uint32_t sum, uint32_t magic, const uint32_t* tab) {
+    if constexpr (LIGHT) return light_encode(tab + 256, light_quot(sum, magic));
+    else return quot(sum, magic);
+}
+
+template <bool LIGHT>
 __global__ __launch_bounds__(256) void window_mean_vec_kernel(const unsigned char* __restrict__ src, int64_t fstride, const int* __restrict__ runs,
-                                                              unsigned char* __restrict__ blur, unsigned char* __restrict__ gt,
-                                                              float* __restrict__ gray, int64_t hw) {
+                                                              const uint32_t* __restrict__ tables, unsigned char* __restrict__ blur,
+                                                              unsigned char* __restrict__ gt, float* __restrict__ gray, int64_t hw) {
     const int m = blockIdx.y;
     const int start = runs[2 * m], len = runs[2 * m + 1];
-    const uint32_t magic = (65536u + len - 1) / len;
+    const uint32_t* tab = nullptr;                         // LIGHT: lin[256], thr[256] in LDS
+    if constexpr (LIGHT) {
+        __shared__ uint32_t lds[LIGHT_WORDS];
+        if (len > 1) light_stage(lds, tables);
+        tab = lds;
+    }
+    const bool copy = LIGHT && len == 1;                   // a run of length 1 returns its bytes; the tables are not staged
+    const uint32_t magic = LIGHT ? (copy ? 0u : light_magic(len)) : (65536u + len - 1) / len;
     const int64_t groups = hw >> 4;                        // 16 pixels = 48 bytes per thread
     const int64_t nb = hw * 3;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < groups; i += (int64_t)gridDim.x * 256) {
@@ -40,15 +62,29 @@ __global__ __launch_bounds__(256) void window_mean_vec_kernel(const unsigned cha
             const uint4* p = reinterpret_cast<const uint4*>(src + (start + t) * fstride + i * 48);
             const uint4 q[3] = {p[0], p[1], p[2]};
             if (t == len / 2) { mid[0] = q[0]; mid[1] = q[1]; mid[2] = q[2]; }
+            if (copy) break;
 #pragma unroll
             for (int v = 0; v < 3; ++v) {
                 const uint32_t w[4] = {q[v].x, q[v].y, q[v].z, q[v].w};
 #pragma unroll
-                for (int j = 0; j < 16; ++j) acc[16 * v + j] += (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+                for (int j = 0; j < 16; ++j) {
+                    const uint32_t b = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+                    if constexpr (LIGHT) acc[16 * v + j] += tab[b];
+                    else acc[16 * v + j] += b;
+                }
             }
         }
+        if (copy) {
 #pragma unroll
-        for (int j = 0; j < 48; ++j) acc[j] = quot(acc[j], magic);
+            for (int v = 0; v < 3; ++v) {
+                const uint32_t w[4] = {mid[v].x, mid[v].y, mid[v].z, mid[v].w};
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[16 * v + j] = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 48; ++j) acc[j] = mean_of<LIGHT>(acc[j], magic, tab);
+        }
         uint4* b = reinterpret_cast<uint4*>(blur + m * nb + i * 48);
         uint4* g = reinterpret_cast<uint4*>(gt + m * nb + i * 48);
 #pragma unroll
@@ -75,24 +111,35 @@ __global__ __launch_bounds__(256) void window_mean_vec_kernel(const unsigned cha
     }
 }
 
+template <bool LIGHT>
 __global__ __launch_bounds__(256) void window_mean_px_kernel(const unsigned char* __restrict__ src, int64_t fstride, const int* __restrict__ runs,
-                                                             unsigned char* __restrict__ blur, unsigned char* __restrict__ gt,
-                                                             float* __restrict__ gray, int64_t hw) {
+                                                             const uint32_t* __restrict__ tables, unsigned char* __restrict__ blur,
+                                                             unsigned char* __restrict__ gt, float* __restrict__ gray, int64_t hw) {
     const int m = blockIdx.y;
     const int start = runs[2 * m], len = runs[2 * m + 1];
-    const uint32_t magic = (65536u + len - 1) / len;
+    const uint32_t* tab = nullptr;                         // LIGHT: lin[256], thr[256] in LDS
+    if constexpr (LIGHT) {
+        __shared__ uint32_t lds[LIGHT_WORDS];
+        if (len > 1) light_stage(lds, tables);
+        tab = lds;
+    }
+    const bool copy = LIGHT && len == 1;                   // a run of length 1 returns its bytes; the tables are not staged
+    const uint32_t magic = LIGHT ? (copy ? 0u : light_magic(len)) : (65536u + len - 1) / len;
     const int64_t nb = hw * 3;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (int64_t)gridDim.x * 256) {
         uint32_t acc[3] = {0u, 0u, 0u};
-        for (int t = 0; t < len; ++t) {
+        for (int t = 0; t < len && !copy; ++t) {
             const unsigned char* p = src + (start + t) * fstride + i * 3;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] += p[c];
+            for (int c = 0; c < 3; ++c) {
+                if constexpr (LIGHT) acc[c] += tab[p[c]];
+                else acc[c] += p[c];
+            }
         }
         const unsigned char* p = src + (start + len / 2) * fstride + i * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            acc[c] = quot(acc[c], magic);
+            acc[c] = copy ? (uint32_t)p[c] : mean_of<LIGHT>(acc[c], magic, tab);
             blur[m * nb + i * 3 + c] = (unsigned char)acc[c];
             gt[m * nb + i * 3 + c] = p[c];
         }
@@ -100,30 +147,49 @@ __global__ __launch_bounds__(256) void window_mean_px_kernel(const unsigned char
     }
 }
 
-}  // namespace
-
-extern "C" int spei_window_mean_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
-                                   unsigned char* blur, unsigned char* gt, float* gray, int H, int W, spei_stream_t stream) {
-    SPEI_REQUIRE(src && runs && runs_host && blur && gt, "spei_window_mean_u8: null pointer (src, runs, runs_host, blur and gt are required)");
+// The runs are checked HERE, on the host copy (and, LIGHT, the tables on theirs): the kernels never meet a run that leaves the clip
+template <bool LIGHT>
+int window_mean(const char* name, const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
+                const uint32_t* tables, const uint32_t* tables_host, unsigned char* blur, unsigned char* gt, float* gray, int H, int W,
+                spei_stream_t stream) {
+    SPEI_REQUIRE(src && runs && runs_host && blur && gt, "%s: null pointer (src, runs, runs_host, blur and gt are required)", name);
     SPEI_REQUIRE(T > 0 && M > 0 && M <= 65535 && H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31),
-                 "spei_window_mean_u8: bad sizes (%d frames of %dx%d, %d runs; at most 65535 runs per launch)", T, H, W, M);
+                 "%s: bad sizes (%d frames of %dx%d, %d runs; at most 65535 runs per launch)", name, T, H, W, M);
     const int64_t hw = (int64_t)H * W;
-    SPEI_REQUIRE(T == 1 || frame_stride >= hw * 3, "spei_window_mean_u8: frame stride %lld < one %dx%d frame", (long long)frame_stride, H, W);
+    SPEI_REQUIRE(T == 1 || frame_stride >= hw * 3, "%s: frame stride %lld < one %dx%d frame", name, (long long)frame_stride, H, W);
     for (int m = 0; m < M; ++m) {
         const int start = runs_host[2 * m], len = runs_host[2 * m + 1];
-        SPEI_REQUIRE(len >= 1 && len <= MAX_RUN, "spei_window_mean_u8: run %d has length %d (1..%d)", m, len, MAX_RUN);
-        SPEI_REQUIRE(start >= 0 && start <= T - len, "spei_window_mean_u8: run %d = frames %d..%d leaves the clip of %d frames", m, start,
+        SPEI_REQUIRE(len >= 1 && len <= MAX_RUN, "%s: run %d has length %d (1..%d)", name, m, len, MAX_RUN);
+        SPEI_REQUIRE(start >= 0 && start <= T - len, "%s: run %d = frames %d..%d leaves the clip of %d frames", name, m, start,
                      start + len - 1, T);
     }
+    if constexpr (LIGHT)
+        if (light_check(name, tables, tables_host)) return -1;
     const bool vec = (hw & 15) == 0 && (((uintptr_t)src | (uintptr_t)blur | (uintptr_t)gt | (uintptr_t)gray) & 15) == 0 &&
                      (T == 1 || (frame_stride & 15) == 0);
     const int64_t items = vec ? hw >> 4 : hw;
     const int64_t bx = (items + 255) / 256;
     const dim3 grid((unsigned)(bx < 4096 ? bx : 4096), (unsigned)M);
     if (vec)
-        hipLaunchKernelGGL(window_mean_vec_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, blur, gt, gray, hw);
+        hipLaunchKernelGGL(window_mean_vec_kernel<LIGHT>, grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, tables, blur, gt,
+                           gray, hw);
     else
-        hipLaunchKernelGGL(window_mean_px_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, blur, gt, gray, hw);
-    SPEI_CHECK_LAUNCH("spei_window_mean_u8");
+        hipLaunchKernelGGL(window_mean_px_kernel<LIGHT>, grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, tables, blur, gt,
+                           gray, hw);
+    SPEI_CHECK_LAUNCH(name);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int spei_window_mean_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
+                                   unsigned char* blur, unsigned char* gt, float* gray, int H, int W, spei_stream_t stream) {
+    return window_mean<false>("spei_window_mean_u8", src, frame_stride, T, runs, runs_host, M, nullptr, nullptr, blur, gt, gray, H, W, stream);
+}
+
+extern "C" int spei_window_mean_light_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
+                                         const uint32_t* tables, const uint32_t* tables_host, unsigned char* blur, unsigned char* gt,
+                                         float* gray, int H, int W, spei_stream_t stream) {
+    return window_mean<true>("spei_window_mean_light_u8", src, frame_stride, T, runs, runs_host, M, tables, tables_host, blur, gt, gray, H, W,
+                             stream);
 }

@@ -24,7 +24,14 @@
 // frames in registers (two bytes per dword, 16 bits each: a sum is at most 15 * 255 = 3825), up to four frames' loads in flight
 // before the first add, divides (blurset.hip's multiply and shift) and packs the four pixels into LDS as above.  Everything after
 // the barrier is shared.  A ground-truth record is a run of length 1 at the run's middle frame.
+//
+// spei_train_batch_runs_light_u8 is that kernel with the run averaged in LINEAR light (csrc/light.h) — the bytes of
+// spei_window_mean_light_u8's blur[m]: the workgroup stages lin[] and thr[] in LDS, thread t decodes its 12 bytes of every frame (one
+// LDS read each) into twelve 32-bit sums — the packed two-sums-per-dword trick does not carry over: a sum reaches 15 (2^24 - 1) —
+// divides (light.h's multiply-high), encodes by the binary search over thr[] and packs the four pixels into LDS as above.  A record
+// of length 1 (every ground-truth record) is loaded as is.  Everything after the barrier is shared.
 #include "common.h"
+#include "light.h"
 
 #include <type_traits>
 
@@ -46,10 +53,39 @@ __device__ __forceinline__ void load12(const unsigned char* s, bool dwords, uint
     }
 }
 
-template <typename Rec>
-__global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict__ table, int n_in, float* __restrict__ input,
-                                                          float* __restrict__ gt, int P, int tiles, float scale) {
+// 12 bytes of a run of len frames fstride apart averaged in linear light (csrc/light.h), packed as load12 packs them; tab = lin[256],
+// thr[256] in LDS, staged iff len > 1
+__device__ __forceinline__ void run_light12(const unsigned char* s, int64_t fstride, int len, bool dwords, const uint32_t* tab, uint32_t w[3]) {
+    if (len == 1) {                                                      // encode(lin[c]) == c
+        load12(s, dwords, w);
+        return;
+    }
+    uint32_t sum[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) sum[j] = 0u;
+    for (int t0 = 0; t0 < len; t0 += RUN_LOADS) {
+        uint32_t q[RUN_LOADS][3];
+#pragma unroll
+        for (int u = 0; u < RUN_LOADS; ++u)
+            if (t0 + u < len) load12(s + (int64_t)(t0 + u) * fstride, dwords, q[u]);
+#pragma unroll
+        for (int u = 0; u < RUN_LOADS; ++u)
+            if (t0 + u < len) {
+#pragma unroll
+                for (int j = 0; j < 12; ++j) sum[j] += tab[(q[u][j >> 2] >> (8 * (j & 3))) & 0xffu];
+            }
+    }
+    const uint32_t magic = light_magic(len);
+    w[0] = w[1] = w[2] = 0u;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) w[j >> 2] |= light_encode(tab + 256, light_quot(sum[j], magic)) << (8 * (j & 3));
+}
+
+template <typename Rec, bool LIGHT>
+__global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict__ table, const uint32_t* __restrict__ tables, int n_in,
+                                                          float* __restrict__ input, float* __restrict__ gt, int P, int tiles, float scale) {
     constexpr bool RUNS = std::is_same<Rec, spei_run_record>::value;
+    static_assert(RUNS || !LIGHT, "a light averages runs");
     __shared__ uint32_t lds[TILE * PITCH];
     const int r = blockIdx.y;
     const Rec rec = table[r];
@@ -62,6 +98,12 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict_
     const int cy_lo = rot ? (vf ? P - oj0 - nJ : oj0) : (vf ? P - oi0 - nI : oi0);
     const int cx_lo = rot ? (hf ? oi0 : P - oi0 - nI) : (hf ? P - oj0 - nJ : oj0);
     if (!zero) {
+        const uint32_t* tab = nullptr;                                   // LIGHT: lin[256], thr[256] in LDS, for a run of 2 or more frames
+        if constexpr (LIGHT) {
+            __shared__ uint32_t light[LIGHT_WORDS];
+            if (rec.length > 1) light_stage(light, tables);
+            tab = light;
+        }
         if (row < nR && g4 < nC) {
             const unsigned char* s = reinterpret_cast<const unsigned char*>(rec.src) + (int64_t)(rec.y0 + cy_lo + row) * rec.pitch +
                                      (int64_t)(rec.x0 + cx_lo + g4) * 3;
@@ -70,29 +112,33 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict_
             if constexpr (RUNS) {
                 const int len = rec.length;
                 dwords = dwords && (len == 1 || (rec.frame_stride & 3) == 0);                                  // ... in every frame of the run
-                // even[k] holds the sums of bytes 0 and 2 of dword k in its two halves, odd[k] those of bytes 1 and 3
-                uint32_t even[3] = {0u, 0u, 0u}, odd[3] = {0u, 0u, 0u};
-                for (int t0 = 0; t0 < len; t0 += RUN_LOADS) {
-                    uint32_t q[RUN_LOADS][3];
+                if constexpr (LIGHT) {
+                    run_light12(s, rec.frame_stride, len, dwords, tab, w);
+                } else {
+                    // even[k] holds the sums of bytes 0 and 2 of dword k in its two halves, odd[k] those of bytes 1 and 3
+                    uint32_t even[3] = {0u, 0u, 0u}, odd[3] = {0u, 0u, 0u};
+                    for (int t0 = 0; t0 < len; t0 += RUN_LOADS) {
+                        uint32_t q[RUN_LOADS][3];
 #pragma unroll
-                    for (int u = 0; u < RUN_LOADS; ++u) {
-                        q[u][0] = q[u][1] = q[u][2] = 0u;
-                        if (t0 + u < len) load12(s + (int64_t)(t0 + u) * rec.frame_stride, dwords, q[u]);
-                    }
-#pragma unroll
-                    for (int u = 0; u < RUN_LOADS; ++u)
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            even[k] += q[u][k] & 0x00ff00ffu;
-                            odd[k] += (q[u][k] >> 8) & 0x00ff00ffu;
+                        for (int u = 0; u < RUN_LOADS; ++u) {
+                            q[u][0] = q[u][1] = q[u][2] = 0u;
+                            if (t0 + u < len) load12(s + (int64_t)(t0 + u) * rec.frame_stride, dwords, q[u]);
                         }
-                }
-                // (sum * m) >> 16 == sum / len with m = ceil(2^16 / len), for every sum <= 15 * 255 and len <= 15 (csrc/blurset.hip)
-                const uint32_t magic = (65536u + len - 1) / len;
 #pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    w[k] = (((even[k] & 0xffffu) * magic) >> 16) | ((((odd[k] & 0xffffu) * magic) >> 16) << 8) |
-                           ((((even[k] >> 16) * magic) >> 16) << 16) | ((((odd[k] >> 16) * magic) >> 16) << 24);
+                        for (int u = 0; u < RUN_LOADS; ++u)
+#pragma unroll
+                            for (int k = 0; k < 3; ++k) {
+                                even[k] += q[u][k] & 0x00ff00ffu;
+                                odd[k] += (q[u][k] >> 8) & 0x00ff00ffu;
+                            }
+                    }
+                    // (sum * m) >> 16 == sum / len with m = ceil(2^16 / len), for every sum <= 15 * 255 and len <= 15 (csrc/blurset.hip)
+                    const uint32_t magic = (65536u + len - 1) / len;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        w[k] = (((even[k] & 0xffffu) * magic) >> 16) | ((((odd[k] & 0xffffu) * magic) >> 16) << 8) |
+                               ((((even[k] >> 16) * magic) >> 16) << 16) | ((((odd[k] >> 16) * magic) >> 16) << 24);
+                }
             } else {
                 load12(s, dwords, w);
             }
@@ -125,9 +171,9 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict_
 }
 
 // Every record is checked HERE, on the host copy: the kernel never meets a record that leaves its frame or its clip
-template <typename Rec>
+template <typename Rec, bool LIGHT = false>
 int train_batch(const char* name, const Rec* table, const Rec* table_host, int n_in, int n_gt, float* input, float* gt, int P, float rgb_range,
-                spei_stream_t stream) {
+                spei_stream_t stream, const uint32_t* tables = nullptr, const uint32_t* tables_host = nullptr) {
     SPEI_REQUIRE(table && table_host, "%s: null record table (the device table and its host copy are both required)", name);
     SPEI_REQUIRE(n_in >= 0 && n_gt >= 0 && n_in + n_gt > 0 && n_in + n_gt <= 65535, "%s: bad record counts %d + %d", name, n_in, n_gt);
     SPEI_REQUIRE((n_in == 0 || input) && (n_gt == 0 || gt), "%s: null dst", name);
@@ -151,10 +197,12 @@ int train_batch(const char* name, const Rec* table, const Rec* table_host, int n
                          c.H, c.pitch);
         }
     }
+    if constexpr (LIGHT)
+        if (light_check(name, tables, tables_host)) return -1;
     const int tiles = cdiv(P, TILE);
     const float scale = (float)((double)rgb_range / 255.0);
-    hipLaunchKernelGGL(train_batch_kernel<Rec>, dim3(tiles * tiles, n_in + n_gt), dim3(256), 0, (hipStream_t)stream, table, n_in, input, gt, P,
-                       tiles, scale);
+    hipLaunchKernelGGL((train_batch_kernel<Rec, LIGHT>), dim3(tiles * tiles, n_in + n_gt), dim3(256), 0, (hipStream_t)stream, table, tables, n_in,
+                       input, gt, P, tiles, scale);
     SPEI_CHECK_LAUNCH(name);
     return 0;
 }
@@ -169,4 +217,11 @@ extern "C" int spei_train_batch_u8(const spei_crop_record* table, const spei_cro
 extern "C" int spei_train_batch_runs_u8(const spei_run_record* table, const spei_run_record* table_host, int n_in, int n_gt, float* input,
                                         float* gt, int P, float rgb_range, spei_stream_t stream) {
     return train_batch("spei_train_batch_runs_u8", table, table_host, n_in, n_gt, input, gt, P, rgb_range, stream);
+}
+
+extern "C" int spei_train_batch_runs_light_u8(const spei_run_record* table, const spei_run_record* table_host, int n_in, int n_gt,
+                                              const uint32_t* tables, const uint32_t* tables_host, float* input, float* gt, int P,
+                                              float rgb_range, spei_stream_t stream) {
+    return train_batch<spei_run_record, true>("spei_train_batch_runs_light_u8", table, table_host, n_in, n_gt, input, gt, P, rgb_range, stream,
+                                              tables, tables_host);
 }

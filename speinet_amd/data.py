@@ -9,7 +9,7 @@
 and, beyond the reference (which precomputes its blurry sets), the same loop fed from SHARP footage, the blur synthesised per batch:
 
     SharpClipSet      folders of sharp frames cut into runs as blurset.write_dataset cuts them, re-drawn for every epoch: epoch e is the
-                      set write_dataset(seed = seed + e) would write, as ClipSet would scan it — but nothing is written
+                      set write_dataset(seed = seed + e, light = light) would write, as ClipSet would scan it — but nothing is written
     SharpStore        the sharp frames, decoded once, uint8 [T,H,W,3] per clip on the device
     run_records       one batch as spei_run_record: an input frame is a run of sharp frames, the ground truth the run's middle frame
     SharpTrainLoader  TrainLoader on that table and spei_train_batch_runs_u8, which averages each crop's run in its load phase
@@ -177,10 +177,13 @@ class SharpClipSet(Windows):
     seed=seed + epoch, ...)` followed by `ClipSet(out, True, ...)` would give — per source clip the runs of `blurset.plan_dataset`,
     label 1 for a run of at most `threshold` frames, names `<clip>.<run index, six digits>`, truncated to n_frames_per_video RUNS,
     pre / sub from the truncated labels — so `len()` and `sample(idx)` are ClipSet's on that set.  A virtual clip also carries `starts`
-    and `lengths` (the runs' sharp frames) and `source` (its index in `sharp`, the scanned folders).  The constructor plans epoch 0."""
+    and `lengths` (the runs' sharp frames) and `source` (its index in `sharp`, the scanned folders).  `light` (speinet_amd.light: "code",
+    "srgb", "gamma:<g>") is the light the loader averages the runs in — write_dataset's `light`; it does not touch the plan.  The
+    constructor plans epoch 0."""
 
     def __init__(self, dir_sharp: str, ratios=(0.5,), threshold: int = 5, window_range=(1, 15), seed: int = 0, n_sequence: int = 3,
-                 n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None):
+                 n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None, light="code"):
+        from . import light as _light
         from .blurset import clip_folders
         from .video import frames_of
         self.dir_data, self.train, self.n_seq, self.references = dir_sharp, True, int(n_sequence), bool(references)
@@ -188,6 +191,9 @@ class SharpClipSet(Windows):
             raise ValueError("samples with references are windows of 3 frames (the reference's zeroing test reads names 2 and 3: videodata_nfs.py:254)")
         self.ratios, self.threshold, self.window_range = list(ratios), int(threshold), tuple(window_range)    # checked by plan_dataset
         self.seed, self.n_frames_per_video = int(seed), int(n_frames_per_video)
+        self.light = _light.name(light)
+        if self.light != _light.CODE:
+            _light.tables(self.light)                                        # ValueError for a light without valid tables
         self.sharp = []
         for name, files in clip_folders(dir_sharp):
             try:
@@ -219,9 +225,9 @@ class SharpClipSet(Windows):
         self._count(f"{self.dir_data} (epoch {epoch})")
 
     def summary(self) -> str:
-        """One line on the current plan: its runs and how many are labelled sharp."""
+        """One line on the current plan: its runs, how many are labelled sharp and the light they are averaged in."""
         runs, sharp = sum(c["T"] for c in self.clips), sum(sum(c["labels"]) for c in self.clips)
-        return f"Plan {self.epoch} of {self.dir_data}: {runs} runs of {sum(c['T'] for c in self.sharp)} sharp frames, {sharp} labelled sharp"
+        return f"Plan {self.epoch} of {self.dir_data}: {runs} runs of {sum(c['T'] for c in self.sharp)} sharp frames, {sharp} labelled sharp, light {self.light}"
 
     def nbytes(self) -> int:
         """Bytes of every sharp frame as uint8 RGB (from the image headers)."""
@@ -547,16 +553,22 @@ class TrainLoader:
 class SharpTrainLoader(TrainLoader):
     """TrainLoader fed from sharp footage: the table is `run_records`, the launch spei_train_batch_runs_u8, which averages the run of
     every crop in its load phase; ring, side stream and prefetch thread are TrainLoader's.  Every `iter()` is one epoch under its own
-    plan (SharpSampler; `replan=False`: plan 0 throughout).  All launches of an epoch are issued before the next one is planned."""
+    plan (SharpSampler; `replan=False`: plan 0 throughout).  All launches of an epoch are issued before the next one is planned.  With
+    `clipset.light` other than "code" the launch is spei_train_batch_runs_light_u8: the light's tables are uploaded here, once, and
+    handed to every launch."""
     RECORD = RUN_RECORD
 
     def __init__(self, clipset: SharpClipSet, store: SharpStore, batch: int, patch: int = 200, seed: int = 1, augment: bool = True,
                  rgb_range: float = 1, prefetch: bool = True, rank: Optional[int] = None, world: Optional[int] = None, replan: bool = True):
         super().__init__(clipset, store, batch, patch, seed, augment, rgb_range, prefetch, rank, world,
                          sampler=SharpSampler(clipset, batch, patch, seed, augment, rank, world, replan))
+        self.light = clipset.light
+        if self.light != "code":
+            from . import light as _light
+            _light.device_tables(self.light, self.device)
 
     def _records(self, items) -> np.ndarray:
         return run_records(self.clipset, self.store, items)
 
     def _build(self, *args) -> None:
-        self.ctx.train_batch_runs(*args)
+        self.ctx.train_batch_runs(*args, light=self.light)

@@ -7,11 +7,11 @@ speinet_amd.trainer.Trainer, fed by speinet_amd.data.TrainLoader.
 
 Both directories hold blur/<clip>/*, gt/<clip>/* and (model speinet) label/<clip>.npy.  In place of `--dir_data`,
 
-        --dir_sharp <dir of folders of sharp frames> [--blur_ratio 0.1 0.3 0.5 --blur_threshold 5 --no_replan]
+        --dir_sharp <dir of folders of sharp frames> [--blur_ratio 0.1 0.3 0.5 --blur_threshold 5 --no_replan --blur_light code|srgb|gamma:<g>]
 
 trains from sharp high-frame-rate footage directly (an extension beyond the reference, which precomputes its sets): the frames stay on
-the device as uint8, every epoch e trains on the set `python -m speinet_amd.blurset --seed <seed + e>` would write — runs, labels and
-references re-drawn, nothing written — and every batch is averaged, cropped and augmented by one launch (data.SharpTrainLoader);
+the device as uint8, every epoch e trains on the set `python -m speinet_amd.blurset --seed <seed + e> --light <blur_light>` would write —
+runs, labels and references re-drawn, nothing written — and every batch is averaged, cropped and augmented by one launch (data.SharpTrainLoader);
 `--no_replan` keeps epoch 0's set.  The validation set stays a written one.  Names and defaults are those of the reference's
 option/__init__.py and its SPEINet template.  Per epoch, in the reference's order: `scheduler.step()`, one `Trainer.step` per batch,
 a log line every `print_every` batches, then `evaluate()` — eval mode, one full-size validation sample at a time through the model's
@@ -249,9 +249,7 @@ def build_model(name: str, device, pre_train: Optional[str] = None, train_precis
     return net
 
 
-def main(argv=None) -> None:
-    from .data import ClipSet, ClipStore, SharpClipSet, SharpStore, SharpTrainLoader, TrainLoader
-    from .loss import Loss
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Train SPEINet (or its swint sub-model) on blur / gt / label folders, or on folders of sharp "
                                              "frames blurred per batch, on one MI355X")
     source = ap.add_mutually_exclusive_group(required=True)
@@ -260,6 +258,8 @@ def main(argv=None) -> None:
     ap.add_argument("--blur_ratio", type=float, nargs="+", default=[0.5], help="--dir_sharp: share of sharp runs; several: one is drawn per clip")
     ap.add_argument("--blur_threshold", type=int, default=5, help="--dir_sharp: a run of at most this many frames is a sharp frame (label 1)")
     ap.add_argument("--no_replan", action="store_true", help="--dir_sharp: keep epoch 0's runs for every epoch")
+    ap.add_argument("--blur_light", default="code", help="--dir_sharp: the light the runs are averaged in: code (code values), srgb or "
+                                                         "gamma:<g> (linear light; speinet_amd.light)")
     ap.add_argument("--dir_data_test", required=True)
     ap.add_argument("--save", required=True)
     ap.add_argument("--model", default="speinet", choices=("speinet", "swint"))
@@ -279,14 +279,31 @@ def main(argv=None) -> None:
     ap.add_argument("--residency", default="device", choices=("device", "host"))
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
+    return ap
+
+
+def main(argv=None) -> None:
+    from . import light as _light
+    from .data import ClipSet, ClipStore, SharpClipSet, SharpStore, SharpTrainLoader, TrainLoader
+    from .loss import Loss
+    ap = parser()
     a = ap.parse_args(argv)
+    try:
+        blur_light = _light.name(a.blur_light)
+        if blur_light != _light.CODE:
+            _light.tables(blur_light)
+    except ValueError as e:
+        ap.error(f"--blur_light: {e}")
+    if a.dir_data and blur_light != _light.CODE:
+        ap.error(f"--blur_light {blur_light} averages the runs of --dir_sharp; a written set (--dir_data) holds its blur already: make it "
+                 "with `python -m speinet_amd.blurset --light`")
     refs = a.model == "speinet"
     if a.dir_sharp and a.residency != "device":
         ap.error("--dir_sharp keeps the sharp frames on the device (--residency device); a set that does not fit is written with "
                  "`python -m speinet_amd.blurset` and trained with --dir_data")
     if a.dir_sharp:
         train_set = SharpClipSet(a.dir_sharp, a.blur_ratio, a.blur_threshold, seed=a.seed, n_frames_per_video=a.n_frames_per_video,
-                                 references=refs, patch=a.patch_size)
+                                 references=refs, patch=a.patch_size, light=blur_light)
     else:
         train_set = ClipSet(a.dir_data, True, 3, a.n_frames_per_video, references=refs, patch=a.patch_size)
     val_set = ClipSet(a.dir_data_test, False, 3, a.n_frames_per_video, references=refs)

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, y4m
+from . import light as _light
 from .pack import BF16, F16, F32, LP_DTYPE, PackedW, fmt_of
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
@@ -304,12 +305,13 @@ def frame_pair_stats_u16(u16: torch.Tensor, depth: int, prev: Optional[torch.Ten
 
 
 def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: Optional[torch.Tensor] = None,
-                   gt: Optional[torch.Tensor] = None):
+                   gt: Optional[torch.Tensor] = None, light=None):
     """The reference's blur synthesis on resident frames (csrc/blurset.hip): uint8 frames [T,H,W,3] on the device (each frame packed,
     any frame stride) and M runs `starts[m]`, `lengths[m]` (1..15 frames, inside the clip) -> (blur uint8 [M,H,W,3] = the per-byte
     integer mean of each run, gt uint8 [M,H,W,3] = the run's middle frame `start + length // 2`, the detector's gray plane [M,H,W] of
     the blurry frames or None when not `gray`).  `blur` / `gt` (optional): contiguous destinations.  One launch on the current stream;
-    the runs are checked on the host before it."""
+    the runs are checked on the host before it.  `light`: None or "code" is that launch (spei_window_mean_u8); "srgb" or "gamma:<g>"
+    averages in linear light (speinet_amd.light, spei_window_mean_light_u8), the gray plane still that of the encoded bytes."""
     assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4
     t, h, w, c = u8.shape
     assert c == 3 and u8.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
@@ -325,9 +327,15 @@ def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: 
     with torch.cuda.device(dev):
         runs = runs_host.to(dev)
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_window_mean_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
-                                           _vp(blur.data_ptr()), _vp(gt.data_ptr()), _vp(g.data_ptr() if g is not None else 0), h, w, st),
-                   "spei_window_mean_u8")
+        if _light.is_code(light):
+            _lib.check(lib.spei_window_mean_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
+                                               _vp(blur.data_ptr()), _vp(gt.data_ptr()), _vp(g.data_ptr() if g is not None else 0), h, w, st),
+                       "spei_window_mean_u8")
+        else:
+            tab, tab_host = _light.device_tables(light, dev)
+            _lib.check(lib.spei_window_mean_light_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
+                                                     _vp(tab.data_ptr()), _vp(tab_host.data_ptr()), _vp(blur.data_ptr()), _vp(gt.data_ptr()),
+                                                     _vp(g.data_ptr() if g is not None else 0), h, w, st), "spei_window_mean_light_u8")
     return blur, gt, g
 
 
@@ -669,16 +677,24 @@ class Ctx:
                                                   patch, float(rgb_range), self._stream()), "spei_train_batch_u8")
 
     def train_batch_runs(self, table: torch.Tensor, table_host: torch.Tensor, n_in: int, n_gt: int, input: torch.Tensor,
-                         gt: torch.Tensor, patch: int, rgb_range: float = 1.0) -> None:
+                         gt: torch.Tensor, patch: int, rgb_range: float = 1.0, light=None) -> None:
         """`train_batch` on run records (speinet_amd.data.RUN_RECORD, 48 bytes each): every output frame is the crop of the per-byte
-        integer mean of a run of 1..15 consecutive resident frames — spei_window_mean_u8's bytes, never written to memory."""
+        integer mean of a run of 1..15 consecutive resident frames — spei_window_mean_u8's bytes, never written to memory.  `light`:
+        None or "code" is that launch; "srgb" or "gamma:<g>" averages in linear light (speinet_amd.light,
+        spei_train_batch_runs_light_u8: `window_mean_u8(light=...)`'s bytes)."""
         nb = (n_in + n_gt) * 48
         assert table.dtype == torch.uint8 and table.numel() >= nb and not table_host.is_cuda and table_host.dtype == torch.uint8 \
             and table_host.is_contiguous() and table_host.numel() >= nb
         assert input.dtype == torch.float32 and input.numel() == n_in * 3 * patch * patch
         assert gt.dtype == torch.float32 and gt.numel() == n_gt * 3 * patch * patch
-        _lib.check(_lib.lib().spei_train_batch_runs_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(input),
-                                                       self._tp(gt), patch, float(rgb_range), self._stream()), "spei_train_batch_runs_u8")
+        if _light.is_code(light):
+            _lib.check(_lib.lib().spei_train_batch_runs_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(input),
+                                                           self._tp(gt), patch, float(rgb_range), self._stream()), "spei_train_batch_runs_u8")
+            return
+        tab, tab_host = _light.device_tables(light, self.device)
+        _lib.check(_lib.lib().spei_train_batch_runs_light_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(tab),
+                                                             C.c_void_p(tab_host.data_ptr()), self._tp(input), self._tp(gt), patch,
+                                                             float(rgb_range), self._stream()), "spei_train_batch_runs_light_u8")
 
     def rl_prior(self, img: torch.Tensor, iters: int, lam: float = 0.01) -> torch.Tensor:
         """img [3,H,W] -> [3,H,W]."""
