@@ -207,10 +207,35 @@ int spei_resblock_gates_batched(const void* x1, int x1_fmt, int batch, int H, in
 int spei_resblock_apply_batched(const float* x, const void* x1, int x1_fmt, const float* s, const float* g1, const float* g2, float* out,
                                 int batch, int H, int W, int C, spei_stream_t stream);
 
+/* The batched apply with a route per launched map instead of one dense fp32 output (the hand-offs between the encoder stacks).  Route i
+ * computes x' = x + x1*s + (x1*g1 + x1*g2) of map `src` — plus x' of map `partner` when partner >= 0 (speinet.py:84,132: the pair
+ * sums enc(RL(x)) + enc(x); a partner needs no route of its own) — and writes it to `out32` (fp32, row stride `ld32` floats; NULL: not
+ * written) and / or, rounded to `fmt`, to `out16` (dense [H*W][C]; NULL: not written).  x' is evaluated exactly as by
+ * spei_resblock_apply, so out32 holds that entry point's bits (with `extra` = the partner's x') and out16 their rounding.  The
+ * routes are read on the host during the call (at most SPEI_APPLY_MAX_ROUTES) and travel to the kernel by value. */
+#define SPEI_APPLY_MAX_ROUTES 16
+typedef struct {
+    float* out32;
+    void* out16;
+    int32_t ld32;
+    int32_t src;
+    int32_t partner; /* -1: none */
+    int32_t reserved;
+} SpeiApplyRoute;
+typedef struct {
+    SpeiApplyRoute r[SPEI_APPLY_MAX_ROUTES];
+} SpeiApplyRoutes;
+int spei_resblock_apply_routed(int fmt, const float* x, const void* x1, int x1_fmt, const float* s, const float* g1, const float* g2,
+                               const SpeiApplyRoute* routes, int nroutes, int batch, int H, int W, int C, spei_stream_t stream);
+
 /* K7 — LayerNorm over C=256, eps 1e-5 (model/swinir.py:244-245,279,528-529,776).  gamma/beta may be NULL
  * (affine folded into the following linear by pack.py); out_fmt: y is fp32, or 16-bit when it only feeds a GEMM. */
 int spei_layernorm256(const float* x, void* y, int out_fmt, const float* gamma, const float* beta, int64_t M,
                       spei_stream_t stream);
+/* y = LayerNorm(LayerNorm(x) * gamma + beta) without affine, stored as out_fmt: the two spei_layernorm256 launches of the Swin entry
+ * (patch-embed norm, then norm1 of the y side) with the first result held in registers; the same expressions in the same order. */
+int spei_layernorm256_twice(const float* x, void* y, int out_fmt, const float* gamma, const float* beta, int64_t M,
+                            spei_stream_t stream);
 
 /* K8 — window attention core: cyclic shift, 5x5 partition, softmax(q k^T + relbias + shift mask) v, reverse
  * (model/swinir.py:115-149, 215-236, 250-275).  q [H*W][256] (scale folded), kv [H*W][512] (K then V, head major),
@@ -281,6 +306,11 @@ int spei_rot90(const float* in, int ldi, float* out, int H, int W, int C, spei_s
  * sum to 1), which the throughput mode uses to run those 1x1 convs at a quarter of the pixels. */
 int spei_upsample_bicubic(const float* in, int ldi, float* out, int ldo, int H, int W, int C, int s, int act,
                           spei_stream_t stream);
+/* The same with the output stored as out_fmt (SPEI_F32, SPEI_BF16 or SPEI_F16; `ldo` in elements): the interpolated (and rectified)
+ * fp32 value rounded to nearest even, for maps whose only readers are operands of single-product 16-bit convs.  A 16-bit output
+ * needs s == 2, C, ldi and ldo multiples of 4, `in` 16-byte and `out` 8-byte aligned. */
+int spei_upsample_bicubic_fmt(const float* in, int ldi, void* out, int ldo, int out_fmt, int H, int W, int C, int s, int act,
+                              spei_stream_t stream);
 
 /* K14 — out = a + b over n floats. */
 int spei_add(const float* a, const float* b, float* out, int64_t n, spei_stream_t stream);

@@ -351,6 +351,17 @@ __global__ __launch_bounds__(256) void gate_maps_kernel(int H, int W, int C, flo
 }
 
 // ---- apply ------------------------------------------------------------------------------------------
+// x' = x + se(x1) + (cw(x1) + hc(x1)) of one element (block.py:136-140): a = x, b = x1, sv / u / v = the SE scale and the two gate
+// maps.  The roundings are spelled out — b * v, two fused multiply-adds, one add, which is how the compiler contracted
+// `(b * sv + (b * u + b * v)) + a` in resblock_apply_kernel — so that every kernel that evaluates x' gives the same bits.
+__device__ __forceinline__ float apply_x3(float a, float b, float sv, float u, float v) {
+    return __fmaf_rn(b, sv, __fmaf_rn(b, u, b * v)) + a;
+}
+__device__ __forceinline__ float4 apply_x3(const float4 a, const float4 b, const float4 sv, const float4 u, const float4 v) {
+    return make_float4(apply_x3(a.x, b.x, sv.x, u.x, v.x), apply_x3(a.y, b.y, sv.y, u.y, v.y), apply_x3(a.z, b.z, sv.z, u.z, v.z),
+                       apply_x3(a.w, b.w, sv.w, u.w, v.w));
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void resblock_apply_kernel(const float* __restrict__ x, const T* __restrict__ x1,
                                                              const float* __restrict__ s, const float* __restrict__ g1,
@@ -373,17 +384,55 @@ __global__ __launch_bounds__(256) void resblock_apply_kernel(const float* __rest
         const float4 sv = *reinterpret_cast<const float4*>(s + c);
         const float4 u = *reinterpret_cast<const float4*>(g1 + (size_t)yy * C + c);
         const float4 v = *reinterpret_cast<const float4*>(g2 + (size_t)xx * C + c);
-        float4 o;
-        // x3 = se(x1) + (cw(x1) + hc(x1));  return x3 + x   (block.py:136-140)
-        o.x = (b.x * sv.x + (b.x * u.x + b.x * v.x)) + a.x;
-        o.y = (b.y * sv.y + (b.y * u.y + b.y * v.y)) + a.y;
-        o.z = (b.z * sv.z + (b.z * u.z + b.z * v.z)) + a.z;
-        o.w = (b.w * sv.w + (b.w * u.w + b.w * v.w)) + a.w;
+        float4 o = apply_x3(a, b, sv, u, v);
         if (extra) {
             const float4 e = *reinterpret_cast<const float4*>(extra + pix * C + c);
             o.x += e.x; o.y += e.y; o.z += e.z; o.w += e.w;
         }
         *reinterpret_cast<float4*>(out + pix * ldo + c) = o;
+    }
+}
+
+// The batched apply with a route per launched map (blockIdx.y = route): x' of map `src` — plus x' of map `partner` when there is one
+// (the encoder's pair sums enc(RL(x)) + enc(x)) — goes to an fp32 destination with its own row stride and / or to a dense 16-bit
+// destination (the operand of a single-product conv, rounded here instead of in that conv's staging).  Same access widths as above.
+template <typename T, typename LP>
+__global__ __launch_bounds__(256) void resblock_apply_routed_kernel(const float* __restrict__ x, const T* __restrict__ x1,
+                                                                    const float* __restrict__ s, const float* __restrict__ g1,
+                                                                    const float* __restrict__ g2, const SpeiApplyRoutes routes,
+                                                                    int H, int W, int C) {
+    const int cg = C / 4;
+    const int64_t total = (int64_t)H * W * cg;
+    const SpeiApplyRoute rt = routes.r[blockIdx.y];
+    const size_t m0 = (size_t)rt.src, m1 = (size_t)(rt.partner < 0 ? rt.src : rt.partner);
+    const bool pair = rt.partner >= 0;
+    const float* xa = x + m0 * H * W * C;   const float* xb = x + m1 * H * W * C;
+    const T* ya = x1 + m0 * H * W * C;      const T* yb = x1 + m1 * H * W * C;
+    const float* sa = s + m0 * C;           const float* sb = s + m1 * C;
+    const float* ua = g1 + m0 * H * C;      const float* ub = g1 + m1 * H * C;
+    const float* va = g2 + m0 * W * C;      const float* vb = g2 + m1 * W * C;
+    float* const o32 = rt.out32;
+    LP* const o16 = reinterpret_cast<LP*>(rt.out16);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i % cg) * 4;
+        const int64_t pix = i / cg;
+        const int xx = (int)(pix % W), yy = (int)(pix / W);
+        auto xprime = [&](const float* xp, const T* yp, const float* sp, const float* up, const float* vp) {
+            const float4 a = *reinterpret_cast<const float4*>(xp + pix * C + c);
+            const f32x4 bv = ld4<T>(yp + pix * C + c);
+            const float4 b = make_float4(bv[0], bv[1], bv[2], bv[3]);
+            const float4 sv = *reinterpret_cast<const float4*>(sp + c);
+            const float4 u = *reinterpret_cast<const float4*>(up + (size_t)yy * C + c);
+            const float4 v = *reinterpret_cast<const float4*>(vp + (size_t)xx * C + c);
+            return apply_x3(a, b, sv, u, v);
+        };
+        float4 o = xprime(xa, ya, sa, ua, va);
+        if (pair) {
+            const float4 e = xprime(xb, yb, sb, ub, vb);
+            o.x += e.x; o.y += e.y; o.z += e.z; o.w += e.w;
+        }
+        if (o32) *reinterpret_cast<float4*>(o32 + pix * rt.ld32 + c) = o;
+        if (o16) *reinterpret_cast<typename lpv<LP>::x4*>(o16 + pix * C + c) = to_lp4<LP>(f32x4{o.x, o.y, o.z, o.w});
     }
 }
 
@@ -469,4 +518,39 @@ extern "C" int spei_resblock_apply(const float* x, const void* x1, int x1_fmt, c
 extern "C" int spei_resblock_apply_batched(const float* x, const void* x1, int x1_fmt, const float* s, const float* g1, const float* g2,
                                            float* out, int batch, int H, int W, int C, spei_stream_t stream) {
     return resblock_apply_run(x, x1, x1_fmt, s, g1, g2, nullptr, out, C, batch, H, W, C, stream);
+}
+
+template <typename LP>
+static void apply_routed_launch(const float* x, const void* x1, bool x1_lp, const float* s, const float* g1, const float* g2,
+                                const SpeiApplyRoutes& routes, dim3 grid, int H, int W, int C, hipStream_t st) {
+    if (x1_lp) hipLaunchKernelGGL((resblock_apply_routed_kernel<LP, LP>), grid, dim3(256), 0, st, x, (const LP*)x1, s, g1, g2, routes, H, W, C);
+    else hipLaunchKernelGGL((resblock_apply_routed_kernel<float, LP>), grid, dim3(256), 0, st, x, (const float*)x1, s, g1, g2, routes, H, W, C);
+}
+
+extern "C" int spei_resblock_apply_routed(int fmt, const float* x, const void* x1, int x1_fmt, const float* s, const float* g1, const float* g2,
+                                          const SpeiApplyRoute* routes, int nroutes, int batch, int H, int W, int C, spei_stream_t stream) {
+    SPEI_REQUIRE(x && x1 && s && g1 && g2 && routes, "spei_resblock_apply_routed: null pointer");
+    SPEI_REQUIRE(fmt == SPEI_BF16 || fmt == SPEI_F16, "spei_resblock_apply_routed: fmt=%d", fmt);
+    SPEI_REQUIRE(x1_fmt == SPEI_F32 || x1_fmt == fmt, "spei_resblock_apply_routed: x1_fmt=%d with fmt=%d", x1_fmt, fmt);
+    SPEI_REQUIRE(batch >= 1 && batch <= 65535 && nroutes >= 1 && nroutes <= SPEI_APPLY_MAX_ROUTES, "spei_resblock_apply_routed: batch=%d nroutes=%d",
+                 batch, nroutes);
+    SPEI_REQUIRE(C % 4 == 0 && H > 0 && W > 0, "spei_resblock_apply_routed: bad shape");
+    SPEI_REQUIRE(((uintptr_t)x | (uintptr_t)x1 | (uintptr_t)s | (uintptr_t)g1 | (uintptr_t)g2) % 16 == 0, "spei_resblock_apply_routed: 16-byte alignment required");
+    SpeiApplyRoutes rs = {};
+    for (int i = 0; i < nroutes; ++i) {
+        const SpeiApplyRoute& r = routes[i];
+        SPEI_REQUIRE(r.src >= 0 && r.src < batch && r.partner < batch && r.partner != r.src, "spei_resblock_apply_routed: route %d: src=%d partner=%d of %d maps",
+                     i, r.src, r.partner, batch);
+        SPEI_REQUIRE(r.out32 || r.out16, "spei_resblock_apply_routed: route %d has no destination", i);
+        SPEI_REQUIRE(!r.out32 || (r.ld32 >= C && r.ld32 % 4 == 0 && (uintptr_t)r.out32 % 16 == 0), "spei_resblock_apply_routed: route %d: ld32=%d", i, r.ld32);
+        SPEI_REQUIRE(!r.out16 || (uintptr_t)r.out16 % 8 == 0, "spei_resblock_apply_routed: route %d: 16-bit destination not 8-byte aligned", i);
+        rs.r[i] = r;
+    }
+    const int64_t total = (int64_t)H * W * (C / 4);
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const dim3 grid(blocks, nroutes);
+    if (fmt == SPEI_BF16) apply_routed_launch<__bf16>(x, x1, x1_fmt != SPEI_F32, s, g1, g2, rs, grid, H, W, C, (hipStream_t)stream);
+    else apply_routed_launch<_Float16>(x, x1, x1_fmt != SPEI_F32, s, g1, g2, rs, grid, H, W, C, (hipStream_t)stream);
+    SPEI_CHECK_LAUNCH("spei_resblock_apply_routed");
+    return 0;
 }

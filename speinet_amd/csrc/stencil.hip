@@ -307,7 +307,9 @@ __global__ __launch_bounds__(256) void bicubic_kernel(const float* __restrict__ 
 // neighbourhood (y - 2 .. y + 2, x - 2 .. x + 2) between them — 25 loads for four outputs instead of 64 (the one-output-per-thread
 // kernel above is bound by its load instructions: 87 us for 181 MB).  Same separable order as above (four horizontal taps per row,
 // then four vertical taps), the two coefficient sets (t = 0.75 for even, 0.25 for odd outputs) are exact in fp32.
-__global__ __launch_bounds__(256) void bicubic2x_kernel(const float* __restrict__ in, int ldi, float* __restrict__ out, int ldo,
+// TO: the output's storage type (float, or the 16-bit format of the convs that read it: rounded as their staging would round it).
+template <typename TO>
+__global__ __launch_bounds__(256) void bicubic2x_kernel(const float* __restrict__ in, int ldi, TO* __restrict__ out, int ldo,
                                                         int H, int W, int C, int relu) {
     const int cg = C / 4;
     const int64_t total = (int64_t)H * W * cg;
@@ -352,21 +354,35 @@ __global__ __launch_bounds__(256) void bicubic2x_kernel(const float* __restrict_
                     for (int a = 1; a < 4; ++a) r = fmaf(h[py + a][e], cy[a], r);
                     acc[e] = relu ? fmaxf(r, 0.f) : r;
                 }
-                *reinterpret_cast<f32x4*>(out + ((size_t)(2 * y + py) * (2 * W) + 2 * x + px) * ldo + c) = acc;
+                TO* o = out + ((size_t)(2 * y + py) * (2 * W) + 2 * x + px) * ldo + c;
+                if constexpr (sizeof(TO) == 4) *reinterpret_cast<f32x4*>(o) = acc;
+                else *reinterpret_cast<typename lpv<TO>::x4*>(o) = to_lp4<TO>(acc);
             }
     }
 }
 
-extern "C" int spei_upsample_bicubic(const float* in, int ldi, float* out, int ldo, int H, int W, int C, int s, int act,
-                                     spei_stream_t stream) {
-    SPEI_REQUIRE(in && out && H > 0 && W > 0 && C > 0 && (s == 2 || s == 4), "spei_upsample_bicubic: bad arguments");
+static int upsample_bicubic_run(const float* in, int ldi, void* out_, int ldo, int out_fmt, int H, int W, int C, int s, int act,
+                                spei_stream_t stream) {
+    SPEI_REQUIRE(in && out_ && H > 0 && W > 0 && C > 0 && (s == 2 || s == 4), "spei_upsample_bicubic: bad arguments");
     SPEI_REQUIRE(act == SPEI_ACT_NONE || act == SPEI_ACT_RELU, "spei_upsample_bicubic: act=%d", act);
     SPEI_REQUIRE(ldi >= C && ldo >= C, "spei_upsample_bicubic: bad row strides");
+    SPEI_REQUIRE(out_fmt == SPEI_F32 || out_fmt == SPEI_BF16 || out_fmt == SPEI_F16, "spei_upsample_bicubic_fmt: out_fmt=%d", out_fmt);
     const bool v4 = (C % 4 == 0) && (ldi % 4 == 0) && (ldo % 4 == 0);
+    if (out_fmt != SPEI_F32) {
+        SPEI_REQUIRE(v4 && s == 2 && (uintptr_t)in % 16 == 0 && (uintptr_t)out_ % 8 == 0,
+                     "spei_upsample_bicubic_fmt: a 16-bit output needs s == 2, C / ldi / ldo multiples of 4 and aligned maps");
+        const int64_t tot2 = (int64_t)H * W * (C / 4);
+        const dim3 grid((unsigned)((tot2 + 255) / 256 < 8192 ? (tot2 + 255) / 256 : 8192));
+        if (out_fmt == SPEI_BF16) hipLaunchKernelGGL(bicubic2x_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, in, ldi, (__bf16*)out_, ldo, H, W, C, act == SPEI_ACT_RELU);
+        else hipLaunchKernelGGL(bicubic2x_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, in, ldi, (_Float16*)out_, ldo, H, W, C, act == SPEI_ACT_RELU);
+        SPEI_CHECK_LAUNCH("spei_upsample_bicubic_fmt");
+        return 0;
+    }
+    float* out = (float*)out_;
     if (v4 && s == 2 && ((uintptr_t)in | (uintptr_t)out) % 16 == 0) {
         const int64_t tot2 = (int64_t)H * W * (C / 4);
         const int blocks2 = (int)((tot2 + 255) / 256 < 8192 ? (tot2 + 255) / 256 : 8192);
-        hipLaunchKernelGGL(bicubic2x_kernel, dim3(blocks2), dim3(256), 0, (hipStream_t)stream, in, ldi, out, ldo, H, W, C, act == SPEI_ACT_RELU);
+        hipLaunchKernelGGL(bicubic2x_kernel<float>, dim3(blocks2), dim3(256), 0, (hipStream_t)stream, in, ldi, out, ldo, H, W, C, act == SPEI_ACT_RELU);
         SPEI_CHECK_LAUNCH("spei_upsample_bicubic");
         return 0;
     }
@@ -376,6 +392,16 @@ extern "C" int spei_upsample_bicubic(const float* in, int ldi, float* out, int l
     else    hipLaunchKernelGGL(bicubic_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, ldi, out, ldo, H, W, C, s, act == SPEI_ACT_RELU);
     SPEI_CHECK_LAUNCH("spei_upsample_bicubic");
     return 0;
+}
+
+extern "C" int spei_upsample_bicubic(const float* in, int ldi, float* out, int ldo, int H, int W, int C, int s, int act,
+                                     spei_stream_t stream) {
+    return upsample_bicubic_run(in, ldi, out, ldo, SPEI_F32, H, W, C, s, act, stream);
+}
+
+extern "C" int spei_upsample_bicubic_fmt(const float* in, int ldi, void* out, int ldo, int out_fmt, int H, int W, int C, int s, int act,
+                                         spei_stream_t stream) {
+    return upsample_bicubic_run(in, ldi, out, ldo, out_fmt, H, W, C, s, act, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -7,6 +7,34 @@ namespace {
 // ---------------------------------------------------------------------------------------------------
 // LayerNorm over 256 channels: one wave per token, 4 channels per lane, two-pass moments in registers.
 // ---------------------------------------------------------------------------------------------------
+// One token's normalisation: this lane's four channels v of the wave's 256 -> (v - mean) * rstd * g + b.  Every rounding is spelled
+// out (contraction off; the two fused multiply-adds are the ones the compiler chose for layernorm256_kernel), so a kernel that
+// normalises twice in registers gives the bits of two launches.
+__device__ __forceinline__ float4 ln256_row(const float4 v, const float4 g, const float4 b) {
+#pragma clang fp contract(off)
+    const float mean = wave_sum((v.x + v.y) + (v.z + v.w)) * (1.0f / 256.0f);
+    const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
+    const float var_eps = __fmaf_rn(wave_sum((dx * dx + dy * dy) + (dz * dz + dw * dw)), 1.0f / 256.0f, 1e-5f);
+    const float rstd = 1.0f / sqrtf(var_eps);
+    float4 o;
+    o.x = __fmaf_rn(dx * rstd, g.x, b.x);
+    o.y = __fmaf_rn(dy * rstd, g.y, b.y);
+    o.z = __fmaf_rn(dz * rstd, g.z, b.z);
+    o.w = __fmaf_rn(dw * rstd, g.w, b.w);
+    return o;
+}
+
+template <typename TO>
+__device__ __forceinline__ void ln256_store(TO* __restrict__ y, const float4 o) {
+    if constexpr (sizeof(TO) == 4) {
+        *reinterpret_cast<float4*>(y) = o;
+    } else {
+        typename lpv<TO>::x4 h;
+        h[0] = (TO)o.x; h[1] = (TO)o.y; h[2] = (TO)o.z; h[3] = (TO)o.w;
+        *reinterpret_cast<typename lpv<TO>::x4*>(y) = h;
+    }
+}
+
 template <typename TO>
 __global__ __launch_bounds__(256) void layernorm256_kernel(const float* __restrict__ x, TO* __restrict__ y,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -19,22 +47,25 @@ __global__ __launch_bounds__(256) void layernorm256_kernel(const float* __restri
     if (beta) b = reinterpret_cast<const float4*>(beta)[lane];
     for (int64_t m = wave; m < M; m += nwaves) {
         const float4 v = reinterpret_cast<const float4*>(x + m * 256)[lane];
-        const float mean = wave_sum((v.x + v.y) + (v.z + v.w)) * (1.0f / 256.0f);
-        const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
-        const float var = wave_sum((dx * dx + dy * dy) + (dz * dz + dw * dw)) * (1.0f / 256.0f);
-        const float rstd = 1.0f / sqrtf(var + 1e-5f);
-        float4 o;
-        o.x = dx * rstd * g.x + b.x;
-        o.y = dy * rstd * g.y + b.y;
-        o.z = dz * rstd * g.z + b.z;
-        o.w = dw * rstd * g.w + b.w;
-        if (sizeof(TO) == 4) {
-            reinterpret_cast<float4*>(y + m * 256)[lane] = o;
-        } else {
-            typename lpv<TO>::x4 h;
-            h[0] = (TO)o.x; h[1] = (TO)o.y; h[2] = (TO)o.z; h[3] = (TO)o.w;
-            reinterpret_cast<typename lpv<TO>::x4*>(y + m * 256)[lane] = h;
-        }
+        ln256_store<TO>(y + m * 256 + 4 * lane, ln256_row(v, g, b));
+    }
+}
+
+// The Swin entry's two normalisations of the y side in one pass: LayerNorm(x) * gamma + beta (the patch-embed norm), then norm1
+// without affine (its gamma / beta live in the q weights), the first result in registers.  The second call sees g = 1, b = 0 as
+// layernorm256_kernel does when it gets no gamma / beta.
+template <typename TO>
+__global__ __launch_bounds__(256) void layernorm256_twice_kernel(const float* __restrict__ x, TO* __restrict__ y,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 int64_t M) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    const float4 one = make_float4(1.f, 1.f, 1.f, 1.f), zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 g = reinterpret_cast<const float4*>(gamma)[lane], b = reinterpret_cast<const float4*>(beta)[lane];
+    for (int64_t m = wave; m < M; m += nwaves) {
+        const float4 v = reinterpret_cast<const float4*>(x + m * 256)[lane];
+        ln256_store<TO>(y + m * 256 + 4 * lane, ln256_row(ln256_row(v, g, b), one, zero));
     }
 }
 
@@ -168,6 +199,19 @@ extern "C" int spei_layernorm256(const float* x, void* y, int out_fmt, const flo
     else if (out_fmt == SPEI_F16) hipLaunchKernelGGL(layernorm256_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, x, (_Float16*)y, gamma, beta, M);
     else hipLaunchKernelGGL(layernorm256_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, (float*)y, gamma, beta, M);
     SPEI_CHECK_LAUNCH("spei_layernorm256");
+    return 0;
+}
+
+extern "C" int spei_layernorm256_twice(const float* x, void* y, int out_fmt, const float* gamma, const float* beta, int64_t M,
+                                       spei_stream_t stream) {
+    SPEI_REQUIRE(x && y && gamma && beta && M > 0, "spei_layernorm256_twice: bad arguments");
+    SPEI_REQUIRE(out_fmt == SPEI_F32 || out_fmt == SPEI_BF16 || out_fmt == SPEI_F16, "spei_layernorm256_twice: out_fmt=%d", out_fmt);
+    const int64_t blocks = (M + 3) / 4;
+    const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
+    if (out_fmt == SPEI_BF16) hipLaunchKernelGGL(layernorm256_twice_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, x, (__bf16*)y, gamma, beta, M);
+    else if (out_fmt == SPEI_F16) hipLaunchKernelGGL(layernorm256_twice_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, x, (_Float16*)y, gamma, beta, M);
+    else hipLaunchKernelGGL(layernorm256_twice_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, (float*)y, gamma, beta, M);
+    SPEI_CHECK_LAUNCH("spei_layernorm256_twice");
     return 0;
 }
 

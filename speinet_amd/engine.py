@@ -1,7 +1,8 @@
 """The per-sequence forward pass as a sequence of HIP kernel launches (one sample at a time).
 
 Mirrors reference model/speinet.py:75-148 (`_process`, `_decode`, `_forwardbs`, `_forwardb`); every step is a
-call into the C-ABI through a `speinet_amd.ops.Ctx` (the call's arithmetic mode / device; no global state).  Feature maps stay NHWC fp32 in HBM between kernels; channel
+call into the C-ABI through a `speinet_amd.ops.Ctx` (the call's arithmetic mode / device; no global state).  Feature maps stay NHWC fp32 in HBM between kernels — 16-bit where every
+reader is the operand of a single-product 16-bit conv (Ctx.handoff16); channel
 concatenations are never materialised (two-source GEMM operands, strided output views).
 """
 from __future__ import annotations
@@ -40,13 +41,21 @@ def enc(ctx: Ctx, frame: torch.Tensor, P: dict, extra=None, out=None) -> FMap:
     return enc_stage(ctx, enc_stage(ctx, in_block(ctx, frame, P["inBlock"]), P["encoder_first"]), P["encoder_second"], extra, out)
 
 
-def enc_batched(ctx: Ctx, frames: list, P: dict):
+def enc_batched(ctx: Ctx, frames: list, P: dict, refs=None, sums=None):
     """The three encoder stages on ALL of a frame's passes at once: frames = [3,H,W] tensors (the window's frames, their
     Richardson-Lucy priors, the sharp reference; model/speinet.py:82-83,125-131 run the same recons_net stacks on each).  Every
     layer is one launch over the stacked maps (ops.BMap); per map the kernels, tiles and arithmetic are those of `enc` — the
-    results are bit-identical to one pass at a time.  Returns the three levels as BMaps."""
+    results are bit-identical to one pass at a time.  Returns the three levels as BMaps.
+
+    With `refs` and `sums` (Ctx.handoff16) the last ResBlock of every stage writes only what is read afterwards: refs = the indices of
+    the sharp-reference passes, sums = [(i, j, dest)]: enc(frames[i]) + enc(frames[j]) goes to the level-3 fp32 FMap `dest` (any row
+    stride).  Levels 1 and 2 then leave the stack as 16-bit maps for the next stage's head conv (which rounds its fp32 input to the
+    same bits while staging) and as fp32 for the reference passes only; at level 3 the pair sums are written by the apply itself.
+    Returns three {ref index: FMap} dicts, one per level."""
     ctx = ctx.for_stage("enc")
     assert ctx.batched_available()
+    if refs is not None:
+        return _enc_batched_routed(ctx, frames, P, list(refs), list(sums))
     b, (h, w) = len(frames), frames[0].shape[-2:]
     ib = P["inBlock"]
     lv1 = BMap.empty(b, h, w, ib["head_b"].numel(), frames[0].device)
@@ -66,6 +75,33 @@ def enc_batched(ctx: Ctx, frames: list, P: dict):
     return levels
 
 
+def _enc_batched_routed(ctx: Ctx, frames: list, P: dict, refs: list, sums: list):
+    b, (h, w) = len(frames), frames[0].shape[-2:]
+    dev, idt = frames[0].device, ctx.inter_dtype()
+    ib = P["inBlock"]
+    f = BMap.empty(b, h, w, ib["head_b"].numel(), dev)
+    for i in range(b):
+        ctx.conv5_in(frames[i], ib["head_w"], ib["head_b"], out=f.map(i))
+    levels = []
+    for name in ("inBlock", "encoder_first", "encoder_second"):
+        st = P[name]
+        if name != "inBlock":
+            f = ctx.igemm_batched(f, st["head_w"], st["head_b"], st["head_b"].numel(), 5, stride=2, act=ACT_RELU)
+        for pk in st["blocks"][:-1]:
+            f = ctx.resblock_batched(f, pk)
+        keep = {r: FMap.empty(f.H, f.W, f.C, dev) for r in refs}
+        if name != "encoder_second":
+            nxt = BMap.empty(b, f.H, f.W, f.C, dev, idt)
+            routes = [(i, None, keep.get(i), nxt.map(i)) for i in range(b)]
+        else:
+            nxt = None
+            routes = [(i, j, dest, None) for i, j, dest in sums] + [(r, None, keep[r], None) for r in refs]
+        ctx.resblock_batched(f, st["blocks"][-1], routes=routes)
+        levels.append(keep)
+        f = nxt
+    return levels
+
+
 def dec_stage(ctx: Ctx, f: FMap, pk: dict) -> FMap:
     f = _resblocks(ctx, f, pk["blocks"])
     return ctx.for_stage("convt").igemm(f, pk["tail_w"], pk["tail_b"], pk["tail_b"].numel(), ksize=3, stride=2, mode=CONV_T, act=ACT_RELU)
@@ -82,16 +118,23 @@ class SwinX:
         self.xt0 = ctx.layernorm(self.x_first.t, sw["pe_g"], sw["pe_b"])
 
 
+def _yhat(ctx: Ctx, y_first: torch.Tensor, sw: dict, idt) -> torch.Tensor:
+    """norm1(patch_embed_norm(y_first)) without norm1's affine (gamma / beta live in wq / bq, pack.py).  The patch-embed result has no
+    other reader: with `handoff16` one launch does both and it never reaches memory."""
+    if ctx.handoff16 and ctx.lp16:
+        return ctx.layernorm_twice(y_first, sw["pe_g"], sw["pe_b"], out_dtype=idt)
+    return ctx.layernorm(ctx.layernorm(y_first, sw["pe_g"], sw["pe_b"]), out_dtype=idt)
+
+
 def swin(ctx: Ctx, sx: SwinX, feat: FMap, sw: dict, out: FMap) -> FMap:
     ctx = ctx.for_stage("swin")
     h, w = feat.H, feat.W
     m = h * w
     dev = feat.t.device
     y_first = ctx.igemm(feat, sw["conv_first_w"], sw["conv_first_b"], 256, ksize=3)
-    yt = ctx.layernorm(y_first.t, sw["pe_g"], sw["pe_b"])
     idt = ctx.inter_dtype()                       # bf16 in the throughput mode: these tensors only feed GEMMs / attention
-    yhat = ctx.layernorm(yt, out_dtype=idt)       # norm1(y) without affine; gamma/beta live in wq/bq (pack.py)
-    del y_first, yt
+    yhat = _yhat(ctx, y_first.t, sw, idt)
+    del y_first
     r = sx.xt0.clone()                            # RSTB input / running residual
     bufs = [torch.empty(m, 256, device=dev), torch.empty(m, 256, device=dev)]
     xh = torch.empty(m, 256, device=dev, dtype=idt)
@@ -146,10 +189,8 @@ def swin_multi(ctx: Ctx, sx: SwinX, feats: BMap, sw: dict, outs: list) -> None:
     m = h * w
     dev = feats.t.device
     y_first = ctx.igemm_batched(feats, sw["conv_first_w"], sw["conv_first_b"], 256, 3)
-    yt = ctx.layernorm(y_first.t, sw["pe_g"], sw["pe_b"])
-    idt = ctx.inter_dtype()
-    yhat = ctx.layernorm(yt, out_dtype=idt)       # norm1(y) without affine; gamma/beta live in wq/bq (pack.py)
-    del y_first, yt
+    yhat = _yhat(ctx, y_first.t, sw, ctx.inter_dtype())
+    del y_first
     r = sx.xt0.repeat(B, 1)                       # RSTB input / running residual, per call
     bufs = [torch.empty(B * m, 256, device=dev), torch.empty(B * m, 256, device=dev)]
     for layer in sw["layers"]:
@@ -228,6 +269,11 @@ def decode(ctx: Ctx, ff: FMap, s: torch.Tensor, t3: FMap, t2: FMap, t1: FMap, P:
     g = ctx.for_stage("glue")        # the 1x1 / 3x3 convs between the stacks (conv_lv*, search*; 1 % of the frame's FLOPs) at H/4, H/2
     g1 = ctx.for_stage("glue1")      # ... and at full resolution
     c = lambda name: (P[name]["w"], P[name]["b"])
+    # upsample(f_lv2), s13, s23 and s33 are read only as operands of `glue1` convs: where those are single-product 16-bit convs the maps are
+    # written in their format (Ctx.handoff16); s13 is produced by a `glue` launch, which can do that where it ends in the upsampler
+    hd = torch.float32
+    if g1.handoff16 and g1.lp16 and (g.commute_any or (g.lp16 and g.commute_upconv)):
+        hd = g1.inter_dtype()
     h3, w3 = ff.H, ff.W
     smap = FMap(s.view(h3 * w3, 1), h3, w3, 1)
     f_lv3 = g.igemm(ff, *c("conv_lv3"), 128, a1=t3, rowscale=s, residual=ff)
@@ -241,9 +287,9 @@ def decode(ctx: Ctx, ff: FMap, s: torch.Tensor, t3: FMap, t2: FMap, t1: FMap, P:
     dec1 = dec_stage(ctx.for_stage("dec1"), f_lv2, P["decoder_first"])
     s4 = ctx.upsample(smap, 4).t.view(-1)
     f_lv1 = g1.igemm(dec1, *c("conv_lv1"), 32, a1=t1, rowscale=s4, residual=dec1)
-    s13 = g.up_conv1x1_relu(f_v3, *c("search13"), 32)
-    s23 = g1.igemm(ctx.upsample(f_lv2, 2), *c("search33"), 32, ksize=3, act=ACT_RELU)
-    s33 = g1.igemm(f_lv1, *c("search43"), 32, ksize=3, act=ACT_RELU)
+    s13 = g.up_conv1x1_relu(f_v3, *c("search13"), 32, out_dtype=hd)
+    s23 = g1.igemm(ctx.upsample(f_lv2, 2, out_dtype=hd), *c("search33"), 32, ksize=3, act=ACT_RELU, out_dtype=hd)
+    s33 = g1.igemm(f_lv1, *c("search43"), 32, ksize=3, act=ACT_RELU, out_dtype=hd)
     acc = g1.igemm(s13, *c("search33"), 32, ksize=3, a1=s23, act=ACT_RELU, residual=f_lv1)
     g1.igemm(s13, *c("search33"), 32, ksize=3, a1=s33, act=ACT_RELU, residual=acc, out=acc)
     g1.igemm(s23, *c("search33"), 32, ksize=3, a1=s33, act=ACT_RELU, residual=acc, out=acc)
@@ -390,6 +436,25 @@ def forward_batch_steps(ctx: Ctx, x: torch.Tensor, P: dict, n_seq: int, zero_ref
                 frames += [x[b, i], ctx.rl_prior(x[b, i], 1, 0.01)]
             if not zero_ref[b]:
                 frames.append(x[b, n_seq + 1])
+        if ctx.for_stage("enc").handoff16:
+            # the last ResBlock of each stack writes the pair sums, the reference maps and the next stack's 16-bit input itself
+            cats, fbs, refs, sums = {}, {}, [], []
+            for b in group:
+                m0 = first[b]
+                cats[b] = FMap(torch.empty(h3 * w3, 128 * n_seq, device=dev), h3, w3, 128 * n_seq)
+                fbs[b] = BMap.empty(len(others), h3, w3, 128, dev)
+                sums.append((m0 + 1, m0, cats[b].view(0, 128)))                              # enc(RL5(mid)) + enc(mid)   (speinet.py:130-132)
+                sums += [(m0 + 3 + 2 * k, m0 + 2 + 2 * k, fbs[b].map(k)) for k in range(len(others))]   # enc(RL1(x_i)) + enc(x_i)
+                if not zero_ref[b]:
+                    refs.append(m0 + 2 + 2 * len(others))
+            r1, r2, r3 = enc_batched(ctx, frames, P, refs=refs, sums=sums)
+            del frames
+            for b in group:
+                mr = first[b] + 2 + 2 * len(others)
+                lv = None if zero_ref[b] else (r1[mr], r2[mr], r3[mr])
+                yield from _fuse_tail(ctx, cats[b].view(0, 128), fbs[b], cats[b], lv, P, out[b], lanes)
+            b0 += len(group)
+            continue
         lv1, lv2, lv3 = enc_batched(ctx, frames, P)
         del frames
         for b in group:

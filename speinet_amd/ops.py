@@ -111,6 +111,15 @@ def _vp(p) -> C.c_void_p:
     return C.c_void_p(p)
 
 
+APPLY_MAX_ROUTES = 16          # SPEI_APPLY_MAX_ROUTES
+
+
+class _ApplyRoute(C.Structure):
+    """SpeiApplyRoute (include/speinet_hip.h)."""
+    _fields_ = [("out32", C.c_void_p), ("out16", C.c_void_p), ("ld32", C.c_int32), ("src", C.c_int32), ("partner", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class _timed:
     def __init__(self, ctx: "Ctx", name: str):
         self.on = ctx.profile is not None and name in ctx.profile
@@ -587,6 +596,12 @@ class Ctx:
     # 16-bit: the 256 -> 256 channel 3x3 convolutions of the Swin body (RSTB tail, conv_after_body) on fp32 token maps whose height is a
     # multiple of 6 and width a multiple of 16 as a persistent pipelined kernel (spei_conv3x3_256_pipe16)
     conv3_pipe: bool = True
+    # 16-bit: a map whose every reader stages it as the operand of a single-product 16-bit conv is written in that conv's
+    # `inter_dtype()` by its producer: the last ResBlock of the batched encoder stacks (routed apply: 16-bit maps for the
+    # next stage's head conv, fp32 only for the sharp reference, the level-3 pair sums straight into their destinations), the
+    # full-resolution glue maps of `decode`, and the Swin entry's two LayerNorms in one launch.  The consumers round the same values
+    # while staging, so frames are bit-identical.  Off: fp32 maps at these hand-offs, the launches of before
+    handoff16: bool = True
     # {stage name: {field: value}} overrides applied by `for_stage` (engine: "enc", "swin", "search", "decode", and inside "decode" the
     # stacks "dec2" (decoder_second), "dec1" (decoder_first), "out" (outBlock) and its final conv "tail")
     stage: Optional[dict] = None
@@ -925,8 +940,9 @@ class Ctx:
                    "spei_conv_slab16_batched")
         return out
 
-    def resblock_batched(self, x: BMap, pk: dict) -> BMap:
-        """`resblock` on every map of x: conv1, conv2, gate statistics, gate maps and the gated sum are ONE launch each."""
+    def resblock_batched(self, x: BMap, pk: dict, routes: Optional[list] = None) -> Optional[BMap]:
+        """`resblock` on every map of x: conv1, conv2, gate statistics, gate maps and the gated sum are ONE launch each.  `routes`: see
+        `_gates_apply_batched`."""
         idt = self.inter_dtype()
         c, dev = x.C, x.t.device
         lib = _lib.lib()
@@ -934,10 +950,14 @@ class Ctx:
         t = self.igemm_batched(x, pk["w1"], pk["b1"], c, 5, act=ACT_RELU, out_dtype=idt)
         x1 = self.igemm_batched(t, pk["w2"], pk["b2"], c, 5, out_dtype=idt)
         del t
-        return self._gates_apply_batched(x, x1, pk)
+        return self._gates_apply_batched(x, x1, pk, routes)
 
     @_family("streaming")
-    def _gates_apply_batched(self, x: BMap, x1: BMap, pk: dict) -> BMap:
+    def _gates_apply_batched(self, x: BMap, x1: BMap, pk: dict, routes: Optional[list] = None) -> Optional[BMap]:
+        """Gate statistics, gate maps and the gated sum x' of every map.  `routes` None: x' of all maps as one fp32 BMap.  Else a list of at
+        most APPLY_MAX_ROUTES tuples (src, partner, out32, out16) and nothing is returned: x' of map `src` — plus x' of map `partner`
+        unless that is None — goes to the fp32 FMap `out32` (any row stride) and / or, rounded to the mode's 16-bit format, to the dense
+        16-bit FMap `out16` (spei_resblock_apply_routed); maps that no route names are not written."""
         c, dev = x.C, x.t.device
         lib = _lib.lib()
         tp = self._tp
@@ -948,6 +968,20 @@ class Ctx:
         _lib.check(lib.spei_resblock_gates_batched(tp(x1.t), x1.fmt, x.B, x.H, x.W, c, tp(pk["se_w1"]), tp(pk["se_b1"]), tp(pk["se_w2"]),
                                                    tp(pk["se_b2"]), tp(pk["cw_w"]), tp(pk["cw_bn"]), tp(pk["hc_w"]), tp(pk["hc_bn"]),
                                                    tp(s), tp(g1), tp(g2), tp(ws), self._stream()), "spei_resblock_gates_batched")
+        if routes is not None:
+            assert self.lp16 and 1 <= len(routes) <= APPLY_MAX_ROUTES
+            arr = (_ApplyRoute * len(routes))()
+            for r, (src, partner, o32, o16) in zip(arr, routes):
+                assert 0 <= src < x.B and (partner is None or (0 <= partner < x.B and partner != src)) and (o32 is not None or o16 is not None)
+                for o, dt in ((o32, torch.float32), (o16, LP_DTYPE[self.fmt])):
+                    assert o is None or ((o.H, o.W, o.C) == (x.H, x.W, c) and o.t.dtype == dt and o.t.device == self.device)
+                assert o16 is None or (o16.ld, o16.off) == (c, 0)
+                r.src, r.partner = src, -1 if partner is None else partner
+                r.out32, r.ld32 = (o32.ptr, o32.ld) if o32 is not None else (None, 0)
+                r.out16 = o16.ptr if o16 is not None else None
+            _lib.check(lib.spei_resblock_apply_routed(self.fmt, tp(x.t), tp(x1.t), x1.fmt, tp(s), tp(g1), tp(g2), arr, len(routes), x.B,
+                                                      x.H, x.W, c, self._stream()), "spei_resblock_apply_routed")
+            return None
         out = BMap.empty(x.B, x.H, x.W, c, dev)
         _lib.check(lib.spei_resblock_apply_batched(tp(x.t), tp(x1.t), x1.fmt, tp(s), tp(g1), tp(g2), tp(out.t), x.B, x.H, x.W, c,
                                                    self._stream()), "spei_resblock_apply_batched")
@@ -1008,6 +1042,15 @@ class Ctx:
         tp = self._tp
         _lib.check(_lib.lib().spei_layernorm256(tp(x), tp(out), fmt_of(out.dtype), tp(g), tp(b), x.shape[0], self._stream()),
                    "spei_layernorm256")
+        return out
+
+    def layernorm_twice(self, x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
+        """layernorm(layernorm(x, g, b), out_dtype=out_dtype) in one launch, the first result in registers: the same bits."""
+        assert x.shape[1] == 256 and x.is_contiguous() and x.dtype == torch.float32 and g.numel() == b.numel() == 256
+        out = torch.empty(x.shape, device=x.device, dtype=out_dtype)
+        tp = self._tp
+        _lib.check(_lib.lib().spei_layernorm256_twice(tp(x), tp(out), fmt_of(out.dtype), tp(g), tp(b), x.shape[0], self._stream()),
+                   "spei_layernorm256_twice")
         return out
 
     def window_attention(self, q: torch.Tensor, kv: torch.Tensor, relbias: torch.Tensor, H: int, W: int, shift: int,
@@ -1100,19 +1143,24 @@ class Ctx:
         _lib.check(_lib.lib().spei_rot90(self._fp(f), f.ld, self._fp(out), f.H, f.W, f.C, self._stream()), "spei_rot90")
         return out
 
-    def upsample(self, f: FMap, s: int, act: int = ACT_NONE) -> FMap:
-        out = FMap.empty(f.H * s, f.W * s, f.C, f.t.device)
-        _lib.check(_lib.lib().spei_upsample_bicubic(self._fp(f), f.ld, self._fp(out), out.ld, f.H, f.W, f.C, s, act, self._stream()),
-                   "spei_upsample_bicubic")
+    def upsample(self, f: FMap, s: int, act: int = ACT_NONE, out_dtype=torch.float32) -> FMap:
+        """out_dtype: fp32, or the 16-bit format of the single-product convs that are the map's only readers (x2 only)."""
+        out = FMap.empty(f.H * s, f.W * s, f.C, f.t.device, out_dtype)
+        if out_dtype == torch.float32:
+            _lib.check(_lib.lib().spei_upsample_bicubic(self._fp(f), f.ld, self._fp(out), out.ld, f.H, f.W, f.C, s, act, self._stream()),
+                       "spei_upsample_bicubic")
+        else:
+            _lib.check(_lib.lib().spei_upsample_bicubic_fmt(self._fp(f), f.ld, self._fp(out), out.ld, out.fmt, f.H, f.W, f.C, s, act,
+                                                            self._stream()), "spei_upsample_bicubic_fmt")
         return out
 
-    def up_conv1x1_relu(self, f: FMap, w, b: torch.Tensor, n: int, s: int = 2) -> FMap:
+    def up_conv1x1_relu(self, f: FMap, w, b: torch.Tensor, n: int, s: int = 2, out_dtype=torch.float32) -> FMap:
         """relu(conv1x1(bicubic_up(f))) (reference model/speinet.py:96-97,108-109, model/SearchTransfer.py:73-76).  Both maps
         are linear and the bicubic weights sum to 1, so the 16-bit modes run the conv first, at 1/s^2 of the pixels and with
         half the bytes through the upsampler; the f32-grade modes keep the reference's order of operations."""
         if (self.lp16 and self.commute_upconv) or self.commute_any:
-            return self.upsample(self.igemm(f, w, b, n), s, act=ACT_RELU)
-        return self.igemm(self.upsample(f, s), w, b, n, act=ACT_RELU)
+            return self.upsample(self.igemm(f, w, b, n), s, act=ACT_RELU, out_dtype=out_dtype)
+        return self.igemm(self.upsample(f, s), w, b, n, act=ACT_RELU, out_dtype=out_dtype)
 
     def add(self, a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if out is None:
