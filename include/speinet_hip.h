@@ -668,6 +668,48 @@ int spei_train_batch_runs_light_u8(const spei_run_record* table, const spei_run_
                                    const uint32_t* tables, const uint32_t* tables_host, float* input, float* gt, int P, float rgb_range,
                                    spei_stream_t stream);
 
+/* ---- sensor noise in blur synthesis (speinet_amd/light.py; an extension beyond the reference) ---- */
+
+/* The mean of n frames carries 1 / n of one frame's noise variance.  The two entries below are the light entries above with that
+ * noise added back in LINEAR light, between the average and the encode, in integer arithmetic; S = 2^24 - 1 as above.
+ * Random words: Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85, ten
+ *   rounds).  For the pixel at column x, row y of the FULL source frame (before any crop, flip or rotation) of output frame `run` of
+ *   clip `clip`: counter (x, y, run, clip), key (key0, key1) = (seed & 0xffffffff, (seed >> 32) & 0xffffffff); output words 0, 1, 2
+ *   serve the R, G and B bytes, word 3 is unused.  Nothing depends on launch geometry, chunking, crop position or augmentation.
+ * Gaussian: `gauss` on the device and `gauss_host` the same words in HOST memory are 1025 int32, made once on the host in float64:
+ *   t[i] = round(4096 * inv_cdf(min(max(i / 1024, 2^-13), 1 - 2^-13)))     (the standard normal quantile in Q12)
+ *   Valid iff strictly increasing and |t[i]| < 2^15.  For a 32-bit word w: i = w >> 22, f = (w >> 10) & 4095,
+ *   z = (t[i] (4096 - f) + t[i + 1] f + 2048) >> 12   (arithmetic shift).
+ * Noise: per byte position of a run of n frames with linear mean L (as defined above) and the record's A < 2^20, B < 2^42:
+ *   V     = floor((A L + B) (n - 1) / n)       (64-bit; V < 2^45)
+ *   sigma = isqrt(V)                           (the mathematical integer square root)
+ *   d     = (sigma z + 2048) >> 12             (arithmetic shift)
+ *   L'    = clamp(L + d, 0, S),  blur = encode(L')
+ *   The factor (n - 1) / n tops the average's noise up to the level of one source frame: a run of length 1 — every ground-truth
+ *   record — has d = 0 and returns its bytes (it takes the copy path and reads neither table).  A = B = 0 gives the light entry's bytes.
+ * Levels: a clip with shot coefficient a and read deviation r (full scale 1, variance a x + r^2) has A = rint(a S), B = rint(r^2 S^2).
+ * The gauss table and every record (A < 2^20, B < 2^42, reserved == 0) are checked on the host copies before anything is launched,
+ * beside every check of the light entries.  sizeof(spei_noise_record) == 24. */
+typedef struct {
+    uint32_t run, clip; /* the output frame's index in its clip's plan; the clip's index */
+    uint32_t A;         /* shot term, < 2^20 */
+    uint32_t reserved;  /* 0 */
+    uint64_t B;         /* read term, < 2^42 */
+} spei_noise_record;
+
+/* spei_window_mean_light_u8 with noise: noise / noise_host hold M records, one per run. */
+int spei_window_mean_noise_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
+                              const uint32_t* tables, const uint32_t* tables_host, const int32_t* gauss, const int32_t* gauss_host,
+                              const spei_noise_record* noise, const spei_noise_record* noise_host, uint32_t key0, uint32_t key1,
+                              unsigned char* blur, unsigned char* gt, float* gray, int H, int W, spei_stream_t stream);
+
+/* spei_train_batch_runs_light_u8 with noise: noise / noise_host hold n_in + n_gt records, one per record of the table; the pixel
+ * coordinates are those of the record's frame, (x0 + column, y0 + row) of the rectangle before flips and rotation. */
+int spei_train_batch_runs_noise_u8(const spei_run_record* table, const spei_run_record* table_host, int n_in, int n_gt,
+                                   const uint32_t* tables, const uint32_t* tables_host, const int32_t* gauss, const int32_t* gauss_host,
+                                   const spei_noise_record* noise, const spei_noise_record* noise_host, uint32_t key0, uint32_t key1,
+                                   float* input, float* gt, int P, float rgb_range, spei_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "speinet_hip.h")
 _lib = None
 
 # the scalar C types the header uses -> ctypes; a pointer parameter of any kind is c_void_p, a `const char*` return c_char_p
-_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "spei_stream_t": C.c_void_p}
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "float": C.c_float, "spei_stream_t": C.c_void_p}
 _DECL = re.compile(r"([^;{}()]*?)\b(spei_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
 
 

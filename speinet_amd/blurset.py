@@ -4,13 +4,16 @@ middle frame is the ground truth (reference LD_detector/mix_choice_dataset.py:46
 38-76).
 
     python -m speinet_amd.blurset --input <dir of clip folders> --output <dir> [--ratio 0.1 0.3 0.5] [--threshold 5] [--seed N]
-                                  [--light code|srgb|gamma:<g>]
+                                  [--light code|srgb|gamma:<g>] [--noise <shot>:<read>]
 
 writes `<output>/blur/<clip>/<i>.png`, `<output>/gt/<clip>/<i>.png` and `<output>/label/<clip>.npy`: the layout `data.ClipSet`,
 `speinet_amd.fit` and `python -m speinet_amd.detector fit` read.  The frame files are numbered with six digits: the loaders pair
 frames and labels by sorted file name (as the reference's do, data/videodata_nfs.py:127-162), and the reference's own `0.png ..
 123.png` do not sort in frame order.  `--light` (default `code`: the reference's average of code values, byte for byte) averages in
 linear light instead, as an exposure does: speinet_amd.light has the integer arithmetic; the ground truth, labels and layout are the same.
+`--noise <shot>:<read>` (with a linear `--light`; each side a number or `lo..hi`, drawn log-uniformly per clip) adds back the sensor
+noise that averaging removed — shot coefficient and read deviation at full scale 1, speinet_amd.light has the contract.  The levels
+are not fitted to any camera.
 
   * `plan_runs`   — the reference's draw sequence on a `random.Random` of the caller's (no global state): runs and labels;
   * `plan_dataset` — that sequence for every clip of a directory on one `random.Random(seed)` (also data.SharpClipSet's, per epoch);
@@ -84,11 +87,15 @@ def _chunks(starts, lengths, chunk_frames: int):
         i = j
 
 
-def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code"):
+def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None):
     """Generator of (first run, blur uint8 [m,H,W,3], gt uint8 [m,H,W,3], gray [m,H,W] or None) on `device`, one item per chunk of
     consecutive runs; see `synthesize`."""
     if not _light.is_code(light):
         _light.tables(light)                              # a light without valid tables is refused before anything is read
+    if noise is not None:
+        noise = _light.ClipNoise(*noise)
+        _light.check_noise(light, noise.spec)
+        levels = _light.noise_levels(noise.spec, noise.seed, noise.clip)
     fr = frames if hasattr(frames, "on_device") else frames_of(frames)
     starts, lengths = (np.asarray(a, np.int64).reshape(-1) for a in runs[:2])
     if starts.size != lengths.size or starts.size == 0:
@@ -137,18 +144,21 @@ def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_fra
                     if fr.on_device(t):
                         src_buf[t - lo].copy_(fr.device(t))
                 src = src_buf[:hi - lo]
-            blur, gt, g = ops.window_mean_u8(src, starts[i:j] - lo, lengths[i:j], gray=gray, light=light)
+            rec = None if noise is None else (_light.noise_records(np.arange(i, j) + noise.first_run, noise.clip, *levels), noise.seed)
+            blur, gt, g = ops.window_mean_u8(src, starts[i:j] - lo, lengths[i:j], gray=gray, light=light, noise=rec)
             yield i, blur, gt, g
 
 
-def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code"):
+def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None):
     """Average the runs of a clip on the GPU: `frames` in any form `video.frames_of` accepts (uint8 [T,H,W,3] array or tensor on the
     host or the device, a list of frames, a list of image paths), `runs` = (starts, lengths[, labels]) as `plan_runs` returns them
     -> (blur uint8 [M,H,W,3], gt uint8 [M,H,W,3]) on `device`, and the detector's gray planes [M,H,W] as a third item when `gray`.
     blur[m] is the per-byte floor of the run's mean (the bytes the reference writes), gt[m] the run's middle frame.  The source
     frames are uploaded `chunk_frames` at a time; only the result is as long as the clip.  `light`: "srgb" or "gamma:<g>" averages in
-    linear light (speinet_amd.light) instead; gt is unchanged and the gray planes are those of the encoded blur bytes."""
-    parts = list(synthesize_chunks(frames, runs, device, gray, chunk_frames, light))
+    linear light (speinet_amd.light) instead; gt is unchanged and the gray planes are those of the encoded blur bytes.  `noise`: None, or
+    `light.ClipNoise(spec, seed, clip[, first_run])` — the sensor noise of clip `clip` under `seed` at the levels of `spec`, run m
+    carrying the id first_run + m; the result does not depend on `chunk_frames`."""
+    parts = list(synthesize_chunks(frames, runs, device, gray, chunk_frames, light, noise))
     out = (torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]))
     return out + (torch.cat([p[3] for p in parts]),) if gray else out
 
@@ -185,15 +195,18 @@ def plan_dataset(clip_lengths, ratios, seed: int = 0, threshold: int = 5, window
 
 
 def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int = 0, threshold: int = 5, window_range=(1, 15),
-                  device="cuda", chunk_frames: int = CHUNK_FRAMES, log=None, light="code") -> list:
+                  device="cuda", chunk_frames: int = CHUNK_FRAMES, log=None, light="code", noise=None) -> list:
     """For every clip folder under src_dir write out_dir/blur/<clip>/<i>.png, out_dir/gt/<clip>/<i>.png and out_dir/label/<clip>.npy
     (reference process_dataset, mix_choice_dataset.py:78-117).  `ratio`: the share of sharp runs; `ratios`: several, one drawn per
     clip (:79) from the same `random.Random(seed)` that then draws the clip's runs (`plan_dataset`).  `light`: the light the runs are
-    averaged in (speinet_amd.light; it changes the blur frames only, and is not recorded in the set).  -> one dict per clip (name,
-    ratio, frames, labels)."""
+    averaged in (speinet_amd.light; it changes the blur frames only, and is not recorded in the set).  `noise`: a spec "<shot>:<read>"
+    (speinet_amd.light): sensor noise in that linear light, keyed by `seed`, the clip's index and the run's, at levels drawn per clip; it
+    does not touch the plan.  -> one dict per clip (name, ratio, frames, labels; with noise also its `shot` and `read`)."""
     light = _light.name(light)
     if light != _light.CODE:
         _light.tables(light)
+    _light.check_noise(light, noise)
+    noise = _light.noise_name(noise)
     clips = []
     for name, files in clip_folders(src_dir):
         try:
@@ -206,7 +219,7 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
     os.makedirs(os.path.join(out_dir, "label"), exist_ok=True)
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-png") as writers, torch.cuda.device(dev):
         ring = HostRing(writers, n=16)
-        for (name, fr), (r, (starts, lengths, labels)) in zip(clips, plans):
+        for k, ((name, fr), (r, (starts, lengths, labels))) in enumerate(zip(clips, plans)):
             bdir, gdir = os.path.join(out_dir, "blur", name), os.path.join(out_dir, "gt", name)
             os.makedirs(bdir, exist_ok=True)
             os.makedirs(gdir, exist_ok=True)
@@ -215,15 +228,20 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
                 _imwrite(pb, b.numpy())
                 _imwrite(pg, g.numpy())
 
-            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths), dev, False, chunk_frames, light):
+            clip_noise = None if noise is None else _light.ClipNoise(noise, seed, k)
+            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths), dev, False, chunk_frames, light, clip_noise):
                 for m in range(blur.shape[0]):
                     fn = f"{i0 + m:06d}.png"
                     ring.land(lambda b, g, pb=os.path.join(bdir, fn), pg=os.path.join(gdir, fn): save(b, g, pb, pg), blur[m], gt[m])
             ring.drain()
             np.save(os.path.join(out_dir, "label", name + ".npy"), labels)
             done.append({"name": name, "ratio": r, "source_frames": fr.T, "frames": int(labels.size), "labels": labels})
+            noisy = ""
+            if noise is not None:
+                done[-1]["shot"], done[-1]["read"] = _light.noise_draw(noise, seed, k)
+                noisy = f", noise shot {done[-1]['shot']:.3g} read {done[-1]['read']:.3g}"
             if log:
-                log(f"> {name}: {fr.T} sharp frames -> {labels.size} frames, {int(labels.sum())} labelled sharp (ratio {r}, light {light})")
+                log(f"> {name}: {fr.T} sharp frames -> {labels.size} frames, {int(labels.sum())} labelled sharp (ratio {r}, light {light}{noisy})")
     return done
 
 
@@ -236,6 +254,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--light", default="code", help="the light the runs are averaged in: code (code values, the reference's sets), srgb or "
                                                    "gamma:<g> (linear light, as an exposure)")
+    p.add_argument("--noise", default=None, help="sensor noise added in the linear --light: <shot>:<read>, the shot coefficient (at most 0.05) "
+                                                 "and the read deviation (at most 0.1) at full scale 1, each a number or lo..hi (drawn "
+                                                 "log-uniformly per clip); not fitted to any camera")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -249,11 +270,18 @@ def main(argv=None) -> None:
             _light.tables(light)
     except ValueError as e:
         p.error(f"--light: {e}")
+    try:
+        noise = _light.noise_name(a.noise)
+    except ValueError as e:
+        p.error(f"--noise: {e}")
+    if noise is not None and light == _light.CODE:
+        p.error("--noise is added in linear light: pass --light srgb or --light gamma:<g> with it")
     t0 = time.time()
     done = write_dataset(a.input, a.output, ratios=a.ratio, seed=a.seed, threshold=a.threshold, device=a.device,
-                         log=lambda s: print(s, flush=True), light=light)
+                         log=lambda s: print(s, flush=True), light=light, noise=noise)
     n_src, n_out = sum(d["source_frames"] for d in done), sum(d["frames"] for d in done)
-    print(f"# {len(done)} clips, {n_src} sharp frames -> {n_out} frames in {time.time() - t0:.2f}s, light {light}", flush=True)
+    print(f"# {len(done)} clips, {n_src} sharp frames -> {n_out} frames in {time.time() - t0:.2f}s, light {light}" + (f", noise {noise}" if noise else ""),
+          flush=True)
 
 
 if __name__ == "__main__":

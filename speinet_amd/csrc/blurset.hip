@@ -22,6 +22,11 @@
 //                         gt and the gray plane of the ENCODED bytes as above.  Both kernels are the templates below with LIGHT set: the
 //                         tables are staged by the workgroup before its first item, and a run of length 1 copies its bytes
 //                         (encode(lin[c]) == c) without touching them.  Same traffic as the code-value launch.
+//
+//   spei_window_mean_noise_u8 — the light launch with sensor noise between the quotient and the encode (csrc/light.h, NOISE set): the
+//                         workgroup also stages the gauss table (4 KB more LDS), a thread makes one Philox call per pixel on the
+//                         counter (x, y, run, clip) — x, y from the pixel's index in the frame — and spends a 64-bit multiply-high, an
+//                         fp32 square root with two integer corrections and a 64-bit multiply per byte.  A run of length 1 still copies.
 #include "common.h"
 #include "light.h"
 
@@ -37,10 +42,35 @@ __device__ __forceinline__ uint32_t mean_of(uint32_t sum, uint32_t magic, const 
     else return quot(sum, magic);
 }
 
-template <bool LIGHT>
+// The per-run constants of a NOISE launch (uniform over the workgroup)
+struct RunNoise {
+    uint32_t run, clip, A, key0, key1;
+    uint64_t B, magic;
+    const int32_t* gauss;                                  // in LDS
+};
+
+// sums of one pixel's three bytes -> its encoded bytes, with noise; (x, y): the pixel in its frame
+__device__ __forceinline__ void noisy_pixel(uint32_t* acc3, uint32_t magic, const uint32_t* tab, const RunNoise& rn, uint32_t x, uint32_t y) {
+    uint32_t w[3];
+    philox3(x, y, rn.run, rn.clip, rn.key0, rn.key1, w);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        acc3[c] = light_encode(tab + 256, noise_apply(light_quot(acc3[c], magic), gauss_z(rn.gauss, w[c]), rn.A, rn.B, rn.magic));
+}
+
+// stage the tables of a run of 2 or more frames (all 256 threads) and read the run's noise record
+__device__ __forceinline__ RunNoise run_noise(int32_t* lds, const NoiseArgs& na, int m, int len) {
+    if (len > 1) gauss_stage(lds, na.gauss);
+    const spei_noise_record r = na.rec[m];
+    return RunNoise{r.run, r.clip, r.A, na.key0, na.key1, r.B, len > 1 ? noise_magic(len) : 0ull, lds};
+}
+
+template <bool LIGHT, bool NOISE>
 __global__ __launch_bounds__(256) void window_mean_vec_kernel(const unsigned char* __restrict__ src, int64_t fstride, const int* __restrict__ runs,
                                                               const uint32_t* __restrict__ tables, unsigned char* __restrict__ blur,
-                                                              unsigned char* __restrict__ gt, float* __restrict__ gray, int64_t hw) {
+                                                              unsigned char* __restrict__ gt, float* __restrict__ gray, int64_t hw, NoiseArgs na,
+                                                              uint32_t W) {
+    static_assert(LIGHT || !NOISE, "noise is added in a linear light");
     const int m = blockIdx.y;
     const int start = runs[2 * m], len = runs[2 * m + 1];
     const uint32_t* tab = nullptr;                         // LIGHT: lin[256], thr[256] in LDS
@@ -48,6 +78,11 @@ __global__ __launch_bounds__(256) void window_mean_vec_kernel(const unsigned cha
         __shared__ uint32_t lds[LIGHT_WORDS];
         if (len > 1) light_stage(lds, tables);
         tab = lds;
+    }
+    RunNoise rn;                                           // NOISE: the gauss table in LDS and the run's record
+    if constexpr (NOISE) {
+        __shared__ int32_t glds[GAUSS_WORDS];
+        rn = run_noise(glds, na, m, len);
     }
     const bool copy = LIGHT && len == 1;                   // a run of length 1 returns its bytes; the tables are not staged
     const uint32_t magic = LIGHT ? (copy ? 0u : light_magic(len)) : (65536u + len - 1) / len;
@@ -82,8 +117,17 @@ __global__ __launch_bounds__(256) void window_mean_vec_kernel(const unsigned cha
                 for (int j = 0; j < 16; ++j) acc[16 * v + j] = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
             }
         } else {
+            if constexpr (NOISE) {
+                uint32_t y = (uint32_t)(i * 16) / W, x = (uint32_t)(i * 16) - y * W;       // H * W * 3 < 2^31
 #pragma unroll
-            for (int j = 0; j < 48; ++j) acc[j] = mean_of<LIGHT>(acc[j], magic, tab);
+                for (int px = 0; px < 16; ++px) {
+                    noisy_pixel(acc + 3 * px, magic, tab, rn, x, y);
+                    if (++x == W) { x = 0u; ++y; }
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 48; ++j) acc[j] = mean_of<LIGHT>(acc[j], magic, tab);
+            }
         }
         uint4* b = reinterpret_cast<uint4*>(blur + m * nb + i * 48);
         uint4* g = reinterpret_cast<uint4*>(gt + m * nb + i * 48);
@@ -111,10 +155,12 @@ __global__ __launch_bounds__(256) void window_mean_vec_kernel(const unsigned cha
     }
 }
 
-template <bool LIGHT>
+template <bool LIGHT, bool NOISE>
 __global__ __launch_bounds__(256) void window_mean_px_kernel(const unsigned char* __restrict__ src, int64_t fstride, const int* __restrict__ runs,
                                                              const uint32_t* __restrict__ tables, unsigned char* __restrict__ blur,
-                                                             unsigned char* __restrict__ gt, float* __restrict__ gray, int64_t hw) {
+                                                             unsigned char* __restrict__ gt, float* __restrict__ gray, int64_t hw, NoiseArgs na,
+                                                             uint32_t W) {
+    static_assert(LIGHT || !NOISE, "noise is added in a linear light");
     const int m = blockIdx.y;
     const int start = runs[2 * m], len = runs[2 * m + 1];
     const uint32_t* tab = nullptr;                         // LIGHT: lin[256], thr[256] in LDS
@@ -122,6 +168,11 @@ __global__ __launch_bounds__(256) void window_mean_px_kernel(const unsigned char
         __shared__ uint32_t lds[LIGHT_WORDS];
         if (len > 1) light_stage(lds, tables);
         tab = lds;
+    }
+    RunNoise rn;                                           // NOISE: the gauss table in LDS and the run's record
+    if constexpr (NOISE) {
+        __shared__ int32_t glds[GAUSS_WORDS];
+        rn = run_noise(glds, na, m, len);
     }
     const bool copy = LIGHT && len == 1;                   // a run of length 1 returns its bytes; the tables are not staged
     const uint32_t magic = LIGHT ? (copy ? 0u : light_magic(len)) : (65536u + len - 1) / len;
@@ -137,9 +188,12 @@ __global__ __launch_bounds__(256) void window_mean_px_kernel(const unsigned char
             }
         }
         const unsigned char* p = src + (start + len / 2) * fstride + i * 3;
+        if constexpr (NOISE)
+            if (!copy) noisy_pixel(acc, magic, tab, rn, (uint32_t)i % W, (uint32_t)i / W);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            acc[c] = copy ? (uint32_t)p[c] : mean_of<LIGHT>(acc[c], magic, tab);
+            if constexpr (!NOISE) acc[c] = copy ? (uint32_t)p[c] : mean_of<LIGHT>(acc[c], magic, tab);
+            else if (copy) acc[c] = (uint32_t)p[c];
             blur[m * nb + i * 3 + c] = (unsigned char)acc[c];
             gt[m * nb + i * 3 + c] = p[c];
         }
@@ -148,10 +202,12 @@ __global__ __launch_bounds__(256) void window_mean_px_kernel(const unsigned char
 }
 
 // The runs are checked HERE, on the host copy (and, LIGHT, the tables on theirs): the kernels never meet a run that leaves the clip
-template <bool LIGHT>
+template <bool LIGHT, bool NOISE = false>
 int window_mean(const char* name, const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
                 const uint32_t* tables, const uint32_t* tables_host, unsigned char* blur, unsigned char* gt, float* gray, int H, int W,
-                spei_stream_t stream) {
+                spei_stream_t stream, const int32_t* gauss = nullptr, const int32_t* gauss_host = nullptr,
+                const spei_noise_record* noise = nullptr, const spei_noise_record* noise_host = nullptr, uint32_t key0 = 0u,
+                uint32_t key1 = 0u) {
     SPEI_REQUIRE(src && runs && runs_host && blur && gt, "%s: null pointer (src, runs, runs_host, blur and gt are required)", name);
     SPEI_REQUIRE(T > 0 && M > 0 && M <= 65535 && H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31),
                  "%s: bad sizes (%d frames of %dx%d, %d runs; at most 65535 runs per launch)", name, T, H, W, M);
@@ -165,17 +221,20 @@ int window_mean(const char* name, const unsigned char* src, int64_t frame_stride
     }
     if constexpr (LIGHT)
         if (light_check(name, tables, tables_host)) return -1;
+    if constexpr (NOISE)
+        if (noise_check(name, gauss, gauss_host, noise, noise_host, M)) return -1;
+    const NoiseArgs na{gauss, noise, key0, key1};
     const bool vec = (hw & 15) == 0 && (((uintptr_t)src | (uintptr_t)blur | (uintptr_t)gt | (uintptr_t)gray) & 15) == 0 &&
                      (T == 1 || (frame_stride & 15) == 0);
     const int64_t items = vec ? hw >> 4 : hw;
     const int64_t bx = (items + 255) / 256;
     const dim3 grid((unsigned)(bx < 4096 ? bx : 4096), (unsigned)M);
     if (vec)
-        hipLaunchKernelGGL(window_mean_vec_kernel<LIGHT>, grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, tables, blur, gt,
-                           gray, hw);
+        hipLaunchKernelGGL((window_mean_vec_kernel<LIGHT, NOISE>), grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, tables, blur,
+                           gt, gray, hw, na, (uint32_t)W);
     else
-        hipLaunchKernelGGL(window_mean_px_kernel<LIGHT>, grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, tables, blur, gt,
-                           gray, hw);
+        hipLaunchKernelGGL((window_mean_px_kernel<LIGHT, NOISE>), grid, dim3(256), 0, (hipStream_t)stream, src, frame_stride, runs, tables, blur,
+                           gt, gray, hw, na, (uint32_t)W);
     SPEI_CHECK_LAUNCH(name);
     return 0;
 }
@@ -192,4 +251,12 @@ extern "C" int spei_window_mean_light_u8(const unsigned char* src, int64_t frame
                                          float* gray, int H, int W, spei_stream_t stream) {
     return window_mean<true>("spei_window_mean_light_u8", src, frame_stride, T, runs, runs_host, M, tables, tables_host, blur, gt, gray, H, W,
                              stream);
+}
+
+extern "C" int spei_window_mean_noise_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
+                                         const uint32_t* tables, const uint32_t* tables_host, const int32_t* gauss, const int32_t* gauss_host,
+                                         const spei_noise_record* noise, const spei_noise_record* noise_host, uint32_t key0, uint32_t key1,
+                                         unsigned char* blur, unsigned char* gt, float* gray, int H, int W, spei_stream_t stream) {
+    return window_mean<true, true>("spei_window_mean_noise_u8", src, frame_stride, T, runs, runs_host, M, tables, tables_host, blur, gt, gray, H,
+                                   W, stream, gauss, gauss_host, noise, noise_host, key0, key1);
 }

@@ -30,6 +30,10 @@
 // LDS read each) into twelve 32-bit sums — the packed two-sums-per-dword trick does not carry over: a sum reaches 15 (2^24 - 1) —
 // divides (light.h's multiply-high), encodes by the binary search over thr[] and packs the four pixels into LDS as above.  A record
 // of length 1 (every ground-truth record) is loaded as is.  Everything after the barrier is shared.
+//
+// spei_train_batch_runs_noise_u8 adds sensor noise between the quotient and the encode (csrc/light.h) — the bytes of
+// spei_window_mean_noise_u8's blur[m]: the workgroup also stages the gauss table, and thread t makes one Philox call for each of its
+// four pixels on the counter (x, y, run, clip) with (x, y) = (x0 + cx_lo + g4 + k, y0 + cy_lo + row), the pixel in its full frame.
 #include "common.h"
 #include "light.h"
 
@@ -54,8 +58,11 @@ __device__ __forceinline__ void load12(const unsigned char* s, bool dwords, uint
 }
 
 // 12 bytes of a run of len frames fstride apart averaged in linear light (csrc/light.h), packed as load12 packs them; tab = lin[256],
-// thr[256] in LDS, staged iff len > 1
-__device__ __forceinline__ void run_light12(const unsigned char* s, int64_t fstride, int len, bool dwords, const uint32_t* tab, uint32_t w[3]) {
+// thr[256] in LDS, staged iff len > 1.  NOISE: with the noise of record nr under the key of na added to the quotient; gauss = the table
+// in LDS (staged iff len > 1), (x, y) = the first of the four pixels in its frame
+template <bool NOISE>
+__device__ __forceinline__ void run_light12(const unsigned char* s, int64_t fstride, int len, bool dwords, const uint32_t* tab, uint32_t w[3],
+                                            const int32_t* gauss, const spei_noise_record& nr, const NoiseArgs& na, uint32_t x, uint32_t y) {
     if (len == 1) {                                                      // encode(lin[c]) == c
         load12(s, dwords, w);
         return;
@@ -77,15 +84,32 @@ __device__ __forceinline__ void run_light12(const unsigned char* s, int64_t fstr
     }
     const uint32_t magic = light_magic(len);
     w[0] = w[1] = w[2] = 0u;
+    if constexpr (NOISE) {
+        const uint64_t nmagic = noise_magic(len);
 #pragma unroll
-    for (int j = 0; j < 12; ++j) w[j >> 2] |= light_encode(tab + 256, light_quot(sum[j], magic)) << (8 * (j & 3));
+        for (int k = 0; k < 4; ++k) {
+            uint32_t rnd[3];
+            philox3(x + k, y, nr.run, nr.clip, na.key0, na.key1, rnd);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int j = 3 * k + c;
+                const uint32_t L = noise_apply(light_quot(sum[j], magic), gauss_z(gauss, rnd[c]), nr.A, nr.B, nmagic);
+                w[j >> 2] |= light_encode(tab + 256, L) << (8 * (j & 3));
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) w[j >> 2] |= light_encode(tab + 256, light_quot(sum[j], magic)) << (8 * (j & 3));
+    }
 }
 
-template <typename Rec, bool LIGHT>
+template <typename Rec, bool LIGHT, bool NOISE>
 __global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict__ table, const uint32_t* __restrict__ tables, int n_in,
-                                                          float* __restrict__ input, float* __restrict__ gt, int P, int tiles, float scale) {
+                                                          float* __restrict__ input, float* __restrict__ gt, int P, int tiles, float scale,
+                                                          NoiseArgs na) {
     constexpr bool RUNS = std::is_same<Rec, spei_run_record>::value;
     static_assert(RUNS || !LIGHT, "a light averages runs");
+    static_assert(LIGHT || !NOISE, "noise is added in a linear light");
     __shared__ uint32_t lds[TILE * PITCH];
     const int r = blockIdx.y;
     const Rec rec = table[r];
@@ -104,6 +128,14 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict_
             if (rec.length > 1) light_stage(light, tables);
             tab = light;
         }
+        const int32_t* gauss = nullptr;                                  // NOISE: the gauss table in LDS, for a run of 2 or more frames
+        spei_noise_record nr{};
+        if constexpr (NOISE) {
+            __shared__ int32_t glds[GAUSS_WORDS];
+            if (rec.length > 1) gauss_stage(glds, na.gauss);
+            gauss = glds;
+            nr = na.rec[r];
+        }
         if (row < nR && g4 < nC) {
             const unsigned char* s = reinterpret_cast<const unsigned char*>(rec.src) + (int64_t)(rec.y0 + cy_lo + row) * rec.pitch +
                                      (int64_t)(rec.x0 + cx_lo + g4) * 3;
@@ -113,7 +145,8 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict_
                 const int len = rec.length;
                 dwords = dwords && (len == 1 || (rec.frame_stride & 3) == 0);                                  // ... in every frame of the run
                 if constexpr (LIGHT) {
-                    run_light12(s, rec.frame_stride, len, dwords, tab, w);
+                    run_light12<NOISE>(s, rec.frame_stride, len, dwords, tab, w, gauss, nr, na, (uint32_t)(rec.x0 + cx_lo + g4),
+                                       (uint32_t)(rec.y0 + cy_lo + row));
                 } else {
                     // even[k] holds the sums of bytes 0 and 2 of dword k in its two halves, odd[k] those of bytes 1 and 3
                     uint32_t even[3] = {0u, 0u, 0u}, odd[3] = {0u, 0u, 0u};
@@ -171,9 +204,11 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict_
 }
 
 // Every record is checked HERE, on the host copy: the kernel never meets a record that leaves its frame or its clip
-template <typename Rec, bool LIGHT = false>
+template <typename Rec, bool LIGHT = false, bool NOISE = false>
 int train_batch(const char* name, const Rec* table, const Rec* table_host, int n_in, int n_gt, float* input, float* gt, int P, float rgb_range,
-                spei_stream_t stream, const uint32_t* tables = nullptr, const uint32_t* tables_host = nullptr) {
+                spei_stream_t stream, const uint32_t* tables = nullptr, const uint32_t* tables_host = nullptr, const int32_t* gauss = nullptr,
+                const int32_t* gauss_host = nullptr, const spei_noise_record* noise = nullptr, const spei_noise_record* noise_host = nullptr,
+                uint32_t key0 = 0u, uint32_t key1 = 0u) {
     SPEI_REQUIRE(table && table_host, "%s: null record table (the device table and its host copy are both required)", name);
     SPEI_REQUIRE(n_in >= 0 && n_gt >= 0 && n_in + n_gt > 0 && n_in + n_gt <= 65535, "%s: bad record counts %d + %d", name, n_in, n_gt);
     SPEI_REQUIRE((n_in == 0 || input) && (n_gt == 0 || gt), "%s: null dst", name);
@@ -199,10 +234,12 @@ int train_batch(const char* name, const Rec* table, const Rec* table_host, int n
     }
     if constexpr (LIGHT)
         if (light_check(name, tables, tables_host)) return -1;
+    if constexpr (NOISE)
+        if (noise_check(name, gauss, gauss_host, noise, noise_host, n_in + n_gt)) return -1;
     const int tiles = cdiv(P, TILE);
     const float scale = (float)((double)rgb_range / 255.0);
-    hipLaunchKernelGGL((train_batch_kernel<Rec, LIGHT>), dim3(tiles * tiles, n_in + n_gt), dim3(256), 0, (hipStream_t)stream, table, tables, n_in,
-                       input, gt, P, tiles, scale);
+    hipLaunchKernelGGL((train_batch_kernel<Rec, LIGHT, NOISE>), dim3(tiles * tiles, n_in + n_gt), dim3(256), 0, (hipStream_t)stream, table, tables,
+                       n_in, input, gt, P, tiles, scale, NoiseArgs{gauss, noise, key0, key1});
     SPEI_CHECK_LAUNCH(name);
     return 0;
 }
@@ -224,4 +261,13 @@ extern "C" int spei_train_batch_runs_light_u8(const spei_run_record* table, cons
                                               float rgb_range, spei_stream_t stream) {
     return train_batch<spei_run_record, true>("spei_train_batch_runs_light_u8", table, table_host, n_in, n_gt, input, gt, P, rgb_range, stream,
                                               tables, tables_host);
+}
+
+extern "C" int spei_train_batch_runs_noise_u8(const spei_run_record* table, const spei_run_record* table_host, int n_in, int n_gt,
+                                              const uint32_t* tables, const uint32_t* tables_host, const int32_t* gauss,
+                                              const int32_t* gauss_host, const spei_noise_record* noise, const spei_noise_record* noise_host,
+                                              uint32_t key0, uint32_t key1, float* input, float* gt, int P, float rgb_range,
+                                              spei_stream_t stream) {
+    return train_batch<spei_run_record, true, true>("spei_train_batch_runs_noise_u8", table, table_host, n_in, n_gt, input, gt, P, rgb_range,
+                                                    stream, tables, tables_host, gauss, gauss_host, noise, noise_host, key0, key1);
 }

@@ -9,7 +9,8 @@
 and, beyond the reference (which precomputes its blurry sets), the same loop fed from SHARP footage, the blur synthesised per batch:
 
     SharpClipSet      folders of sharp frames cut into runs as blurset.write_dataset cuts them, re-drawn for every epoch: epoch e is the
-                      set write_dataset(seed = seed + e, light = light) would write, as ClipSet would scan it — but nothing is written
+                      set write_dataset(seed = seed + e, light = light, noise = noise) would write, as ClipSet would scan it — but
+                      nothing is written
     SharpStore        the sharp frames, decoded once, uint8 [T,H,W,3] per clip on the device
     run_records       one batch as spei_run_record: an input frame is a run of sharp frames, the ground truth the run's middle frame
     SharpTrainLoader  TrainLoader on that table and spei_train_batch_runs_u8, which averages each crop's run in its load phase
@@ -178,11 +179,12 @@ class SharpClipSet(Windows):
     label 1 for a run of at most `threshold` frames, names `<clip>.<run index, six digits>`, truncated to n_frames_per_video RUNS,
     pre / sub from the truncated labels — so `len()` and `sample(idx)` are ClipSet's on that set.  A virtual clip also carries `starts`
     and `lengths` (the runs' sharp frames) and `source` (its index in `sharp`, the scanned folders).  `light` (speinet_amd.light: "code",
-    "srgb", "gamma:<g>") is the light the loader averages the runs in — write_dataset's `light`; it does not touch the plan.  The
-    constructor plans epoch 0."""
+    "srgb", "gamma:<g>") is the light the loader averages the runs in — write_dataset's `light`; it does not touch the plan.  `noise`
+    (a spec "<shot>:<read>" of speinet_amd.light, with a linear light) is write_dataset's `noise`: every plan draws the clips' levels
+    under its own seed (`noise` of a virtual clip: its a, r, A and B), and does not touch the runs either.  The constructor plans epoch 0."""
 
     def __init__(self, dir_sharp: str, ratios=(0.5,), threshold: int = 5, window_range=(1, 15), seed: int = 0, n_sequence: int = 3,
-                 n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None, light="code"):
+                 n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None, light="code", noise=None):
         from . import light as _light
         from .blurset import clip_folders
         from .video import frames_of
@@ -194,6 +196,8 @@ class SharpClipSet(Windows):
         self.light = _light.name(light)
         if self.light != _light.CODE:
             _light.tables(self.light)                                        # ValueError for a light without valid tables
+        _light.check_noise(self.light, noise)                                # ... and for noise on code values
+        self.noise = _light.noise_name(noise)
         self.sharp = []
         for name, files in clip_folders(dir_sharp):
             try:
@@ -206,6 +210,7 @@ class SharpClipSet(Windows):
         self.plan(0)
 
     def plan(self, epoch: int) -> None:
+        from . import light as _light
         from .blurset import plan_dataset
         plans = plan_dataset([c["T"] for c in self.sharp], self.ratios, self.seed + epoch, self.threshold, self.window_range)
         clips = []
@@ -220,6 +225,8 @@ class SharpClipSet(Windows):
                     "names": [f"{src['name']}.{m:06d}" for m in range(len(labels))]}
             if self.references:
                 clip["pre"], clip["sub"] = selection.blurry_indices(labels)
+            if self.noise is not None:
+                clip["noise"] = _light.noise_draw(self.noise, self.seed + epoch, k) + _light.noise_levels(self.noise, self.seed + epoch, k)
             clips.append(clip)
         self.clips, self.epoch = clips, epoch
         self._count(f"{self.dir_data} (epoch {epoch})")
@@ -227,7 +234,13 @@ class SharpClipSet(Windows):
     def summary(self) -> str:
         """One line on the current plan: its runs, how many are labelled sharp and the light they are averaged in."""
         runs, sharp = sum(c["T"] for c in self.clips), sum(sum(c["labels"]) for c in self.clips)
-        return f"Plan {self.epoch} of {self.dir_data}: {runs} runs of {sum(c['T'] for c in self.sharp)} sharp frames, {sharp} labelled sharp, light {self.light}"
+        noisy = "" if self.noise is None else f", noise {self.noise}"
+        return (f"Plan {self.epoch} of {self.dir_data}: {runs} runs of {sum(c['T'] for c in self.sharp)} sharp frames, {sharp} labelled sharp, "
+                f"light {self.light}{noisy}")
+
+    def noise_lines(self) -> list:
+        """One line per clip on the levels the current plan drew for it; empty without noise."""
+        return [f"> {c['name']}: noise shot {c['noise'][0]:.3g} read {c['noise'][1]:.3g}" for c in self.clips if self.noise is not None]
 
     def nbytes(self) -> int:
         """Bytes of every sharp frame as uint8 RGB (from the image headers)."""
@@ -440,6 +453,25 @@ def run_records(clipset: SharpClipSet, store: SharpStore, items) -> np.ndarray:
     return rec
 
 
+def run_noise_records(clipset: SharpClipSet, items) -> np.ndarray:
+    """The spei_noise_record table beside `run_records`' table, record for record: the run's index in its clip's plan, the clip's index
+    in the scanned folders and the levels the plan drew for the clip.  A gt record (a run of length 1: no noise) carries its window's
+    middle run."""
+    from .light import NOISE_RECORD
+    n_seq, refs = clipset.n_seq, clipset.references
+    F = n_seq + (2 if refs else 0)
+    B = len(items)
+    rec = np.zeros(B * F + B, dtype=NOISE_RECORD)
+    inp, gt = rec[:B * F].reshape(B, F), rec[B * F:]
+    for b, (_idx, s, _d) in enumerate(items):
+        c = clipset.clips[s.clip]
+        inp[b]["run"] = list(s.frames) + ([s.pre, s.sub] if refs else [])
+        gt[b]["run"] = s.frames[n_seq // 2]
+        for part in (inp[b], gt[b:b + 1]):
+            part["clip"], part["A"], part["B"] = c["source"], c["noise"][2], c["noise"][3]
+    return rec
+
+
 class TrainLoader:
     """Iterates (input [B,F,3,P,P], gt [B,3,P,P]) fp32 device tensors of one epoch per `iter()`.
 
@@ -555,7 +587,8 @@ class SharpTrainLoader(TrainLoader):
     every crop in its load phase; ring, side stream and prefetch thread are TrainLoader's.  Every `iter()` is one epoch under its own
     plan (SharpSampler; `replan=False`: plan 0 throughout).  All launches of an epoch are issued before the next one is planned.  With
     `clipset.light` other than "code" the launch is spei_train_batch_runs_light_u8: the light's tables are uploaded here, once, and
-    handed to every launch."""
+    handed to every launch.  With `clipset.noise` it is spei_train_batch_runs_noise_u8: the noise records are built with the run
+    records, one batch ahead, under the seed of the plan in force, and travel through a ring of their own beside the table's."""
     RECORD = RUN_RECORD
 
     def __init__(self, clipset: SharpClipSet, store: SharpStore, batch: int, patch: int = 200, seed: int = 1, augment: bool = True,
@@ -566,9 +599,28 @@ class SharpTrainLoader(TrainLoader):
         if self.light != "code":
             from . import light as _light
             _light.device_tables(self.light, self.device)
+        self.noise = clipset.noise
+        if self.noise is not None:
+            from . import light as _light
+            _light.device_gauss(self.device)
+            nb = batch * (self.F + 1) * _light.NOISE_RECORD.itemsize
+            with torch.cuda.device(self.device):
+                for slot in self.slots:
+                    slot["noise_host"] = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
+                    slot["noise_dev"] = torch.empty(nb, dtype=torch.uint8, device=self.device)
 
     def _records(self, items) -> np.ndarray:
+        if self.noise is not None:                            # consumed by the `_build` of the same `_launch`
+            self._noise = (run_noise_records(self.clipset, items), self.clipset.seed + self.clipset.epoch)
         return run_records(self.clipset, self.store, items)
 
     def _build(self, *args) -> None:
-        self.ctx.train_batch_runs(*args, light=self.light)
+        if self.noise is None:
+            self.ctx.train_batch_runs(*args, light=self.light)
+            return
+        rec, seed = self._noise
+        slot = self.slots[(self.launched - 1) % self.RING]     # `_launch`'s slot: its event has been waited for
+        host, dev = slot["noise_host"][:rec.nbytes], slot["noise_dev"][:rec.nbytes]
+        host.numpy()[...] = rec.view(np.uint8).reshape(-1)
+        dev.copy_(host, non_blocking=True)
+        self.ctx.train_batch_runs(*args, light=self.light, noise=(dev, host, seed))

@@ -7,10 +7,12 @@ speinet_amd.trainer.Trainer, fed by speinet_amd.data.TrainLoader.
 
 Both directories hold blur/<clip>/*, gt/<clip>/* and (model speinet) label/<clip>.npy.  In place of `--dir_data`,
 
-        --dir_sharp <dir of folders of sharp frames> [--blur_ratio 0.1 0.3 0.5 --blur_threshold 5 --no_replan --blur_light code|srgb|gamma:<g>]
+        --dir_sharp <dir of folders of sharp frames> [--blur_ratio 0.1 0.3 0.5 --blur_threshold 5 --no_replan --blur_light code|srgb|gamma:<g>
+                                                      --blur_noise <shot>:<read>]
 
 trains from sharp high-frame-rate footage directly (an extension beyond the reference, which precomputes its sets): the frames stay on
-the device as uint8, every epoch e trains on the set `python -m speinet_amd.blurset --seed <seed + e> --light <blur_light>` would write —
+the device as uint8, every epoch e trains on the set `python -m speinet_amd.blurset --seed <seed + e> --light <blur_light> [--noise
+<blur_noise>]` would write (`--blur_noise`: sensor noise in the linear light, levels drawn per clip and per epoch; speinet_amd.light) —
 runs, labels and references re-drawn, nothing written — and every batch is averaged, cropped and augmented by one launch (data.SharpTrainLoader);
 `--no_replan` keeps epoch 0's set.  The validation set stays a written one.  Names and defaults are those of the reference's
 option/__init__.py and its SPEINet template.  Per epoch, in the reference's order: `scheduler.step()`, one `Trainer.step` per batch,
@@ -157,6 +159,8 @@ class Fit:
         for batch, (inp, gt) in enumerate(self.loader):
             if batch == 0 and hasattr(self.loader.clipset, "summary"):
                 self.log(self.loader.clipset.summary())      # a SharpClipSet: this epoch's runs
+                for line in self.loader.clipset.noise_lines():   # ... and the noise levels drawn for its clips
+                    self.log(line)
             total += self.trainer.step(inp, gt)
             n_batches += 1
             if (batch + 1) % self.print_every == 0:
@@ -260,6 +264,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--no_replan", action="store_true", help="--dir_sharp: keep epoch 0's runs for every epoch")
     ap.add_argument("--blur_light", default="code", help="--dir_sharp: the light the runs are averaged in: code (code values), srgb or "
                                                          "gamma:<g> (linear light; speinet_amd.light)")
+    ap.add_argument("--blur_noise", default=None, help="--dir_sharp: sensor noise added in the linear --blur_light: <shot>:<read>, each a number "
+                                                       "or lo..hi (drawn log-uniformly per clip and epoch; speinet_amd.light)")
     ap.add_argument("--dir_data_test", required=True)
     ap.add_argument("--save", required=True)
     ap.add_argument("--model", default="speinet", choices=("speinet", "swint"))
@@ -297,13 +303,22 @@ def main(argv=None) -> None:
     if a.dir_data and blur_light != _light.CODE:
         ap.error(f"--blur_light {blur_light} averages the runs of --dir_sharp; a written set (--dir_data) holds its blur already: make it "
                  "with `python -m speinet_amd.blurset --light`")
+    try:
+        blur_noise = _light.noise_name(a.blur_noise)
+    except ValueError as e:
+        ap.error(f"--blur_noise: {e}")
+    if a.dir_data and blur_noise is not None:
+        ap.error(f"--blur_noise {blur_noise} is added to the runs of --dir_sharp; a written set (--dir_data) holds its blur already: make it "
+                 "with `python -m speinet_amd.blurset --light --noise`")
+    if blur_noise is not None and blur_light == _light.CODE:
+        ap.error("--blur_noise is added in linear light: pass --blur_light srgb or --blur_light gamma:<g> with it")
     refs = a.model == "speinet"
     if a.dir_sharp and a.residency != "device":
         ap.error("--dir_sharp keeps the sharp frames on the device (--residency device); a set that does not fit is written with "
                  "`python -m speinet_amd.blurset` and trained with --dir_data")
     if a.dir_sharp:
         train_set = SharpClipSet(a.dir_sharp, a.blur_ratio, a.blur_threshold, seed=a.seed, n_frames_per_video=a.n_frames_per_video,
-                                 references=refs, patch=a.patch_size, light=blur_light)
+                                 references=refs, patch=a.patch_size, light=blur_light, noise=blur_noise)
     else:
         train_set = ClipSet(a.dir_data, True, 3, a.n_frames_per_video, references=refs, patch=a.patch_size)
     val_set = ClipSet(a.dir_data_test, False, 3, a.n_frames_per_video, references=refs)

@@ -25,17 +25,57 @@ by the C entry points on the host copy they are handed.
 
 `srgb` and `gamma:2.2` are the conventional approximations of a camera curve that is not known; no model has been trained here on
 either.
+
+SENSOR NOISE (opt-in; `noise=` / `--noise` / `--blur_noise`).  The mean of n frames carries 1 / n of one frame's noise variance, so a
+long run comes out almost noise-free where a real exposure has the noise of any other frame.  With a noise spec the variance that the
+average lost is added back in linear light, between the average and the encode, again bit for bit in integers.  Noise needs a linear
+light: `code` plus noise is a ValueError.
+
+    words     Philox4x32-10 (Salmon et al., SC'11): multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85, ten
+              rounds.  For the pixel at column x, row y of the full source frame (before any crop, flip or rotation) of output frame
+              `run` of clip `clip`: counter (x, y, run, clip), key (seed & 0xffffffff, (seed >> 32) & 0xffffffff); output words 0, 1, 2
+              serve the R, G and B bytes, word 3 is unused.  Nothing depends on launch geometry, chunking, crop position or augmentation.
+    t[i]      round(4096 * statistics.NormalDist().inv_cdf(min(max(i / 1024, 2^-13), 1 - 2^-13))), i = 0..1024     (`gauss_table`)
+              VALID iff strictly increasing and |t[i]| < 2^15.
+    z         for a word w: i = w >> 22, f = (w >> 10) & 4095, z = (t[i] (4096 - f) + t[i + 1] f + 2048) >> 12   (arithmetic shift, Q12)
+    V         floor((A L + B) (n - 1) / n)            per byte, with L as above and the clip's integers A < 2^20, B < 2^42
+    sigma     isqrt(V)
+    d         (sigma z + 2048) >> 12
+    L'        clamp(L + d, 0, S);   blur = encode(L')
+
+(n - 1) / n tops the average's noise up to the level of ONE source frame, so a run of length 1 — every ground-truth record — has d = 0
+and still returns its bytes.  The gray plane is that of the noisy encoded bytes; a `zero` record stays zero.
+
+    levels    one shot coefficient a and one read deviation r per clip: full scale 1, variance a x + r^2; 0 <= a <= 0.05, 0 <= r <= 0.1;
+              A = rint(a S), B = rint(r^2 S^2)
+    spec      "<shot>:<read>", each side a number or "lo..hi" with 0 < lo <= hi: a range is drawn log-uniformly per clip and per seed,
+              on the host: w = philox((0xffffffff, 0xffffffff, 0, clip), key), a = lo (hi / lo) ** (w0 / 2^32), r likewise from w1.
+    ids       clip: the clip's index in blurset.clip_folders order (SharpClipSet's `source`); run: the run's index in the clip's plan,
+              the number in the six-digit file name, global across synthesize_chunks' chunks; seed: write_dataset's, seed + e in epoch e.
+
+The plan's random.Random stream is not touched: plan_dataset's output is the same with and without noise.  One level per clip, not
+one per frame: a clip is shot at one gain.  The levels are NOT fitted to any camera, and no model has been trained with them here.
 """
 from __future__ import annotations
 
 import math
+import statistics
 import threading
+from collections import namedtuple
 from typing import Optional, Tuple
 
 import numpy as np
 
 S = 2 ** 24 - 1
 CODE = "code"
+
+MAX_SHOT, MAX_READ = 0.05, 0.1
+GAUSS_WORDS = 1025
+# spei_noise_record
+NOISE_RECORD = np.dtype([("run", "<u4"), ("clip", "<u4"), ("A", "<u4"), ("reserved", "<u4"), ("B", "<u8")])
+assert NOISE_RECORD.itemsize == 24
+# the noise of one clip for blurset.synthesize: its spec, write_dataset's seed, the clip's index and the id of the first run handed over
+ClipNoise = namedtuple("ClipNoise", "spec seed clip first_run", defaults=(0,))
 
 _cache = {}
 _cache_lock = threading.Lock()
@@ -128,6 +168,128 @@ def device_tables(spec, device):
         if key not in _cache:
             lin, thr = tables(spec)
             host = torch.from_numpy(np.concatenate([lin, thr]).astype(np.int32))
+            on = host.to(dev)
+            torch.cuda.current_stream(dev).synchronize()
+            _cache[key] = (on, host)
+        return _cache[key]
+
+
+# ---- sensor noise ----
+
+def philox(counter, key) -> Tuple[int, int, int, int]:
+    """Philox4x32-10 of four counter words under two key words, in Python integers (the host's draws; the kernels have their own)."""
+    c0, c1, c2, c3 = (int(v) & 0xffffffff for v in counter)
+    k0, k1 = (int(v) & 0xffffffff for v in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xffffffff, (p0 >> 32) ^ c3 ^ k1, p0 & 0xffffffff
+        k0, k1 = (k0 + 0x9E3779B9) & 0xffffffff, (k1 + 0xBB67AE85) & 0xffffffff
+    return c0, c1, c2, c3
+
+
+def key_of(seed: int) -> Tuple[int, int]:
+    """(key0, key1) of a seed."""
+    return int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff
+
+
+def gauss_table() -> np.ndarray:
+    """The 1025 Q12 quantiles of the standard normal distribution the kernels interpolate in, int32."""
+    nd = statistics.NormalDist()
+    lo = 2.0 ** -13
+    return np.array([round(4096 * nd.inv_cdf(min(max(i / 1024, lo), 1 - lo))) for i in range(GAUSS_WORDS)], dtype=np.int32)
+
+
+def gauss_valid(t) -> bool:
+    """Is `t` a table the C entry points accept: 1025 words, strictly increasing, every |t[i]| < 2^15?"""
+    t = np.asarray(t).astype(np.int64).reshape(-1)
+    return bool(t.size == GAUSS_WORDS and np.all(t[:-1] < t[1:]) and np.all(np.abs(t) < 2 ** 15))
+
+
+def _side(text: str, what: str, top: float):
+    def number(v):
+        try:
+            x = float(v)
+        except ValueError:
+            x = math.nan
+        if not math.isfinite(x):
+            raise ValueError(f"noise: {what} {v!r} is not a number")
+        if not 0 <= x <= top:
+            raise ValueError(f"noise: {what} {x!r} lies outside [0, {top}]")
+        return x
+    if ".." in text:
+        lo, hi = (number(v) for v in text.split("..", 1))
+        if not 0 < lo <= hi:
+            raise ValueError(f"noise: the {what} range {text!r} needs 0 < lo <= hi (it is drawn log-uniformly)")
+        return lo, hi
+    x = number(text)
+    return x, x
+
+
+def parse_noise(spec):
+    """`spec` "<shot>:<read>", each side a number or "lo..hi" -> ((shot lo, shot hi), (read lo, read hi)); None -> None.  ValueError
+    for anything else, for a level outside 0 <= shot <= 0.05, 0 <= read <= 0.1 and for a range without 0 < lo <= hi."""
+    if spec is None:
+        return None
+    if not isinstance(spec, str) or spec.count(":") != 1:
+        raise ValueError(f"noise {spec!r}: expected '<shot>:<read>', each a number or 'lo..hi'")
+    shot, read = spec.split(":")
+    return _side(shot.strip(), "shot coefficient", MAX_SHOT), _side(read.strip(), "read deviation", MAX_READ)
+
+
+def noise_text(parsed) -> str:
+    return ":".join(repr(lo) if lo == hi else f"{lo!r}..{hi!r}" for lo, hi in parsed)
+
+
+def noise_name(spec) -> Optional[str]:
+    """The canonical spelling of a noise spec (the reprs of its floats), or None for None."""
+    return None if spec is None else noise_text(parse_noise(spec))
+
+
+def check_noise(light, noise) -> None:
+    """ValueError for a noise spec that does not parse and for noise on the light `code`."""
+    if noise is None:
+        return
+    parse_noise(noise)
+    if is_code(light):
+        raise ValueError("noise is added in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
+
+
+def noise_draw(spec, seed: int, clip: int) -> Tuple[float, float]:
+    """(a, r) of clip `clip` under `seed`: a side that is a number is that number, a range is drawn log-uniformly from the Philox words
+    of the counter (0xffffffff, 0xffffffff, 0, clip) — no pixel has that counter."""
+    (a_lo, a_hi), (r_lo, r_hi) = parse_noise(spec)
+    w = philox((0xffffffff, 0xffffffff, 0, clip), key_of(seed))
+    a = a_lo if a_lo == a_hi else min(max(a_lo * (a_hi / a_lo) ** (w[0] / 2.0 ** 32), a_lo), a_hi)
+    r = r_lo if r_lo == r_hi else min(max(r_lo * (r_hi / r_lo) ** (w[1] / 2.0 ** 32), r_lo), r_hi)
+    return a, r
+
+
+def noise_levels(spec, seed: int, clip: int) -> Tuple[int, int]:
+    """(A, B) = (rint(a S), rint(r^2 S^2)) of clip `clip` under `seed`."""
+    a, r = noise_draw(spec, seed, clip)
+    return int(np.rint(a * S)), int(np.rint(r * r * float(S) * float(S)))
+
+
+def noise_records(runs, clip: int, A: int, B: int) -> np.ndarray:
+    """NOISE_RECORD [len(runs)] of one clip: the run ids `runs` at the levels (A, B)."""
+    runs = np.asarray(runs, np.int64).reshape(-1)
+    rec = np.zeros(runs.size, dtype=NOISE_RECORD)
+    rec["run"], rec["clip"], rec["A"], rec["B"] = runs, clip, A, B
+    return rec
+
+
+def device_gauss(device):
+    """(device, host) int32 tensors of the gauss table for the C entry points, made once per device and kept, as `device_tables`."""
+    import torch
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("the gauss table lives on an MI355X (HIP kernels); there is no CPU path")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = ("gauss", dev.index)
+    with _cache_lock:
+        if key not in _cache:
+            host = torch.from_numpy(gauss_table())
             on = host.to(dev)
             torch.cuda.current_stream(dev).synchronize()
             _cache[key] = (on, host)
