@@ -517,6 +517,34 @@ int spei_frame_u16_out(const float* src, uint16_t* dst, int* nonfinite, int H, i
 int spei_frame_pair_stats_u16(const uint16_t* src, int64_t frame_stride, const uint16_t* prev, int N, int H, int W, int depth, int* hist,
                               int64_t* sad, spei_stream_t stream);
 
+/* ---- tile I/O of the clip API's large-frame mode (speinet_amd/tiles.py; the reference's forward_chop, inference_SPEINet.py:545-607,
+ * is the 2x2 case) ----
+ * A frame is deblurred as a grid of rows x cols (1..8 each) overlapping tiles of ONE shape th x tw, tile k = i * cols + j at rows
+ * y0[i].. and columns x0[j].., and stitched with hard seams: tile (i, j) owns the band [yb[i], yb[i+1]) x [xb[j], xb[j+1]).  Every
+ * `*_host` table is a HOST array, read during the call and passed to the kernel by value: it may be freed when the call returns.
+ * A bad table (rows or cols out of range, a tile outside the frame, a band outside its tile, bands that do not span the frame)
+ * returns non-zero before anything is launched.
+ * spei_tiles_u8_in: src one packed uint8 [H][W][3] frame -> for every tile k, fp32 [3][thp][twp] at dst + k * tile_stride (floats;
+ *   thp / twp = th / tw rounded up to multiples of 20; tile_stride >= 3 * thp * twp and a multiple of 4, dst 16-byte aligned),
+ *   bit-identical to spei_frames_u8_in on the packed crop src[y0[i] : y0[i] + th][x0[j] : x0[j] + tw], its reflect pad included
+ *   (which needs thp - th < th and twp - tw < tw).  One launch.
+ * spei_tiles_u16_in: the same on a packed uint16 frame of `depth` 10 or 12, bit-identical to spei_frames_u16_in on the crop.
+ * spei_tiles_u8_out: tiles_host = rows * cols device pointers to fp32 [3][thp][twp] (twp a multiple of 4) -> dst packed uint8
+ *   [H][W][3]: pixel (y, x) of band (i, j) is spei_frame_u8_out's value of tile[i * cols + j][c][y - y0[i]][x - x0[j]].  nonfinite
+ *   (or NULL): one int, cleared on the stream, then nonzero iff a pixel of a band (an OWNED pixel) was a NaN or an infinity; what
+ *   a tile holds outside its band is never read.  One launch.
+ * spei_tiles_u16_out: the same with spei_frame_u16_out's values for `depth` 10 or 12, dst packed uint16. */
+int spei_tiles_u8_in(const unsigned char* src, int H, int W, float* dst, int64_t tile_stride, const int* y0_host, const int* x0_host,
+                     int rows, int cols, int th, int tw, spei_stream_t stream);
+int spei_tiles_u16_in(const uint16_t* src, int H, int W, float* dst, int64_t tile_stride, const int* y0_host, const int* x0_host,
+                      int rows, int cols, int th, int tw, int depth, spei_stream_t stream);
+int spei_tiles_u8_out(const float* const* tiles_host, unsigned char* dst, int* nonfinite, int H, int W, const int* y0_host,
+                      const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp,
+                      spei_stream_t stream);
+int spei_tiles_u16_out(const float* const* tiles_host, uint16_t* dst, int* nonfinite, int H, int W, const int* y0_host,
+                       const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp, int depth,
+                       spei_stream_t stream);
+
 /* ---- planar YUV frames of the clip API (speinet_amd/y4m.py, speinet_amd/video.py; an extension beyond the reference) ---- */
 
 #define SPEI_YUV_420_CENTER 0 /* 4:2:0, chroma sample at the centre of its 2x2 block (y4m C420jpeg, and bare C420) */

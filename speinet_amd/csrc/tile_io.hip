@@ -1,0 +1,271 @@
+// Tile I/O of the clip API's large-frame mode (speinet_amd/tiles.py, video.deblur_clip(..., tiles=)): a frame is deblurred as a grid
+// of rows x cols overlapping tiles of ONE shape, stitched with hard seams, as the reference's forward_chop does for 2x2
+// (inference_SPEINet.py:545-607).
+//
+//   spei_tiles_u8_in / spei_tiles_u16_in   — one packed [H][W][3] frame -> every tile's fp32 [3][thp][twp] planes, tile k = i * cols + j
+//                        at dst + k * tile_stride: bit-identical to spei_frames_u8_in / spei_frames_u16_in (frame_io.hip) on the packed
+//                        crop [y0[i], y0[i] + th) x [x0[j], x0[j] + tw), its reflect pad to thp x twp included.  One launch per frame.
+//   spei_tiles_u8_out / spei_tiles_u16_out — rows * cols fp32 [3][thp][twp] tiles -> one packed [H][W][3] frame: pixel (y, x) of band
+//                        [yb[i], yb[i+1]) x [xb[j], xb[j+1]) comes from tile (i, j) with spei_frame_u8_out / spei_frame_u16_out's
+//                        rounding; the flag is set by OWNED pixels only, a tile's margin is never read.  One launch per frame.
+//
+// The tables (at most 8 origins and 9 band bounds per axis, 64 tile pointers) are read from host memory at call time and travel to the
+// kernel by value, in its arguments.  Streaming kernels in the style of frame_io.hip: one thread per group of 4 pixels of a row, 12
+// bytes (24 for deep frames) as three dwords (three 8-byte words) where the address allows and sample by sample otherwise, one
+// 16-byte access per plane.  Tile origins are arbitrary, so the ingest decides per row whether its source is aligned, and the egress
+// per group whether its four pixels are one aligned run of one tile.
+#include "common.h"
+
+namespace {
+
+constexpr int MULT = 20;
+constexpr int GRID_MAX = 8;                                // rows, cols
+constexpr int BLOCKS_MAX = 8192;
+constexpr float INV255 = (float)(1.0 / 255.0);             // spei_frames_u8_in's scale
+
+struct InTab { int y0[GRID_MAX], x0[GRID_MAX]; };
+struct OutTab {
+    const float* tile[GRID_MAX * GRID_MAX];
+    int y0[GRID_MAX], x0[GRID_MAX], yb[GRID_MAX + 1], xb[GRID_MAX + 1];
+};
+
+__device__ __forceinline__ int byte_of(const uint32_t (&w)[3], int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xff; }
+__device__ __forceinline__ int half_of(const uint2 (&w)[3], int j) {
+    const uint2 q = w[j >> 2];
+    return (((j & 2) ? q.y : q.x) >> (16 * (j & 1))) & 0xffff;
+}
+
+// T = unsigned char (D = 255, inv = INV255) or uint16_t (D = 2^depth - 1, inv = (float)(1.0 / D); a word above D reads as D)
+template <typename T>
+__global__ __launch_bounds__(256) void tiles_in_kernel(const T* __restrict__ src, int W, float* __restrict__ dst, int64_t tstride,
+                                                       InTab tab, int cols, int th, int tw, int thp, int twp, int64_t total, int D,
+                                                       float inv) {
+    constexpr uintptr_t MASK = sizeof(T) == 1 ? 3 : 7;     // a group is 12 (24) bytes: aligned iff its row's first sample is
+    const int gw = twp >> 2;                               // groups per padded row (twp % 20 == 0)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / gw;                        // k * thp + y
+        const int x = (int)(i - row * gw) * 4;
+        const int k = (int)(row / thp), y = (int)(row - (int64_t)k * thp);
+        const int ti = k / cols, tj = k - ti * cols;
+        const int sy = y < th ? y : 2 * th - 2 - y;        // padded row th + j reads row th - 2 - j of the tile
+        const T* s = src + ((int64_t)(tab.y0[ti] + sy) * W + tab.x0[tj]) * 3;
+        float v[3][4];
+        if (x + 4 <= tw && ((uintptr_t)s & MASK) == 0) {   // interior of an aligned row: 12 consecutive samples
+            if constexpr (sizeof(T) == 1) {
+                const uint32_t* p = reinterpret_cast<const uint32_t*>(s + x * 3);
+                const uint32_t w[3] = {p[0], p[1], p[2]};
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) v[c][q] = (float)byte_of(w, 3 * q + c);
+            } else {
+                const uint2* p = reinterpret_cast<const uint2*>(s + x * 3);
+                const uint2 w[3] = {p[0], p[1], p[2]};
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) v[c][q] = (float)min(half_of(w, 3 * q + c), D);
+            }
+        } else {                                           // unaligned rows, right edge and pad band: column tw + j reads tw - 2 - j
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int xx = x + q, sx = xx < tw ? xx : 2 * tw - 2 - xx;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][q] = (float)min((int)s[sx * 3 + c], D);
+            }
+        }
+        float* d = dst + k * tstride + (int64_t)y * twp + x;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            *reinterpret_cast<float4*>(d + (int64_t)c * thp * twp) = make_float4(v[c][0] * inv, v[c][1] * inv, v[c][2] * inv, v[c][3] * inv);
+    }
+}
+
+__device__ __forceinline__ uint32_t quantise(float v, float Df) {
+    const float q = rintf(fminf(fmaxf(v * Df, 0.0f), Df));             // mul(D).clamp(0, D).round(): half to even, as torch
+    return isfinite(v) ? (uint32_t)q : 0u;
+}
+
+// the band of coordinate p: the number of inner bounds b[1 .. n-1] at or below it
+__device__ __forceinline__ int band_of(const int (&b)[GRID_MAX + 1], int n, int p) {
+    int r = 0;
+#pragma unroll
+    for (int i = 1; i < GRID_MAX; ++i) r += (i < n && p >= b[i]) ? 1 : 0;
+    return r;
+}
+
+// T = unsigned char (Df = 255) or uint16_t (Df = 2^depth - 1)
+template <typename T>
+__global__ __launch_bounds__(256) void tiles_out_kernel(OutTab tab, T* __restrict__ dst, int* __restrict__ nonfinite, int W, int rows,
+                                                        int cols, int twp, int64_t plane, int gw, int64_t total, int vec_out, float Df) {
+    int bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int y = (int)(i / gw), x = (int)(i - (int64_t)y * gw) * 4;
+        const int bi = band_of(tab.yb, rows, y), bj = band_of(tab.xb, cols, x);
+        const int ry = y - tab.y0[bi];
+        uint32_t q[3][4];
+        const float* t = tab.tile[bi * cols + bj];
+        const int rx = x - tab.x0[bj];
+        if (x + 4 <= W && band_of(tab.xb, cols, x + 3) == bj && (rx & 3) == 0 && ((uintptr_t)t & 15) == 0) {
+            const float* s = t + (int64_t)ry * twp + rx;   // four owned pixels of one tile, 16-byte aligned there (twp % 4 == 0)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float4 f = *reinterpret_cast<const float4*>(s + c * plane);
+                const float e[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    q[c][k] = quantise(e[k], Df);
+                    bad |= isfinite(e[k]) ? 0 : 1;
+                }
+            }
+        } else {                                           // a seam inside the group, an odd tile column or the frame's right edge
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int xx = x + k;
+                const int j = band_of(tab.xb, cols, xx);   // xx >= W: the last band, never read
+                const float* s = tab.tile[bi * cols + j] + (int64_t)ry * twp + (xx - tab.x0[j]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float v = xx < W ? s[c * plane] : 0.0f;
+                    q[c][k] = quantise(v, Df);
+                    bad |= isfinite(v) ? 0 : 1;
+                }
+            }
+        }
+        T* d = dst + ((int64_t)y * W + x) * 3;
+        if (vec_out && x + 4 <= W) {                       // 12 samples as three dwords (three 8-byte words)
+            if constexpr (sizeof(T) == 1) {
+                uint32_t w[3] = {0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 12; ++j) w[j >> 2] |= q[j % 3][j / 3] << (8 * (j & 3));
+                uint32_t* p = reinterpret_cast<uint32_t*>(d);
+                p[0] = w[0]; p[1] = w[1]; p[2] = w[2];
+            } else {
+                uint32_t w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 12; ++j) w[j >> 1] |= q[j % 3][j / 3] << (16 * (j & 1));
+                uint2* p = reinterpret_cast<uint2*>(d);
+                p[0] = make_uint2(w[0], w[1]); p[1] = make_uint2(w[2], w[3]); p[2] = make_uint2(w[4], w[5]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x + k < W)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) d[k * 3 + c] = (T)q[c][k];
+        }
+    }
+    if (nonfinite && bad) atomicOr(nonfinite, 1);           // rare: one atomic per thread that met a non-finite value
+}
+
+inline int grid_for(int64_t total) { return (int)((total + 255) / 256 < BLOCKS_MAX ? (total + 255) / 256 : BLOCKS_MAX); }
+
+template <typename T>
+int tiles_in(const char* name, const T* src, int H, int W, float* dst, int64_t tile_stride, const int* y0, const int* x0, int rows,
+             int cols, int th, int tw, int depth, hipStream_t stream) {
+    SPEI_REQUIRE(src && dst && y0 && x0, "%s: null pointer", name);
+    SPEI_REQUIRE(H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
+    SPEI_REQUIRE(rows >= 1 && rows <= GRID_MAX && cols >= 1 && cols <= GRID_MAX, "%s: a grid of %dx%d tiles (1..%d rows and columns)",
+                 name, rows, cols, GRID_MAX);
+    SPEI_REQUIRE(th > 0 && tw > 0 && th <= H && tw <= W, "%s: a %dx%d tile does not fit a %dx%d frame", name, th, tw, H, W);
+    const int thp = (th + MULT - 1) / MULT * MULT, twp = (tw + MULT - 1) / MULT * MULT;
+    SPEI_REQUIRE(thp - th < th && twp - tw < tw, "%s: a %dx%d tile cannot reflect-pad to %dx%d (the pad must be smaller than the tile)",
+                 name, th, tw, thp, twp);
+    SPEI_REQUIRE(sizeof(T) == 1 || depth == 10 || depth == 12, "%s: unknown depth %d (10 or 12)", name, depth);
+    SPEI_REQUIRE(((uintptr_t)src & (sizeof(T) - 1)) == 0, "%s: src must be %d-byte aligned", name, (int)sizeof(T));
+    SPEI_REQUIRE(((uintptr_t)dst & 15) == 0 && (tile_stride & 3) == 0, "%s: dst must be 16-byte aligned and the tile stride a multiple of "
+                 "4 floats", name);
+    SPEI_REQUIRE(tile_stride >= (int64_t)3 * thp * twp, "%s: tile stride %lld < one tile of 3x%dx%d floats", name, (long long)tile_stride,
+                 thp, twp);
+    InTab tab = {};
+    for (int i = 0; i < rows; ++i) {
+        SPEI_REQUIRE(y0[i] >= 0 && y0[i] <= H - th, "%s: tile row %d at y %d, %d rows, lies outside the %dx%d frame", name, i, y0[i], th, H, W);
+        tab.y0[i] = y0[i];
+    }
+    for (int j = 0; j < cols; ++j) {
+        SPEI_REQUIRE(x0[j] >= 0 && x0[j] <= W - tw, "%s: tile column %d at x %d, %d columns, lies outside the %dx%d frame", name, j, x0[j],
+                     tw, H, W);
+        tab.x0[j] = x0[j];
+    }
+    const int64_t total = (int64_t)rows * cols * thp * (twp / 4);
+    const int D = sizeof(T) == 1 ? 255 : (1 << depth) - 1;
+    hipLaunchKernelGGL(tiles_in_kernel<T>, dim3(grid_for(total)), dim3(256), 0, stream, src, W, dst, tile_stride, tab, cols, th, tw, thp,
+                       twp, total, D, sizeof(T) == 1 ? INV255 : (float)(1.0 / D));
+    SPEI_CHECK_LAUNCH(name);
+    return 0;
+}
+
+template <typename T>
+int tiles_out(const char* name, const float* const* tiles, T* dst, int* nonfinite, int H, int W, const int* y0, const int* x0,
+              const int* yb, const int* xb, int rows, int cols, int thp, int twp, int depth, hipStream_t stream) {
+    SPEI_REQUIRE(tiles && dst && y0 && x0 && yb && xb, "%s: null pointer", name);
+    SPEI_REQUIRE(H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
+    SPEI_REQUIRE(rows >= 1 && rows <= GRID_MAX && cols >= 1 && cols <= GRID_MAX, "%s: a grid of %dx%d tiles (1..%d rows and columns)",
+                 name, rows, cols, GRID_MAX);
+    SPEI_REQUIRE(thp > 0 && twp > 0 && (twp & 3) == 0 && (int64_t)thp * twp < (1ll << 30), "%s: bad tile planes %dx%d (the width a "
+                 "multiple of 4)", name, thp, twp);
+    SPEI_REQUIRE(sizeof(T) == 1 || depth == 10 || depth == 12, "%s: unknown depth %d (10 or 12)", name, depth);
+    SPEI_REQUIRE(((uintptr_t)dst & (sizeof(T) - 1)) == 0, "%s: dst must be %d-byte aligned", name, (int)sizeof(T));
+    OutTab tab = {};
+    SPEI_REQUIRE(yb[0] == 0 && yb[rows] == H && xb[0] == 0 && xb[cols] == W, "%s: the bands must span the %dx%d frame (rows %d..%d, "
+                 "columns %d..%d)", name, H, W, yb[0], yb[rows], xb[0], xb[cols]);
+    for (int i = 0; i < rows; ++i) {
+        SPEI_REQUIRE(yb[i] < yb[i + 1], "%s: row band %d is empty or reversed (%d..%d)", name, i, yb[i], yb[i + 1]);
+        SPEI_REQUIRE(y0[i] >= 0 && y0[i] < H, "%s: tile row %d at y %d lies outside the %dx%d frame", name, i, y0[i], H, W);
+        SPEI_REQUIRE(y0[i] <= yb[i] && yb[i + 1] - y0[i] <= thp, "%s: row band %d (%d..%d) lies outside its tile (%d..%d)", name, i, yb[i],
+                     yb[i + 1], y0[i], y0[i] + thp);
+        tab.y0[i] = y0[i];
+    }
+    for (int j = 0; j < cols; ++j) {
+        SPEI_REQUIRE(xb[j] < xb[j + 1], "%s: column band %d is empty or reversed (%d..%d)", name, j, xb[j], xb[j + 1]);
+        SPEI_REQUIRE(x0[j] >= 0 && x0[j] < W, "%s: tile column %d at x %d lies outside the %dx%d frame", name, j, x0[j], H, W);
+        SPEI_REQUIRE(x0[j] <= xb[j] && xb[j + 1] - x0[j] <= twp, "%s: column band %d (%d..%d) lies outside its tile (%d..%d)", name, j,
+                     xb[j], xb[j + 1], x0[j], x0[j] + twp);
+        tab.x0[j] = x0[j];
+    }
+    for (int i = 0; i <= rows; ++i) tab.yb[i] = yb[i];
+    for (int j = 0; j <= cols; ++j) tab.xb[j] = xb[j];
+    for (int k = 0; k < rows * cols; ++k) {
+        SPEI_REQUIRE(tiles[k] && ((uintptr_t)tiles[k] & 3) == 0, "%s: tile %d is a null or misaligned pointer", name, k);
+        tab.tile[k] = tiles[k];
+    }
+    const int gw = (W + 3) / 4;
+    const int vec_out = (W & 3) == 0 && ((uintptr_t)dst & (sizeof(T) == 1 ? 3 : 7)) == 0;
+    const int64_t total = (int64_t)H * gw;
+    if (nonfinite && hipMemsetAsync(nonfinite, 0, sizeof(int), stream) != hipSuccess) {
+        spei_set_error("%s: clearing the non-finite flag failed", name);
+        return -2;
+    }
+    hipLaunchKernelGGL(tiles_out_kernel<T>, dim3(grid_for(total)), dim3(256), 0, stream, tab, dst, nonfinite, W, rows, cols, twp,
+                       (int64_t)thp * twp, gw, total, vec_out, sizeof(T) == 1 ? 255.0f : (float)((1 << depth) - 1));
+    SPEI_CHECK_LAUNCH(name);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int spei_tiles_u8_in(const unsigned char* src, int H, int W, float* dst, int64_t tile_stride, const int* y0_host,
+                                const int* x0_host, int rows, int cols, int th, int tw, spei_stream_t stream) {
+    return tiles_in<unsigned char>("spei_tiles_u8_in", src, H, W, dst, tile_stride, y0_host, x0_host, rows, cols, th, tw, 8,
+                                   (hipStream_t)stream);
+}
+
+extern "C" int spei_tiles_u16_in(const uint16_t* src, int H, int W, float* dst, int64_t tile_stride, const int* y0_host,
+                                 const int* x0_host, int rows, int cols, int th, int tw, int depth, spei_stream_t stream) {
+    return tiles_in<uint16_t>("spei_tiles_u16_in", src, H, W, dst, tile_stride, y0_host, x0_host, rows, cols, th, tw, depth,
+                              (hipStream_t)stream);
+}
+
+extern "C" int spei_tiles_u8_out(const float* const* tiles_host, unsigned char* dst, int* nonfinite, int H, int W, const int* y0_host,
+                                 const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp,
+                                 spei_stream_t stream) {
+    return tiles_out<unsigned char>("spei_tiles_u8_out", tiles_host, dst, nonfinite, H, W, y0_host, x0_host, yb_host, xb_host, rows, cols,
+                                    thp, twp, 8, (hipStream_t)stream);
+}
+
+extern "C" int spei_tiles_u16_out(const float* const* tiles_host, uint16_t* dst, int* nonfinite, int H, int W, const int* y0_host,
+                                  const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp,
+                                  int depth, spei_stream_t stream) {
+    return tiles_out<uint16_t>("spei_tiles_u16_out", tiles_host, dst, nonfinite, H, W, y0_host, x0_host, yb_host, xb_host, rows, cols,
+                               thp, twp, depth, (hipStream_t)stream);
+}

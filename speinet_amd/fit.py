@@ -30,7 +30,7 @@ loader's sampler is advanced by as many epochs, so the resumed run continues wit
 would see (torch's and numpy's generators — DropPath, the HEM masks — are re-seeded, not restored, as in the reference).
 Multi-rank (one process per GPU under torch.distributed): `seed_rank`, and rank r takes every world-th batch of the shared epoch
 order; rank 0 evaluates and writes the files.  That split is tested on the CPU (gloo); a multi-GPU run of this loop has not been made.
-Not built: the logger's plots, forward_chop, save_images.  The data set itself and its labels come from speinet_amd.blurset and
+Not built: the logger's plots, forward_chop in training (the clip API has it: speinet_amd.tiles), save_images.  The data set itself and its labels come from speinet_amd.blurset and
 speinet_amd.detector.
 """
 from __future__ import annotations

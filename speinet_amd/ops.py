@@ -406,6 +406,87 @@ def frame_u16_out(x: torch.Tensor, h: int, w: int, depth: int, out: Optional[tor
     return out
 
 
+def _int_table(values, n: int, what: str):
+    """A host table of n ints for the tile entry points (read during the call)."""
+    vals = [int(v) for v in values]
+    if len(vals) != n:
+        raise ValueError(f"the tile plan's {what} has {len(vals)} entries, not {n}")
+    return (C.c_int * n)(*vals)
+
+
+def tiles_in(frame: torch.Tensor, plan, out: torch.Tensor, depth: Optional[int] = None) -> torch.Tensor:
+    """One packed frame [H,W,3] on the device, uint8 (`depth` None) or uint16 of `depth` 10 or 12 bits -> every tile of `plan` (a
+    `tiles.TilePlan`, or anything with its fields) as fp32 planes in `out` [plan.n, 3, thp, twp]: tile k = i * cols + j is
+    bit-identical to `frames_u8_in` / `frames_u16_in` on the crop frame[y0[i] : y0[i] + th, x0[j] : x0[j] + tw], reflect pad included.
+    `out` may be a view with any tile stride (a multiple of 4 floats) whose tiles are contiguous, such as x[:, j] of the window inputs
+    [n, n_seq + 2, 3, thp, twp] of all tiles.  One launch on the current stream (csrc/tile_io.hip), no host sync."""
+    deep = frame.dtype == torch.uint16
+    assert frame.is_cuda and frame.dtype in (torch.uint8, torch.uint16) and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    if deep:
+        depth = _depth(depth)
+    elif depth is not None:
+        raise ValueError(f"depth= applies to uint16 frames only; the frame is {frame.dtype}")
+    h, w = frame.shape[:2]
+    if (h, w) != (plan.H, plan.W):
+        raise ValueError(f"the tile plan is for a {plan.W}x{plan.H} frame, the frame is {w}x{h}")
+    thp, twp = padded_size(plan.th), padded_size(plan.tw)
+    n = plan.rows * plan.cols
+    assert out.is_cuda and out.device == frame.device and out.dtype == torch.float32 and tuple(out.shape) == (n, 3, thp, twp)
+    assert out.stride()[1:] == (thp * twp, twp, 1), "every tile of out must be contiguous (any tile stride)"
+    y0, x0 = _int_table(plan.y0, plan.rows, "y0"), _int_table(plan.x0, plan.cols, "x0")
+    lib = _lib.lib()
+    with torch.cuda.device(frame.device):
+        st = C.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)
+        stride = out.stride(0) if n > 1 else 3 * thp * twp
+        if deep:
+            _lib.check(lib.spei_tiles_u16_in(_vp(frame.data_ptr()), h, w, _vp(out.data_ptr()), stride, y0, x0, plan.rows, plan.cols,
+                                             plan.th, plan.tw, depth, st), "spei_tiles_u16_in")
+        else:
+            _lib.check(lib.spei_tiles_u8_in(_vp(frame.data_ptr()), h, w, _vp(out.data_ptr()), stride, y0, x0, plan.rows, plan.cols,
+                                            plan.th, plan.tw, st), "spei_tiles_u8_in")
+    return out
+
+
+def tiles_out(tiles, plan, out_depth: int = 8, out: Optional[torch.Tensor] = None,
+              nonfinite: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The tiles of `plan` (plan.n contiguous fp32 [3,thp,twp] tensors on one device, or one tensor of them; tile k = i * cols + j)
+    -> the stitched frame, uint8 [H,W,3] for `out_depth` 8 and uint16 for 10 and 12: pixel (y, x) of band [yb[i], yb[i+1]) x
+    [xb[j], xb[j+1]) has `frame_u8_out` / `frame_u16_out`'s value of tile (i, j) at (y - y0[i], x - x0[j]).  Hard seams, no blending.
+    `out` (optional): the packed destination.  `nonfinite` (optional): an int32 device tensor whose first element becomes nonzero iff
+    a pixel of a band was a NaN or an infinity; a tile's margin outside its band is never read.  One launch on the current stream
+    (csrc/tile_io.hip), no host sync."""
+    n = plan.rows * plan.cols
+    tiles = list(tiles)
+    if len(tiles) != n:
+        raise ValueError(f"the tile plan has {n} tiles, got {len(tiles)}")
+    thp, twp = padded_size(plan.th), padded_size(plan.tw)
+    dev = tiles[0].device
+    for t in tiles:
+        assert t.is_cuda and t.device == dev and t.dtype == torch.float32 and tuple(t.shape) == (3, thp, twp) and t.is_contiguous()
+    if out_depth not in y4m.DEPTHS:
+        raise ValueError(f"out_depth must be 8, 10 or 12, got {out_depth!r}")
+    dtype = torch.uint8 if out_depth == 8 else torch.uint16
+    h, w = plan.H, plan.W
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=dtype, device=dev)
+    assert out.device == dev and out.dtype == dtype and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
+    assert nonfinite is None or (nonfinite.device == dev and nonfinite.dtype == torch.int32 and nonfinite.numel() >= 1)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in tiles])
+    tabs = (_int_table(plan.y0, plan.rows, "y0"), _int_table(plan.x0, plan.cols, "x0"),
+            _int_table(plan.yb, plan.rows + 1, "yb"), _int_table(plan.xb, plan.cols + 1, "xb"))
+    flag = _vp(nonfinite.data_ptr() if nonfinite is not None else 0)
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if out_depth == 8:
+            _lib.check(lib.spei_tiles_u8_out(ptrs, _vp(out.data_ptr()), flag, h, w, *tabs, plan.rows, plan.cols, thp, twp, st),
+                       "spei_tiles_u8_out")
+        else:
+            _lib.check(lib.spei_tiles_u16_out(ptrs, _vp(out.data_ptr()), flag, h, w, *tabs, plan.rows, plan.cols, thp, twp, out_depth, st),
+                       "spei_tiles_u16_out")
+    return out
+
+
 def yuv_frame_bytes(h: int, w: int, layout: int) -> int:
     """Bytes of one planar YUV frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0, [h][w] each for 4:4:4."""
     return y4m.frame_bytes(h, w, layout)

@@ -4,7 +4,7 @@
     python -m speinet_amd.video --input <dir | glob | clip.y4m | -> --output <dir | out.y4m | -> --model_path <checkpoint | synthetic>
                                 [--labels <file.npy>] [--detector <detector.json>] [--cuts none|auto|<file>]
                                 [--matrix bt601|bt709] [--range full|limited] [--fps num:den] [--chroma 420jpeg|420mpeg2|444]
-                                [--out_depth 8|10|12]
+                                [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N]
 
 (`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; stdin is spooled to a temporary file
 on disk before the first frame is deblurred, see `main`)
@@ -27,6 +27,10 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     8 bits: its bytes cross PCIe through the same page-locked rings, the labelling pass, the scene statistics and the window loop
     read uint16 frames (`ops.frames_u16_in`, `ops.frame_pair_stats_u16`), and the deblurred frame is quantised once, to `out_depth`
     (`ops.frame_u16_out`).  Image files stay 8-bit.
+  * a large frame can be deblurred as a grid of overlapping tiles (`tiles=`, `--tiles`; speinet_amd.tiles, csrc/tile_io.hip): what the
+    reference's `forward_chop` does with four quadrants.  The frames are still uploaded, labelled and planned whole; every window
+    then runs once per tile, all tiles of one shape (one set of captured graphs, one encoder cache with keys per tile), and one
+    launch stitches the tiles' bands into the frame with hard seams, no blending.  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -48,7 +52,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import detector, engine, ops, selection, y4m
+from . import detector, engine, ops, selection, tiles as tiling, y4m
 from .speinet import EncoderCache
 
 ZERO = ("zero",)                 # window key of a zeroed reference frame
@@ -422,11 +426,13 @@ class ClipRun:
     access when the caller gave none), `cuts` (the scene cuts in use; found on first access when the caller asked for "auto", in the
     labelling pass when that runs too) and `plan` (`window_plan(labels, numbers=numbers, cuts=cuts)`) describe what runs; `recomputed` lists the
     frames that were recomputed in bf16x3 because their 16-bit pass left a non-finite value; `seconds[k]` is window k's host time
-    [assembling its input, enqueueing it] (the wait for a free launch slot excluded)."""
+    [assembling its input, enqueueing it] (the wait for a free launch slot excluded).  `tiles` is the `tiles.TilePlan` of a clip that is
+    deblurred tile by tile, None for one that is deblurred whole (a plan of one tile included)."""
 
     def __init__(self, model, frames: _Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
-                 out_depth: Optional[int] = None):
+                 out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None):
         self.model, self.frames = model, frames
+        self.tiles = tiles               # the tile plan of a clip that is deblurred tile by tile (more than one tile), or None
         self.depth = frames.depth
         self.out_depth = frames.depth if out_depth is None else out_depth
         self.detector = detector.DEFAULT if detector_params is None else detector_params
@@ -487,13 +493,15 @@ class ClipRun:
     def _run(self):
         m, dev, fr = self.model, self.device, self.frames
         T, H, W = fr.T, fr.H, fr.W
-        Hp, Wp = padded_size(H), padded_size(W)
+        tp = self.tiles
+        nt = 1 if tp is None else tp.n                 # tiles per frame: each is a window of its own, all of one shape
+        Hp, Wp = (padded_size(H), padded_size(W)) if tp is None else tp.padded
         plan = self.plan
         n = m.n_sequence
         pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
         # frames (uint8, or uint16 for a deep clip), decoded and uploaded once each; a y4m clip's as planar bytes, made RGB on the device
         cache = FrameCache(pool, fr.host, dev, convert=None if fr.yuv is None else (lambda planar: fr.rgb(planar)[0]))
-        enc = EncoderCache()
+        enc = EncoderCache() if tp is None else EncoderCache(EncoderCache().capacity * nt)
         inflight, ready = collections.deque(), collections.deque()
         # the stream current at the first `next` assembles the inputs; the windows run on the lanes; a frame handed out is ordered
         # before later work on whatever stream is current at that `next`
@@ -506,28 +514,38 @@ class ClipRun:
         depth, out_depth = self.depth, self.out_depth
         out_dtype = torch.uint8 if out_depth == 8 else torch.uint16
 
-        def ingest(f, dst):
-            return ops.frames_u8_in(f, out=dst) if depth == 8 else ops.frames_u16_in(f, depth, out=dst)
+        def ingest(f, x, j):
+            """Frame f as frame j of the window's input: of its one sample, or of every tile's in one launch."""
+            if tp is not None:
+                return ops.tiles_in(f, tp, x[:, j], None if depth == 8 else depth)
+            return ops.frames_u8_in(f, out=x[0, j]) if depth == 8 else ops.frames_u16_in(f, depth, out=x[0, j])
 
         def egress(y, dst, flag):
+            """The model's output [nt, 3, Hp, Wp] (or a list of nt planes) as the frame: the crop, or the tiles' bands stitched."""
+            if tp is not None:
+                return ops.tiles_out(y, tp, out_depth, out=dst, nonfinite=flag)
             if out_depth == 8:
-                return ops.frame_u8_out(y, H, W, out=dst, nonfinite=flag)
-            return ops.frame_u16_out(y, H, W, out_depth, out=dst, nonfinite=flag)
+                return ops.frame_u8_out(y[0], H, W, out=dst, nonfinite=flag)
+            return ops.frame_u16_out(y[0], H, W, out_depth, out=dst, nonfinite=flag)
+
+        def tile_keys(keys, t):
+            """The `forward_window` keys of tile t: equal pixels per (tile, frame)."""
+            return [(t, key) for key in keys]
 
         def frame(i):
             return fr.device(i).to(dev).contiguous() if fr.on_device(i) else cache.get_dev(i)
 
         def prepare(k):
-            """Window k's input [1, n + 2, 3, Hp, Wp] on the home stream."""
+            """Window k's input [nt, n + 2, 3, Hp, Wp] on the home stream (nt = 1 without tiles)."""
             t0 = time.time()
             for ahead in plan[k:k + 1 + PREFETCH]:
                 cache.request([i for i in ahead["keys"] if i is not ZERO and not fr.on_device(i)])
-            x = torch.empty(1, n + 2, 3, Hp, Wp, device=dev)
+            x = torch.empty(nt, n + 2, 3, Hp, Wp, device=dev)
             for j, key in enumerate(plan[k]["keys"]):
                 if key is ZERO:
-                    x[0, j].zero_()
+                    x[:, j].zero_()
                 else:
-                    ingest(frame(key), x[0, j])
+                    ingest(frame(key), x, j)
             self.seconds.append([time.time() - t0, 0.0])
             return x
 
@@ -546,9 +564,17 @@ class ClipRun:
                 dst.record_stream(lane)
                 if nxt is not None:
                     nxt.record_stream(lane)
-                    m.prefetch_window(nxt, plan[k + 1]["keys"], enc, zero_ref=plan[k + 1]["zero_pre"])
-                y = m.forward_window(x, w["keys"], enc, zero_ref=w["zero_pre"])
-                egress(y[0], dst, flags[slot:slot + 1])
+                if tp is None:
+                    if nxt is not None:
+                        m.prefetch_window(nxt, plan[k + 1]["keys"], enc, zero_ref=plan[k + 1]["zero_pre"])
+                    y = m.forward_window(x, w["keys"], enc, zero_ref=w["zero_pre"])
+                else:                                      # every tile is a window of its own; one shape, so one set of graphs
+                    y = []
+                    for t in range(nt):
+                        if nxt is not None:
+                            m.prefetch_window(nxt[t:t + 1], tile_keys(plan[k + 1]["keys"], t), enc, zero_ref=plan[k + 1]["zero_pre"])
+                        y.append(m.forward_window(x[t:t + 1], tile_keys(w["keys"], t), enc, zero_ref=w["zero_pre"])[0])
+                egress(y, dst, flags[slot:slot + 1])
                 flags_host[slot:slot + 1].copy_(flags[slot:slot + 1], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
@@ -562,11 +588,11 @@ class ClipRun:
             keep = (m.precision, m.corr_precision, m.use_graph)
             m.precision, m.corr_precision, m.use_graph = "bf16x3", "bf16x3", False
             try:
-                y = m(x, routing=[plan[k]["zero_pre"]])
+                y = [m(x[t:t + 1], routing=[plan[k]["zero_pre"]])[0] for t in range(nt)]      # every tile of the window
             finally:
                 m.precision, m.corr_precision, m.use_graph = keep
             slot = k % FLAG_RING
-            egress(y[0], dst, flags[slot:slot + 1])
+            egress(y, dst, flags[slot:slot + 1])
             if int(flags[slot].item()):
                 raise FloatingPointError(f"non-finite values in deblurred frame {k} in bf16x3 arithmetic as well: the input or the "
                                          "checkpoint is at fault")
@@ -614,7 +640,7 @@ class ClipRun:
 
 def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
                 detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None,
-                depth: Optional[int] = None, out_depth: Optional[int] = None) -> ClipRun:
+                depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20) -> ClipRun:
     """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
     or uint16 frames when `out_depth` is 10 or 12.
 
@@ -648,6 +674,14 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              output; None: the input's depth.  An 8-bit clip with `out_depth=10` is allowed and useful: the model's output carries
              more than 8 bits.
 
+    tiles  — None (the default): every frame is deblurred whole.  (rows, cols), 1..8 each, or "auto": the frame is cut into a grid
+             of overlapping tiles of one shape (`tiles.tile_plan`), every tile is deblurred as a clip of its own and the tiles' bands
+             are stitched with hard seams, as the reference's `forward_chop` does for 2x2 (no blending).  "auto" leaves a frame of
+             at most 960000 pixels whole and otherwise takes the fewest tiles of at most that many pixels.  A tile's result differs
+             from the whole frame's there: its correlation and attention see the tile only.  Labels, scene cuts and the window plan
+             are still those of the whole frames.  `ClipRun.tiles` holds the plan in use (None for one tile).
+    shave  — 0..200: the margin in pixels a tile keeps around the band it owns (the reference's 20).
+
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
@@ -675,7 +709,10 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     if cut_params is not None and set(cut_params) - {"hist_min", "ratio", "min_delta", "window"}:
         raise ValueError(f"cut_params holds {sorted(set(cut_params) - {'hist_min', 'ratio', 'min_delta', 'window'})}: "
                          "find_cuts takes hist_min, ratio, min_delta and window")
-    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth)
+    tp = None if tiles is None else tiling.tile_plan(fr.H, fr.W, tuple(tiles) if isinstance(tiles, list) else tiles, shave)
+    if tp is not None and tp.n == 1:
+        tp = None                        # one tile that spans the frame: the untiled path
+    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp)
 
 
 def _inputs(spec: str) -> list:
@@ -763,8 +800,16 @@ def main(argv=None) -> None:
                    "12-bit 4:2:0 y4m input, whose tag carries none (default 420mpeg2: co-sited with the even column)")
     p.add_argument("--out_depth", type=int, choices=y4m.DEPTHS, default=None, help="bits per sample of the output (default: the "
                    "input's for y4m output; a PNG directory always gets 8-bit files)")
+    p.add_argument("--tiles", default="none", help="deblur every frame as a grid of overlapping tiles, stitched with hard seams: 'none' "
+                   "(the default: whole frames), 'auto' (whole up to 960000 pixels, else the fewest tiles of at most that many) or RxC "
+                   "(rows x columns, 1..8 each, such as 2x2: the reference's forward_chop)")
+    p.add_argument("--shave", type=int, default=20, help="pixels of margin a tile keeps around the band it owns (default 20, 0..200)")
     p.add_argument("--spool_dir", default=None, help="directory of the temporary file that '--input -' is copied to (default: the system's)")
     a = p.parse_args(argv)
+    try:
+        tiles = tiling.parse_tiles(a.tiles)
+    except ValueError as e:
+        raise SystemExit(f"--tiles: {e}")
     to_stdout = a.output == "-"
     to_y4m = to_stdout or a.output.lower().endswith(".y4m")
     log = sys.stderr if to_stdout else sys.stdout
@@ -803,7 +848,7 @@ def main(argv=None) -> None:
             say(f"# {reader.depth}-bit input, PNG output: the frames are written with 8 bits per sample (out_depth 8)")
         out_depth = 8
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
-                      yuv=yuv or None, out_depth=out_depth)
+                      yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave)
     out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
@@ -820,6 +865,8 @@ def main(argv=None) -> None:
         os.makedirs(a.output, exist_ok=True)
     for c in run.cuts:
         say(f"# cut before {names[c]}")
+    if run.tiles is not None:
+        say(f"# {run.tiles.rows}x{run.tiles.cols} tiles of {run.tiles.tw}x{run.tiles.th}, shave {run.tiles.shave}")
     t0 = t_prev = time.time()
     # PNGs are encoded on four threads; a y4m stream is written by ONE, so its frames land in the order they were queued
     with ThreadPoolExecutor(max_workers=1 if to_y4m else 4, thread_name_prefix="speinet-y4m" if to_y4m else "speinet-png") as writers:
