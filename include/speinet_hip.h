@@ -533,7 +533,29 @@ int spei_frame_pair_stats_u16(const uint16_t* src, int64_t frame_stride, const u
  *   [H][W][3]: pixel (y, x) of band (i, j) is spei_frame_u8_out's value of tile[i * cols + j][c][y - y0[i]][x - x0[j]].  nonfinite
  *   (or NULL): one int, cleared on the stream, then nonzero iff a pixel of a band (an OWNED pixel) was a NaN or an infinity; what
  *   a tile holds outside its band is never read.  One launch.
- * spei_tiles_u16_out: the same with spei_frame_u16_out's values for `depth` 10 or 12, dst packed uint16. */
+ * spei_tiles_u16_out: the same with spei_frame_u16_out's values for `depth` 10 or 12, dst packed uint16.
+ * spei_tiles_u8_blend / spei_tiles_u16_blend: spei_tiles_u8_out / spei_tiles_u16_out with FEATHERED seams: the margins that two
+ *   neighbouring tiles compute past their seam are blended over a ramp instead of being thrown away.  th, tw: the tile's real size
+ *   (thp, twp must be th, tw rounded up to multiples of 20; th <= H, tw <= W); feather 0..200.  Per axis of n pixels, r tiles of real
+ *   length t, origins o[0..r), band bounds b[0..r], the inner seam s = 1..r-1 lies at b[s] between tile s-1 and tile s, with the
+ *   half-width
+ *     f_s = max(0, min(feather, b[s] - o[s], o[s-1] + t - b[s],
+ *                      (b[s] - b[s-1]) / 2 where s > 1, else b[1] - b[0],
+ *                      (b[s+1] - b[s]) / 2 where s < r-1, else b[r] - b[r-1]))                         (integer division)
+ *   (and b[s] - o[s-1], o[s] + t - b[s], which bind only in a table whose origins do not increase), so the ramp
+ *   [b[s] - f_s, b[s] + f_s) lies on real pixels of both tiles, never on their reflect pad, and inside the two bands next to the
+ *   seam: a band with seams on both sides gives each at most half of itself, a band at the frame's edge all of itself, so the ramps
+ *   of an axis never overlap and none leaves the frame.  For every plan of tiles.tile_plan,
+ *   f_s == feather whenever feather <= shave.  f_s == 0 is a hard seam.  A pixel p of the ramp of seam s has the low tile s-1, the
+ *   high tile s and the weight
+ *     w = fl32(fl32(2 * (p - b[s] + f_s) + 1) * fl32(1 / (4 f_s)))      (the reciprocal rounded once from double, on the host)
+ *   which runs from 1 / (4 f) to (4 f - 1) / (4 f), symmetric about the seam, never 0 or 1.  In two dimensions the blend is
+ *   separable: with a, b, c, d the values of the tiles (low row, low column), (low row, high column), (high row, low column), (high
+ *   row, high column) at the pixel, v = lerp(lerp(a, b, wx), lerp(c, d, wx), wy) in float32 with lerp(lo, hi, w) = fma(w, hi - lo, lo),
+ *   and the sample is spei_frame_u8_out's (u16_out's) value of v.  Outside a row ramp only a, b contribute, outside a column ramp
+ *   only a, c; a pixel outside every ramp has the band's owner alone and is bit-identical to spei_tiles_u8_out's.  At most four
+ *   tiles contribute to a pixel.  nonfinite: nonzero iff a CONTRIBUTING value of some pixel was a NaN or an infinity, and that pixel
+ *   is 0; what no pixel reads (the rest of the margins, the reflect pad) may hold anything.  One launch. */
 int spei_tiles_u8_in(const unsigned char* src, int H, int W, float* dst, int64_t tile_stride, const int* y0_host, const int* x0_host,
                      int rows, int cols, int th, int tw, spei_stream_t stream);
 int spei_tiles_u16_in(const uint16_t* src, int H, int W, float* dst, int64_t tile_stride, const int* y0_host, const int* x0_host,
@@ -544,6 +566,12 @@ int spei_tiles_u8_out(const float* const* tiles_host, unsigned char* dst, int* n
 int spei_tiles_u16_out(const float* const* tiles_host, uint16_t* dst, int* nonfinite, int H, int W, const int* y0_host,
                        const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp, int depth,
                        spei_stream_t stream);
+int spei_tiles_u8_blend(const float* const* tiles_host, unsigned char* dst, int* nonfinite, int H, int W, const int* y0_host,
+                        const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp, int th, int tw,
+                        int feather, spei_stream_t stream);
+int spei_tiles_u16_blend(const float* const* tiles_host, uint16_t* dst, int* nonfinite, int H, int W, const int* y0_host,
+                         const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp, int th, int tw,
+                         int feather, int depth, spei_stream_t stream);
 
 /* ---- planar YUV frames of the clip API (speinet_amd/y4m.py, speinet_amd/video.py; an extension beyond the reference) ---- */
 

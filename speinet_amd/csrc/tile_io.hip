@@ -8,6 +8,9 @@
 //   spei_tiles_u8_out / spei_tiles_u16_out — rows * cols fp32 [3][thp][twp] tiles -> one packed [H][W][3] frame: pixel (y, x) of band
 //                        [yb[i], yb[i+1]) x [xb[j], xb[j+1]) comes from tile (i, j) with spei_frame_u8_out / spei_frame_u16_out's
 //                        rounding; the flag is set by OWNED pixels only, a tile's margin is never read.  One launch per frame.
+//   spei_tiles_u8_blend / spei_tiles_u16_blend — the same with feathered seams (the definition is in include/speinet_hip.h): around
+//                        every inner seam a ramp of up to 2 * feather pixels blends the two tiles that computed it, four where a row
+//                        and a column ramp cross; every other pixel is the hard stitch's, bit for bit.  One launch per frame.
 //
 // The tables (at most 8 origins and 9 band bounds per axis, 64 tile pointers) are read from host memory at call time and travel to the
 // kernel by value, in its arguments.  Streaming kernels in the style of frame_io.hip: one thread per group of 4 pixels of a row, 12
@@ -158,6 +161,218 @@ __global__ __launch_bounds__(256) void tiles_out_kernel(OutTab tab, T* __restric
     if (nonfinite && bad) atomicOr(nonfinite, 1);           // rare: one atomic per thread that met a non-finite value
 }
 
+// ---- feathered seams ------------------------------------------------------------------------------------------------------------------
+constexpr int FEATHER_MAX = 200;
+
+// OutTab and, per axis, the half-width f[s] of the ramp of inner seam s = 1 .. n-1 (0: a hard seam) and r[s] = (float)(1 / (4 f[s]))
+struct BlendTab {
+    OutTab t;
+    int fy[GRID_MAX], fx[GRID_MAX];
+    float ry[GRID_MAX], rx[GRID_MAX];
+    // for the one test that sends a group to the ramp code: the ramps' starts b[s] - f[s], and their widths 2 f[s], the columns' plus
+    // 3 for the group's own width; a width of 0 (a hard seam, no seam) matches nothing
+    int ylo[GRID_MAX], yw[GRID_MAX], xlo[GRID_MAX], xw[GRID_MAX];
+};
+
+// does [p, p + ext] meet a ramp?  w[s] = 2 f[s] + ext, or 0.  Seven compares against wave-uniform operands, joined as lane masks
+__device__ __forceinline__ bool meets_ramp(const int (&lo)[GRID_MAX], const int (&w)[GRID_MAX], int p_ext) {
+    bool r = false;
+#pragma unroll
+    for (int s = 1; s < GRID_MAX; ++s) r |= (unsigned)(p_ext - lo[s]) < (unsigned)w[s];
+    return r;
+}
+
+// the seam whose ramp [b[s] - f[s], b[s] + f[s]) holds coordinate p of band i, or 0: the ramps of an axis do not overlap
+__device__ __forceinline__ int ramp_of(const int (&b)[GRID_MAX + 1], const int (&f)[GRID_MAX], int n, int i, int p) {
+    if (i >= 1 && p < b[i] + f[i]) return i;
+    if (i + 1 < n && p >= b[i + 1] - f[i + 1]) return i + 1;
+    return 0;
+}
+
+// the weight of the high tile at coordinate p of the ramp of seam s: (2 (p - b[s] + f) + 1) / (4 f) with one float32 multiply
+__device__ __forceinline__ float ramp_weight(int p, int b, int f, float r) { return (float)(2 * (p - b + f) + 1) * r; }
+
+// tiles_out_kernel with ramps.  A group of four pixels whose row and columns meet no ramp (one test on wave-uniform operands, no table
+// lookups: 94 % of the groups at 2160p 2x5) runs tiles_out_kernel's body and gives its values.  Of the others, a group
+// that lies in one ramp and is aligned in both of its tiles (every ramp group of a plan whose seams and origins are multiples of 4, as
+// at 1080p and 2160p) loads 16 bytes per plane from each contributing tile; only a ramp's odd ends go pixel by pixel.  Rows are
+// uniform over (nearly) a wave, so a row ramp adds its loads to whole waves and a column ramp only to the groups it crosses.
+template <typename T>
+__global__ __launch_bounds__(256) void tiles_blend_kernel(BlendTab tab, T* __restrict__ dst, int* __restrict__ nonfinite, int W, int rows,
+                                                          int cols, int twp, int64_t plane, int gw, int64_t total, int vec_out, float Df) {
+    int bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int y = (int)(i / gw), x = (int)(i - (int64_t)y * gw) * 4;
+        const int bi = band_of(tab.t.yb, rows, y), bj = band_of(tab.t.xb, cols, x);
+        uint32_t q[3][4];
+        if (!meets_ramp(tab.ylo, tab.yw, y) && !meets_ramp(tab.xlo, tab.xw, x + 3)) {
+            // the row in no row ramp, the four pixels in no column ramp: tiles_out_kernel's body, word for word
+            const int ry = y - tab.t.y0[bi];
+            const float* t = tab.t.tile[bi * cols + bj];
+            const int rx = x - tab.t.x0[bj];
+            if (x + 4 <= W && band_of(tab.t.xb, cols, x + 3) == bj && (rx & 3) == 0 && ((uintptr_t)t & 15) == 0) {
+                const float* s = t + (int64_t)ry * twp + rx;   // four owned pixels of one tile, 16-byte aligned there (twp % 4 == 0)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float4 f = *reinterpret_cast<const float4*>(s + c * plane);
+                    const float e[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        q[c][k] = quantise(e[k], Df);
+                        bad |= isfinite(e[k]) ? 0 : 1;
+                    }
+                }
+            } else {                                       // a hard seam inside the group, an odd tile column or the frame's right edge
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int xx = x + k;
+                    const int j = band_of(tab.t.xb, cols, xx); // xx >= W: the last band, never read
+                    const float* s = tab.t.tile[bi * cols + j] + (int64_t)ry * twp + (xx - tab.t.x0[j]);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float v = xx < W ? s[c * plane] : 0.0f;
+                        q[c][k] = quantise(v, Df);
+                        bad |= isfinite(v) ? 0 : 1;
+                    }
+                }
+            }
+        } else {
+            const int sy = ramp_of(tab.t.yb, tab.fy, rows, bi, y);
+            const int ilo = sy ? sy - 1 : bi, ihi = sy ? sy : bi;                  // the low and the high tile row (one row outside a ramp)
+            const float wy = sy ? ramp_weight(y, tab.t.yb[sy], tab.fy[sy], tab.ry[sy]) : 0.0f;
+            const int64_t olo = (int64_t)(y - tab.t.y0[ilo]) * twp, ohi = (int64_t)(y - tab.t.y0[ihi]) * twp;
+            // the group as a whole: pixels x and x + 3 in one ramp, or in one band and in no ramp, say the same of the two between them
+            // (a ramp is an interval, and a band's ramps are its two ends)
+            const int j3 = band_of(tab.t.xb, cols, x + 3);
+            const int gx = ramp_of(tab.t.xb, tab.fx, cols, bj, x);
+            const int glo = gx ? gx - 1 : bj, ghi = gx ? gx : bj;                      // the low and the high tile column
+            const int glc = x - tab.t.x0[glo], ghc = x - tab.t.x0[ghi];
+            const float* ga = tab.t.tile[ilo * cols + glo];
+            const float* gb = tab.t.tile[ilo * cols + ghi];
+            const float* gc = tab.t.tile[ihi * cols + glo];
+            const float* gd = tab.t.tile[ihi * cols + ghi];
+            if (x + 4 <= W && gx == ramp_of(tab.t.xb, tab.fx, cols, j3, x + 3) && (gx || j3 == bj) && ((glc | ghc) & 3) == 0 &&
+                (((uintptr_t)ga | (uintptr_t)gb | (uintptr_t)gc | (uintptr_t)gd) & 15) == 0) {
+                // four pixels with the same tiles, 16-byte aligned in each.  No ramp: tiles_out_kernel's loads and values.  A ramp: one
+                // 16-byte load per plane and contributing tile, all of a plane's in flight before the first is used
+                float wx[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) wx[k] = gx ? ramp_weight(x + k, tab.t.xb[gx], tab.fx[gx], tab.rx[gx]) : 0.0f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float4 fa = *reinterpret_cast<const float4*>(ga + olo + glc + c * plane);
+                    float4 fb = fa, fc = fa, fd = fa;
+                    if (gx) fb = *reinterpret_cast<const float4*>(gb + olo + ghc + c * plane);
+                    if (sy) {
+                        fc = *reinterpret_cast<const float4*>(gc + ohi + glc + c * plane);
+                        fd = fc;
+                        if (gx) fd = *reinterpret_cast<const float4*>(gd + ohi + ghc + c * plane);
+                    }
+                    const float ea[4] = {fa.x, fa.y, fa.z, fa.w}, eb[4] = {fb.x, fb.y, fb.z, fb.w};
+                    const float ec[4] = {fc.x, fc.y, fc.z, fc.w}, ed[4] = {fd.x, fd.y, fd.z, fd.w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        float v = ea[k];
+                        bool fin = isfinite(v);
+                        if (gx) {
+                            fin = fin && isfinite(eb[k]);
+                            v = fmaf(wx[k], eb[k] - v, v);
+                        }
+                        if (sy) {
+                            float u = ec[k];
+                            fin = fin && isfinite(u);
+                            if (gx) {
+                                fin = fin && isfinite(ed[k]);
+                                u = fmaf(wx[k], ed[k] - u, u);
+                            }
+                            v = fmaf(wy, u - v, v);
+                        }
+                        q[c][k] = fin ? quantise(v, Df) : 0u;  // 0 if any contributing value is not finite
+                        bad |= fin ? 0 : 1;
+                    }
+                }
+            } else {                                       // a ramp's end or a seam inside the group, an odd tile column or the right edge
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int xx = x + k;
+                    const int j = band_of(tab.t.xb, cols, xx);                         // xx >= W: the last band, never read
+                    const int sx = xx < W ? ramp_of(tab.t.xb, tab.fx, cols, j, xx) : 0;
+                    const int jlo = sx ? sx - 1 : j, jhi = sx ? sx : j;
+                    const float wx = sx ? ramp_weight(xx, tab.t.xb[sx], tab.fx[sx], tab.rx[sx]) : 0.0f;
+                    const int clo = xx - tab.t.x0[jlo], chi = xx - tab.t.x0[jhi];
+                    const float* pa = tab.t.tile[ilo * cols + jlo] + olo + clo;    // (low row, low column): the owner outside every ramp
+                    const float* pb = tab.t.tile[ilo * cols + jhi] + olo + chi;
+                    const float* pc = tab.t.tile[ihi * cols + jlo] + ohi + clo;
+                    const float* pd = tab.t.tile[ihi * cols + jhi] + ohi + chi;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        float v = 0.0f;
+                        bool fin = true;
+                        if (xx < W) {
+                            v = pa[c * plane];
+                            fin = isfinite(v);
+                            if (sx) {
+                                const float b = pb[c * plane];
+                                fin = fin && isfinite(b);
+                                v = fmaf(wx, b - v, v);
+                            }
+                            if (sy) {
+                                float u = pc[c * plane];
+                                fin = fin && isfinite(u);
+                                if (sx) {
+                                    const float d = pd[c * plane];
+                                    fin = fin && isfinite(d);
+                                    u = fmaf(wx, d - u, u);
+                                }
+                                v = fmaf(wy, u - v, v);
+                            }
+                        }
+                        q[c][k] = fin ? quantise(v, Df) : 0u;  // 0 if any contributing value is not finite
+                        bad |= fin ? 0 : 1;
+                    }
+                }
+            }
+        }
+        T* d = dst + ((int64_t)y * W + x) * 3;
+        if (vec_out && x + 4 <= W) {                       // 12 samples as three dwords (three 8-byte words)
+            if constexpr (sizeof(T) == 1) {
+                uint32_t w[3] = {0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 12; ++j) w[j >> 2] |= q[j % 3][j / 3] << (8 * (j & 3));
+                uint32_t* p = reinterpret_cast<uint32_t*>(d);
+                p[0] = w[0]; p[1] = w[1]; p[2] = w[2];
+            } else {
+                uint32_t w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 12; ++j) w[j >> 1] |= q[j % 3][j / 3] << (16 * (j & 1));
+                uint2* p = reinterpret_cast<uint2*>(d);
+                p[0] = make_uint2(w[0], w[1]); p[1] = make_uint2(w[2], w[3]); p[2] = make_uint2(w[4], w[5]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x + k < W)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) d[k * 3 + c] = (T)q[c][k];
+        }
+    }
+    if (nonfinite && bad) atomicOr(nonfinite, 1);           // rare: one atomic per thread that met a non-finite value
+}
+
+// the half-width of inner seam s of an axis of r tiles of real length t (the rule of include/speinet_hip.h)
+inline int seam_half(const int* o, const int* b, int r, int t, int s, int feather) {
+    int f = feather;
+    for (int k = s - 1; k <= s; ++k) {                     // [b - f, b + f) inside the real pixels [o, o + t) of the low and the high tile
+        f = f < b[s] - o[k] ? f : b[s] - o[k];
+        f = f < o[k] + t - b[s] ? f : o[k] + t - b[s];
+    }
+    // the two bands next to the seam: half of one with a seam on its other side as well, all of one at the frame's edge
+    const int below = s > 1 ? (b[s] - b[s - 1]) / 2 : b[s] - b[s - 1], above = s + 1 < r ? (b[s + 1] - b[s]) / 2 : b[s + 1] - b[s];
+    f = f < below ? f : below;
+    f = f < above ? f : above;
+    return f > 0 ? f : 0;
+}
+
 inline int grid_for(int64_t total) { return (int)((total + 255) / 256 < BLOCKS_MAX ? (total + 255) / 256 : BLOCKS_MAX); }
 
 template <typename T>
@@ -242,7 +457,87 @@ int tiles_out(const char* name, const float* const* tiles, T* dst, int* nonfinit
     return 0;
 }
 
+// tiles_out's checks (stated again: that path stays as it is), then the real tile size and the feather
+template <typename T>
+int tiles_blend(const char* name, const float* const* tiles, T* dst, int* nonfinite, int H, int W, const int* y0, const int* x0,
+                const int* yb, const int* xb, int rows, int cols, int thp, int twp, int th, int tw, int feather, int depth,
+                hipStream_t stream) {
+    SPEI_REQUIRE(tiles && dst && y0 && x0 && yb && xb, "%s: null pointer", name);
+    SPEI_REQUIRE(H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
+    SPEI_REQUIRE(rows >= 1 && rows <= GRID_MAX && cols >= 1 && cols <= GRID_MAX, "%s: a grid of %dx%d tiles (1..%d rows and columns)",
+                 name, rows, cols, GRID_MAX);
+    SPEI_REQUIRE(thp > 0 && twp > 0 && (twp & 3) == 0 && (int64_t)thp * twp < (1ll << 30), "%s: bad tile planes %dx%d (the width a "
+                 "multiple of 4)", name, thp, twp);
+    SPEI_REQUIRE(th > 0 && tw > 0 && th <= H && tw <= W, "%s: a %dx%d tile does not fit a %dx%d frame", name, th, tw, H, W);
+    SPEI_REQUIRE(thp == (th + MULT - 1) / MULT * MULT && twp == (tw + MULT - 1) / MULT * MULT, "%s: tile planes %dx%d are not the %dx%d "
+                 "tile rounded up to multiples of %d", name, thp, twp, th, tw, MULT);
+    SPEI_REQUIRE(feather >= 0 && feather <= FEATHER_MAX, "%s: feather %d (0..%d)", name, feather, FEATHER_MAX);
+    SPEI_REQUIRE(sizeof(T) == 1 || depth == 10 || depth == 12, "%s: unknown depth %d (10 or 12)", name, depth);
+    SPEI_REQUIRE(((uintptr_t)dst & (sizeof(T) - 1)) == 0, "%s: dst must be %d-byte aligned", name, (int)sizeof(T));
+    BlendTab tab = {};
+    SPEI_REQUIRE(yb[0] == 0 && yb[rows] == H && xb[0] == 0 && xb[cols] == W, "%s: the bands must span the %dx%d frame (rows %d..%d, "
+                 "columns %d..%d)", name, H, W, yb[0], yb[rows], xb[0], xb[cols]);
+    for (int i = 0; i < rows; ++i) {
+        SPEI_REQUIRE(yb[i] < yb[i + 1], "%s: row band %d is empty or reversed (%d..%d)", name, i, yb[i], yb[i + 1]);
+        SPEI_REQUIRE(y0[i] >= 0 && y0[i] < H, "%s: tile row %d at y %d lies outside the %dx%d frame", name, i, y0[i], H, W);
+        SPEI_REQUIRE(y0[i] <= yb[i] && yb[i + 1] - y0[i] <= thp, "%s: row band %d (%d..%d) lies outside its tile (%d..%d)", name, i, yb[i],
+                     yb[i + 1], y0[i], y0[i] + thp);
+        tab.t.y0[i] = y0[i];
+    }
+    for (int j = 0; j < cols; ++j) {
+        SPEI_REQUIRE(xb[j] < xb[j + 1], "%s: column band %d is empty or reversed (%d..%d)", name, j, xb[j], xb[j + 1]);
+        SPEI_REQUIRE(x0[j] >= 0 && x0[j] < W, "%s: tile column %d at x %d lies outside the %dx%d frame", name, j, x0[j], H, W);
+        SPEI_REQUIRE(x0[j] <= xb[j] && xb[j + 1] - x0[j] <= twp, "%s: column band %d (%d..%d) lies outside its tile (%d..%d)", name, j,
+                     xb[j], xb[j + 1], x0[j], x0[j] + twp);
+        tab.t.x0[j] = x0[j];
+    }
+    for (int i = 0; i <= rows; ++i) tab.t.yb[i] = yb[i];
+    for (int j = 0; j <= cols; ++j) tab.t.xb[j] = xb[j];
+    for (int k = 0; k < rows * cols; ++k) {
+        SPEI_REQUIRE(tiles[k] && ((uintptr_t)tiles[k] & 3) == 0, "%s: tile %d is a null or misaligned pointer", name, k);
+        tab.t.tile[k] = tiles[k];
+    }
+    // every ramp [b - f, b + f) lies in rows (columns) [0, th) ([0, tw)) of both of its tiles by seam_half's clip
+    for (int s = 1; s < rows; ++s) {
+        tab.fy[s] = seam_half(y0, yb, rows, th, s, feather);
+        tab.ry[s] = tab.fy[s] ? (float)(1.0 / (4.0 * tab.fy[s])) : 0.0f;
+        tab.ylo[s] = yb[s] - tab.fy[s];
+        tab.yw[s] = 2 * tab.fy[s];
+    }
+    for (int s = 1; s < cols; ++s) {
+        tab.fx[s] = seam_half(x0, xb, cols, tw, s, feather);
+        tab.rx[s] = tab.fx[s] ? (float)(1.0 / (4.0 * tab.fx[s])) : 0.0f;
+        tab.xlo[s] = xb[s] - tab.fx[s];
+        tab.xw[s] = tab.fx[s] ? 2 * tab.fx[s] + 3 : 0;     // a group [x, x + 3] meets the ramp iff 0 <= x + 3 - xlo < 2 f + 3
+    }
+    const int gw = (W + 3) / 4;
+    const int vec_out = (W & 3) == 0 && ((uintptr_t)dst & (sizeof(T) == 1 ? 3 : 7)) == 0;
+    const int64_t total = (int64_t)H * gw;
+    if (nonfinite && hipMemsetAsync(nonfinite, 0, sizeof(int), stream) != hipSuccess) {
+        spei_set_error("%s: clearing the non-finite flag failed", name);
+        return -2;
+    }
+    hipLaunchKernelGGL(tiles_blend_kernel<T>, dim3(grid_for(total)), dim3(256), 0, stream, tab, dst, nonfinite, W, rows, cols, twp,
+                       (int64_t)thp * twp, gw, total, vec_out, sizeof(T) == 1 ? 255.0f : (float)((1 << depth) - 1));
+    SPEI_CHECK_LAUNCH(name);
+    return 0;
+}
+
 }  // namespace
+
+extern "C" int spei_tiles_u8_blend(const float* const* tiles_host, unsigned char* dst, int* nonfinite, int H, int W, const int* y0_host,
+                                   const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp,
+                                   int th, int tw, int feather, spei_stream_t stream) {
+    return tiles_blend<unsigned char>("spei_tiles_u8_blend", tiles_host, dst, nonfinite, H, W, y0_host, x0_host, yb_host, xb_host, rows,
+                                      cols, thp, twp, th, tw, feather, 8, (hipStream_t)stream);
+}
+
+extern "C" int spei_tiles_u16_blend(const float* const* tiles_host, uint16_t* dst, int* nonfinite, int H, int W, const int* y0_host,
+                                    const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp,
+                                    int th, int tw, int feather, int depth, spei_stream_t stream) {
+    return tiles_blend<uint16_t>("spei_tiles_u16_blend", tiles_host, dst, nonfinite, H, W, y0_host, x0_host, yb_host, xb_host, rows, cols,
+                                 thp, twp, th, tw, feather, depth, (hipStream_t)stream);
+}
 
 extern "C" int spei_tiles_u8_in(const unsigned char* src, int H, int W, float* dst, int64_t tile_stride, const int* y0_host,
                                 const int* x0_host, int rows, int cols, int th, int tw, spei_stream_t stream) {

@@ -451,10 +451,17 @@ def tiles_out(tiles, plan, out_depth: int = 8, out: Optional[torch.Tensor] = Non
               nonfinite: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The tiles of `plan` (plan.n contiguous fp32 [3,thp,twp] tensors on one device, or one tensor of them; tile k = i * cols + j)
     -> the stitched frame, uint8 [H,W,3] for `out_depth` 8 and uint16 for 10 and 12: pixel (y, x) of band [yb[i], yb[i+1]) x
-    [xb[j], xb[j+1]) has `frame_u8_out` / `frame_u16_out`'s value of tile (i, j) at (y - y0[i], x - x0[j]).  Hard seams, no blending.
+    [xb[j], xb[j+1]) has `frame_u8_out` / `frame_u16_out`'s value of tile (i, j) at (y - y0[i], x - x0[j]).
     `out` (optional): the packed destination.  `nonfinite` (optional): an int32 device tensor whose first element becomes nonzero iff
-    a pixel of a band was a NaN or an infinity; a tile's margin outside its band is never read.  One launch on the current stream
-    (csrc/tile_io.hip), no host sync."""
+    a value that a pixel was made from was a NaN or an infinity (that pixel is 0).  Which pixels are read depends on the plan's
+    `feather` (a missing field means 0):
+      * 0 — hard seams, no blending (`spei_tiles_u8_out` / `spei_tiles_u16_out`): every tile is read in its band only, a tile's
+        margin outside its band never;
+      * > 0 — feathered seams (`spei_tiles_u8_blend` / `spei_tiles_u16_blend`): inside the ramp of `tiles.seam_ramps(plan)` pixels
+        on either side of an inner seam the two tiles of the seam are read and blended (four where a row and a column ramp cross),
+        so a tile is read in its band and in the ramps next to it; the rest of its margin and its reflect pad never.  A pixel
+        outside every ramp is the hard stitch's, bit for bit.
+    One launch on the current stream (csrc/tile_io.hip), no host sync."""
     n = plan.rows * plan.cols
     tiles = list(tiles)
     if len(tiles) != n:
@@ -475,10 +482,20 @@ def tiles_out(tiles, plan, out_depth: int = 8, out: Optional[torch.Tensor] = Non
     tabs = (_int_table(plan.y0, plan.rows, "y0"), _int_table(plan.x0, plan.cols, "x0"),
             _int_table(plan.yb, plan.rows + 1, "yb"), _int_table(plan.xb, plan.cols + 1, "xb"))
     flag = _vp(nonfinite.data_ptr() if nonfinite is not None else 0)
+    feather = getattr(plan, "feather", 0)
+    if isinstance(feather, bool) or not isinstance(feather, int) or feather < 0:
+        raise ValueError(f"the tile plan's feather must be a whole number >= 0, got {feather!r}")
     lib = _lib.lib()
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if out_depth == 8:
+        if feather > 0:
+            size = (plan.rows, plan.cols, thp, twp, int(plan.th), int(plan.tw), feather)
+            if out_depth == 8:
+                _lib.check(lib.spei_tiles_u8_blend(ptrs, _vp(out.data_ptr()), flag, h, w, *tabs, *size, st), "spei_tiles_u8_blend")
+            else:
+                _lib.check(lib.spei_tiles_u16_blend(ptrs, _vp(out.data_ptr()), flag, h, w, *tabs, *size, out_depth, st),
+                           "spei_tiles_u16_blend")
+        elif out_depth == 8:
             _lib.check(lib.spei_tiles_u8_out(ptrs, _vp(out.data_ptr()), flag, h, w, *tabs, plan.rows, plan.cols, thp, twp, st),
                        "spei_tiles_u8_out")
         else:

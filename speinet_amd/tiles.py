@@ -1,5 +1,6 @@
 """The tile plan of the clip API's large-frame mode (`video.deblur_clip(..., tiles=)`): a frame cut into a grid of overlapping tiles of
-ONE shape, each run through the net on its own, the results stitched with hard seams.  The reference's `forward_chop`
+ONE shape, each run through the net on its own, the results stitched with hard seams (or, with `feather`, blended over a ramp around
+every seam: `seam_ramps`).  The reference's `forward_chop`
 (inference_SPEINet.py:545-607, trainer/trainer_swint_hsa_nsf.py:96) is the 2x2 case: four quadrants that overlap by `shave` = 20
 pixels, seams at h // 2 and w // 2, recursion while a piece has 6 * 160000 pixels or more (`MAX_TILE_PIXELS`).
 
@@ -44,6 +45,7 @@ class TilePlan:
     yb: Tuple[int, ...]
     xb: Tuple[int, ...]
     shave: int = 20
+    feather: int = 0                 # half-width of the blend ramp around every inner seam (0: hard seams); see `seam_ramps`
 
     @property
     def n(self) -> int:
@@ -95,12 +97,17 @@ def _auto(H: int, W: int, shave: int):
     return best[1], best[2]
 
 
-def tile_plan(H: int, W: int, tiles: Union[str, Tuple[int, int]], shave: int = 20) -> TilePlan:
+def tile_plan(H: int, W: int, tiles: Union[str, Tuple[int, int]], shave: int = 20, feather: int = 0) -> TilePlan:
     """The plan for an H x W frame.  `tiles`: (rows, cols), 1..8 each, or "auto": a 1x1 grid for a frame of at most MAX_TILE_PIXELS
     pixels, otherwise the grid of the fewest tiles whose tile has at most that many (ties: the squarer tile, then fewer rows).  `shave`
-    (0..200): the margin a tile keeps around the band it owns.  Raises ValueError with the reason."""
+    (0..200): the margin a tile keeps around the band it owns.  `feather` (0..shave): the half-width of the ramp over which the
+    egress blends the two tiles of a seam (0: hard seams); within the margin every seam gets the whole of it (`seam_ramps`).  Raises
+    ValueError with the reason."""
     if isinstance(shave, bool) or not isinstance(shave, int) or not 0 <= shave <= MAX_SHAVE:
         raise ValueError(f"shave must be a whole number 0..{MAX_SHAVE}, got {shave!r}")
+    if isinstance(feather, bool) or not isinstance(feather, int) or not 0 <= feather <= shave:
+        raise ValueError(f"feather must be a whole number 0..shave ({shave}): the ramp is blended from the margin the tiles keep, "
+                         f"got {feather!r}")
     if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, int) or not isinstance(W, int) or H < 1 or W < 1:
         raise ValueError(f"a frame is H x W pixels, got {H!r} x {W!r}")
     if isinstance(tiles, str):
@@ -117,7 +124,34 @@ def tile_plan(H: int, W: int, tiles: Union[str, Tuple[int, int]], shave: int = 2
                 raise ValueError(f"a tile grid has 1..{MAX_GRID} rows and columns, got {tiles!r}")
     th, y0, yb = axis_plan(H, rows, shave)
     tw, x0, xb = axis_plan(W, cols, shave)
-    return TilePlan(H, W, rows, cols, th, tw, tuple(y0), tuple(x0), tuple(yb), tuple(xb), shave)
+    return TilePlan(H, W, rows, cols, th, tw, tuple(y0), tuple(x0), tuple(yb), tuple(xb), shave, feather)
+
+
+def axis_ramps(o, b, t: int, feather: int) -> Tuple[int, ...]:
+    """The half-widths f_s of the inner seams s = 1 .. r-1 of one axis: origins o[r], band bounds b[r + 1], real tile length t.  The
+    ramp [b[s] - f_s, b[s] + f_s) lies inside the real pixels [o, o + t) of the low tile s-1 and the high tile s (never in a reflect
+    pad) and inside the two bands next to the seam: a band with a seam on both sides gives each at most half of itself, a band at
+    the frame's edge all of itself, so the ramps of an axis never overlap and none leaves the frame:
+        f_s = max(0, min(feather, b[s] - o[s], o[s-1] + t - b[s],
+                         (b[s] - b[s-1]) // 2 where s > 1, else b[1] - b[0];  (b[s+1] - b[s]) // 2 where s < r-1, else b[r] - b[r-1]))
+    (and b[s] - o[s-1], o[s] + t - b[s], which bind only in a hand-made table whose origins do not increase).  0 is a hard seam.  The
+    rule of include/speinet_hip.h, which csrc/tile_io.hip applies to the tables it is given."""
+    r = len(o)
+    out = []
+    for s in range(1, r):
+        f = min(feather, *(v for k in (s - 1, s) for v in (b[s] - o[k], o[k] + t - b[s])))
+        f = min(f, (b[s] - b[s - 1]) // 2 if s > 1 else b[s] - b[s - 1])
+        f = min(f, (b[s + 1] - b[s]) // 2 if s < r - 1 else b[s + 1] - b[s])
+        out.append(max(f, 0))
+    return tuple(out)
+
+
+def seam_ramps(plan) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """(row half-widths [rows - 1], column half-widths [cols - 1]) of the blend ramps of `plan` (a `TilePlan`, or anything with its
+    fields; no `feather` field means 0).  For every plan of `tile_plan` each is `plan.feather`: every band is at least 2 * shave
+    pixels and every inner seam has shave pixels of margin on both sides."""
+    f = int(getattr(plan, "feather", 0))
+    return axis_ramps(plan.y0, plan.yb, plan.th, f), axis_ramps(plan.x0, plan.xb, plan.tw, f)
 
 
 def parse_tiles(text: str) -> Optional[Union[str, Tuple[int, int]]]:

@@ -4,7 +4,7 @@
     python -m speinet_amd.video --input <dir | glob | clip.y4m | -> --output <dir | out.y4m | -> --model_path <checkpoint | synthetic>
                                 [--labels <file.npy>] [--detector <detector.json>] [--cuts none|auto|<file>]
                                 [--matrix bt601|bt709] [--range full|limited] [--fps num:den] [--chroma 420jpeg|420mpeg2|444]
-                                [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N]
+                                [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N]
 
 (`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; stdin is spooled to a temporary file
 on disk before the first frame is deblurred, see `main`)
@@ -30,7 +30,9 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
   * a large frame can be deblurred as a grid of overlapping tiles (`tiles=`, `--tiles`; speinet_amd.tiles, csrc/tile_io.hip): what the
     reference's `forward_chop` does with four quadrants.  The frames are still uploaded, labelled and planned whole; every window
     then runs once per tile, all tiles of one shape (one set of captured graphs, one encoder cache with keys per tile), and one
-    launch stitches the tiles' bands into the frame with hard seams, no blending.  Off by default.
+    launch stitches the tiles' bands into the frame: with hard seams and no blending by default, as the reference does, or
+    (`feather=`, `--feather`) blending the margins that both tiles of a seam computed over a ramp of 2 * feather pixels around it
+    (`tiles.seam_ramps`, `ops.tiles_out`).  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -640,7 +642,7 @@ class ClipRun:
 
 def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
                 detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None,
-                depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20) -> ClipRun:
+                depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20, feather: int = 0) -> ClipRun:
     """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
     or uint16 frames when `out_depth` is 10 or 12.
 
@@ -676,16 +678,23 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
 
     tiles  — None (the default): every frame is deblurred whole.  (rows, cols), 1..8 each, or "auto": the frame is cut into a grid
              of overlapping tiles of one shape (`tiles.tile_plan`), every tile is deblurred as a clip of its own and the tiles' bands
-             are stitched with hard seams, as the reference's `forward_chop` does for 2x2 (no blending).  "auto" leaves a frame of
-             at most 960000 pixels whole and otherwise takes the fewest tiles of at most that many pixels.  A tile's result differs
-             from the whole frame's there: its correlation and attention see the tile only.  Labels, scene cuts and the window plan
-             are still those of the whole frames.  `ClipRun.tiles` holds the plan in use (None for one tile).
+             are stitched with hard seams, as the reference's `forward_chop` does for 2x2 (no blending unless `feather` is set).
+             "auto" leaves a frame of at most 960000 pixels whole and otherwise takes the fewest tiles of at most that many.  A
+             tile's result differs from the whole frame's there: its correlation and attention see the tile only.  Labels, scene
+             cuts and the window plan are still those of the whole frames.  `ClipRun.tiles` holds the plan in use (None for one
+             tile).
     shave  — 0..200: the margin in pixels a tile keeps around the band it owns (the reference's 20).
+    feather — 0..shave, with `tiles` only: 0 (the default) stitches with hard seams.  N > 0 blends the two tiles of every inner seam
+             linearly over the 2 N pixels around it (four tiles where a row and a column ramp cross), from the margins the tiles
+             computed anyway; every pixel further than N from the seams is the hard stitch's, bit for bit.  A non-finite value
+             anywhere a pixel is blended from sends the window to the bf16x3 recompute, as one in a band does.
 
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
     to `ClipRun.recomputed` with a RuntimeWarning, and FloatingPointError is raised if the frame is still not finite."""
+    if tiles is None and not (isinstance(feather, int) and not isinstance(feather, bool) and feather == 0):
+        raise ValueError(f"feather={feather!r} needs tiles=: it blends the seams between tiles, and an untiled frame has none")
     if isinstance(frames, (str, os.PathLike)) and os.fspath(frames).lower().endswith(".y4m"):
         frames = y4m.Y4MReader(frames, depths=y4m.DEPTHS)
     fr = frames_of(frames, crop, yuv, depth)
@@ -709,7 +718,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     if cut_params is not None and set(cut_params) - {"hist_min", "ratio", "min_delta", "window"}:
         raise ValueError(f"cut_params holds {sorted(set(cut_params) - {'hist_min', 'ratio', 'min_delta', 'window'})}: "
                          "find_cuts takes hist_min, ratio, min_delta and window")
-    tp = None if tiles is None else tiling.tile_plan(fr.H, fr.W, tuple(tiles) if isinstance(tiles, list) else tiles, shave)
+    tp = None if tiles is None else tiling.tile_plan(fr.H, fr.W, tuple(tiles) if isinstance(tiles, list) else tiles, shave, feather)
     if tp is not None and tp.n == 1:
         tp = None                        # one tile that spans the frame: the untiled path
     return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp)
@@ -800,16 +809,25 @@ def main(argv=None) -> None:
                    "12-bit 4:2:0 y4m input, whose tag carries none (default 420mpeg2: co-sited with the even column)")
     p.add_argument("--out_depth", type=int, choices=y4m.DEPTHS, default=None, help="bits per sample of the output (default: the "
                    "input's for y4m output; a PNG directory always gets 8-bit files)")
-    p.add_argument("--tiles", default="none", help="deblur every frame as a grid of overlapping tiles, stitched with hard seams: 'none' "
+    p.add_argument("--tiles", default="none", help="deblur every frame as a grid of overlapping tiles, stitched with hard seams (or "
+                   "blended ones: --feather): 'none' "
                    "(the default: whole frames), 'auto' (whole up to 960000 pixels, else the fewest tiles of at most that many) or RxC "
                    "(rows x columns, 1..8 each, such as 2x2: the reference's forward_chop)")
     p.add_argument("--shave", type=int, default=20, help="pixels of margin a tile keeps around the band it owns (default 20, 0..200)")
+    p.add_argument("--feather", type=int, default=0, help="with --tiles: blend the two tiles of every seam over the 2 N pixels around it, "
+                   "from the margins they keep (0..shave; default 0: hard seams)")
     p.add_argument("--spool_dir", default=None, help="directory of the temporary file that '--input -' is copied to (default: the system's)")
     a = p.parse_args(argv)
     try:
         tiles = tiling.parse_tiles(a.tiles)
     except ValueError as e:
         raise SystemExit(f"--tiles: {e}")
+    if a.feather != 0:                                     # refused here, before the model is loaded
+        if tiles is None:
+            raise SystemExit(f"--feather {a.feather}: needs --tiles: it blends the seams between tiles")
+        if not 0 <= a.shave <= tiling.MAX_SHAVE or not 0 <= a.feather <= a.shave:
+            raise SystemExit(f"--feather {a.feather}: must be 0..shave (--shave {a.shave}, itself 0..{tiling.MAX_SHAVE}): the ramp is "
+                             "blended from the margin the tiles keep")
     to_stdout = a.output == "-"
     to_y4m = to_stdout or a.output.lower().endswith(".y4m")
     log = sys.stderr if to_stdout else sys.stdout
@@ -848,7 +866,7 @@ def main(argv=None) -> None:
             say(f"# {reader.depth}-bit input, PNG output: the frames are written with 8 bits per sample (out_depth 8)")
         out_depth = 8
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
-                      yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave)
+                      yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather)
     out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
@@ -866,7 +884,8 @@ def main(argv=None) -> None:
     for c in run.cuts:
         say(f"# cut before {names[c]}")
     if run.tiles is not None:
-        say(f"# {run.tiles.rows}x{run.tiles.cols} tiles of {run.tiles.tw}x{run.tiles.th}, shave {run.tiles.shave}")
+        say(f"# {run.tiles.rows}x{run.tiles.cols} tiles of {run.tiles.tw}x{run.tiles.th}, shave {run.tiles.shave}"
+            + (f", feather {run.tiles.feather}" if run.tiles.feather else ""))
     t0 = t_prev = time.time()
     # PNGs are encoded on four threads; a y4m stream is written by ONE, so its frames land in the order they were queued
     with ThreadPoolExecutor(max_workers=1 if to_y4m else 4, thread_name_prefix="speinet-y4m" if to_y4m else "speinet-png") as writers:
