@@ -275,7 +275,12 @@ int spei_corr_slab16(int fmt, const void* lr_hi, const void* lr_lo, const void* 
  * 16-bit products keeping the TWO best candidates of every query: arg / arg2 (arg2 = -1: no second candidate) with their
  * approximate, un-normalised-by-inv_lr scores S / S2.  spei_corr_rescore then re-scores both candidates on the fp32 maps
  * with fp64 accumulation and overwrites S (= dot * inv_ref[j] * inv_lr[i], fp32) and arg (ties -> lowest index): the
- * winner no longer depends on 16-bit rounding (model/SearchTransfer.py:33-34 computes R in fp32). */
+ * winner no longer depends on 16-bit rounding (model/SearchTransfer.py:33-34 computes R in fp32).
+ * Candidate scores: S / S2 carry a position tag in their low five or six mantissa bits (the score itself is truncated there).
+ * Ties in a candidate pass (both forms): arg and arg2 are always two different positions holding the two best truncated scores, but
+ * which of several positions of EQUAL truncated score is kept, and in which order, is implementation-defined — inside a tile the
+ * tag orders them (a positive score goes to the lower position, a negative one to the higher), across tiles the forms differ.
+ * Only spei_corr_rescore's output follows the lowest-index rule. */
 int spei_corr_slab_top2_16(int fmt, const void* lr16, const void* ref16, const float* inv_lr, const float* inv_ref,
                            int Hl, int Wl, int Hr, int Wr, int C, float* S, int32_t* arg, float* S2, int32_t* arg2,
                            float* ws, spei_stream_t stream);

@@ -161,6 +161,11 @@ __global__ __launch_bounds__(512) void corr_diag_kernel(const CorrDiagParams<LP>
                 lk1 = vmax(lk1, key);
             }
         }
+        // A position right of the reference map has a NaN normaliser and so a NaN key, which v_max and v_med3 pass over.  But the
+        // compiler folds the chain's first med3(lk1, -inf, key) into min(lk1, key), and that returns lk1 for a NaN key: with a valid
+        // first and a NaN second position of a lane (Wr % 64 == 1 or 5) the pair held one position twice, and the query lost its
+        // runner-up when that position won.  Keys of two positions never compare equal (their tags differ), so an equal pair is that.
+        lk2 = lk2 == lk1 ? -INFINITY : lk2;
         auto retag = [&](float k) __attribute__((always_inline)) {
             const unsigned u = __float_as_uint(k);
             const int row = 31 - (int)(u & 31u);
