@@ -578,6 +578,30 @@ int spei_tiles_u16_blend(const float* const* tiles_host, uint16_t* dst, int* non
                          const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp, int th, int tw,
                          int feather, int depth, spei_stream_t stream);
 
+/* ---- geometric self-ensemble of the clip API (speinet_amd/ensemble.py, video.deblur_clip(..., ensemble=); the reference's
+ * forward_x8, util/network_utils.py:308-341, which it never calls) ----
+ * Member `op` in 0..7, the reference's enumeration: bit 0 reverses the columns of a plane (a[:, ::-1], its 'v'), bit 1 reverses the
+ * rows (a[::-1, :], its 'h'), bit 2 transposes.  T_op applies them in that order, so T_op of an [H][W] plane is [W][H] for op & 4:
+ *     T_op(a)[i][j] = a[fy(j)][fx(i)] for op & 4, else a[fy(i)][fx(j)],   fx(p) = op & 1 ? W - 1 - p : p,  fy(p) = op & 2 ? H - 1 - p : p
+ * and T_op^-1 transposes first and then flips.  An ensemble of K in {1, 2, 4, 8} uses the members 0..K-1 (2: the frame and its mirror;
+ * 4: the flips, one frame shape; 8: also the four transposed members).  With m_k = T_k^-1(model(T_k(x))) its result is
+ *     R = fl32((((m_0 + m_1) + m_2) + ... + m_{K-1})) * 2^-log2 K
+ * in float32: a sequential sum that starts from m_0 (not from 0.0) and an exact scale, so R is defined bit for bit wherever it is
+ * finite and is NaN wherever that sum is NaN.
+ * spei_planes_d4: plane p of dst (at dst + p * dst_stride, [H][W], or [W][H] for op & 4) = T_op of plane p of src (at src + p *
+ *   src_stride, [H][W]); strides in floats, each at least H * W.  Values are copied as bits: NaN payloads and -0.0 survive.  Any
+ *   H, W >= 1; 16-byte accesses on both sides where H, W and both strides are multiples of 4 and both bases 16-byte aligned, element
+ *   by element otherwise.  Null pointers, an op outside 0..7, a stride smaller than a plane, and src and dst ranges that overlap
+ *   return non-zero before anything is launched.  One launch, no workspace.
+ * spei_d4_mean: members_host = K device pointers, ops_host = K ops: HOST arrays, read during the call and passed to the kernel by
+ *   value.  Member k is a packed fp32 [C][H][W], or [C][W][H] where ops_host[k] & 4: T_op of its term.  dst packed [C][H][W] = R above
+ *   with m_k = T_{ops_host[k]}^-1(member k), summed in TABLE order; K = 1 is the inverse transform alone, copied as bits.  The same
+ *   alignment split (dst and every member 16-byte aligned).  K outside {1, 2, 4, 8}, an op outside 0..7, a null member and a dst
+ *   that overlaps a member return non-zero before anything is launched.  One launch, no workspace, no atomics. */
+int spei_planes_d4(const float* src, int64_t src_stride, float* dst, int64_t dst_stride, int64_t n_planes, int H, int W, int op,
+                   spei_stream_t stream);
+int spei_d4_mean(const float* const* members_host, const int* ops_host, int K, float* dst, int C, int H, int W, spei_stream_t stream);
+
 /* ---- planar YUV frames of the clip API (speinet_amd/y4m.py, speinet_amd/video.py; an extension beyond the reference) ---- */
 
 #define SPEI_YUV_420_CENTER 0 /* 4:2:0, chroma sample at the centre of its 2x2 block (y4m C420jpeg, and bare C420) */

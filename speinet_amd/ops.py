@@ -504,6 +504,63 @@ def tiles_out(tiles, plan, out_depth: int = 8, out: Optional[torch.Tensor] = Non
     return out
 
 
+def planes_d4(x: torch.Tensor, op: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Member `op` (0..7, speinet_amd/ensemble.py) of every plane of `x`: fp32 [..., H, W] on the device -> `ensemble.apply(x, op)` as a
+    contiguous tensor, [..., W, H] for op & 4, copied as bits.  `x` may be a view whose planes are contiguous and evenly spaced (any
+    leading shape that collapses to one plane stride, such as a contiguous tensor or a slice of its first axis); `out` (optional): a
+    destination of the result's shape with such planes that does not overlap `x`.  One launch on the current stream
+    (csrc/ensemble_io.hip), no host sync."""
+    from . import ensemble
+    op = ensemble.check_op(op)
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2
+    h, w = x.shape[-2:]
+    shape = tuple(x.shape[:-2]) + ensemble.shape_of(h, w, op)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    assert out.device == x.device and out.dtype == torch.float32 and tuple(out.shape) == shape
+    n = x.numel() // (h * w)
+    strides = []
+    for t, (r, c) in ((x, (h, w)), (out, shape[-2:])):
+        flat = t.reshape(n, r, c)
+        if flat.data_ptr() != t.data_ptr() or flat.stride()[1:] != (c, 1):
+            raise ValueError(f"planes_d4 needs contiguous planes at one stride; got shape {tuple(t.shape)} with strides {t.stride()}")
+        strides.append(flat.stride(0) if n > 1 else h * w)
+    lib = _lib.lib()
+    with torch.cuda.device(x.device):
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(lib.spei_planes_d4(_vp(x.data_ptr()), strides[0], _vp(out.data_ptr()), strides[1], n, h, w, op, st), "spei_planes_d4")
+    return out
+
+
+def d4_mean(members, member_ops, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The ensemble mean of K = 1, 2, 4 or 8 members: contiguous fp32 [C, H, W] tensors on one device, [C, W, H] where the member's op
+    (0..7, `member_ops[k]`) transposes; member k is T_op of its term.  Returns `out` [C, H, W] (allocated if None; it must not overlap a
+    member): the float32 sum of `ensemble.invert(members[k], member_ops[k])` in the order given, starting from the first, times
+    1 / K; K = 1 is the inverse transform, copied as bits.  One launch on the current stream (csrc/ensemble_io.hip), no host sync."""
+    from . import ensemble
+    members, member_ops = list(members), [ensemble.check_op(g) for g in member_ops]
+    k = len(members)
+    if k not in ensemble.SIZES or len(member_ops) != k:
+        raise ValueError(f"d4_mean takes 1, 2, 4 or 8 members and one op per member, got {k} members and {len(member_ops)} ops")
+    dev = members[0].device
+    for t in members:
+        assert t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous()
+    c = members[0].shape[0]
+    h, w = ensemble.shape_of(*members[0].shape[1:], member_ops[0])          # a transposition is its own inverse on shapes
+    for t, g in zip(members, member_ops):
+        if tuple(t.shape) != (c,) + ensemble.shape_of(h, w, g):
+            raise ValueError(f"member with op {g} has shape {tuple(t.shape)}, not {(c,) + ensemble.shape_of(h, w, g)}")
+    if out is None:
+        out = torch.empty(c, h, w, dtype=torch.float32, device=dev)
+    assert out.device == dev and out.dtype == torch.float32 and tuple(out.shape) == (c, h, w) and out.is_contiguous()
+    ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in members])
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.spei_d4_mean(ptrs, (C.c_int * k)(*member_ops), k, _vp(out.data_ptr()), c, h, w, st), "spei_d4_mean")
+    return out
+
+
 def yuv_frame_bytes(h: int, w: int, layout: int) -> int:
     """Bytes of one planar YUV frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0, [h][w] each for 4:4:4."""
     return y4m.frame_bytes(h, w, layout)

@@ -4,7 +4,7 @@
     python -m speinet_amd.video --input <dir | glob | clip.y4m | -> --output <dir | out.y4m | -> --model_path <checkpoint | synthetic>
                                 [--labels <file.npy>] [--detector <detector.json>] [--cuts none|auto|<file>]
                                 [--matrix bt601|bt709] [--range full|limited] [--fps num:den] [--chroma 420jpeg|420mpeg2|444]
-                                [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N]
+                                [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N] [--ensemble 1|2|4|8]
 
 (`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; stdin is spooled to a temporary file
 on disk before the first frame is deblurred, see `main`)
@@ -33,6 +33,11 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     launch stitches the tiles' bands into the frame: with hard seams and no blending by default, as the reference does, or
     (`feather=`, `--feather`) blending the margins that both tiles of a seam computed over a ramp of 2 * feather pixels around it
     (`tiles.seam_ramps`, `ops.tiles_out`).  Off by default.
+  * geometric self-ensemble (`ensemble=`, `--ensemble`; speinet_amd.ensemble, csrc/ensemble_io.hip): every window also runs on the
+    mirrored, upside-down and (for 8) transposed copies of its padded input, made on the device by one launch per member
+    (`ops.planes_d4`), and one launch transforms the members' outputs back and averages them in float32 in a fixed order
+    (`ops.d4_mean`) in front of the unchanged egress: what the reference's `forward_x8` does on the host, and never calls.  K members
+    cost K forward passes.  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -54,7 +59,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import detector, engine, ops, selection, tiles as tiling, y4m
+from . import detector, engine, ensemble as ens, ops, selection, tiles as tiling, y4m
 from .speinet import EncoderCache
 
 ZERO = ("zero",)                 # window key of a zeroed reference frame
@@ -429,11 +434,13 @@ class ClipRun:
     labelling pass when that runs too) and `plan` (`window_plan(labels, numbers=numbers, cuts=cuts)`) describe what runs; `recomputed` lists the
     frames that were recomputed in bf16x3 because their 16-bit pass left a non-finite value; `seconds[k]` is window k's host time
     [assembling its input, enqueueing it] (the wait for a free launch slot excluded).  `tiles` is the `tiles.TilePlan` of a clip that is
-    deblurred tile by tile, None for one that is deblurred whole (a plan of one tile included)."""
+    deblurred tile by tile, None for one that is deblurred whole (a plan of one tile included).  `ensemble` is the number of members of
+    the geometric self-ensemble every window runs as (1: none)."""
 
     def __init__(self, model, frames: _Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
-                 out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None):
+                 out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None, ensemble: int = 1):
         self.model, self.frames = model, frames
+        self.ensemble = ens.check_size(ensemble)
         self.tiles = tiles               # the tile plan of a clip that is deblurred tile by tile (more than one tile), or None
         self.depth = frames.depth
         self.out_depth = frames.depth if out_depth is None else out_depth
@@ -503,7 +510,9 @@ class ClipRun:
         pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
         # frames (uint8, or uint16 for a deep clip), decoded and uploaded once each; a y4m clip's as planar bytes, made RGB on the device
         cache = FrameCache(pool, fr.host, dev, convert=None if fr.yuv is None else (lambda planar: fr.rgb(planar)[0]))
-        enc = EncoderCache() if tp is None else EncoderCache(EncoderCache().capacity * nt)
+        K = self.ensemble
+        members = ens.MEMBERS[K]         # every window runs once per member (and tile): K - 1 transformed copies of its input
+        enc = EncoderCache() if nt * K == 1 else EncoderCache(EncoderCache().capacity * nt * K)
         inflight, ready = collections.deque(), collections.deque()
         # the stream current at the first `next` assembles the inputs; the windows run on the lanes; a frame handed out is ordered
         # before later work on whatever stream is current at that `next`
@@ -534,11 +543,20 @@ class ClipRun:
             """The `forward_window` keys of tile t: equal pixels per (tile, frame)."""
             return [(t, key) for key in keys]
 
+        def member_keys(keys, g, t):
+            """The `forward_window` keys of ensemble member g of tile t: equal pixels per (member, tile, frame)."""
+            return [(g, t, key) for key in keys]
+
+        def members_of(x):
+            """The window input of every ensemble member: x itself, and T_g of all its planes for g = 1 .. K-1, one launch each
+            (a zeroed frame stays zero)."""
+            return [x] + [ops.planes_d4(x, g) for g in members[1:]]
+
         def frame(i):
             return fr.device(i).to(dev).contiguous() if fr.on_device(i) else cache.get_dev(i)
 
         def prepare(k):
-            """Window k's input [nt, n + 2, 3, Hp, Wp] on the home stream (nt = 1 without tiles)."""
+            """Window k's input [nt, n + 2, 3, Hp, Wp] on the home stream (nt = 1 without tiles): one per ensemble member."""
             t0 = time.time()
             for ahead in plan[k:k + 1 + PREFETCH]:
                 cache.request([i for i in ahead["keys"] if i is not ZERO and not fr.on_device(i)])
@@ -548,11 +566,13 @@ class ClipRun:
                     x[:, j].zero_()
                 else:
                     ingest(frame(key), x, j)
+            xs = members_of(x)
             self.seconds.append([time.time() - t0, 0.0])
-            return x
+            return xs
 
-        def enqueue(k, x, nxt):
+        def enqueue(k, xs, nxts):
             """Window k on its lane (and window k + 1's encoder passes on the model's prefetch stream)."""
+            x, nxt = xs[0], None if nxts is None else nxts[0]
             if len(inflight) >= max(2, len(lanes)):
                 inflight.popleft().synchronize()           # the host stays at most two windows ahead of the GPU
             t0 = time.time()
@@ -562,11 +582,22 @@ class ClipRun:
             lane.wait_stream(home)                         # the window's input was assembled on the home stream
             slot = k % FLAG_RING
             with torch.cuda.stream(lane):
-                x.record_stream(lane)
+                for v in xs + (nxts or []):
+                    v.record_stream(lane)
                 dst.record_stream(lane)
-                if nxt is not None:
-                    nxt.record_stream(lane)
-                if tp is None:
+                if K > 1:                                  # every member of every tile is a window of its own, one after the other
+                    y = []
+                    for t in range(nt):
+                        outs = []
+                        for g in members:
+                            if nxts is not None:
+                                m.prefetch_window(nxts[g][t:t + 1], member_keys(plan[k + 1]["keys"], g, t), enc,
+                                                  zero_ref=plan[k + 1]["zero_pre"])
+                            outs.append(m.forward_window(xs[g][t:t + 1], member_keys(w["keys"], g, t), enc, zero_ref=w["zero_pre"])[0])
+                        # `forward_window` hands out a copy of its graph's static output, so a member's output outlives the next
+                        # member's replay: one launch turns them back and averages them
+                        y.append(ops.d4_mean(outs, members))
+                elif tp is None:
                     if nxt is not None:
                         m.prefetch_window(nxt, plan[k + 1]["keys"], enc, zero_ref=plan[k + 1]["zero_pre"])
                     y = m.forward_window(x, w["keys"], enc, zero_ref=w["zero_pre"])
@@ -581,16 +612,21 @@ class ClipRun:
                 ev = torch.cuda.Event()
                 ev.record()
             inflight.append(ev)
-            ready.append((k, dst, ev, x))
+            ready.append((k, dst, ev, xs))
             self.seconds[k][1] = time.time() - t0
 
-        def redo(k, x, dst):
+        def redo(k, xs, dst):
             """Window k again in split-bf16 arithmetic (fp32 exponent range), eagerly, on the home stream: a 16-bit pass left a NaN or an
-            infinity in the frame (half operands do not saturate)."""
+            infinity in the frame (half operands do not saturate; one in any ensemble member reaches the mean, and so the flag).  Every
+            member of every tile runs again."""
+            x = xs[0]
             keep = (m.precision, m.corr_precision, m.use_graph)
             m.precision, m.corr_precision, m.use_graph = "bf16x3", "bf16x3", False
             try:
-                y = [m(x[t:t + 1], routing=[plan[k]["zero_pre"]])[0] for t in range(nt)]      # every tile of the window
+                if K > 1:
+                    y = [ops.d4_mean([m(xs[g][t:t + 1], routing=[plan[k]["zero_pre"]])[0] for g in members], members) for t in range(nt)]
+                else:
+                    y = [m(x[t:t + 1], routing=[plan[k]["zero_pre"]])[0] for t in range(nt)]      # every tile of the window
             finally:
                 m.precision, m.corr_precision, m.use_graph = keep
             slot = k % FLAG_RING
@@ -642,7 +678,8 @@ class ClipRun:
 
 def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
                 detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None,
-                depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20, feather: int = 0) -> ClipRun:
+                depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20, feather: int = 0,
+                ensemble: int = 1) -> ClipRun:
     """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
     or uint16 frames when `out_depth` is 10 or 12.
 
@@ -688,11 +725,19 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              linearly over the 2 N pixels around it (four tiles where a row and a column ramp cross), from the margins the tiles
              computed anyway; every pixel further than N from the seams is the hard stitch's, bit for bit.  A non-finite value
              anywhere a pixel is blended from sends the window to the bf16x3 recompute, as one in a band does.
+    ensemble — 1 (the default), 2, 4 or 8: geometric self-ensemble over the members 0..K-1 of `speinet_amd.ensemble` (2: the frame and
+             its mirror; 4: the four flips, one frame shape; 8: also the four transposed members, a second frame shape with its own
+             captured graphs).  Every window runs once per member on the transformed padded input; the outputs are transformed back and
+             averaged in float32 in member order (`ops.d4_mean`) in front of the egress, so it composes with `tiles`, `feather`,
+             `out_depth` and y4m.  K forward passes per frame; labels, scene cuts and the window plan are those of the upright frames.
+             A non-finite value in any member sends the window to the bf16x3 recompute, which runs all K members again.  1 is the
+             path without it, launch for launch.  `ClipRun.ensemble` holds it.
 
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
     to `ClipRun.recomputed` with a RuntimeWarning, and FloatingPointError is raised if the frame is still not finite."""
+    ensemble = ens.check_size(ensemble)                    # in front of everything else: no frame is looked at
     if tiles is None and not (isinstance(feather, int) and not isinstance(feather, bool) and feather == 0):
         raise ValueError(f"feather={feather!r} needs tiles=: it blends the seams between tiles, and an untiled frame has none")
     if isinstance(frames, (str, os.PathLike)) and os.fspath(frames).lower().endswith(".y4m"):
@@ -721,7 +766,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     tp = None if tiles is None else tiling.tile_plan(fr.H, fr.W, tuple(tiles) if isinstance(tiles, list) else tiles, shave, feather)
     if tp is not None and tp.n == 1:
         tp = None                        # one tile that spans the frame: the untiled path
-    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp)
+    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp, ensemble)
 
 
 def _inputs(spec: str) -> list:
@@ -816,6 +861,9 @@ def main(argv=None) -> None:
     p.add_argument("--shave", type=int, default=20, help="pixels of margin a tile keeps around the band it owns (default 20, 0..200)")
     p.add_argument("--feather", type=int, default=0, help="with --tiles: blend the two tiles of every seam over the 2 N pixels around it, "
                    "from the margins they keep (0..shave; default 0: hard seams)")
+    p.add_argument("--ensemble", type=int, choices=ens.SIZES, default=1, help="geometric self-ensemble: run every window on 2 (the frame "
+                   "and its mirror), 4 (the flips) or 8 (flips and transpositions) transformed copies and average the results; K times "
+                   "the work (default 1: off)")
     p.add_argument("--spool_dir", default=None, help="directory of the temporary file that '--input -' is copied to (default: the system's)")
     a = p.parse_args(argv)
     try:
@@ -866,7 +914,7 @@ def main(argv=None) -> None:
             say(f"# {reader.depth}-bit input, PNG output: the frames are written with 8 bits per sample (out_depth 8)")
         out_depth = 8
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
-                      yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather)
+                      yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather, ensemble=a.ensemble)
     out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
@@ -886,6 +934,8 @@ def main(argv=None) -> None:
     if run.tiles is not None:
         say(f"# {run.tiles.rows}x{run.tiles.cols} tiles of {run.tiles.tw}x{run.tiles.th}, shave {run.tiles.shave}"
             + (f", feather {run.tiles.feather}" if run.tiles.feather else ""))
+    if run.ensemble > 1:
+        say(f"# ensemble {run.ensemble}: members 0..{run.ensemble - 1}, {run.ensemble} forward passes per frame")
     t0 = t_prev = time.time()
     # PNGs are encoded on four threads; a y4m stream is written by ONE, so its frames land in the order they were queued
     with ThreadPoolExecutor(max_workers=1 if to_y4m else 4, thread_name_prefix="speinet-y4m" if to_y4m else "speinet-png") as writers:
@@ -907,7 +957,8 @@ def main(argv=None) -> None:
     if writer is not None:
         writer.close()
     dt = time.time() - t0
-    say(f"# {len(names)} frames {W}x{H} in {dt:.2f}s: {len(names) / dt:.2f} frames/s ({a.precision})")
+    say(f"# {len(names)} frames {W}x{H} in {dt:.2f}s: {len(names) / dt:.2f} frames/s ({a.precision}"
+        + (f", ensemble {run.ensemble}" if run.ensemble > 1 else "") + ")")
 
 
 if __name__ == "__main__":
