@@ -602,6 +602,46 @@ int spei_planes_d4(const float* src, int64_t src_stride, float* dst, int64_t dst
                    spei_stream_t stream);
 int spei_d4_mean(const float* const* members_host, const int* ops_host, int K, float* dst, int C, int H, int W, spei_stream_t stream);
 
+/* ---- region of interest of the clip API (video.deblur_clip(..., roi=); an extension beyond the reference) ----
+ * Only the rectangle [y0, y0 + h) x [x0, x0 + w) of every frame is deblurred (ingested by spei_tiles_u8_in / spei_tiles_u16_in with
+ * a 1x1 table at (y0, x0)); the rest of the frame is the input's.  With D = 2^depth - 1,
+ *     requant(v) = (min(v, D_in) * 2 * D_out + D_in) / (2 * D_in)          (integer division: v * D_out / D_in rounded half up)
+ * is the input sample at the output depth, the identity where the depths are equal.
+ * spei_roi_paste_u8: src = the model's fp32 [3][hp][wp], hp / wp = h / w rounded up to multiples of 20 (16-byte aligned); frame = the
+ *   packed input frame [H][W][3] of in_depth 8 (uint8), 10 or 12 (little-endian 16-bit words, 2-byte aligned; a word above D_in reads
+ *   as D_in); dst = the packed uint8 output frame [H][W][3].  ONE launch writes every sample of dst, in a single pass: outside the
+ *   rectangle requant(frame), inside it, with feather == 0, spei_frame_u8_out's value of src[c][y - y0][x - x0]; with y0 = x0 = 0,
+ *   h = H, w = W the result is bit-identical to spei_frame_u8_out's.  nonfinite (or NULL): one int, cleared on the stream, then
+ *   nonzero iff a value of src inside the h x w crop was a NaN or an infinity; that sample is 0.  What src holds in its pad is never
+ *   read.
+ *   feather = N > 0 blends the model's output with the input over the N pixels inside every side of the rectangle that is not also a
+ *   side of the frame (a side on the frame's border has no seam, so it gets no ramp).  Per axis a pixel at distance d = 0..N-1 from
+ *   such a side has the weight
+ *     wa = fl32(fl32(2 d + 1) * fl32(1 / (2 N)))                            (the reciprocal rounded once from double, on the host)
+ *   and wa = 1 elsewhere; N <= min(200, h / 2, w / 2), so the two ramps of an axis never overlap.  With wt = fl32(wy * wx), m the
+ *   model's value and o = fl32((float)min(v, D_in) * fl32(1 / D_in)) the input's, the sample is the egress quantisation
+ *   (spei_frame_u8_out's) of fmaf(wt, m - o, o) where wt != 1, and of m itself where wt == 1: every pixel outside the ramps keeps
+ *   the hard paste's bits.  The flag, and a 0 sample, follow m, not the blend's result.
+ *   Non-zero before anything is launched: a null src, frame or dst; an in_depth outside {8, 10, 12}; a rectangle outside the frame or
+ *   with h or w below 1; hp, wp not the rounded-up sizes; a feather outside 0..min(200, h / 2, w / 2); a dst that overlaps frame or src.
+ * spei_roi_paste_u16: the same with a packed uint16 dst of `depth` 10 or 12 and spei_frame_u16_out's quantisation. */
+int spei_roi_paste_u8(const float* src, const void* frame, int in_depth, unsigned char* dst, int* nonfinite, int H, int W, int y0, int x0,
+                      int h, int w, int hp, int wp, int feather, spei_stream_t stream);
+int spei_roi_paste_u16(const float* src, const void* frame, int in_depth, uint16_t* dst, int* nonfinite, int H, int W, int y0, int x0,
+                       int h, int w, int hp, int wp, int feather, int depth, spei_stream_t stream);
+
+/* The extent of the picture in N packed uint8 [H][W][3] frames, frame_stride bytes apart (rows packed; the frame-size bound of
+ * spei_frames_u8_in), for the clip API's bar rule (video.find_bars): on the integer luma of spei_frame_pair_stats,
+ * Y = (77 R + 150 G + 29 B + 128) >> 8, rowmax[y] (H ints) is the maximum of Y over row y of all N frames and colmax[x] (W ints) the
+ * maximum over column x.  accumulate == 0 clears both on the stream first; otherwise the maxima join what is there, so a clip is
+ * scanned batch by batch.  An integer maximum commutes: the result is exact, whatever the launch shape and the order of the updates.
+ * spei_frame_extent_u16: the same on uint16 frames of `depth` 10 or 12 (frame_stride in BYTES and even, src 2-byte aligned, a word
+ * above D reads as D), on the d-bit luma of spei_frame_pair_stats_u16. */
+int spei_frame_extent(const unsigned char* src, int64_t frame_stride, int N, int H, int W, int* rowmax, int* colmax, int accumulate,
+                      spei_stream_t stream);
+int spei_frame_extent_u16(const uint16_t* src, int64_t frame_stride, int N, int H, int W, int depth, int* rowmax, int* colmax,
+                          int accumulate, spei_stream_t stream);
+
 /* ---- planar YUV frames of the clip API (speinet_amd/y4m.py, speinet_amd/video.py; an extension beyond the reference) ---- */
 
 #define SPEI_YUV_420_CENTER 0 /* 4:2:0, chroma sample at the centre of its 2x2 block (y4m C420jpeg, and bare C420) */

@@ -504,6 +504,116 @@ def tiles_out(tiles, plan, out_depth: int = 8, out: Optional[torch.Tensor] = Non
     return out
 
 
+ROI_FEATHER_MAX = 200
+
+
+def _rect(roi, h: int, w: int) -> tuple:
+    """(y0, x0, rh, rw) of a rectangle inside an h x w frame, as ints; ValueError otherwise."""
+    vals = tuple(roi) if isinstance(roi, (tuple, list)) else ()
+    if len(vals) != 4 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in vals):
+        raise ValueError(f"a rectangle is four whole numbers (y0, x0, h, w), got {roi!r}")
+    y0, x0, rh, rw = (int(v) for v in vals)
+    if rh < 1 or rw < 1 or y0 < 0 or x0 < 0 or y0 + rh > h or x0 + rw > w:
+        raise ValueError(f"the rectangle {(y0, x0, rh, rw)} is empty or lies outside the {w}x{h} frame")
+    return y0, x0, rh, rw
+
+
+def roi_in(frame: torch.Tensor, roi, out: torch.Tensor, depth: Optional[int] = None) -> torch.Tensor:
+    """One packed frame [H,W,3] on the device, uint8 (`depth` None) or uint16 of `depth` 10 or 12 bits -> the rectangle `roi` =
+    (y0, x0, h, w) of it as fp32 planes in `out` [3, hp, wp] (contiguous; hp, wp = h, w rounded up to multiples of 20): bit-identical
+    to `frames_u8_in` / `frames_u16_in` on the crop frame[y0 : y0 + h, x0 : x0 + w], reflect pad included.  It is `tiles_in` with a
+    table of one tile at (y0, x0): one launch on the current stream (csrc/tile_io.hip), no host sync."""
+    from types import SimpleNamespace
+    assert frame.dim() == 3
+    y0, x0, rh, rw = _rect(roi, *frame.shape[:2])
+    plan = SimpleNamespace(H=int(frame.shape[0]), W=int(frame.shape[1]), rows=1, cols=1, th=rh, tw=rw, y0=(y0,), x0=(x0,))
+    assert out.dim() == 3 and out.is_contiguous()
+    tiles_in(frame, plan, out.unsqueeze(0), depth)
+    return out
+
+
+def roi_paste(x: torch.Tensor, frame: torch.Tensor, roi, out_depth: int = 8, feather: int = 0, in_depth: Optional[int] = None,
+              out: Optional[torch.Tensor] = None, nonfinite: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The model's output for a rectangle, pasted into the input frame: `x` fp32 [3,hp,wp] on the device (contiguous; hp, wp = h, w
+    rounded up to multiples of 20), `frame` the packed input frame [H,W,3], uint8 (`in_depth` None) or uint16 of `in_depth` 10 or 12
+    bits, `roi` = (y0, x0, h, w) -> the output frame, uint8 [H,W,3] for `out_depth` 8 and uint16 for 10 and 12.  Inside the rectangle
+    it holds `frame_u8_out` / `frame_u16_out`'s value of x[:, y - y0, x - x0], outside it the input sample at the output depth,
+    (min(v, D_in) * 2 * D_out + D_in) // (2 * D_in) with D = 2^depth - 1 (the identity at equal depths).  `feather` N in
+    0..min(200, h // 2, w // 2): N > 0 blends the two over the N pixels inside every side of the rectangle that is not a side of the
+    frame (include/speinet_hip.h has the weights); every pixel off the ramps keeps the hard paste's bits.  `out` (optional): the packed
+    destination; it may not overlap `frame` or `x`.  `nonfinite` (optional): an int32 device tensor whose first element becomes nonzero
+    iff a value of x inside the h x w crop was a NaN or an infinity (that sample is 0); the pad of x is never read.  One launch on the
+    current stream writes the whole frame (csrc/roi_io.hip), no host sync."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 3 and x.is_contiguous()
+    deep = frame.dtype == torch.uint16
+    assert frame.device == x.device and frame.dtype in (torch.uint8, torch.uint16) and frame.dim() == 3 and frame.shape[2] == 3
+    assert frame.is_contiguous()
+    if deep:
+        in_depth = _depth(in_depth)
+    elif in_depth not in (None, 8):
+        raise ValueError(f"in_depth= applies to uint16 frames only; the frame is {frame.dtype}")
+    else:
+        in_depth = 8
+    if isinstance(out_depth, bool) or out_depth not in y4m.DEPTHS:
+        raise ValueError(f"out_depth must be 8, 10 or 12, got {out_depth!r}")
+    h, w = (int(v) for v in frame.shape[:2])
+    y0, x0, rh, rw = _rect(roi, h, w)
+    hp, wp = padded_size(rh), padded_size(rw)
+    if tuple(x.shape[1:]) != (hp, wp):
+        raise ValueError(f"the planes are {tuple(x.shape[1:])}, a {rh}x{rw} rectangle rounds up to {(hp, wp)}")
+    fmax = min(ROI_FEATHER_MAX, rh // 2, rw // 2)
+    if isinstance(feather, bool) or not isinstance(feather, (int, np.integer)) or not 0 <= feather <= fmax:
+        raise ValueError(f"feather must be a whole number in 0..{fmax} (at most {ROI_FEATHER_MAX} and half of the {rh}x{rw} rectangle), "
+                         f"got {feather!r}")
+    dtype = torch.uint8 if out_depth == 8 else torch.uint16
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=dtype, device=x.device)
+    assert out.device == x.device and out.dtype == dtype and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
+    assert nonfinite is None or (nonfinite.device == x.device and nonfinite.dtype == torch.int32 and nonfinite.numel() >= 1)
+    flag = _vp(nonfinite.data_ptr() if nonfinite is not None else 0)
+    lib = _lib.lib()
+    with torch.cuda.device(x.device):
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        head = (_vp(x.data_ptr()), _vp(frame.data_ptr()), in_depth, _vp(out.data_ptr()), flag, h, w, y0, x0, rh, rw, hp, wp, int(feather))
+        if out_depth == 8:
+            _lib.check(lib.spei_roi_paste_u8(*head, st), "spei_roi_paste_u8")
+        else:
+            _lib.check(lib.spei_roi_paste_u16(*head, out_depth, st), "spei_roi_paste_u16")
+    return out
+
+
+def frame_extent(frames: torch.Tensor, depth: Optional[int] = None, out=None):
+    """The extent of the picture in packed frames [N,H,W,3] on the device (any frame stride), uint8 (`depth` None) or uint16 of `depth`
+    10 or 12 bits -> (rowmax int32 [H], colmax int32 [W]): the maximum over every row, and over every column, of all N frames of the
+    integer luma of `frame_pair_stats` / `frame_pair_stats_u16`, Y = (77 R + 150 G + 29 B + 128) >> 8.  `out` (optional): the
+    (rowmax, colmax) of an earlier call, which the maxima then JOIN (a clip is scanned batch by batch); None: fresh tables, cleared on
+    the stream.  Exact integers.  One launch on the current stream (csrc/roi_io.hip), no host sync."""
+    assert frames.is_cuda and frames.dtype in (torch.uint8, torch.uint16) and frames.dim() == 4
+    deep = frames.dtype == torch.uint16
+    if deep:
+        depth = _depth(depth)
+    elif depth not in (None, 8):
+        raise ValueError(f"depth= applies to uint16 frames only; the frames are {frames.dtype}")
+    n, h, w, c = frames.shape
+    assert c == 3 and frames.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
+    dev = frames.device
+    if out is None:
+        rowmax, colmax = torch.empty(h, dtype=torch.int32, device=dev), torch.empty(w, dtype=torch.int32, device=dev)
+    else:
+        rowmax, colmax = out
+        for t, size in ((rowmax, h), (colmax, w)):
+            assert t.device == dev and t.dtype == torch.int32 and tuple(t.shape) == (size,) and t.is_contiguous()
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        tail = (_vp(rowmax.data_ptr()), _vp(colmax.data_ptr()), 0 if out is None else 1, st)
+        if deep:
+            _lib.check(lib.spei_frame_extent_u16(_vp(frames.data_ptr()), 2 * frames.stride(0), n, h, w, depth, *tail), "spei_frame_extent_u16")
+        else:
+            _lib.check(lib.spei_frame_extent(_vp(frames.data_ptr()), frames.stride(0), n, h, w, *tail), "spei_frame_extent")
+    return rowmax, colmax
+
+
 def planes_d4(x: torch.Tensor, op: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Member `op` (0..7, speinet_amd/ensemble.py) of every plane of `x`: fp32 [..., H, W] on the device -> `ensemble.apply(x, op)` as a
     contiguous tensor, [..., W, H] for op & 4, copied as bits.  `x` may be a view whose planes are contiguous and evenly spaced (any

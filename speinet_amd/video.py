@@ -5,6 +5,7 @@
                                 [--labels <file.npy>] [--detector <detector.json>] [--cuts none|auto|<file>]
                                 [--matrix bt601|bt709] [--range full|limited] [--fps num:den] [--chroma 420jpeg|420mpeg2|444]
                                 [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N] [--ensemble 1|2|4|8]
+                                [--roi none|auto|Y,X,H,W] [--roi_feather N]
 
 (`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; stdin is spooled to a temporary file
 on disk before the first frame is deblurred, see `main`)
@@ -38,6 +39,12 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     (`ops.planes_d4`), and one launch transforms the members' outputs back and averages them in float32 in a fixed order
     (`ops.d4_mean`) in front of the unchanged egress: what the reference's `forward_x8` does on the host, and never calls.  K members
     cost K forward passes.  Off by default.
+  * a region of interest (`roi=`, `--roi`; csrc/roi_io.hip): only a rectangle of every frame is deblurred, given, or found as the
+    active picture area of letterboxed or pillarboxed footage ("auto": `active_area`, one `ops.frame_extent` launch per batch of
+    sampled frames, and the bar rule `find_bars`).  The frames are still uploaded and cached whole; the labelling pass, the scene
+    statistics and the window plan see the cropped frames; the rectangle is ingested by the tile ingest with a table of one tile
+    (`ops.roi_in`) and one launch pastes the model's output into the otherwise untouched frame (`ops.roi_paste`), with a hard edge
+    or (`roi_feather=`, `--roi_feather`) blended with the input over a ramp inside the rectangle.  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -48,6 +55,7 @@ from __future__ import annotations
 
 import argparse
 import collections
+import copy
 import glob
 import os
 import sys
@@ -195,17 +203,42 @@ class _Frames:
     bottom and right to H x W (`crop`: the source size rounded down to multiples of 20; otherwise the source size).  A y4m clip
     (`yuv`: its (layout, matrix, range); `items` the `Y4MReader`) is the exception: `host` returns the frame's planar bytes as they
     are in the file, and `rgb` turns uploaded planar frames into the cropped RGB frames on the device.  `depth`: 8 (uint8 frames), or
-    10 / 12 (uint16 frames: `dtype`; the planar bytes of a deep y4m clip are still uint8, two per sample)."""
+    10 / 12 (uint16 frames: `dtype`; the planar bytes of a deep y4m clip are still uint8, two per sample).  `view` is the same clip
+    seen through a rectangle (the region of interest: the analysis pass is handed that view), `sample` a subset of its frames."""
 
     def __init__(self, items, T: int, H: int, W: int, paths: bool, crop: bool = False, yuv=None, depth: int = 8):
         self.items, self.T, self.paths, self.src, self.yuv, self.depth = items, T, paths, (H, W), yuv, depth
         self.dtype = torch.uint8 if depth == 8 else torch.uint16
         self.H, self.W = (H - H % 20, W - W % 20) if crop else (H, W)
+        self.y0 = self.x0 = 0            # the origin of the H x W view in the source frames (`view`: a rectangle)
+        self.index = None                # the source frame of each of the T frames (`sample`: a subset); None: all, in order
+
+    def view(self, rect) -> "_Frames":
+        """The same clip seen through the rectangle (y0, x0, h, w) of this view: `device`, `host` and `rgb` hand out the cropped
+        frames, H and W are the rectangle's.  Nothing is copied."""
+        y0, x0, h, w = rect
+        assert 0 <= y0 and 0 <= x0 and y0 + h <= self.H and x0 + w <= self.W
+        v = copy.copy(self)
+        v.y0, v.x0, v.H, v.W = self.y0 + y0, self.x0 + x0, h, w
+        return v
+
+    def sample(self, index) -> "_Frames":
+        """The clip of the frames `index` (indices into this one) of this clip.  Nothing is copied."""
+        v = copy.copy(self)
+        v.index = [self._at(int(i)) for i in index]
+        v.T = len(v.index)
+        return v
+
+    def _at(self, i: int) -> int:
+        return i if self.index is None else self.index[i]
+
+    def _crop(self, f):
+        return f[..., self.y0:self.y0 + self.H, self.x0:self.x0 + self.W, :]
 
     def on_device(self, i: int) -> bool:
         if self.yuv is not None:
             return False
-        f = self.items[i]
+        f = self.items[self._at(i)]
         return torch.is_tensor(f) and f.is_cuda
 
     def rgb(self, planar: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -221,23 +254,23 @@ class _Frames:
                 return ops.yuv_to_rgb_u16(p, h, w, *how, self.depth, out=out)
         if (self.H, self.W) == self.src:
             return convert(planar, self.H, self.W, *self.yuv, out=out)
-        full = convert(planar, *self.src, *self.yuv)[:, :self.H, :self.W]
+        full = self._crop(convert(planar, *self.src, *self.yuv))
         return full.contiguous() if out is None else out.copy_(full)
 
     def device(self, i: int) -> torch.Tensor:
-        return self.items[i][:self.H, :self.W]
+        return self._crop(self.items[self._at(i)])
 
     def host(self, i: int) -> np.ndarray:
         if self.yuv is not None:
-            return self.items.raw(i)
-        f = self.items[i]
+            return self.items.raw(self._at(i))
+        f = self.items[self._at(i)]
         if self.paths:
             img = _imread(f)
             if img.shape[:2] != self.src:
                 raise ValueError(f"frame {i} ({f}) is {img.shape[1]}x{img.shape[0]}, the clip is {self.src[1]}x{self.src[0]}")
         else:
             img = f.numpy() if torch.is_tensor(f) else np.asarray(f)
-        return img[:self.H, :self.W]
+        return self._crop(img)
 
 
 def _check_frame(i, shape, dtype, depth=None) -> None:
@@ -384,6 +417,82 @@ def _sad_8bit(sad: np.ndarray, depth: int) -> np.ndarray:
     return sad if depth == 8 else sad / float(1 << (depth - 8))
 
 
+BAR_PARAMS = ("level", "min_bar", "frames")       # `bar_params`: find_bars' keywords, and the number of frames `active_area` scans
+ROI_FEATHER_MAX = ops.ROI_FEATHER_MAX
+
+
+def find_bars(rowmax, colmax, depth: int = 8, *, level: int = 24, min_bar: int = 4):
+    """The active picture area of a clip from its extent maxima (`active_area`): rowmax [H], colmax [W], the maximum over every row
+    and every column of the clip's integer luma at `depth` bits.  A line is black iff its maximum is at most level << (depth - 8);
+    top, bottom, left and right are the numbers of leading / trailing black rows and columns; a bar of fewer than `min_bar` lines
+    counts as none (a dark edge line is not a bar).  Returns the rectangle (y0, x0, h, w) that is left, or None when no bar is left
+    (the whole frame is picture) or when the rest is smaller than 20x20 (a black clip).
+
+    `level` and `min_bar` are design parameters, not measurements: limited-range black is 16 and compression leaves a few levels of
+    noise above it, hence 24; nobody has tuned either on real footage, which is why they are keywords (`bar_params=`).  Blind spots: a
+    logo or a subtitle inside a bar ends the bar there; a scene darker than `level` along a whole edge reads as a bar (scan more frames)."""
+    if isinstance(depth, bool) or depth not in y4m.DEPTHS:
+        raise ValueError(f"find_bars: depth must be 8, 10 or 12, got {depth!r}")
+    for name, v in (("level", level), ("min_bar", min_bar)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"find_bars: {name} must be a whole number >= 0, got {v!r}")
+    rows, cols = np.asarray(rowmax).reshape(-1), np.asarray(colmax).reshape(-1)
+    thr = int(level) << (depth - 8)
+
+    def lead(a) -> int:
+        lit = np.flatnonzero(a > thr)
+        return int(lit[0]) if lit.size else int(a.size)
+
+    bars = [lead(rows), lead(rows[::-1]), lead(cols), lead(cols[::-1])]
+    top, bottom, left, right = (b if b >= min_bar else 0 for b in bars)
+    if not (top or bottom or left or right):
+        return None
+    h, w = rows.size - top - bottom, cols.size - left - right
+    if h < MIN_SIZE or w < MIN_SIZE:
+        return None
+    return top, left, h, w
+
+
+def sample_indices(T: int, n: Optional[int]) -> list:
+    """min(n, T) frame indices spread evenly over a clip of T frames, the middle of each of as many equal parts (None: every frame)."""
+    n = T if n is None else min(int(n), T)
+    return [((2 * k + 1) * T) // (2 * n) for k in range(n)]
+
+
+def active_area(frames, device, frames_max: Optional[int] = 64):
+    """The extent maxima of a clip (anything `frames_of` accepts, or its result): (rowmax int64 [H], colmax int64 [W]) as numpy arrays,
+    the input of `find_bars`, from one streaming pass on `device` over at most `frames_max` frames spread evenly over the clip (None:
+    every frame).  The pass is `detector.clip_batches` on that subset, DETECT_BATCH frames at a time, so a y4m or deep clip goes
+    through its usual conversion, with one `ops.frame_extent` launch per batch joining the maxima: the sampled frames are uploaded once
+    more than a run that does not ask for the area."""
+    fr = frames if isinstance(frames, _Frames) else frames_of(frames)
+    if frames_max is not None and (isinstance(frames_max, bool) or not isinstance(frames_max, (int, np.integer)) or frames_max < 1):
+        raise ValueError(f"active_area: frames_max must be None or a whole number >= 1, got {frames_max!r}")
+    sub = fr.sample(sample_indices(fr.T, frames_max))
+    dev, ext = torch.device(device), None
+    with torch.no_grad(), torch.cuda.device(dev):
+        for _, batch in detector.clip_batches(sub, dev, DETECT_BATCH):
+            ext = ops.frame_extent(batch, None if fr.depth == 8 else fr.depth, out=ext)
+    return ext[0].cpu().numpy().astype(np.int64), ext[1].cpu().numpy().astype(np.int64)
+
+
+def roi_of(roi, H: int, W: int):
+    """Validate a region of interest for H x W frames: None, "auto", or (y0, x0, h, w), four whole numbers (no bools) with
+    0 <= y0, y0 + h <= H, the same for x, and h, w >= 20.  Returns None, "auto", the tuple of ints, or None for the rectangle that is
+    the whole frame (the path without a region).  Raises ValueError with the reason."""
+    if roi is None or (isinstance(roi, str) and roi == "auto"):
+        return roi
+    vals = tuple(roi) if isinstance(roi, (tuple, list)) else ()
+    if len(vals) != 4 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in vals):
+        raise ValueError(f"roi must be None, \"auto\" or four whole numbers (y0, x0, h, w), got {roi!r}")
+    y0, x0, h, w = (int(v) for v in vals)
+    if h < MIN_SIZE or w < MIN_SIZE:
+        raise ValueError(f"roi {(y0, x0, h, w)}: the rectangle must be at least {MIN_SIZE}x{MIN_SIZE}, the smallest frame the clip API takes")
+    if y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"roi {(y0, x0, h, w)}: the rectangle lies outside the {W}x{H} frame (0 <= y0, y0 + h <= {H}, 0 <= x0, x0 + w <= {W})")
+    return None if (y0, x0, h, w) == (0, 0, H, W) else (y0, x0, h, w)
+
+
 def _scene_plan(labels, n_seq: int, numbers) -> list:
     """The plan of one continuous scene: `selection.assemble_windows` on its frames."""
     T = len(labels)
@@ -435,11 +544,17 @@ class ClipRun:
     frames that were recomputed in bf16x3 because their 16-bit pass left a non-finite value; `seconds[k]` is window k's host time
     [assembling its input, enqueueing it] (the wait for a free launch slot excluded).  `tiles` is the `tiles.TilePlan` of a clip that is
     deblurred tile by tile, None for one that is deblurred whole (a plan of one tile included).  `ensemble` is the number of members of
-    the geometric self-ensemble every window runs as (1: none)."""
+    the geometric self-ensemble every window runs as (1: none).  `roi` is the region of interest in use, (y0, x0, h, w), or None for a
+    clip that is deblurred whole (found on first access, by `active_area` + `find_bars`, when the caller asked for "auto"); labels,
+    cuts and the plan are then those of the clip of cropped frames."""
 
     def __init__(self, model, frames: _Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
-                 out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None, ensemble: int = 1):
+                 out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None, ensemble: int = 1, roi=None,
+                 roi_feather: int = 0, bar_params: Optional[dict] = None):
         self.model, self.frames = model, frames
+        self._roi = roi                  # None, a rectangle, or "auto" while the scan has not run
+        self.roi_feather = roi_feather
+        self.bar_params = dict(bar_params or {})
         self.ensemble = ens.check_size(ensemble)
         self.tiles = tiles               # the tile plan of a clip that is deblurred tile by tile (more than one tile), or None
         self.depth = frames.depth
@@ -460,6 +575,22 @@ class ClipRun:
         self.numbers = numbers
         self._plan = None
         self._it = None
+
+    @property
+    def roi(self):
+        if isinstance(self._roi, str):   # "auto": the bar rule on the extent maxima of the sampled frames; no bars: the path without
+            fr, bp = self.frames, self.bar_params
+            ext = active_area(fr, self.device, bp.get("frames", 64))
+            found = find_bars(*ext, fr.depth, **{k: v for k, v in bp.items() if k != "frames"})
+            self._roi = None if found is None else roi_of(found, fr.H, fr.W)
+            if self._roi is not None and self.roi_feather > min(ROI_FEATHER_MAX, self._roi[2] // 2, self._roi[3] // 2):
+                raise ValueError(f"roi_feather={self.roi_feather} does not fit the rectangle {self._roi} that roi=\"auto\" found: at most "
+                                 f"min({ROI_FEATHER_MAX}, h // 2, w // 2)")
+        return self._roi
+
+    def _view(self) -> _Frames:
+        """The clip the analysis pass sees: the frames cropped to the region of interest."""
+        return self.frames if self.roi is None else self.frames.view(self.roi)
 
     @property
     def labels(self) -> np.ndarray:
@@ -490,8 +621,9 @@ class ClipRun:
     def _analyse(self) -> None:
         """Whatever is missing of the LD detector's labels and the scene cuts, in ONE pass over the clip, DETECT_BATCH frames at a time:
         upload, then gray planes (spei_frames_u8_in / spei_frames_u16_in) and focus measures, pair statistics (spei_frame_pair_stats /
-        spei_frame_pair_stats_u16), or both.  A deep clip stays deep throughout."""
-        p, fr = self.detector, self.frames
+        spei_frame_pair_stats_u16), or both.  A deep clip stays deep throughout.  With a region of interest the pass is handed the
+        clip's view through it, so the detector and the pair statistics see the cropped frames."""
+        p, fr = self.detector, self._view()
         feats, stats = detector.clip_pass(fr, self.device, p.kernel_size, DETECT_BATCH, features=self._labels is None,
                                           pair_stats=self._cuts is None)
         if feats is not None:
@@ -505,6 +637,11 @@ class ClipRun:
         tp = self.tiles
         nt = 1 if tp is None else tp.n                 # tiles per frame: each is a window of its own, all of one shape
         Hp, Wp = (padded_size(H), padded_size(W)) if tp is None else tp.padded
+        # a region of interest: the model sees the rectangle only, the cache keeps whole frames (the paste needs them)
+        roi, roi_feather = self.roi, self.roi_feather
+        if roi is not None:
+            Hp, Wp = padded_size(roi[2]), padded_size(roi[3])
+        centres = {}                     # per window in flight: its centre input frame, whole, for the paste (and a recompute's)
         plan = self.plan
         n = m.n_sequence
         pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
@@ -529,12 +666,18 @@ class ClipRun:
             """Frame f as frame j of the window's input: of its one sample, or of every tile's in one launch."""
             if tp is not None:
                 return ops.tiles_in(f, tp, x[:, j], None if depth == 8 else depth)
+            if roi is not None:          # the tile ingest with a table of one tile: bit-identical to the frame ingest on the crop
+                return ops.roi_in(f, roi, x[0, j], None if depth == 8 else depth)
             return ops.frames_u8_in(f, out=x[0, j]) if depth == 8 else ops.frames_u16_in(f, depth, out=x[0, j])
 
-        def egress(y, dst, flag):
-            """The model's output [nt, 3, Hp, Wp] (or a list of nt planes) as the frame: the crop, or the tiles' bands stitched."""
+        def egress(y, dst, flag, k):
+            """The model's output [nt, 3, Hp, Wp] (or a list of nt planes) as frame k: the crop, the tiles' bands stitched, or the
+            rectangle pasted into the input frame."""
             if tp is not None:
                 return ops.tiles_out(y, tp, out_depth, out=dst, nonfinite=flag)
+            if roi is not None:
+                return ops.roi_paste(y[0], centres[k], roi, out_depth, roi_feather, None if depth == 8 else depth, out=dst,
+                                     nonfinite=flag)
             if out_depth == 8:
                 return ops.frame_u8_out(y[0], H, W, out=dst, nonfinite=flag)
             return ops.frame_u16_out(y[0], H, W, out_depth, out=dst, nonfinite=flag)
@@ -566,6 +709,8 @@ class ClipRun:
                     x[:, j].zero_()
                 else:
                     ingest(frame(key), x, j)
+            if roi is not None:
+                centres[k] = frame(plan[k]["window"][n // 2])     # uploaded just now: the frame that window k deblurs
             xs = members_of(x)
             self.seconds.append([time.time() - t0, 0.0])
             return xs
@@ -607,7 +752,9 @@ class ClipRun:
                         if nxt is not None:
                             m.prefetch_window(nxt[t:t + 1], tile_keys(plan[k + 1]["keys"], t), enc, zero_ref=plan[k + 1]["zero_pre"])
                         y.append(m.forward_window(x[t:t + 1], tile_keys(w["keys"], t), enc, zero_ref=w["zero_pre"])[0])
-                egress(y, dst, flags[slot:slot + 1])
+                if roi is not None:
+                    centres[k].record_stream(lane)
+                egress(y, dst, flags[slot:slot + 1], k)
                 flags_host[slot:slot + 1].copy_(flags[slot:slot + 1], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
@@ -630,7 +777,7 @@ class ClipRun:
             finally:
                 m.precision, m.corr_precision, m.use_graph = keep
             slot = k % FLAG_RING
-            egress(y, dst, flags[slot:slot + 1])
+            egress(y, dst, flags[slot:slot + 1], k)          # a region of interest: the same paste
             if int(flags[slot].item()):
                 raise FloatingPointError(f"non-finite values in deblurred frame {k} in bf16x3 arithmetic as well: the input or the "
                                          "checkpoint is at fault")
@@ -649,6 +796,7 @@ class ClipRun:
                 cur.wait_stream(home)
             else:
                 cur.wait_event(e)
+            centres.pop(k, None)
             if cur != home:
                 t.record_stream(cur)
             return k, t
@@ -679,7 +827,7 @@ class ClipRun:
 def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
                 detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None,
                 depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20, feather: int = 0,
-                ensemble: int = 1) -> ClipRun:
+                ensemble: int = 1, roi=None, roi_feather: int = 0, bar_params: Optional[dict] = None) -> ClipRun:
     """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
     or uint16 frames when `out_depth` is 10 or 12.
 
@@ -732,6 +880,23 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              `out_depth` and y4m.  K forward passes per frame; labels, scene cuts and the window plan are those of the upright frames.
              A non-finite value in any member sends the window to the bf16x3 recompute, which runs all K members again.  1 is the
              path without it, launch for launch.  `ClipRun.ensemble` holds it.
+    roi    — region of interest: None (the default) deblurs whole frames, launch for launch the path without it.  (y0, x0, h, w), four
+             whole numbers with the rectangle inside the frame and h, w >= 20: only that rectangle is deblurred.  Inside it, frame i of
+             the result is frame i of `deblur_clip` on the clip of cropped frames f[y0:y0+h, x0:x0+w] with every other argument the
+             same, bit for bit (`roi_feather` 0): its reflect pad at the rectangle's bottom and right, the detector's labels of the
+             cropped frames when `labels` is None, `cuts="auto"` on their pair statistics, their window plan.  Outside it, it is the
+             input frame's sample at the output depth, (min(v, D_in) * 2 * D_out + D_in) // (2 * D_in) with D = 2^depth - 1 (exact,
+             rounds half up, the identity at equal depths); for a y4m clip the input frame is the RGB frame made from it.  One launch
+             per frame pastes the rectangle into the frame (`ops.roi_paste`); the rectangle is ingested by the tile ingest with a table
+             of one tile (`ops.roi_in`).  A rectangle equal to the whole frame is the path without it.  "auto": the active picture area
+             of letterboxed or pillarboxed footage, found by `active_area` (one more streaming pass over at most 64 sampled frames) and
+             `find_bars`; no bars: the path without it.  Not with `tiles` (the tile egress writes whole frames only) and not with
+             `crop`.  `ClipRun.roi` holds the rectangle in use, or None.
+    roi_feather — 0..min(200, h // 2, w // 2), with `roi` only: 0 (the default) pastes with a hard edge.  N > 0 blends the deblurred
+             rectangle with the input linearly over the N pixels inside every side of the rectangle that is not a side of the frame;
+             every pixel off those ramps is the hard paste's, bit for bit.
+    bar_params — optional keyword arguments of `find_bars` for "auto" (level, min_bar: untuned defaults), and `frames`: the number of
+             frames `active_area` scans (default 64, None: every frame).
 
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
@@ -740,9 +905,32 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     ensemble = ens.check_size(ensemble)                    # in front of everything else: no frame is looked at
     if tiles is None and not (isinstance(feather, int) and not isinstance(feather, bool) and feather == 0):
         raise ValueError(f"feather={feather!r} needs tiles=: it blends the seams between tiles, and an untiled frame has none")
+    if isinstance(roi_feather, bool) or not isinstance(roi_feather, (int, np.integer)) or roi_feather < 0:
+        raise ValueError(f"roi_feather must be a whole number >= 0, got {roi_feather!r}")
+    if roi is None and roi_feather != 0:
+        raise ValueError(f"roi_feather={roi_feather!r} needs roi=: it blends the edge of the region of interest, and a whole frame has none")
+    if roi is not None and tiles is not None:
+        raise ValueError("roi= with tiles= is not built: the tile egress writes whole packed frames only, not a rectangle of one")
+    if roi is not None and crop:
+        raise ValueError("roi= with crop=True: the rectangle is given in the frames as they are, crop them first or leave crop off")
+    if bar_params is not None and set(bar_params) - set(BAR_PARAMS):
+        raise ValueError(f"bar_params holds {sorted(set(bar_params) - set(BAR_PARAMS))}: find_bars takes level and min_bar, and frames is "
+                         "the number of frames that active_area scans")
     if isinstance(frames, (str, os.PathLike)) and os.fspath(frames).lower().endswith(".y4m"):
         frames = y4m.Y4MReader(frames, depths=y4m.DEPTHS)
     fr = frames_of(frames, crop, yuv, depth)
+    if roi is not None and not isinstance(roi, str):
+        rect = roi_of(tuple(roi) if isinstance(roi, list) else roi, fr.H, fr.W)
+        h, w = (fr.H, fr.W) if rect is None else rect[2:]
+        if roi_feather > min(ROI_FEATHER_MAX, h // 2, w // 2):
+            raise ValueError(f"roi_feather={roi_feather} is outside 0..{min(ROI_FEATHER_MAX, h // 2, w // 2)}: at most {ROI_FEATHER_MAX} "
+                             f"and half of the {w}x{h} rectangle")
+        roi = rect
+    elif roi is not None:
+        roi = roi_of(roi, fr.H, fr.W)    # "auto", or a ValueError for any other string
+        if roi_feather > min(ROI_FEATHER_MAX, fr.H // 2, fr.W // 2):
+            raise ValueError(f"roi_feather={roi_feather} is outside 0..{min(ROI_FEATHER_MAX, fr.H // 2, fr.W // 2)}: at most "
+                             f"{ROI_FEATHER_MAX} and half of the rectangle, which lies inside the {fr.W}x{fr.H} frame")
     if out_depth is not None and (isinstance(out_depth, bool) or out_depth not in y4m.DEPTHS):
         raise ValueError(f"out_depth must be None, 8, 10 or 12, got {out_depth!r}")
     out_depth = fr.depth if out_depth is None else int(out_depth)
@@ -766,12 +954,22 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     tp = None if tiles is None else tiling.tile_plan(fr.H, fr.W, tuple(tiles) if isinstance(tiles, list) else tiles, shave, feather)
     if tp is not None and tp.n == 1:
         tp = None                        # one tile that spans the frame: the untiled path
-    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp, ensemble)
+    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp, ensemble, roi, int(roi_feather), bar_params)
 
 
 def _inputs(spec: str) -> list:
     files = [os.path.join(spec, f) for f in os.listdir(spec)] if os.path.isdir(spec) else glob.glob(spec)
     return sorted(f for f in files if f.lower().endswith(IMAGE_EXTS) and os.path.isfile(f))
+
+
+def parse_roi(text: str):
+    """`--roi`: 'none' -> None, 'auto' -> "auto", 'Y,X,H,W' -> (y0, x0, h, w).  Raises ValueError with the reason."""
+    if text in ("none", "auto"):
+        return None if text == "none" else "auto"
+    parts = text.split(",")
+    if len(parts) != 4 or not all(p.strip().lstrip("+").isdigit() for p in parts):
+        raise ValueError(f"{text!r} is not none, auto or Y,X,H,W (four whole numbers: top, left, height, width)")
+    return tuple(int(p) for p in parts)
 
 
 def read_cuts(path: str) -> list:
@@ -864,6 +1062,11 @@ def main(argv=None) -> None:
     p.add_argument("--ensemble", type=int, choices=ens.SIZES, default=1, help="geometric self-ensemble: run every window on 2 (the frame "
                    "and its mirror), 4 (the flips) or 8 (flips and transpositions) transformed copies and average the results; K times "
                    "the work (default 1: off)")
+    p.add_argument("--roi", default="none", help="region of interest: 'none' (the default: whole frames), 'auto' (the active picture area "
+                   "of letterboxed or pillarboxed footage, found from the clip) or Y,X,H,W (top, left, height, width; at least 20x20): "
+                   "only that rectangle is deblurred, the rest of every frame is the input's")
+    p.add_argument("--roi_feather", type=int, default=0, help="with --roi: blend the deblurred rectangle with the input over the N pixels "
+                   "inside every side of it that is not a side of the frame (0..min(200, H/2, W/2); default 0: a hard edge)")
     p.add_argument("--spool_dir", default=None, help="directory of the temporary file that '--input -' is copied to (default: the system's)")
     a = p.parse_args(argv)
     try:
@@ -876,6 +1079,14 @@ def main(argv=None) -> None:
         if not 0 <= a.shave <= tiling.MAX_SHAVE or not 0 <= a.feather <= a.shave:
             raise SystemExit(f"--feather {a.feather}: must be 0..shave (--shave {a.shave}, itself 0..{tiling.MAX_SHAVE}): the ramp is "
                              "blended from the margin the tiles keep")
+    try:
+        roi = parse_roi(a.roi)
+    except ValueError as e:
+        raise SystemExit(f"--roi: {e}")
+    if roi is not None and tiles is not None:              # refused here, before the model is loaded
+        raise SystemExit("--roi with --tiles is not built: the tile egress writes whole frames only")
+    if a.roi_feather != 0 and roi is None:
+        raise SystemExit(f"--roi_feather {a.roi_feather}: needs --roi: it blends the edge of the region of interest")
     to_stdout = a.output == "-"
     to_y4m = to_stdout or a.output.lower().endswith(".y4m")
     log = sys.stderr if to_stdout else sys.stdout
@@ -914,7 +1125,8 @@ def main(argv=None) -> None:
             say(f"# {reader.depth}-bit input, PNG output: the frames are written with 8 bits per sample (out_depth 8)")
         out_depth = 8
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
-                      yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather, ensemble=a.ensemble)
+                      yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather, ensemble=a.ensemble,
+                      roi=roi, roi_feather=a.roi_feather)
     out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
@@ -929,6 +1141,8 @@ def main(argv=None) -> None:
         writer = y4m.Y4MWriter(sys.stdout.buffer if to_stdout else a.output, W, H, fps, layout, rng, aspect, depth=out_depth)
     else:
         os.makedirs(a.output, exist_ok=True)
+    if run.roi is not None:
+        say("# roi " + ",".join(str(v) for v in run.roi))
     for c in run.cuts:
         say(f"# cut before {names[c]}")
     if run.tiles is not None:
