@@ -12,17 +12,12 @@
 //                        row and over every column: the input of the clip API's bar rule (video.find_bars).  Integer maxima
 //                        commute, so the result is exact whatever the launch shape.
 //
-// Streaming kernels in the style of frame_io.hip / tile_io.hip: one thread per group of 4 pixels of a row, 12 bytes (24 for deep
-// frames) as three dwords (three 8-byte words) where the address allows and sample by sample otherwise, one 16-byte load per plane.
-// The rectangle's origin is arbitrary, so the paste decides per group whether its four pixels are one aligned run of the model's
-// planes; the rectangle and the ramps travel by value and every inside / outside / ramp decision is a compare against them.
-#include "common.h"
+// Streaming kernels on the pixel group of pixel_group.h, whose loads, luma, rounding and store they share with frame_io.hip and
+// tile_io.hip.  The rectangle's origin is arbitrary, so the paste decides per group whether its four pixels are one aligned run of
+// the model's planes; the rectangle and the ramps travel by value and every inside / outside / ramp decision is a compare against them.
+#include "pixel_group.h"
 
 namespace {
-
-constexpr int MULT = 20;
-constexpr int BLOCKS_MAX = 8192;
-constexpr int FEATHER_MAX = 200;
 
 // the rectangle, and the ramp widths inside its four sides (the feather N, or 0 for a side on the frame's border); r = (float)(1 / (2 N))
 struct Rect {
@@ -32,42 +27,11 @@ struct Rect {
     float r;
 };
 
-__device__ __forceinline__ int byte_of(const uint32_t (&w)[3], int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xff; }
-__device__ __forceinline__ int half_of(const uint2 (&w)[3], int j) {
-    const uint2 q = w[j >> 2];
-    return (((j & 2) ? q.y : q.x) >> (16 * (j & 1))) & 0xffff;
-}
-
-// the 12 samples of a group of 4 pixels at p, clamped to D; `valid` pixels (1..4) exist, the others read as 0
-template <typename T>
-__device__ __forceinline__ void load_group(const T* __restrict__ p, int valid, bool aligned, int D, int (&c)[12]) {
-    if (valid == 4 && aligned) {
-        if constexpr (sizeof(T) == 1) {
-            const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-            const uint32_t w[3] = {q[0], q[1], q[2]};
-#pragma unroll
-            for (int j = 0; j < 12; ++j) c[j] = byte_of(w, j);
-        } else {
-            const uint2* q = reinterpret_cast<const uint2*>(p);
-            const uint2 w[3] = {q[0], q[1], q[2]};
-#pragma unroll
-            for (int j = 0; j < 12; ++j) c[j] = min(half_of(w, j), D);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) c[j] = j < 3 * valid ? min((int)p[j], D) : 0;
-    }
-}
-
 // the input sample at the output depth: v * Dout / Din rounded half up, in integers (at most 4095 * 8190 + 4095 < 2^26)
 __device__ __forceinline__ uint32_t requant(int v, int Din, int Dout) {
     if (Din == Dout) return (uint32_t)v;
     const uint32_t n = (uint32_t)v * 2u * (uint32_t)Dout + (uint32_t)Din;
     return Din == 255 ? n / 510u : Din == 1023 ? n / 2046u : n / 8190u;       // constant divisors: a multiply and a shift each
-}
-
-__device__ __forceinline__ uint32_t quantise(float v, float Df) {
-    return (uint32_t)rintf(fminf(fmaxf(v * Df, 0.0f), Df));                   // mul(D).clamp(0, D).round(): half to even, as torch
 }
 
 // the weight of the model's output at place p of an axis of `len` pixels with ramps of lo / hi pixels at its two ends
@@ -132,32 +96,11 @@ __global__ __launch_bounds__(256) void roi_paste_kernel(const float* __restrict_
                     }
                     const bool fin = isfinite(mv);         // the flag and the 0 follow the model's value, not the blend's
                     bad |= fin ? 0 : 1;
-                    q[c][k] = in ? (fin ? quantise(v, Df) : 0u) : requant(fv[3 * k + c], Din, Dout);
+                    q[c][k] = in ? (fin ? round_sample(v, Df) : 0u) : requant(fv[3 * k + c], Din, Dout);
                 }
             }
         }
-        TO* d = dst + ((int64_t)y * W + x) * 3;
-        if (vec_out && x + 4 <= W) {                       // 12 samples as three dwords (three 8-byte words)
-            if constexpr (sizeof(TO) == 1) {
-                uint32_t w[3] = {0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < 12; ++j) w[j >> 2] |= q[j % 3][j / 3] << (8 * (j & 3));
-                uint32_t* p = reinterpret_cast<uint32_t*>(d);
-                p[0] = w[0]; p[1] = w[1]; p[2] = w[2];
-            } else {
-                uint32_t w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < 12; ++j) w[j >> 1] |= q[j % 3][j / 3] << (16 * (j & 1));
-                uint2* p = reinterpret_cast<uint2*>(d);
-                p[0] = make_uint2(w[0], w[1]); p[1] = make_uint2(w[2], w[3]); p[2] = make_uint2(w[4], w[5]);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (x + k < W)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) d[k * 3 + c] = (TO)q[c][k];
-        }
+        store_group(dst + ((int64_t)y * W + x) * 3, q, vec_out != 0, W - x);
     }
     if (nonfinite && bad) atomicOr(nonfinite, 1);           // rare: one atomic per thread that met a non-finite value
 }
@@ -197,8 +140,7 @@ __global__ __launch_bounds__(256) void frame_extent_kernel(const T* __restrict__
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int ya = (77 * a[3 * k] + 150 * a[3 * k + 1] + 29 * a[3 * k + 2] + 128) >> 8;
-                const int yb = (77 * b[3 * k] + 150 * b[3 * k + 1] + 29 * b[3 * k + 2] + 128) >> 8;
+                const int ya = luma_of(a, k), yb = luma_of(b, k);
                 const bool px = k < valid;                 // a missing pixel has no luma (its zeros would give 0 anyway)
                 ra = max(ra, px ? ya : 0);
                 rb = max(rb, px ? yb : 0);
@@ -225,8 +167,6 @@ __global__ __launch_bounds__(256) void frame_extent_kernel(const T* __restrict__
         if (c > colmax[cx]) atomicMax(&colmax[cx], c);
     }
 }
-
-inline int grid_for(int64_t total) { return (int)((total + 255) / 256 < BLOCKS_MAX ? (total + 255) / 256 : BLOCKS_MAX); }
 
 inline bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
@@ -266,7 +206,7 @@ int roi_paste(const char* name, const float* src, const void* frame, int in_dept
     const int64_t total = (int64_t)H * gw;
     const int vec_src = ((uintptr_t)src & 15) == 0;
     const int vec_frame = (W & 3) == 0 && ((uintptr_t)frame & (in_bytes == 1 ? 3 : 7)) == 0;
-    const int vec_out = (W & 3) == 0 && ((uintptr_t)dst & (sizeof(TO) == 1 ? 3 : 7)) == 0;
+    const int vec_out = (W & 3) == 0 && ((uintptr_t)dst & GROUP_MASK<TO>) == 0;
     const int Din = (1 << in_depth) - 1, Dout = (1 << depth) - 1;
     if (nonfinite && hipMemsetAsync(nonfinite, 0, sizeof(int), stream) != hipSuccess) {
         spei_set_error("%s: clearing the non-finite flag failed", name);
@@ -296,8 +236,7 @@ int frame_extent(const char* name, const T* src, int64_t frame_stride, int N, in
     SPEI_REQUIRE(N == 1 || (frame_stride & (sizeof(T) - 1)) == 0, "%s: odd frame stride %lld (bytes, a multiple of 2)", name,
                  (long long)frame_stride);
     SPEI_REQUIRE(((uintptr_t)src & (sizeof(T) - 1)) == 0, "%s: src must be %d-byte aligned", name, (int)sizeof(T));
-    constexpr int MASK = sizeof(T) == 1 ? 3 : 7;           // a group is 12 (24) bytes
-    const int aligned = ((uintptr_t)src & MASK) == 0 && (N == 1 || (frame_stride & MASK) == 0) && (W & 3) == 0;
+    const int aligned = ((uintptr_t)src & GROUP_MASK<T>) == 0 && (N == 1 || (frame_stride & GROUP_MASK<T>) == 0) && (W & 3) == 0;
     if (!accumulate && (hipMemsetAsync(rowmax, 0, sizeof(int) * H, stream) != hipSuccess ||
                         hipMemsetAsync(colmax, 0, sizeof(int) * W, stream) != hipSuccess)) {
         spei_set_error("%s: clearing the maxima failed", name);

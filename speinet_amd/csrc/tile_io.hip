@@ -13,18 +13,14 @@
 //                        and a column ramp cross; every other pixel is the hard stitch's, bit for bit.  One launch per frame.
 //
 // The tables (at most 8 origins and 9 band bounds per axis, 64 tile pointers) are read from host memory at call time and travel to the
-// kernel by value, in its arguments.  Streaming kernels in the style of frame_io.hip: one thread per group of 4 pixels of a row, 12
-// bytes (24 for deep frames) as three dwords (three 8-byte words) where the address allows and sample by sample otherwise, one
-// 16-byte access per plane.  Tile origins are arbitrary, so the ingest decides per row whether its source is aligned, and the egress
+// kernel by value, in its arguments.  Streaming kernels on the pixel group of pixel_group.h, whose ingest, rounding and store they
+// share with frame_io.hip.  Tile origins are arbitrary, so the ingest decides per row whether its source is aligned, and the egress
 // per group whether its four pixels are one aligned run of one tile.
-#include "common.h"
+#include "pixel_group.h"
 
 namespace {
 
-constexpr int MULT = 20;
 constexpr int GRID_MAX = 8;                                // rows, cols
-constexpr int BLOCKS_MAX = 8192;
-constexpr float INV255 = (float)(1.0 / 255.0);             // spei_frames_u8_in's scale
 
 struct InTab { int y0[GRID_MAX], x0[GRID_MAX]; };
 struct OutTab {
@@ -32,18 +28,11 @@ struct OutTab {
     int y0[GRID_MAX], x0[GRID_MAX], yb[GRID_MAX + 1], xb[GRID_MAX + 1];
 };
 
-__device__ __forceinline__ int byte_of(const uint32_t (&w)[3], int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xff; }
-__device__ __forceinline__ int half_of(const uint2 (&w)[3], int j) {
-    const uint2 q = w[j >> 2];
-    return (((j & 2) ? q.y : q.x) >> (16 * (j & 1))) & 0xffff;
-}
-
 // T = unsigned char (D = 255, inv = INV255) or uint16_t (D = 2^depth - 1, inv = (float)(1.0 / D); a word above D reads as D)
 template <typename T>
 __global__ __launch_bounds__(256) void tiles_in_kernel(const T* __restrict__ src, int W, float* __restrict__ dst, int64_t tstride,
                                                        InTab tab, int cols, int th, int tw, int thp, int twp, int64_t total, int D,
                                                        float inv) {
-    constexpr uintptr_t MASK = sizeof(T) == 1 ? 3 : 7;     // a group is 12 (24) bytes: aligned iff its row's first sample is
     const int gw = twp >> 2;                               // groups per padded row (twp % 20 == 0)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / gw;                        // k * thp + y
@@ -53,40 +42,12 @@ __global__ __launch_bounds__(256) void tiles_in_kernel(const T* __restrict__ src
         const int sy = y < th ? y : 2 * th - 2 - y;        // padded row th + j reads row th - 2 - j of the tile
         const T* s = src + ((int64_t)(tab.y0[ti] + sy) * W + tab.x0[tj]) * 3;
         float v[3][4];
-        if (x + 4 <= tw && ((uintptr_t)s & MASK) == 0) {   // interior of an aligned row: 12 consecutive samples
-            if constexpr (sizeof(T) == 1) {
-                const uint32_t* p = reinterpret_cast<const uint32_t*>(s + x * 3);
-                const uint32_t w[3] = {p[0], p[1], p[2]};
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) v[c][q] = (float)byte_of(w, 3 * q + c);
-            } else {
-                const uint2* p = reinterpret_cast<const uint2*>(s + x * 3);
-                const uint2 w[3] = {p[0], p[1], p[2]};
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) v[c][q] = (float)min(half_of(w, 3 * q + c), D);
-            }
-        } else {                                           // unaligned rows, right edge and pad band: column tw + j reads tw - 2 - j
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int xx = x + q, sx = xx < tw ? xx : 2 * tw - 2 - xx;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c][q] = (float)min((int)s[sx * 3 + c], D);
-            }
-        }
+        ingest_group(s, x, tw, ((uintptr_t)s & GROUP_MASK<T>) == 0, D, v);     // spei_frames_u8_in's values of the tile's row
         float* d = dst + k * tstride + (int64_t)y * twp + x;
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             *reinterpret_cast<float4*>(d + (int64_t)c * thp * twp) = make_float4(v[c][0] * inv, v[c][1] * inv, v[c][2] * inv, v[c][3] * inv);
     }
-}
-
-__device__ __forceinline__ uint32_t quantise(float v, float Df) {
-    const float q = rintf(fminf(fmaxf(v * Df, 0.0f), Df));             // mul(D).clamp(0, D).round(): half to even, as torch
-    return isfinite(v) ? (uint32_t)q : 0u;
 }
 
 // the band of coordinate p: the number of inner bounds b[1 .. n-1] at or below it
@@ -97,6 +58,31 @@ __device__ __forceinline__ int band_of(const int (&b)[GRID_MAX + 1], int n, int 
     return r;
 }
 
+// the hard stitch of one group: pixels x .. x + 3 of row y, which lies in row band bi and whose first pixel lies in column band bj
+// -> their samples q[channel][pixel] from the tiles that own them, spei_frame_u8_out's values; returns nonzero iff one was not finite
+__device__ __forceinline__ int hard_stitch(const OutTab& tab, int y, int x, int bi, int bj, int W, int cols, int twp, int64_t plane,
+                                           float Df, uint32_t (&q)[3][4]) {
+    const int ry = y - tab.y0[bi];
+    const float* t = tab.tile[bi * cols + bj];
+    const int rx = x - tab.x0[bj];
+    if (x + 4 <= W && band_of(tab.xb, cols, x + 3) == bj && (rx & 3) == 0 && ((uintptr_t)t & 15) == 0)
+        return quantise_planes(t + (int64_t)ry * twp + rx, plane, Df, 4, q);     // four owned pixels of one tile, 16-byte aligned there
+    int bad = 0;                                           // a seam inside the group, an odd tile column or the frame's right edge
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int xx = x + k;
+        const int j = band_of(tab.xb, cols, xx);           // xx >= W: the last band, never read
+        const float* s = tab.tile[bi * cols + j] + (int64_t)ry * twp + (xx - tab.x0[j]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = xx < W ? s[c * plane] : 0.0f;
+            q[c][k] = quantise(v, Df);
+            bad |= isfinite(v) ? 0 : 1;
+        }
+    }
+    return bad;
+}
+
 // T = unsigned char (Df = 255) or uint16_t (Df = 2^depth - 1)
 template <typename T>
 __global__ __launch_bounds__(256) void tiles_out_kernel(OutTab tab, T* __restrict__ dst, int* __restrict__ nonfinite, int W, int rows,
@@ -104,66 +90,14 @@ __global__ __launch_bounds__(256) void tiles_out_kernel(OutTab tab, T* __restric
     int bad = 0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int y = (int)(i / gw), x = (int)(i - (int64_t)y * gw) * 4;
-        const int bi = band_of(tab.yb, rows, y), bj = band_of(tab.xb, cols, x);
-        const int ry = y - tab.y0[bi];
         uint32_t q[3][4];
-        const float* t = tab.tile[bi * cols + bj];
-        const int rx = x - tab.x0[bj];
-        if (x + 4 <= W && band_of(tab.xb, cols, x + 3) == bj && (rx & 3) == 0 && ((uintptr_t)t & 15) == 0) {
-            const float* s = t + (int64_t)ry * twp + rx;   // four owned pixels of one tile, 16-byte aligned there (twp % 4 == 0)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float4 f = *reinterpret_cast<const float4*>(s + c * plane);
-                const float e[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    q[c][k] = quantise(e[k], Df);
-                    bad |= isfinite(e[k]) ? 0 : 1;
-                }
-            }
-        } else {                                           // a seam inside the group, an odd tile column or the frame's right edge
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int xx = x + k;
-                const int j = band_of(tab.xb, cols, xx);   // xx >= W: the last band, never read
-                const float* s = tab.tile[bi * cols + j] + (int64_t)ry * twp + (xx - tab.x0[j]);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float v = xx < W ? s[c * plane] : 0.0f;
-                    q[c][k] = quantise(v, Df);
-                    bad |= isfinite(v) ? 0 : 1;
-                }
-            }
-        }
-        T* d = dst + ((int64_t)y * W + x) * 3;
-        if (vec_out && x + 4 <= W) {                       // 12 samples as three dwords (three 8-byte words)
-            if constexpr (sizeof(T) == 1) {
-                uint32_t w[3] = {0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < 12; ++j) w[j >> 2] |= q[j % 3][j / 3] << (8 * (j & 3));
-                uint32_t* p = reinterpret_cast<uint32_t*>(d);
-                p[0] = w[0]; p[1] = w[1]; p[2] = w[2];
-            } else {
-                uint32_t w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < 12; ++j) w[j >> 1] |= q[j % 3][j / 3] << (16 * (j & 1));
-                uint2* p = reinterpret_cast<uint2*>(d);
-                p[0] = make_uint2(w[0], w[1]); p[1] = make_uint2(w[2], w[3]); p[2] = make_uint2(w[4], w[5]);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (x + k < W)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) d[k * 3 + c] = (T)q[c][k];
-        }
+        bad |= hard_stitch(tab, y, x, band_of(tab.yb, rows, y), band_of(tab.xb, cols, x), W, cols, twp, plane, Df, q);
+        store_group(dst + ((int64_t)y * W + x) * 3, q, vec_out != 0, W - x);
     }
     if (nonfinite && bad) atomicOr(nonfinite, 1);           // rare: one atomic per thread that met a non-finite value
 }
 
 // ---- feathered seams ------------------------------------------------------------------------------------------------------------------
-constexpr int FEATHER_MAX = 200;
-
 // OutTab and, per axis, the half-width f[s] of the ramp of inner seam s = 1 .. n-1 (0: a hard seam) and r[s] = (float)(1 / (4 f[s]))
 struct BlendTab {
     OutTab t;
@@ -193,7 +127,7 @@ __device__ __forceinline__ int ramp_of(const int (&b)[GRID_MAX + 1], const int (
 __device__ __forceinline__ float ramp_weight(int p, int b, int f, float r) { return (float)(2 * (p - b + f) + 1) * r; }
 
 // tiles_out_kernel with ramps.  A group of four pixels whose row and columns meet no ramp (one test on wave-uniform operands, no table
-// lookups: 94 % of the groups at 2160p 2x5) runs tiles_out_kernel's body and gives its values.  Of the others, a group
+// lookups: 94 % of the groups at 2160p 2x5) runs hard_stitch, as tiles_out_kernel does, and gives its values.  Of the others, a group
 // that lies in one ramp and is aligned in both of its tiles (every ramp group of a plan whose seams and origins are multiples of 4, as
 // at 1080p and 2160p) loads 16 bytes per plane from each contributing tile; only a ramp's odd ends go pixel by pixel.  Rows are
 // uniform over (nearly) a wave, so a row ramp adds its loads to whole waves and a column ramp only to the groups it crosses.
@@ -206,36 +140,8 @@ __global__ __launch_bounds__(256) void tiles_blend_kernel(BlendTab tab, T* __res
         const int bi = band_of(tab.t.yb, rows, y), bj = band_of(tab.t.xb, cols, x);
         uint32_t q[3][4];
         if (!meets_ramp(tab.ylo, tab.yw, y) && !meets_ramp(tab.xlo, tab.xw, x + 3)) {
-            // the row in no row ramp, the four pixels in no column ramp: tiles_out_kernel's body, word for word
-            const int ry = y - tab.t.y0[bi];
-            const float* t = tab.t.tile[bi * cols + bj];
-            const int rx = x - tab.t.x0[bj];
-            if (x + 4 <= W && band_of(tab.t.xb, cols, x + 3) == bj && (rx & 3) == 0 && ((uintptr_t)t & 15) == 0) {
-                const float* s = t + (int64_t)ry * twp + rx;   // four owned pixels of one tile, 16-byte aligned there (twp % 4 == 0)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float4 f = *reinterpret_cast<const float4*>(s + c * plane);
-                    const float e[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        q[c][k] = quantise(e[k], Df);
-                        bad |= isfinite(e[k]) ? 0 : 1;
-                    }
-                }
-            } else {                                       // a hard seam inside the group, an odd tile column or the frame's right edge
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int xx = x + k;
-                    const int j = band_of(tab.t.xb, cols, xx); // xx >= W: the last band, never read
-                    const float* s = tab.t.tile[bi * cols + j] + (int64_t)ry * twp + (xx - tab.t.x0[j]);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float v = xx < W ? s[c * plane] : 0.0f;
-                        q[c][k] = quantise(v, Df);
-                        bad |= isfinite(v) ? 0 : 1;
-                    }
-                }
-            }
+            // the row in no row ramp, the four pixels in no column ramp: the hard stitch
+            bad |= hard_stitch(tab.t, y, x, bi, bj, W, cols, twp, plane, Df, q);
         } else {
             const int sy = ramp_of(tab.t.yb, tab.fy, rows, bi, y);
             const int ilo = sy ? sy - 1 : bi, ihi = sy ? sy : bi;                  // the low and the high tile row (one row outside a ramp)
@@ -253,7 +159,7 @@ __global__ __launch_bounds__(256) void tiles_blend_kernel(BlendTab tab, T* __res
             const float* gd = tab.t.tile[ihi * cols + ghi];
             if (x + 4 <= W && gx == ramp_of(tab.t.xb, tab.fx, cols, j3, x + 3) && (gx || j3 == bj) && ((glc | ghc) & 3) == 0 &&
                 (((uintptr_t)ga | (uintptr_t)gb | (uintptr_t)gc | (uintptr_t)gd) & 15) == 0) {
-                // four pixels with the same tiles, 16-byte aligned in each.  No ramp: tiles_out_kernel's loads and values.  A ramp: one
+                // four pixels with the same tiles, 16-byte aligned in each.  No ramp: the hard stitch's loads and values.  A ramp: one
                 // 16-byte load per plane and contributing tile, all of a plane's in flight before the first is used
                 float wx[4];
 #pragma unroll
@@ -333,28 +239,7 @@ __global__ __launch_bounds__(256) void tiles_blend_kernel(BlendTab tab, T* __res
                 }
             }
         }
-        T* d = dst + ((int64_t)y * W + x) * 3;
-        if (vec_out && x + 4 <= W) {                       // 12 samples as three dwords (three 8-byte words)
-            if constexpr (sizeof(T) == 1) {
-                uint32_t w[3] = {0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < 12; ++j) w[j >> 2] |= q[j % 3][j / 3] << (8 * (j & 3));
-                uint32_t* p = reinterpret_cast<uint32_t*>(d);
-                p[0] = w[0]; p[1] = w[1]; p[2] = w[2];
-            } else {
-                uint32_t w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < 12; ++j) w[j >> 1] |= q[j % 3][j / 3] << (16 * (j & 1));
-                uint2* p = reinterpret_cast<uint2*>(d);
-                p[0] = make_uint2(w[0], w[1]); p[1] = make_uint2(w[2], w[3]); p[2] = make_uint2(w[4], w[5]);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (x + k < W)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) d[k * 3 + c] = (T)q[c][k];
-        }
+        store_group(dst + ((int64_t)y * W + x) * 3, q, vec_out != 0, W - x);
     }
     if (nonfinite && bad) atomicOr(nonfinite, 1);           // rare: one atomic per thread that met a non-finite value
 }
@@ -372,8 +257,6 @@ inline int seam_half(const int* o, const int* b, int r, int t, int s, int feathe
     f = f < above ? f : above;
     return f > 0 ? f : 0;
 }
-
-inline int grid_for(int64_t total) { return (int)((total + 255) / 256 < BLOCKS_MAX ? (total + 255) / 256 : BLOCKS_MAX); }
 
 template <typename T>
 int tiles_in(const char* name, const T* src, int H, int W, float* dst, int64_t tile_stride, const int* y0, const int* x0, int rows,
@@ -410,9 +293,10 @@ int tiles_in(const char* name, const T* src, int H, int W, float* dst, int64_t t
     return 0;
 }
 
+// what the hard and the feathered stitch share on the host: the checks of a call, and its tables as the kernels take them
 template <typename T>
-int tiles_out(const char* name, const float* const* tiles, T* dst, int* nonfinite, int H, int W, const int* y0, const int* x0,
-              const int* yb, const int* xb, int rows, int cols, int thp, int twp, int depth, hipStream_t stream) {
+int out_table(const char* name, const float* const* tiles, const T* dst, int H, int W, const int* y0, const int* x0, const int* yb,
+              const int* xb, int rows, int cols, int thp, int twp, int depth, OutTab& tab) {
     SPEI_REQUIRE(tiles && dst && y0 && x0 && yb && xb, "%s: null pointer", name);
     SPEI_REQUIRE(H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
     SPEI_REQUIRE(rows >= 1 && rows <= GRID_MAX && cols >= 1 && cols <= GRID_MAX, "%s: a grid of %dx%d tiles (1..%d rows and columns)",
@@ -421,7 +305,6 @@ int tiles_out(const char* name, const float* const* tiles, T* dst, int* nonfinit
                  "multiple of 4)", name, thp, twp);
     SPEI_REQUIRE(sizeof(T) == 1 || depth == 10 || depth == 12, "%s: unknown depth %d (10 or 12)", name, depth);
     SPEI_REQUIRE(((uintptr_t)dst & (sizeof(T) - 1)) == 0, "%s: dst must be %d-byte aligned", name, (int)sizeof(T));
-    OutTab tab = {};
     SPEI_REQUIRE(yb[0] == 0 && yb[rows] == H && xb[0] == 0 && xb[cols] == W, "%s: the bands must span the %dx%d frame (rows %d..%d, "
                  "columns %d..%d)", name, H, W, yb[0], yb[rows], xb[0], xb[cols]);
     for (int i = 0; i < rows; ++i) {
@@ -444,59 +327,45 @@ int tiles_out(const char* name, const float* const* tiles, T* dst, int* nonfinit
         SPEI_REQUIRE(tiles[k] && ((uintptr_t)tiles[k] & 3) == 0, "%s: tile %d is a null or misaligned pointer", name, k);
         tab.tile[k] = tiles[k];
     }
+    return 0;
+}
+
+// the one launch of an egress call: tiles_out_kernel on an OutTab or tiles_blend_kernel on a BlendTab
+template <typename T, typename Tab>
+int launch_out(const char* name, void (*kernel)(Tab, T*, int*, int, int, int, int, int64_t, int, int64_t, int, float), const Tab& tab,
+               T* dst, int* nonfinite, int H, int W, int rows, int cols, int thp, int twp, int depth, hipStream_t stream) {
     const int gw = (W + 3) / 4;
-    const int vec_out = (W & 3) == 0 && ((uintptr_t)dst & (sizeof(T) == 1 ? 3 : 7)) == 0;
+    const int vec_out = (W & 3) == 0 && ((uintptr_t)dst & GROUP_MASK<T>) == 0;
     const int64_t total = (int64_t)H * gw;
     if (nonfinite && hipMemsetAsync(nonfinite, 0, sizeof(int), stream) != hipSuccess) {
         spei_set_error("%s: clearing the non-finite flag failed", name);
         return -2;
     }
-    hipLaunchKernelGGL(tiles_out_kernel<T>, dim3(grid_for(total)), dim3(256), 0, stream, tab, dst, nonfinite, W, rows, cols, twp,
-                       (int64_t)thp * twp, gw, total, vec_out, sizeof(T) == 1 ? 255.0f : (float)((1 << depth) - 1));
+    hipLaunchKernelGGL(kernel, dim3(grid_for(total)), dim3(256), 0, stream, tab, dst, nonfinite, W, rows, cols, twp, (int64_t)thp * twp, gw,
+                       total, vec_out, sizeof(T) == 1 ? 255.0f : (float)((1 << depth) - 1));
     SPEI_CHECK_LAUNCH(name);
     return 0;
 }
 
-// tiles_out's checks (stated again: that path stays as it is), then the real tile size and the feather
+template <typename T>
+int tiles_out(const char* name, const float* const* tiles, T* dst, int* nonfinite, int H, int W, const int* y0, const int* x0,
+              const int* yb, const int* xb, int rows, int cols, int thp, int twp, int depth, hipStream_t stream) {
+    OutTab tab = {};
+    if (out_table(name, tiles, dst, H, W, y0, x0, yb, xb, rows, cols, thp, twp, depth, tab)) return -1;
+    return launch_out(name, tiles_out_kernel<T>, tab, dst, nonfinite, H, W, rows, cols, thp, twp, depth, stream);
+}
+
+// the hard stitch's call, and with it the real tile size and the feather, which place the ramps
 template <typename T>
 int tiles_blend(const char* name, const float* const* tiles, T* dst, int* nonfinite, int H, int W, const int* y0, const int* x0,
                 const int* yb, const int* xb, int rows, int cols, int thp, int twp, int th, int tw, int feather, int depth,
                 hipStream_t stream) {
-    SPEI_REQUIRE(tiles && dst && y0 && x0 && yb && xb, "%s: null pointer", name);
-    SPEI_REQUIRE(H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
-    SPEI_REQUIRE(rows >= 1 && rows <= GRID_MAX && cols >= 1 && cols <= GRID_MAX, "%s: a grid of %dx%d tiles (1..%d rows and columns)",
-                 name, rows, cols, GRID_MAX);
-    SPEI_REQUIRE(thp > 0 && twp > 0 && (twp & 3) == 0 && (int64_t)thp * twp < (1ll << 30), "%s: bad tile planes %dx%d (the width a "
-                 "multiple of 4)", name, thp, twp);
+    BlendTab tab = {};
+    if (out_table(name, tiles, dst, H, W, y0, x0, yb, xb, rows, cols, thp, twp, depth, tab.t)) return -1;
     SPEI_REQUIRE(th > 0 && tw > 0 && th <= H && tw <= W, "%s: a %dx%d tile does not fit a %dx%d frame", name, th, tw, H, W);
     SPEI_REQUIRE(thp == (th + MULT - 1) / MULT * MULT && twp == (tw + MULT - 1) / MULT * MULT, "%s: tile planes %dx%d are not the %dx%d "
                  "tile rounded up to multiples of %d", name, thp, twp, th, tw, MULT);
     SPEI_REQUIRE(feather >= 0 && feather <= FEATHER_MAX, "%s: feather %d (0..%d)", name, feather, FEATHER_MAX);
-    SPEI_REQUIRE(sizeof(T) == 1 || depth == 10 || depth == 12, "%s: unknown depth %d (10 or 12)", name, depth);
-    SPEI_REQUIRE(((uintptr_t)dst & (sizeof(T) - 1)) == 0, "%s: dst must be %d-byte aligned", name, (int)sizeof(T));
-    BlendTab tab = {};
-    SPEI_REQUIRE(yb[0] == 0 && yb[rows] == H && xb[0] == 0 && xb[cols] == W, "%s: the bands must span the %dx%d frame (rows %d..%d, "
-                 "columns %d..%d)", name, H, W, yb[0], yb[rows], xb[0], xb[cols]);
-    for (int i = 0; i < rows; ++i) {
-        SPEI_REQUIRE(yb[i] < yb[i + 1], "%s: row band %d is empty or reversed (%d..%d)", name, i, yb[i], yb[i + 1]);
-        SPEI_REQUIRE(y0[i] >= 0 && y0[i] < H, "%s: tile row %d at y %d lies outside the %dx%d frame", name, i, y0[i], H, W);
-        SPEI_REQUIRE(y0[i] <= yb[i] && yb[i + 1] - y0[i] <= thp, "%s: row band %d (%d..%d) lies outside its tile (%d..%d)", name, i, yb[i],
-                     yb[i + 1], y0[i], y0[i] + thp);
-        tab.t.y0[i] = y0[i];
-    }
-    for (int j = 0; j < cols; ++j) {
-        SPEI_REQUIRE(xb[j] < xb[j + 1], "%s: column band %d is empty or reversed (%d..%d)", name, j, xb[j], xb[j + 1]);
-        SPEI_REQUIRE(x0[j] >= 0 && x0[j] < W, "%s: tile column %d at x %d lies outside the %dx%d frame", name, j, x0[j], H, W);
-        SPEI_REQUIRE(x0[j] <= xb[j] && xb[j + 1] - x0[j] <= twp, "%s: column band %d (%d..%d) lies outside its tile (%d..%d)", name, j,
-                     xb[j], xb[j + 1], x0[j], x0[j] + twp);
-        tab.t.x0[j] = x0[j];
-    }
-    for (int i = 0; i <= rows; ++i) tab.t.yb[i] = yb[i];
-    for (int j = 0; j <= cols; ++j) tab.t.xb[j] = xb[j];
-    for (int k = 0; k < rows * cols; ++k) {
-        SPEI_REQUIRE(tiles[k] && ((uintptr_t)tiles[k] & 3) == 0, "%s: tile %d is a null or misaligned pointer", name, k);
-        tab.t.tile[k] = tiles[k];
-    }
     // every ramp [b - f, b + f) lies in rows (columns) [0, th) ([0, tw)) of both of its tiles by seam_half's clip
     for (int s = 1; s < rows; ++s) {
         tab.fy[s] = seam_half(y0, yb, rows, th, s, feather);
@@ -510,17 +379,7 @@ int tiles_blend(const char* name, const float* const* tiles, T* dst, int* nonfin
         tab.xlo[s] = xb[s] - tab.fx[s];
         tab.xw[s] = tab.fx[s] ? 2 * tab.fx[s] + 3 : 0;     // a group [x, x + 3] meets the ramp iff 0 <= x + 3 - xlo < 2 f + 3
     }
-    const int gw = (W + 3) / 4;
-    const int vec_out = (W & 3) == 0 && ((uintptr_t)dst & (sizeof(T) == 1 ? 3 : 7)) == 0;
-    const int64_t total = (int64_t)H * gw;
-    if (nonfinite && hipMemsetAsync(nonfinite, 0, sizeof(int), stream) != hipSuccess) {
-        spei_set_error("%s: clearing the non-finite flag failed", name);
-        return -2;
-    }
-    hipLaunchKernelGGL(tiles_blend_kernel<T>, dim3(grid_for(total)), dim3(256), 0, stream, tab, dst, nonfinite, W, rows, cols, twp,
-                       (int64_t)thp * twp, gw, total, vec_out, sizeof(T) == 1 ? 255.0f : (float)((1 << depth) - 1));
-    SPEI_CHECK_LAUNCH(name);
-    return 0;
+    return launch_out(name, tiles_blend_kernel<T>, tab, dst, nonfinite, H, W, rows, cols, thp, twp, depth, stream);
 }
 
 }  // namespace

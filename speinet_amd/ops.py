@@ -212,16 +212,15 @@ def padded_size(n: int) -> int:
     return -(-n // 20) * 20
 
 
-def frames_u8_in(u8: torch.Tensor, out: Optional[torch.Tensor] = None, gray: bool = False, planes: bool = True):
-    """uint8 frames [N,H,W,3] (or one [H,W,3]; each frame packed, any frame stride) on the device -> (fp32 [N,3,Hp,Wp] reflect-padded
-    to multiples of 20 with `numpy2tensor`'s values, or None when not `planes`; the detector's gray plane [N,H,W], or None when not
-    `gray`).  `out` (optional): the planes' destination, contiguous, N*3*Hp*Wp floats.  One launch on the current stream (csrc/frame_io.hip)."""
-    assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() in (3, 4) and (planes or gray)
-    fr = u8 if u8.dim() == 4 else u8.unsqueeze(0)
+def _frames_in(fr: torch.Tensor, dtype, depth: Optional[int], out: Optional[torch.Tensor], gray: bool, planes: bool):
+    """`frames_u8_in` (`depth` None) and `frames_u16_in` on frames of `dtype`."""
+    assert fr.is_cuda and fr.dtype == dtype and fr.dim() in (3, 4) and (planes or gray)
+    if fr.dim() == 3:
+        fr = fr.unsqueeze(0)
     n, h, w, c = fr.shape
     assert c == 3 and fr.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
     hp, wp = padded_size(h), padded_size(w)
-    dev = u8.device
+    dev = fr.device
     if planes:
         if out is None:
             out = torch.empty(n, 3, hp, wp, device=dev)
@@ -230,11 +229,38 @@ def frames_u8_in(u8: torch.Tensor, out: Optional[torch.Tensor] = None, gray: boo
         out = None
     g = torch.empty(n, h, w, device=dev) if gray else None
     lib = _lib.lib()
+    name = "spei_frames_u8_in" if depth is None else "spei_frames_u16_in"
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_frames_u8_in(_vp(fr.data_ptr()), fr.stride(0), _vp(out.data_ptr() if out is not None else 0),
-                                         _vp(g.data_ptr() if g is not None else 0), n, h, w, st), "spei_frames_u8_in")
+        _lib.check(getattr(lib, name)(_vp(fr.data_ptr()), fr.element_size() * fr.stride(0), _vp(out.data_ptr() if out is not None else 0),
+                                      _vp(g.data_ptr() if g is not None else 0), n, h, w, *(() if depth is None else (depth,)), st), name)
     return out, g
+
+
+def frames_u8_in(u8: torch.Tensor, out: Optional[torch.Tensor] = None, gray: bool = False, planes: bool = True):
+    """uint8 frames [N,H,W,3] (or one [H,W,3]; each frame packed, any frame stride) on the device -> (fp32 [N,3,Hp,Wp] reflect-padded
+    to multiples of 20 with `numpy2tensor`'s values, or None when not `planes`; the detector's gray plane [N,H,W], or None when not
+    `gray`).  `out` (optional): the planes' destination, contiguous, N*3*Hp*Wp floats.  One launch on the current stream (csrc/frame_io.hip)."""
+    return _frames_in(u8, torch.uint8, None, out, gray, planes)
+
+
+def _pair_stats(fr: torch.Tensor, dtype, depth: Optional[int], prev: Optional[torch.Tensor]):
+    """`frame_pair_stats` (`depth` None) and `frame_pair_stats_u16` on frames of `dtype`."""
+    assert fr.is_cuda and fr.dtype == dtype and fr.dim() == 4
+    n, h, w, c = fr.shape
+    assert c == 3 and fr.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
+    dev = fr.device
+    assert prev is None or (prev.device == dev and prev.dtype == dtype and tuple(prev.shape) == (h, w, 3) and prev.is_contiguous())
+    pairs = n if prev is not None else n - 1
+    hist = torch.empty(n, 64, dtype=torch.int32, device=dev)
+    sad = torch.empty(pairs, dtype=torch.int64, device=dev)
+    lib = _lib.lib()
+    name = "spei_frame_pair_stats" if depth is None else "spei_frame_pair_stats_u16"
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(getattr(lib, name)(_vp(fr.data_ptr()), fr.element_size() * fr.stride(0), _vp(prev.data_ptr() if prev is not None else 0),
+                                      n, h, w, *(() if depth is None else (depth,)), _vp(hist.data_ptr()), _vp(sad.data_ptr()), st), name)
+    return sad, hist.long()
 
 
 def frame_pair_stats(u8: torch.Tensor, prev: Optional[torch.Tensor] = None):
@@ -242,20 +268,7 @@ def frame_pair_stats(u8: torch.Tensor, prev: Optional[torch.Tensor] = None):
     packed frame `prev` [H,W,3] before them, on the integer luma Y = (77 R + 150 G + 29 B + 128) >> 8 (csrc/frame_io.hip) ->
     (sad int64 [N-1], or [N] with `prev` (pair 0 is then (prev, frame 0)): the sum over pixels of |Y_a - Y_b| per consecutive pair;
     hist int64 [N,64]: pixels per value of Y >> 2).  Exact integers.  One launch on the current stream, no host sync."""
-    assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4
-    n, h, w, c = u8.shape
-    assert c == 3 and u8.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
-    dev = u8.device
-    assert prev is None or (prev.device == dev and prev.dtype == torch.uint8 and tuple(prev.shape) == (h, w, 3) and prev.is_contiguous())
-    pairs = n if prev is not None else n - 1
-    hist = torch.empty(n, 64, dtype=torch.int32, device=dev)
-    sad = torch.empty(pairs, dtype=torch.int64, device=dev)
-    lib = _lib.lib()
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_frame_pair_stats(_vp(u8.data_ptr()), u8.stride(0), _vp(prev.data_ptr() if prev is not None else 0), n, h, w,
-                                             _vp(hist.data_ptr()), _vp(sad.data_ptr()), st), "spei_frame_pair_stats")
-    return sad, hist.long()
+    return _pair_stats(u8, torch.uint8, None, prev)
 
 
 def _depth(depth: int) -> int:
@@ -269,48 +282,14 @@ def frames_u16_in(u16: torch.Tensor, depth: int, out: Optional[torch.Tensor] = N
     D = 2^depth - 1 (a word above D reads as D) -> (fp32 [N,3,Hp,Wp] = v * float32(1 / D), reflect-padded, or None when not `planes`;
     the detector's gray plane [N,H,W] of the frames as fp32 v * float32(255 / D), or None when not `gray`).  One launch on the
     current stream (csrc/frame_io.hip)."""
-    assert u16.is_cuda and u16.dtype == torch.uint16 and u16.dim() in (3, 4) and (planes or gray)
-    depth = _depth(depth)
-    fr = u16 if u16.dim() == 4 else u16.unsqueeze(0)
-    n, h, w, c = fr.shape
-    assert c == 3 and fr.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
-    hp, wp = padded_size(h), padded_size(w)
-    dev = u16.device
-    if planes:
-        if out is None:
-            out = torch.empty(n, 3, hp, wp, device=dev)
-        assert out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * 3 * hp * wp
-    else:
-        out = None
-    g = torch.empty(n, h, w, device=dev) if gray else None
-    lib = _lib.lib()
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_frames_u16_in(_vp(fr.data_ptr()), 2 * fr.stride(0), _vp(out.data_ptr() if out is not None else 0),
-                                          _vp(g.data_ptr() if g is not None else 0), n, h, w, depth, st), "spei_frames_u16_in")
-    return out, g
+    return _frames_in(u16, torch.uint16, _depth(depth), out, gray, planes)
 
 
 def frame_pair_stats_u16(u16: torch.Tensor, depth: int, prev: Optional[torch.Tensor] = None):
     """`frame_pair_stats` for deep frames: uint16 [N,H,W,3] of `depth` 10 or 12 bits (and optionally the packed frame `prev` before
     them), on the depth-bit luma Yd = (77 R + 150 G + 29 B + 128) >> 8 -> (sad int64 over Yd, 2^(depth-8) times the 8-bit unit;
     hist int64 [N,64]: pixels per value of Yd >> (depth - 6)).  Exact integers.  One launch on the current stream, no host sync."""
-    assert u16.is_cuda and u16.dtype == torch.uint16 and u16.dim() == 4
-    depth = _depth(depth)
-    n, h, w, c = u16.shape
-    assert c == 3 and u16.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
-    dev = u16.device
-    assert prev is None or (prev.device == dev and prev.dtype == torch.uint16 and tuple(prev.shape) == (h, w, 3) and prev.is_contiguous())
-    pairs = n if prev is not None else n - 1
-    hist = torch.empty(n, 64, dtype=torch.int32, device=dev)
-    sad = torch.empty(pairs, dtype=torch.int64, device=dev)
-    lib = _lib.lib()
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_frame_pair_stats_u16(_vp(u16.data_ptr()), 2 * u16.stride(0), _vp(prev.data_ptr() if prev is not None else 0),
-                                                 n, h, w, depth, _vp(hist.data_ptr()), _vp(sad.data_ptr()), st),
-                   "spei_frame_pair_stats_u16")
-    return sad, hist.long()
+    return _pair_stats(u16, torch.uint16, _depth(depth), prev)
 
 
 def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: Optional[torch.Tensor] = None,
@@ -367,23 +346,30 @@ def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: 
     return blur, gt, g
 
 
+def _frame_out(x: torch.Tensor, h: int, w: int, depth: Optional[int], out: Optional[torch.Tensor], nonfinite: Optional[torch.Tensor]):
+    """`frame_u8_out` (`depth` None) and `frame_u16_out`."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 3 and x.is_contiguous()
+    dtype = torch.uint8 if depth is None else torch.uint16
+    hp, wp = x.shape[1:]
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=dtype, device=x.device)
+    assert out.device == x.device and out.dtype == dtype and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
+    assert nonfinite is None or (nonfinite.device == x.device and nonfinite.dtype == torch.int32 and nonfinite.numel() >= 1)
+    lib = _lib.lib()
+    name = "spei_frame_u8_out" if depth is None else "spei_frame_u16_out"
+    with torch.cuda.device(x.device):
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(getattr(lib, name)(_vp(x.data_ptr()), _vp(out.data_ptr()), _vp(nonfinite.data_ptr() if nonfinite is not None else 0),
+                                      h, w, hp, wp, *(() if depth is None else (depth,)), st), name)
+    return out
+
+
 def frame_u8_out(x: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None,
                  nonfinite: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 [3,Hp,Wp] on the device -> its top-left h x w crop as uint8 [h,w,3] (`tensor2numpy`'s values, 0 for a non-finite value).
     `out` (optional): a packed uint8 [h,w,3] destination.  `nonfinite` (optional): an int32 device tensor whose first element becomes
     nonzero iff the crop held a NaN or an infinity.  Launches on the current stream (csrc/frame_io.hip), no host sync."""
-    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 3 and x.is_contiguous()
-    hp, wp = x.shape[1:]
-    if out is None:
-        out = torch.empty(h, w, 3, dtype=torch.uint8, device=x.device)
-    assert out.device == x.device and out.dtype == torch.uint8 and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
-    assert nonfinite is None or (nonfinite.device == x.device and nonfinite.dtype == torch.int32 and nonfinite.numel() >= 1)
-    lib = _lib.lib()
-    with torch.cuda.device(x.device):
-        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(lib.spei_frame_u8_out(_vp(x.data_ptr()), _vp(out.data_ptr()), _vp(nonfinite.data_ptr() if nonfinite is not None else 0),
-                                         h, w, hp, wp, st), "spei_frame_u8_out")
-    return out
+    return _frame_out(x, h, w, None, out, nonfinite)
 
 
 def frame_u16_out(x: torch.Tensor, h: int, w: int, depth: int, out: Optional[torch.Tensor] = None,
@@ -391,19 +377,7 @@ def frame_u16_out(x: torch.Tensor, h: int, w: int, depth: int, out: Optional[tor
     """`frame_u8_out` for deep frames: fp32 [3,Hp,Wp] on the device -> its top-left h x w crop as uint16 [h,w,3] of `depth` 10 or 12
     bits, round_half_even(clamp(x * D, 0, D)) with D = 2^depth - 1, 0 for a non-finite value.  `out` (optional): a packed uint16
     [h,w,3] destination.  `nonfinite`: as in `frame_u8_out`.  Launches on the current stream (csrc/frame_io.hip), no host sync."""
-    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 3 and x.is_contiguous()
-    depth = _depth(depth)
-    hp, wp = x.shape[1:]
-    if out is None:
-        out = torch.empty(h, w, 3, dtype=torch.uint16, device=x.device)
-    assert out.device == x.device and out.dtype == torch.uint16 and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
-    assert nonfinite is None or (nonfinite.device == x.device and nonfinite.dtype == torch.int32 and nonfinite.numel() >= 1)
-    lib = _lib.lib()
-    with torch.cuda.device(x.device):
-        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(lib.spei_frame_u16_out(_vp(x.data_ptr()), _vp(out.data_ptr()), _vp(nonfinite.data_ptr() if nonfinite is not None else 0),
-                                          h, w, hp, wp, depth, st), "spei_frame_u16_out")
-    return out
+    return _frame_out(x, h, w, _depth(depth), out, nonfinite)
 
 
 def _int_table(values, n: int, what: str):

@@ -162,6 +162,39 @@ def test_edge_band_clips_the_ramp():
     assert ((ref["lo"] <= g) & (g <= ref["hi"])).all()
 
 
+@pytest.mark.parametrize("depth", [8, 10, 12])
+def test_egress_paths_agree(depth):
+    """The four ways out of the model's planes share one rounding, one non-finite rule and one store (csrc/pixel_group.h): on a 37x53
+    frame in planes of 40x60 the hard stitch of a 1x1 plan, the feathered stitch of the same plan (no seam, so no ramp) and the ROI
+    paste of the whole frame give the frame egress's frame and flag, with non-finite values inside the crop and, unseen, in the pad."""
+    h, w, hp, wp = 37, 53, 40, 60
+    hard = T.tile_plan(h, w, (1, 1))
+    assert (hard.th, hard.tw, hard.padded, hard.y0, hard.x0, hard.yb, hard.xb) == (h, w, (hp, wp), (0,), (0,), (0, h), (0, w))
+    soft = dataclasses.replace(hard, feather=20)
+    dtype = torch.uint8 if depth == 8 else torch.uint16
+    x = np.random.default_rng(3753 + depth).uniform(-0.1, 1.1, (3, hp, wp)).astype(np.float32)
+    x[1, 38, 10] = np.nan                                                         # the pad: a row below the crop,
+    x[0, 5, 53] = np.nan                                                          # and a column of the crop's last group of four
+    frame = torch.full((h, w, 3), 77, dtype=torch.uint8, device=DEV)              # the paste's input frame: every pixel replaced
+    for bad in (True, False):
+        xs = x.copy()
+        if bad:
+            xs[0, 5, 7], xs[2, 36, 52] = np.nan, np.inf                           # inside the crop, the second in its last row and column
+        planes = torch.from_numpy(xs).to(DEV)
+        flag = torch.full((1,), 7, dtype=torch.int32, device=DEV)
+        want = (ops.frame_u8_out(planes, h, w, nonfinite=flag) if depth == 8 else ops.frame_u16_out(planes, h, w, depth, nonfinite=flag))
+        want, want_flag = want.cpu().numpy(), int(flag.item())
+        assert want.dtype == (np.uint8 if depth == 8 else np.uint16) and (want_flag != 0) == bad
+        assert len(np.unique(want)) > 200 and (not bad or (want[5, 7, 0] == 0 and want[36, 52, 2] == 0))
+        for name, call in (("tiles_out, hard", lambda f: ops.tiles_out([planes], hard, depth, nonfinite=f)),
+                           ("tiles_out, feather 20", lambda f: ops.tiles_out([planes], soft, depth, nonfinite=f)),
+                           ("roi_paste", lambda f: ops.roi_paste(planes, frame, (0, 0, h, w), depth, nonfinite=f))):
+            flag.fill_(7)
+            got = call(flag)
+            assert got.dtype == dtype and np.array_equal(got.cpu().numpy(), want), (name, bad)
+            assert (int(flag.item()) != 0) == (want_flag != 0), (name, bad)
+
+
 def test_bad_arguments():
     """Refused through the C-ABI before anything is launched: the flag is not cleared, the frame not written."""
     plan = HAND
