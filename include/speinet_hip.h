@@ -835,6 +835,53 @@ int spei_train_batch_runs_noise_u8(const spei_run_record* table, const spei_run_
                                    const spei_noise_record* noise, const spei_noise_record* noise_host, uint32_t key0, uint32_t key1,
                                    float* input, float* gt, int P, float rgb_range, spei_stream_t stream);
 
+/* ---- camera-shake blur in blur synthesis (speinet_amd/shake.py; an extension beyond the reference) ---- */
+
+/* The blur a hand-held camera adds inside one exposure: the run's linear mean is correlated with a point-spread function (PSF) before
+ * the noise and the encode, in integer arithmetic.  Lm(y, x, c) is the linear mean defined above, floor(sum of lin[byte] / n), at pixel
+ * (y, x) of the FULL source frame [H][W].  A PSF is w[dy][dx], -r <= dy, dx <= r, radius r in 0..16: unsigned Q16 weights that sum to
+ * exactly 65536.
+ *   Lb(y, x, c) = (sum over dy, dx of w[dy][dx] Lm(clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1), c) + 2^15) >> 16
+ *   The sum is exact (below 2^40 + 2^15: a 64-bit accumulator).  A correlation, not a flipped convolution: the weight at (dy, dx)
+ *   multiplies the pixel dy rows below and dx columns to the right.  Coordinates clamp to the FRAME, never to a crop: the halo of a
+ *   training crop reads the real neighbours outside the crop.  r = 0 (the delta PSF) gives Lb = Lm: the light / noise entry's bytes.
+ * Without noise blur = encode(Lb).  With noise the formulas above run on Lb with the variance generalised — the PSF averages noise
+ * away too: X = A Lb + B, q16 = floor(sum of w^2 / 2^16) (at most 65536),
+ *   V = X - ceil(X q16 / (n 2^16))       (64-bit; X q16 < 2^61)
+ *   which for the delta PSF (q16 = 65536) is floor(X (n - 1) / n), the V above.  sigma, z, d, L', the counter (x, y, run, clip) of the
+ *   OUTPUT pixel in its full frame and encode are unchanged.  The gray plane is that of the final encoded bytes; a zero record stays zero.
+ * `psfs` on the device and `psfs_host` the same words in HOST memory are n_psf tables of uint32 [33][33], centre at [16][16]: entry
+ * [16 + dy][16 + dx] holds w[dy][dx].  One spei_shake_record per run / per table record: a record with radius == 0 ignores `psf` and
+ * must carry q16 == 65536 (ground-truth records are such records).  Checked on the host copies before anything is launched, beside
+ * every check of the light and noise entries: radius <= 16, psf < n_psf, every weight outside the radius 0, the sum 65536, q16 as
+ * defined, reserved == 0; a bad record is an error that names the record.  psfs / psfs_host may be NULL when n_psf == 0.
+ * sizeof(spei_shake_record) == 16. */
+typedef struct {
+    uint32_t psf;      /* index of the record's table in psfs */
+    uint32_t radius;   /* 0..16; 0: the delta, no table is read */
+    uint32_t q16;      /* floor(sum of w^2 / 2^16); 65536 for radius 0 */
+    uint32_t reserved; /* 0 */
+} spei_shake_record;
+
+/* spei_window_mean_noise_u8 with shake: shake / shake_host hold M records, one per run.  gauss == NULL: no noise — gauss_host, noise,
+ * noise_host and the keys are ignored and blur = encode(Lb).  With every record at radius 0 this is spei_window_mean_noise_u8's (or,
+ * gauss == NULL, spei_window_mean_light_u8's) launch. */
+int spei_window_mean_shake_u8(const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
+                              const uint32_t* tables, const uint32_t* tables_host, const int32_t* gauss, const int32_t* gauss_host,
+                              const spei_noise_record* noise, const spei_noise_record* noise_host, uint32_t key0, uint32_t key1,
+                              const uint32_t* psfs, const uint32_t* psfs_host, int n_psf, const spei_shake_record* shake,
+                              const spei_shake_record* shake_host, unsigned char* blur, unsigned char* gt, float* gray, int H, int W,
+                              spei_stream_t stream);
+
+/* spei_train_batch_runs_noise_u8 with shake: shake / shake_host hold n_in + n_gt records, one per record of the table; the halo of a
+ * rectangle is read from the record's frame [H][W], clamped at the frame's edges.  gauss == NULL and all-radius-0 tables as above. */
+int spei_train_batch_runs_shake_u8(const spei_run_record* table, const spei_run_record* table_host, int n_in, int n_gt,
+                                   const uint32_t* tables, const uint32_t* tables_host, const int32_t* gauss, const int32_t* gauss_host,
+                                   const spei_noise_record* noise, const spei_noise_record* noise_host, uint32_t key0, uint32_t key1,
+                                   const uint32_t* psfs, const uint32_t* psfs_host, int n_psf, const spei_shake_record* shake,
+                                   const spei_shake_record* shake_host, float* input, float* gt, int P, float rgb_range,
+                                   spei_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

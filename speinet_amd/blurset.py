@@ -4,7 +4,7 @@ middle frame is the ground truth (reference LD_detector/mix_choice_dataset.py:46
 38-76).
 
     python -m speinet_amd.blurset --input <dir of clip folders> --output <dir> [--ratio 0.1 0.3 0.5] [--threshold 5] [--seed N]
-                                  [--light code|srgb|gamma:<g>] [--noise <shot>:<read>]
+                                  [--light code|srgb|gamma:<g>] [--noise <shot>:<read>] [--shake <len>|<lo>..<hi>] [--frames runs|single]
 
 writes `<output>/blur/<clip>/<i>.png`, `<output>/gt/<clip>/<i>.png` and `<output>/label/<clip>.npy`: the layout `data.ClipSet`,
 `speinet_amd.fit` and `python -m speinet_amd.detector fit` read.  The frame files are numbered with six digits: the loaders pair
@@ -13,9 +13,15 @@ frames and labels by sorted file name (as the reference's do, data/videodata_nfs
 linear light instead, as an exposure does: speinet_amd.light has the integer arithmetic; the ground truth, labels and layout are the same.
 `--noise <shot>:<read>` (with a linear `--light`; each side a number or `lo..hi`, drawn log-uniformly per clip) adds back the sensor
 noise that averaging removed — shot coefficient and read deviation at full scale 1, speinet_amd.light has the contract.  The levels
-are not fitted to any camera.
+are not fitted to any camera.  `--shake <len>` or `<lo>..<hi>` (with a linear `--light`; the blur extent in pixels, 2..30) correlates
+every frame labelled blurry with a random camera-shake trajectory PSF of its own, in linear light before the noise — the blur a
+hand-held camera adds inside one exposure; speinet_amd.shake has the contract.  `--frames single` is the mode for ordinary 24 / 30 fps
+footage, where averaging runs gives ghost copies, not motion blur: every source frame is its own output frame, steady (label 1) with
+probability `--ratio` and shaken otherwise; it needs `--shake`.  One PSF per frame, drawn independently (no camera path across
+frames); extents and trajectory constants are not fitted to any camera.
 
   * `plan_runs`   — the reference's draw sequence on a `random.Random` of the caller's (no global state): runs and labels;
+  * `plan_single` — `--frames single`: one run of length 1 per source frame, its label drawn on the caller's `random.Random`;
   * `plan_dataset` — that sequence for every clip of a directory on one `random.Random(seed)` (also data.SharpClipSet's, per epoch);
   * `synthesize`  — the averaging on the GPU (csrc/blurset.hip, one launch per chunk of the clip): frames cross PCIe once as uint8,
                     device memory is bounded by the chunk;
@@ -34,6 +40,7 @@ import torch
 
 from . import light as _light
 from . import ops
+from . import shake as _shake
 from .video import IMAGE_EXTS, HostRing, _imwrite, frames_of
 
 MAX_RUN = 15                     # spei_window_mean_u8's longest run
@@ -75,6 +82,20 @@ def plan_runs(n_frames: int, ratio: float, threshold: int = 5, window_range=(1, 
     return np.asarray(starts, np.int64), np.asarray(lengths, np.int64), np.asarray(labels, np.int64)
 
 
+def plan_single(n_frames: int, ratio: float, rng: random.Random = None):
+    """The plan of ordinary-frame-rate footage (`frames="single"`): every source frame is its own run of length 1, labelled
+    `int(rng.random() < ratio)` in frame order — 1 steady, 0 shaken (speinet_amd.shake) — on the caller's `random.Random`, as
+    `plan_runs` draws its labels.  -> (starts, lengths, labels) int64 arrays."""
+    if ratio is None or not 0 <= ratio <= 1:
+        raise ValueError(f"ratio {ratio} must lie in [0, 1]")
+    if n_frames < 1:
+        raise ValueError(f"a clip needs at least one frame; got {n_frames}")
+    if rng is None:
+        raise ValueError("pass a random.Random (plan_single touches no global random state)")
+    labels = [int(rng.random() < ratio) for _ in range(n_frames)]
+    return np.arange(n_frames, dtype=np.int64), np.ones(n_frames, np.int64), np.asarray(labels, np.int64)
+
+
 def _chunks(starts, lengths, chunk_frames: int):
     """Consecutive runs grouped so that each group reads at most chunk_frames source frames: (first run, last run + 1, lo, hi)."""
     i, M = 0, len(starts)
@@ -87,7 +108,8 @@ def _chunks(starts, lengths, chunk_frames: int):
         i = j
 
 
-def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None):
+def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None,
+                      shake=None):
     """Generator of (first run, blur uint8 [m,H,W,3], gt uint8 [m,H,W,3], gray [m,H,W] or None) on `device`, one item per chunk of
     consecutive runs; see `synthesize`."""
     if not _light.is_code(light):
@@ -100,6 +122,12 @@ def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_fra
     starts, lengths = (np.asarray(a, np.int64).reshape(-1) for a in runs[:2])
     if starts.size != lengths.size or starts.size == 0:
         raise ValueError(f"runs must be (starts, lengths) of one length >= 1; got {starts.size} and {lengths.size}")
+    if shake is not None:
+        shake = _shake.ClipShake(*shake)
+        _shake.check(light, shake.spec)
+        if len(runs) < 3 or np.asarray(runs[2]).size != starts.size:
+            raise ValueError("shake: runs must be (starts, lengths, labels): the runs labelled 0 are the shaken ones")
+        labels = np.asarray(runs[2], np.int64).reshape(-1)
     if lengths.min() < 1 or lengths.max() > MAX_RUN or starts.min() < 0 or (starts + lengths).max() > fr.T:
         raise ValueError(f"every run must hold 1..{MAX_RUN} frames inside the clip of {fr.T}")
     dev = torch.device(device)
@@ -145,11 +173,16 @@ def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_fra
                         src_buf[t - lo].copy_(fr.device(t))
                 src = src_buf[:hi - lo]
             rec = None if noise is None else (_light.noise_records(np.arange(i, j) + noise.first_run, noise.clip, *levels), noise.seed)
-            blur, gt, g = ops.window_mean_u8(src, starts[i:j] - lo, lengths[i:j], gray=gray, light=light, noise=rec)
+            srec = None
+            if shake is not None:                          # the PSFs depend on (seed, clip, run id) alone: not on the chunk
+                ids = np.arange(i, j) + shake.first_run
+                srec = (_shake.records(shake.spec, shake.seed, shake.clip, ids, labels[i:j]),
+                        _shake.psf_table(shake.spec, shake.seed, shake.clip, ids, labels[i:j]))
+            blur, gt, g = ops.window_mean_u8(src, starts[i:j] - lo, lengths[i:j], gray=gray, light=light, noise=rec, shake=srec)
             yield i, blur, gt, g
 
 
-def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None):
+def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None, shake=None):
     """Average the runs of a clip on the GPU: `frames` in any form `video.frames_of` accepts (uint8 [T,H,W,3] array or tensor on the
     host or the device, a list of frames, a list of image paths), `runs` = (starts, lengths[, labels]) as `plan_runs` returns them
     -> (blur uint8 [M,H,W,3], gt uint8 [M,H,W,3]) on `device`, and the detector's gray planes [M,H,W] as a third item when `gray`.
@@ -157,8 +190,10 @@ def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: in
     frames are uploaded `chunk_frames` at a time; only the result is as long as the clip.  `light`: "srgb" or "gamma:<g>" averages in
     linear light (speinet_amd.light) instead; gt is unchanged and the gray planes are those of the encoded blur bytes.  `noise`: None, or
     `light.ClipNoise(spec, seed, clip[, first_run])` — the sensor noise of clip `clip` under `seed` at the levels of `spec`, run m
-    carrying the id first_run + m; the result does not depend on `chunk_frames`."""
-    parts = list(synthesize_chunks(frames, runs, device, gray, chunk_frames, light, noise))
+    carrying the id first_run + m; the result does not depend on `chunk_frames`.  `shake`: None, or `shake.ClipShake(spec, seed,
+    clip[, first_run])` — camera shake (speinet_amd.shake) on the runs labelled 0 (`runs` must then carry its labels), one PSF per run
+    drawn from (seed, clip, run id); it needs a linear light and does not depend on `chunk_frames` either."""
+    parts = list(synthesize_chunks(frames, runs, device, gray, chunk_frames, light, noise, shake))
     out = (torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]))
     return out + (torch.cat([p[3] for p in parts]),) if gray else out
 
@@ -177,43 +212,53 @@ def clip_folders(src_dir: str) -> list:
     return clips
 
 
-def plan_dataset(clip_lengths, ratios, seed: int = 0, threshold: int = 5, window_range=(1, 15)) -> list:
+def plan_dataset(clip_lengths, ratios, seed: int = 0, threshold: int = 5, window_range=(1, 15), frames: str = "runs") -> list:
     """The draws of a whole directory on ONE `random.Random(seed)` (reference process_dataset, mix_choice_dataset.py:78-117): for every
     clip, in the clips' sorted order (`clip_lengths`: their frame counts in that order), `rng.choice(ratios)` — drawn only when there
-    are several ratios (:79) — then the clip's `plan_runs`.  -> one (ratio, (starts, lengths, labels)) per clip."""
+    are several ratios (:79) — then the clip's `plan_runs`, or with `frames="single"` its `plan_single`.  -> one (ratio, (starts,
+    lengths, labels)) per clip."""
     ratios = list(ratios)
     if not ratios:
         raise ValueError("give ratio or ratios")
+    if frames not in _shake.FRAMES:
+        raise ValueError(f"frames {frames!r}: expected 'runs' or 'single'")
     for r in ratios:
         check_arguments(r, threshold, window_range)
     rng = random.Random(seed)
     plans = []
     for n_frames in clip_lengths:
         r = rng.choice(ratios) if len(ratios) > 1 else ratios[0]
-        plans.append((r, plan_runs(int(n_frames), r, threshold, window_range, rng)))
+        plans.append((r, plan_single(int(n_frames), r, rng) if frames == "single" else plan_runs(int(n_frames), r, threshold, window_range, rng)))
     return plans
 
 
 def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int = 0, threshold: int = 5, window_range=(1, 15),
-                  device="cuda", chunk_frames: int = CHUNK_FRAMES, log=None, light="code", noise=None) -> list:
+                  device="cuda", chunk_frames: int = CHUNK_FRAMES, log=None, light="code", noise=None, shake=None,
+                  frames: str = "runs") -> list:
     """For every clip folder under src_dir write out_dir/blur/<clip>/<i>.png, out_dir/gt/<clip>/<i>.png and out_dir/label/<clip>.npy
     (reference process_dataset, mix_choice_dataset.py:78-117).  `ratio`: the share of sharp runs; `ratios`: several, one drawn per
     clip (:79) from the same `random.Random(seed)` that then draws the clip's runs (`plan_dataset`).  `light`: the light the runs are
     averaged in (speinet_amd.light; it changes the blur frames only, and is not recorded in the set).  `noise`: a spec "<shot>:<read>"
     (speinet_amd.light): sensor noise in that linear light, keyed by `seed`, the clip's index and the run's, at levels drawn per clip; it
-    does not touch the plan.  -> one dict per clip (name, ratio, frames, labels; with noise also its `shot` and `read`)."""
+    does not touch the plan.  `shake`: a spec "<lo>..<hi>" or "<len>" (speinet_amd.shake): camera-shake blur in that linear light on the
+    frames labelled 0, one PSF per frame drawn from `seed`, the clip's index and the run's; it does not touch the plan either.
+    `frames`: "runs" (the plan above) or "single" — for ordinary-frame-rate footage: every source frame is its own run of length 1
+    (`plan_single`), steady (label 1) with probability `ratio`, shaken otherwise; it needs a shake spec.  -> one dict per clip (name,
+    ratio, frames, labels; with noise also its `shot` and `read`)."""
     light = _light.name(light)
     if light != _light.CODE:
         _light.tables(light)
     _light.check_noise(light, noise)
     noise = _light.noise_name(noise)
+    _shake.check(light, shake, frames)
+    shake = _shake.name(shake)
     clips = []
     for name, files in clip_folders(src_dir):
         try:
             clips.append((name, frames_of(files)))
         except ValueError as e:
             raise ValueError(f"clip {name}: {e}") from None
-    plans = plan_dataset([fr.T for _, fr in clips], [ratio] if ratios is None else ratios, seed, threshold, window_range)
+    plans = plan_dataset([fr.T for _, fr in clips], [ratio] if ratios is None else ratios, seed, threshold, window_range, frames)
     dev = torch.device(device)
     done = []
     os.makedirs(os.path.join(out_dir, "label"), exist_ok=True)
@@ -229,7 +274,8 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
                 _imwrite(pg, g.numpy())
 
             clip_noise = None if noise is None else _light.ClipNoise(noise, seed, k)
-            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths), dev, False, chunk_frames, light, clip_noise):
+            clip_shake = None if shake is None else _shake.ClipShake(shake, seed, k)
+            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths, labels), dev, False, chunk_frames, light, clip_noise, clip_shake):
                 for m in range(blur.shape[0]):
                     fn = f"{i0 + m:06d}.png"
                     ring.land(lambda b, g, pb=os.path.join(bdir, fn), pg=os.path.join(gdir, fn): save(b, g, pb, pg), blur[m], gt[m])
@@ -240,6 +286,8 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
             if noise is not None:
                 done[-1]["shot"], done[-1]["read"] = _light.noise_draw(noise, seed, k)
                 noisy = f", noise shot {done[-1]['shot']:.3g} read {done[-1]['read']:.3g}"
+            if shake is not None:
+                noisy += f", shake {shake} on {int((labels == 0).sum())} frames"
             if log:
                 log(f"> {name}: {fr.T} sharp frames -> {labels.size} frames, {int(labels.sum())} labelled sharp (ratio {r}, light {light}{noisy})")
     return done
@@ -257,6 +305,12 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--noise", default=None, help="sensor noise added in the linear --light: <shot>:<read>, the shot coefficient (at most 0.05) "
                                                  "and the read deviation (at most 0.1) at full scale 1, each a number or lo..hi (drawn "
                                                  "log-uniformly per clip); not fitted to any camera")
+    p.add_argument("--shake", default=None, help="camera-shake blur applied in the linear --light to the frames labelled blurry: the blur "
+                                                 "extent in pixels, <len> or <lo>..<hi> within 2..30 (one trajectory PSF is drawn per frame); "
+                                                 "not fitted to any camera")
+    p.add_argument("--frames", default="runs", choices=_shake.FRAMES, help="runs: average runs of 1..15 frames (high-frame-rate footage); "
+                                                                           "single: every frame is its own output frame, shaken unless "
+                                                                           "drawn steady with probability --ratio (ordinary footage; needs --shake)")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -276,12 +330,20 @@ def main(argv=None) -> None:
         p.error(f"--noise: {e}")
     if noise is not None and light == _light.CODE:
         p.error("--noise is added in linear light: pass --light srgb or --light gamma:<g> with it")
+    try:
+        shake = _shake.name(a.shake)
+    except ValueError as e:
+        p.error(f"--shake: {e}")
+    if shake is not None and light == _light.CODE:
+        p.error("--shake is applied in linear light: pass --light srgb or --light gamma:<g> with it")
+    if a.frames == "single" and shake is None:
+        p.error("--frames single makes every frame its own output frame: pass --shake with it, or every frame comes out sharp")
     t0 = time.time()
     done = write_dataset(a.input, a.output, ratios=a.ratio, seed=a.seed, threshold=a.threshold, device=a.device,
-                         log=lambda s: print(s, flush=True), light=light, noise=noise)
+                         log=lambda s: print(s, flush=True), light=light, noise=noise, shake=shake, frames=a.frames)
     n_src, n_out = sum(d["source_frames"] for d in done), sum(d["frames"] for d in done)
-    print(f"# {len(done)} clips, {n_src} sharp frames -> {n_out} frames in {time.time() - t0:.2f}s, light {light}" + (f", noise {noise}" if noise else ""),
-          flush=True)
+    print(f"# {len(done)} clips, {n_src} sharp frames -> {n_out} frames in {time.time() - t0:.2f}s, light {light}" + (f", noise {noise}" if noise else "")
+          + (f", shake {shake}, frames {a.frames}" if shake else ""), flush=True)
 
 
 if __name__ == "__main__":

@@ -29,10 +29,9 @@
 //                         fp32 square root with two integer corrections and a 64-bit multiply per byte.  A run of length 1 still copies.
 #include "common.h"
 #include "light.h"
+#include "run_checks.h"
 
 namespace {
-
-constexpr int MAX_RUN = 15;
 
 __device__ __forceinline__ uint32_t quot(uint32_t s, uint32_t magic) { return (s * magic) >> 16; }
 
@@ -201,24 +200,15 @@ __global__ __launch_bounds__(256) void window_mean_px_kernel(const unsigned char
     }
 }
 
-// The runs are checked HERE, on the host copy (and, LIGHT, the tables on theirs): the kernels never meet a run that leaves the clip
+// The runs are checked on the host copy (run_checks.h; LIGHT: the tables on theirs): the kernels never meet a run that leaves the clip
 template <bool LIGHT, bool NOISE = false>
 int window_mean(const char* name, const unsigned char* src, int64_t frame_stride, int T, const int* runs, const int* runs_host, int M,
                 const uint32_t* tables, const uint32_t* tables_host, unsigned char* blur, unsigned char* gt, float* gray, int H, int W,
                 spei_stream_t stream, const int32_t* gauss = nullptr, const int32_t* gauss_host = nullptr,
                 const spei_noise_record* noise = nullptr, const spei_noise_record* noise_host = nullptr, uint32_t key0 = 0u,
                 uint32_t key1 = 0u) {
-    SPEI_REQUIRE(src && runs && runs_host && blur && gt, "%s: null pointer (src, runs, runs_host, blur and gt are required)", name);
-    SPEI_REQUIRE(T > 0 && M > 0 && M <= 65535 && H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31),
-                 "%s: bad sizes (%d frames of %dx%d, %d runs; at most 65535 runs per launch)", name, T, H, W, M);
+    if (window_runs_check(name, src, frame_stride, T, runs, runs_host, M, blur, gt, H, W)) return -1;
     const int64_t hw = (int64_t)H * W;
-    SPEI_REQUIRE(T == 1 || frame_stride >= hw * 3, "%s: frame stride %lld < one %dx%d frame", name, (long long)frame_stride, H, W);
-    for (int m = 0; m < M; ++m) {
-        const int start = runs_host[2 * m], len = runs_host[2 * m + 1];
-        SPEI_REQUIRE(len >= 1 && len <= MAX_RUN, "%s: run %d has length %d (1..%d)", name, m, len, MAX_RUN);
-        SPEI_REQUIRE(start >= 0 && start <= T - len, "%s: run %d = frames %d..%d leaves the clip of %d frames", name, m, start,
-                     start + len - 1, T);
-    }
     if constexpr (LIGHT)
         if (light_check(name, tables, tables_host)) return -1;
     if constexpr (NOISE)

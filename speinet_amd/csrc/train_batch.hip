@@ -36,26 +36,12 @@
 // four pixels on the counter (x, y, run, clip) with (x, y) = (x0 + cx_lo + g4 + k, y0 + cy_lo + row), the pixel in its full frame.
 #include "common.h"
 #include "light.h"
-
-#include <type_traits>
+#include "run_checks.h"
+#include "train_tile.h"
 
 namespace {
 
-constexpr int TILE = 32, PITCH = TILE + 1;
-constexpr int F_HFLIP = 1, F_VFLIP = 2, F_ROT90 = 4, F_ZERO = 8;
-constexpr int MAX_RUN = 15, RUN_LOADS = 4;                               // RUN_LOADS frames' loads are issued before their adds
-
-// 12 bytes = 4 pixels of one source row, as three dwords
-__device__ __forceinline__ void load12(const unsigned char* s, bool dwords, uint32_t w[3]) {
-    if (dwords) {
-        const uint32_t* p = reinterpret_cast<const uint32_t*>(s);
-        w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            w[k] = (uint32_t)s[4 * k] | ((uint32_t)s[4 * k + 1] << 8) | ((uint32_t)s[4 * k + 2] << 16) | ((uint32_t)s[4 * k + 3] << 24);
-    }
-}
+constexpr int RUN_LOADS = 4;                                             // RUN_LOADS frames' loads are issued before their adds
 
 // 12 bytes of a run of len frames fstride apart averaged in linear light (csrc/light.h), packed as load12 packs them; tab = lin[256],
 // thr[256] in LDS, staged iff len > 1.  NOISE: with the noise of record nr under the key of na added to the quotient; gauss = the table
@@ -113,15 +99,10 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict_
     __shared__ uint32_t lds[TILE * PITCH];
     const int r = blockIdx.y;
     const Rec rec = table[r];
-    const int oi0 = (blockIdx.x / tiles) * TILE, oj0 = (blockIdx.x % tiles) * TILE;
-    const int nI = min(TILE, P - oi0), nJ = min(TILE, P - oj0);          // multiples of 4 (P % 4 == 0)
+    const TileGeom g = tile_geom(rec.flags, P, tiles);
     const int row = threadIdx.x >> 3, g4 = (threadIdx.x & 7) * 4;
-    const bool hf = rec.flags & F_HFLIP, vf = rec.flags & F_VFLIP, rot = rec.flags & F_ROT90, zero = rec.flags & F_ZERO;
-    // the source tile inside the crop: rows [cy_lo, cy_lo + nR), columns [cx_lo, cx_lo + nC); cx_lo % 4 == 0
-    const int nR = rot ? nJ : nI, nC = rot ? nI : nJ;
-    const int cy_lo = rot ? (vf ? P - oj0 - nJ : oj0) : (vf ? P - oi0 - nI : oi0);
-    const int cx_lo = rot ? (hf ? oi0 : P - oi0 - nI) : (hf ? P - oj0 - nJ : oj0);
-    if (!zero) {
+    const int nR = g.nR, nC = g.nC, cy_lo = g.cy_lo, cx_lo = g.cx_lo;
+    if (!g.zero) {
         const uint32_t* tab = nullptr;                                   // LIGHT: lin[256], thr[256] in LDS, for a run of 2 or more frames
         if constexpr (LIGHT) {
             __shared__ uint32_t light[LIGHT_WORDS];
@@ -175,63 +156,20 @@ __global__ __launch_bounds__(256) void train_batch_kernel(const Rec* __restrict_
             } else {
                 load12(s, dwords, w);
             }
-            // 12 bytes = 4 pixels: pixel k is bytes 3k .. 3k+2 -> one dword 0x00BBGGRR each
-            const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32), hi = (uint64_t)w[1] | ((uint64_t)w[2] << 32);
-            uint32_t* d = lds + row * PITCH + g4;
-            d[0] = (uint32_t)lo & 0xffffffu;
-            d[1] = (uint32_t)(lo >> 24) & 0xffffffu;
-            d[2] = (uint32_t)(hi >> 16) & 0xffffffu;
-            d[3] = (uint32_t)(hi >> 40) & 0xffffffu;
+            unpack12(w, lds + row * PITCH + g4);
         }
         __syncthreads();
     }
-    if (row >= nI || g4 >= nJ) return;
-    const int i = oi0 + row;
-    float v[3][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int j = oj0 + g4 + k;
-        const int cy = rot ? (vf ? P - 1 - j : j) : (vf ? P - 1 - i : i);
-        const int cx = rot ? (hf ? i : P - 1 - i) : (hf ? P - 1 - j : j);
-        const uint32_t px = zero ? 0u : lds[(cy - cy_lo) * PITCH + (cx - cx_lo)];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c][k] = (float)((px >> (8 * c)) & 0xffu) * scale;
-    }
-    float* base = r < n_in ? input + (int64_t)r * 3 * P * P : gt + (int64_t)(r - n_in) * 3 * P * P;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-        *reinterpret_cast<float4*>(base + ((int64_t)c * P + i) * P + oj0 + g4) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+    store_tile(lds, g, r, n_in, input, gt, P, scale);
 }
 
-// Every record is checked HERE, on the host copy: the kernel never meets a record that leaves its frame or its clip
+// Every record is checked on the host copy (run_checks.h): the kernel never meets a record that leaves its frame or its clip
 template <typename Rec, bool LIGHT = false, bool NOISE = false>
 int train_batch(const char* name, const Rec* table, const Rec* table_host, int n_in, int n_gt, float* input, float* gt, int P, float rgb_range,
                 spei_stream_t stream, const uint32_t* tables = nullptr, const uint32_t* tables_host = nullptr, const int32_t* gauss = nullptr,
                 const int32_t* gauss_host = nullptr, const spei_noise_record* noise = nullptr, const spei_noise_record* noise_host = nullptr,
                 uint32_t key0 = 0u, uint32_t key1 = 0u) {
-    SPEI_REQUIRE(table && table_host, "%s: null record table (the device table and its host copy are both required)", name);
-    SPEI_REQUIRE(n_in >= 0 && n_gt >= 0 && n_in + n_gt > 0 && n_in + n_gt <= 65535, "%s: bad record counts %d + %d", name, n_in, n_gt);
-    SPEI_REQUIRE((n_in == 0 || input) && (n_gt == 0 || gt), "%s: null dst", name);
-    SPEI_REQUIRE(((uintptr_t)input & 15) == 0 && ((uintptr_t)gt & 15) == 0, "%s: dst must be 16-byte aligned", name);
-    SPEI_REQUIRE(P > 0 && P % 4 == 0 && P <= 4096, "%s: patch size %d must be a positive multiple of 4 (at most 4096)", name, P);
-    SPEI_REQUIRE(rgb_range > 0.0f, "%s: rgb_range %g must be positive", name, (double)rgb_range);
-    for (int r = 0; r < n_in + n_gt; ++r) {
-        const Rec& c = table_host[r];
-        SPEI_REQUIRE((c.flags & ~15) == 0, "%s: record %d has unknown flag bits 0x%x", name, r, (unsigned)c.flags);
-        if (c.flags & F_ZERO) continue;
-        SPEI_REQUIRE(c.src != 0, "%s: record %d has a null frame address", name, r);
-        SPEI_REQUIRE(c.H > 0 && c.W > 0 && c.W <= (1 << 24) && c.pitch >= c.W * 3, "%s: record %d: frame %dx%d with a row pitch of %d bytes", name,
-                     r, c.W, c.H, c.pitch);
-        SPEI_REQUIRE(c.y0 >= 0 && c.x0 >= 0 && (int64_t)c.y0 + P <= c.H && (int64_t)c.x0 + P <= c.W,
-                     "%s: record %d: the %dx%d rectangle at (y %d, x %d) leaves its %dx%d frame", name, r, P, P, c.y0, c.x0, c.W, c.H);
-        if constexpr (std::is_same<Rec, spei_run_record>::value) {
-            SPEI_REQUIRE(c.length >= 1 && c.length <= MAX_RUN, "%s: record %d has a run of length %d (1..%d)", name, r, c.length, MAX_RUN);
-            SPEI_REQUIRE(c.length <= c.avail, "%s: record %d: a run of %d frames where %d are left of its clip", name, r, c.length, c.avail);
-            SPEI_REQUIRE(c.length == 1 || c.frame_stride >= (int64_t)c.H * c.pitch,
-                         "%s: record %d: frame stride %lld < one %dx%d frame with a row pitch of %d bytes", name, r, (long long)c.frame_stride, c.W,
-                         c.H, c.pitch);
-        }
-    }
+    if (batch_table_check(name, table, table_host, n_in, n_gt, input, gt, P, rgb_range)) return -1;
     if constexpr (LIGHT)
         if (light_check(name, tables, tables_host)) return -1;
     if constexpr (NOISE)

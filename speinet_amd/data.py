@@ -181,11 +181,17 @@ class SharpClipSet(Windows):
     and `lengths` (the runs' sharp frames) and `source` (its index in `sharp`, the scanned folders).  `light` (speinet_amd.light: "code",
     "srgb", "gamma:<g>") is the light the loader averages the runs in — write_dataset's `light`; it does not touch the plan.  `noise`
     (a spec "<shot>:<read>" of speinet_amd.light, with a linear light) is write_dataset's `noise`: every plan draws the clips' levels
-    under its own seed (`noise` of a virtual clip: its a, r, A and B), and does not touch the runs either.  The constructor plans epoch 0."""
+    under its own seed (`noise` of a virtual clip: its a, r, A and B), and does not touch the runs either.  `shake` (a spec of
+    speinet_amd.shake, with a linear light) is write_dataset's `shake`: every plan draws one camera-shake PSF per run labelled 0 under
+    its own seed — `shake` of a virtual clip: its spei_shake_record per run, indexing `psfs`, the plan's one uint32 [n,33,33] table —
+    and `frames` ("runs" | "single") is write_dataset's `frames`: "single" plans with `blurset.plan_single`, one run of length 1 per
+    sharp frame, for ordinary-frame-rate footage; it needs `shake`.  The constructor plans epoch 0."""
 
     def __init__(self, dir_sharp: str, ratios=(0.5,), threshold: int = 5, window_range=(1, 15), seed: int = 0, n_sequence: int = 3,
-                 n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None, light="code", noise=None):
+                 n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None, light="code", noise=None,
+                 shake=None, frames: str = "runs"):
         from . import light as _light
+        from . import shake as _shake
         from .blurset import clip_folders
         from .video import frames_of
         self.dir_data, self.train, self.n_seq, self.references = dir_sharp, True, int(n_sequence), bool(references)
@@ -198,6 +204,8 @@ class SharpClipSet(Windows):
             _light.tables(self.light)                                        # ValueError for a light without valid tables
         _light.check_noise(self.light, noise)                                # ... and for noise on code values
         self.noise = _light.noise_name(noise)
+        _shake.check(self.light, shake, frames)                              # ... for shake on code values and `single` without shake
+        self.shake, self.frames = _shake.name(shake), frames
         self.sharp = []
         for name, files in clip_folders(dir_sharp):
             try:
@@ -211,9 +219,10 @@ class SharpClipSet(Windows):
 
     def plan(self, epoch: int) -> None:
         from . import light as _light
+        from . import shake as _shake
         from .blurset import plan_dataset
-        plans = plan_dataset([c["T"] for c in self.sharp], self.ratios, self.seed + epoch, self.threshold, self.window_range)
-        clips = []
+        plans = plan_dataset([c["T"] for c in self.sharp], self.ratios, self.seed + epoch, self.threshold, self.window_range, self.frames)
+        clips, psfs, n_psf = [], [], 0
         for k, (src, (ratio, (starts, lengths, labels))) in enumerate(zip(self.sharp, plans)):
             cut = slice(0, self.n_frames_per_video)
             starts, lengths, labels = starts[cut], lengths[cut], [int(v) for v in labels[cut]]
@@ -227,7 +236,13 @@ class SharpClipSet(Windows):
                 clip["pre"], clip["sub"] = selection.blurry_indices(labels)
             if self.noise is not None:
                 clip["noise"] = _light.noise_draw(self.noise, self.seed + epoch, k) + _light.noise_levels(self.noise, self.seed + epoch, k)
+            if self.shake is not None:                                       # the clip's records index the plan's one table
+                ids = np.arange(len(labels))
+                clip["shake"] = _shake.records(self.shake, self.seed + epoch, k, ids, labels, base=n_psf)
+                psfs.append(_shake.psf_table(self.shake, self.seed + epoch, k, ids, labels))
+                n_psf += psfs[-1].shape[0]
             clips.append(clip)
+        self.psfs = np.concatenate(psfs) if psfs else None                   # uint32 [n,33,33]: every PSF of the plan (SharpTrainLoader uploads it once)
         self.clips, self.epoch = clips, epoch
         self._count(f"{self.dir_data} (epoch {epoch})")
 
@@ -235,6 +250,8 @@ class SharpClipSet(Windows):
         """One line on the current plan: its runs, how many are labelled sharp and the light they are averaged in."""
         runs, sharp = sum(c["T"] for c in self.clips), sum(sum(c["labels"]) for c in self.clips)
         noisy = "" if self.noise is None else f", noise {self.noise}"
+        if self.shake is not None:
+            noisy += f", shake {self.shake} on {sum(int((c['shake']['radius'] > 0).sum()) for c in self.clips)} runs (frames {self.frames})"
         return (f"Plan {self.epoch} of {self.dir_data}: {runs} runs of {sum(c['T'] for c in self.sharp)} sharp frames, {sharp} labelled sharp, "
                 f"light {self.light}{noisy}")
 
@@ -472,6 +489,21 @@ def run_noise_records(clipset: SharpClipSet, items) -> np.ndarray:
     return rec
 
 
+def run_shake_records(clipset: SharpClipSet, items) -> np.ndarray:
+    """The spei_shake_record table beside `run_records`' table, record for record: the record the plan made for the run (its PSF's index
+    in `clipset.psfs`, radius and q16).  A gt record (a run of length 1 on the copy path) carries the delta: radius 0."""
+    from .shake import SHAKE_RECORD
+    n_seq, refs = clipset.n_seq, clipset.references
+    F = n_seq + (2 if refs else 0)
+    B = len(items)
+    rec = np.zeros(B * F + B, dtype=SHAKE_RECORD)
+    rec["q16"] = 65536
+    inp = rec[:B * F].reshape(B, F)
+    for b, (_idx, s, _d) in enumerate(items):
+        inp[b] = clipset.clips[s.clip]["shake"][list(s.frames) + ([s.pre, s.sub] if refs else [])]
+    return rec
+
+
 class TrainLoader:
     """Iterates (input [B,F,3,P,P], gt [B,3,P,P]) fp32 device tensors of one epoch per `iter()`.
 
@@ -588,7 +620,9 @@ class SharpTrainLoader(TrainLoader):
     plan (SharpSampler; `replan=False`: plan 0 throughout).  All launches of an epoch are issued before the next one is planned.  With
     `clipset.light` other than "code" the launch is spei_train_batch_runs_light_u8: the light's tables are uploaded here, once, and
     handed to every launch.  With `clipset.noise` it is spei_train_batch_runs_noise_u8: the noise records are built with the run
-    records, one batch ahead, under the seed of the plan in force, and travel through a ring of their own beside the table's."""
+    records, one batch ahead, under the seed of the plan in force, and travel through a ring of their own beside the table's.  With
+    `clipset.shake` it is spei_train_batch_runs_shake_u8: the shake records (`run_shake_records`) travel the same way, and the plan's PSF
+    table is uploaded once per plan, ahead of the plan's first launch."""
     RECORD = RUN_RECORD
 
     def __init__(self, clipset: SharpClipSet, store: SharpStore, batch: int, patch: int = 200, seed: int = 1, augment: bool = True,
@@ -608,19 +642,39 @@ class SharpTrainLoader(TrainLoader):
                 for slot in self.slots:
                     slot["noise_host"] = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
                     slot["noise_dev"] = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self.shake = clipset.shake
+        self._psfs, self._psfs_epoch = None, None               # the plan's PSF table on the device and the plan it belongs to
+        if self.shake is not None:
+            from .shake import SHAKE_RECORD
+            nb = batch * (self.F + 1) * SHAKE_RECORD.itemsize
+            with torch.cuda.device(self.device):
+                for slot in self.slots:
+                    slot["shake_host"] = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
+                    slot["shake_dev"] = torch.empty(nb, dtype=torch.uint8, device=self.device)
 
     def _records(self, items) -> np.ndarray:
         if self.noise is not None:                            # consumed by the `_build` of the same `_launch`
             self._noise = (run_noise_records(self.clipset, items), self.clipset.seed + self.clipset.epoch)
+        if self.shake is not None:
+            self._shake = run_shake_records(self.clipset, items)
         return run_records(self.clipset, self.store, items)
 
-    def _build(self, *args) -> None:
-        if self.noise is None:
-            self.ctx.train_batch_runs(*args, light=self.light)
-            return
-        rec, seed = self._noise
-        slot = self.slots[(self.launched - 1) % self.RING]     # `_launch`'s slot: its event has been waited for
-        host, dev = slot["noise_host"][:rec.nbytes], slot["noise_dev"][:rec.nbytes]
+    def _ring(self, slot, key: str, rec: np.ndarray):
+        """`rec` through the slot's page-locked buffer `key`_host into its device buffer `key`_dev; -> (device, host) views."""
+        host, dev = slot[key + "_host"][:rec.nbytes], slot[key + "_dev"][:rec.nbytes]
         host.numpy()[...] = rec.view(np.uint8).reshape(-1)
         dev.copy_(host, non_blocking=True)
-        self.ctx.train_batch_runs(*args, light=self.light, noise=(dev, host, seed))
+        return dev, host
+
+    def _build(self, *args) -> None:
+        slot = self.slots[(self.launched - 1) % self.RING]     # `_launch`'s slot: its event has been waited for
+        noise = shake = None
+        if self.noise is not None:
+            rec, seed = self._noise
+            noise = self._ring(slot, "noise", rec) + (seed,)
+        if self.shake is not None:
+            if self._psfs_epoch != self.clipset.epoch:          # once per plan, on the side stream, ahead of the plan's first launch
+                from .shake import device_psfs
+                self._psfs, self._psfs_epoch = device_psfs(self.clipset.psfs, self.device), self.clipset.epoch
+            shake = self._ring(slot, "shake", self._shake) + (self._psfs,)
+        self.ctx.train_batch_runs(*args, light=self.light, noise=noise, shake=shake)

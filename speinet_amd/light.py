@@ -55,6 +55,9 @@ and still returns its bytes.  The gray plane is that of the noisy encoded bytes;
 
 The plan's random.Random stream is not touched: plan_dataset's output is the same with and without noise.  One level per clip, not
 one per frame: a clip is shot at one gain.  The levels are NOT fitted to any camera, and no model has been trained with them here.
+
+CAMERA SHAKE (opt-in; `shake=` / `--shake` / `--blur_shake`) correlates L with a point-spread function between the average and the
+noise, and generalises V to X - ceil(X q16 / (n 2^16)): speinet_amd/shake.py has that contract.
 """
 from __future__ import annotations
 

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib, y4m
 from . import light as _light
+from . import shake as _shake
 from .pack import BF16, F16, F32, LP_DTYPE, PackedW, fmt_of
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
@@ -293,7 +294,7 @@ def frame_pair_stats_u16(u16: torch.Tensor, depth: int, prev: Optional[torch.Ten
 
 
 def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: Optional[torch.Tensor] = None,
-                   gt: Optional[torch.Tensor] = None, light=None, noise=None):
+                   gt: Optional[torch.Tensor] = None, light=None, noise=None, shake=None):
     """The reference's blur synthesis on resident frames (csrc/blurset.hip): uint8 frames [T,H,W,3] on the device (each frame packed,
     any frame stride) and M runs `starts[m]`, `lengths[m]` (1..15 frames, inside the clip) -> (blur uint8 [M,H,W,3] = the per-byte
     integer mean of each run, gt uint8 [M,H,W,3] = the run's middle frame `start + length // 2`, the detector's gray plane [M,H,W] of
@@ -301,9 +302,14 @@ def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: 
     the runs are checked on the host before it.  `light`: None or "code" is that launch (spei_window_mean_u8); "srgb" or "gamma:<g>"
     averages in linear light (speinet_amd.light, spei_window_mean_light_u8), the gray plane still that of the encoded bytes.  `noise`:
     None, or (records, seed) — one speinet_amd.light.NOISE_RECORD per run (its run and clip ids and the clip's levels A, B) and the
-    seed that keys the generator: sensor noise is added in that linear light (spei_window_mean_noise_u8); with "code" a ValueError."""
+    seed that keys the generator: sensor noise is added in that linear light (spei_window_mean_noise_u8); with "code" a ValueError.
+    `shake`: None (exactly the launches above), or (records, psf_table) — one speinet_amd.shake.SHAKE_RECORD per run and the uint32
+    [n,33,33] PSFs they index (an array, or a (device, host) pair of `shake.device_psfs`): the run's linear mean is correlated with its
+    PSF before the noise and the encode (spei_window_mean_shake_u8); with "code" a ValueError."""
     if noise is not None and _light.is_code(light):
         raise ValueError("noise is added in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
+    if shake is not None and _light.is_code(light):
+        raise ValueError("shake is applied in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
     assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4
     t, h, w, c = u8.shape
     assert c == 3 and u8.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
@@ -319,20 +325,44 @@ def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: 
     with torch.cuda.device(dev):
         runs = runs_host.to(dev)
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if _light.is_code(light):
-            _lib.check(lib.spei_window_mean_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
-                                               _vp(blur.data_ptr()), _vp(gt.data_ptr()), _vp(g.data_ptr() if g is not None else 0), h, w, st),
-                       "spei_window_mean_u8")
-        elif noise is not None:
+        rec_dev = rec_host = gs = gs_host = None
+        key0 = key1 = 0
+        if noise is not None:
             rec, seed = noise
             rec = np.ascontiguousarray(rec, dtype=_light.NOISE_RECORD).reshape(-1)
             if rec.size != m:
                 raise ValueError(f"noise: {rec.size} records for {m} runs")
             rec_host = torch.from_numpy(rec.view(np.uint8).copy())
             rec_dev = rec_host.to(dev)
-            tab, tab_host = _light.device_tables(light, dev)
             gs, gs_host = _light.device_gauss(dev)
             key0, key1 = _light.key_of(seed)
+        if _light.is_code(light):
+            _lib.check(lib.spei_window_mean_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
+                                               _vp(blur.data_ptr()), _vp(gt.data_ptr()), _vp(g.data_ptr() if g is not None else 0), h, w, st),
+                       "spei_window_mean_u8")
+        elif shake is not None:
+            srec, psfs = shake
+            srec = np.ascontiguousarray(srec, dtype=_shake.SHAKE_RECORD).reshape(-1)
+            if srec.size != m:
+                raise ValueError(f"shake: {srec.size} records for {m} runs")
+            srec_host = torch.from_numpy(srec.view(np.uint8).copy())
+            srec_dev = srec_host.to(dev)
+            psf_dev, psf_host = psfs if isinstance(psfs, tuple) else _shake.device_psfs(psfs, dev)
+            n_psf = psf_host.numel() // (_shake.SIDE * _shake.SIDE)
+            tab, tab_host = _light.device_tables(light, dev)
+            null = _vp(0)
+            _lib.check(lib.spei_window_mean_shake_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
+                                                     _vp(tab.data_ptr()), _vp(tab_host.data_ptr()),
+                                                     _vp(gs.data_ptr()) if noise is not None else null,
+                                                     _vp(gs_host.data_ptr()) if noise is not None else null,
+                                                     _vp(rec_dev.data_ptr()) if noise is not None else null,
+                                                     _vp(rec_host.data_ptr()) if noise is not None else null, key0, key1,
+                                                     _vp(psf_dev.data_ptr()) if n_psf else null, _vp(psf_host.data_ptr()) if n_psf else null, n_psf,
+                                                     _vp(srec_dev.data_ptr()), _vp(srec_host.data_ptr()), _vp(blur.data_ptr()),
+                                                     _vp(gt.data_ptr()), _vp(g.data_ptr() if g is not None else 0), h, w, st),
+                       "spei_window_mean_shake_u8")
+        elif noise is not None:
+            tab, tab_host = _light.device_tables(light, dev)
             _lib.check(lib.spei_window_mean_noise_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
                                                      _vp(tab.data_ptr()), _vp(tab_host.data_ptr()), _vp(gs.data_ptr()), _vp(gs_host.data_ptr()),
                                                      _vp(rec_dev.data_ptr()), _vp(rec_host.data_ptr()), key0, key1, _vp(blur.data_ptr()),
@@ -950,16 +980,21 @@ class Ctx:
                                                   patch, float(rgb_range), self._stream()), "spei_train_batch_u8")
 
     def train_batch_runs(self, table: torch.Tensor, table_host: torch.Tensor, n_in: int, n_gt: int, input: torch.Tensor,
-                         gt: torch.Tensor, patch: int, rgb_range: float = 1.0, light=None, noise=None) -> None:
+                         gt: torch.Tensor, patch: int, rgb_range: float = 1.0, light=None, noise=None, shake=None) -> None:
         """`train_batch` on run records (speinet_amd.data.RUN_RECORD, 48 bytes each): every output frame is the crop of the per-byte
         integer mean of a run of 1..15 consecutive resident frames — spei_window_mean_u8's bytes, never written to memory.  `light`:
         None or "code" is that launch; "srgb" or "gamma:<g>" averages in linear light (speinet_amd.light,
         spei_train_batch_runs_light_u8: `window_mean_u8(light=...)`'s bytes).  `noise`: None, or (records, records_host, seed) — one
         speinet_amd.light.NOISE_RECORD (24 bytes) per record of the table as uint8 tensors on the device and on the host, and the seed
         that keys the generator: sensor noise in that linear light (spei_train_batch_runs_noise_u8: `window_mean_u8(light=, noise=)`'s
-        bytes); with "code" a ValueError."""
+        bytes); with "code" a ValueError.  `shake`: None (exactly the launches above), or (records, records_host, (psfs, psfs_host)) — one
+        speinet_amd.shake.SHAKE_RECORD (16 bytes) per record of the table as uint8 tensors on the device and on the host, and the PSF
+        table as `shake.device_psfs` returns it: camera shake in that linear light (spei_train_batch_runs_shake_u8:
+        `window_mean_u8(light=, noise=, shake=)`'s bytes); with "code" a ValueError."""
         if noise is not None and _light.is_code(light):
             raise ValueError("noise is added in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
+        if shake is not None and _light.is_code(light):
+            raise ValueError("shake is applied in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
         nb = (n_in + n_gt) * 48
         assert table.dtype == torch.uint8 and table.numel() >= nb and not table_host.is_cuda and table_host.dtype == torch.uint8 \
             and table_host.is_contiguous() and table_host.numel() >= nb
@@ -977,6 +1012,25 @@ class Ctx:
                 and rec_host.is_contiguous() and rec_host.numel() >= nn
             gs, gs_host = _light.device_gauss(self.device)
             key0, key1 = _light.key_of(seed)
+        if shake is not None:
+            srec, srec_host, (psf_dev, psf_host) = shake
+            ns = (n_in + n_gt) * 16
+            assert srec.dtype == torch.uint8 and srec.numel() >= ns and not srec_host.is_cuda and srec_host.dtype == torch.uint8 \
+                and srec_host.is_contiguous() and srec_host.numel() >= ns
+            n_psf = psf_host.numel() // (_shake.SIDE * _shake.SIDE)
+            null = C.c_void_p(0)
+            noisy = noise is not None
+            _lib.check(_lib.lib().spei_train_batch_runs_shake_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(tab),
+                                                                 C.c_void_p(tab_host.data_ptr()), self._tp(gs) if noisy else null,
+                                                                 C.c_void_p(gs_host.data_ptr()) if noisy else null,
+                                                                 self._tp(rec) if noisy else null,
+                                                                 C.c_void_p(rec_host.data_ptr()) if noisy else null, key0 if noisy else 0,
+                                                                 key1 if noisy else 0, self._tp(psf_dev) if n_psf else null,
+                                                                 C.c_void_p(psf_host.data_ptr()) if n_psf else null, n_psf, self._tp(srec),
+                                                                 C.c_void_p(srec_host.data_ptr()), self._tp(input), self._tp(gt), patch,
+                                                                 float(rgb_range), self._stream()), "spei_train_batch_runs_shake_u8")
+            return
+        if noise is not None:
             _lib.check(_lib.lib().spei_train_batch_runs_noise_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(tab),
                                                                  C.c_void_p(tab_host.data_ptr()), self._tp(gs), C.c_void_p(gs_host.data_ptr()),
                                                                  self._tp(rec), C.c_void_p(rec_host.data_ptr()), key0, key1, self._tp(input),
