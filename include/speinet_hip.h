@@ -882,6 +882,52 @@ int spei_train_batch_runs_shake_u8(const spei_run_record* table, const spei_run_
                                    const spei_shake_record* shake_host, float* input, float* gt, int P, float rgb_range,
                                    spei_stream_t stream);
 
+/* ---- codec artefacts in blur synthesis (speinet_amd/codec.py; an extension beyond the reference) ---- */
+
+/* A JPEG-style round trip of the synthesis's INPUT frames, on the final encoded bytes: YCbCr 4:2:0, 8x8 DCT, quantisation by quality-
+ * scaled tables, dequantisation, inverse DCT, back to RGB.  Everything is int32, `>>` is an arithmetic shift (it floors), and the
+ * result is defined bit for bit.  speinet_amd/codec.py's docstring is the definition; in short:
+ * Grid: MCUs are 16 x 16 pixels; one corner of the grid sits at (-oy, -ox) of the frame or rectangle, 0 <= oy, ox < 16.  A sample outside
+ *   the frame or rectangle is the nearest one inside (coordinates clamp).  An MCU reads and writes only its own pixels.
+ * Colour: BT.601 full range, the Q14 constants of the `601 full` row above and the CENTER rule: Y = (yr R + yg G + yb B + 2^13) >> 14
+ *   per pixel; Cb, Cr on the 2 x 2 channel sums with + 2^15, >> 16, + 128 and a clip to 0..255.  Back: chroma is REPLICATED,
+ *   U16 = 16 Cb[y >> 1][x >> 1] (no bilinear taps), then R = clip((yy + rv v + 2^17) >> 18) and likewise G, B as in spei_yuv_to_rgb_u8.
+ * Transform: D[u][x] = rint(8192 a(u) cos((2x + 1) u pi / 16)), a(0) = sqrt(1/8), a(u > 0) = 1/2.  Per 8 x 8 block of s = value - 128:
+ *   T[y][u] = (sum_x D[u][x] s[y][x] + 2^9) >> 10             |sum| <= 2 965 504
+ *   F[v][u] = (sum_y D[v][y] T[y][u] + 2^12) >> 13            |sum| <= 67 094 528; the coefficient in Q3
+ *   q = sign(F) ((|F| + 4 Q) / (8 Q)), truncating division; G = q Q
+ *   U[y][u] = (sum_v D[v][y] G[v][u] + 2^9) >> 10             |sum| <= 24 908 791
+ *   r[y][x] = (sum_u D[u][x] U[y][u] + 2^15) >> 16            |sum| <= 526 417 325;  sample = clip(r + 128, 0, 255)
+ * Tables: `qtabs` on the device and `qtabs_host` the same words in HOST memory are n_qtab tables of uint16 [2][64], luminance then
+ *   chrominance, row-major [v][u], every entry in 1..255 (speinet_amd.codec.quant_tables: ITU-T T.81 Annex K scaled by libjpeg's rule).
+ * Checked on the host copies before anything is launched: qtab < n_qtab, oy, ox < 16, only known flag bits, every table entry in
+ * 1..255; a bad record is an error that names the record.  sizeof(spei_codec_record) == 16. */
+#define SPEI_CODEC_SKIP 16 /* the record's frame is left alone */
+typedef struct {
+    uint32_t qtab;   /* index of the record's tables in qtabs */
+    uint32_t oy, ox; /* 0..15: the grid's corner at (-oy, -ox) */
+    uint32_t flags;  /* SPEI_CROP_HFLIP | VFLIP | ROT90 | ZERO, SPEI_CODEC_SKIP */
+} spei_codec_record;
+
+/* The round trip in place on N packed uint8 [H][W][3] frames, frame_stride bytes apart; records / records_host hold N records whose
+ * flags are 0 or SPEI_CODEC_SKIP.  A SKIP record leaves its frame and its gray plane alone.  gray (or NULL): [N][H][W] fp32, rewritten
+ * for every coded frame, bit-identical to spei_frames_u8_in's gray plane of the new bytes. */
+int spei_codec_u8(unsigned char* frames, int64_t frame_stride, int N, int H, int W, const spei_codec_record* records,
+                  const spei_codec_record* records_host, const uint16_t* qtabs, const uint16_t* qtabs_host, int n_qtab, float* gray,
+                  spei_stream_t stream);
+
+/* The round trip in place on the fp32 [n_in][3][P][P] input tensor a spei_train_batch_runs_* entry wrote; records / records_host hold
+ * n_in records.  With s = (float)(rgb_range / 255) and inv = (float)(255 / rgb_range) the byte of a value v is (int)(v * inv + 0.5f);
+ * that this returns u from (float)u * s for all 256 codes is verified on the host before the launch, and an rgb_range for which it
+ * does not is an error.  The round trip runs on the P x P rectangle in SOURCE orientation: the record's SPEI_CROP_* flags say how the
+ * stored plane is flipped and rotated (spei_train_batch_u8's geometry), and its bytes u' are written back as (float)u' * s.  A ZERO
+ * record stays zero, a SKIP record is left alone.  With oy = y0 % 16, ox = x0 % 16 the grid is the FULL frame's: every MCU wholly inside
+ * the rectangle equals spei_codec_u8 on the whole frame bit for bit; the partial MCUs on the rectangle's border ring replicate the
+ * RECTANGLE's edge, not the frame's real neighbours. */
+int spei_train_batch_codec_f32(float* input, int n_in, int P, float rgb_range, const spei_codec_record* records,
+                               const spei_codec_record* records_host, const uint16_t* qtabs, const uint16_t* qtabs_host, int n_qtab,
+                               spei_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

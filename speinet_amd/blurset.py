@@ -5,6 +5,7 @@ middle frame is the ground truth (reference LD_detector/mix_choice_dataset.py:46
 
     python -m speinet_amd.blurset --input <dir of clip folders> --output <dir> [--ratio 0.1 0.3 0.5] [--threshold 5] [--seed N]
                                   [--light code|srgb|gamma:<g>] [--noise <shot>:<read>] [--shake <len>|<lo>..<hi>] [--frames runs|single]
+                                  [--codec <q>|<lo>..<hi>]
 
 writes `<output>/blur/<clip>/<i>.png`, `<output>/gt/<clip>/<i>.png` and `<output>/label/<clip>.npy`: the layout `data.ClipSet`,
 `speinet_amd.fit` and `python -m speinet_amd.detector fit` read.  The frame files are numbered with six digits: the loaders pair
@@ -18,7 +19,10 @@ every frame labelled blurry with a random camera-shake trajectory PSF of its own
 hand-held camera adds inside one exposure; speinet_amd.shake has the contract.  `--frames single` is the mode for ordinary 24 / 30 fps
 footage, where averaging runs gives ghost copies, not motion blur: every source frame is its own output frame, steady (label 1) with
 probability `--ratio` and shaken otherwise; it needs `--shake`.  One PSF per frame, drawn independently (no camera path across
-frames); extents and trajectory constants are not fitted to any camera.
+frames); extents and trajectory constants are not fitted to any camera.  `--codec <q>` or `<lo>..<hi>` (JPEG qualities 1..100, one drawn
+per clip; any `--light`) puts every frame under `blur/` — the sharp-labelled ones too, never `gt/` — through a JPEG-style round trip
+(YCbCr 4:2:0, 8x8 DCT, quality-scaled quantisation) as the last step, on the final bytes: the block edges and ringing of footage that
+reaches the deblurrer out of a video or JPEG file; speinet_amd.codec has the contract.  The qualities and the proxy are untuned.
 
   * `plan_runs`   — the reference's draw sequence on a `random.Random` of the caller's (no global state): runs and labels;
   * `plan_single` — `--frames single`: one run of length 1 per source frame, its label drawn on the caller's `random.Random`;
@@ -38,6 +42,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from . import codec as _codec
 from . import light as _light
 from . import ops
 from . import shake as _shake
@@ -109,7 +114,7 @@ def _chunks(starts, lengths, chunk_frames: int):
 
 
 def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None,
-                      shake=None):
+                      shake=None, codec=None):
     """Generator of (first run, blur uint8 [m,H,W,3], gt uint8 [m,H,W,3], gray [m,H,W] or None) on `device`, one item per chunk of
     consecutive runs; see `synthesize`."""
     if not _light.is_code(light):
@@ -128,6 +133,9 @@ def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_fra
         if len(runs) < 3 or np.asarray(runs[2]).size != starts.size:
             raise ValueError("shake: runs must be (starts, lengths, labels): the runs labelled 0 are the shaken ones")
         labels = np.asarray(runs[2], np.int64).reshape(-1)
+    if codec is not None:                                  # one quality per clip: a pure function of (spec, seed, clip)
+        codec = _codec.ClipCodec(*codec)
+        qtabs = _codec.quant_tables(_codec.quality(codec.spec, codec.seed, codec.clip))[None]
     if lengths.min() < 1 or lengths.max() > MAX_RUN or starts.min() < 0 or (starts + lengths).max() > fr.T:
         raise ValueError(f"every run must hold 1..{MAX_RUN} frames inside the clip of {fr.T}")
     dev = torch.device(device)
@@ -179,10 +187,13 @@ def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_fra
                 srec = (_shake.records(shake.spec, shake.seed, shake.clip, ids, labels[i:j]),
                         _shake.psf_table(shake.spec, shake.seed, shake.clip, ids, labels[i:j]))
             blur, gt, g = ops.window_mean_u8(src, starts[i:j] - lo, lengths[i:j], gray=gray, light=light, noise=rec, shake=srec)
+            if codec is not None:                          # whole frames on the grid at (0, 0): nothing depends on the chunk
+                ops.codec_u8(blur, _codec.records(j - i), qtabs, gray=g)
             yield i, blur, gt, g
 
 
-def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None, shake=None):
+def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None, shake=None,
+               codec=None):
     """Average the runs of a clip on the GPU: `frames` in any form `video.frames_of` accepts (uint8 [T,H,W,3] array or tensor on the
     host or the device, a list of frames, a list of image paths), `runs` = (starts, lengths[, labels]) as `plan_runs` returns them
     -> (blur uint8 [M,H,W,3], gt uint8 [M,H,W,3]) on `device`, and the detector's gray planes [M,H,W] as a third item when `gray`.
@@ -192,8 +203,11 @@ def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: in
     `light.ClipNoise(spec, seed, clip[, first_run])` — the sensor noise of clip `clip` under `seed` at the levels of `spec`, run m
     carrying the id first_run + m; the result does not depend on `chunk_frames`.  `shake`: None, or `shake.ClipShake(spec, seed,
     clip[, first_run])` — camera shake (speinet_amd.shake) on the runs labelled 0 (`runs` must then carry its labels), one PSF per run
-    drawn from (seed, clip, run id); it needs a linear light and does not depend on `chunk_frames` either."""
-    parts = list(synthesize_chunks(frames, runs, device, gray, chunk_frames, light, noise, shake))
+    drawn from (seed, clip, run id); it needs a linear light and does not depend on `chunk_frames` either.  `codec`: None, or
+    `codec.ClipCodec(spec, seed, clip)` — every blur frame (any label, any light) goes through speinet_amd.codec's JPEG-style round trip
+    at the clip's one quality, in place after the launch above (one more launch per chunk); gt is untouched and the gray planes are
+    those of the coded bytes."""
+    parts = list(synthesize_chunks(frames, runs, device, gray, chunk_frames, light, noise, shake, codec))
     out = (torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]))
     return out + (torch.cat([p[3] for p in parts]),) if gray else out
 
@@ -234,7 +248,7 @@ def plan_dataset(clip_lengths, ratios, seed: int = 0, threshold: int = 5, window
 
 def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int = 0, threshold: int = 5, window_range=(1, 15),
                   device="cuda", chunk_frames: int = CHUNK_FRAMES, log=None, light="code", noise=None, shake=None,
-                  frames: str = "runs") -> list:
+                  frames: str = "runs", codec=None) -> list:
     """For every clip folder under src_dir write out_dir/blur/<clip>/<i>.png, out_dir/gt/<clip>/<i>.png and out_dir/label/<clip>.npy
     (reference process_dataset, mix_choice_dataset.py:78-117).  `ratio`: the share of sharp runs; `ratios`: several, one drawn per
     clip (:79) from the same `random.Random(seed)` that then draws the clip's runs (`plan_dataset`).  `light`: the light the runs are
@@ -243,8 +257,10 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
     does not touch the plan.  `shake`: a spec "<lo>..<hi>" or "<len>" (speinet_amd.shake): camera-shake blur in that linear light on the
     frames labelled 0, one PSF per frame drawn from `seed`, the clip's index and the run's; it does not touch the plan either.
     `frames`: "runs" (the plan above) or "single" — for ordinary-frame-rate footage: every source frame is its own run of length 1
-    (`plan_single`), steady (label 1) with probability `ratio`, shaken otherwise; it needs a shake spec.  -> one dict per clip (name,
-    ratio, frames, labels; with noise also its `shot` and `read`)."""
+    (`plan_single`), steady (label 1) with probability `ratio`, shaken otherwise; it needs a shake spec.  `codec`: a spec "<q>" or
+    "<lo>..<hi>" (speinet_amd.codec): every blur frame goes through the JPEG-style round trip at a quality drawn per clip from `seed` and
+    the clip's index; it does not touch the plan and goes with any light.  -> one dict per clip (name, ratio, frames, labels; with noise
+    also its `shot` and `read`, with a codec its `quality`)."""
     light = _light.name(light)
     if light != _light.CODE:
         _light.tables(light)
@@ -252,6 +268,7 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
     noise = _light.noise_name(noise)
     _shake.check(light, shake, frames)
     shake = _shake.name(shake)
+    codec = _codec.name(codec)
     clips = []
     for name, files in clip_folders(src_dir):
         try:
@@ -275,7 +292,9 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
 
             clip_noise = None if noise is None else _light.ClipNoise(noise, seed, k)
             clip_shake = None if shake is None else _shake.ClipShake(shake, seed, k)
-            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths, labels), dev, False, chunk_frames, light, clip_noise, clip_shake):
+            clip_codec = None if codec is None else _codec.ClipCodec(codec, seed, k)
+            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths, labels), dev, False, chunk_frames, light, clip_noise, clip_shake,
+                                                     clip_codec):
                 for m in range(blur.shape[0]):
                     fn = f"{i0 + m:06d}.png"
                     ring.land(lambda b, g, pb=os.path.join(bdir, fn), pg=os.path.join(gdir, fn): save(b, g, pb, pg), blur[m], gt[m])
@@ -288,6 +307,9 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
                 noisy = f", noise shot {done[-1]['shot']:.3g} read {done[-1]['read']:.3g}"
             if shake is not None:
                 noisy += f", shake {shake} on {int((labels == 0).sum())} frames"
+            if codec is not None:
+                done[-1]["quality"] = _codec.quality(codec, seed, k)
+                noisy += f", codec quality {done[-1]['quality']}"
             if log:
                 log(f"> {name}: {fr.T} sharp frames -> {labels.size} frames, {int(labels.sum())} labelled sharp (ratio {r}, light {light}{noisy})")
     return done
@@ -311,6 +333,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--frames", default="runs", choices=_shake.FRAMES, help="runs: average runs of 1..15 frames (high-frame-rate footage); "
                                                                            "single: every frame is its own output frame, shaken unless "
                                                                            "drawn steady with probability --ratio (ordinary footage; needs --shake)")
+    p.add_argument("--codec", default=None, help="JPEG-style codec artefacts on every blur frame (never on gt), as the last step: the "
+                                                 "quality, <q> or <lo>..<hi> within 1..100 (one is drawn per clip); goes with any --light; "
+                                                 "untuned")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -338,12 +363,17 @@ def main(argv=None) -> None:
         p.error("--shake is applied in linear light: pass --light srgb or --light gamma:<g> with it")
     if a.frames == "single" and shake is None:
         p.error("--frames single makes every frame its own output frame: pass --shake with it, or every frame comes out sharp")
+    try:
+        codec = _codec.name(a.codec)
+    except ValueError as e:
+        p.error(f"--codec: {e}")
     t0 = time.time()
     done = write_dataset(a.input, a.output, ratios=a.ratio, seed=a.seed, threshold=a.threshold, device=a.device,
-                         log=lambda s: print(s, flush=True), light=light, noise=noise, shake=shake, frames=a.frames)
+                         log=lambda s: print(s, flush=True), light=light, noise=noise, shake=shake, frames=a.frames,
+                         codec=codec)
     n_src, n_out = sum(d["source_frames"] for d in done), sum(d["frames"] for d in done)
     print(f"# {len(done)} clips, {n_src} sharp frames -> {n_out} frames in {time.time() - t0:.2f}s, light {light}" + (f", noise {noise}" if noise else "")
-          + (f", shake {shake}, frames {a.frames}" if shake else ""), flush=True)
+          + (f", shake {shake}, frames {a.frames}" if shake else "") + (f", codec {codec}" if codec else ""), flush=True)
 
 
 if __name__ == "__main__":

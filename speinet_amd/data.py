@@ -185,11 +185,14 @@ class SharpClipSet(Windows):
     speinet_amd.shake, with a linear light) is write_dataset's `shake`: every plan draws one camera-shake PSF per run labelled 0 under
     its own seed — `shake` of a virtual clip: its spei_shake_record per run, indexing `psfs`, the plan's one uint32 [n,33,33] table —
     and `frames` ("runs" | "single") is write_dataset's `frames`: "single" plans with `blurset.plan_single`, one run of length 1 per
-    sharp frame, for ordinary-frame-rate footage; it needs `shake`.  The constructor plans epoch 0."""
+    sharp frame, for ordinary-frame-rate footage; it needs `shake`.  `codec` (a spec "<q>" or "<lo>..<hi>" of speinet_amd.codec, with any
+    light) is write_dataset's `codec`: every plan draws one JPEG quality per clip under its own seed (`quality` of a virtual clip) and
+    does not touch the runs.  The constructor plans epoch 0."""
 
     def __init__(self, dir_sharp: str, ratios=(0.5,), threshold: int = 5, window_range=(1, 15), seed: int = 0, n_sequence: int = 3,
                  n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None, light="code", noise=None,
-                 shake=None, frames: str = "runs"):
+                 shake=None, frames: str = "runs", codec=None):
+        from . import codec as _codec
         from . import light as _light
         from . import shake as _shake
         from .blurset import clip_folders
@@ -206,6 +209,7 @@ class SharpClipSet(Windows):
         self.noise = _light.noise_name(noise)
         _shake.check(self.light, shake, frames)                              # ... for shake on code values and `single` without shake
         self.shake, self.frames = _shake.name(shake), frames
+        self.codec = _codec.name(codec)                                      # ... and for a codec spec that does not parse
         self.sharp = []
         for name, files in clip_folders(dir_sharp):
             try:
@@ -218,6 +222,7 @@ class SharpClipSet(Windows):
         self.plan(0)
 
     def plan(self, epoch: int) -> None:
+        from . import codec as _codec
         from . import light as _light
         from . import shake as _shake
         from .blurset import plan_dataset
@@ -241,6 +246,8 @@ class SharpClipSet(Windows):
                 clip["shake"] = _shake.records(self.shake, self.seed + epoch, k, ids, labels, base=n_psf)
                 psfs.append(_shake.psf_table(self.shake, self.seed + epoch, k, ids, labels))
                 n_psf += psfs[-1].shape[0]
+            if self.codec is not None:
+                clip["quality"] = _codec.quality(self.codec, self.seed + epoch, k)
             clips.append(clip)
         self.psfs = np.concatenate(psfs) if psfs else None                   # uint32 [n,33,33]: every PSF of the plan (SharpTrainLoader uploads it once)
         self.clips, self.epoch = clips, epoch
@@ -252,6 +259,9 @@ class SharpClipSet(Windows):
         noisy = "" if self.noise is None else f", noise {self.noise}"
         if self.shake is not None:
             noisy += f", shake {self.shake} on {sum(int((c['shake']['radius'] > 0).sum()) for c in self.clips)} runs (frames {self.frames})"
+        if self.codec is not None:
+            q = [c["quality"] for c in self.clips]
+            noisy += f", codec {self.codec} (qualities {min(q)}..{max(q)})"
         return (f"Plan {self.epoch} of {self.dir_data}: {runs} runs of {sum(c['T'] for c in self.sharp)} sharp frames, {sharp} labelled sharp, "
                 f"light {self.light}{noisy}")
 
@@ -504,6 +514,20 @@ def run_shake_records(clipset: SharpClipSet, items) -> np.ndarray:
     return rec
 
 
+def run_codec_records(clipset: SharpClipSet, items, rec: np.ndarray) -> np.ndarray:
+    """The spei_codec_record table beside the INPUT records of `run_records`' table `rec`, record for record: the tables of the clip's
+    quality (index quality - 1 of `codec.all_tables`), the grid offsets oy = y0 % 16, ox = x0 % 16 — the full frame's grid — and the table
+    record's flags.  Ground truth is never coded: it has no record."""
+    from .codec import CODEC_RECORD
+    F = clipset.n_seq + (2 if clipset.references else 0)
+    B = len(items)
+    out = np.zeros(B * F, dtype=CODEC_RECORD)
+    inp = rec[:B * F]
+    out["oy"], out["ox"], out["flags"] = inp["y0"] % 16, inp["x0"] % 16, inp["flags"]
+    out["qtab"] = np.repeat([clipset.clips[s.clip]["quality"] - 1 for _idx, s, _d in items], F)
+    return out
+
+
 class TrainLoader:
     """Iterates (input [B,F,3,P,P], gt [B,3,P,P]) fp32 device tensors of one epoch per `iter()`.
 
@@ -622,7 +646,9 @@ class SharpTrainLoader(TrainLoader):
     handed to every launch.  With `clipset.noise` it is spei_train_batch_runs_noise_u8: the noise records are built with the run
     records, one batch ahead, under the seed of the plan in force, and travel through a ring of their own beside the table's.  With
     `clipset.shake` it is spei_train_batch_runs_shake_u8: the shake records (`run_shake_records`) travel the same way, and the plan's PSF
-    table is uploaded once per plan, ahead of the plan's first launch."""
+    table is uploaded once per plan, ahead of the plan's first launch.  With `clipset.codec` one more launch follows on the same stream,
+    spei_train_batch_codec_f32 in place on the input tensor: its records (`run_codec_records`) travel through a ring of their own, and
+    the tables of all 100 qualities are uploaded once."""
     RECORD = RUN_RECORD
 
     def __init__(self, clipset: SharpClipSet, store: SharpStore, batch: int, patch: int = 200, seed: int = 1, augment: bool = True,
@@ -651,13 +677,25 @@ class SharpTrainLoader(TrainLoader):
                 for slot in self.slots:
                     slot["shake_host"] = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
                     slot["shake_dev"] = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self.codec = clipset.codec
+        if self.codec is not None:
+            from . import codec as _codec
+            nb = batch * self.F * _codec.CODEC_RECORD.itemsize
+            with torch.cuda.device(self.device):
+                self._qtabs = _codec.device_qtabs(_codec.all_tables(), self.device)
+                for slot in self.slots:
+                    slot["codec_host"] = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
+                    slot["codec_dev"] = torch.empty(nb, dtype=torch.uint8, device=self.device)
 
     def _records(self, items) -> np.ndarray:
         if self.noise is not None:                            # consumed by the `_build` of the same `_launch`
             self._noise = (run_noise_records(self.clipset, items), self.clipset.seed + self.clipset.epoch)
         if self.shake is not None:
             self._shake = run_shake_records(self.clipset, items)
-        return run_records(self.clipset, self.store, items)
+        rec = run_records(self.clipset, self.store, items)
+        if self.codec is not None:
+            self._codec = run_codec_records(self.clipset, items, rec)
+        return rec
 
     def _ring(self, slot, key: str, rec: np.ndarray):
         """`rec` through the slot's page-locked buffer `key`_host into its device buffer `key`_dev; -> (device, host) views."""
@@ -678,3 +716,6 @@ class SharpTrainLoader(TrainLoader):
                 self._psfs, self._psfs_epoch = device_psfs(self.clipset.psfs, self.device), self.clipset.epoch
             shake = self._ring(slot, "shake", self._shake) + (self._psfs,)
         self.ctx.train_batch_runs(*args, light=self.light, noise=noise, shake=shake)
+        if self.codec is not None:                            # in place on the input the launch above wrote, on the same stream
+            _table, _host, n_in, _n_gt, inp, _gt, P, rgb_range = args
+            self.ctx.train_batch_codec(inp, n_in, P, rgb_range, *self._ring(slot, "codec", self._codec), self._qtabs)

@@ -8,14 +8,16 @@ speinet_amd.trainer.Trainer, fed by speinet_amd.data.TrainLoader.
 Both directories hold blur/<clip>/*, gt/<clip>/* and (model speinet) label/<clip>.npy.  In place of `--dir_data`,
 
         --dir_sharp <dir of folders of sharp frames> [--blur_ratio 0.1 0.3 0.5 --blur_threshold 5 --no_replan --blur_light code|srgb|gamma:<g>
-                                                      --blur_noise <shot>:<read> --blur_shake <len>|<lo>..<hi> --blur_frames runs|single]
+                                                      --blur_noise <shot>:<read> --blur_shake <len>|<lo>..<hi> --blur_frames runs|single
+                                                      --blur_codec <q>|<lo>..<hi>]
 
 trains from sharp high-frame-rate footage directly (an extension beyond the reference, which precomputes its sets): the frames stay on
 the device as uint8, every epoch e trains on the set `python -m speinet_amd.blurset --seed <seed + e> --light <blur_light> [--noise
-<blur_noise>] [--shake <blur_shake>] [--frames <blur_frames>]` would write (`--blur_noise`: sensor noise in the linear light, levels
+<blur_noise>] [--shake <blur_shake>] [--frames <blur_frames>] [--codec <blur_codec>]` would write (`--blur_noise`: sensor noise in the linear light, levels
 drawn per clip and per epoch; speinet_amd.light.  `--blur_shake`: camera-shake blur in the linear light on the frames labelled blurry,
 one trajectory PSF per frame and per epoch; `--blur_frames single`: ordinary-frame-rate footage, every frame its own output frame;
-speinet_amd.shake) — runs, labels and references re-drawn, nothing written — and every batch is averaged, cropped and augmented by one launch (data.SharpTrainLoader);
+speinet_amd.shake.  `--blur_codec`: JPEG-style codec artefacts on every input frame of a batch, never on the ground truth, at a quality
+drawn per clip and per epoch, by one more launch in place on the batch; any `--blur_light`; speinet_amd.codec) — runs, labels and references re-drawn, nothing written — and every batch is averaged, cropped and augmented by one launch (data.SharpTrainLoader);
 `--no_replan` keeps epoch 0's set.  The validation set stays a written one.  Names and defaults are those of the reference's
 option/__init__.py and its SPEINet template.  Per epoch, in the reference's order: `scheduler.step()`, one `Trainer.step` per batch,
 a log line every `print_every` batches, then `evaluate()` — eval mode, one full-size validation sample at a time through the model's
@@ -274,6 +276,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--blur_frames", default="runs", choices=("runs", "single"),
                     help="--dir_sharp: runs averages runs of 1..15 frames; single makes every frame its own output frame, shaken unless drawn "
                          "steady with probability --blur_ratio (ordinary-frame-rate footage; needs --blur_shake)")
+    ap.add_argument("--blur_codec", default=None, help="--dir_sharp: JPEG-style codec artefacts on every input frame of a batch (never on the "
+                                                       "ground truth): the quality, <q> or <lo>..<hi> within 1..100 (one per clip and epoch; "
+                                                       "any --blur_light; untuned; speinet_amd.codec)")
     ap.add_argument("--dir_data_test", required=True)
     ap.add_argument("--save", required=True)
     ap.add_argument("--model", default="speinet", choices=("speinet", "swint"))
@@ -297,6 +302,7 @@ def parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None) -> None:
+    from . import codec as _codec
     from . import light as _light
     from . import shake as _shake
     from .data import ClipSet, ClipStore, SharpClipSet, SharpStore, SharpTrainLoader, TrainLoader
@@ -332,6 +338,13 @@ def main(argv=None) -> None:
         ap.error("--blur_shake is applied in linear light: pass --blur_light srgb or --blur_light gamma:<g> with it")
     if a.blur_frames == "single" and blur_shake is None:
         ap.error("--blur_frames single makes every frame its own output frame: pass --blur_shake with it, or every frame comes out sharp")
+    try:
+        blur_codec = _codec.name(a.blur_codec)
+    except ValueError as e:
+        ap.error(f"--blur_codec: {e}")
+    if a.dir_data and blur_codec is not None:
+        ap.error(f"--blur_codec {blur_codec} codes the frames synthesised from --dir_sharp; a written set (--dir_data) holds its blur already: "
+                 "make it with `python -m speinet_amd.blurset --codec`")
     refs = a.model == "speinet"
     if a.dir_sharp and a.residency != "device":
         ap.error("--dir_sharp keeps the sharp frames on the device (--residency device); a set that does not fit is written with "
@@ -339,7 +352,7 @@ def main(argv=None) -> None:
     if a.dir_sharp:
         train_set = SharpClipSet(a.dir_sharp, a.blur_ratio, a.blur_threshold, seed=a.seed, n_frames_per_video=a.n_frames_per_video,
                                  references=refs, patch=a.patch_size, light=blur_light, noise=blur_noise, shake=blur_shake,
-                                 frames=a.blur_frames)
+                                 frames=a.blur_frames, codec=blur_codec)
     else:
         train_set = ClipSet(a.dir_data, True, 3, a.n_frames_per_video, references=refs, patch=a.patch_size)
     val_set = ClipSet(a.dir_data_test, False, 3, a.n_frames_per_video, references=refs)

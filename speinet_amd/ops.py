@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, y4m
+from . import codec as _codec
 from . import light as _light
 from . import shake as _shake
 from .pack import BF16, F16, F32, LP_DTYPE, PackedW, fmt_of
@@ -374,6 +375,40 @@ def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: 
                                                      _vp(tab.data_ptr()), _vp(tab_host.data_ptr()), _vp(blur.data_ptr()), _vp(gt.data_ptr()),
                                                      _vp(g.data_ptr() if g is not None else 0), h, w, st), "spei_window_mean_light_u8")
     return blur, gt, g
+
+
+def _qtabs(qtabs, dev):
+    """(device, host, n) of quantisation tables given as a uint16 [n,2,64] array or as a `codec.device_qtabs` pair."""
+    q_dev, q_host = qtabs if isinstance(qtabs, tuple) else _codec.device_qtabs(qtabs, dev)
+    assert q_dev.is_cuda and q_dev.device == dev and not q_host.is_cuda and q_host.dtype == q_dev.dtype == torch.int16 \
+        and q_host.is_contiguous() and q_dev.is_contiguous() and q_host.numel() == q_dev.numel() and q_host.numel() % 128 == 0
+    return q_dev, q_host, q_host.numel() // 128
+
+
+def codec_u8(frames: torch.Tensor, records, qtabs, gray: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The JPEG-style round trip of speinet_amd.codec IN PLACE on uint8 frames [N,H,W,3] on the device (each frame packed, any frame
+    stride; csrc/codec.hip, spei_codec_u8): `records` one speinet_amd.codec.CODEC_RECORD per frame (its tables' index, the grid offsets
+    oy, ox in 0..15, flags 0 or codec.SKIP), `qtabs` the uint16 [n,2,64] tables they index (an array, or a (device, host) pair of
+    `codec.device_qtabs`).  `gray` (optional): the frames' contiguous fp32 [N,H,W] gray planes, rewritten for every coded frame to
+    `frames_u8_in`'s plane of the new bytes.  One launch on the current stream; records and tables are checked on the host before it.
+    -> frames."""
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4
+    n, h, w, c = frames.shape
+    assert c == 3 and frames.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
+    dev = frames.device
+    assert gray is None or (gray.device == dev and gray.dtype == torch.float32 and tuple(gray.shape) == (n, h, w) and gray.is_contiguous())
+    rec = np.ascontiguousarray(records, dtype=_codec.CODEC_RECORD).reshape(-1)
+    if rec.size != n:
+        raise ValueError(f"codec: {rec.size} records for {n} frames")
+    with torch.cuda.device(dev):
+        rec_host = torch.from_numpy(rec.view(np.uint8).copy())
+        rec_dev = rec_host.to(dev)
+        q_dev, q_host, n_qtab = _qtabs(qtabs, dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().spei_codec_u8(_vp(frames.data_ptr()), frames.stride(0), n, h, w, _vp(rec_dev.data_ptr()), _vp(rec_host.data_ptr()),
+                                            _vp(q_dev.data_ptr()), _vp(q_host.data_ptr()), n_qtab, _vp(gray.data_ptr() if gray is not None else 0),
+                                            st), "spei_codec_u8")
+    return frames
 
 
 def _frame_out(x: torch.Tensor, h: int, w: int, depth: Optional[int], out: Optional[torch.Tensor], nonfinite: Optional[torch.Tensor]):
@@ -1040,6 +1075,22 @@ class Ctx:
         _lib.check(_lib.lib().spei_train_batch_runs_light_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(tab),
                                                              C.c_void_p(tab_host.data_ptr()), self._tp(input), self._tp(gt), patch,
                                                              float(rgb_range), self._stream()), "spei_train_batch_runs_light_u8")
+
+    def train_batch_codec(self, input: torch.Tensor, n_in: int, patch: int, rgb_range: float, records: torch.Tensor,
+                          records_host: torch.Tensor, qtabs) -> None:
+        """The JPEG-style round trip of speinet_amd.codec IN PLACE on the fp32 input [n_in,3,P,P] (any leading shape) that `train_batch_runs`
+        wrote (csrc/codec.hip, spei_train_batch_codec_f32): `records` / `records_host` one speinet_amd.codec.CODEC_RECORD (16 bytes) per
+        input record as uint8 tensors on the device and on the host — its tables' index, oy = y0 % 16, ox = x0 % 16 and the table
+        record's flags — and `qtabs` the tables as `codec.device_qtabs` returns them.  One launch on the current stream; an `rgb_range`
+        whose values do not give their bytes back is a RuntimeError."""
+        nb = n_in * 16
+        assert records.dtype == torch.uint8 and records.numel() >= nb and not records_host.is_cuda and records_host.dtype == torch.uint8 \
+            and records_host.is_contiguous() and records_host.numel() >= nb
+        assert input.dtype == torch.float32 and input.numel() == n_in * 3 * patch * patch
+        q_dev, q_host, n_qtab = _qtabs(qtabs, self.device)
+        _lib.check(_lib.lib().spei_train_batch_codec_f32(self._tp(input), n_in, patch, float(rgb_range), self._tp(records),
+                                                         C.c_void_p(records_host.data_ptr()), self._tp(q_dev), C.c_void_p(q_host.data_ptr()), n_qtab,
+                                                         self._stream()), "spei_train_batch_codec_f32")
 
     def rl_prior(self, img: torch.Tensor, iters: int, lam: float = 0.01) -> torch.Tensor:
         """img [3,H,W] -> [3,H,W]."""
