@@ -10,19 +10,9 @@ middle frame is the ground truth (reference LD_detector/mix_choice_dataset.py:46
 writes `<output>/blur/<clip>/<i>.png`, `<output>/gt/<clip>/<i>.png` and `<output>/label/<clip>.npy`: the layout `data.ClipSet`,
 `speinet_amd.fit` and `python -m speinet_amd.detector fit` read.  The frame files are numbered with six digits: the loaders pair
 frames and labels by sorted file name (as the reference's do, data/videodata_nfs.py:127-162), and the reference's own `0.png ..
-123.png` do not sort in frame order.  `--light` (default `code`: the reference's average of code values, byte for byte) averages in
-linear light instead, as an exposure does: speinet_amd.light has the integer arithmetic; the ground truth, labels and layout are the same.
-`--noise <shot>:<read>` (with a linear `--light`; each side a number or `lo..hi`, drawn log-uniformly per clip) adds back the sensor
-noise that averaging removed — shot coefficient and read deviation at full scale 1, speinet_amd.light has the contract.  The levels
-are not fitted to any camera.  `--shake <len>` or `<lo>..<hi>` (with a linear `--light`; the blur extent in pixels, 2..30) correlates
-every frame labelled blurry with a random camera-shake trajectory PSF of its own, in linear light before the noise — the blur a
-hand-held camera adds inside one exposure; speinet_amd.shake has the contract.  `--frames single` is the mode for ordinary 24 / 30 fps
-footage, where averaging runs gives ghost copies, not motion blur: every source frame is its own output frame, steady (label 1) with
-probability `--ratio` and shaken otherwise; it needs `--shake`.  One PSF per frame, drawn independently (no camera path across
-frames); extents and trajectory constants are not fitted to any camera.  `--codec <q>` or `<lo>..<hi>` (JPEG qualities 1..100, one drawn
-per clip; any `--light`) puts every frame under `blur/` — the sharp-labelled ones too, never `gt/` — through a JPEG-style round trip
-(YCbCr 4:2:0, 8x8 DCT, quality-scaled quantisation) as the last step, on the final bytes: the block edges and ringing of footage that
-reaches the deblurrer out of a video or JPEG file; speinet_amd.codec has the contract.  The qualities and the proxy are untuned.
+123.png` do not sort in frame order.  `--light`, `--noise`, `--shake`, `--frames` and `--codec` are the blur-synthesis recipe:
+speinet_amd.recipe states it (the default is the reference's average of code values, byte for byte; `--frames single` is the mode for
+ordinary 24 / 30 fps footage and needs `--shake`); they change the frames under `blur/` only: ground truth, labels and layout stay.
 
   * `plan_runs`   — the reference's draw sequence on a `random.Random` of the caller's (no global state): runs and labels;
   * `plan_single` — `--frames single`: one run of length 1 per source frame, its label drawn on the caller's `random.Random`;
@@ -43,9 +33,9 @@ import numpy as np
 import torch
 
 from . import codec as _codec
-from . import light as _light
 from . import ops
 from . import shake as _shake
+from .recipe import Clip, Recipe, add_arguments, from_args
 from .video import IMAGE_EXTS, HostRing, _imwrite, frames_of
 
 MAX_RUN = 15                     # spei_window_mean_u8's longest run
@@ -117,25 +107,16 @@ def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_fra
                       shake=None, codec=None):
     """Generator of (first run, blur uint8 [m,H,W,3], gt uint8 [m,H,W,3], gray [m,H,W] or None) on `device`, one item per chunk of
     consecutive runs; see `synthesize`."""
-    if not _light.is_code(light):
-        _light.tables(light)                              # a light without valid tables is refused before anything is read
-    if noise is not None:
-        noise = _light.ClipNoise(*noise)
-        _light.check_noise(light, noise.spec)
-        levels = _light.noise_levels(noise.spec, noise.seed, noise.clip)
+    clip = Clip.of(light, noise, shake, codec)                 # the one validation (speinet_amd.recipe)
     fr = frames if hasattr(frames, "on_device") else frames_of(frames)
     starts, lengths = (np.asarray(a, np.int64).reshape(-1) for a in runs[:2])
     if starts.size != lengths.size or starts.size == 0:
         raise ValueError(f"runs must be (starts, lengths) of one length >= 1; got {starts.size} and {lengths.size}")
-    if shake is not None:
-        shake = _shake.ClipShake(*shake)
-        _shake.check(light, shake.spec)
-        if len(runs) < 3 or np.asarray(runs[2]).size != starts.size:
-            raise ValueError("shake: runs must be (starts, lengths, labels): the runs labelled 0 are the shaken ones")
-        labels = np.asarray(runs[2], np.int64).reshape(-1)
-    if codec is not None:                                  # one quality per clip: a pure function of (spec, seed, clip)
-        codec = _codec.ClipCodec(*codec)
-        qtabs = _codec.quant_tables(_codec.quality(codec.spec, codec.seed, codec.clip))[None]
+    labels = np.asarray(runs[2] if len(runs) > 2 else [], np.int64).reshape(-1)
+    if clip.recipe.shake is not None and labels.size != starts.size:
+        raise ValueError("shake: runs must be (starts, lengths, labels): the runs labelled 0 are the shaken ones")
+    quality = clip.quality                                     # one per clip: a pure function of (spec, seed, clip)
+    qtabs = quality and _codec.quant_tables(quality)[None]
     if lengths.min() < 1 or lengths.max() > MAX_RUN or starts.min() < 0 or (starts + lengths).max() > fr.T:
         raise ValueError(f"every run must hold 1..{MAX_RUN} frames inside the clip of {fr.T}")
     dev = torch.device(device)
@@ -180,14 +161,10 @@ def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_fra
                     if fr.on_device(t):
                         src_buf[t - lo].copy_(fr.device(t))
                 src = src_buf[:hi - lo]
-            rec = None if noise is None else (_light.noise_records(np.arange(i, j) + noise.first_run, noise.clip, *levels), noise.seed)
-            srec = None
-            if shake is not None:                          # the PSFs depend on (seed, clip, run id) alone: not on the chunk
-                ids = np.arange(i, j) + shake.first_run
-                srec = (_shake.records(shake.spec, shake.seed, shake.clip, ids, labels[i:j]),
-                        _shake.psf_table(shake.spec, shake.seed, shake.clip, ids, labels[i:j]))
-            blur, gt, g = ops.window_mean_u8(src, starts[i:j] - lo, lengths[i:j], gray=gray, light=light, noise=rec, shake=srec)
-            if codec is not None:                          # whole frames on the grid at (0, 0): nothing depends on the chunk
+            ids = np.arange(i, j)                              # noise and PSFs depend on (seed, clip, run id) alone: not on the chunk
+            blur, gt, g = ops.window_mean_u8(src, starts[i:j] - lo, lengths[i:j], gray=gray, light=clip.recipe.light,
+                                             noise=clip.noise_records(ids), shake=clip.shake(ids, labels[i:j]))
+            if quality is not None:                            # whole frames on the grid at (0, 0): nothing depends on the chunk
                 ops.codec_u8(blur, _codec.records(j - i), qtabs, gray=g)
             yield i, blur, gt, g
 
@@ -251,31 +228,19 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
                   frames: str = "runs", codec=None) -> list:
     """For every clip folder under src_dir write out_dir/blur/<clip>/<i>.png, out_dir/gt/<clip>/<i>.png and out_dir/label/<clip>.npy
     (reference process_dataset, mix_choice_dataset.py:78-117).  `ratio`: the share of sharp runs; `ratios`: several, one drawn per
-    clip (:79) from the same `random.Random(seed)` that then draws the clip's runs (`plan_dataset`).  `light`: the light the runs are
-    averaged in (speinet_amd.light; it changes the blur frames only, and is not recorded in the set).  `noise`: a spec "<shot>:<read>"
-    (speinet_amd.light): sensor noise in that linear light, keyed by `seed`, the clip's index and the run's, at levels drawn per clip; it
-    does not touch the plan.  `shake`: a spec "<lo>..<hi>" or "<len>" (speinet_amd.shake): camera-shake blur in that linear light on the
-    frames labelled 0, one PSF per frame drawn from `seed`, the clip's index and the run's; it does not touch the plan either.
-    `frames`: "runs" (the plan above) or "single" — for ordinary-frame-rate footage: every source frame is its own run of length 1
-    (`plan_single`), steady (label 1) with probability `ratio`, shaken otherwise; it needs a shake spec.  `codec`: a spec "<q>" or
-    "<lo>..<hi>" (speinet_amd.codec): every blur frame goes through the JPEG-style round trip at a quality drawn per clip from `seed` and
-    the clip's index; it does not touch the plan and goes with any light.  -> one dict per clip (name, ratio, frames, labels; with noise
-    also its `shot` and `read`, with a codec its `quality`)."""
-    light = _light.name(light)
-    if light != _light.CODE:
-        _light.tables(light)
-    _light.check_noise(light, noise)
-    noise = _light.noise_name(noise)
-    _shake.check(light, shake, frames)
-    shake = _shake.name(shake)
-    codec = _codec.name(codec)
+    clip (:79) from the same `random.Random(seed)` that then draws the clip's runs (`plan_dataset`).  `light`, `noise`, `shake`, `frames`
+    and `codec` are the recipe (speinet_amd.recipe.Recipe: specs, validated there): noise levels, PSFs and the JPEG quality are drawn
+    from `seed`, the clip's index and the run's; none of them touches the plan, except that `frames="single"` plans with `plan_single`.
+    They change the frames under blur/ only and are not recorded in the set.  -> one dict per clip (name, ratio, frames, labels; with
+    noise also its `shot` and `read`, with a codec its `quality`)."""
+    recipe = Recipe(light, noise, shake, frames, codec)
     clips = []
     for name, files in clip_folders(src_dir):
         try:
             clips.append((name, frames_of(files)))
         except ValueError as e:
             raise ValueError(f"clip {name}: {e}") from None
-    plans = plan_dataset([fr.T for _, fr in clips], [ratio] if ratios is None else ratios, seed, threshold, window_range, frames)
+    plans = plan_dataset([fr.T for _, fr in clips], [ratio] if ratios is None else ratios, seed, threshold, window_range, recipe.frames)
     dev = torch.device(device)
     done = []
     os.makedirs(os.path.join(out_dir, "label"), exist_ok=True)
@@ -290,28 +255,19 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
                 _imwrite(pb, b.numpy())
                 _imwrite(pg, g.numpy())
 
-            clip_noise = None if noise is None else _light.ClipNoise(noise, seed, k)
-            clip_shake = None if shake is None else _shake.ClipShake(shake, seed, k)
-            clip_codec = None if codec is None else _codec.ClipCodec(codec, seed, k)
-            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths, labels), dev, False, chunk_frames, light, clip_noise, clip_shake,
-                                                     clip_codec):
+            draw = recipe.clip(seed, k)
+            for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths, labels), dev, False, chunk_frames, **draw.stages()):
                 for m in range(blur.shape[0]):
                     fn = f"{i0 + m:06d}.png"
                     ring.land(lambda b, g, pb=os.path.join(bdir, fn), pg=os.path.join(gdir, fn): save(b, g, pb, pg), blur[m], gt[m])
             ring.drain()
             np.save(os.path.join(out_dir, "label", name + ".npy"), labels)
-            done.append({"name": name, "ratio": r, "source_frames": fr.T, "frames": int(labels.size), "labels": labels})
-            noisy = ""
-            if noise is not None:
-                done[-1]["shot"], done[-1]["read"] = _light.noise_draw(noise, seed, k)
-                noisy = f", noise shot {done[-1]['shot']:.3g} read {done[-1]['read']:.3g}"
-            if shake is not None:
-                noisy += f", shake {shake} on {int((labels == 0).sum())} frames"
-            if codec is not None:
-                done[-1]["quality"] = _codec.quality(codec, seed, k)
-                noisy += f", codec quality {done[-1]['quality']}"
+            d = draw.drawn()
+            done.append({"name": name, "ratio": r, "source_frames": fr.T, "frames": int(labels.size), "labels": labels, **d})
             if log:
-                log(f"> {name}: {fr.T} sharp frames -> {labels.size} frames, {int(labels.sum())} labelled sharp (ratio {r}, light {light}{noisy})")
+                said = recipe.describe(noise=lambda: f"shot {d['shot']:.3g} read {d['read']:.3g}", codec=lambda: f"quality {d['quality']}",
+                                       shake=lambda: f"{recipe.shake} on {int((labels == 0).sum())} frames")
+                log(f"> {name}: {fr.T} sharp frames -> {labels.size} frames, {int(labels.sum())} labelled sharp (ratio {r}, {said})")
     return done
 
 
@@ -322,20 +278,7 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--ratio", type=float, nargs="+", default=[0.5], help="share of sharp runs; several: one is drawn per clip")
     p.add_argument("--threshold", type=int, default=5, help="a run of at most this many frames is a sharp frame (label 1)")
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--light", default="code", help="the light the runs are averaged in: code (code values, the reference's sets), srgb or "
-                                                   "gamma:<g> (linear light, as an exposure)")
-    p.add_argument("--noise", default=None, help="sensor noise added in the linear --light: <shot>:<read>, the shot coefficient (at most 0.05) "
-                                                 "and the read deviation (at most 0.1) at full scale 1, each a number or lo..hi (drawn "
-                                                 "log-uniformly per clip); not fitted to any camera")
-    p.add_argument("--shake", default=None, help="camera-shake blur applied in the linear --light to the frames labelled blurry: the blur "
-                                                 "extent in pixels, <len> or <lo>..<hi> within 2..30 (one trajectory PSF is drawn per frame); "
-                                                 "not fitted to any camera")
-    p.add_argument("--frames", default="runs", choices=_shake.FRAMES, help="runs: average runs of 1..15 frames (high-frame-rate footage); "
-                                                                           "single: every frame is its own output frame, shaken unless "
-                                                                           "drawn steady with probability --ratio (ordinary footage; needs --shake)")
-    p.add_argument("--codec", default=None, help="JPEG-style codec artefacts on every blur frame (never on gt), as the last step: the "
-                                                 "quality, <q> or <lo>..<hi> within 1..100 (one is drawn per clip); goes with any --light; "
-                                                 "untuned")
+    add_arguments(p)                                           # --light --noise --shake --frames --codec
     p.add_argument("--device", default="cuda")
     return p
 
@@ -343,37 +286,13 @@ def parser() -> argparse.ArgumentParser:
 def main(argv=None) -> None:
     p = parser()
     a = p.parse_args(argv)
-    try:
-        light = _light.name(a.light)
-        if light != _light.CODE:
-            _light.tables(light)
-    except ValueError as e:
-        p.error(f"--light: {e}")
-    try:
-        noise = _light.noise_name(a.noise)
-    except ValueError as e:
-        p.error(f"--noise: {e}")
-    if noise is not None and light == _light.CODE:
-        p.error("--noise is added in linear light: pass --light srgb or --light gamma:<g> with it")
-    try:
-        shake = _shake.name(a.shake)
-    except ValueError as e:
-        p.error(f"--shake: {e}")
-    if shake is not None and light == _light.CODE:
-        p.error("--shake is applied in linear light: pass --light srgb or --light gamma:<g> with it")
-    if a.frames == "single" and shake is None:
-        p.error("--frames single makes every frame its own output frame: pass --shake with it, or every frame comes out sharp")
-    try:
-        codec = _codec.name(a.codec)
-    except ValueError as e:
-        p.error(f"--codec: {e}")
+    recipe = from_args(p, a)
     t0 = time.time()
     done = write_dataset(a.input, a.output, ratios=a.ratio, seed=a.seed, threshold=a.threshold, device=a.device,
-                         log=lambda s: print(s, flush=True), light=light, noise=noise, shake=shake, frames=a.frames,
-                         codec=codec)
+                         log=lambda s: print(s, flush=True), **recipe._asdict())
     n_src, n_out = sum(d["source_frames"] for d in done), sum(d["frames"] for d in done)
-    print(f"# {len(done)} clips, {n_src} sharp frames -> {n_out} frames in {time.time() - t0:.2f}s, light {light}" + (f", noise {noise}" if noise else "")
-          + (f", shake {shake}, frames {a.frames}" if shake else "") + (f", codec {codec}" if codec else ""), flush=True)
+    said = recipe.describe(shake=lambda: f"{recipe.shake}, frames {recipe.frames}")
+    print(f"# {len(done)} clips, {n_src} sharp frames -> {n_out} frames in {time.time() - t0:.2f}s, {said}", flush=True)
 
 
 if __name__ == "__main__":

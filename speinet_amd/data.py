@@ -9,7 +9,7 @@
 and, beyond the reference (which precomputes its blurry sets), the same loop fed from SHARP footage, the blur synthesised per batch:
 
     SharpClipSet      folders of sharp frames cut into runs as blurset.write_dataset cuts them, re-drawn for every epoch: epoch e is the
-                      set write_dataset(seed = seed + e, light = light, noise = noise) would write, as ClipSet would scan it — but
+                      set write_dataset(seed = seed + e) would write under the same recipe, as ClipSet would scan it — but
                       nothing is written
     SharpStore        the sharp frames, decoded once, uint8 [T,H,W,3] per clip on the device
     run_records       one batch as spei_run_record: an input frame is a run of sharp frames, the ground truth the run's middle frame
@@ -44,7 +44,11 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from . import codec as _codec
+from . import light as _light
 from . import selection
+from . import shake as _shake
+from .recipe import Recipe
 
 MAX_GAP = 7
 F_HFLIP, F_VFLIP, F_ROT90, F_ZERO = 1, 2, 4, 8                        # SPEI_CROP_* of include/speinet_hip.h
@@ -178,23 +182,15 @@ class SharpClipSet(Windows):
     seed=seed + epoch, ...)` followed by `ClipSet(out, True, ...)` would give — per source clip the runs of `blurset.plan_dataset`,
     label 1 for a run of at most `threshold` frames, names `<clip>.<run index, six digits>`, truncated to n_frames_per_video RUNS,
     pre / sub from the truncated labels — so `len()` and `sample(idx)` are ClipSet's on that set.  A virtual clip also carries `starts`
-    and `lengths` (the runs' sharp frames) and `source` (its index in `sharp`, the scanned folders).  `light` (speinet_amd.light: "code",
-    "srgb", "gamma:<g>") is the light the loader averages the runs in — write_dataset's `light`; it does not touch the plan.  `noise`
-    (a spec "<shot>:<read>" of speinet_amd.light, with a linear light) is write_dataset's `noise`: every plan draws the clips' levels
-    under its own seed (`noise` of a virtual clip: its a, r, A and B), and does not touch the runs either.  `shake` (a spec of
-    speinet_amd.shake, with a linear light) is write_dataset's `shake`: every plan draws one camera-shake PSF per run labelled 0 under
-    its own seed — `shake` of a virtual clip: its spei_shake_record per run, indexing `psfs`, the plan's one uint32 [n,33,33] table —
-    and `frames` ("runs" | "single") is write_dataset's `frames`: "single" plans with `blurset.plan_single`, one run of length 1 per
-    sharp frame, for ordinary-frame-rate footage; it needs `shake`.  `codec` (a spec "<q>" or "<lo>..<hi>" of speinet_amd.codec, with any
-    light) is write_dataset's `codec`: every plan draws one JPEG quality per clip under its own seed (`quality` of a virtual clip) and
-    does not touch the runs.  The constructor plans epoch 0."""
+    and `lengths` (the runs' sharp frames) and `source` (its index in `sharp`, the scanned folders).  `light`, `noise`, `shake`, `frames`
+    and `codec` are write_dataset's: the recipe (speinet_amd.recipe.Recipe, kept as `recipe`; the five read back as attributes).  Only
+    `frames="single"` touches the runs (`blurset.plan_single`); every plan draws, under its own seed, what `Recipe.clip` gives a clip:
+    `noise` of a virtual clip (its a, r, A and B), `shake` (its spei_shake_record per run, indexing `psfs`, the plan's one uint32
+    [n,33,33] table) and `quality`, each only with its stage.  The constructor plans epoch 0."""
 
     def __init__(self, dir_sharp: str, ratios=(0.5,), threshold: int = 5, window_range=(1, 15), seed: int = 0, n_sequence: int = 3,
                  n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None, light="code", noise=None,
                  shake=None, frames: str = "runs", codec=None):
-        from . import codec as _codec
-        from . import light as _light
-        from . import shake as _shake
         from .blurset import clip_folders
         from .video import frames_of
         self.dir_data, self.train, self.n_seq, self.references = dir_sharp, True, int(n_sequence), bool(references)
@@ -202,14 +198,7 @@ class SharpClipSet(Windows):
             raise ValueError("samples with references are windows of 3 frames (the reference's zeroing test reads names 2 and 3: videodata_nfs.py:254)")
         self.ratios, self.threshold, self.window_range = list(ratios), int(threshold), tuple(window_range)    # checked by plan_dataset
         self.seed, self.n_frames_per_video = int(seed), int(n_frames_per_video)
-        self.light = _light.name(light)
-        if self.light != _light.CODE:
-            _light.tables(self.light)                                        # ValueError for a light without valid tables
-        _light.check_noise(self.light, noise)                                # ... and for noise on code values
-        self.noise = _light.noise_name(noise)
-        _shake.check(self.light, shake, frames)                              # ... for shake on code values and `single` without shake
-        self.shake, self.frames = _shake.name(shake), frames
-        self.codec = _codec.name(codec)                                      # ... and for a codec spec that does not parse
+        self.recipe = Recipe(light, noise, shake, frames, codec)
         self.sharp = []
         for name, files in clip_folders(dir_sharp):
             try:
@@ -221,10 +210,9 @@ class SharpClipSet(Windows):
             self.sharp.append({"name": name, "files": files, "T": fr.T, "H": fr.H, "W": fr.W})
         self.plan(0)
 
+    light, noise, shake, frames, codec = (property(lambda self, f=f: getattr(self.recipe, f)) for f in Recipe._fields)
+
     def plan(self, epoch: int) -> None:
-        from . import codec as _codec
-        from . import light as _light
-        from . import shake as _shake
         from .blurset import plan_dataset
         plans = plan_dataset([c["T"] for c in self.sharp], self.ratios, self.seed + epoch, self.threshold, self.window_range, self.frames)
         clips, psfs, n_psf = [], [], 0
@@ -239,15 +227,13 @@ class SharpClipSet(Windows):
                     "names": [f"{src['name']}.{m:06d}" for m in range(len(labels))]}
             if self.references:
                 clip["pre"], clip["sub"] = selection.blurry_indices(labels)
-            if self.noise is not None:
-                clip["noise"] = _light.noise_draw(self.noise, self.seed + epoch, k) + _light.noise_levels(self.noise, self.seed + epoch, k)
-            if self.shake is not None:                                       # the clip's records index the plan's one table
-                ids = np.arange(len(labels))
-                clip["shake"] = _shake.records(self.shake, self.seed + epoch, k, ids, labels, base=n_psf)
-                psfs.append(_shake.psf_table(self.shake, self.seed + epoch, k, ids, labels))
-                n_psf += psfs[-1].shape[0]
-            if self.codec is not None:
-                clip["quality"] = _codec.quality(self.codec, self.seed + epoch, k)
+            draw = self.recipe.clip(self.seed + epoch, k)
+            shaken = draw.shake(np.arange(len(labels)), labels, base=n_psf)      # the clip's records index the plan's one table
+            if shaken is not None:
+                psfs.append(shaken[1])
+                n_psf += shaken[1].shape[0]
+            made = {"noise": draw.noise, "shake": shaken and shaken[0], "quality": draw.quality}
+            clip.update({key: v for key, v in made.items() if v is not None})
             clips.append(clip)
         self.psfs = np.concatenate(psfs) if psfs else None                   # uint32 [n,33,33]: every PSF of the plan (SharpTrainLoader uploads it once)
         self.clips, self.epoch = clips, epoch
@@ -256,14 +242,11 @@ class SharpClipSet(Windows):
     def summary(self) -> str:
         """One line on the current plan: its runs, how many are labelled sharp and the light they are averaged in."""
         runs, sharp = sum(c["T"] for c in self.clips), sum(sum(c["labels"]) for c in self.clips)
-        noisy = "" if self.noise is None else f", noise {self.noise}"
-        if self.shake is not None:
-            noisy += f", shake {self.shake} on {sum(int((c['shake']['radius'] > 0).sum()) for c in self.clips)} runs (frames {self.frames})"
-        if self.codec is not None:
-            q = [c["quality"] for c in self.clips]
-            noisy += f", codec {self.codec} (qualities {min(q)}..{max(q)})"
-        return (f"Plan {self.epoch} of {self.dir_data}: {runs} runs of {sum(c['T'] for c in self.sharp)} sharp frames, {sharp} labelled sharp, "
-                f"light {self.light}{noisy}")
+        q = [c.get("quality") for c in self.clips]
+        said = self.recipe.describe(shake=lambda: f"{self.shake} on {sum(int((c['shake']['radius'] > 0).sum()) for c in self.clips)} runs "
+                                                  f"(frames {self.frames})",
+                                    codec=lambda: f"{self.codec} (qualities {min(q)}..{max(q)})")
+        return f"Plan {self.epoch} of {self.dir_data}: {runs} runs of {sum(c['T'] for c in self.sharp)} sharp frames, {sharp} labelled sharp, {said}"
 
     def noise_lines(self) -> list:
         """One line per clip on the levels the current plan drew for it; empty without noise."""
@@ -484,11 +467,10 @@ def run_noise_records(clipset: SharpClipSet, items) -> np.ndarray:
     """The spei_noise_record table beside `run_records`' table, record for record: the run's index in its clip's plan, the clip's index
     in the scanned folders and the levels the plan drew for the clip.  A gt record (a run of length 1: no noise) carries its window's
     middle run."""
-    from .light import NOISE_RECORD
     n_seq, refs = clipset.n_seq, clipset.references
     F = n_seq + (2 if refs else 0)
     B = len(items)
-    rec = np.zeros(B * F + B, dtype=NOISE_RECORD)
+    rec = np.zeros(B * F + B, dtype=_light.NOISE_RECORD)
     inp, gt = rec[:B * F].reshape(B, F), rec[B * F:]
     for b, (_idx, s, _d) in enumerate(items):
         c = clipset.clips[s.clip]
@@ -502,11 +484,10 @@ def run_noise_records(clipset: SharpClipSet, items) -> np.ndarray:
 def run_shake_records(clipset: SharpClipSet, items) -> np.ndarray:
     """The spei_shake_record table beside `run_records`' table, record for record: the record the plan made for the run (its PSF's index
     in `clipset.psfs`, radius and q16).  A gt record (a run of length 1 on the copy path) carries the delta: radius 0."""
-    from .shake import SHAKE_RECORD
     n_seq, refs = clipset.n_seq, clipset.references
     F = n_seq + (2 if refs else 0)
     B = len(items)
-    rec = np.zeros(B * F + B, dtype=SHAKE_RECORD)
+    rec = np.zeros(B * F + B, dtype=_shake.SHAKE_RECORD)
     rec["q16"] = 65536
     inp = rec[:B * F].reshape(B, F)
     for b, (_idx, s, _d) in enumerate(items):
@@ -518,10 +499,9 @@ def run_codec_records(clipset: SharpClipSet, items, rec: np.ndarray) -> np.ndarr
     """The spei_codec_record table beside the INPUT records of `run_records`' table `rec`, record for record: the tables of the clip's
     quality (index quality - 1 of `codec.all_tables`), the grid offsets oy = y0 % 16, ox = x0 % 16 — the full frame's grid — and the table
     record's flags.  Ground truth is never coded: it has no record."""
-    from .codec import CODEC_RECORD
     F = clipset.n_seq + (2 if clipset.references else 0)
     B = len(items)
-    out = np.zeros(B * F, dtype=CODEC_RECORD)
+    out = np.zeros(B * F, dtype=_codec.CODEC_RECORD)
     inp = rec[:B * F]
     out["oy"], out["ox"], out["flags"] = inp["y0"] % 16, inp["x0"] % 16, inp["flags"]
     out["qtab"] = np.repeat([clipset.clips[s.clip]["quality"] - 1 for _idx, s, _d in items], F)
@@ -641,81 +621,60 @@ class TrainLoader:
 class SharpTrainLoader(TrainLoader):
     """TrainLoader fed from sharp footage: the table is `run_records`, the launch spei_train_batch_runs_u8, which averages the run of
     every crop in its load phase; ring, side stream and prefetch thread are TrainLoader's.  Every `iter()` is one epoch under its own
-    plan (SharpSampler; `replan=False`: plan 0 throughout).  All launches of an epoch are issued before the next one is planned.  With
-    `clipset.light` other than "code" the launch is spei_train_batch_runs_light_u8: the light's tables are uploaded here, once, and
-    handed to every launch.  With `clipset.noise` it is spei_train_batch_runs_noise_u8: the noise records are built with the run
-    records, one batch ahead, under the seed of the plan in force, and travel through a ring of their own beside the table's.  With
-    `clipset.shake` it is spei_train_batch_runs_shake_u8: the shake records (`run_shake_records`) travel the same way, and the plan's PSF
-    table is uploaded once per plan, ahead of the plan's first launch.  With `clipset.codec` one more launch follows on the same stream,
-    spei_train_batch_codec_f32 in place on the input tensor: its records (`run_codec_records`) travel through a ring of their own, and
-    the tables of all 100 qualities are uploaded once."""
+    plan (SharpSampler; `replan=False`: plan 0 throughout).  All launches of an epoch are issued before the next one is planned.  The
+    set's recipe picks the launch (`Ctx.train_batch_runs`: _light_, _noise_ or _shake_u8; with a codec spei_train_batch_codec_f32 follows
+    in place on the input, on the same stream).  Uploaded here, once: the light's tables, the gauss table, the tables of all 100
+    qualities; once per plan, ahead of its first launch: the plan's PSF table.  The records of the active stages (`STAGES`) are built
+    with the run records, one batch ahead, under the seed of the plan in force, and travel through rings of their own beside the table's."""
     RECORD = RUN_RECORD
+    # key, its records beside `run_records`' table, their type, records per sample beyond the F inputs (gt is never coded)
+    STAGES = (("noise", lambda cs, items, rec: run_noise_records(cs, items), _light.NOISE_RECORD, 1),
+              ("shake", lambda cs, items, rec: run_shake_records(cs, items), _shake.SHAKE_RECORD, 1),
+              ("codec", run_codec_records, _codec.CODEC_RECORD, 0))
 
     def __init__(self, clipset: SharpClipSet, store: SharpStore, batch: int, patch: int = 200, seed: int = 1, augment: bool = True,
                  rgb_range: float = 1, prefetch: bool = True, rank: Optional[int] = None, world: Optional[int] = None, replan: bool = True):
         super().__init__(clipset, store, batch, patch, seed, augment, rgb_range, prefetch, rank, world,
                          sampler=SharpSampler(clipset, batch, patch, seed, augment, rank, world, replan))
-        self.light = clipset.light
-        if self.light != "code":
-            from . import light as _light
-            _light.device_tables(self.light, self.device)
-        self.noise = clipset.noise
-        if self.noise is not None:
-            from . import light as _light
-            _light.device_gauss(self.device)
-            nb = batch * (self.F + 1) * _light.NOISE_RECORD.itemsize
-            with torch.cuda.device(self.device):
-                for slot in self.slots:
-                    slot["noise_host"] = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
-                    slot["noise_dev"] = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        self.shake = clipset.shake
+        recipe = self.recipe = clipset.recipe
+        self.stages = [row for row in self.STAGES if getattr(recipe, row[0]) is not None]
         self._psfs, self._psfs_epoch = None, None               # the plan's PSF table on the device and the plan it belongs to
-        if self.shake is not None:
-            from .shake import SHAKE_RECORD
-            nb = batch * (self.F + 1) * SHAKE_RECORD.itemsize
-            with torch.cuda.device(self.device):
-                for slot in self.slots:
-                    slot["shake_host"] = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
-                    slot["shake_dev"] = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        self.codec = clipset.codec
-        if self.codec is not None:
-            from . import codec as _codec
-            nb = batch * self.F * _codec.CODEC_RECORD.itemsize
-            with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device):
+            if recipe.light != _light.CODE:
+                _light.device_tables(recipe.light, self.device)
+            if recipe.noise is not None:
+                _light.device_gauss(self.device)
+            if recipe.codec is not None:
                 self._qtabs = _codec.device_qtabs(_codec.all_tables(), self.device)
+            for key, _make, dtype, extra in self.stages:
+                nb = batch * (self.F + extra) * dtype.itemsize
                 for slot in self.slots:
-                    slot["codec_host"] = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
-                    slot["codec_dev"] = torch.empty(nb, dtype=torch.uint8, device=self.device)
+                    slot[key + "_host"] = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
+                    slot[key + "_dev"] = torch.empty(nb, dtype=torch.uint8, device=self.device)
 
     def _records(self, items) -> np.ndarray:
-        if self.noise is not None:                            # consumed by the `_build` of the same `_launch`
-            self._noise = (run_noise_records(self.clipset, items), self.clipset.seed + self.clipset.epoch)
-        if self.shake is not None:
-            self._shake = run_shake_records(self.clipset, items)
         rec = run_records(self.clipset, self.store, items)
-        if self.codec is not None:
-            self._codec = run_codec_records(self.clipset, items, rec)
+        # consumed by the `_build` of the same `_launch`: the active stages' records and the seed of the plan in force
+        self._staged = {key: make(self.clipset, items, rec) for key, make, _dtype, _extra in self.stages}, self.clipset.seed + self.clipset.epoch
         return rec
-
-    def _ring(self, slot, key: str, rec: np.ndarray):
-        """`rec` through the slot's page-locked buffer `key`_host into its device buffer `key`_dev; -> (device, host) views."""
-        host, dev = slot[key + "_host"][:rec.nbytes], slot[key + "_dev"][:rec.nbytes]
-        host.numpy()[...] = rec.view(np.uint8).reshape(-1)
-        dev.copy_(host, non_blocking=True)
-        return dev, host
 
     def _build(self, *args) -> None:
         slot = self.slots[(self.launched - 1) % self.RING]     # `_launch`'s slot: its event has been waited for
-        noise = shake = None
-        if self.noise is not None:
-            rec, seed = self._noise
-            noise = self._ring(slot, "noise", rec) + (seed,)
-        if self.shake is not None:
-            if self._psfs_epoch != self.clipset.epoch:          # once per plan, on the side stream, ahead of the plan's first launch
-                from .shake import device_psfs
-                self._psfs, self._psfs_epoch = device_psfs(self.clipset.psfs, self.device), self.clipset.epoch
-            shake = self._ring(slot, "shake", self._shake) + (self._psfs,)
-        self.ctx.train_batch_runs(*args, light=self.light, noise=noise, shake=shake)
-        if self.codec is not None:                            # in place on the input the launch above wrote, on the same stream
+        recs, seed = self._staged
+
+        def ring(key: str):
+            """The stage's records through the slot's page-locked buffer into its device buffer; -> (device, host) views."""
+            rec = recs[key]
+            host, dev = slot[key + "_host"][:rec.nbytes], slot[key + "_dev"][:rec.nbytes]
+            host.numpy()[...] = rec.view(np.uint8).reshape(-1)
+            dev.copy_(host, non_blocking=True)
+            return dev, host
+
+        noise = ring("noise") + (seed,) if "noise" in recs else None
+        if "shake" in recs and self._psfs_epoch != self.clipset.epoch:   # once per plan, on the side stream, ahead of the plan's first launch
+            self._psfs, self._psfs_epoch = _shake.device_psfs(self.clipset.psfs, self.device), self.clipset.epoch
+        shake = ring("shake") + (self._psfs,) if "shake" in recs else None
+        self.ctx.train_batch_runs(*args, light=self.recipe.light, noise=noise, shake=shake)
+        if "codec" in recs:                                    # in place on the input the launch above wrote, on the same stream
             _table, _host, n_in, _n_gt, inp, _gt, P, rgb_range = args
-            self.ctx.train_batch_codec(inp, n_in, P, rgb_range, *self._ring(slot, "codec", self._codec), self._qtabs)
+            self.ctx.train_batch_codec(inp, n_in, P, rgb_range, *ring("codec"), self._qtabs)

@@ -12,12 +12,10 @@ Both directories hold blur/<clip>/*, gt/<clip>/* and (model speinet) label/<clip
                                                       --blur_codec <q>|<lo>..<hi>]
 
 trains from sharp high-frame-rate footage directly (an extension beyond the reference, which precomputes its sets): the frames stay on
-the device as uint8, every epoch e trains on the set `python -m speinet_amd.blurset --seed <seed + e> --light <blur_light> [--noise
-<blur_noise>] [--shake <blur_shake>] [--frames <blur_frames>] [--codec <blur_codec>]` would write (`--blur_noise`: sensor noise in the linear light, levels
-drawn per clip and per epoch; speinet_amd.light.  `--blur_shake`: camera-shake blur in the linear light on the frames labelled blurry,
-one trajectory PSF per frame and per epoch; `--blur_frames single`: ordinary-frame-rate footage, every frame its own output frame;
-speinet_amd.shake.  `--blur_codec`: JPEG-style codec artefacts on every input frame of a batch, never on the ground truth, at a quality
-drawn per clip and per epoch, by one more launch in place on the batch; any `--blur_light`; speinet_amd.codec) — runs, labels and references re-drawn, nothing written — and every batch is averaged, cropped and augmented by one launch (data.SharpTrainLoader);
+the device as uint8, and every epoch e trains on the set `python -m speinet_amd.blurset --seed <seed + e>` would write under the same
+recipe (the `--blur_*` options are blurset's `--light --noise --shake --frames --codec`; speinet_amd.recipe states them) — runs, labels,
+references, noise levels, PSFs and JPEG qualities re-drawn, nothing written — and every batch is averaged, cropped and augmented by
+one launch, with a codec by one more in place on the batch (data.SharpTrainLoader);
 `--no_replan` keeps epoch 0's set.  The validation set stays a written one.  Names and defaults are those of the reference's
 option/__init__.py and its SPEINet template.  Per epoch, in the reference's order: `scheduler.step()`, one `Trainer.step` per batch,
 a log line every `print_every` batches, then `evaluate()` — eval mode, one full-size validation sample at a time through the model's
@@ -47,6 +45,7 @@ from typing import Optional
 import torch
 
 from . import checkpoint, ops
+from .recipe import Recipe, add_arguments, from_args
 from .trainer import Trainer, seed_rank
 
 
@@ -266,19 +265,7 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--blur_ratio", type=float, nargs="+", default=[0.5], help="--dir_sharp: share of sharp runs; several: one is drawn per clip")
     ap.add_argument("--blur_threshold", type=int, default=5, help="--dir_sharp: a run of at most this many frames is a sharp frame (label 1)")
     ap.add_argument("--no_replan", action="store_true", help="--dir_sharp: keep epoch 0's runs for every epoch")
-    ap.add_argument("--blur_light", default="code", help="--dir_sharp: the light the runs are averaged in: code (code values), srgb or "
-                                                         "gamma:<g> (linear light; speinet_amd.light)")
-    ap.add_argument("--blur_noise", default=None, help="--dir_sharp: sensor noise added in the linear --blur_light: <shot>:<read>, each a number "
-                                                       "or lo..hi (drawn log-uniformly per clip and epoch; speinet_amd.light)")
-    ap.add_argument("--blur_shake", default=None, help="--dir_sharp: camera-shake blur applied in the linear --blur_light to the frames labelled "
-                                                       "blurry: the extent in pixels, <len> or <lo>..<hi> within 2..30 (one trajectory PSF per "
-                                                       "frame and epoch; speinet_amd.shake)")
-    ap.add_argument("--blur_frames", default="runs", choices=("runs", "single"),
-                    help="--dir_sharp: runs averages runs of 1..15 frames; single makes every frame its own output frame, shaken unless drawn "
-                         "steady with probability --blur_ratio (ordinary-frame-rate footage; needs --blur_shake)")
-    ap.add_argument("--blur_codec", default=None, help="--dir_sharp: JPEG-style codec artefacts on every input frame of a batch (never on the "
-                                                       "ground truth): the quality, <q> or <lo>..<hi> within 1..100 (one per clip and epoch; "
-                                                       "any --blur_light; untuned; speinet_amd.codec)")
+    add_arguments(ap, "blur_", "--dir_sharp: ")                # --blur_light --blur_noise --blur_shake --blur_frames --blur_codec
     ap.add_argument("--dir_data_test", required=True)
     ap.add_argument("--save", required=True)
     ap.add_argument("--model", default="speinet", choices=("speinet", "swint"))
@@ -302,57 +289,23 @@ def parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None) -> None:
-    from . import codec as _codec
-    from . import light as _light
-    from . import shake as _shake
     from .data import ClipSet, ClipStore, SharpClipSet, SharpStore, SharpTrainLoader, TrainLoader
     from .loss import Loss
     ap = parser()
     a = ap.parse_args(argv)
-    try:
-        blur_light = _light.name(a.blur_light)
-        if blur_light != _light.CODE:
-            _light.tables(blur_light)
-    except ValueError as e:
-        ap.error(f"--blur_light: {e}")
-    if a.dir_data and blur_light != _light.CODE:
-        ap.error(f"--blur_light {blur_light} averages the runs of --dir_sharp; a written set (--dir_data) holds its blur already: make it "
-                 "with `python -m speinet_amd.blurset --light`")
-    try:
-        blur_noise = _light.noise_name(a.blur_noise)
-    except ValueError as e:
-        ap.error(f"--blur_noise: {e}")
-    if a.dir_data and blur_noise is not None:
-        ap.error(f"--blur_noise {blur_noise} is added to the runs of --dir_sharp; a written set (--dir_data) holds its blur already: make it "
-                 "with `python -m speinet_amd.blurset --light --noise`")
-    if blur_noise is not None and blur_light == _light.CODE:
-        ap.error("--blur_noise is added in linear light: pass --blur_light srgb or --blur_light gamma:<g> with it")
-    try:
-        blur_shake = _shake.name(a.blur_shake)
-    except ValueError as e:
-        ap.error(f"--blur_shake: {e}")
-    if a.dir_data and (blur_shake is not None or a.blur_frames != "runs"):
-        ap.error("--blur_shake / --blur_frames shape the runs of --dir_sharp; a written set (--dir_data) holds its blur already: make it "
-                 "with `python -m speinet_amd.blurset --light --shake [--frames single]`")
-    if blur_shake is not None and blur_light == _light.CODE:
-        ap.error("--blur_shake is applied in linear light: pass --blur_light srgb or --blur_light gamma:<g> with it")
-    if a.blur_frames == "single" and blur_shake is None:
-        ap.error("--blur_frames single makes every frame its own output frame: pass --blur_shake with it, or every frame comes out sharp")
-    try:
-        blur_codec = _codec.name(a.blur_codec)
-    except ValueError as e:
-        ap.error(f"--blur_codec: {e}")
-    if a.dir_data and blur_codec is not None:
-        ap.error(f"--blur_codec {blur_codec} codes the frames synthesised from --dir_sharp; a written set (--dir_data) holds its blur already: "
-                 "make it with `python -m speinet_amd.blurset --codec`")
+    given = [f for f, d in zip(Recipe._fields, Recipe()) if getattr(a, "blur_" + f) != d]
+    if a.dir_data and given:
+        ap.error(" ".join(f"--blur_{f} {getattr(a, 'blur_' + f)}" for f in given) + ": the recipe shapes the blur synthesised from --dir_sharp; a "
+                 "written set (--dir_data) holds its blur already: make it with `python -m speinet_amd.blurset "
+                 + " ".join(f"--{f}" for f in given) + "`")
+    recipe = from_args(ap, a, "blur_")
     refs = a.model == "speinet"
     if a.dir_sharp and a.residency != "device":
         ap.error("--dir_sharp keeps the sharp frames on the device (--residency device); a set that does not fit is written with "
                  "`python -m speinet_amd.blurset` and trained with --dir_data")
     if a.dir_sharp:
         train_set = SharpClipSet(a.dir_sharp, a.blur_ratio, a.blur_threshold, seed=a.seed, n_frames_per_video=a.n_frames_per_video,
-                                 references=refs, patch=a.patch_size, light=blur_light, noise=blur_noise, shake=blur_shake,
-                                 frames=a.blur_frames, codec=blur_codec)
+                                 references=refs, patch=a.patch_size, **recipe._asdict())
     else:
         train_set = ClipSet(a.dir_data, True, 3, a.n_frames_per_video, references=refs, patch=a.patch_size)
     val_set = ClipSet(a.dir_data_test, False, 3, a.n_frames_per_video, references=refs)

@@ -294,6 +294,37 @@ def frame_pair_stats_u16(u16: torch.Tensor, depth: int, prev: Optional[torch.Ten
     return _pair_stats(u16, torch.uint16, _depth(depth), prev)
 
 
+def _stage_args(light, noise, shake, dev, put):
+    """What `window_mean_u8` and `Ctx.train_batch_runs` share: -> (the infix of the entry to call — "" for the light `code`, "_light",
+    "_noise" or "_shake" —, its arguments between the run table and the outputs: the light's tables; gauss table, noise records and
+    keys; PSFs and shake records —, and the tensors those arguments point into, for the caller to hold until it has launched).
+    `noise`: None or (records, seed); `shake`: None or (records, PSFs as an array or a `shake.device_psfs` pair); `put(what, records,
+    record dtype)` -> the caller's records as (device, host) uint8 tensors.  A shake launch without noise takes NULL for the noise
+    group, a table without PSFs NULL for the table."""
+    if noise is not None and _light.is_code(light):
+        raise ValueError("noise is added in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
+    if shake is not None and _light.is_code(light):
+        raise ValueError("shake is applied in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
+    if _light.is_code(light):
+        return "", [], []
+    keep = []                                                # every tensor an argument points into: the caller holds it over the launch
+
+    def p(*tensors):
+        keep.extend(tensors)
+        return [C.c_void_p(t.data_ptr()) for t in tensors]
+
+    args = p(*_light.device_tables(light, dev))
+    if noise is not None:
+        args += p(*_light.device_gauss(dev), *put("noise", noise[0], _light.NOISE_RECORD)) + list(_light.key_of(noise[1]))
+    elif shake is not None:
+        args += [None] * 4 + [0, 0]
+    if shake is not None:
+        psf_dev, psf_host = shake[1] if isinstance(shake[1], tuple) else _shake.device_psfs(shake[1], dev)
+        n_psf = psf_host.numel() // (_shake.SIDE * _shake.SIDE)
+        args += (p(psf_dev, psf_host) if n_psf else [None, None]) + [n_psf] + p(*put("shake", shake[0], _shake.SHAKE_RECORD))
+    return "_shake" if shake is not None else "_noise" if noise is not None else "_light", args, keep
+
+
 def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: Optional[torch.Tensor] = None,
                    gt: Optional[torch.Tensor] = None, light=None, noise=None, shake=None):
     """The reference's blur synthesis on resident frames (csrc/blurset.hip): uint8 frames [T,H,W,3] on the device (each frame packed,
@@ -307,10 +338,6 @@ def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: 
     `shake`: None (exactly the launches above), or (records, psf_table) — one speinet_amd.shake.SHAKE_RECORD per run and the uint32
     [n,33,33] PSFs they index (an array, or a (device, host) pair of `shake.device_psfs`): the run's linear mean is correlated with its
     PSF before the noise and the encode (spei_window_mean_shake_u8); with "code" a ValueError."""
-    if noise is not None and _light.is_code(light):
-        raise ValueError("noise is added in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
-    if shake is not None and _light.is_code(light):
-        raise ValueError("shake is applied in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
     assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4
     t, h, w, c = u8.shape
     assert c == 3 and u8.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
@@ -326,54 +353,18 @@ def window_mean_u8(u8: torch.Tensor, starts, lengths, gray: bool = False, blur: 
     with torch.cuda.device(dev):
         runs = runs_host.to(dev)
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rec_dev = rec_host = gs = gs_host = None
-        key0 = key1 = 0
-        if noise is not None:
-            rec, seed = noise
-            rec = np.ascontiguousarray(rec, dtype=_light.NOISE_RECORD).reshape(-1)
+
+        def put(what, rec, dtype):                           # the caller's arrays, uploaded per call
+            rec = np.ascontiguousarray(rec, dtype=dtype).reshape(-1)
             if rec.size != m:
-                raise ValueError(f"noise: {rec.size} records for {m} runs")
-            rec_host = torch.from_numpy(rec.view(np.uint8).copy())
-            rec_dev = rec_host.to(dev)
-            gs, gs_host = _light.device_gauss(dev)
-            key0, key1 = _light.key_of(seed)
-        if _light.is_code(light):
-            _lib.check(lib.spei_window_mean_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
-                                               _vp(blur.data_ptr()), _vp(gt.data_ptr()), _vp(g.data_ptr() if g is not None else 0), h, w, st),
-                       "spei_window_mean_u8")
-        elif shake is not None:
-            srec, psfs = shake
-            srec = np.ascontiguousarray(srec, dtype=_shake.SHAKE_RECORD).reshape(-1)
-            if srec.size != m:
-                raise ValueError(f"shake: {srec.size} records for {m} runs")
-            srec_host = torch.from_numpy(srec.view(np.uint8).copy())
-            srec_dev = srec_host.to(dev)
-            psf_dev, psf_host = psfs if isinstance(psfs, tuple) else _shake.device_psfs(psfs, dev)
-            n_psf = psf_host.numel() // (_shake.SIDE * _shake.SIDE)
-            tab, tab_host = _light.device_tables(light, dev)
-            null = _vp(0)
-            _lib.check(lib.spei_window_mean_shake_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
-                                                     _vp(tab.data_ptr()), _vp(tab_host.data_ptr()),
-                                                     _vp(gs.data_ptr()) if noise is not None else null,
-                                                     _vp(gs_host.data_ptr()) if noise is not None else null,
-                                                     _vp(rec_dev.data_ptr()) if noise is not None else null,
-                                                     _vp(rec_host.data_ptr()) if noise is not None else null, key0, key1,
-                                                     _vp(psf_dev.data_ptr()) if n_psf else null, _vp(psf_host.data_ptr()) if n_psf else null, n_psf,
-                                                     _vp(srec_dev.data_ptr()), _vp(srec_host.data_ptr()), _vp(blur.data_ptr()),
-                                                     _vp(gt.data_ptr()), _vp(g.data_ptr() if g is not None else 0), h, w, st),
-                       "spei_window_mean_shake_u8")
-        elif noise is not None:
-            tab, tab_host = _light.device_tables(light, dev)
-            _lib.check(lib.spei_window_mean_noise_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
-                                                     _vp(tab.data_ptr()), _vp(tab_host.data_ptr()), _vp(gs.data_ptr()), _vp(gs_host.data_ptr()),
-                                                     _vp(rec_dev.data_ptr()), _vp(rec_host.data_ptr()), key0, key1, _vp(blur.data_ptr()),
-                                                     _vp(gt.data_ptr()), _vp(g.data_ptr() if g is not None else 0), h, w, st),
-                       "spei_window_mean_noise_u8")
-        else:
-            tab, tab_host = _light.device_tables(light, dev)
-            _lib.check(lib.spei_window_mean_light_u8(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
-                                                     _vp(tab.data_ptr()), _vp(tab_host.data_ptr()), _vp(blur.data_ptr()), _vp(gt.data_ptr()),
-                                                     _vp(g.data_ptr() if g is not None else 0), h, w, st), "spei_window_mean_light_u8")
+                raise ValueError(f"{what}: {rec.size} records for {m} runs")
+            host = torch.from_numpy(rec.view(np.uint8).copy())
+            return host.to(dev), host
+
+        infix, stages, _held = _stage_args(light, noise, shake, dev, put)
+        _lib.check(getattr(lib, f"spei_window_mean{infix}_u8")(_vp(u8.data_ptr()), u8.stride(0), t, _vp(runs.data_ptr()), _vp(runs_host.data_ptr()), m,
+                                                              *stages, _vp(blur.data_ptr()), _vp(gt.data_ptr()),
+                                                              _vp(g.data_ptr() if g is not None else 0), h, w, st), f"spei_window_mean{infix}_u8")
     return blur, gt, g
 
 
@@ -1026,55 +1017,23 @@ class Ctx:
         speinet_amd.shake.SHAKE_RECORD (16 bytes) per record of the table as uint8 tensors on the device and on the host, and the PSF
         table as `shake.device_psfs` returns it: camera shake in that linear light (spei_train_batch_runs_shake_u8:
         `window_mean_u8(light=, noise=, shake=)`'s bytes); with "code" a ValueError."""
-        if noise is not None and _light.is_code(light):
-            raise ValueError("noise is added in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
-        if shake is not None and _light.is_code(light):
-            raise ValueError("shake is applied in linear light: give a light 'srgb' or 'gamma:<g>' beside it (--light / --blur_light), not 'code'")
         nb = (n_in + n_gt) * 48
         assert table.dtype == torch.uint8 and table.numel() >= nb and not table_host.is_cuda and table_host.dtype == torch.uint8 \
             and table_host.is_contiguous() and table_host.numel() >= nb
         assert input.dtype == torch.float32 and input.numel() == n_in * 3 * patch * patch
         assert gt.dtype == torch.float32 and gt.numel() == n_gt * 3 * patch * patch
-        if _light.is_code(light):
-            _lib.check(_lib.lib().spei_train_batch_runs_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(input),
-                                                           self._tp(gt), patch, float(rgb_range), self._stream()), "spei_train_batch_runs_u8")
-            return
-        tab, tab_host = _light.device_tables(light, self.device)
-        if noise is not None:
-            rec, rec_host, seed = noise
-            nn = (n_in + n_gt) * 24
-            assert rec.dtype == torch.uint8 and rec.numel() >= nn and not rec_host.is_cuda and rec_host.dtype == torch.uint8 \
-                and rec_host.is_contiguous() and rec_host.numel() >= nn
-            gs, gs_host = _light.device_gauss(self.device)
-            key0, key1 = _light.key_of(seed)
-        if shake is not None:
-            srec, srec_host, (psf_dev, psf_host) = shake
-            ns = (n_in + n_gt) * 16
-            assert srec.dtype == torch.uint8 and srec.numel() >= ns and not srec_host.is_cuda and srec_host.dtype == torch.uint8 \
-                and srec_host.is_contiguous() and srec_host.numel() >= ns
-            n_psf = psf_host.numel() // (_shake.SIDE * _shake.SIDE)
-            null = C.c_void_p(0)
-            noisy = noise is not None
-            _lib.check(_lib.lib().spei_train_batch_runs_shake_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(tab),
-                                                                 C.c_void_p(tab_host.data_ptr()), self._tp(gs) if noisy else null,
-                                                                 C.c_void_p(gs_host.data_ptr()) if noisy else null,
-                                                                 self._tp(rec) if noisy else null,
-                                                                 C.c_void_p(rec_host.data_ptr()) if noisy else null, key0 if noisy else 0,
-                                                                 key1 if noisy else 0, self._tp(psf_dev) if n_psf else null,
-                                                                 C.c_void_p(psf_host.data_ptr()) if n_psf else null, n_psf, self._tp(srec),
-                                                                 C.c_void_p(srec_host.data_ptr()), self._tp(input), self._tp(gt), patch,
-                                                                 float(rgb_range), self._stream()), "spei_train_batch_runs_shake_u8")
-            return
-        if noise is not None:
-            _lib.check(_lib.lib().spei_train_batch_runs_noise_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(tab),
-                                                                 C.c_void_p(tab_host.data_ptr()), self._tp(gs), C.c_void_p(gs_host.data_ptr()),
-                                                                 self._tp(rec), C.c_void_p(rec_host.data_ptr()), key0, key1, self._tp(input),
-                                                                 self._tp(gt), patch, float(rgb_range), self._stream()),
-                       "spei_train_batch_runs_noise_u8")
-            return
-        _lib.check(_lib.lib().spei_train_batch_runs_light_u8(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, self._tp(tab),
-                                                             C.c_void_p(tab_host.data_ptr()), self._tp(input), self._tp(gt), patch,
-                                                             float(rgb_range), self._stream()), "spei_train_batch_runs_light_u8")
+
+        def put(what, pair, dtype):                          # the caller's ring tensors, already on their way
+            rec, rec_host = pair
+            nr = (n_in + n_gt) * dtype.itemsize
+            assert rec.device == self.device and rec.dtype == torch.uint8 and rec.numel() >= nr and not rec_host.is_cuda \
+                and rec_host.dtype == torch.uint8 and rec_host.is_contiguous() and rec_host.numel() >= nr, what
+            return pair
+
+        infix, stages, _held = _stage_args(light, noise and (noise[:2], noise[2]), shake and (shake[:2], shake[2]), self.device, put)
+        _lib.check(getattr(_lib.lib(), f"spei_train_batch_runs{infix}_u8")(self._tp(table), C.c_void_p(table_host.data_ptr()), n_in, n_gt, *stages,
+                                                                          self._tp(input), self._tp(gt), patch, float(rgb_range), self._stream()),
+                   f"spei_train_batch_runs{infix}_u8")
 
     def train_batch_codec(self, input: torch.Tensor, n_in: int, patch: int, rgb_range: float, records: torch.Tensor,
                           records_host: torch.Tensor, qtabs) -> None:

@@ -71,8 +71,9 @@ for light, spec, noise in LIGHTS:
         host = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy())
         nz = None
         if noise is not None:                                      # the noise records already on the device, as the run records are
-            nhost = torch.from_numpy(loader._noise[0].view(np.uint8).reshape(-1).copy())
-            nz = (nhost.to(DEV), nhost, loader._noise[1])
+            recs, seed = loader._staged
+            nhost = torch.from_numpy(recs["noise"].view(np.uint8).reshape(-1).copy())
+            nz = (nhost.to(DEV), nhost, seed)
         tables.append((host.to(DEV), host, torch.empty((BATCH, loader.F, 3, PATCH, PATCH), device=DEV), torch.empty((BATCH, 3, PATCH, PATCH), device=DEV), nz))
     if light == "code":
         rec = np.concatenate([loader._records(b)[:BATCH * loader.F] for b in batches])
@@ -81,7 +82,7 @@ for light, spec, noise in LIGHTS:
     def run(loader=loader, tables=tables):
         for k in range(LAUNCHES):
             dev, host, inp, gt, nz = tables[k % len(tables)]
-            loader.ctx.train_batch_runs(dev, host, BATCH * loader.F, BATCH, inp, gt, PATCH, 1.0, light=loader.light, noise=nz)
+            loader.ctx.train_batch_runs(dev, host, BATCH * loader.F, BATCH, inp, gt, PATCH, 1.0, light=loader.recipe.light, noise=nz)
     variants[f"train_batch_runs_launch_{light}"] = (run, LAUNCHES)
 
 clip = torch.cat(store.frames)                                     # [2 * frames, 720, 1280, 3]
