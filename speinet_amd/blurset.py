@@ -19,7 +19,7 @@ ordinary 24 / 30 fps footage and needs `--shake`); they change the frames under 
   * `plan_dataset` — that sequence for every clip of a directory on one `random.Random(seed)` (also data.SharpClipSet's, per epoch);
   * `synthesize`  — the averaging on the GPU (csrc/blurset.hip, one launch per chunk of the clip): frames cross PCIe once as uint8,
                     device memory is bounded by the chunk;
-  * `write_dataset` — every clip folder of a directory, PNGs encoded on worker threads behind `video.HostRing`.
+  * `write_dataset` — every clip folder of a directory, PNGs encoded on worker threads behind `clip.HostRing`.
 """
 from __future__ import annotations
 
@@ -35,8 +35,8 @@ import torch
 from . import codec as _codec
 from . import ops
 from . import shake as _shake
+from .clip import IMAGE_EXTS, HostRing, frames_of, imwrite
 from .recipe import Clip, Recipe, add_arguments, from_args
-from .video import IMAGE_EXTS, HostRing, _imwrite, frames_of
 
 MAX_RUN = 15                     # spei_window_mean_u8's longest run
 CHUNK_FRAMES = 64                # source frames resident per launch (a 720p frame is 2.8 MB)
@@ -171,7 +171,7 @@ def synthesize_chunks(frames, runs, device="cuda", gray: bool = False, chunk_fra
 
 def synthesize(frames, runs, device="cuda", gray: bool = False, chunk_frames: int = CHUNK_FRAMES, light="code", noise=None, shake=None,
                codec=None):
-    """Average the runs of a clip on the GPU: `frames` in any form `video.frames_of` accepts (uint8 [T,H,W,3] array or tensor on the
+    """Average the runs of a clip on the GPU: `frames` in any form `clip.frames_of` accepts (uint8 [T,H,W,3] array or tensor on the
     host or the device, a list of frames, a list of image paths), `runs` = (starts, lengths[, labels]) as `plan_runs` returns them
     -> (blur uint8 [M,H,W,3], gt uint8 [M,H,W,3]) on `device`, and the detector's gray planes [M,H,W] as a third item when `gray`.
     blur[m] is the per-byte floor of the run's mean (the bytes the reference writes), gt[m] the run's middle frame.  The source
@@ -252,8 +252,8 @@ def write_dataset(src_dir: str, out_dir: str, ratio=None, ratios=None, seed: int
             os.makedirs(gdir, exist_ok=True)
 
             def save(b, g, pb, pg):
-                _imwrite(pb, b.numpy())
-                _imwrite(pg, g.numpy())
+                imwrite(pb, b.numpy())
+                imwrite(pg, g.numpy())
 
             draw = recipe.clip(seed, k)
             for i0, blur, gt, _ in synthesize_chunks(fr, (starts, lengths, labels), dev, False, chunk_frames, **draw.stages()):

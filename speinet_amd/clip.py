@@ -1,0 +1,284 @@
+"""The clip as a source, for the clip loop (speinet_amd.video), the labelling pass (speinet_amd.detector), the loaders (speinet_amd.data),
+blur synthesis (speinet_amd.blurset) and the harness (speinet_amd.inference).  `frames_of` validates a clip in any form the clip API takes
+and returns it as `Frames`: frame i on the host or on the device, a rectangle of every frame (`view`), a subset of the frames (`sample`).
+Frames cross PCIe as uint8 (a deep clip's as its bytes) from page-locked staging buffers (`FrameCache`) and are decoded, for image paths, on
+worker threads a few windows ahead; finished frames land in page-locked memory for worker threads (`HostRing`).  `imread` / `imwrite`: the
+image codec of every tool."""
+from __future__ import annotations
+
+import collections
+import copy
+import os
+from concurrent.futures import Future, ThreadPoolExecutor
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops, y4m
+
+MIN_SIZE = 20
+IMAGE_EXTS = (".png", ".jpg", ".jpeg", ".bmp")
+
+padded_size = ops.padded_size
+
+
+def imread(path: str) -> np.ndarray:
+    from PIL import Image
+    return np.asarray(Image.open(path).convert("RGB"))
+
+
+def imwrite(path: str, img: np.ndarray) -> None:
+    """Lossless PNG at zlib level 1: the reference writes with cv2.imwrite's default, OpenCV's "best speed" PNG setting
+    (inference_SPEINet.py:415-417); PIL's own default (level 6) costs twice the encode time for 10 % smaller files."""
+    from PIL import Image
+    Image.fromarray(img).save(path, compress_level=1)
+
+
+class FrameCache:
+    """Decode-once, upload-once cache of frames: `load(key)` decodes one (host uint8 [H,W,3]).  `request(keys)` schedules decodes on
+    the thread pool; `get_dev(key)` returns the frame on the device, uploaded once however many windows share it (a frame is a
+    neighbour twice, a middle frame once and often a reference).  Uploads go through a small ring of page-locked staging buffers
+    allocated once: a copy from pageable memory makes the host wait for everything queued on the stream before it (one full GPU drain
+    per window), and allocating page-locked memory per frame synchronises the device.  Bounded LRUs (a 720p RGB frame is 2.8 MB)."""
+    RING = 8
+
+    def __init__(self, pool: ThreadPoolExecutor, load, device, capacity: int = 16, convert=None):
+        self.pool, self.load, self.device, self.capacity = pool, load, device, capacity
+        self.convert = convert           # uploaded bytes -> the frame that is kept (planar YUV -> packed RGB, on the device)
+        self.items: "collections.OrderedDict[object, Future]" = collections.OrderedDict()
+        self.dev: "collections.OrderedDict[object, torch.Tensor]" = collections.OrderedDict()
+        self._ring, self._events, self._n = [], [], 0
+
+    def request(self, keys) -> None:
+        for p in keys:
+            if p in self.items:
+                self.items.move_to_end(p)
+            elif p not in self.dev:
+                self.items[p] = self.pool.submit(self.load, p)
+        while len(self.items) > self.capacity:
+            self.items.popitem(last=False)
+
+    def _upload(self, arr: np.ndarray) -> torch.Tensor:
+        n = arr.nbytes
+        if not self._ring or self._ring[0].numel() < n:
+            self._ring = [torch.empty(n, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
+            self._events = [None] * self.RING
+        i = self._n % self.RING
+        self._n += 1
+        if self._events[i] is not None:
+            self._events[i].synchronize()                 # the copy issued RING uploads ago: long finished
+        stage = self._ring[i][:n]
+        if arr.dtype == np.uint16:                        # a deep frame crosses as its bytes
+            stage = stage.view(torch.uint16)
+        stage = stage.view(arr.shape)
+        stage.numpy()[...] = arr
+        t = stage.to(self.device, non_blocking=True)
+        self._events[i] = torch.cuda.Event()
+        self._events[i].record()
+        return t
+
+    def get_dev(self, key) -> torch.Tensor:
+        t = self.dev.get(key)
+        if t is None:
+            self.request([key])
+            t = self._upload(self.items.pop(key).result())
+            t = self.dev[key] = t if self.convert is None else self.convert(t)
+            while len(self.dev) > self.capacity:
+                self.dev.popitem(last=False)
+        else:
+            self.dev.move_to_end(key)
+        return t
+
+
+class HostRing:
+    """Finished frames landed in page-locked memory for worker threads: `land(fn, *tensors)` queues the device->host copies of the
+    tensors on the current stream, behind whatever produced them, and returns the future of `fn(*host_tensors)`, which runs on the
+    pool once those copies are done.  A worker waits on its own copies only: a `.cpu()` from a worker thread is a synchronous copy on
+    the stream and would wait for every window queued after its own as well.  `n` slots in turn, a slot reused once its last worker
+    has finished; the buffers are allocated once per set of shapes (allocating page-locked memory synchronises the device)."""
+
+    def __init__(self, pool: ThreadPoolExecutor, n: int = 8):
+        self.pool, self.n, self.k = pool, n, 0
+        self.bufs, self.futs = [], [None] * n
+
+    def land(self, fn, *tensors) -> Future:
+        if not self.bufs or [(b.shape, b.dtype) for b in self.bufs[0]] != [(t.shape, t.dtype) for t in tensors]:
+            self.drain()
+            self.bufs = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors] for _ in range(self.n)]
+        i = self.k % self.n
+        self.k += 1
+        if self.futs[i] is not None:
+            self.futs[i].result()
+        for b, t in zip(self.bufs[i], tensors):
+            b.copy_(t, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.futs[i] = self.pool.submit(self._work, fn, ev, self.bufs[i])
+        return self.futs[i]
+
+    @staticmethod
+    def _work(fn, ev, bufs):
+        ev.synchronize()
+        return fn(*bufs)
+
+    def drain(self) -> None:
+        for f in self.futs:
+            if f is not None:
+                f.result()
+
+
+def reflect_index(n: int, n_pad: Optional[int] = None) -> np.ndarray:
+    """Source row (or column) of each of the n_pad padded rows of a dimension of n: i < n reads i, n + j reads n - 2 - j (torch F.pad
+    mode "reflect"; what spei_frames_u8_in computes in its pad band)."""
+    n_pad = padded_size(n) if n_pad is None else n_pad
+    if not n_pad - n < n:
+        raise ValueError(f"reflect padding of {n} to {n_pad} needs a pad smaller than {n}")
+    i = np.arange(n_pad)
+    return np.where(i < n, i, 2 * n - 2 - i)
+
+
+class Frames:
+    """The clip behind one interface: frame i as a host uint8 [H,W,3] array (`host`) or a device tensor (`device`), cropped at the
+    bottom and right to H x W (`crop`: the source size rounded down to multiples of 20; otherwise the source size).  A y4m clip
+    (`yuv`: its (layout, matrix, range); `items` the `Y4MReader`) is the exception: `host` returns the frame's planar bytes as they
+    are in the file, and `rgb` turns uploaded planar frames into the cropped RGB frames on the device.  `depth`: 8 (uint8 frames), or
+    10 / 12 (uint16 frames: `dtype`; the planar bytes of a deep y4m clip are still uint8, two per sample).  `view` is the same clip
+    seen through a rectangle (the region of interest: the analysis pass is handed that view), `sample` a subset of its frames."""
+
+    def __init__(self, items, T: int, H: int, W: int, paths: bool, crop: bool = False, yuv=None, depth: int = 8):
+        self.items, self.T, self.paths, self.src, self.yuv, self.depth = items, T, paths, (H, W), yuv, depth
+        self.dtype = torch.uint8 if depth == 8 else torch.uint16
+        self.H, self.W = (H - H % 20, W - W % 20) if crop else (H, W)
+        self.y0 = self.x0 = 0            # the origin of the H x W view in the source frames (`view`: a rectangle)
+        self.index = None                # the source frame of each of the T frames (`sample`: a subset); None: all, in order
+
+    def view(self, rect) -> "Frames":
+        """The same clip seen through the rectangle (y0, x0, h, w) of this view: `device`, `host` and `rgb` hand out the cropped
+        frames, H and W are the rectangle's.  Nothing is copied."""
+        y0, x0, h, w = rect
+        assert 0 <= y0 and 0 <= x0 and y0 + h <= self.H and x0 + w <= self.W
+        v = copy.copy(self)
+        v.y0, v.x0, v.H, v.W = self.y0 + y0, self.x0 + x0, h, w
+        return v
+
+    def sample(self, index) -> "Frames":
+        """The clip of the frames `index` (indices into this one) of this clip.  Nothing is copied."""
+        v = copy.copy(self)
+        v.index = [self._at(int(i)) for i in index]
+        v.T = len(v.index)
+        return v
+
+    def _at(self, i: int) -> int:
+        return i if self.index is None else self.index[i]
+
+    def _crop(self, f):
+        return f[..., self.y0:self.y0 + self.H, self.x0:self.x0 + self.W, :]
+
+    def on_device(self, i: int) -> bool:
+        if self.yuv is not None:
+            return False
+        f = self.items[self._at(i)]
+        return torch.is_tensor(f) and f.is_cuda
+
+    def rgb(self, planar: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Planar frames [N, frame_bytes] (uint8: the file's bytes) of a y4m clip on the device -> uint8 [N,H,W,3] there
+        (`ops.yuv_to_rgb_u8`), or uint16 for a deep clip (`ops.yuv_to_rgb_u16` on the bytes viewed as words); cropped after the
+        conversion, into the contiguous `out` if given."""
+        if self.depth == 8:
+            convert = ops.yuv_to_rgb_u8
+        else:
+            planar = planar.view(torch.uint16)
+
+            def convert(p, h, w, *how, out=None):
+                return ops.yuv_to_rgb_u16(p, h, w, *how, self.depth, out=out)
+        if (self.H, self.W) == self.src:
+            return convert(planar, self.H, self.W, *self.yuv, out=out)
+        full = self._crop(convert(planar, *self.src, *self.yuv))
+        return full.contiguous() if out is None else out.copy_(full)
+
+    def device(self, i: int) -> torch.Tensor:
+        return self._crop(self.items[self._at(i)])
+
+    def host(self, i: int) -> np.ndarray:
+        if self.yuv is not None:
+            return self.items.raw(self._at(i))
+        f = self.items[self._at(i)]
+        if self.paths:
+            img = imread(f)
+            if img.shape[:2] != self.src:
+                raise ValueError(f"frame {i} ({f}) is {img.shape[1]}x{img.shape[0]}, the clip is {self.src[1]}x{self.src[0]}")
+        else:
+            img = f.numpy() if torch.is_tensor(f) else np.asarray(f)
+        return self._crop(img)
+
+
+def _check_frame(i, shape, dtype, depth=None) -> None:
+    if dtype in (np.uint16, torch.uint16):
+        if depth is None:
+            raise ValueError(f"uint16 frames need depth=10 or depth=12 (bits per sample); frame {i} is {dtype}")
+    elif depth is not None:
+        raise ValueError(f"depth= applies to uint16 frames only; frame {i} is {dtype}")
+    elif dtype not in (np.uint8, torch.uint8):
+        raise ValueError(f"frames must be uint8, or uint16 with depth=; frame {i} is {dtype}")
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"frames must be 3-channel HWC arrays [H,W,3]; frame {i} has shape {tuple(shape)}")
+    if shape[0] < MIN_SIZE or shape[1] < MIN_SIZE:
+        raise ValueError(f"frames must be at least {MIN_SIZE}x{MIN_SIZE}; frame {i} is {shape[1]}x{shape[0]}")
+
+
+def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None, depth: Optional[int] = None) -> Frames:
+    """Validate a clip: a uint8 [T,H,W,3] array or tensor (host or device), a list of uint8 [H,W,3] arrays / tensors, a list of
+    image paths (only their headers are read here), or a `y4m.Y4MReader` (`yuv`: optional `matrix` / `range` in place of the
+    reader's; a reader opened with `depths=(8, 10, 12)` may hold a deep clip).  uint16 arrays, tensors or lists of them are deep
+    frames and need `depth` = 10 or 12 (bits per sample; a word above 2^depth - 1 reads as that); `depth` with anything else is an
+    error.  Raises ValueError with the reason."""
+    if depth is not None and (isinstance(depth, bool) or depth not in (10, 12)):
+        raise ValueError(f"depth must be 10 or 12, got {depth!r}")
+    if isinstance(frames, y4m.Y4MReader):
+        if depth is not None:
+            raise ValueError("depth= applies to uint16 frames only: a y4m clip carries its own")
+        if set(yuv or {}) - {"matrix", "range"}:
+            raise ValueError(f"yuv holds {sorted(set(yuv) - {'matrix', 'range'})}: it takes matrix and range")
+        if len(frames) < 2:
+            raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {len(frames)}")
+        _check_frame(0, (frames.height, frames.width, 3), np.uint8)
+        how = (frames.layout, y4m.matrix_of((yuv or {}).get("matrix", frames.matrix)), y4m.range_of((yuv or {}).get("range", frames.range)))
+        return Frames(frames, len(frames), frames.height, frames.width, paths=False, crop=crop, yuv=how, depth=frames.depth)
+    if yuv is not None:
+        raise ValueError("yuv= applies to y4m clips only")
+    if isinstance(frames, (str, bytes)) or not hasattr(frames, "__len__") or not hasattr(frames, "__getitem__"):
+        raise ValueError(f"frames must be an indexable sequence of frames, got {type(frames).__name__}")
+    T = len(frames)
+    if T < 2:
+        raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {T}")
+    if isinstance(frames, (np.ndarray, torch.Tensor)):
+        if frames.ndim != 4:
+            raise ValueError(f"a frame array must be [T,H,W,3]; got shape {tuple(frames.shape)}")
+        _check_frame(0, tuple(frames.shape[1:]), frames.dtype, depth)
+        return Frames(frames, T, int(frames.shape[1]), int(frames.shape[2]), paths=False, crop=crop, depth=depth or 8)
+    items = list(frames)
+    is_path = [isinstance(f, (str, os.PathLike)) for f in items]
+    if any(is_path) and not all(is_path):
+        raise ValueError("frames mixes image paths and arrays")
+    if all(is_path):
+        if depth is not None:
+            raise ValueError("depth= applies to uint16 frames only: image files are read as 8-bit")
+        from PIL import Image
+        sizes = []
+        for p in items:
+            with Image.open(p) as im:           # the header only: decoding happens later, on worker threads
+                sizes.append((im.size[1], im.size[0]))
+        for i, (h, w) in enumerate(sizes):
+            _check_frame(i, (h, w, 3), np.uint8)
+            if (h, w) != sizes[0]:
+                raise ValueError(f"mixed frame sizes: frame 0 is {sizes[0][1]}x{sizes[0][0]}, frame {i} ({items[i]}) is {w}x{h}")
+        return Frames([os.fspath(p) for p in items], T, sizes[0][0], sizes[0][1], paths=True, crop=crop)
+    for i, f in enumerate(items):
+        if not isinstance(f, (np.ndarray, torch.Tensor)):
+            raise ValueError(f"frame {i} is a {type(f).__name__}, not an array, tensor or image path")
+        _check_frame(i, tuple(f.shape), f.dtype, depth)
+        if tuple(f.shape) != tuple(items[0].shape):
+            raise ValueError(f"mixed frame sizes: frame 0 is {items[0].shape[1]}x{items[0].shape[0]}, frame {i} is {f.shape[1]}x{f.shape[0]}")
+    return Frames(items, T, int(items[0].shape[0]), int(items[0].shape[1]), paths=False, crop=crop, depth=depth or 8)
+

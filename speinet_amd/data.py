@@ -48,6 +48,7 @@ from . import codec as _codec
 from . import light as _light
 from . import selection
 from . import shake as _shake
+from .clip import frames_of, imread
 from .recipe import Recipe
 
 MAX_GAP = 7
@@ -121,7 +122,6 @@ class ClipSet(Windows):
 
     def __init__(self, dir_data: str, train: bool, n_sequence: int = 3, n_frames_per_video: int = 200, references: bool = True,
                  patch: Optional[int] = None):
-        from .video import frames_of
         self.dir_data, self.train, self.n_seq, self.references = dir_data, bool(train), int(n_sequence), bool(references)
         if self.references and self.n_seq != 3:
             raise ValueError("samples with references are windows of 3 frames (the reference's zeroing test reads names 2 and 3: videodata_nfs.py:254)")
@@ -192,7 +192,6 @@ class SharpClipSet(Windows):
                  n_frames_per_video: int = 200, references: bool = True, patch: Optional[int] = None, light="code", noise=None,
                  shake=None, frames: str = "runs", codec=None):
         from .blurset import clip_folders
-        from .video import frames_of
         self.dir_data, self.train, self.n_seq, self.references = dir_sharp, True, int(n_sequence), bool(references)
         if self.references and self.n_seq != 3:
             raise ValueError("samples with references are windows of 3 frames (the reference's zeroing test reads names 2 and 3: videodata_nfs.py:254)")
@@ -314,13 +313,12 @@ class ClipStore:
                               f"{budget_bytes} bytes; {otherwise}")
 
     def _load(self, pool, clip, paths) -> torch.Tensor:
-        from .video import _imread
         T, H, W = clip["T"], clip["H"], clip["W"]
         host = torch.empty((T, H, W, 3), dtype=torch.uint8, pin_memory=self.residency == "host")
         arr = host.numpy()
 
         def one(i):
-            img = _imread(paths[i])
+            img = imread(paths[i])
             if img.shape != (H, W, 3):
                 raise ValueError(f"{paths[i]} decodes to {img.shape}, its header said {W}x{H}")
             arr[i] = img
@@ -517,7 +515,7 @@ class TrainLoader:
     staging copies) as well as the launch — runs on a worker thread that is started when batch k is handed out, so it overlaps step k
     on both the host and the device; without it, `_launch` runs in the consumer's thread when the batch is asked for.  The output
     tensors are allocated on the side stream and handed to the consumer's stream with `record_stream`.  A slot is rewritten only after
-    its event has completed (the discipline of video.FrameCache).  Host residency: the patch rectangles of the batch are first copied,
+    its event has completed (the discipline of clip.FrameCache).  Host residency: the patch rectangles of the batch are first copied,
     row range by row range, into the slot's page-locked staging buffer and uploaded with one asynchronous copy; the records then point
     into the uploaded rectangles (offsets rebased to 0) and go through the same kernel, so the results are bit-identical."""
     RING = 3

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .clip import IMAGE_EXTS, frames_of
 
 DETECT_BATCH = 16                # frames per launch of a streaming feature pass (the harness's batch)
 
@@ -111,7 +112,7 @@ def predict(features, params: Optional[DetectorParams] = None) -> np.ndarray:
 
 
 def clip_batches(fr, device, batch: int = DETECT_BATCH):
-    """One streaming pass over a clip (`video.frames_of`'s result): yields (first frame index, uint8 [n,H,W,3] device view) for every
+    """One streaming pass over a clip (`clip.frames_of`'s result): yields (first frame index, uint8 [n,H,W,3] device view) for every
     `batch` frames in turn, on the current stream of `device`.  Host frames are uploaded from two page-locked staging buffers (image
     paths decoded on worker threads two batches ahead), device-resident frames copied on the device.  The frames of a y4m clip are
     staged and uploaded as their planar bytes and made RGB on the device (`fr.rgb`: ops.yuv_to_rgb_u8, or ops.yuv_to_rgb_u16 for a
@@ -188,7 +189,7 @@ def clip_pass(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, feat
 
 
 def clip_features(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH) -> torch.Tensor:
-    """The six measures of every frame of a clip (`video.frames_of`'s result), `batch` frames at a time: uint8 upload from two
+    """The six measures of every frame of a clip (`clip.frames_of`'s result), `batch` frames at a time: uint8 upload from two
     page-locked staging buffers, gray planes (spei_frames_u8_in), focus measures.  Image paths are decoded on worker threads two
     batches ahead.  [T,6] float32 on `device`; device memory is bounded by one batch."""
     return clip_pass(fr, device, kernel_size, batch)[0]
@@ -196,7 +197,6 @@ def clip_features(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH) 
 
 def _clips(dir_data: str) -> list:
     """(clip name, its frames in file-name order) for every folder under dir_data/blur, as data.ClipSet scans them."""
-    from .video import IMAGE_EXTS
     root = os.path.join(dir_data, "blur")
     if not os.path.isdir(root):
         raise ValueError(f"{dir_data}: no blur/ directory (one folder of frames per clip)")
@@ -216,7 +216,6 @@ def dataset_features(dir_data: str, kernel_size: int = 11, device="cuda"):
     """The six measures of every frame of every `blur/<clip>` under dir_data, streamed through `clip_features` (reference
     collate_all_vars, sharp_detector_params_estimation_parallel.py:221-237, on frames that are already blurred).
     -> (features [N,6] float32, labels [N] int64 from label/<clip>.npy or None when a clip has none, clip names, frames per clip)."""
-    from .video import frames_of
     feats, labels, names, counts = [], [], [], []
     for name, files in _clips(dir_data):
         try:

@@ -27,9 +27,11 @@ import numpy as np
 import torch
 
 from . import checkpoint, detector, ops, selection, video
+from .clip import FrameCache, HostRing, imread, imwrite
 from .dist import gather_metrics, shard_clips_by_length
 from .speinet import SPEINet, default_args
-from .video import FrameCache, HostRing, _imread, _imwrite
+
+_imread, _imwrite = imread, imwrite
 
 
 def calc_ssim(img1: np.ndarray, img2: np.ndarray) -> float:
@@ -101,7 +103,7 @@ class Inference:
         p = os.path.join(self.args.data_path, "label", clip + ".npy")
         if os.path.exists(p):
             return np.load(p)                                   # allow_pickle=False: plain int arrays only
-        imgs = torch.from_numpy(np.stack([_imread(f) for f in frames]).astype(np.float32)).permute(0, 3, 1, 2)
+        imgs = torch.from_numpy(np.stack([imread(f) for f in frames]).astype(np.float32)).permute(0, 3, 1, 2)
         feats = torch.cat([detector.focus_measures(imgs[i:i + 16].to(self.device), 11) for i in range(0, len(imgs), 16)])
         return detector.predict(feats)
 
@@ -110,7 +112,7 @@ class Inference:
         """Worker thread, once the frame and its metrics have landed: encode the PNG.  Returns (PSNR, SSIM, seconds)."""
         t0 = time.time()
         if save_to:
-            _imwrite(save_to, frame.numpy())
+            imwrite(save_to, frame.numpy())
         psnr, ssim = met.tolist()
         return psnr, ssim, time.time() - t0
 
@@ -129,7 +131,7 @@ class Inference:
             run = video.deblur_clip(self.net, blur, self.labels_for(clip, blur), crop=True,
                                     numbers=[selection.frame_number(f) for f in blur])
             H, W = run.frames.H, run.frames.W                   # the model needs multiples of 20 (reference crops to 4)
-            gt_cache = FrameCache(self.pool, lambda p: _imread(p)[:H, :W], self.device)
+            gt_cache = FrameCache(self.pool, lambda p: imread(p)[:H, :W], self.device)
             if a.save_image:
                 os.makedirs(os.path.join(a.result_path, clip), exist_ok=True)
             vp, vs = [], []

@@ -20,8 +20,7 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     data sets are one folder per shot);
   * the windows — `forward_window` with a per-clip `EncoderCache`, `prefetch_window` one window ahead, windows alternating over two
     launch streams that the model keeps, in whatever `precision` / `corr_precision` / `use_graph` / `streams` the caller set on it;
-  * frames cross PCIe as uint8 from page-locked staging buffers (`FrameCache`) and are decoded, for image paths, on worker threads a
-    few windows ahead; a window whose 16-bit pass left a non-finite value is recomputed in bf16x3;
+  * the frames come from speinet_amd.clip (`frames_of`, `FrameCache`); a window whose 16-bit pass left a non-finite value is recomputed in bf16x3;
   * a y4m clip (speinet_amd.y4m) crosses PCIe as its planar bytes, 1.5 per pixel for 4:2:0, and becomes packed RGB on the device
     (csrc/yuv_io.hip, integer arithmetic); a y4m output is made there from the deblurred frame the same way;
   * a deep clip (10 or 12 bits per sample: a `C420p10` ... `C444p12` y4m stream, or uint16 frames with `depth=`) never passes through
@@ -55,292 +54,30 @@ from __future__ import annotations
 
 import argparse
 import collections
-import copy
 import glob
 import os
 import sys
 import time
 import warnings
-from concurrent.futures import Future, ThreadPoolExecutor
+from concurrent.futures import ThreadPoolExecutor
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import detector, engine, ensemble as ens, ops, selection, tiles as tiling, y4m
+from .clip import IMAGE_EXTS, MIN_SIZE, FrameCache, Frames, HostRing, frames_of, imread, imwrite, padded_size, reflect_index  # noqa: F401
 from .speinet import EncoderCache
 
+_imread, _imwrite = imread, imwrite
+
 ZERO = ("zero",)                 # window key of a zeroed reference frame
-MIN_SIZE = 20
-IMAGE_EXTS = (".png", ".jpg", ".jpeg", ".bmp")
 CORR_PRECISION = {"f32": "bf16x3", "bf16x3": "bf16x3", "bf16": "top2", "f16": "top2"}    # correlation arithmetic per precision
 DETECT_BATCH = 16                # frames per launch of the labelling pass (the harness's batch)
 PREFETCH = 4                     # windows decoded ahead of the GPU
 LANES = 2                        # launch streams the windows alternate over (3 and 4 measured 8-25 % slower than 2 on 720p)
 LAG = 2                          # windows enqueued after a frame before it is handed out
 FLAG_RING = 8                    # non-finite flags in flight (> LAG + 1)
-
-padded_size = ops.padded_size
-
-
-def _imread(path: str) -> np.ndarray:
-    from PIL import Image
-    return np.asarray(Image.open(path).convert("RGB"))
-
-
-def _imwrite(path: str, img: np.ndarray) -> None:
-    """Lossless PNG at zlib level 1: the reference writes with cv2.imwrite's default, OpenCV's "best speed" PNG setting
-    (inference_SPEINet.py:415-417); PIL's own default (level 6) costs twice the encode time for 10 % smaller files."""
-    from PIL import Image
-    Image.fromarray(img).save(path, compress_level=1)
-
-
-class FrameCache:
-    """Decode-once, upload-once cache of frames: `load(key)` decodes one (host uint8 [H,W,3]).  `request(keys)` schedules decodes on
-    the thread pool; `get_dev(key)` returns the frame on the device, uploaded once however many windows share it (a frame is a
-    neighbour twice, a middle frame once and often a reference).  Uploads go through a small ring of page-locked staging buffers
-    allocated once: a copy from pageable memory makes the host wait for everything queued on the stream before it (one full GPU drain
-    per window), and allocating page-locked memory per frame synchronises the device.  Bounded LRUs (a 720p RGB frame is 2.8 MB)."""
-    RING = 8
-
-    def __init__(self, pool: ThreadPoolExecutor, load, device, capacity: int = 16, convert=None):
-        self.pool, self.load, self.device, self.capacity = pool, load, device, capacity
-        self.convert = convert           # uploaded bytes -> the frame that is kept (planar YUV -> packed RGB, on the device)
-        self.items: "collections.OrderedDict[object, Future]" = collections.OrderedDict()
-        self.dev: "collections.OrderedDict[object, torch.Tensor]" = collections.OrderedDict()
-        self._ring, self._events, self._n = [], [], 0
-
-    def request(self, keys) -> None:
-        for p in keys:
-            if p in self.items:
-                self.items.move_to_end(p)
-            elif p not in self.dev:
-                self.items[p] = self.pool.submit(self.load, p)
-        while len(self.items) > self.capacity:
-            self.items.popitem(last=False)
-
-    def _upload(self, arr: np.ndarray) -> torch.Tensor:
-        n = arr.nbytes
-        if not self._ring or self._ring[0].numel() < n:
-            self._ring = [torch.empty(n, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
-            self._events = [None] * self.RING
-        i = self._n % self.RING
-        self._n += 1
-        if self._events[i] is not None:
-            self._events[i].synchronize()                 # the copy issued RING uploads ago: long finished
-        stage = self._ring[i][:n]
-        if arr.dtype == np.uint16:                        # a deep frame crosses as its bytes
-            stage = stage.view(torch.uint16)
-        stage = stage.view(arr.shape)
-        stage.numpy()[...] = arr
-        t = stage.to(self.device, non_blocking=True)
-        self._events[i] = torch.cuda.Event()
-        self._events[i].record()
-        return t
-
-    def get_dev(self, key) -> torch.Tensor:
-        t = self.dev.get(key)
-        if t is None:
-            self.request([key])
-            t = self._upload(self.items.pop(key).result())
-            t = self.dev[key] = t if self.convert is None else self.convert(t)
-            while len(self.dev) > self.capacity:
-                self.dev.popitem(last=False)
-        else:
-            self.dev.move_to_end(key)
-        return t
-
-
-class HostRing:
-    """Finished frames landed in page-locked memory for worker threads: `land(fn, *tensors)` queues the device->host copies of the
-    tensors on the current stream, behind whatever produced them, and returns the future of `fn(*host_tensors)`, which runs on the
-    pool once those copies are done.  A worker waits on its own copies only: a `.cpu()` from a worker thread is a synchronous copy on
-    the stream and would wait for every window queued after its own as well.  `n` slots in turn, a slot reused once its last worker
-    has finished; the buffers are allocated once per set of shapes (allocating page-locked memory synchronises the device)."""
-
-    def __init__(self, pool: ThreadPoolExecutor, n: int = 8):
-        self.pool, self.n, self.k = pool, n, 0
-        self.bufs, self.futs = [], [None] * n
-
-    def land(self, fn, *tensors) -> Future:
-        if not self.bufs or [(b.shape, b.dtype) for b in self.bufs[0]] != [(t.shape, t.dtype) for t in tensors]:
-            self.drain()
-            self.bufs = [[torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors] for _ in range(self.n)]
-        i = self.k % self.n
-        self.k += 1
-        if self.futs[i] is not None:
-            self.futs[i].result()
-        for b, t in zip(self.bufs[i], tensors):
-            b.copy_(t, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.futs[i] = self.pool.submit(self._work, fn, ev, self.bufs[i])
-        return self.futs[i]
-
-    @staticmethod
-    def _work(fn, ev, bufs):
-        ev.synchronize()
-        return fn(*bufs)
-
-    def drain(self) -> None:
-        for f in self.futs:
-            if f is not None:
-                f.result()
-
-
-def reflect_index(n: int, n_pad: Optional[int] = None) -> np.ndarray:
-    """Source row (or column) of each of the n_pad padded rows of a dimension of n: i < n reads i, n + j reads n - 2 - j (torch F.pad
-    mode "reflect"; what spei_frames_u8_in computes in its pad band)."""
-    n_pad = padded_size(n) if n_pad is None else n_pad
-    if not n_pad - n < n:
-        raise ValueError(f"reflect padding of {n} to {n_pad} needs a pad smaller than {n}")
-    i = np.arange(n_pad)
-    return np.where(i < n, i, 2 * n - 2 - i)
-
-
-class _Frames:
-    """The clip behind one interface: frame i as a host uint8 [H,W,3] array (`host`) or a device tensor (`device`), cropped at the
-    bottom and right to H x W (`crop`: the source size rounded down to multiples of 20; otherwise the source size).  A y4m clip
-    (`yuv`: its (layout, matrix, range); `items` the `Y4MReader`) is the exception: `host` returns the frame's planar bytes as they
-    are in the file, and `rgb` turns uploaded planar frames into the cropped RGB frames on the device.  `depth`: 8 (uint8 frames), or
-    10 / 12 (uint16 frames: `dtype`; the planar bytes of a deep y4m clip are still uint8, two per sample).  `view` is the same clip
-    seen through a rectangle (the region of interest: the analysis pass is handed that view), `sample` a subset of its frames."""
-
-    def __init__(self, items, T: int, H: int, W: int, paths: bool, crop: bool = False, yuv=None, depth: int = 8):
-        self.items, self.T, self.paths, self.src, self.yuv, self.depth = items, T, paths, (H, W), yuv, depth
-        self.dtype = torch.uint8 if depth == 8 else torch.uint16
-        self.H, self.W = (H - H % 20, W - W % 20) if crop else (H, W)
-        self.y0 = self.x0 = 0            # the origin of the H x W view in the source frames (`view`: a rectangle)
-        self.index = None                # the source frame of each of the T frames (`sample`: a subset); None: all, in order
-
-    def view(self, rect) -> "_Frames":
-        """The same clip seen through the rectangle (y0, x0, h, w) of this view: `device`, `host` and `rgb` hand out the cropped
-        frames, H and W are the rectangle's.  Nothing is copied."""
-        y0, x0, h, w = rect
-        assert 0 <= y0 and 0 <= x0 and y0 + h <= self.H and x0 + w <= self.W
-        v = copy.copy(self)
-        v.y0, v.x0, v.H, v.W = self.y0 + y0, self.x0 + x0, h, w
-        return v
-
-    def sample(self, index) -> "_Frames":
-        """The clip of the frames `index` (indices into this one) of this clip.  Nothing is copied."""
-        v = copy.copy(self)
-        v.index = [self._at(int(i)) for i in index]
-        v.T = len(v.index)
-        return v
-
-    def _at(self, i: int) -> int:
-        return i if self.index is None else self.index[i]
-
-    def _crop(self, f):
-        return f[..., self.y0:self.y0 + self.H, self.x0:self.x0 + self.W, :]
-
-    def on_device(self, i: int) -> bool:
-        if self.yuv is not None:
-            return False
-        f = self.items[self._at(i)]
-        return torch.is_tensor(f) and f.is_cuda
-
-    def rgb(self, planar: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Planar frames [N, frame_bytes] (uint8: the file's bytes) of a y4m clip on the device -> uint8 [N,H,W,3] there
-        (`ops.yuv_to_rgb_u8`), or uint16 for a deep clip (`ops.yuv_to_rgb_u16` on the bytes viewed as words); cropped after the
-        conversion, into the contiguous `out` if given."""
-        if self.depth == 8:
-            convert = ops.yuv_to_rgb_u8
-        else:
-            planar = planar.view(torch.uint16)
-
-            def convert(p, h, w, *how, out=None):
-                return ops.yuv_to_rgb_u16(p, h, w, *how, self.depth, out=out)
-        if (self.H, self.W) == self.src:
-            return convert(planar, self.H, self.W, *self.yuv, out=out)
-        full = self._crop(convert(planar, *self.src, *self.yuv))
-        return full.contiguous() if out is None else out.copy_(full)
-
-    def device(self, i: int) -> torch.Tensor:
-        return self._crop(self.items[self._at(i)])
-
-    def host(self, i: int) -> np.ndarray:
-        if self.yuv is not None:
-            return self.items.raw(self._at(i))
-        f = self.items[self._at(i)]
-        if self.paths:
-            img = _imread(f)
-            if img.shape[:2] != self.src:
-                raise ValueError(f"frame {i} ({f}) is {img.shape[1]}x{img.shape[0]}, the clip is {self.src[1]}x{self.src[0]}")
-        else:
-            img = f.numpy() if torch.is_tensor(f) else np.asarray(f)
-        return self._crop(img)
-
-
-def _check_frame(i, shape, dtype, depth=None) -> None:
-    if dtype in (np.uint16, torch.uint16):
-        if depth is None:
-            raise ValueError(f"uint16 frames need depth=10 or depth=12 (bits per sample); frame {i} is {dtype}")
-    elif depth is not None:
-        raise ValueError(f"depth= applies to uint16 frames only; frame {i} is {dtype}")
-    elif dtype not in (np.uint8, torch.uint8):
-        raise ValueError(f"frames must be uint8, or uint16 with depth=; frame {i} is {dtype}")
-    if len(shape) != 3 or shape[2] != 3:
-        raise ValueError(f"frames must be 3-channel HWC arrays [H,W,3]; frame {i} has shape {tuple(shape)}")
-    if shape[0] < MIN_SIZE or shape[1] < MIN_SIZE:
-        raise ValueError(f"frames must be at least {MIN_SIZE}x{MIN_SIZE}; frame {i} is {shape[1]}x{shape[0]}")
-
-
-def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None, depth: Optional[int] = None) -> _Frames:
-    """Validate a clip: a uint8 [T,H,W,3] array or tensor (host or device), a list of uint8 [H,W,3] arrays / tensors, a list of
-    image paths (only their headers are read here), or a `y4m.Y4MReader` (`yuv`: optional `matrix` / `range` in place of the
-    reader's; a reader opened with `depths=(8, 10, 12)` may hold a deep clip).  uint16 arrays, tensors or lists of them are deep
-    frames and need `depth` = 10 or 12 (bits per sample; a word above 2^depth - 1 reads as that); `depth` with anything else is an
-    error.  Raises ValueError with the reason."""
-    if depth is not None and (isinstance(depth, bool) or depth not in (10, 12)):
-        raise ValueError(f"depth must be 10 or 12, got {depth!r}")
-    if isinstance(frames, y4m.Y4MReader):
-        if depth is not None:
-            raise ValueError("depth= applies to uint16 frames only: a y4m clip carries its own")
-        if set(yuv or {}) - {"matrix", "range"}:
-            raise ValueError(f"yuv holds {sorted(set(yuv) - {'matrix', 'range'})}: it takes matrix and range")
-        if len(frames) < 2:
-            raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {len(frames)}")
-        _check_frame(0, (frames.height, frames.width, 3), np.uint8)
-        how = (frames.layout, y4m.matrix_of((yuv or {}).get("matrix", frames.matrix)), y4m.range_of((yuv or {}).get("range", frames.range)))
-        return _Frames(frames, len(frames), frames.height, frames.width, paths=False, crop=crop, yuv=how, depth=frames.depth)
-    if yuv is not None:
-        raise ValueError("yuv= applies to y4m clips only")
-    if isinstance(frames, (str, bytes)) or not hasattr(frames, "__len__") or not hasattr(frames, "__getitem__"):
-        raise ValueError(f"frames must be an indexable sequence of frames, got {type(frames).__name__}")
-    T = len(frames)
-    if T < 2:
-        raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {T}")
-    if isinstance(frames, (np.ndarray, torch.Tensor)):
-        if frames.ndim != 4:
-            raise ValueError(f"a frame array must be [T,H,W,3]; got shape {tuple(frames.shape)}")
-        _check_frame(0, tuple(frames.shape[1:]), frames.dtype, depth)
-        return _Frames(frames, T, int(frames.shape[1]), int(frames.shape[2]), paths=False, crop=crop, depth=depth or 8)
-    items = list(frames)
-    is_path = [isinstance(f, (str, os.PathLike)) for f in items]
-    if any(is_path) and not all(is_path):
-        raise ValueError("frames mixes image paths and arrays")
-    if all(is_path):
-        if depth is not None:
-            raise ValueError("depth= applies to uint16 frames only: image files are read as 8-bit")
-        from PIL import Image
-        sizes = []
-        for p in items:
-            with Image.open(p) as im:           # the header only: decoding happens later, on worker threads
-                sizes.append((im.size[1], im.size[0]))
-        for i, (h, w) in enumerate(sizes):
-            _check_frame(i, (h, w, 3), np.uint8)
-            if (h, w) != sizes[0]:
-                raise ValueError(f"mixed frame sizes: frame 0 is {sizes[0][1]}x{sizes[0][0]}, frame {i} ({items[i]}) is {w}x{h}")
-        return _Frames([os.fspath(p) for p in items], T, sizes[0][0], sizes[0][1], paths=True, crop=crop)
-    for i, f in enumerate(items):
-        if not isinstance(f, (np.ndarray, torch.Tensor)):
-            raise ValueError(f"frame {i} is a {type(f).__name__}, not an array, tensor or image path")
-        _check_frame(i, tuple(f.shape), f.dtype, depth)
-        if tuple(f.shape) != tuple(items[0].shape):
-            raise ValueError(f"mixed frame sizes: frame 0 is {items[0].shape[1]}x{items[0].shape[0]}, frame {i} is {f.shape[1]}x{f.shape[0]}")
-    return _Frames(items, T, int(items[0].shape[0]), int(items[0].shape[1]), paths=False, crop=crop, depth=depth or 8)
 
 
 def labels_of(labels, T: int) -> np.ndarray:
@@ -404,10 +141,10 @@ def find_cuts(sad, hist, pixels: int, *, hist_min: float = 0.25, ratio: float = 
 def scene_stats(frames, device):
     """The pair statistics of a clip (anything `frames_of` accepts) in one streaming pass of DETECT_BATCH frames at a time on `device`
     (`detector.clip_pass`: the labelling pass's uploader; `ops.frame_pair_stats` per batch, the last frame of a batch carried over as
-    `prev` of the next): (sad int64 [T-1], hist int64 [T,64]) as numpy arrays, the input of `find_cuts`.  A deep clip (a `_Frames`
+    `prev` of the next): (sad int64 [T-1], hist int64 [T,64]) as numpy arrays, the input of `find_cuts`.  A deep clip (a `Frames`
     of `frames_of(..., depth=)`, or a deep y4m reader) goes through `ops.frame_pair_stats_u16`, and its sad comes back divided by
     2^(depth-8), as float64, so that `find_cuts`' `min_delta` keeps its 8-bit unit."""
-    fr = frames if isinstance(frames, _Frames) else frames_of(frames)
+    fr = frames if isinstance(frames, Frames) else frames_of(frames)
     sad, hist = detector.clip_pass(fr, device, batch=DETECT_BATCH, features=False, pair_stats=True)[1]
     return _sad_8bit(sad.cpu().numpy(), fr.depth), hist.cpu().numpy()
 
@@ -465,7 +202,7 @@ def active_area(frames, device, frames_max: Optional[int] = 64):
     every frame).  The pass is `detector.clip_batches` on that subset, DETECT_BATCH frames at a time, so a y4m or deep clip goes
     through its usual conversion, with one `ops.frame_extent` launch per batch joining the maxima: the sampled frames are uploaded once
     more than a run that does not ask for the area."""
-    fr = frames if isinstance(frames, _Frames) else frames_of(frames)
+    fr = frames if isinstance(frames, Frames) else frames_of(frames)
     if frames_max is not None and (isinstance(frames_max, bool) or not isinstance(frames_max, (int, np.integer)) or frames_max < 1):
         raise ValueError(f"active_area: frames_max must be None or a whole number >= 1, got {frames_max!r}")
     sub = fr.sample(sample_indices(fr.T, frames_max))
@@ -491,6 +228,13 @@ def roi_of(roi, H: int, W: int):
     if y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
         raise ValueError(f"roi {(y0, x0, h, w)}: the rectangle lies outside the {W}x{H} frame (0 <= y0, y0 + h <= {H}, 0 <= x0, x0 + w <= {W})")
     return None if (y0, x0, h, w) == (0, 0, H, W) else (y0, x0, h, w)
+
+
+def check_roi_feather(roi_feather: int, h: int, w: int, tail) -> None:
+    """Refuse a `roi_feather` above the bound for an h x w rectangle; `tail(bound)` is what the ValueError says after "roi_feather=N "."""
+    bound = min(ROI_FEATHER_MAX, h // 2, w // 2)
+    if roi_feather > bound:
+        raise ValueError(f"roi_feather={roi_feather} " + tail(bound))
 
 
 def _scene_plan(labels, n_seq: int, numbers) -> list:
@@ -548,7 +292,7 @@ class ClipRun:
     clip that is deblurred whole (found on first access, by `active_area` + `find_bars`, when the caller asked for "auto"); labels,
     cuts and the plan are then those of the clip of cropped frames."""
 
-    def __init__(self, model, frames: _Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
+    def __init__(self, model, frames: Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
                  out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None, ensemble: int = 1, roi=None,
                  roi_feather: int = 0, bar_params: Optional[dict] = None):
         self.model, self.frames = model, frames
@@ -583,12 +327,12 @@ class ClipRun:
             ext = active_area(fr, self.device, bp.get("frames", 64))
             found = find_bars(*ext, fr.depth, **{k: v for k, v in bp.items() if k != "frames"})
             self._roi = None if found is None else roi_of(found, fr.H, fr.W)
-            if self._roi is not None and self.roi_feather > min(ROI_FEATHER_MAX, self._roi[2] // 2, self._roi[3] // 2):
-                raise ValueError(f"roi_feather={self.roi_feather} does not fit the rectangle {self._roi} that roi=\"auto\" found: at most "
-                                 f"min({ROI_FEATHER_MAX}, h // 2, w // 2)")
+            if self._roi is not None:
+                check_roi_feather(self.roi_feather, *self._roi[2:], lambda _: f"does not fit the rectangle {self._roi} that "
+                                  f"roi=\"auto\" found: at most min({ROI_FEATHER_MAX}, h // 2, w // 2)")
         return self._roi
 
-    def _view(self) -> _Frames:
+    def _view(self) -> Frames:
         """The clip the analysis pass sees: the frames cropped to the region of interest."""
         return self.frames if self.roi is None else self.frames.view(self.roi)
 
@@ -649,7 +393,7 @@ class ClipRun:
         cache = FrameCache(pool, fr.host, dev, convert=None if fr.yuv is None else (lambda planar: fr.rgb(planar)[0]))
         K = self.ensemble
         members = ens.MEMBERS[K]         # every window runs once per member (and tile): K - 1 transformed copies of its input
-        enc = EncoderCache() if nt * K == 1 else EncoderCache(EncoderCache().capacity * nt * K)
+        enc = EncoderCache(EncoderCache().capacity * nt * K)
         inflight, ready = collections.deque(), collections.deque()
         # the stream current at the first `next` assembles the inputs; the windows run on the lanes; a frame handed out is ordered
         # before later work on whatever stream is current at that `next`
@@ -671,8 +415,8 @@ class ClipRun:
             return ops.frames_u8_in(f, out=x[0, j]) if depth == 8 else ops.frames_u16_in(f, depth, out=x[0, j])
 
         def egress(y, dst, flag, k):
-            """The model's output [nt, 3, Hp, Wp] (or a list of nt planes) as frame k: the crop, the tiles' bands stitched, or the
-            rectangle pasted into the input frame."""
+            """The model's output, a list of nt planes [3, Hp, Wp], as frame k: the crop, the tiles' bands stitched, or the rectangle
+            pasted into the input frame."""
             if tp is not None:
                 return ops.tiles_out(y, tp, out_depth, out=dst, nonfinite=flag)
             if roi is not None:
@@ -682,18 +426,11 @@ class ClipRun:
                 return ops.frame_u8_out(y[0], H, W, out=dst, nonfinite=flag)
             return ops.frame_u16_out(y[0], H, W, out_depth, out=dst, nonfinite=flag)
 
-        def tile_keys(keys, t):
-            """The `forward_window` keys of tile t: equal pixels per (tile, frame)."""
-            return [(t, key) for key in keys]
-
-        def member_keys(keys, g, t):
-            """The `forward_window` keys of ensemble member g of tile t: equal pixels per (member, tile, frame)."""
-            return [(g, t, key) for key in keys]
-
-        def members_of(x):
-            """The window input of every ensemble member: x itself, and T_g of all its planes for g = 1 .. K-1, one launch each
-            (a zeroed frame stays zero)."""
-            return [x] + [ops.planes_d4(x, g) for g in members[1:]]
+        def parts(run):
+            """The nt planes of a window.  It runs as nt * K parts, one after the other: `run(t, g)` is the output plane of member g of
+            tile t on the input xs[g][t:t + 1]; one launch turns the K planes of a tile back and averages them (K = 1: none)."""
+            mean = (lambda outs: outs[0]) if K == 1 else (lambda outs: ops.d4_mean(outs, members))
+            return [mean([run(t, g) for g in members]) for t in range(nt)]
 
         def frame(i):
             return fr.device(i).to(dev).contiguous() if fr.on_device(i) else cache.get_dev(i)
@@ -711,13 +448,12 @@ class ClipRun:
                     ingest(frame(key), x, j)
             if roi is not None:
                 centres[k] = frame(plan[k]["window"][n // 2])     # uploaded just now: the frame that window k deblurs
-            xs = members_of(x)
+            xs = [x] + [ops.planes_d4(x, g) for g in members[1:]]     # T_g of all its planes, one launch each (a zeroed frame stays zero)
             self.seconds.append([time.time() - t0, 0.0])
             return xs
 
         def enqueue(k, xs, nxts):
             """Window k on its lane (and window k + 1's encoder passes on the model's prefetch stream)."""
-            x, nxt = xs[0], None if nxts is None else nxts[0]
             if len(inflight) >= max(2, len(lanes)):
                 inflight.popleft().synchronize()           # the host stays at most two windows ahead of the GPU
             t0 = time.time()
@@ -726,32 +462,19 @@ class ClipRun:
             lane = lanes[k % len(lanes)]
             lane.wait_stream(home)                         # the window's input was assembled on the home stream
             slot = k % FLAG_RING
+
+            def part(t, g):
+                """Part (t, g) of window k behind the encoder passes of that part of window k + 1.  The keys: equal pixels per (member, tile,
+                frame).  `forward_window` hands out a copy of its graph's static output, so the plane outlives the next part's replay."""
+                if nxts is not None:
+                    m.prefetch_window(nxts[g][t:t + 1], [(g, t, key) for key in plan[k + 1]["keys"]], enc, zero_ref=plan[k + 1]["zero_pre"])
+                return m.forward_window(xs[g][t:t + 1], [(g, t, key) for key in w["keys"]], enc, zero_ref=w["zero_pre"])[0]
+
             with torch.cuda.stream(lane):
                 for v in xs + (nxts or []):
                     v.record_stream(lane)
                 dst.record_stream(lane)
-                if K > 1:                                  # every member of every tile is a window of its own, one after the other
-                    y = []
-                    for t in range(nt):
-                        outs = []
-                        for g in members:
-                            if nxts is not None:
-                                m.prefetch_window(nxts[g][t:t + 1], member_keys(plan[k + 1]["keys"], g, t), enc,
-                                                  zero_ref=plan[k + 1]["zero_pre"])
-                            outs.append(m.forward_window(xs[g][t:t + 1], member_keys(w["keys"], g, t), enc, zero_ref=w["zero_pre"])[0])
-                        # `forward_window` hands out a copy of its graph's static output, so a member's output outlives the next
-                        # member's replay: one launch turns them back and averages them
-                        y.append(ops.d4_mean(outs, members))
-                elif tp is None:
-                    if nxt is not None:
-                        m.prefetch_window(nxt, plan[k + 1]["keys"], enc, zero_ref=plan[k + 1]["zero_pre"])
-                    y = m.forward_window(x, w["keys"], enc, zero_ref=w["zero_pre"])
-                else:                                      # every tile is a window of its own; one shape, so one set of graphs
-                    y = []
-                    for t in range(nt):
-                        if nxt is not None:
-                            m.prefetch_window(nxt[t:t + 1], tile_keys(plan[k + 1]["keys"], t), enc, zero_ref=plan[k + 1]["zero_pre"])
-                        y.append(m.forward_window(x[t:t + 1], tile_keys(w["keys"], t), enc, zero_ref=w["zero_pre"])[0])
+                y = parts(part)
                 if roi is not None:
                     centres[k].record_stream(lane)
                 egress(y, dst, flags[slot:slot + 1], k)
@@ -766,14 +489,10 @@ class ClipRun:
             """Window k again in split-bf16 arithmetic (fp32 exponent range), eagerly, on the home stream: a 16-bit pass left a NaN or an
             infinity in the frame (half operands do not saturate; one in any ensemble member reaches the mean, and so the flag).  Every
             member of every tile runs again."""
-            x = xs[0]
             keep = (m.precision, m.corr_precision, m.use_graph)
             m.precision, m.corr_precision, m.use_graph = "bf16x3", "bf16x3", False
             try:
-                if K > 1:
-                    y = [ops.d4_mean([m(xs[g][t:t + 1], routing=[plan[k]["zero_pre"]])[0] for g in members], members) for t in range(nt)]
-                else:
-                    y = [m(x[t:t + 1], routing=[plan[k]["zero_pre"]])[0] for t in range(nt)]      # every tile of the window
+                y = parts(lambda t, g: m(xs[g][t:t + 1], routing=[plan[k]["zero_pre"]])[0])
             finally:
                 m.precision, m.corr_precision, m.use_graph = keep
             slot = k % FLAG_RING
@@ -920,17 +639,13 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
         frames = y4m.Y4MReader(frames, depths=y4m.DEPTHS)
     fr = frames_of(frames, crop, yuv, depth)
     if roi is not None and not isinstance(roi, str):
-        rect = roi_of(tuple(roi) if isinstance(roi, list) else roi, fr.H, fr.W)
-        h, w = (fr.H, fr.W) if rect is None else rect[2:]
-        if roi_feather > min(ROI_FEATHER_MAX, h // 2, w // 2):
-            raise ValueError(f"roi_feather={roi_feather} is outside 0..{min(ROI_FEATHER_MAX, h // 2, w // 2)}: at most {ROI_FEATHER_MAX} "
-                             f"and half of the {w}x{h} rectangle")
-        roi = rect
+        roi = roi_of(tuple(roi) if isinstance(roi, list) else roi, fr.H, fr.W)
+        h, w = (fr.H, fr.W) if roi is None else roi[2:]
+        check_roi_feather(roi_feather, h, w, lambda bound: f"is outside 0..{bound}: at most {ROI_FEATHER_MAX} and half of the {w}x{h} rectangle")
     elif roi is not None:
         roi = roi_of(roi, fr.H, fr.W)    # "auto", or a ValueError for any other string
-        if roi_feather > min(ROI_FEATHER_MAX, fr.H // 2, fr.W // 2):
-            raise ValueError(f"roi_feather={roi_feather} is outside 0..{min(ROI_FEATHER_MAX, fr.H // 2, fr.W // 2)}: at most "
-                             f"{ROI_FEATHER_MAX} and half of the rectangle, which lies inside the {fr.W}x{fr.H} frame")
+        check_roi_feather(roi_feather, fr.H, fr.W, lambda bound: f"is outside 0..{bound}: at most {ROI_FEATHER_MAX} and half of the "
+                          f"rectangle, which lies inside the {fr.W}x{fr.H} frame")
     if out_depth is not None and (isinstance(out_depth, bool) or out_depth not in y4m.DEPTHS):
         raise ValueError(f"out_depth must be None, 8, 10 or 12, got {out_depth!r}")
     out_depth = fr.depth if out_depth is None else int(out_depth)
@@ -1160,7 +875,7 @@ def main(argv=None) -> None:
                           ops.rgb_u16_to_yuv(frame, layout, matrix, rng, out_depth))
                 ring.land(lambda buf: writer.write(buf.numpy()), planar)
             else:
-                ring.land(lambda buf, path=os.path.join(a.output, names[i]): _imwrite(path, buf.numpy()), frame)
+                ring.land(lambda buf, path=os.path.join(a.output, names[i]): imwrite(path, buf.numpy()), frame)
             now = time.time()
             branch = "no-reference" if run.plan[i]["zero_pre"] else "reference"
             say(f"> {names[i]} {branch} {now - t_prev:.3f}s")

@@ -308,3 +308,51 @@ def test_cli(net32, tmp_path):
         img = inference._imread(str(dst / n))
         assert img.shape == (90, 130, 3)
         assert np.array_equal(img, ref[i].cpu().numpy())
+
+
+# ---- 8. the I/O launches of every clip geometry ---------------------------------------------------------------------------------------
+IO_ENTRIES = ("spei_frames_u8_in", "spei_frames_u16_in", "spei_frame_u8_out", "spei_frame_u16_out", "spei_tiles_u8_in", "spei_tiles_u16_in",
+              "spei_tiles_u8_out", "spei_tiles_u16_out", "spei_tiles_u8_blend", "spei_tiles_u16_blend", "spei_roi_paste_u8",
+              "spei_roi_paste_u16", "spei_planes_d4", "spei_d4_mean")
+
+
+def test_io_launches_per_geometry(monkeypatch):
+    """The ingest, member and egress launches of a 4-frame clip, counted by entry point for every geometry: one ingest per frame of a
+    window that is not zeroed (N_in over the clip, whatever the number of tiles or members), one egress per frame (T), one
+    `planes_d4` per window and member after the first, one `d4_mean` per window and tile.  `tiles=(1, 1)`, `ensemble=1` and the
+    rectangle that is the whole frame are the path without them, launch for launch."""
+    seen = []
+    orig = _lib.check
+
+    def check(rc, what):
+        seen.append(what)
+        return orig(rc, what)
+    monkeypatch.setattr(_lib, "check", check)
+    net = video.load_model("synthetic", DEV, "f16", graph=True)
+    labels, numbers, T = [1, 0, 0, 1], [0, 1, 12, 13], 4
+    small, large = _clip(T, 40, 60), _clip(T, 80, 120)
+    deep = small.astype(np.uint16) << 2
+    cases = [
+        (small, {}, lambda n: {"spei_frames_u8_in": n, "spei_frame_u8_out": T}),
+        # the three "path without it" arguments, in two runs: `deblur_clip` refuses roi= together with tiles= before it looks at either
+        (small, dict(tiles=(1, 1), ensemble=1), lambda n: {"spei_frames_u8_in": n, "spei_frame_u8_out": T}),
+        (small, dict(ensemble=1, roi=(0, 0, 40, 60)), lambda n: {"spei_frames_u8_in": n, "spei_frame_u8_out": T}),
+        (deep, dict(depth=10), lambda n: {"spei_frames_u16_in": n, "spei_frame_u16_out": T}),
+        (large, dict(tiles=(2, 2)), lambda n: {"spei_tiles_u8_in": n, "spei_tiles_u8_out": T}),
+        (large, dict(tiles=(2, 2), feather=8), lambda n: {"spei_tiles_u8_in": n, "spei_tiles_u8_blend": T}),
+        (large, dict(roi=(10, 20, 40, 60)), lambda n: {"spei_tiles_u8_in": n, "spei_roi_paste_u8": T}),     # roi_in is the tile ingest
+        (small, dict(ensemble=2), lambda n: {"spei_frames_u8_in": n, "spei_planes_d4": T, "spei_d4_mean": T, "spei_frame_u8_out": T}),
+        (large, dict(tiles=(2, 2), ensemble=2),
+         lambda n: {"spei_tiles_u8_in": n, "spei_planes_d4": T, "spei_d4_mean": 4 * T, "spei_tiles_u8_out": T}),
+    ]
+    for frames, kw, expected in cases:
+        run = video.deblur_clip(net, frames, labels, numbers=numbers, **kw)
+        assert {p["zero_pre"] for p in run.plan} == {True, False}, kw
+        n_in = sum(key is not video.ZERO for p in run.plan for key in p["keys"])
+        assert 0 < n_in < 5 * T, kw                            # some keys are ZERO
+        seen.clear()
+        got = [i for i, _ in run]
+        torch.cuda.synchronize()
+        assert got == list(range(T)) and run.recomputed == [], kw
+        counts = {name: seen.count(name) for name in IO_ENTRIES}
+        assert counts == {**dict.fromkeys(IO_ENTRIES, 0), **expected(n_in)}, kw
