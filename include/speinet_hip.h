@@ -647,6 +647,8 @@ int spei_frame_extent_u16(const uint16_t* src, int64_t frame_stride, int N, int 
 #define SPEI_YUV_420_CENTER 0 /* 4:2:0, chroma sample at the centre of its 2x2 block (y4m C420jpeg, and bare C420) */
 #define SPEI_YUV_420_LEFT 1   /* 4:2:0, chroma co-sited with the even column, between the two rows (y4m C420mpeg2) */
 #define SPEI_YUV_444 2        /* 4:4:4 (y4m C444) */
+#define SPEI_YUV_422 3        /* 4:2:2, chroma co-sited with the even column of its own row (y4m C422, C422p10, C422p12) */
+#define SPEI_YUV_MONO 4       /* the Y plane alone (y4m Cmono, Cmono10, Cmono12) */
 #define SPEI_YUV_BT601 0
 #define SPEI_YUV_BT709 1
 #define SPEI_YUV_FULL 0    /* Y, U, V in 0..255 */
@@ -702,6 +704,31 @@ int spei_yuv_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst
                         int depth, spei_stream_t stream);
 int spei_rgb_u16_to_yuv(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
                         spei_stream_t stream);
+
+/* 4:2:2 and mono frames: the four conversions above on layout = SPEI_YUV_422 or SPEI_YUV_MONO (any other layout is refused here, as
+ * the four entries above refuse these two), with their arguments, checks, coefficient rows, clipping limits, yo, chroma zero and deep
+ * rule (s = depth - 8, D = 2^depth - 1, a word above D reads as D; s = 0 and D = 255 for the u8 entries).  Indices are clamped to the
+ * plane or frame.
+ * SPEI_YUV_422: a planar frame is Y [H][W], then U, then V, [H][ceil(W/2)] each.  A chroma sample is co-sited with the even column of
+ * its own row: no vertical subsampling, no siting option.
+ *   YUV -> RGB, with i = x >> 1: even x: U16 = 16 U[y][i]; odd x: U16 = 8 (U[y][i] + U[y][i+1]); V likewise, then the R, G, B
+ *   expressions above.  This is LEFT's column rule (4 : 0 at even x, 2 : 2 at odd x) without a row step.
+ *   RGB -> YUV: Y per pixel as above.  Per row y and chroma column i, S_c = c[y][2i-1] + 2 c[y][2i] + c[y][2i+1] for each channel c,
+ *   U = clip(((ur S_R + ug S_G + ub S_B + 2^15) >> 16) + (128 << s)), V likewise.  Every product and sum fits int32 (|sum| < 1.4e8
+ *   at 12 bits).
+ * SPEI_YUV_MONO: a planar frame is the Y plane [H][W] alone.
+ *   YUV -> RGB: U16 = V16 = 2048 << s, so R = G = B = clip((cy * 16 * (Y - yo) + 2^17) >> 18, 0, D); `matrix` is checked and has no
+ *   effect.
+ *   RGB -> YUV: the Y expression alone, with the matrix's luma row.
+ * Like the 4:2:0 rule, the 4:2:2 resampling is this project's own definition, not a bit-match of swscale. */
+int spei_planar_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W, int layout, int matrix,
+                          int range, spei_stream_t stream);
+int spei_rgb_u8_to_planar(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
+                          spei_stream_t stream);
+int spei_planar_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout, int matrix, int range,
+                           int depth, spei_stream_t stream);
+int spei_rgb_u16_to_planar(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
+                           spei_stream_t stream);
 
 /* ---- training on a dataset (speinet_amd/data.py, speinet_amd/fit.py) ---- */
 

@@ -4,6 +4,8 @@
 //   spei_yuv_to_rgb_u8 — N planar uint8 frames (Y [H][W], then U, then V: [ceil(H/2)][ceil(W/2)] each for 4:2:0, [H][W] each for
 //                        4:4:4) -> N packed uint8 [H][W][3] RGB frames, what spei_frames_u8_in and spei_frame_pair_stats take.
 //   spei_rgb_u8_to_yuv — one packed uint8 [H][W][3] RGB frame (what spei_frame_u8_out makes) -> one planar frame.
+//   spei_planar_to_rgb_u8, spei_rgb_u8_to_planar — the same two for 4:2:2 (U, V: [H][ceil(W/2)] each, co-sited with the even column
+//                        of their own row) and mono (the Y plane alone) frames: two more LAYOUT values of the same kernels.
 //
 // Integer arithmetic only: the result is defined bit for bit and depends on neither the launch shape nor the access path.  `>>` is
 // an arithmetic shift (it floors).  Clipping is to [0,255] for RGB and full range, to [16,235] (Y) and [16,240] (U, V) for limited.
@@ -13,6 +15,8 @@
 //   4:2:0 rows     j = y >> 1, the other row j - 1 (y even) or j + 1 (y odd), weights 3 : 1 (both sitings)
 //   CENTER columns the same rule with i = x >> 1
 //   LEFT columns   4 : 0 at even x (co-sited), 2 : 2 of columns i and i + 1 at odd x
+//   4:2:2          LEFT's column rule on row y itself: U16 = 16 U[y][i] at even x, 8 (U[y][i] + U[y][i + 1]) at odd x
+//   mono           U16 = V16 = 2048: R = G = B
 // then, with yy = cy * 16 * (Y - yo), u = U16 - 2048, v = V16 - 2048:
 //   R = clip((yy + rv v + 2^17) >> 18)   G = clip((yy + gu u + gv v + 2^17) >> 18)   B = clip((yy + bu u + 2^17) >> 18)
 // Every intermediate fits int32 (about 1.5e8 at most).
@@ -21,13 +25,14 @@
 //   4:4:4   U = clip(((ur R + ug G + ub B + 2^13) >> 14) + 128) per pixel, V likewise
 //   CENTER  the same on S_c, the sum of channel c over rows 2j, 2j + 1 and columns 2i, 2i + 1, with 2^15 and >> 16
 //   LEFT    the same on the sum over rows 2j, 2j + 1 of c[2i - 1] + 2 c[2i] + c[2i + 1], with 2^16 and >> 17
+//   4:2:2   the same on c[y][2i - 1] + 2 c[y][2i] + c[y][2i + 1] of row y alone, with 2^15 and >> 16 (mono: no chroma)
 // indices clamped to the frame.  The 4:2:0 resampling (3 : 1 bilinear up, box or [1 2 1] down) is this project's own definition.
 //
 // Streaming kernels in the style of frame_io.hip, one thread per group of 4 pixels of a row in a grid-stride loop: dword accesses
 // where the rows are 4-byte aligned, bytes otherwise and at the right edge.  In spei_rgb_u8_to_yuv the thread of an even row and an
 // even group also makes the (up to) 4 chroma samples of the 2 x 8 pixels below and right of it; the RGB bytes it reads again for
-// that are its neighbours' and come from the cache.  No atomics.  HBM-bound: a 720p 4:2:0 frame is 1.4 MB on one side and 2.8 MB on
-// the other.
+// that are its neighbours' and come from the cache (4:2:2: the even group of every row, for the 8 pixels right of it).  No atomics.
+// HBM-bound: a 720p 4:2:0 frame is 1.4 MB on one side and 2.8 MB on the other.
 #include "common.h"
 
 namespace {
@@ -74,12 +79,19 @@ __device__ __forceinline__ void store4(unsigned char* __restrict__ row, int x0, 
     }
 }
 
+// samples of one chroma plane: [H][W] for 4:4:4, [H][ceil(W/2)] for 4:2:2, none for mono, [ceil(H/2)][ceil(W/2)] for 4:2:0
+__host__ __device__ __forceinline__ int64_t chroma_size(int H, int W, int layout) {
+    if (layout == SPEI_YUV_444) return (int64_t)H * W;
+    if (layout == SPEI_YUV_MONO) return 0;
+    return (int64_t)(layout == SPEI_YUV_422 ? H : (H + 1) >> 1) * ((W + 1) >> 1);
+}
+
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const unsigned char* __restrict__ src, int64_t fstride,
                                                          unsigned char* __restrict__ dst, int H, int W, int64_t total, Coef k,
                                                          int aligned) {
     const int gw = (W + 3) >> 2, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
-    const int64_t ysize = (int64_t)H * W, csize = LAYOUT == SPEI_YUV_444 ? ysize : (int64_t)Hc * Wc;
+    const int64_t ysize = (int64_t)H * W, csize = chroma_size(H, W, LAYOUT);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / gw;                        // n * H + y
         const int x0 = (int)(i - row * gw) * 4;
@@ -95,6 +107,26 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const unsigned char* __
             load4(vp + (int64_t)y * W, x0, W, dword, V16);
 #pragma unroll
             for (int p = 0; p < 4; ++p) { U16[p] *= 16; V16[p] *= 16; }
+        } else if (LAYOUT == SPEI_YUV_MONO) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) U16[p] = V16[p] = 2048;
+        } else if (LAYOUT == SPEI_YUV_422) {
+            // chroma columns i0 .. i0 + 2 (clamped) of row y serve the 4 pixels: LEFT's column rule, no row step
+            const int i0 = x0 >> 1;
+            const int64_t r = (int64_t)y * Wc;
+            int u[3], v[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int c = min(i0 + q, Wc - 1);
+                u[q] = up[r + c];
+                v[q] = vp[r + c];
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int a = p >> 1;                      // column i = x >> 1
+                U16[p] = (p & 1) ? 8 * (u[a] + u[a + 1]) : 16 * u[a];
+                V16[p] = (p & 1) ? 8 * (v[a] + v[a + 1]) : 16 * v[a];
+            }
         } else {
             // chroma columns i0 - 1 .. i0 + 2 (clamped) serve the 4 pixels; rows first: 3 of row j, 1 of the other
             const int j = y >> 1, jo = clip((y & 1) ? j + 1 : j - 1, 0, Hc - 1), i0 = x0 >> 1;
@@ -145,8 +177,9 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const unsigned char* __
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int H,
                                                          int W, int64_t total, Coef k, int limited, int al_src, int al_y, int al_c) {
-    const int gw = (W + 3) >> 2, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
-    const int64_t ysize = (int64_t)H * W, csize = LAYOUT == SPEI_YUV_444 ? ysize : (int64_t)Hc * Wc;
+    const int gw = (W + 3) >> 2, Wc = (W + 1) >> 1;
+    const int64_t ysize = (int64_t)H * W, csize = chroma_size(H, W, LAYOUT);
+    constexpr bool TWO = LAYOUT != SPEI_YUV_422;           // a chroma sample spans two rows (4:2:0) or one
     const int ylo = limited ? 16 : 0, yhi = limited ? 235 : 255, clo = ylo, chi = limited ? 240 : 255;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int y = (int)(i / gw), g = (int)(i - (int64_t)y * gw), x0 = g * 4;
@@ -176,10 +209,11 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const unsigned char* __
         if (LAYOUT == SPEI_YUV_444) {
             store4(dst + ysize + (int64_t)y * W, x0, W, dword, U);
             store4(dst + 2 * ysize + (int64_t)y * W, x0, W, dword, V);
-        } else if (!(y & 1) && !(g & 1)) {
-            // chroma samples (j, i0 .. i0 + 3) of rows y, y + 1 and columns x0 .. x0 + 7: s[ch][q] is the sum over the two rows of
-            // channel ch at column x0 - 1 + q, rows and columns clamped to the frame (q = 0 is LEFT's left neighbour)
-            const int j = y >> 1, i0 = x0 >> 1;
+        } else if (LAYOUT != SPEI_YUV_MONO && (!TWO || !(y & 1)) && !(g & 1)) {
+            // chroma samples (j, i0 .. i0 + 3) of rows y, y + 1 (4:2:2: of row y alone) and columns x0 .. x0 + 7: s[ch][q] is the sum
+            // over those rows of channel ch at column x0 - 1 + q, rows and columns clamped to the frame (q = 0 is the left neighbour
+            // of LEFT and 4:2:2)
+            const int j = TWO ? y >> 1 : y, i0 = x0 >> 1;
             const unsigned char* r1 = src + (int64_t)min(y + 1, H - 1) * W * 3;
             int s[3][9];
             if (al_src && x0 + 8 <= W) {
@@ -187,7 +221,7 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const unsigned char* __
                 const uint32_t* b = reinterpret_cast<const uint32_t*>(r1 + x0 * 3);
 #pragma unroll
                 for (int d = 0; d < 6; ++d) {
-                    const uint32_t wa = a[d], wb = b[d];
+                    const uint32_t wa = a[d], wb = TWO ? b[d] : 0u;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int t = 4 * d + e;
@@ -196,13 +230,13 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const unsigned char* __
                 }
                 const int xl = max(x0 - 1, 0) * 3;
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) s[ch][0] = LAYOUT == SPEI_YUV_420_LEFT ? r0[xl + ch] + r1[xl + ch] : 0;
+                for (int ch = 0; ch < 3; ++ch) s[ch][0] = LAYOUT == SPEI_YUV_420_CENTER ? 0 : r0[xl + ch] + (TWO ? r1[xl + ch] : 0);
             } else {
 #pragma unroll
                 for (int q = 0; q < 9; ++q) {
                     const int x = clip(x0 - 1 + q, 0, W - 1) * 3;
 #pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) s[ch][q] = r0[x + ch] + r1[x + ch];
+                    for (int ch = 0; ch < 3; ++ch) s[ch][q] = r0[x + ch] + (TWO ? r1[x + ch] : 0);
                 }
             }
             int Uc[4], Vc[4];
@@ -213,7 +247,7 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const unsigned char* __
                 for (int ch = 0; ch < 3; ++ch)
                     S[ch] = LAYOUT == SPEI_YUV_420_CENTER ? s[ch][1 + 2 * m] + s[ch][2 + 2 * m]
                                                           : s[ch][2 * m] + 2 * s[ch][1 + 2 * m] + s[ch][2 + 2 * m];
-                constexpr int SH = LAYOUT == SPEI_YUV_420_CENTER ? 16 : 17;
+                constexpr int SH = LAYOUT == SPEI_YUV_420_LEFT ? 17 : 16;     // Q14 and the sum's 4 (CENTER, 4:2:2) or 8 (LEFT) weights
                 Uc[m] = clip(((k.ur * S[0] + k.ug * S[1] + k.ub * S[2] + (1 << (SH - 1))) >> SH) + 128, clo, chi);
                 Vc[m] = clip(((k.vr * S[0] + k.vg * S[1] + k.vb * S[2] + (1 << (SH - 1))) >> SH) + 128, clo, chi);
             }
@@ -285,7 +319,7 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_u16_kernel(const uint16_t* __r
                                                              uint16_t* __restrict__ dst, int H, int W, int64_t total, Coef k, int s,
                                                              int aligned) {
     const int gw = (W + 3) >> 2, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1, D = (256 << s) - 1;
-    const int64_t ysize = (int64_t)H * W, csize = LAYOUT == SPEI_YUV_444 ? ysize : (int64_t)Hc * Wc;
+    const int64_t ysize = (int64_t)H * W, csize = chroma_size(H, W, LAYOUT);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / gw;                        // n * H + y
         const int x0 = (int)(i - row * gw) * 4;
@@ -301,6 +335,25 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_u16_kernel(const uint16_t* __r
             load4(vp + (int64_t)y * W, x0, W, wide, D, V16);
 #pragma unroll
             for (int p = 0; p < 4; ++p) { U16[p] *= 16; V16[p] *= 16; }
+        } else if (LAYOUT == SPEI_YUV_MONO) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) U16[p] = V16[p] = 2048 << s;
+        } else if (LAYOUT == SPEI_YUV_422) {
+            const int i0 = x0 >> 1;
+            const int64_t r = (int64_t)y * Wc;
+            int u[3], v[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int c = min(i0 + q, Wc - 1);
+                u[q] = min((int)up[r + c], D);
+                v[q] = min((int)vp[r + c], D);
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int a = p >> 1;                      // column i = x >> 1
+                U16[p] = (p & 1) ? 8 * (u[a] + u[a + 1]) : 16 * u[a];
+                V16[p] = (p & 1) ? 8 * (v[a] + v[a + 1]) : 16 * v[a];
+            }
         } else {
             const int j = y >> 1, jo = clip((y & 1) ? j + 1 : j - 1, 0, Hc - 1), i0 = x0 >> 1;
             const int64_t rj = (int64_t)j * Wc, ro = (int64_t)jo * Wc;
@@ -351,8 +404,9 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_u16_kernel(const uint16_t* __r
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void rgb_u16_to_yuv_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, int H, int W,
                                                              int64_t total, Coef k, int limited, int s, int al_src, int al_y, int al_c) {
-    const int gw = (W + 3) >> 2, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1, D = (256 << s) - 1, mid = 128 << s;
-    const int64_t ysize = (int64_t)H * W, csize = LAYOUT == SPEI_YUV_444 ? ysize : (int64_t)Hc * Wc;
+    const int gw = (W + 3) >> 2, Wc = (W + 1) >> 1, D = (256 << s) - 1, mid = 128 << s;
+    const int64_t ysize = (int64_t)H * W, csize = chroma_size(H, W, LAYOUT);
+    constexpr bool TWO = LAYOUT != SPEI_YUV_422;           // a chroma sample spans two rows (4:2:0) or one
     const int ylo = limited ? 16 << s : 0, yhi = limited ? 235 << s : D, clo = ylo, chi = limited ? 240 << s : D;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int y = (int)(i / gw), g = (int)(i - (int64_t)y * gw), x0 = g * 4;
@@ -374,31 +428,32 @@ __global__ __launch_bounds__(256) void rgb_u16_to_yuv_kernel(const uint16_t* __r
         if (LAYOUT == SPEI_YUV_444) {
             store4(dst + ysize + (int64_t)y * W, x0, W, wide, U);
             store4(dst + 2 * ysize + (int64_t)y * W, x0, W, wide, V);
-        } else if (!(y & 1) && !(g & 1)) {
-            // chroma samples (j, i0 .. i0 + 3) of rows y, y + 1 and columns x0 .. x0 + 7: sm[ch][q] is the sum over the two rows of
-            // channel ch at column x0 - 1 + q, rows and columns clamped to the frame (q = 0 is LEFT's left neighbour)
-            const int j = y >> 1, i0 = x0 >> 1;
+        } else if (LAYOUT != SPEI_YUV_MONO && (!TWO || !(y & 1)) && !(g & 1)) {
+            // chroma samples (j, i0 .. i0 + 3) of rows y, y + 1 (4:2:2: of row y alone) and columns x0 .. x0 + 7: sm[ch][q] is the sum
+            // over those rows of channel ch at column x0 - 1 + q, rows and columns clamped to the frame (q = 0 is the left neighbour
+            // of LEFT and 4:2:2)
+            const int j = TWO ? y >> 1 : y, i0 = x0 >> 1;
             const uint16_t* r1 = src + (int64_t)min(y + 1, H - 1) * W * 3;
             int sm[3][9];
             if (al_src && x0 + 8 <= W) {
-                int a[12], b[12];
+                int a[12], b[12] = {};
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     load_rgb4(r0, x0 + 4 * h, W, true, D, a);
-                    load_rgb4(r1, x0 + 4 * h, W, true, D, b);
+                    if (TWO) load_rgb4(r1, x0 + 4 * h, W, true, D, b);
 #pragma unroll
                     for (int t = 0; t < 12; ++t) sm[t % 3][1 + 4 * h + t / 3] = a[t] + b[t];
                 }
                 const int xl = max(x0 - 1, 0) * 3;
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch)
-                    sm[ch][0] = LAYOUT == SPEI_YUV_420_LEFT ? min((int)r0[xl + ch], D) + min((int)r1[xl + ch], D) : 0;
+                    sm[ch][0] = LAYOUT == SPEI_YUV_420_CENTER ? 0 : min((int)r0[xl + ch], D) + (TWO ? min((int)r1[xl + ch], D) : 0);
             } else {
 #pragma unroll
                 for (int q = 0; q < 9; ++q) {
                     const int x = clip(x0 - 1 + q, 0, W - 1) * 3;
 #pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) sm[ch][q] = min((int)r0[x + ch], D) + min((int)r1[x + ch], D);
+                    for (int ch = 0; ch < 3; ++ch) sm[ch][q] = min((int)r0[x + ch], D) + (TWO ? min((int)r1[x + ch], D) : 0);
                 }
             }
             int Uc[4], Vc[4];
@@ -409,7 +464,7 @@ __global__ __launch_bounds__(256) void rgb_u16_to_yuv_kernel(const uint16_t* __r
                 for (int ch = 0; ch < 3; ++ch)
                     S[ch] = LAYOUT == SPEI_YUV_420_CENTER ? sm[ch][1 + 2 * m] + sm[ch][2 + 2 * m]
                                                           : sm[ch][2 * m] + 2 * sm[ch][1 + 2 * m] + sm[ch][2 + 2 * m];
-                constexpr int SH = LAYOUT == SPEI_YUV_420_CENTER ? 16 : 17;
+                constexpr int SH = LAYOUT == SPEI_YUV_420_LEFT ? 17 : 16;     // Q14 and the sum's 4 (CENTER, 4:2:2) or 8 (LEFT) weights
                 Uc[m] = clip(((k.ur * S[0] + k.ug * S[1] + k.ub * S[2] + (1 << (SH - 1))) >> SH) + mid, clo, chi);
                 Vc[m] = clip(((k.vr * S[0] + k.vg * S[1] + k.vb * S[2] + (1 << (SH - 1))) >> SH) + mid, clo, chi);
             }
@@ -423,55 +478,55 @@ __global__ __launch_bounds__(256) void rgb_u16_to_yuv_kernel(const uint16_t* __r
 
 inline int grid_for(int64_t total) { return (int)((total + 255) / 256 < BLOCKS_MAX ? (total + 255) / 256 : BLOCKS_MAX); }
 
-inline int64_t planar_bytes(int H, int W, int layout) {
-    const int64_t c = layout == SPEI_YUV_444 ? (int64_t)H * W : (int64_t)((H + 1) / 2) * ((W + 1) / 2);
-    return (int64_t)H * W + 2 * c;
-}
+inline int64_t planar_bytes(int H, int W, int layout) { return (int64_t)H * W + 2 * chroma_size(H, W, layout); }
 
-inline bool known(int layout, int matrix, int range) {
-    return (layout == SPEI_YUV_420_CENTER || layout == SPEI_YUV_420_LEFT || layout == SPEI_YUV_444) &&
-           (matrix == SPEI_YUV_BT601 || matrix == SPEI_YUV_BT709) && (range == SPEI_YUV_FULL || range == SPEI_YUV_LIMITED);
+// spei_yuv_* take the layouts lo .. hi = SPEI_YUV_420_CENTER .. SPEI_YUV_444, spei_planar_* SPEI_YUV_422 .. SPEI_YUV_MONO
+inline bool known(int layout, int lo, int hi, int matrix, int range) {
+    return layout >= lo && layout <= hi && (matrix == SPEI_YUV_BT601 || matrix == SPEI_YUV_BT709) &&
+           (range == SPEI_YUV_FULL || range == SPEI_YUV_LIMITED);
 }
 
 inline Coef deep_coef(int depth, int matrix, int range) {
     return range == SPEI_YUV_FULL ? COEF[matrix][0] : COEF_DEEP[depth == 12][matrix];
 }
 
-}  // namespace
+// one launch of KERNEL<layout> on `grid`, `block` and `stream` of the calling body; the layout is a checked one
+#define SPEI_YUV_LAUNCH_AS(KERNEL, L, ...) hipLaunchKernelGGL(KERNEL<L>, grid, block, 0, (hipStream_t)stream, __VA_ARGS__)
+#define SPEI_YUV_LAUNCH(KERNEL, layout, ...)                                                 \
+    switch (layout) {                                                                       \
+        case SPEI_YUV_420_CENTER: SPEI_YUV_LAUNCH_AS(KERNEL, SPEI_YUV_420_CENTER, __VA_ARGS__); break; \
+        case SPEI_YUV_420_LEFT: SPEI_YUV_LAUNCH_AS(KERNEL, SPEI_YUV_420_LEFT, __VA_ARGS__); break;     \
+        case SPEI_YUV_444: SPEI_YUV_LAUNCH_AS(KERNEL, SPEI_YUV_444, __VA_ARGS__); break;               \
+        case SPEI_YUV_422: SPEI_YUV_LAUNCH_AS(KERNEL, SPEI_YUV_422, __VA_ARGS__); break;               \
+        default: SPEI_YUV_LAUNCH_AS(KERNEL, SPEI_YUV_MONO, __VA_ARGS__); break;                        \
+    }
 
-extern "C" int spei_yuv_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W, int layout,
-                                  int matrix, int range, spei_stream_t stream) {
-    SPEI_REQUIRE(src && dst, "spei_yuv_to_rgb_u8: null pointer");
-    SPEI_REQUIRE(N >= 1 && H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "spei_yuv_to_rgb_u8: bad frame shape %d x %dx%d", N, H, W);
-    SPEI_REQUIRE(known(layout, matrix, range), "spei_yuv_to_rgb_u8: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", layout, matrix,
+// The bodies of the entry points: `name` is the entry's, lo .. hi the layouts it takes.
+int to_rgb_u8(const char* name, int lo, int hi, const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W,
+              int layout, int matrix, int range, spei_stream_t stream) {
+    SPEI_REQUIRE(src && dst, "%s: null pointer", name);
+    SPEI_REQUIRE(N >= 1 && H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %d x %dx%d", name, N, H, W);
+    SPEI_REQUIRE(known(layout, lo, hi, matrix, range), "%s: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", name, layout, matrix,
                  range);
-    SPEI_REQUIRE(N == 1 || frame_stride >= planar_bytes(H, W, layout), "spei_yuv_to_rgb_u8: frame stride %lld < one %dx%d planar frame "
-                 "of %lld bytes", (long long)frame_stride, H, W, (long long)planar_bytes(H, W, layout));
+    SPEI_REQUIRE(N == 1 || frame_stride >= planar_bytes(H, W, layout), "%s: frame stride %lld < one %dx%d planar frame of %lld bytes", name,
+                 (long long)frame_stride, H, W, (long long)planar_bytes(H, W, layout));
     const int aligned = (((uintptr_t)src | (uintptr_t)dst) & 3) == 0 && (N == 1 || (frame_stride & 3) == 0) && (W & 3) == 0;
     const int64_t total = (int64_t)N * H * ((W + 3) / 4);
     const Coef k = COEF[matrix][range];
     const dim3 grid(grid_for(total)), block(256);
-    if (layout == SPEI_YUV_420_CENTER)
-        hipLaunchKernelGGL(yuv_to_rgb_kernel<SPEI_YUV_420_CENTER>, grid, block, 0, (hipStream_t)stream, src, frame_stride, dst, H, W, total,
-                           k, aligned);
-    else if (layout == SPEI_YUV_420_LEFT)
-        hipLaunchKernelGGL(yuv_to_rgb_kernel<SPEI_YUV_420_LEFT>, grid, block, 0, (hipStream_t)stream, src, frame_stride, dst, H, W, total, k,
-                           aligned);
-    else
-        hipLaunchKernelGGL(yuv_to_rgb_kernel<SPEI_YUV_444>, grid, block, 0, (hipStream_t)stream, src, frame_stride, dst, H, W, total, k,
-                           aligned);
-    SPEI_CHECK_LAUNCH("spei_yuv_to_rgb_u8");
+    SPEI_YUV_LAUNCH(yuv_to_rgb_kernel, layout, src, frame_stride, dst, H, W, total, k, aligned);
+    SPEI_CHECK_LAUNCH(name);
     return 0;
 }
 
-extern "C" int spei_rgb_u8_to_yuv(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
-                                  spei_stream_t stream) {
-    SPEI_REQUIRE(src && dst, "spei_rgb_u8_to_yuv: null pointer");
-    SPEI_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "spei_rgb_u8_to_yuv: bad frame shape %dx%d", H, W);
-    SPEI_REQUIRE(known(layout, matrix, range), "spei_rgb_u8_to_yuv: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", layout, matrix,
+int from_rgb_u8(const char* name, int lo, int hi, const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix,
+                int range, spei_stream_t stream) {
+    SPEI_REQUIRE(src && dst, "%s: null pointer", name);
+    SPEI_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
+    SPEI_REQUIRE(known(layout, lo, hi, matrix, range), "%s: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", name, layout, matrix,
                  range);
     // rows of 3 W, W and ceil(W/2) bytes: 4-byte aligned when W % 4 == 0 (RGB, Y, and the 4:4:4 planes at H W and 2 H W) and, for
-    // the 4:2:0 chroma planes, when W % 8 == 0
+    // the 4:2:0 and 4:2:2 chroma planes, when W % 8 == 0
     const int al_src = ((uintptr_t)src & 3) == 0 && (W & 3) == 0;
     const int al_y = ((uintptr_t)dst & 3) == 0 && (W & 3) == 0;
     const int al_c = ((uintptr_t)dst & 3) == 0 && (W & 7) == 0;
@@ -479,59 +534,42 @@ extern "C" int spei_rgb_u8_to_yuv(const unsigned char* src, unsigned char* dst, 
     const Coef k = COEF[matrix][range];
     const int limited = range == SPEI_YUV_LIMITED;
     const dim3 grid(grid_for(total)), block(256);
-    if (layout == SPEI_YUV_420_CENTER)
-        hipLaunchKernelGGL(rgb_to_yuv_kernel<SPEI_YUV_420_CENTER>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k, limited,
-                           al_src, al_y, al_c);
-    else if (layout == SPEI_YUV_420_LEFT)
-        hipLaunchKernelGGL(rgb_to_yuv_kernel<SPEI_YUV_420_LEFT>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k, limited,
-                           al_src, al_y, al_c);
-    else
-        hipLaunchKernelGGL(rgb_to_yuv_kernel<SPEI_YUV_444>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k, limited, al_src,
-                           al_y, al_c);
-    SPEI_CHECK_LAUNCH("spei_rgb_u8_to_yuv");
+    SPEI_YUV_LAUNCH(rgb_to_yuv_kernel, layout, src, dst, H, W, total, k, limited, al_src, al_y, al_c);
+    SPEI_CHECK_LAUNCH(name);
     return 0;
 }
 
-extern "C" int spei_yuv_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout, int matrix,
-                                   int range, int depth, spei_stream_t stream) {
-    SPEI_REQUIRE(src && dst, "spei_yuv_to_rgb_u16: null pointer");
-    SPEI_REQUIRE(N >= 1 && H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "spei_yuv_to_rgb_u16: bad frame shape %d x %dx%d", N, H, W);
-    SPEI_REQUIRE(known(layout, matrix, range), "spei_yuv_to_rgb_u16: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", layout, matrix,
+int to_rgb_u16(const char* name, int lo, int hi, const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout,
+               int matrix, int range, int depth, spei_stream_t stream) {
+    SPEI_REQUIRE(src && dst, "%s: null pointer", name);
+    SPEI_REQUIRE(N >= 1 && H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %d x %dx%d", name, N, H, W);
+    SPEI_REQUIRE(known(layout, lo, hi, matrix, range), "%s: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", name, layout, matrix,
                  range);
-    SPEI_REQUIRE(depth == 10 || depth == 12, "spei_yuv_to_rgb_u16: unknown depth %d (10 or 12)", depth);
-    SPEI_REQUIRE(N == 1 || frame_stride >= 2 * planar_bytes(H, W, layout), "spei_yuv_to_rgb_u16: frame stride %lld < one %dx%d planar "
-                 "frame of %lld bytes", (long long)frame_stride, H, W, (long long)(2 * planar_bytes(H, W, layout)));
-    SPEI_REQUIRE(N == 1 || (frame_stride & 1) == 0, "spei_yuv_to_rgb_u16: odd frame stride %lld (bytes, a multiple of 2)",
-                 (long long)frame_stride);
-    SPEI_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 1) == 0, "spei_yuv_to_rgb_u16: src and dst must be 2-byte aligned");
+    SPEI_REQUIRE(depth == 10 || depth == 12, "%s: unknown depth %d (10 or 12)", name, depth);
+    SPEI_REQUIRE(N == 1 || frame_stride >= 2 * planar_bytes(H, W, layout), "%s: frame stride %lld < one %dx%d planar frame of %lld bytes",
+                 name, (long long)frame_stride, H, W, (long long)(2 * planar_bytes(H, W, layout)));
+    SPEI_REQUIRE(N == 1 || (frame_stride & 1) == 0, "%s: odd frame stride %lld (bytes, a multiple of 2)", name, (long long)frame_stride);
+    SPEI_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 1) == 0, "%s: src and dst must be 2-byte aligned", name);
     const int aligned = (((uintptr_t)src | (uintptr_t)dst) & 7) == 0 && (N == 1 || (frame_stride & 7) == 0) && (W & 3) == 0;
     const int64_t total = (int64_t)N * H * ((W + 3) / 4), fstride = N == 1 ? 0 : frame_stride / 2;
     const Coef k = deep_coef(depth, matrix, range);
     const int s = depth - 8;
     const dim3 grid(grid_for(total)), block(256);
-    if (layout == SPEI_YUV_420_CENTER)
-        hipLaunchKernelGGL(yuv_to_rgb_u16_kernel<SPEI_YUV_420_CENTER>, grid, block, 0, (hipStream_t)stream, src, fstride, dst, H, W, total,
-                           k, s, aligned);
-    else if (layout == SPEI_YUV_420_LEFT)
-        hipLaunchKernelGGL(yuv_to_rgb_u16_kernel<SPEI_YUV_420_LEFT>, grid, block, 0, (hipStream_t)stream, src, fstride, dst, H, W, total, k,
-                           s, aligned);
-    else
-        hipLaunchKernelGGL(yuv_to_rgb_u16_kernel<SPEI_YUV_444>, grid, block, 0, (hipStream_t)stream, src, fstride, dst, H, W, total, k, s,
-                           aligned);
-    SPEI_CHECK_LAUNCH("spei_yuv_to_rgb_u16");
+    SPEI_YUV_LAUNCH(yuv_to_rgb_u16_kernel, layout, src, fstride, dst, H, W, total, k, s, aligned);
+    SPEI_CHECK_LAUNCH(name);
     return 0;
 }
 
-extern "C" int spei_rgb_u16_to_yuv(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
-                                   spei_stream_t stream) {
-    SPEI_REQUIRE(src && dst, "spei_rgb_u16_to_yuv: null pointer");
-    SPEI_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "spei_rgb_u16_to_yuv: bad frame shape %dx%d", H, W);
-    SPEI_REQUIRE(known(layout, matrix, range), "spei_rgb_u16_to_yuv: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", layout, matrix,
+int from_rgb_u16(const char* name, int lo, int hi, const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range,
+                 int depth, spei_stream_t stream) {
+    SPEI_REQUIRE(src && dst, "%s: null pointer", name);
+    SPEI_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
+    SPEI_REQUIRE(known(layout, lo, hi, matrix, range), "%s: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", name, layout, matrix,
                  range);
-    SPEI_REQUIRE(depth == 10 || depth == 12, "spei_rgb_u16_to_yuv: unknown depth %d (10 or 12)", depth);
-    SPEI_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 1) == 0, "spei_rgb_u16_to_yuv: src and dst must be 2-byte aligned");
-    // rows of 6 W, 2 W and 2 ceil(W/2) bytes: 8-byte aligned when W % 4 == 0 (RGB, Y, and the 4:4:4 planes) and, for the 4:2:0 chroma
-    // planes, when W % 8 == 0
+    SPEI_REQUIRE(depth == 10 || depth == 12, "%s: unknown depth %d (10 or 12)", name, depth);
+    SPEI_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 1) == 0, "%s: src and dst must be 2-byte aligned", name);
+    // rows of 6 W, 2 W and 2 ceil(W/2) bytes: 8-byte aligned when W % 4 == 0 (RGB, Y, and the 4:4:4 planes) and, for the 4:2:0 and
+    // 4:2:2 chroma planes, when W % 8 == 0
     const int al_src = ((uintptr_t)src & 7) == 0 && (W & 3) == 0;
     const int al_y = ((uintptr_t)dst & 7) == 0 && (W & 3) == 0;
     const int al_c = ((uintptr_t)dst & 7) == 0 && (W & 7) == 0;
@@ -539,15 +577,52 @@ extern "C" int spei_rgb_u16_to_yuv(const uint16_t* src, uint16_t* dst, int H, in
     const Coef k = deep_coef(depth, matrix, range);
     const int limited = range == SPEI_YUV_LIMITED, s = depth - 8;
     const dim3 grid(grid_for(total)), block(256);
-    if (layout == SPEI_YUV_420_CENTER)
-        hipLaunchKernelGGL(rgb_u16_to_yuv_kernel<SPEI_YUV_420_CENTER>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k,
-                           limited, s, al_src, al_y, al_c);
-    else if (layout == SPEI_YUV_420_LEFT)
-        hipLaunchKernelGGL(rgb_u16_to_yuv_kernel<SPEI_YUV_420_LEFT>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k, limited,
-                           s, al_src, al_y, al_c);
-    else
-        hipLaunchKernelGGL(rgb_u16_to_yuv_kernel<SPEI_YUV_444>, grid, block, 0, (hipStream_t)stream, src, dst, H, W, total, k, limited, s,
-                           al_src, al_y, al_c);
-    SPEI_CHECK_LAUNCH("spei_rgb_u16_to_yuv");
+    SPEI_YUV_LAUNCH(rgb_u16_to_yuv_kernel, layout, src, dst, H, W, total, k, limited, s, al_src, al_y, al_c);
+    SPEI_CHECK_LAUNCH(name);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int spei_yuv_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W, int layout,
+                                  int matrix, int range, spei_stream_t stream) {
+    return to_rgb_u8("spei_yuv_to_rgb_u8", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, frame_stride, dst, N, H, W, layout, matrix, range, stream);
+}
+
+extern "C" int spei_rgb_u8_to_yuv(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
+                                  spei_stream_t stream) {
+    return from_rgb_u8("spei_rgb_u8_to_yuv", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, dst, H, W, layout, matrix, range, stream);
+}
+
+extern "C" int spei_yuv_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout, int matrix,
+                                   int range, int depth, spei_stream_t stream) {
+    return to_rgb_u16("spei_yuv_to_rgb_u16", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, frame_stride, dst, N, H, W, layout, matrix, range,
+                      depth, stream);
+}
+
+extern "C" int spei_rgb_u16_to_yuv(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
+                                   spei_stream_t stream) {
+    return from_rgb_u16("spei_rgb_u16_to_yuv", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, dst, H, W, layout, matrix, range, depth, stream);
+}
+
+// ---- 4:2:2 and mono: the same four bodies on SPEI_YUV_422 and SPEI_YUV_MONO ------------------------------------------------------
+extern "C" int spei_planar_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W, int layout,
+                                     int matrix, int range, spei_stream_t stream) {
+    return to_rgb_u8("spei_planar_to_rgb_u8", SPEI_YUV_422, SPEI_YUV_MONO, src, frame_stride, dst, N, H, W, layout, matrix, range, stream);
+}
+
+extern "C" int spei_rgb_u8_to_planar(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
+                                     spei_stream_t stream) {
+    return from_rgb_u8("spei_rgb_u8_to_planar", SPEI_YUV_422, SPEI_YUV_MONO, src, dst, H, W, layout, matrix, range, stream);
+}
+
+extern "C" int spei_planar_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout, int matrix,
+                                      int range, int depth, spei_stream_t stream) {
+    return to_rgb_u16("spei_planar_to_rgb_u16", SPEI_YUV_422, SPEI_YUV_MONO, src, frame_stride, dst, N, H, W, layout, matrix, range, depth,
+                      stream);
+}
+
+extern "C" int spei_rgb_u16_to_planar(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
+                                      spei_stream_t stream) {
+    return from_rgb_u16("spei_rgb_u16_to_planar", SPEI_YUV_422, SPEI_YUV_MONO, src, dst, H, W, layout, matrix, range, depth, stream);
 }

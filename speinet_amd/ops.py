@@ -702,15 +702,22 @@ def d4_mean(members, member_ops, out: Optional[torch.Tensor] = None) -> torch.Te
 
 
 def yuv_frame_bytes(h: int, w: int, layout: int) -> int:
-    """Bytes of one planar YUV frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0, [h][w] each for 4:4:4."""
+    """Bytes of one planar YUV frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0, [h][ceil(w/2)] each for 4:2:2,
+    [h][w] each for 4:4:4; the Y plane alone for mono."""
     return y4m.frame_bytes(h, w, layout)
+
+
+def _yuv_entry(layout: int, name: str, planar: str) -> str:
+    """The C-ABI entry of a conversion for a layout: `name` (spei_yuv_* / spei_*_to_yuv) takes 4:2:0 and 4:4:4, `planar` 4:2:2 and
+    mono (csrc/yuv_io.hip: one kernel template behind both)."""
+    return planar if layout in (y4m.P422, y4m.MONO) else name
 
 
 def yuv_to_rgb_u8(planar: torch.Tensor, h: int, w: int, layout: int, matrix: int, range: int,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Planar uint8 YUV frames on the device, [N, frame_bytes] (rows any stride apart) or one [frame_bytes], as in a y4m FRAME payload
     -> packed RGB uint8 [N,h,w,3] (csrc/yuv_io.hip: integer arithmetic, defined bit for bit in include/speinet_hip.h).  `layout`,
-    `matrix`, `range`: the constants of speinet_amd.y4m (SPEI_YUV_*).  `out` (optional): a contiguous uint8 [N,h,w,3] destination.
+    `matrix`, `range`: the constants of speinet_amd.y4m (SPEI_YUV_*; P422 and MONO go to spei_planar_to_rgb_u8).  `out` (optional): a contiguous uint8 [N,h,w,3] destination.
     One launch on the current stream, no host sync."""
     assert planar.is_cuda and planar.dtype == torch.uint8 and planar.dim() in (1, 2)
     fr = planar if planar.dim() == 2 else planar.unsqueeze(0)
@@ -723,8 +730,8 @@ def yuv_to_rgb_u8(planar: torch.Tensor, h: int, w: int, layout: int, matrix: int
     lib = _lib.lib()
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_yuv_to_rgb_u8(_vp(fr.data_ptr()), fr.stride(0), _vp(out.data_ptr()), n, h, w, layout, matrix, range, st),
-                   "spei_yuv_to_rgb_u8")
+        entry = _yuv_entry(layout, "spei_yuv_to_rgb_u8", "spei_planar_to_rgb_u8")
+        _lib.check(getattr(lib, entry)(_vp(fr.data_ptr()), fr.stride(0), _vp(out.data_ptr()), n, h, w, layout, matrix, range, st), entry)
     return out
 
 
@@ -742,8 +749,8 @@ def rgb_u8_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, out: 
     lib = _lib.lib()
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_rgb_u8_to_yuv(_vp(rgb.data_ptr()), _vp(out.data_ptr()), h, w, layout, matrix, range, st),
-                   "spei_rgb_u8_to_yuv")
+        entry = _yuv_entry(layout, "spei_rgb_u8_to_yuv", "spei_rgb_u8_to_planar")
+        _lib.check(getattr(lib, entry)(_vp(rgb.data_ptr()), _vp(out.data_ptr()), h, w, layout, matrix, range, st), entry)
     return out
 
 
@@ -765,8 +772,9 @@ def yuv_to_rgb_u16(planar: torch.Tensor, h: int, w: int, layout: int, matrix: in
     lib = _lib.lib()
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_yuv_to_rgb_u16(_vp(fr.data_ptr()), 2 * fr.stride(0), _vp(out.data_ptr()), n, h, w, layout, matrix, range, depth,
-                                           st), "spei_yuv_to_rgb_u16")
+        entry = _yuv_entry(layout, "spei_yuv_to_rgb_u16", "spei_planar_to_rgb_u16")
+        _lib.check(getattr(lib, entry)(_vp(fr.data_ptr()), 2 * fr.stride(0), _vp(out.data_ptr()), n, h, w, layout, matrix, range, depth, st),
+                   entry)
     return out
 
 
@@ -785,8 +793,8 @@ def rgb_u16_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, dept
     lib = _lib.lib()
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.spei_rgb_u16_to_yuv(_vp(rgb.data_ptr()), _vp(out.data_ptr()), h, w, layout, matrix, range, depth, st),
-                   "spei_rgb_u16_to_yuv")
+        entry = _yuv_entry(layout, "spei_rgb_u16_to_yuv", "spei_rgb_u16_to_planar")
+        _lib.check(getattr(lib, entry)(_vp(rgb.data_ptr()), _vp(out.data_ptr()), h, w, layout, matrix, range, depth, st), entry)
     return out
 
 

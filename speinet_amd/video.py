@@ -3,7 +3,8 @@
 
     python -m speinet_amd.video --input <dir | glob | clip.y4m | -> --output <dir | out.y4m | -> --model_path <checkpoint | synthetic>
                                 [--labels <file.npy>] [--detector <detector.json>] [--cuts none|auto|<file>]
-                                [--matrix bt601|bt709] [--range full|limited] [--fps num:den] [--chroma 420jpeg|420mpeg2|444]
+                                [--matrix bt601|bt709] [--range full|limited] [--fps num:den]
+                                [--chroma 420jpeg|420mpeg2|422|444|mono] [--out_chroma 420jpeg|420mpeg2|422|444|mono]
                                 [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N] [--ensemble 1|2|4|8]
                                 [--roi none|auto|Y,X,H,W] [--roi_feather N]
 
@@ -23,6 +24,10 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
   * the frames come from speinet_amd.clip (`frames_of`, `FrameCache`); a window whose 16-bit pass left a non-finite value is recomputed in bf16x3;
   * a y4m clip (speinet_amd.y4m) crosses PCIe as its planar bytes, 1.5 per pixel for 4:2:0, and becomes packed RGB on the device
     (csrc/yuv_io.hip, integer arithmetic); a y4m output is made there from the deblurred frame the same way;
+  * 4:2:2 and mono streams (`C422`, `C422p10`, `C422p12`, `Cmono`, `Cmono10`, `Cmono12`: what `ffmpeg -pix_fmt yuv422p10le` or `gray10le`
+    `-f yuv4mpegpipe` writes) take the same road at 2 and 1 samples per pixel: `deblur_clip` and the command line open their readers
+    with `layouts=y4m.LAYOUTS`, and everything behind `Frames.rgb` sees packed RGB.  `--out_chroma` writes the y4m output in another
+    layout than the input's (4:2:2 in and 4:2:0 out for delivery, 4:2:0 in and 4:4:4 out to avoid a second subsampling);
   * a deep clip (10 or 12 bits per sample: a `C420p10` ... `C444p12` y4m stream, or uint16 frames with `depth=`) never passes through
     8 bits: its bytes cross PCIe through the same page-locked rings, the labelling pass, the scene statistics and the window loop
     read uint16 frames (`ops.frames_u16_in`, `ops.frame_pair_stats_u16`), and the deblurred frame is quantised once, to `out_depth`
@@ -558,6 +563,8 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              Deep clips: a 10- or 12-bit y4m stream (`C420p10` ... `C444p12`; a path, or a reader opened with
              `depths=(8, 10, 12)`; deep 4:2:0 has no siting tag, the reader's `layout` says LEFT unless the caller sets it), or uint16
              frames ([T,H,W,3], or a list of [H,W,3]) with `depth`.  A deep clip never passes through 8 bits.
+             4:2:2 and mono clips (`C422*`, `Cmono*`): a path, or a reader opened with `layouts=y4m.LAYOUTS`; 2 and 1 samples per
+             pixel cross PCIe.
     labels — optional 0/1 per frame (1 = sharp); None: the LD detector labels the clip in a first streaming pass.
     out    — optional contiguous [T,H,W,3] tensor on the model's device, uint8 for `out_depth` 8 and uint16 for 10 and 12: frame i is
              written to out[i] and that view is yielded.
@@ -636,7 +643,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
         raise ValueError(f"bar_params holds {sorted(set(bar_params) - set(BAR_PARAMS))}: find_bars takes level and min_bar, and frames is "
                          "the number of frames that active_area scans")
     if isinstance(frames, (str, os.PathLike)) and os.fspath(frames).lower().endswith(".y4m"):
-        frames = y4m.Y4MReader(frames, depths=y4m.DEPTHS)
+        frames = y4m.Y4MReader(frames, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
     fr = frames_of(frames, crop, yuv, depth)
     if roi is not None and not isinstance(roi, str):
         roi = roi_of(tuple(roi) if isinstance(roi, list) else roi, fr.H, fr.W)
@@ -763,8 +770,11 @@ def main(argv=None) -> None:
                    "input's XCOLORRANGE tag, limited without one; full for image input)")
     p.add_argument("--fps", type=_fps, default=None, help="frame rate of y4m output as num:den (default: the y4m input's; 25:1 for image input)")
     p.add_argument("--chroma", choices=sorted(y4m.TAG_OF_LAYOUT.values()), default=None, help="chroma layout of y4m output from image "
-                   "input (default 420jpeg; y4m input keeps its own); 420jpeg | 420mpeg2 also select the chroma siting of a 10- or "
-                   "12-bit 4:2:0 y4m input, whose tag carries none (default 420mpeg2: co-sited with the even column)")
+                   "input (default 420jpeg; y4m input keeps its own, see --out_chroma); 420jpeg | 420mpeg2 also select the chroma "
+                   "siting of a 10- or 12-bit 4:2:0 y4m input, whose tag carries none (default 420mpeg2: co-sited with the even column)")
+    p.add_argument("--out_chroma", choices=sorted(y4m.TAG_OF_LAYOUT.values()), default=None, help="chroma layout of the y4m output whatever "
+                   "the input was: 4:2:2 in and 420mpeg2 out for delivery, 4:2:0 in and 444 out to avoid a second subsampling (default: "
+                   "the y4m input's layout, or --chroma for image input)")
     p.add_argument("--out_depth", type=int, choices=y4m.DEPTHS, default=None, help="bits per sample of the output (default: the "
                    "input's for y4m output; a PNG directory always gets 8-bit files)")
     p.add_argument("--tiles", default="none", help="deblur every frame as a grid of overlapping tiles, stitched with hard seams (or "
@@ -808,16 +818,19 @@ def main(argv=None) -> None:
     if not to_y4m and a.out_depth not in (None, 8):
         raise SystemExit(f"--out_depth {a.out_depth}: a PNG directory gets 8-bit files; write a .y4m file or '-' for a deep output")
 
+    if not to_y4m and a.out_chroma is not None:
+        raise SystemExit(f"--out_chroma {a.out_chroma}: a PNG directory holds RGB files; write a .y4m file or '-' for a chroma layout")
+
     def say(text: str) -> None:
         print(text, file=log, flush=True)
 
     reader = None
     if a.input == "-":
-        reader = y4m.Y4MReader(_spool(sys.stdin.buffer, a.spool_dir), depths=y4m.DEPTHS)
+        reader = y4m.Y4MReader(_spool(sys.stdin.buffer, a.spool_dir), depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
     elif a.input.lower().endswith(".y4m") and os.path.isfile(a.input):
-        reader = y4m.Y4MReader(a.input, depths=y4m.DEPTHS)
+        reader = y4m.Y4MReader(a.input, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
     if reader is not None:
-        if reader.depth > 8 and reader.layout != y4m.P444 and a.chroma in ("420jpeg", "420mpeg2"):
+        if reader.depth > 8 and reader.layout in (y4m.CENTER, y4m.LEFT) and a.chroma in ("420jpeg", "420mpeg2"):
             reader.layout = y4m.layout_of(a.chroma)
         if len(reader) < 2:
             raise SystemExit(f"--input {a.input}: {len(reader)} frame(s) found, a clip needs at least 2")
@@ -853,9 +866,13 @@ def main(argv=None) -> None:
             layout, rng = y4m.layout_of(a.chroma or "420jpeg"), y4m.range_of(a.range or "full")
             matrix = y4m.matrix_of(a.matrix) if a.matrix else (y4m.BT709 if H >= 720 else y4m.BT601)
             fps, aspect = a.fps or (25, 1), None
+        if a.out_chroma is not None:
+            layout = y4m.layout_of(a.out_chroma)
         writer = y4m.Y4MWriter(sys.stdout.buffer if to_stdout else a.output, W, H, fps, layout, rng, aspect, depth=out_depth)
     else:
         os.makedirs(a.output, exist_ok=True)
+    if reader is not None:
+        say(f"# y4m input C{reader.chroma}" + (f", output C{writer.chroma}" if writer is not None and writer.chroma != reader.chroma else ""))
     if run.roi is not None:
         say("# roi " + ",".join(str(v) for v in run.roi))
     for c in run.cuts:

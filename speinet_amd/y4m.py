@@ -4,8 +4,10 @@ become packed RGB there (csrc/yuv_io.hip, `ops.yuv_to_rgb_u8`), and come back th
 
 Supported: progressive 8-bit 4:2:0 (`C420jpeg`, bare `C420`, `C420mpeg2`) and 4:4:4 (`C444`), and, for a reader opened with
 `depths=(8, 10, 12)`, 10- and 12-bit 4:2:0 and 4:4:4 (`C420p10`, `C420p12`, `C444p10`, `C444p12`: little-endian 16-bit samples, which
-`ops.yuv_to_rgb_u16` / `ops.rgb_u16_to_yuv` convert).  Not supported: interlaced streams, other depths, 4:2:2, 4:1:1, mono,
-`C420paldv`."""
+`ops.yuv_to_rgb_u16` / `ops.rgb_u16_to_yuv` convert).  For a reader opened with `layouts=LAYOUTS`, also 4:2:2 (`C422`, `C422p10`,
+`C422p12`: chroma planes [H][ceil(W/2)], co-sited with the even column) and mono (`Cmono`, `Cmono10`, `Cmono12`: the Y plane alone) at
+the depths it was given; the same four `ops` functions convert them.  Not supported: interlaced streams, other depths (9, 14, 16
+bits), 4:1:1, 4:4:0, `C420paldv`."""
 from __future__ import annotations
 
 import os
@@ -15,14 +17,18 @@ import threading
 import numpy as np
 
 CENTER, LEFT, P444 = 0, 1, 2           # SPEI_YUV_420_CENTER, SPEI_YUV_420_LEFT, SPEI_YUV_444 (include/speinet_hip.h)
+P422, MONO = 3, 4                      # SPEI_YUV_422, SPEI_YUV_MONO
+LAYOUTS = (CENTER, LEFT, P444, P422, MONO)
 BT601, BT709 = 0, 1                    # SPEI_YUV_BT601, SPEI_YUV_BT709
 FULL, LIMITED = 0, 1                   # SPEI_YUV_FULL, SPEI_YUV_LIMITED
 
 MAGIC = b"YUV4MPEG2"
-LAYOUT_OF_TAG = {"420jpeg": CENTER, "420": CENTER, "420mpeg2": LEFT, "444": P444}
-DEEP_TAGS = {"420p10": (LEFT, 10), "420p12": (LEFT, 12), "444p10": (P444, 10), "444p12": (P444, 12)}     # tag -> (layout, depth)
+# a reader takes a tag only if its layout is among the reader's `layouts` (P422 and MONO are an opt-in)
+LAYOUT_OF_TAG = {"420jpeg": CENTER, "420": CENTER, "420mpeg2": LEFT, "444": P444, "422": P422, "mono": MONO}
+DEEP_TAGS = {"420p10": (LEFT, 10), "420p12": (LEFT, 12), "444p10": (P444, 10), "444p12": (P444, 12),     # tag -> (layout, depth)
+             "422p10": (P422, 10), "422p12": (P422, 12), "mono10": (MONO, 10), "mono12": (MONO, 12)}
 DEPTHS = (8, 10, 12)
-TAG_OF_LAYOUT = {CENTER: "420jpeg", LEFT: "420mpeg2", P444: "444"}
+TAG_OF_LAYOUT = {CENTER: "420jpeg", LEFT: "420mpeg2", P444: "444", P422: "422", MONO: "mono"}
 MATRIX_NAMES = {"bt601": BT601, "bt709": BT709}
 RANGE_NAMES = {"full": FULL, "limited": LIMITED}
 HINT = "convert it with `ffmpeg -i <in> -pix_fmt yuv420p -f yuv4mpegpipe <out.y4m>`"
@@ -48,7 +54,8 @@ def range_of(value) -> int:
 
 
 def layout_of(value) -> int:
-    """CENTER / LEFT / P444 from the constant or from a y4m chroma tag ("420jpeg", "420", "420mpeg2", "444")."""
+    """CENTER / LEFT / P444 / P422 / MONO from the constant or from a y4m chroma tag ("420jpeg", "420", "420mpeg2", "444", "422",
+    "mono")."""
     return _named(value, LAYOUT_OF_TAG, "chroma layout")
 
 
@@ -60,20 +67,21 @@ def depth_of(depth) -> int:
 
 
 def frame_bytes(h: int, w: int, layout: int, depth: int = 8) -> int:
-    """Bytes of one planar frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0 and [h][w] each for 4:4:4; one byte
-    per sample at `depth` 8, two (a little-endian word) at 10 and 12."""
+    """Bytes of one planar frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0, [h][ceil(w/2)] each for 4:2:2 and
+    [h][w] each for 4:4:4 (mono: the Y plane alone); one byte per sample at `depth` 8, two (a little-endian word) at 10 and 12."""
     if layout not in TAG_OF_LAYOUT:
         raise ValueError(f"unknown chroma layout {layout!r}")
-    samples = h * w + 2 * (h * w if layout == P444 else ((h + 1) // 2) * ((w + 1) // 2))
+    chroma = {P444: h * w, P422: h * ((w + 1) // 2), MONO: 0}.get(layout, ((h + 1) // 2) * ((w + 1) // 2))
+    samples = h * w + 2 * chroma
     return samples * (1 if depth_of(depth) == 8 else 2)
 
 
 def chroma_tag(layout: int, depth: int = 8) -> str:
-    """The C tag's text of a layout at a depth: "420jpeg", "420mpeg2", "444"; "420p10", "444p12" and the like for deep streams (which
-    carry no siting)."""
+    """The C tag's text of a layout at a depth: "420jpeg", "420mpeg2", "444", "422", "mono"; "420p10", "444p12", "422p10", "mono12"
+    and the like for deep streams (which carry no siting)."""
     if depth_of(depth) == 8:
         return TAG_OF_LAYOUT[layout]
-    return f"{'444' if layout == P444 else '420'}p{depth}"
+    return {P444: "444p", P422: "422p", MONO: "mono"}.get(layout, "420p") + str(depth)
 
 
 def _ratio(tag: str, text: str):
@@ -99,16 +107,22 @@ class Y4MReader:
     siting: `layout` is then LEFT, the MPEG-2 siting of the codecs such streams come from; it is a plain attribute that the caller
     may set to CENTER before the clip is used.
 
-    Attributes: `width`, `height`, `fps` and `aspect` ((num, den); 25:1 and None when absent), `layout` (CENTER / LEFT / P444),
+    `layouts`: the chroma layouts the caller can take, an opt-in like `depths`.  The default, (CENTER, LEFT, P444), refuses `C422*`
+    and `Cmono*`, whatever `depths` says; with `layouts=LAYOUTS` the reader also accepts `C422` and `Cmono` and, at the depths it
+    was given, `C422p10`, `C422p12`, `Cmono10` and `Cmono12` (`layout` is then P422 or MONO).
+
+    Attributes: `width`, `height`, `fps` and `aspect` ((num, den); 25:1 and None when absent), `layout` (CENTER / LEFT / P444; P422 /
+    MONO for a reader that takes them),
     `depth` (8, 10 or 12), `chroma` (the C tag's text), `range` (from XCOLORRANGE=FULL|LIMITED; LIMITED when absent), `matrix`, `frame_bytes`.  y4m carries
     no matrix tag: `matrix` is BT709 when height >= 720 and BT601 otherwise, which is ffmpeg's usual guess for untagged video;
     assign `matrix` / `range`, or pass `yuv=dict(matrix=..., range=...)` to `deblur_clip`, to override.
 
-    Interlaced streams, depths outside `depths` (9, 14 and 16 bits always), C420paldv, C422, C411 and Cmono at any depth are
-    rejected with a ValueError that names the tag."""
+    Interlaced streams, depths outside `depths` (9, 14 and 16 bits always), layouts outside `layouts` (C422 and Cmono at any depth
+    by default), C420paldv, C411 and C440 are rejected with a ValueError that names the tag."""
 
-    def __init__(self, path_or_file, depths=(8,)):
+    def __init__(self, path_or_file, depths=(8,), layouts=(CENTER, LEFT, P444)):
         self.depths = tuple(depth_of(d) for d in depths)
+        self.layouts = tuple(layout_of(v) for v in layouts)
         self._own = isinstance(path_or_file, (str, bytes, os.PathLike))
         self._f = open(path_or_file, "rb") if self._own else path_or_file
         self.name = os.fspath(path_or_file) if self._own else getattr(path_or_file, "name", "<file>")
@@ -158,20 +172,25 @@ class Y4MReader:
             if val < 1:
                 self._fail(f"tag {key}{val}: the size must be positive")
         c = self.chroma
-        if c in DEEP_TAGS and DEEP_TAGS[c][1] in self.depths:
-            self.layout, self.depth = DEEP_TAGS[c]
-        elif c in LAYOUT_OF_TAG and 8 in self.depths:
-            self.layout, self.depth = LAYOUT_OF_TAG[c], 8
+        # the tags of the layouts this reader takes: a tag of another layout is as unknown to it as C411
+        flat = {t: lay for t, lay in LAYOUT_OF_TAG.items() if lay in self.layouts}
+        deep_tags = {t: v for t, v in DEEP_TAGS.items() if v[0] in self.layouts}
+        if c in deep_tags and deep_tags[c][1] in self.depths:
+            self.layout, self.depth = deep_tags[c]
+        elif c in flat and 8 in self.depths:
+            self.layout, self.depth = flat[c], 8
         else:
             deep = re.fullmatch(r"(?:(?:420|422|444)p|mono)(\d+)", c)
-            if c in LAYOUT_OF_TAG:
+            wide = P422 in self.layouts or MONO in self.layouts
+            if c in flat:
                 why = f"8 bits per sample ({', '.join(map(str, self.depths))} only)"
             elif deep and self.depths != (8,) and int(deep.group(1)) in self.depths:     # C422p10, Cmono12: not the depth's fault
                 why = "only 4:2:0 and 4:4:4 are supported"
             elif deep:
                 why = f"{deep.group(1)} bits per sample ({', '.join(map(str, self.depths))} only)"
             elif c.startswith(("422", "411", "mono")) or c == "420paldv":
-                why = "only 4:2:0 (C420jpeg, C420, C420mpeg2) and 4:4:4 (C444) are supported"
+                why = ("only 4:2:0 (C420jpeg, C420, C420mpeg2), 4:2:2 (C422), 4:4:4 (C444) and mono (Cmono) are supported" if wide else
+                       "only 4:2:0 (C420jpeg, C420, C420mpeg2) and 4:4:4 (C444) are supported")
             else:
                 why = "unknown chroma format"
             self._fail(f"tag C{c}: {why}")
@@ -235,8 +254,9 @@ class Y4MReader:
 class Y4MWriter:
     """Write a progressive y4m stream: the header once, then `write(planar bytes)` per frame (`frame_bytes` bytes: a bytes-like
     object or a contiguous numpy array, uint8, or uint16 for a deep stream).  `path_or_file`: a path, or a binary file object (a pipe
-    will do), which `close` flushes and leaves open.  `depth` 10 or 12 writes `C420p10`, `C444p12` and the like (little-endian words;
-    the tag carries no siting, whatever `layout` says) and adds `XYSCSS=420P10` and the like, as ffmpeg does."""
+    will do), which `close` flushes and leaves open.  `depth` 10 or 12 writes `C420p10`, `C444p12`, `C422p10`, `Cmono12` and the like
+    (little-endian words; the tag carries no siting, whatever `layout` says) and adds `XYSCSS=420P10`, `XYSCSS=422P12` and the like,
+    as ffmpeg does (none for mono).  `layout` P422 / MONO writes `C422` / `Cmono` frames: Y, then U and V of [h][ceil(w/2)]; Y alone."""
 
     def __init__(self, path_or_file, w: int, h: int, fps=(25, 1), layout: int = CENTER, range: int = LIMITED, aspect=None,
                  depth: int = 8):
@@ -251,7 +271,7 @@ class Y4MWriter:
         tags = [f"W{self.width}", f"H{self.height}", f"F{self.fps[0]}:{self.fps[1]}", "Ip"]
         if aspect is not None:
             tags.append(f"A{int(aspect[0])}:{int(aspect[1])}")
-        tags += [f"C{self.chroma}"] + ([] if self.depth == 8 else [f"XYSCSS={self.chroma.upper()}"])
+        tags += [f"C{self.chroma}"] + ([] if self.depth == 8 or self.layout == MONO else [f"XYSCSS={self.chroma.upper()}"])
         tags += ["XCOLORRANGE=" + ("FULL" if self.range == FULL else "LIMITED")]
         self._f.write(MAGIC + b" " + " ".join(tags).encode("ascii") + b"\n")
         self.frames = 0
