@@ -1,6 +1,8 @@
 """The clip as a source, for the clip loop (speinet_amd.video), the labelling pass (speinet_amd.detector), the loaders (speinet_amd.data),
 blur synthesis (speinet_amd.blurset) and the harness (speinet_amd.inference).  `frames_of` validates a clip in any form the clip API takes
-and returns it as `Frames`: frame i on the host or on the device, a rectangle of every frame (`view`), a subset of the frames (`sample`).
+and returns it as `Frames`: frame i on the host or on the device, a rectangle of every frame (`view`), a subset of the frames (`sample`);
+a clip of unknown length (a `y4m.Y4MStream`, an iterator of frames) as `StreamFrames`, the same interface over a bounded ring of frames
+that one reader thread fills (`FrameRing`).
 Frames cross PCIe as uint8 (a deep clip's as its bytes) from page-locked staging buffers (`FrameCache`) and are decoded, for image paths, on
 worker threads a few windows ahead; finished frames land in page-locked memory for worker threads (`HostRing`).  `imread` / `imwrite`: the
 image codec of every tool."""
@@ -175,6 +177,13 @@ class Frames:
     def _crop(self, f):
         return f[..., self.y0:self.y0 + self.H, self.x0:self.x0 + self.W, :]
 
+    def upto(self, i: int) -> int:
+        """How many of the first i frames exist: min(i, T).  A stream (`StreamFrames`) waits for frame i - 1 or its end."""
+        return min(i, self.T)
+
+    def release(self, lo: int) -> None:
+        """No frame below `lo` will be asked for again: a stream gives up their buffers."""
+
     def on_device(self, i: int) -> bool:
         if self.yuv is not None:
             return False
@@ -213,6 +222,157 @@ class Frames:
         return self._crop(img)
 
 
+class FrameRing:
+    """A bounded window on a stream of frames: one reader thread calls `fill(slot) -> bool` (False: the stream has ended) for frame
+    0, 1, 2, ... in turn, each into slot i % capacity of `capacity` buffers of one shape, page-locked where a GPU is present.  The
+    thread blocks while frame `lo + capacity` would overwrite a frame that has not been released; `release(lo)` frees every frame
+    below `lo`.  `upto(i)` blocks until frame i - 1 has been read or the stream has ended and returns min(i, frames read);
+    `get(i)` is frame i's buffer (a view, valid until the frame is released), and an IndexError for a frame that was released or
+    has not been read yet: either is a bug of the caller's.  `T` is None until the stream has ended, then its length.  An error in
+    the reader thread (a frame cut short) is raised from `upto`."""
+
+    def __init__(self, fill, shape, dtype, capacity: int):
+        import threading
+        if capacity < 1:
+            raise ValueError(f"a frame ring needs at least one slot, got {capacity}")
+        pin = torch.cuda.is_available()
+        self.slots = [torch.empty(shape, dtype=dtype, pin_memory=pin).numpy() for _ in range(capacity)]
+        self.capacity, self.fill = capacity, fill
+        self.lo, self.read, self.T, self.error, self.closed = 0, 0, None, None, False
+        self.cv = threading.Condition()
+        self.thread = threading.Thread(target=self._work, name="speinet-frame-ring", daemon=True)
+        self.thread.start()                          # `fill` must not need this object: it is not its owner's yet
+
+    def _work(self) -> None:
+        try:
+            while True:
+                with self.cv:
+                    self.cv.wait_for(lambda: self.closed or self.read < self.lo + self.capacity)
+                    if self.closed:
+                        return
+                    slot = self.slots[self.read % self.capacity]
+                more = self.fill(slot)               # blocks on the source, outside the lock
+                with self.cv:
+                    if more:
+                        self.read += 1
+                    else:
+                        self.T = self.read
+                    self.cv.notify_all()
+                if not more:
+                    return
+        except BaseException as e:                   # handed to the consumer: `upto` raises it
+            with self.cv:
+                self.error, self.T = e, self.read
+                self.cv.notify_all()
+
+    def upto(self, i: int) -> int:
+        with self.cv:
+            if self.T is None and i > self.lo + self.capacity:
+                raise IndexError(f"frame {i - 1} cannot be waited for: the ring holds {self.capacity} frames from {self.lo} on")
+            self.cv.wait_for(lambda: self.read >= i or self.T is not None)
+            if self.error is not None and self.read < i:
+                raise self.error
+            return min(i, self.read)
+
+    def ready(self, i: int) -> int:
+        """min(i, frames read so far), without waiting."""
+        with self.cv:
+            return min(i, self.read)
+
+    def get(self, i: int) -> np.ndarray:
+        with self.cv:
+            if not self.lo <= i < self.read:
+                raise IndexError(f"frame {i} was released already (the ring starts at {self.lo})" if i < self.lo else
+                                 f"frame {i} has not been read yet ({self.read} so far)")
+            return self.slots[i % self.capacity]
+
+    def release(self, lo: int) -> None:
+        with self.cv:
+            if lo > self.lo:
+                self.lo = min(lo, self.read)
+                self.cv.notify_all()
+
+    def close(self) -> None:
+        """Stop the reader thread at its next frame (one blocked on its source ends with the process: it is a daemon)."""
+        with self.cv:
+            self.closed = True
+            self.cv.notify_all()
+
+
+class StreamFrames(Frames):
+    """A clip whose length is not known before its last frame: `Frames` over a `FrameRing`.  `T` is None until the stream has ended.
+    `source`: a `y4m.Y4MStream` (`host(i)` is then the frame's planar bytes and `yuv` its (layout, matrix, range), as for a reader),
+    or an iterator of uint8 [H,W,3] frames (uint16 with `depth`: arrays or host tensors), whose first frame `frames_of` has taken
+    already (`first`).  `host`, `rgb`, `view`, `depth`, `dtype` and `yuv` are `Frames`'; `upto(i)` waits for frame i - 1 (or the
+    end), `release(lo)` gives up every frame below `lo`, `ready(i)` does not wait.  `capacity`: the ring's slots; the clip loop sets
+    it from its look-ahead (`reserve`) before the first frame is asked for, which is when the reader thread starts."""
+
+    def __init__(self, source, H: int, W: int, crop: bool = False, yuv=None, depth: int = 8, first=None, capacity: int = 64):
+        Frames.__init__(self, source, None, H, W, paths=False, crop=crop, yuv=yuv, depth=depth)
+        self._shared = {"ring": None, "capacity": capacity, "first": first}
+
+    T = property(lambda self: None if self._shared["ring"] is None else self._shared["ring"].T, lambda self, value: None)
+
+    def reserve(self, capacity: int) -> None:
+        if self._shared["ring"] is not None:
+            raise RuntimeError("the frame ring is running already")
+        self._shared["capacity"] = capacity
+
+    @property
+    def ring(self) -> FrameRing:
+        sh = self._shared
+        if sh["ring"] is None:
+            if self.yuv is not None:
+                sh["ring"] = FrameRing(self.items.read_into, (self.items.frame_bytes,), torch.uint8, sh["capacity"])
+            else:
+                sh["ring"] = FrameRing(self._next, (*self.src, 3), self.dtype, sh["capacity"])
+        return sh["ring"]
+
+    def _next(self, slot: np.ndarray) -> bool:
+        """The iterator's next frame into `slot` (the reader thread)."""
+        sh = self._shared
+        f, sh["first"] = sh["first"], None
+        if f is None:
+            f = next(self.items, None)
+            if f is None:
+                return False
+        n = sh["taken"] = sh.get("taken", -1) + 1
+        if not isinstance(f, (np.ndarray, torch.Tensor)) or (torch.is_tensor(f) and f.is_cuda):
+            raise ValueError(f"frame {n} of the stream is a {type(f).__name__}, not a host array or tensor")
+        a = f.numpy() if torch.is_tensor(f) else f
+        if a.shape != slot.shape or a.dtype != slot.dtype:
+            raise ValueError(f"mixed frames: frame 0 is {self.src[1]}x{self.src[0]} {slot.dtype}, frame {n} has shape {tuple(a.shape)} "
+                             f"and is {a.dtype}")
+        slot[...] = a
+        return True
+
+    def upto(self, i: int) -> int:
+        return self.ring.upto(i)
+
+    def ready(self, i: int) -> int:
+        return self.ring.ready(i)
+
+    def release(self, lo: int) -> None:
+        self.ring.release(lo)
+
+    def close(self) -> None:
+        if self._shared["ring"] is not None:
+            self._shared["ring"].close()
+
+    def sample(self, index):
+        raise ValueError("a stream cannot be sampled: its frames are read once, in order")
+
+    def on_device(self, i: int) -> bool:
+        return False
+
+    def device(self, i: int):
+        raise ValueError("a stream's frames are on the host")
+
+    def host(self, i: int) -> np.ndarray:
+        f = self.ring.get(i)
+        return f if self.yuv is not None else self._crop(f)
+
+
 def _check_frame(i, shape, dtype, depth=None) -> None:
     if dtype in (np.uint16, torch.uint16):
         if depth is None:
@@ -232,7 +392,8 @@ def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None, depth: Opt
     image paths (only their headers are read here), or a `y4m.Y4MReader` (`yuv`: optional `matrix` / `range` in place of the
     reader's; a reader opened with `depths=(8, 10, 12)` may hold a deep clip).  uint16 arrays, tensors or lists of them are deep
     frames and need `depth` = 10 or 12 (bits per sample; a word above 2^depth - 1 reads as that); `depth` with anything else is an
-    error.  Raises ValueError with the reason."""
+    error.  A `y4m.Y4MStream`, or an iterator of host frames ([H,W,3] uint8, or uint16 with `depth`), is a clip of unknown length
+    and comes back as `StreamFrames` (the iterator's first frame is taken here).  Raises ValueError with the reason."""
     if depth is not None and (isinstance(depth, bool) or depth not in (10, 12)):
         raise ValueError(f"depth must be 10 or 12, got {depth!r}")
     if isinstance(frames, y4m.Y4MReader):
@@ -245,8 +406,24 @@ def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None, depth: Opt
         _check_frame(0, (frames.height, frames.width, 3), np.uint8)
         how = (frames.layout, y4m.matrix_of((yuv or {}).get("matrix", frames.matrix)), y4m.range_of((yuv or {}).get("range", frames.range)))
         return Frames(frames, len(frames), frames.height, frames.width, paths=False, crop=crop, yuv=how, depth=frames.depth)
+    if isinstance(frames, y4m.Y4MStream):              # a stream: its length is not known here (`StreamFrames`)
+        if depth is not None:
+            raise ValueError("depth= applies to uint16 frames only: a y4m clip carries its own")
+        if set(yuv or {}) - {"matrix", "range"}:
+            raise ValueError(f"yuv holds {sorted(set(yuv) - {'matrix', 'range'})}: it takes matrix and range")
+        _check_frame(0, (frames.height, frames.width, 3), np.uint8)
+        how = (frames.layout, y4m.matrix_of((yuv or {}).get("matrix", frames.matrix)), y4m.range_of((yuv or {}).get("range", frames.range)))
+        return StreamFrames(frames, frames.height, frames.width, crop=crop, yuv=how, depth=frames.depth)
     if yuv is not None:
         raise ValueError("yuv= applies to y4m clips only")
+    if hasattr(frames, "__next__"):                    # an iterator of frames: the first one says what the others must be
+        first = next(frames, None)
+        if first is None:
+            raise ValueError("a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got 0")
+        if not isinstance(first, (np.ndarray, torch.Tensor)) or (torch.is_tensor(first) and first.is_cuda):
+            raise ValueError(f"frame 0 of the stream is a {type(first).__name__}, not a host array or tensor")
+        _check_frame(0, tuple(first.shape), first.dtype, depth)
+        return StreamFrames(frames, int(first.shape[0]), int(first.shape[1]), crop=crop, depth=depth or 8, first=first)
     if isinstance(frames, (str, bytes)) or not hasattr(frames, "__len__") or not hasattr(frames, "__getitem__"):
         raise ValueError(f"frames must be an indexable sequence of frames, got {type(frames).__name__}")
     T = len(frames)

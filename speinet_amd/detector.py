@@ -112,19 +112,20 @@ def predict(features, params: Optional[DetectorParams] = None) -> np.ndarray:
 
 
 def clip_batches(fr, device, batch: int = DETECT_BATCH):
-    """One streaming pass over a clip (`clip.frames_of`'s result): yields (first frame index, uint8 [n,H,W,3] device view) for every
+    """One streaming pass over a clip (`clip.frames_of`'s result; a `clip.StreamFrames` is read as it arrives: `fr.upto` waits for
+    the next batch's frames or the stream's end): yields (first frame index, uint8 [n,H,W,3] device view) for every
     `batch` frames in turn, on the current stream of `device`.  Host frames are uploaded from two page-locked staging buffers (image
     paths decoded on worker threads two batches ahead), device-resident frames copied on the device.  The frames of a y4m clip are
     staged and uploaded as their planar bytes and made RGB on the device (`fr.rgb`: ops.yuv_to_rgb_u8, or ops.yuv_to_rgb_u16 for a
     deep clip).  A deep clip (`fr.depth` 10 or 12) yields uint16 frames: its samples never pass through 8 bits.  The view is of ONE
     buffer that the next batch overwrites: device memory is bounded by one batch.  The consumer sets grad mode and the current device."""
     dev, B = torch.device(device), batch
-    T, H, W = fr.T, fr.H, fr.W
+    H, W = fr.H, fr.W
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as pool:
         futs = {}
 
         def want(upto):
-            for i in range(min(upto, T)):
+            for i in range(done, upto):           # frames below `done` were yielded: a stream has given them up
                 if i not in futs and not fr.on_device(i):
                     futs[i] = pool.submit(fr.host, i)
 
@@ -133,9 +134,12 @@ def clip_batches(fr, device, batch: int = DETECT_BATCH):
         events = [None, None]
         dev_batch = torch.empty(B, H, W, 3, dtype=fr.dtype, device=dev)
         dev_planar = None if fr.yuv is None else torch.empty(shape, dtype=torch.uint8, device=dev)
-        for b, i0 in enumerate(range(0, T, B)):
-            n = min(B, T - i0)
-            want(i0 + 2 * B)
+        b = i0 = done = 0
+        while True:
+            n = fr.upto(i0 + B) - i0                  # a stream waits here for its next B frames, or for its end
+            if n <= 0:
+                break
+            want(i0 + n if fr.T is None else min(i0 + 2 * B, fr.T))      # a stream has read no further
             st = stage[b % 2]
             if events[b % 2] is not None:
                 events[b % 2].synchronize()           # the upload issued two batches ago
@@ -154,37 +158,54 @@ def clip_batches(fr, device, batch: int = DETECT_BATCH):
                 if fr.on_device(i):
                     dev_batch[i - i0].copy_(fr.device(i))
             yield i0, dev_batch[:n]
+            b, i0, done = b + 1, i0 + n, i0 + n
 
 
-def clip_pass(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, features: bool = True, pair_stats: bool = False):
-    """One `clip_batches` pass over a clip that yields the six focus measures of every frame ([T,6] float32, or None when not
-    `features`), the pair statistics of `ops.frame_pair_stats` over the whole clip ((sad int64 [T-1], hist int64 [T,64]), or None when
-    not `pair_stats`), or both, all on `device`.  A deep clip goes through `ops.frames_u16_in` and `ops.frame_pair_stats_u16` (its
-    sad is in units of the clip's own depth).  The last frame of a batch is kept as `prev` of the next, so a pair that straddles two
-    batches is counted like any other: device memory is bounded by one batch plus one frame."""
+def clip_analysis(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, features: bool = True, pair_stats: bool = False):
+    """The analysis of a clip batch by batch, for a whole clip (`clip_pass`) and for a stream (speinet_amd.video, as its frames
+    arrive): per `clip_batches` batch, yields (first frame index, the six focus measures [n,6] float32 or None when not `features`,
+    the batch's `ops.frame_pair_stats` (sad [n] int64, or [n-1] for the first batch; hist [n,64] int64) or None when not
+    `pair_stats`), on the current stream of `device`.  A deep clip goes through `ops.frames_u16_in` and `ops.frame_pair_stats_u16`
+    (its sad is in units of the clip's own depth).  The last frame of a batch is kept as `prev` of the next, so a pair that straddles
+    two batches is counted like any other: device memory is bounded by one batch plus one frame.  The consumer sets grad mode and the
+    current device around every `next`."""
     from . import ops
     dev = torch.device(device)
     if pair_stats and batch < 2:
         raise ValueError("pair statistics need batches of at least 2 frames (the first batch has no frame before it)")
-    feats, sads, hists, prev = [], [], [], None
+    prev = None
+    for i0, frames in clip_batches(fr, dev, batch):
+        feats = stats = None
+        if features:
+            if fr.depth == 8:
+                _, gray = ops.frames_u8_in(frames, gray=True, planes=False)
+            else:
+                _, gray = ops.frames_u16_in(frames, fr.depth, gray=True, planes=False)
+            feats = gray_focus_measures(gray, kernel_size)
+        if pair_stats:
+            if fr.depth == 8:
+                stats = ops.frame_pair_stats(frames, prev if i0 else None)
+            else:
+                stats = ops.frame_pair_stats_u16(frames, fr.depth, prev if i0 else None)
+            if fr.T is None or i0 + len(frames) < fr.T:      # a stream that has not ended may have a next batch
+                prev = torch.empty_like(frames[-1]) if prev is None else prev
+                prev.copy_(frames[-1])
+        yield i0, feats, stats
+
+
+def clip_pass(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, features: bool = True, pair_stats: bool = False):
+    """One `clip_analysis` pass over a whole clip: the six focus measures of every frame ([T,6] float32, or None when not `features`),
+    the pair statistics of `ops.frame_pair_stats` over the whole clip ((sad int64 [T-1], hist int64 [T,64]), or None when not
+    `pair_stats`), or both, all on `device`."""
+    dev = torch.device(device)
+    feats, sads, hists = [], [], []
     with torch.no_grad(), torch.cuda.device(dev):
-        for i0, frames in clip_batches(fr, dev, batch):
+        for _, f, st in clip_analysis(fr, dev, kernel_size, batch, features, pair_stats):
             if features:
-                if fr.depth == 8:
-                    _, gray = ops.frames_u8_in(frames, gray=True, planes=False)
-                else:
-                    _, gray = ops.frames_u16_in(frames, fr.depth, gray=True, planes=False)
-                feats.append(gray_focus_measures(gray, kernel_size))
+                feats.append(f)
             if pair_stats:
-                if fr.depth == 8:
-                    sad, hist = ops.frame_pair_stats(frames, prev if i0 else None)
-                else:
-                    sad, hist = ops.frame_pair_stats_u16(frames, fr.depth, prev if i0 else None)
-                sads.append(sad)
-                hists.append(hist)
-                if i0 + len(frames) < fr.T:
-                    prev = torch.empty_like(frames[-1]) if prev is None else prev
-                    prev.copy_(frames[-1])
+                sads.append(st[0])
+                hists.append(st[1])
     return (torch.cat(feats) if features else None), ((torch.cat(sads), torch.cat(hists)) if pair_stats else None)
 
 

@@ -6,10 +6,10 @@
                                 [--matrix bt601|bt709] [--range full|limited] [--fps num:den]
                                 [--chroma 420jpeg|420mpeg2|422|444|mono] [--out_chroma 420jpeg|420mpeg2|422|444|mono]
                                 [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N] [--ensemble 1|2|4|8]
-                                [--roi none|auto|Y,X,H,W] [--roi_feather N]
+                                [--roi none|auto|Y,X,H,W] [--roi_feather N] [--stream [--horizon N]]
 
-(`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; stdin is spooled to a temporary file
-on disk before the first frame is deblurred, see `main`)
+(`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; by default stdin is spooled to a temporary
+file on disk before the first frame is deblurred, with `--stream` it is deblurred as it arrives, see `main`)
 
 and the dataset harness (speinet_amd.inference) runs every clip through `deblur_clip` as well, adding its ground truth and metrics.
   * labels — given (0/1 per frame, 1 = sharp), or computed by the LD detector (speinet_amd.detector) in a first streaming pass over the
@@ -49,6 +49,13 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     statistics and the window plan see the cropped frames; the rectangle is ingested by the tile ingest with a table of one tile
     (`ops.roi_in`) and one launch pastes the model's output into the otherwise untouched frame (`ops.roi_paste`), with a hard edge
     or (`roi_feather=`, `--roi_feather`) blended with the input over a ramp inside the rectangle.  Off by default.
+  * a stream (`stream=True`, `--stream`): a clip whose length is not known (a `y4m.Y4MStream` on a pipe, an iterator of frames) is read
+    by one thread into a bounded ring of page-locked frames (`clip.StreamFrames`); the labelling pass and the scene statistics run in the
+    same batches as frames arrive (`detector.clip_analysis`), `StreamCuts` decides a cut once `find_cuts`' neighbourhood is known, and
+    `StreamPlan` hands out the entries of `window_plan` as soon as no continuation of the stream can change them, or `horizon` frames
+    ahead under a stated assumption in the two situations where the reference's selection depends on the whole rest of a scene
+    (`ClipRun.assumed` lists those frames).  The window loop behind the plan is the whole clip's, launch for launch: every frame
+    outside `assumed` is bit-identical.  Host memory is bounded by the look-ahead.  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -279,6 +286,257 @@ def window_plan(labels, n_seq: int = 3, numbers=None, cuts=None) -> list:
     return plan
 
 
+class StreamCuts:
+    """`find_cuts` as the pair statistics arrive: `feed(sad, hist)` takes the next frames' batch (`hist` [n,64]; `sad` [n], or [n-1]
+    for the first batch, which has no frame before it: what `detector.clip_analysis` yields) and returns the cuts that became
+    certain, `finish()` those that the end of the stream decides.  Pair i is decided once pair i + `window` is known (or the stream
+    has ended): the neighbourhood rule looks no further.  `cuts` holds every cut found so far; after `finish` it equals `find_cuts`
+    on the whole arrays, with the same arithmetic per pair.  `safe` is the number of leading frames whose scene is certain: no cut
+    that is still undecided lies in front of any of them."""
+
+    def __init__(self, pixels: int, *, hist_min: float = 0.25, ratio: float = 3.0, min_delta: float = 8.0, window: int = 2):
+        if pixels <= 0 or window < 0:
+            raise ValueError(f"find_cuts: pixels must be positive and window >= 0; got {pixels} and {window}")
+        self.pixels, self.hist_min, self.ratio, self.min_delta, self.window = pixels, hist_min, ratio, min_delta, int(window)
+        self.g, self.d, self.cuts = [], [], []
+        self.frames = self.decided = 0
+        self._last = None
+
+    def feed(self, sad, hist) -> list:
+        hist = np.asarray(hist, dtype=np.int64)
+        sad = np.asarray(sad, dtype=np.float64).reshape(-1)
+        rows = hist if self._last is None or hist.ndim != 2 else np.concatenate([self._last[None], hist])
+        if hist.ndim != 2 or hist.shape[0] < 1 or sad.size != rows.shape[0] - 1:
+            raise ValueError(f"StreamCuts.feed needs hist [n,bins] of n >= 1 frames and sad of one entry per new pair; got {hist.shape} "
+                             f"and {sad.shape} after {self.frames} frames")
+        self.g += (np.abs(np.diff(rows, axis=0)).sum(axis=1) / (2.0 * self.pixels)).tolist()
+        self.d += (sad / self.pixels).tolist()
+        self._last, self.frames = hist[-1].copy(), self.frames + hist.shape[0]
+        return self._decide(False)
+
+    def finish(self) -> list:
+        return self._decide(True)
+
+    def _decide(self, ended: bool) -> list:
+        g, w, new = self.g, self.window, []
+        while self.decided < len(g) and (ended or self.decided + w < len(g)):
+            i = self.decided
+            others = g[max(0, i - w):i] + g[i + 1:i + 1 + w]
+            if g[i] >= self.hist_min and self.d[i] >= self.min_delta and (not others or g[i] >= self.ratio * max(others)):
+                new.append(i + 1)
+            self.decided += 1
+        self.cuts += new
+        return new
+
+    @property
+    def safe(self) -> int:
+        return min(self.frames, self.decided + 1)
+
+
+ASSUMED_TAIL = [0] * 16 + [1, 1]     # what `StreamPlan` assumes of a scene at its horizon: it goes on, with sharp frames out of reach
+MIN_HORIZON = 24
+
+
+class StreamPlan:
+    """`window_plan` as the labels arrive: the plan of a clip whose length, later labels and later cuts are not known yet.
+
+    `feed(labels=None, sad=None, hist=None, count=None)` takes the next frames' batch and returns the plan entries that can be handed
+    out now, in frame order, each the dict that `window_plan` makes; `finish()` ends the stream and returns the rest.  `labels`: the
+    batch's 0/1 per frame, or None when the constructor was given `labels` for the whole stream (then `count`, or `hist`, says how
+    many frames the batch holds; a stream longer or shorter than the labels is a ValueError from the `feed` or the `finish` that
+    finds it out).  `cuts`: None (one scene), a strictly increasing list of first-frame-of-scene indices, or "auto": `sad` / `hist`
+    of every batch go to a `StreamCuts` (`pixels`, `cut_params`).  `labels`, `cuts` and `plan` hold what is known so far, `assumed`
+    the frames whose entry was handed out under the assumption below, `at[j]` the number of frames that had been taken in when entry
+    j was handed out.
+
+    The contract, with `horizon` (at least 24; default 48, about 2 s of video: a design parameter, larger than every bounded
+    dependence of the plan):
+      * an entry is handed out as soon as it is FINAL: its `keys`, `zero_pre` and `zero_sub` are the same for every continuation of
+        the stream, whatever labels follow, however long the scene gets, and wherever a cut that `StreamCuts` has not excluded yet
+        falls.  At the end of a scene (a cut that is certain, or the end of the stream) everything left is final: it is planned on
+        the scene's true labels;
+      * if frame j + horizon is known to lie in entry j's scene and entry j is still not final, it is handed out as entry j of
+        `window_plan` on the scene's known labels followed by `ASSUMED_TAIL` (the scene goes on and holds later sharp frames, none
+        within reach), and j is appended to `assumed`.
+    A batch is taken in 8 frames at a time, so an entry is handed out no later than the feed position j + horizon + window + 9
+    (`window`: `find_cuts`' neighbourhood, 2 by default, 0 without "auto"), which is below j + horizon + DETECT_BATCH.
+
+    Why this is enough.  With m frames of the scene known, m >= 24 and m >= j + 11 (j counted from the scene's start), every
+    continuation gives the scene at least m frames, so both far indices of `blurry_indices` (the padded clip's ends) are more than 7
+    frames from entry j's last window frame and are zeroed, and every later sharp frame, the reflected one at the padded clip's end
+    included, is at least 10 frames past that frame: out of reach of the 7-frame rule.  What is left of the future in entry j is one
+    bit: whether ANY sharp frame follows the known ones.  So the entry is computed for the continuation without one (the known
+    labels and two blurry frames) and for `ASSUMED_TAIL`, and is final iff the two agree.  They disagree in two situations only,
+    the two global quirks of the reference's selection:
+      1. after the last sharp frame so far: entry j's last window frame is fewer than 7 frames past a sharp frame s and no known
+         sharp frame follows it.  If s is the scene's last sharp frame the later reference is s; if any sharp frame follows, however
+         far, it is the zeroed far index;
+      2. exactly one sharp frame in the scene's padded labels so far: the scene is planned by the neighbour rule, and a second sharp
+         frame anywhere later switches all of it to the nearest-sharp rule.
+    `numbers=` is not supported: the gap rule is in frame indices.  `pre` and `sub` of a zeroed reference (`keys` holds `ZERO` there)
+    name the far frame of the continuation the entry was computed on, which need not be the whole clip's, nor a frame of it.
+
+    A long scene is planned on its last frames only (`keep`, at least horizon + 32, kept behind the next entry), with the sharp
+    frames before them stood in for by none, one or two sharp frames out of reach: entry j depends on what lies more than 7 frames
+    behind it only through their count (none, one, more)."""
+
+    STEP = 8
+
+    def __init__(self, horizon: int = 48, cuts=None, labels=None, pixels: Optional[int] = None, cut_params: Optional[dict] = None,
+                 n_seq: int = 3, keep: Optional[int] = None):
+        if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon < MIN_HORIZON:
+            raise ValueError(f"horizon must be a whole number >= {MIN_HORIZON}, got {horizon!r}")
+        if n_seq != 3:
+            raise ValueError("StreamPlan plans 3-frame windows")
+        self.horizon, self.n_seq = int(horizon), n_seq
+        self.keep = max(self.horizon + 32, 64) if keep is None else int(keep)
+        if self.keep < self.horizon + 32:
+            raise ValueError(f"keep must be at least horizon + 32 = {self.horizon + 32}, got {keep!r}")
+        self._given = None
+        if labels is not None:
+            lab = np.asarray(labels).reshape(-1)
+            if not np.isin(lab, (0, 1)).all():
+                raise ValueError("labels must be 0 (blurry) or 1 (sharp) per frame")
+            self._given = lab.astype(np.int64)
+        self._auto = None
+        self._cut_list = None
+        if isinstance(cuts, str):
+            if cuts != "auto":
+                raise ValueError(f"cuts must be None, \"auto\" or a sequence of frame indices, got {cuts!r}")
+            if pixels is None:
+                raise ValueError("cuts=\"auto\" needs pixels= (H * W)")
+            self._auto = StreamCuts(pixels, **(cut_params or {}))
+        elif cuts is not None:
+            try:                         # the clip's length is not known: every bound but the upper one is checked here
+                top = max((int(c) for c in cuts), default=0)
+            except (TypeError, ValueError):
+                top = 0
+            self._cut_list = cuts_of(cuts, top + 1)
+        self.labels, self.cuts, self.plan, self.assumed, self.at = [], [], [], [], []
+        self.fed = 0                     # frames taken in
+        self.start = 0                   # first frame of the scene being planned
+        self._c0, self._before = 0, 0    # the scene is planned from frame _c0 on; sharp frames (padded) of the scene before it
+        self.ended = False
+
+    # ---- feeding ----
+    def feed(self, labels=None, sad=None, hist=None, count: Optional[int] = None) -> list:
+        if self.ended:
+            raise ValueError("the stream has ended")
+        if self._given is not None:
+            n = int(count) if count is not None else (len(hist) if hist is not None else len(labels))
+            if self.fed + n > self._given.size:
+                raise ValueError(f"labels has {self._given.size} entries and the stream is longer: frame {self._given.size} has arrived")
+            lab = self._given[self.fed:self.fed + n]
+        else:
+            lab = np.asarray(labels).reshape(-1)
+            if not np.isin(lab, (0, 1)).all():
+                raise ValueError("labels must be 0 (blurry) or 1 (sharp) per frame")
+        n = len(lab)
+        if self._auto is not None:
+            if hist is None or sad is None or len(hist) != n:
+                raise ValueError(f"cuts=\"auto\" needs the pair statistics of the batch's {n} frames")
+            sad, hist = np.asarray(sad).reshape(-1), np.asarray(hist)
+        out, lead = [], 1 if self.fed == 0 else 0        # the stream's first batch has no pair for its first frame
+        for a in range(0, n, self.STEP):
+            b = min(n, a + self.STEP)
+            self.labels += [int(v) for v in lab[a:b]]
+            self.fed += b - a
+            if self._auto is not None:
+                self._auto.feed(sad[max(a - lead, 0):b - lead], hist[a:b])
+                self.cuts = list(self._auto.cuts)
+            out += self._advance()
+        return out
+
+    def finish(self) -> list:
+        if self.ended:
+            return []
+        if self._given is not None and self.fed != self._given.size:
+            raise ValueError(f"labels has {self._given.size} entries and the stream is shorter: it ended after {self.fed} frames")
+        if self._cut_list and self._cut_list[-1] > self.fed - 1:
+            cuts_of(self._cut_list, self.fed)
+        self.ended = True
+        if self._auto is not None:
+            self._auto.finish()
+            self.cuts = list(self._auto.cuts)
+        return self._advance()
+
+    # ---- planning ----
+    def _safe(self) -> int:
+        return self.fed if self._auto is None or self.ended else self._auto.safe
+
+    def _scene_end(self) -> Optional[int]:
+        """The end of the scene being planned, once it is certain; None while it is not."""
+        if self._cut_list is not None:
+            nxt = next((c for c in self._cut_list if c > self.start), None)
+            if nxt is not None and nxt <= self.fed:
+                if nxt not in self.cuts:
+                    self.cuts.append(nxt)
+                return nxt
+        elif self._auto is not None:
+            nxt = next((c for c in self.cuts if c > self.start), None)
+            if nxt is not None:
+                return nxt
+        return self.fed if self.ended else None
+
+    def _planned(self, stop: int, tail: list):
+        """`_scene_plan` of the scene's frames [_c0, stop) and `tail`, behind the stand-in of what was dropped; (plan, offset): entry
+        j of the clip is plan[j - offset], its frame indices shifted by offset."""
+        head = [] if self._c0 == self.start else [0, 0, 0] + [1] * min(self._before, 2) + [0] * 16
+        return _scene_plan(head + self.labels[self._c0:stop] + tail, self.n_seq, None), self._c0 - len(head)
+
+    @staticmethod
+    def _shift(p: dict, j: int, off: int) -> dict:
+        q = dict(p, index=j, window=[f + off for f in p["window"]], pre=p["pre"] + off, sub=p["sub"] + off)
+        q["keys"] = [k if k is ZERO else k + off for k in p["keys"]]
+        return q
+
+    def _hand(self, q: dict, assumed: bool = False) -> dict:
+        if assumed:
+            self.assumed.append(q["index"])
+        self.plan.append(q)
+        self.at.append(self.fed)
+        return q
+
+    def _advance(self) -> list:
+        out = []
+        while True:
+            nxt, end = len(self.plan), self._scene_end()
+            if end is not None:          # a whole scene (what is left of it): its true labels
+                if end - self.start == 1:
+                    i = self.start           # as `window_plan`: the first entry of the two-frame clip [i, i]
+                    p = _scene_plan([self.labels[i]] * 2, self.n_seq, None)[0]
+                    q = dict(p, index=i, window=[i] * len(p["window"]), pre=i, sub=i, keys=[k if k is ZERO else i for k in p["keys"]])
+                    out.append(self._hand(q))
+                elif nxt < end:
+                    plan, off = self._planned(end, [])
+                    out += [self._hand(self._shift(plan[j - off], j, off)) for j in range(nxt, end)]
+                if end >= self.fed and self.ended:
+                    return out
+                self.start = self._c0 = end
+                self._before = 0
+                continue
+            m = self._safe() - self.start                                  # frames known to lie in the scene
+            if self._cut_list is not None:
+                m = min(m, next((c for c in self._cut_list if c > self.start), self.fed) - self.start)
+            if m < MIN_HORIZON or nxt - self.start + 11 > m:
+                return out
+            if nxt - self._c0 > 2 * self.keep:                             # plan on the scene's last frames only
+                c0 = nxt - self.keep
+                if self._c0 == self.start:
+                    self._before += self.labels[self.start + 1]            # the padded clip's first frame is frame 1 again
+                self._before += sum(self.labels[self._c0:c0])
+                self._c0 = c0
+            stop = self.start + m
+            (blurry, off), (sharp, _) = self._planned(stop, [0, 0]), self._planned(stop, ASSUMED_TAIL)
+            for j in range(nxt, stop - 10):
+                a, b = blurry[j - off], sharp[j - off]
+                final = (a["keys"], a["zero_pre"], a["zero_sub"]) == (b["keys"], b["zero_pre"], b["zero_sub"])
+                if not final and not j + self.horizon < stop:
+                    break
+                out.append(self._hand(self._shift(b, j, off), assumed=not final))
+            return out
+
+
 def _lanes(model, device, n: int) -> list:
     """The launch streams of the windows, one set per model and device: `forward_window` captures one graph per launch stream, so
     fresh streams per clip would capture fresh graphs per clip."""
@@ -295,11 +553,13 @@ class ClipRun:
     deblurred tile by tile, None for one that is deblurred whole (a plan of one tile included).  `ensemble` is the number of members of
     the geometric self-ensemble every window runs as (1: none).  `roi` is the region of interest in use, (y0, x0, h, w), or None for a
     clip that is deblurred whole (found on first access, by `active_area` + `find_bars`, when the caller asked for "auto"); labels,
-    cuts and the plan are then those of the clip of cropped frames."""
+    cuts and the plan are then those of the clip of cropped frames.  In stream mode (`horizon` set: the clip is a `clip.StreamFrames`)
+    `labels`, `cuts` and `plan` hold what is known so far and are complete after the last frame, and `assumed` lists the frames whose
+    plan entry `StreamPlan` handed out under its assumption (empty in whole-clip mode)."""
 
     def __init__(self, model, frames: Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
                  out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None, ensemble: int = 1, roi=None,
-                 roi_feather: int = 0, bar_params: Optional[dict] = None):
+                 roi_feather: int = 0, bar_params: Optional[dict] = None, horizon: Optional[int] = None):
         self.model, self.frames = model, frames
         self._roi = roi                  # None, a rectangle, or "auto" while the scan has not run
         self.roi_feather = roi_feather
@@ -324,6 +584,16 @@ class ClipRun:
         self.numbers = numbers
         self._plan = None
         self._it = None
+        self.assumed = []            # stream mode: the frames whose plan entry was handed out under `StreamPlan`'s assumption
+        self.horizon = horizon       # None: the whole clip is known; a number: stream mode, with that look-ahead
+        self._stream = None
+        if horizon is not None:
+            view = self._view()
+            self._stream = StreamPlan(horizon, cuts="auto" if cuts is None else (cuts or None), labels=labels, pixels=view.H * view.W,
+                                      cut_params=self.cut_params)
+            self.assumed = self._stream.assumed
+            # what is held at once: the look-ahead of the plan, the analysis batch in front of it and the windows behind (`_run`)
+            frames.reserve(self._stream.horizon + 2 * DETECT_BATCH + PREFETCH + 4 + (self.cut_params.get("window", 2) - 2 if cuts is None else 0))
 
     @property
     def roi(self):
@@ -343,18 +613,24 @@ class ClipRun:
 
     @property
     def labels(self) -> np.ndarray:
+        if self._stream is not None:
+            return np.asarray(self._stream.labels, dtype=np.int64)
         if self._labels is None:
             self._analyse()
         return self._labels
 
     @property
     def cuts(self) -> list:
+        if self._stream is not None:
+            return self._stream.cuts
         if self._cuts is None:
             self._analyse()
         return self._cuts
 
     @property
     def plan(self) -> list:
+        if self._stream is not None:
+            return self._stream.plan
         if self._plan is None:
             self._plan = window_plan(self.labels, numbers=self.numbers, cuts=self.cuts)
         return self._plan
@@ -382,7 +658,7 @@ class ClipRun:
 
     def _run(self):
         m, dev, fr = self.model, self.device, self.frames
-        T, H, W = fr.T, fr.H, fr.W
+        H, W = fr.H, fr.W
         tp = self.tiles
         nt = 1 if tp is None else tp.n                 # tiles per frame: each is a window of its own, all of one shape
         Hp, Wp = (padded_size(H), padded_size(W)) if tp is None else tp.padded
@@ -391,7 +667,45 @@ class ClipRun:
         if roi is not None:
             Hp, Wp = padded_size(roi[2]), padded_size(roi[3])
         centres = {}                     # per window in flight: its centre input frame, whole, for the paste (and a recompute's)
-        plan = self.plan
+        sp = self._stream
+        plan = self.plan                 # the whole clip's; a stream's grows as `pump` analyses it
+        if sp is None:
+            def has(k):
+                return k < len(plan)
+        else:
+            p, view = self.detector, self._view()
+            analysis = None
+            if self._labels is None or self._cuts is None:
+                analysis = detector.clip_analysis(view, dev, p.kernel_size, DETECT_BATCH, features=self._labels is None,
+                                                  pair_stats=self._cuts is None)
+
+            def pump():
+                """One DETECT_BATCH of the stream into the plan, as soon as its frames have arrived: the batch `_analyse` would run."""
+                if analysis is not None:
+                    item = next(analysis, None)
+                    n = 0 if item is None else len(item[1] if item[1] is not None else item[2][1])
+                else:
+                    n = view.upto(sp.fed + DETECT_BATCH) - sp.fed
+                if n <= 0:
+                    if sp.fed < 2:
+                        raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {sp.fed}")
+                    sp.finish()
+                elif analysis is None:
+                    sp.feed(count=n)
+                else:
+                    _, feats, stats = item
+                    sad, hist = (None, None) if stats is None else (_sad_8bit(stats[0].cpu().numpy(), view.depth), stats[1].cpu().numpy())
+                    sp.feed(None if feats is None else detector.predict(feats, p), sad, hist, count=n)
+
+            def has(k):
+                """Whether the clip has a frame k: analyses the stream until entry k is planned (or the stream has ended), and on
+                until the plan is PREFETCH entries ahead while that takes no waiting.  Frames that neither a later window (its
+                references lie at most 7 behind its last frame) nor the analysis will ask for are given up."""
+                fr.release(max(0, min(sp.fed, k - 8)))
+                while not sp.ended and (len(plan) <= k or (len(plan) <= k + PREFETCH and fr.ready(sp.fed + DETECT_BATCH) == sp.fed + DETECT_BATCH)):
+                    with torch.no_grad(), torch.cuda.device(dev), torch.cuda.stream(home):
+                        pump()
+                return k < len(plan)
         n = m.n_sequence
         pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
         # frames (uint8, or uint16 for a deep clip), decoded and uploaded once each; a y4m clip's as planar bytes, made RGB on the device
@@ -527,13 +841,17 @@ class ClipRun:
 
         # grad mode and the current device are set around each step, not across a `yield`: they are the caller's while it holds a frame
         try:
+            has(0)
             with torch.no_grad(), torch.cuda.device(dev), torch.cuda.stream(home):
                 nxt = prepare(0)
-            for k in range(T):
+            k = -1
+            while nxt is not None:
+                k += 1
+                more = has(k + 1)
                 with torch.no_grad(), torch.cuda.device(dev):
                     with torch.cuda.stream(home):
                         x = nxt
-                        nxt = prepare(k + 1) if k + 1 < T else None
+                        nxt = prepare(k + 1) if more else None
                         enqueue(k, x, nxt)
                     # frames are handed out LAG windows behind: by then the limiter has waited for that window, so its non-finite flag
                     # is on the host without a stall, and the windows after it keep running
@@ -546,12 +864,15 @@ class ClipRun:
                 yield got
         finally:
             pool.shutdown(wait=False, cancel_futures=True)
+            if sp is not None:
+                fr.close()
 
 
 def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
                 detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None,
                 depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20, feather: int = 0,
-                ensemble: int = 1, roi=None, roi_feather: int = 0, bar_params: Optional[dict] = None) -> ClipRun:
+                ensemble: int = 1, roi=None, roi_feather: int = 0, bar_params: Optional[dict] = None, stream=False,
+                horizon: int = 48) -> ClipRun:
     """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
     or uint16 frames when `out_depth` is 10 or 12.
 
@@ -624,6 +945,15 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     bar_params — optional keyword arguments of `find_bars` for "auto" (level, min_bar: untuned defaults), and `frames`: the number of
              frames `active_area` scans (default 64, None: every frame).
 
+    stream — False (the default): the clip's length is known and it is planned whole.  True: `frames` is a `y4m.Y4MStream` (or the path
+             of a `.y4m` file, then read in order) or an iterator of host frames, uint8 [H,W,3] or uint16 with `depth`; its length is
+             not known, at least 2 frames must come.  Frames are handed out while the stream is still being read, after a bounded
+             look-ahead; `labels` (for the whole stream; a stream longer or shorter is a ValueError when that is known), `cuts`
+             (a list, "auto" or None), a fixed `roi`, `tiles`, `feather`, `ensemble`, `out_depth`, `yuv` and `depth` work as above.
+             Not with `out`, `numbers` or `roi="auto"`, and not on an indexable clip (its whole-clip plan is exact) unless
+             `stream="force"`.  `ClipRun.assumed` lists the frames that are not the whole-clip run's, see `StreamPlan`.
+    horizon — with `stream`: the look-ahead in frames, at least 24, after which a plan entry is committed (`StreamPlan`).
+
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
@@ -642,9 +972,32 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     if bar_params is not None and set(bar_params) - set(BAR_PARAMS):
         raise ValueError(f"bar_params holds {sorted(set(bar_params) - set(BAR_PARAMS))}: find_bars takes level and min_bar, and frames is "
                          "the number of frames that active_area scans")
+    if stream not in (False, True, "force"):
+        raise ValueError(f"stream must be False, True or \"force\", got {stream!r}")
     if isinstance(frames, (str, os.PathLike)) and os.fspath(frames).lower().endswith(".y4m"):
-        frames = y4m.Y4MReader(frames, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
+        frames = (y4m.Y4MStream if stream else y4m.Y4MReader)(frames, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
+    unbounded = isinstance(frames, y4m.Y4MStream) or hasattr(frames, "__next__")
+    if unbounded and not stream:
+        raise ValueError("frames is a stream (a Y4MStream, or an iterator of frames): its length is not known, pass stream=True")
+    if stream and not unbounded:
+        if stream != "force":
+            raise ValueError("stream=True on a clip whose length is known: the whole-clip plan is exact and costs no look-ahead; pass a "
+                             "y4m.Y4MStream or an iterator of frames (stream=\"force\" streams an array or a list of host frames)")
+        if isinstance(frames, y4m.Y4MReader) or isinstance(frames, (str, bytes)) or not hasattr(frames, "__iter__"):
+            raise ValueError("stream=\"force\" takes an array or a list of host frames; open a y4m clip as a y4m.Y4MStream")
+        frames = iter(frames)
+    if stream:                                             # what needs the whole clip, or its length
+        if out is not None:
+            raise ValueError("out= with stream=True: the tensor holds every frame, and a stream's length is not known")
+        if numbers is not None:
+            raise ValueError("numbers= with stream=True: the incremental plan measures the reference gap in frame indices")
+        if isinstance(roi, str) and roi == "auto":
+            raise ValueError("roi=\"auto\" with stream=True: the active area is found from frames sampled over the whole clip; give "
+                             "the rectangle (y0, x0, h, w)")
     fr = frames_of(frames, crop, yuv, depth)
+    if stream:
+        return _stream_run(model, fr, labels, detector, cuts, cut_params, out_depth, tiles, shave, feather, ensemble, roi, roi_feather,
+                           horizon)
     if roi is not None and not isinstance(roi, str):
         roi = roi_of(tuple(roi) if isinstance(roi, list) else roi, fr.H, fr.W)
         h, w = (fr.H, fr.W) if roi is None else roi[2:]
@@ -677,6 +1030,31 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     if tp is not None and tp.n == 1:
         tp = None                        # one tile that spans the frame: the untiled path
     return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp, ensemble, roi, int(roi_feather), bar_params)
+
+
+def _stream_run(model, fr, labels, detector, cuts, cut_params, out_depth, tiles, shave, feather, ensemble, roi, roi_feather, horizon) -> ClipRun:
+    """`deblur_clip`'s checks for a clip of unknown length, and its `ClipRun`: whatever is measured against the length is checked by
+    the incremental plan as the stream goes (`StreamPlan`)."""
+    if roi is not None:
+        roi = roi_of(tuple(roi) if isinstance(roi, list) else roi, fr.H, fr.W)
+        h, w = (fr.H, fr.W) if roi is None else roi[2:]
+        check_roi_feather(roi_feather, h, w, lambda bound: f"is outside 0..{bound}: at most {ROI_FEATHER_MAX} and half of the {w}x{h} rectangle")
+    if out_depth is not None and (isinstance(out_depth, bool) or out_depth not in y4m.DEPTHS):
+        raise ValueError(f"out_depth must be None, 8, 10 or 12, got {out_depth!r}")
+    if isinstance(cuts, str):
+        if cuts != "auto":
+            raise ValueError(f"cuts must be None, \"auto\" or a sequence of frame indices, got {cuts!r}")
+        cuts = None                      # `ClipRun`: found as the run goes
+    elif cuts is None:
+        cuts = []
+    if cut_params is not None and set(cut_params) - {"hist_min", "ratio", "min_delta", "window"}:
+        raise ValueError(f"cut_params holds {sorted(set(cut_params) - {'hist_min', 'ratio', 'min_delta', 'window'})}: "
+                         "find_cuts takes hist_min, ratio, min_delta and window")
+    tp = None if tiles is None else tiling.tile_plan(fr.H, fr.W, tuple(tiles) if isinstance(tiles, list) else tiles, shave, feather)
+    if tp is not None and tp.n == 1:
+        tp = None
+    return ClipRun(model, fr, labels, None, None, detector, cuts, cut_params, None if out_depth is None else int(out_depth), tp, ensemble,
+                   roi, int(roi_feather), None, horizon=horizon)
 
 
 def _inputs(spec: str) -> list:
@@ -727,6 +1105,16 @@ def _fps(text: str):
     return int(num), int(den or 1)
 
 
+class _Numbered:
+    """The frame names of a clip whose length is not known: 000000, 000001, ..."""
+
+    def __init__(self, ext: str):
+        self.ext = ext
+
+    def __getitem__(self, i: int) -> str:
+        return f"{i:06d}{self.ext}"
+
+
 def _spool(stream, spool_dir: Optional[str]):
     """Copy a pipe to an unnamed temporary file (in `spool_dir`, default: the system's) and return that file."""
     import shutil
@@ -745,9 +1133,11 @@ def main(argv=None) -> None:
         ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe - | python -m speinet_amd.video --input - --output - --model_path ... \
             | ffmpeg -f yuv4mpegpipe -i - out.mp4
 
-    A pipe on stdin is SPOOLED TO DISK first, to an unnamed temporary file (`--spool_dir`), all of it before the first frame is
-    deblurred: the window plan needs the clip's length and its labels before the first window.  The y4m output is written by one
-    thread, in frame order."""
+    By default a pipe on stdin is SPOOLED TO DISK first, to an unnamed temporary file (`--spool_dir`), all of it before the first
+    frame is deblurred: the whole-clip window plan needs the clip's length and its labels before the first window.  With `--stream
+    [--horizon N]` stdin (or a `.y4m` file) is read through `y4m.Y4MStream` as it arrives, with no spool: the first frames leave
+    while the input is still coming, every output frame is flushed, cuts are reported as they are found, and the last log line
+    says how many frames were planned under `StreamPlan`'s assumption.  The y4m output is written by one thread, in frame order."""
     p = argparse.ArgumentParser(description="Deblur a clip of any size (at least 20x20) on an MI355X: image files or a YUV4MPEG2 stream in, "
                                 "one PNG per frame or a YUV4MPEG2 stream out")
     p.add_argument("--input", required=True, help="a directory of frames, or a glob (PNG / JPG / BMP); frames in file-name order; or a "
@@ -792,6 +1182,12 @@ def main(argv=None) -> None:
                    "only that rectangle is deblurred, the rest of every frame is the input's")
     p.add_argument("--roi_feather", type=int, default=0, help="with --roi: blend the deblurred rectangle with the input over the N pixels "
                    "inside every side of it that is not a side of the frame (0..min(200, H/2, W/2); default 0: a hard edge)")
+    p.add_argument("--stream", action="store_true", help="y4m input only: deblur the stream as it arrives, with a bounded look-ahead and "
+                   "no spool ('--input -' reads stdin as a pipe; a .y4m file is read in order); the first frames leave before the "
+                   "input has ended.  The window plan is exact except where it depends on the rest of a scene, however long: there it "
+                   "is committed --horizon frames ahead under an assumption (see StreamPlan) and the frame is counted as assumed")
+    p.add_argument("--horizon", type=int, default=48, help=f"with --stream: frames of look-ahead after which a plan entry is committed "
+                   f"(default 48, at least {MIN_HORIZON})")
     p.add_argument("--spool_dir", default=None, help="directory of the temporary file that '--input -' is copied to (default: the system's)")
     a = p.parse_args(argv)
     try:
@@ -825,16 +1221,24 @@ def main(argv=None) -> None:
         print(text, file=log, flush=True)
 
     reader = None
-    if a.input == "-":
+    if a.stream:
+        if a.horizon < MIN_HORIZON:
+            raise SystemExit(f"--horizon {a.horizon}: at least {MIN_HORIZON}")
+        if a.roi == "auto":
+            raise SystemExit("--roi auto with --stream: the active area is found from the whole clip; give Y,X,H,W")
+        if a.input != "-" and not (a.input.lower().endswith(".y4m") and os.path.isfile(a.input)):
+            raise SystemExit(f"--stream: --input {a.input} is not '-' or a .y4m file (image files have a known length: nothing to stream)")
+        reader = y4m.Y4MStream(sys.stdin.buffer if a.input == "-" else a.input, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
+    elif a.input == "-":
         reader = y4m.Y4MReader(_spool(sys.stdin.buffer, a.spool_dir), depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
     elif a.input.lower().endswith(".y4m") and os.path.isfile(a.input):
         reader = y4m.Y4MReader(a.input, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
     if reader is not None:
         if reader.depth > 8 and reader.layout in (y4m.CENTER, y4m.LEFT) and a.chroma in ("420jpeg", "420mpeg2"):
             reader.layout = y4m.layout_of(a.chroma)
-        if len(reader) < 2:
+        if not a.stream and len(reader) < 2:
             raise SystemExit(f"--input {a.input}: {len(reader)} frame(s) found, a clip needs at least 2")
-        files, stems = reader, [f"{i:06d}" for i in range(len(reader))]
+        files, stems = reader, None if a.stream else [f"{i:06d}" for i in range(len(reader))]
     else:
         files = _inputs(a.input)
         if len(files) < 2:
@@ -842,7 +1246,7 @@ def main(argv=None) -> None:
         stems = [os.path.splitext(os.path.basename(f))[0] for f in files]
         if len(set(stems)) != len(stems):
             raise SystemExit(f"--input {a.input}: two frames share a file name stem (the outputs are <stem>.png)")
-    names = [s if to_y4m else s + ".png" for s in stems]
+    names = _Numbered("" if to_y4m else ".png") if stems is None else [s if to_y4m else s + ".png" for s in stems]
     labels = np.load(a.labels) if a.labels else None
     net = load_model(a.model_path, a.device, a.precision, a.graph)
     cuts = {"none": None, "auto": "auto"}[a.cuts] if a.cuts in ("none", "auto") else read_cuts(a.cuts)
@@ -854,7 +1258,7 @@ def main(argv=None) -> None:
         out_depth = 8
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
                       yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather, ensemble=a.ensemble,
-                      roi=roi, roi_feather=a.roi_feather)
+                      roi=roi, roi_feather=a.roi_feather, stream=a.stream, horizon=a.horizon)
     out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
@@ -875,22 +1279,35 @@ def main(argv=None) -> None:
         say(f"# y4m input C{reader.chroma}" + (f", output C{writer.chroma}" if writer is not None and writer.chroma != reader.chroma else ""))
     if run.roi is not None:
         say("# roi " + ",".join(str(v) for v in run.roi))
-    for c in run.cuts:
-        say(f"# cut before {names[c]}")
+    said = 0                                               # a stream's cuts are reported as they are found
+    if not a.stream:
+        for c in run.cuts:
+            say(f"# cut before {names[c]}")
     if run.tiles is not None:
         say(f"# {run.tiles.rows}x{run.tiles.cols} tiles of {run.tiles.tw}x{run.tiles.th}, shave {run.tiles.shave}"
             + (f", feather {run.tiles.feather}" if run.tiles.feather else ""))
     if run.ensemble > 1:
         say(f"# ensemble {run.ensemble}: members 0..{run.ensemble - 1}, {run.ensemble} forward passes per frame")
     t0 = t_prev = time.time()
+    done = 0
+
+    def write(buf) -> None:
+        writer.write(buf.numpy())
+        if a.stream and to_stdout:                         # a live pipe: the frame leaves now, not when the buffer is full
+            sys.stdout.buffer.flush()
     # PNGs are encoded on four threads; a y4m stream is written by ONE, so its frames land in the order they were queued
     with ThreadPoolExecutor(max_workers=1 if to_y4m else 4, thread_name_prefix="speinet-y4m" if to_y4m else "speinet-png") as writers:
         ring = HostRing(writers)
         for i, frame in run:
+            done = i + 1
+            if a.stream:
+                for c in run.cuts[said:]:
+                    say(f"# cut before {names[c]}")
+                said = len(run.cuts)
             if to_y4m:
                 planar = (ops.rgb_u8_to_yuv(frame, layout, matrix, rng) if out_depth == 8 else
                           ops.rgb_u16_to_yuv(frame, layout, matrix, rng, out_depth))
-                ring.land(lambda buf: writer.write(buf.numpy()), planar)
+                ring.land(write, planar)
             else:
                 ring.land(lambda buf, path=os.path.join(a.output, names[i]): imwrite(path, buf.numpy()), frame)
             now = time.time()
@@ -903,8 +1320,9 @@ def main(argv=None) -> None:
     if writer is not None:
         writer.close()
     dt = time.time() - t0
-    say(f"# {len(names)} frames {W}x{H} in {dt:.2f}s: {len(names) / dt:.2f} frames/s ({a.precision}"
-        + (f", ensemble {run.ensemble}" if run.ensemble > 1 else "") + ")")
+    say(f"# {done} frames {W}x{H} in {dt:.2f}s: {done / dt:.2f} frames/s ({a.precision}"
+        + (f", ensemble {run.ensemble}" if run.ensemble > 1 else "")
+        + (f", streamed with horizon {a.horizon}: {len(run.assumed)} frames assumed" if a.stream else "") + ")")
 
 
 if __name__ == "__main__":

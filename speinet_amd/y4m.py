@@ -6,7 +6,8 @@ Supported: progressive 8-bit 4:2:0 (`C420jpeg`, bare `C420`, `C420mpeg2`) and 4:
 `depths=(8, 10, 12)`, 10- and 12-bit 4:2:0 and 4:4:4 (`C420p10`, `C420p12`, `C444p10`, `C444p12`: little-endian 16-bit samples, which
 `ops.yuv_to_rgb_u16` / `ops.rgb_u16_to_yuv` convert).  For a reader opened with `layouts=LAYOUTS`, also 4:2:2 (`C422`, `C422p10`,
 `C422p12`: chroma planes [H][ceil(W/2)], co-sited with the even column) and mono (`Cmono`, `Cmono10`, `Cmono12`: the Y plane alone) at
-the depths it was given; the same four `ops` functions convert them.  Not supported: interlaced streams, other depths (9, 14, 16
+the depths it was given; the same four `ops` functions convert them.  `Y4MReader` indexes a file; `Y4MStream` reads a pipe in order, with the same header
+parsing and error texts.  Not supported: interlaced streams, other depths (9, 14, 16
 bits), 4:1:1, 4:4:0, `C420paldv`."""
 from __future__ import annotations
 
@@ -92,54 +93,21 @@ def _ratio(tag: str, text: str):
         raise ValueError(f"y4m header: tag {tag}{text} is not <int>:<int>") from None
 
 
-class Y4MReader:
-    """A y4m file as an indexable sequence of frames: `len(r)`, and `r.raw(i)` = the `frame_bytes` planar bytes of frame i as a uint8
-    numpy array, read at its offset with `readinto` (callable from several threads).  `path_or_file`: a path, or a seekable binary
-    file object (a pipe has no length: the command line spools it to a file first).
+class _Header:
+    """What `Y4MReader` and `Y4MStream` share: the header line's tags, their validation and the error texts."""
 
-    Only the header line and the first `FRAME` line are scanned.  `FRAME` lines may carry parameters, but every one must be as long
-    as the first: T is then the payload size divided by the record size, and a later line that differs raises ValueError when its
-    frame is read.  A file that ends inside a frame raises ValueError here.
-
-    `depths`: the sample depths the caller can take.  The default, (8,), refuses deep streams, as every caller that indexes the
-    payload as bytes needs; with (8, 10, 12) the reader also accepts `C420p10`, `C420p12`, `C444p10` and `C444p12`.  `raw(i)` still
-    returns the payload's bytes as uint8 (`frame_bytes` of them, two per sample, little-endian).  A deep 4:2:0 tag carries no
-    siting: `layout` is then LEFT, the MPEG-2 siting of the codecs such streams come from; it is a plain attribute that the caller
-    may set to CENTER before the clip is used.
-
-    `layouts`: the chroma layouts the caller can take, an opt-in like `depths`.  The default, (CENTER, LEFT, P444), refuses `C422*`
-    and `Cmono*`, whatever `depths` says; with `layouts=LAYOUTS` the reader also accepts `C422` and `Cmono` and, at the depths it
-    was given, `C422p10`, `C422p12`, `Cmono10` and `Cmono12` (`layout` is then P422 or MONO).
-
-    Attributes: `width`, `height`, `fps` and `aspect` ((num, den); 25:1 and None when absent), `layout` (CENTER / LEFT / P444; P422 /
-    MONO for a reader that takes them),
-    `depth` (8, 10 or 12), `chroma` (the C tag's text), `range` (from XCOLORRANGE=FULL|LIMITED; LIMITED when absent), `matrix`, `frame_bytes`.  y4m carries
-    no matrix tag: `matrix` is BT709 when height >= 720 and BT601 otherwise, which is ffmpeg's usual guess for untagged video;
-    assign `matrix` / `range`, or pass `yuv=dict(matrix=..., range=...)` to `deblur_clip`, to override.
-
-    Interlaced streams, depths outside `depths` (9, 14 and 16 bits always), layouts outside `layouts` (C422 and Cmono at any depth
-    by default), C420paldv, C411 and C440 are rejected with a ValueError that names the tag."""
-
-    def __init__(self, path_or_file, depths=(8,), layouts=(CENTER, LEFT, P444)):
+    def _open(self, path_or_file, depths, layouts, mode: str = "rb") -> None:
         self.depths = tuple(depth_of(d) for d in depths)
         self.layouts = tuple(layout_of(v) for v in layouts)
         self._own = isinstance(path_or_file, (str, bytes, os.PathLike))
-        self._f = open(path_or_file, "rb") if self._own else path_or_file
+        self._f = open(path_or_file, mode) if self._own else path_or_file
         self.name = os.fspath(path_or_file) if self._own else getattr(path_or_file, "name", "<file>")
-        self._lock = threading.Lock()
-        try:
-            self._parse()
-        except Exception:
-            self.close()
-            raise
 
     def _fail(self, text: str):
         raise ValueError(f"{self.name}: {text}; {HINT}")
 
-    def _parse(self) -> None:
-        f = self._f
-        f.seek(0)
-        head = f.read(MAX_HEADER)
+    def _header(self, head: bytes) -> int:
+        """Parse the header line at the start of `head` into the attributes; returns the offset of its newline."""
         end = head.find(b"\n")
         if not head.startswith(MAGIC) or end < 0:
             raise ValueError(f"{self.name}: not a YUV4MPEG2 stream (no '{MAGIC.decode()} ...' header line)")
@@ -196,6 +164,68 @@ class Y4MReader:
             self._fail(f"tag C{c}: {why}")
         self.matrix = BT709 if self.height >= 720 else BT601
         self.frame_bytes = frame_bytes(self.height, self.width, self.layout, self.depth)
+        return end
+
+    @staticmethod
+    def _is_frame_line(line: bytes) -> bool:
+        return line[:5] == b"FRAME" and line[5:6] in (b" ", b"\n") and line.find(b"\n") == len(line) - 1
+
+    def _bad_line(self, i: int, n: int, first: bytes):
+        raise ValueError(f"{self.name}: frame {i} does not start with a FRAME line of {n} bytes like the first frame's "
+                         f"({bytes(first)!r}): FRAME lines of different lengths are not supported")
+
+    def close(self) -> None:
+        if self._own:
+            self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+class Y4MReader(_Header):
+    """A y4m file as an indexable sequence of frames: `len(r)`, and `r.raw(i)` = the `frame_bytes` planar bytes of frame i as a uint8
+    numpy array, read at its offset with `readinto` (callable from several threads).  `path_or_file`: a path, or a seekable binary
+    file object (a pipe has no length: the command line spools it to a file first).
+
+    Only the header line and the first `FRAME` line are scanned.  `FRAME` lines may carry parameters, but every one must be as long
+    as the first: T is then the payload size divided by the record size, and a later line that differs raises ValueError when its
+    frame is read.  A file that ends inside a frame raises ValueError here.
+
+    `depths`: the sample depths the caller can take.  The default, (8,), refuses deep streams, as every caller that indexes the
+    payload as bytes needs; with (8, 10, 12) the reader also accepts `C420p10`, `C420p12`, `C444p10` and `C444p12`.  `raw(i)` still
+    returns the payload's bytes as uint8 (`frame_bytes` of them, two per sample, little-endian).  A deep 4:2:0 tag carries no
+    siting: `layout` is then LEFT, the MPEG-2 siting of the codecs such streams come from; it is a plain attribute that the caller
+    may set to CENTER before the clip is used.
+
+    `layouts`: the chroma layouts the caller can take, an opt-in like `depths`.  The default, (CENTER, LEFT, P444), refuses `C422*`
+    and `Cmono*`, whatever `depths` says; with `layouts=LAYOUTS` the reader also accepts `C422` and `Cmono` and, at the depths it
+    was given, `C422p10`, `C422p12`, `Cmono10` and `Cmono12` (`layout` is then P422 or MONO).
+
+    Attributes: `width`, `height`, `fps` and `aspect` ((num, den); 25:1 and None when absent), `layout` (CENTER / LEFT / P444; P422 /
+    MONO for a reader that takes them),
+    `depth` (8, 10 or 12), `chroma` (the C tag's text), `range` (from XCOLORRANGE=FULL|LIMITED; LIMITED when absent), `matrix`, `frame_bytes`.  y4m carries
+    no matrix tag: `matrix` is BT709 when height >= 720 and BT601 otherwise, which is ffmpeg's usual guess for untagged video;
+    assign `matrix` / `range`, or pass `yuv=dict(matrix=..., range=...)` to `deblur_clip`, to override.
+
+    Interlaced streams, depths outside `depths` (9, 14 and 16 bits always), layouts outside `layouts` (C422 and Cmono at any depth
+    by default), C420paldv, C411 and C440 are rejected with a ValueError that names the tag."""
+
+    def __init__(self, path_or_file, depths=(8,), layouts=(CENTER, LEFT, P444)):
+        self._open(path_or_file, depths, layouts)
+        self._lock = threading.Lock()
+        try:
+            self._parse()
+        except Exception:
+            self.close()
+            raise
+
+    def _parse(self) -> None:
+        f = self._f
+        f.seek(0)
+        end = self._header(f.read(MAX_HEADER))
+        c = self.chroma
         self._data = end + 1
         size = f.seek(0, os.SEEK_END)
         if size == self._data:
@@ -214,10 +244,6 @@ class Y4MReader:
                              f"{record} bytes ({len(self._line)} of FRAME line, {self.frame_bytes} of {self.width}x{self.height} "
                              f"C{c}) and {rest} bytes more (a cut last frame, or FRAME lines of different lengths)")
 
-    @staticmethod
-    def _is_frame_line(line: bytes) -> bool:
-        return line[:5] == b"FRAME" and line[5:6] in (b" ", b"\n") and line.find(b"\n") == len(line) - 1
-
     def __len__(self) -> int:
         return self._T
 
@@ -233,22 +259,87 @@ class Y4MReader:
         if got != (n, self.frame_bytes):
             raise ValueError(f"{self.name}: frame {i} is cut short")
         if not self._is_frame_line(bytes(line)):
-            raise ValueError(f"{self.name}: frame {i} does not start with a FRAME line of {n} bytes like the first frame's "
-                             f"({bytes(self._line)!r}): FRAME lines of different lengths are not supported")
+            self._bad_line(i, n, self._line)
         return buf
 
     def __getitem__(self, i: int) -> np.ndarray:
         return self.raw(i + self._T if isinstance(i, int) and i < 0 else i)
 
-    def close(self) -> None:
-        if self._own:
-            self._f.close()
 
-    def __enter__(self):
-        return self
+class Y4MStream(_Header):
+    """A y4m stream read in order from a binary file object that need not seek (a pipe, a socket's file, stdin), or from a path: what
+    `Y4MReader` is for a file, without a length.  The header line is read here, with `Y4MReader`'s tags, `depths=` / `layouts=`
+    opt-ins, attributes and error texts (the two share the code); then `read_into(buf)` fills `buf` (`frame_bytes` bytes: a uint8
+    numpy array or any writable buffer) with the next frame's planar bytes and returns True, or returns False at a clean end of the
+    stream (the end in front of a FRAME line).  Short reads are put together.  ValueError: a stream that ends inside a FRAME line or
+    a frame, or a FRAME line that is not one of the first frame's length.  `frames` counts the frames read so far.  One reader at
+    a time: the object keeps the bytes it read past a line."""
 
-    def __exit__(self, *exc):
-        self.close()
+    def __init__(self, path_or_file, depths=(8,), layouts=(CENTER, LEFT, P444)):
+        self._open(path_or_file, depths, layouts)
+        self._rest, self._line, self.frames = b"", None, 0
+        try:
+            head = b""
+            while b"\n" not in head and len(head) < MAX_HEADER:
+                more = getattr(self._f, "read1", self._f.read)(MAX_HEADER - len(head))       # what the pipe holds, not all 4096
+                if not more:
+                    break
+                head += more
+            end = self._header(head)
+            self._rest = head[end + 1:]
+        except Exception:
+            self.close()
+            raise
+
+    def _fill(self, view: memoryview) -> int:
+        """Fill `view` from the bytes kept and then the file; returns the bytes got (fewer than asked: the stream has ended)."""
+        got = min(len(self._rest), len(view))
+        if got:
+            view[:got] = self._rest[:got]
+            self._rest = self._rest[got:]
+        while got < len(view):
+            n = self._f.readinto(view[got:])
+            if not n:
+                break
+            got += n
+        return got
+
+    def _frame_line(self) -> bool:
+        i = self.frames
+        if self._line is None:               # the first frame's line: up to its newline, byte by byte from what a pipe holds
+            line = bytearray()
+            while not line.endswith(b"\n") and len(line) < MAX_HEADER:
+                one = bytearray(1)
+                if not self._fill(memoryview(one)):
+                    break
+                line += one
+            if not line:
+                return False
+            if not self._is_frame_line(bytes(line)):
+                raise ValueError(f"{self.name}: no FRAME line after the header")
+            self._line = bytes(line)
+            return True
+        n = len(self._line)
+        line = bytearray(n)
+        got = self._fill(memoryview(line))
+        if got == 0:
+            return False
+        if got != n:
+            raise ValueError(f"{self.name}: frame {i} is cut short")
+        if not self._is_frame_line(bytes(line)):
+            self._bad_line(i, n, self._line)
+        return True
+
+    def read_into(self, buf) -> bool:
+        view = memoryview(buf).cast("B")
+        if view.nbytes != self.frame_bytes:
+            raise ValueError(f"y4m: a {self.width}x{self.height} C{self.chroma} frame is {self.frame_bytes} bytes, the buffer holds {view.nbytes}")
+        if not self._frame_line():
+            return False
+        if self._fill(view) != self.frame_bytes:
+            raise ValueError(f"{self.name}: frame {self.frames} is cut short")
+        self.frames += 1
+        return True
 
 
 class Y4MWriter:
