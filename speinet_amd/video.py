@@ -14,11 +14,9 @@ file on disk before the first frame is deblurred, with `--stream` it is deblurre
 and the dataset harness (speinet_amd.inference) runs every clip through `deblur_clip` as well, adding its ground truth and metrics.
   * labels — given (0/1 per frame, 1 = sharp), or computed by the LD detector (speinet_amd.detector) in a first streaming pass over the
     clip in batches of 16 frames: gray planes from the ingest kernel, focus measures, logistic regression;
-  * the window plan — `selection.assemble_windows` on the frame numbers (by default a frame's number is its index in the clip; the
-    harness passes the numbers in its file names): reflect-padded clip, `blurry_indices`, references more than 7 frames away zeroed,
-    routing by the zeroed reference; with scene cuts (`cuts`: given, or found by `scene_stats` + `find_cuts` in the labelling pass),
-    every scene is planned as a clip of its own, so no window and no reference frame crosses a cut (an extension: the reference's
-    data sets are one folder per shot);
+  * the window plan — speinet_amd.plan (host-only; its public names are this module's too): `window_plan` runs
+    `selection.assemble_windows` on the frame numbers, every scene between two cuts (`cuts`: given, or found by `find_cuts` from the
+    pair statistics of the labelling pass) as a clip of its own, so no window and no reference frame crosses a cut;
   * the windows — `forward_window` with a per-clip `EncoderCache`, `prefetch_window` one window ahead, windows alternating over two
     launch streams that the model keeps, in whatever `precision` / `corr_precision` / `use_graph` / `streams` the caller set on it;
   * the frames come from speinet_amd.clip (`frames_of`, `FrameCache`); a window whose 16-bit pass left a non-finite value is recomputed in bf16x3;
@@ -51,11 +49,11 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     or (`roi_feather=`, `--roi_feather`) blended with the input over a ramp inside the rectangle.  Off by default.
   * a stream (`stream=True`, `--stream`): a clip whose length is not known (a `y4m.Y4MStream` on a pipe, an iterator of frames) is read
     by one thread into a bounded ring of page-locked frames (`clip.StreamFrames`); the labelling pass and the scene statistics run in the
-    same batches as frames arrive (`detector.clip_analysis`), `StreamCuts` decides a cut once `find_cuts`' neighbourhood is known, and
-    `StreamPlan` hands out the entries of `window_plan` as soon as no continuation of the stream can change them, or `horizon` frames
-    ahead under a stated assumption in the two situations where the reference's selection depends on the whole rest of a scene
-    (`ClipRun.assumed` lists those frames).  The window loop behind the plan is the whole clip's, launch for launch: every frame
-    outside `assumed` is bit-identical.  Host memory is bounded by the look-ahead.  Off by default.
+    same batches as frames arrive (`detector.clip_analysis`) and feed `plan.StreamPlan`, which hands out the entries of `window_plan`
+    after a look-ahead of at most `horizon` frames (`ClipRun.assumed` lists the frames it planned under its assumption).  The loop
+    asks its plan source whether frame k is planned yet (`_WholePlan`: always; `_ArrivingPlan`: after analysing as far as needed) and
+    is otherwise the whole clip's, launch for launch: every frame outside `assumed` is bit-identical.  Host memory is bounded by
+    the look-ahead.  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -77,77 +75,20 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import detector, engine, ensemble as ens, ops, selection, tiles as tiling, y4m
+from . import detector, engine, ensemble as ens, ops, tiles as tiling, y4m
 from .clip import IMAGE_EXTS, MIN_SIZE, FrameCache, Frames, HostRing, frames_of, imread, imwrite, padded_size, reflect_index  # noqa: F401
+from .plan import (ASSUMED_TAIL, CUT_PARAMS, MIN_HORIZON, ZERO, StreamCuts, StreamPlan, cuts_of, find_cuts, labels_of,  # noqa: F401
+                   window_plan)
 from .speinet import EncoderCache
 
 _imread, _imwrite = imread, imwrite
 
-ZERO = ("zero",)                 # window key of a zeroed reference frame
 CORR_PRECISION = {"f32": "bf16x3", "bf16x3": "bf16x3", "bf16": "top2", "f16": "top2"}    # correlation arithmetic per precision
 DETECT_BATCH = 16                # frames per launch of the labelling pass (the harness's batch)
 PREFETCH = 4                     # windows decoded ahead of the GPU
 LANES = 2                        # launch streams the windows alternate over (3 and 4 measured 8-25 % slower than 2 on 720p)
 LAG = 2                          # windows enqueued after a frame before it is handed out
 FLAG_RING = 8                    # non-finite flags in flight (> LAG + 1)
-
-
-def labels_of(labels, T: int) -> np.ndarray:
-    lab = np.asarray(labels).reshape(-1)
-    if lab.size != T:
-        raise ValueError(f"labels has {lab.size} entries for a clip of {T} frames")
-    if not np.isin(lab, (0, 1)).all():
-        raise ValueError("labels must be 0 (blurry) or 1 (sharp) per frame")
-    return lab.astype(np.int64)
-
-
-def cuts_of(cuts, T: int) -> list:
-    """Validate scene cuts for a clip of T frames: a strictly increasing sequence of first-frame-of-scene indices in 1..T-1 (None: no
-    cuts).  Raises ValueError with the reason."""
-    if cuts is None:
-        return []
-    if isinstance(cuts, (str, bytes)) or not hasattr(cuts, "__iter__"):
-        raise ValueError(f"cuts must be a sequence of frame indices, got {cuts!r}")
-    arr = np.asarray(list(cuts))
-    whole = arr.size == 0 or arr.dtype.kind in "iu" or (arr.dtype.kind == "f" and (arr == np.floor(arr)).all())
-    if arr.ndim != 1 or not whole:
-        raise ValueError(f"cuts must be a flat sequence of whole frame indices, got {cuts!r}")
-    out = [int(c) for c in arr]
-    for c in out:
-        if not 1 <= c <= T - 1:
-            raise ValueError(f"cut {c} is outside 1..{T - 1}: a cut is the index of a scene's first frame in a clip of {T} frames")
-    if any(b <= a for a, b in zip(out, out[1:])):
-        raise ValueError(f"cuts must be strictly increasing, got {out}")
-    return out
-
-
-def find_cuts(sad, hist, pixels: int, *, hist_min: float = 0.25, ratio: float = 3.0, min_delta: float = 8.0, window: int = 2) -> list:
-    """Hard scene cuts from the pair statistics of a clip (`scene_stats`): sad [T-1], hist [T,64], `pixels` = H * W.  With
-    g[i] = sum_b |hist[i+1][b] - hist[i][b]| / (2 pixels) (the share of pixels that changed luma bin, 0..1) and d[i] = sad[i] / pixels
-    (mean absolute luma difference), there is a cut before frame i + 1 iff
-      g[i] >= hist_min,  d[i] >= min_delta,  and  g[i] >= ratio * max(g[j]) over the other pairs j with |j - i| <= window
-    (vacuously true when there are none).  The histogram term is blind to motion; the SAD term vetoes small global brightness steps;
-    the neighbourhood term makes a one-frame flash no cut, because its two pairs veto each other.  Returns the sorted list of
-    first-frame-of-scene indices.
-
-    Blind spots: a cut between two shots of the same tonal distribution has g near 0 and is missed; dissolves and fades are not hard
-    cuts and are not looked for; two cuts within `window` frames of each other veto each other.  The four defaults are design
-    parameters, not measurements: ratio 3 over a window of 2 is borrowed from common adaptive cut detectors, and nobody has tuned any
-    of them on real footage.  An extension beyond the reference, whose data sets hold one shot per folder."""
-    hist = np.asarray(hist, dtype=np.int64)
-    sad = np.asarray(sad, dtype=np.float64).reshape(-1)
-    if hist.ndim != 2 or hist.shape[0] < 2 or sad.size != hist.shape[0] - 1:
-        raise ValueError(f"find_cuts needs hist [T,bins] of T >= 2 frames and sad [T-1]; got {hist.shape} and {sad.shape}")
-    if pixels <= 0 or window < 0:
-        raise ValueError(f"find_cuts: pixels must be positive and window >= 0; got {pixels} and {window}")
-    g = np.abs(np.diff(hist, axis=0)).sum(axis=1) / (2.0 * pixels)
-    d = sad / pixels
-    cuts = []
-    for i in range(g.size):
-        others = np.concatenate([g[max(0, i - window):i], g[i + 1:i + 1 + window]])
-        if g[i] >= hist_min and d[i] >= min_delta and (others.size == 0 or g[i] >= ratio * others.max()):
-            cuts.append(i + 1)
-    return cuts
 
 
 def scene_stats(frames, device):
@@ -157,13 +98,14 @@ def scene_stats(frames, device):
     of `frames_of(..., depth=)`, or a deep y4m reader) goes through `ops.frame_pair_stats_u16`, and its sad comes back divided by
     2^(depth-8), as float64, so that `find_cuts`' `min_delta` keeps its 8-bit unit."""
     fr = frames if isinstance(frames, Frames) else frames_of(frames)
-    sad, hist = detector.clip_pass(fr, device, batch=DETECT_BATCH, features=False, pair_stats=True)[1]
-    return _sad_8bit(sad.cpu().numpy(), fr.depth), hist.cpu().numpy()
+    return _host_stats(detector.clip_pass(fr, device, batch=DETECT_BATCH, features=False, pair_stats=True)[1], fr.depth)
 
 
-def _sad_8bit(sad: np.ndarray, depth: int) -> np.ndarray:
-    """The pair SAD of a clip of `depth` bits in the 8-bit unit of `find_cuts`' `min_delta` (an exact division by a power of 2)."""
-    return sad if depth == 8 else sad / float(1 << (depth - 8))
+def _host_stats(stats, depth: int):
+    """Pair statistics (sad, hist) on the device as the host arrays `find_cuts` takes: the SAD of a clip of `depth` bits in the 8-bit
+    unit of `min_delta` (an exact division by a power of 2)."""
+    sad, hist = stats[0].cpu().numpy(), stats[1].cpu().numpy()
+    return (sad if depth == 8 else sad / float(1 << (depth - 8))), hist
 
 
 BAR_PARAMS = ("level", "min_bar", "frames")       # `bar_params`: find_bars' keywords, and the number of frames `active_area` scans
@@ -249,298 +191,96 @@ def check_roi_feather(roi_feather: int, h: int, w: int, tail) -> None:
         raise ValueError(f"roi_feather={roi_feather} " + tail(bound))
 
 
-def _scene_plan(labels, n_seq: int, numbers) -> list:
-    """The plan of one continuous scene: `selection.assemble_windows` on its frames."""
-    T = len(labels)
-    number = int if numbers is None else (lambda i: int(numbers[int(i)]))
-    wins = selection.assemble_windows([str(i) for i in range(T)], labels, n_seq, True, number=number)
-    plan = []
-    for k, w in enumerate(wins):
-        win, pre, sub = [int(f) for f in w["window"]], int(w["pre"]), int(w["sub"])
-        plan.append({"index": k, "window": win, "pre": pre, "sub": sub, "zero_pre": bool(w["zero_pre"]), "zero_sub": bool(w["zero_sub"]),
-                     "keys": win + [ZERO if w["zero_pre"] else pre, ZERO if w["zero_sub"] else sub]})
-    return plan
-
-
-def window_plan(labels, n_seq: int = 3, numbers=None, cuts=None) -> list:
-    """The window plan for a clip labelled `labels`: one entry per output frame with the n_seq window frames, the two reference frames
-    (frame indices), whether each reference is zeroed (more than 7 frame numbers from the last window frame; `zero_pre` is the
-    routing: True = no-reference branch) and the n_seq + 2 `forward_window` keys (frame indices, `ZERO` for a zeroed reference).
-    `numbers`: the frame numbers the reference gap is measured in (the harness's come from its file names); default: the indices.
-    `cuts` (`cuts_of`): the first frame of every scene after the first.  Each scene [a, b) is planned as a clip of its own, on
-    labels[a:b] and numbers[a:b], with every frame index shifted by a (`index` stays the output frame's index in the whole clip): the
-    windows reflect at the scene's ends and the references come from the scene.  A one-frame scene {i} is planned as the first entry of
-    the two-frame clip [i, i] with labels [l_i, l_i] and numbers [n_i, n_i]."""
-    T = len(labels)
-    cuts = cuts_of(cuts, T)
-    if not cuts:
-        return _scene_plan(labels, n_seq, numbers)
-    plan = []
-    for a, b in zip([0] + cuts, cuts + [T]):
-        at = [a, a] if b - a == 1 else list(range(a, b))           # the scene's frames: a one-frame scene twice
-        scene = _scene_plan([labels[i] for i in at], n_seq, [i if numbers is None else numbers[i] for i in at])[:b - a]
-        for p in scene:
-            q = dict(p, index=a + p["index"], window=[at[i] for i in p["window"]], pre=at[p["pre"]], sub=at[p["sub"]])
-            q["keys"] = [k if k is ZERO else at[k] for k in p["keys"]]
-            plan.append(q)
-    return plan
-
-
-class StreamCuts:
-    """`find_cuts` as the pair statistics arrive: `feed(sad, hist)` takes the next frames' batch (`hist` [n,64]; `sad` [n], or [n-1]
-    for the first batch, which has no frame before it: what `detector.clip_analysis` yields) and returns the cuts that became
-    certain, `finish()` those that the end of the stream decides.  Pair i is decided once pair i + `window` is known (or the stream
-    has ended): the neighbourhood rule looks no further.  `cuts` holds every cut found so far; after `finish` it equals `find_cuts`
-    on the whole arrays, with the same arithmetic per pair.  `safe` is the number of leading frames whose scene is certain: no cut
-    that is still undecided lies in front of any of them."""
-
-    def __init__(self, pixels: int, *, hist_min: float = 0.25, ratio: float = 3.0, min_delta: float = 8.0, window: int = 2):
-        if pixels <= 0 or window < 0:
-            raise ValueError(f"find_cuts: pixels must be positive and window >= 0; got {pixels} and {window}")
-        self.pixels, self.hist_min, self.ratio, self.min_delta, self.window = pixels, hist_min, ratio, min_delta, int(window)
-        self.g, self.d, self.cuts = [], [], []
-        self.frames = self.decided = 0
-        self._last = None
-
-    def feed(self, sad, hist) -> list:
-        hist = np.asarray(hist, dtype=np.int64)
-        sad = np.asarray(sad, dtype=np.float64).reshape(-1)
-        rows = hist if self._last is None or hist.ndim != 2 else np.concatenate([self._last[None], hist])
-        if hist.ndim != 2 or hist.shape[0] < 1 or sad.size != rows.shape[0] - 1:
-            raise ValueError(f"StreamCuts.feed needs hist [n,bins] of n >= 1 frames and sad of one entry per new pair; got {hist.shape} "
-                             f"and {sad.shape} after {self.frames} frames")
-        self.g += (np.abs(np.diff(rows, axis=0)).sum(axis=1) / (2.0 * self.pixels)).tolist()
-        self.d += (sad / self.pixels).tolist()
-        self._last, self.frames = hist[-1].copy(), self.frames + hist.shape[0]
-        return self._decide(False)
-
-    def finish(self) -> list:
-        return self._decide(True)
-
-    def _decide(self, ended: bool) -> list:
-        g, w, new = self.g, self.window, []
-        while self.decided < len(g) and (ended or self.decided + w < len(g)):
-            i = self.decided
-            others = g[max(0, i - w):i] + g[i + 1:i + 1 + w]
-            if g[i] >= self.hist_min and self.d[i] >= self.min_delta and (not others or g[i] >= self.ratio * max(others)):
-                new.append(i + 1)
-            self.decided += 1
-        self.cuts += new
-        return new
-
-    @property
-    def safe(self) -> int:
-        return min(self.frames, self.decided + 1)
-
-
-ASSUMED_TAIL = [0] * 16 + [1, 1]     # what `StreamPlan` assumes of a scene at its horizon: it goes on, with sharp frames out of reach
-MIN_HORIZON = 24
-
-
-class StreamPlan:
-    """`window_plan` as the labels arrive: the plan of a clip whose length, later labels and later cuts are not known yet.
-
-    `feed(labels=None, sad=None, hist=None, count=None)` takes the next frames' batch and returns the plan entries that can be handed
-    out now, in frame order, each the dict that `window_plan` makes; `finish()` ends the stream and returns the rest.  `labels`: the
-    batch's 0/1 per frame, or None when the constructor was given `labels` for the whole stream (then `count`, or `hist`, says how
-    many frames the batch holds; a stream longer or shorter than the labels is a ValueError from the `feed` or the `finish` that
-    finds it out).  `cuts`: None (one scene), a strictly increasing list of first-frame-of-scene indices, or "auto": `sad` / `hist`
-    of every batch go to a `StreamCuts` (`pixels`, `cut_params`).  `labels`, `cuts` and `plan` hold what is known so far, `assumed`
-    the frames whose entry was handed out under the assumption below, `at[j]` the number of frames that had been taken in when entry
-    j was handed out.
-
-    The contract, with `horizon` (at least 24; default 48, about 2 s of video: a design parameter, larger than every bounded
-    dependence of the plan):
-      * an entry is handed out as soon as it is FINAL: its `keys`, `zero_pre` and `zero_sub` are the same for every continuation of
-        the stream, whatever labels follow, however long the scene gets, and wherever a cut that `StreamCuts` has not excluded yet
-        falls.  At the end of a scene (a cut that is certain, or the end of the stream) everything left is final: it is planned on
-        the scene's true labels;
-      * if frame j + horizon is known to lie in entry j's scene and entry j is still not final, it is handed out as entry j of
-        `window_plan` on the scene's known labels followed by `ASSUMED_TAIL` (the scene goes on and holds later sharp frames, none
-        within reach), and j is appended to `assumed`.
-    A batch is taken in 8 frames at a time, so an entry is handed out no later than the feed position j + horizon + window + 9
-    (`window`: `find_cuts`' neighbourhood, 2 by default, 0 without "auto"), which is below j + horizon + DETECT_BATCH.
-
-    Why this is enough.  With m frames of the scene known, m >= 24 and m >= j + 11 (j counted from the scene's start), every
-    continuation gives the scene at least m frames, so both far indices of `blurry_indices` (the padded clip's ends) are more than 7
-    frames from entry j's last window frame and are zeroed, and every later sharp frame, the reflected one at the padded clip's end
-    included, is at least 10 frames past that frame: out of reach of the 7-frame rule.  What is left of the future in entry j is one
-    bit: whether ANY sharp frame follows the known ones.  So the entry is computed for the continuation without one (the known
-    labels and two blurry frames) and for `ASSUMED_TAIL`, and is final iff the two agree.  They disagree in two situations only,
-    the two global quirks of the reference's selection:
-      1. after the last sharp frame so far: entry j's last window frame is fewer than 7 frames past a sharp frame s and no known
-         sharp frame follows it.  If s is the scene's last sharp frame the later reference is s; if any sharp frame follows, however
-         far, it is the zeroed far index;
-      2. exactly one sharp frame in the scene's padded labels so far: the scene is planned by the neighbour rule, and a second sharp
-         frame anywhere later switches all of it to the nearest-sharp rule.
-    `numbers=` is not supported: the gap rule is in frame indices.  `pre` and `sub` of a zeroed reference (`keys` holds `ZERO` there)
-    name the far frame of the continuation the entry was computed on, which need not be the whole clip's, nor a frame of it.
-
-    A long scene is planned on its last frames only (`keep`, at least horizon + 32, kept behind the next entry), with the sharp
-    frames before them stood in for by none, one or two sharp frames out of reach: entry j depends on what lies more than 7 frames
-    behind it only through their count (none, one, more)."""
-
-    STEP = 8
-
-    def __init__(self, horizon: int = 48, cuts=None, labels=None, pixels: Optional[int] = None, cut_params: Optional[dict] = None,
-                 n_seq: int = 3, keep: Optional[int] = None):
-        if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon < MIN_HORIZON:
-            raise ValueError(f"horizon must be a whole number >= {MIN_HORIZON}, got {horizon!r}")
-        if n_seq != 3:
-            raise ValueError("StreamPlan plans 3-frame windows")
-        self.horizon, self.n_seq = int(horizon), n_seq
-        self.keep = max(self.horizon + 32, 64) if keep is None else int(keep)
-        if self.keep < self.horizon + 32:
-            raise ValueError(f"keep must be at least horizon + 32 = {self.horizon + 32}, got {keep!r}")
-        self._given = None
-        if labels is not None:
-            lab = np.asarray(labels).reshape(-1)
-            if not np.isin(lab, (0, 1)).all():
-                raise ValueError("labels must be 0 (blurry) or 1 (sharp) per frame")
-            self._given = lab.astype(np.int64)
-        self._auto = None
-        self._cut_list = None
-        if isinstance(cuts, str):
-            if cuts != "auto":
-                raise ValueError(f"cuts must be None, \"auto\" or a sequence of frame indices, got {cuts!r}")
-            if pixels is None:
-                raise ValueError("cuts=\"auto\" needs pixels= (H * W)")
-            self._auto = StreamCuts(pixels, **(cut_params or {}))
-        elif cuts is not None:
-            try:                         # the clip's length is not known: every bound but the upper one is checked here
-                top = max((int(c) for c in cuts), default=0)
-            except (TypeError, ValueError):
-                top = 0
-            self._cut_list = cuts_of(cuts, top + 1)
-        self.labels, self.cuts, self.plan, self.assumed, self.at = [], [], [], [], []
-        self.fed = 0                     # frames taken in
-        self.start = 0                   # first frame of the scene being planned
-        self._c0, self._before = 0, 0    # the scene is planned from frame _c0 on; sharp frames (padded) of the scene before it
-        self.ended = False
-
-    # ---- feeding ----
-    def feed(self, labels=None, sad=None, hist=None, count: Optional[int] = None) -> list:
-        if self.ended:
-            raise ValueError("the stream has ended")
-        if self._given is not None:
-            n = int(count) if count is not None else (len(hist) if hist is not None else len(labels))
-            if self.fed + n > self._given.size:
-                raise ValueError(f"labels has {self._given.size} entries and the stream is longer: frame {self._given.size} has arrived")
-            lab = self._given[self.fed:self.fed + n]
-        else:
-            lab = np.asarray(labels).reshape(-1)
-            if not np.isin(lab, (0, 1)).all():
-                raise ValueError("labels must be 0 (blurry) or 1 (sharp) per frame")
-        n = len(lab)
-        if self._auto is not None:
-            if hist is None or sad is None or len(hist) != n:
-                raise ValueError(f"cuts=\"auto\" needs the pair statistics of the batch's {n} frames")
-            sad, hist = np.asarray(sad).reshape(-1), np.asarray(hist)
-        out, lead = [], 1 if self.fed == 0 else 0        # the stream's first batch has no pair for its first frame
-        for a in range(0, n, self.STEP):
-            b = min(n, a + self.STEP)
-            self.labels += [int(v) for v in lab[a:b]]
-            self.fed += b - a
-            if self._auto is not None:
-                self._auto.feed(sad[max(a - lead, 0):b - lead], hist[a:b])
-                self.cuts = list(self._auto.cuts)
-            out += self._advance()
-        return out
-
-    def finish(self) -> list:
-        if self.ended:
-            return []
-        if self._given is not None and self.fed != self._given.size:
-            raise ValueError(f"labels has {self._given.size} entries and the stream is shorter: it ended after {self.fed} frames")
-        if self._cut_list and self._cut_list[-1] > self.fed - 1:
-            cuts_of(self._cut_list, self.fed)
-        self.ended = True
-        if self._auto is not None:
-            self._auto.finish()
-            self.cuts = list(self._auto.cuts)
-        return self._advance()
-
-    # ---- planning ----
-    def _safe(self) -> int:
-        return self.fed if self._auto is None or self.ended else self._auto.safe
-
-    def _scene_end(self) -> Optional[int]:
-        """The end of the scene being planned, once it is certain; None while it is not."""
-        if self._cut_list is not None:
-            nxt = next((c for c in self._cut_list if c > self.start), None)
-            if nxt is not None and nxt <= self.fed:
-                if nxt not in self.cuts:
-                    self.cuts.append(nxt)
-                return nxt
-        elif self._auto is not None:
-            nxt = next((c for c in self.cuts if c > self.start), None)
-            if nxt is not None:
-                return nxt
-        return self.fed if self.ended else None
-
-    def _planned(self, stop: int, tail: list):
-        """`_scene_plan` of the scene's frames [_c0, stop) and `tail`, behind the stand-in of what was dropped; (plan, offset): entry
-        j of the clip is plan[j - offset], its frame indices shifted by offset."""
-        head = [] if self._c0 == self.start else [0, 0, 0] + [1] * min(self._before, 2) + [0] * 16
-        return _scene_plan(head + self.labels[self._c0:stop] + tail, self.n_seq, None), self._c0 - len(head)
-
-    @staticmethod
-    def _shift(p: dict, j: int, off: int) -> dict:
-        q = dict(p, index=j, window=[f + off for f in p["window"]], pre=p["pre"] + off, sub=p["sub"] + off)
-        q["keys"] = [k if k is ZERO else k + off for k in p["keys"]]
-        return q
-
-    def _hand(self, q: dict, assumed: bool = False) -> dict:
-        if assumed:
-            self.assumed.append(q["index"])
-        self.plan.append(q)
-        self.at.append(self.fed)
-        return q
-
-    def _advance(self) -> list:
-        out = []
-        while True:
-            nxt, end = len(self.plan), self._scene_end()
-            if end is not None:          # a whole scene (what is left of it): its true labels
-                if end - self.start == 1:
-                    i = self.start           # as `window_plan`: the first entry of the two-frame clip [i, i]
-                    p = _scene_plan([self.labels[i]] * 2, self.n_seq, None)[0]
-                    q = dict(p, index=i, window=[i] * len(p["window"]), pre=i, sub=i, keys=[k if k is ZERO else i for k in p["keys"]])
-                    out.append(self._hand(q))
-                elif nxt < end:
-                    plan, off = self._planned(end, [])
-                    out += [self._hand(self._shift(plan[j - off], j, off)) for j in range(nxt, end)]
-                if end >= self.fed and self.ended:
-                    return out
-                self.start = self._c0 = end
-                self._before = 0
-                continue
-            m = self._safe() - self.start                                  # frames known to lie in the scene
-            if self._cut_list is not None:
-                m = min(m, next((c for c in self._cut_list if c > self.start), self.fed) - self.start)
-            if m < MIN_HORIZON or nxt - self.start + 11 > m:
-                return out
-            if nxt - self._c0 > 2 * self.keep:                             # plan on the scene's last frames only
-                c0 = nxt - self.keep
-                if self._c0 == self.start:
-                    self._before += self.labels[self.start + 1]            # the padded clip's first frame is frame 1 again
-                self._before += sum(self.labels[self._c0:c0])
-                self._c0 = c0
-            stop = self.start + m
-            (blurry, off), (sharp, _) = self._planned(stop, [0, 0]), self._planned(stop, ASSUMED_TAIL)
-            for j in range(nxt, stop - 10):
-                a, b = blurry[j - off], sharp[j - off]
-                final = (a["keys"], a["zero_pre"], a["zero_sub"]) == (b["keys"], b["zero_pre"], b["zero_sub"])
-                if not final and not j + self.horizon < stop:
-                    break
-                out.append(self._hand(self._shift(b, j, off), assumed=not final))
-            return out
-
-
 def _lanes(model, device, n: int) -> list:
     """The launch streams of the windows, one set per model and device: `forward_window` captures one graph per launch stream, so
     fresh streams per clip would capture fresh graphs per clip."""
     return engine.model_streams(model, ("video_lanes", device.index, n), device, n)
+
+
+class _WholePlan:
+    """The plan source of a clip whose length is known: `labels`, `cuts` and `plan` of the whole clip, `has(k)`: it has a frame k."""
+
+    def __init__(self, run: "ClipRun", labels, cuts):
+        self.run, self._labels, self._cuts, self._plan, self.assumed = run, labels, cuts, None, []
+
+    def _known(self, name: str):
+        if getattr(self, name) is None:
+            self._analyse()
+        return getattr(self, name)
+
+    labels = property(lambda self: self._known("_labels"))
+    cuts = property(lambda self: self._known("_cuts"))
+
+    @property
+    def plan(self) -> list:
+        if self._plan is None:
+            self._plan = window_plan(self.labels, numbers=self.run.numbers, cuts=self.cuts)
+        return self._plan
+
+    def _analyse(self) -> None:
+        """Whatever is missing of the LD detector's labels and the scene cuts, in ONE pass over the clip, DETECT_BATCH frames at a time:
+        upload, then gray planes (spei_frames_u8_in / spei_frames_u16_in) and focus measures, pair statistics (spei_frame_pair_stats /
+        spei_frame_pair_stats_u16), or both.  A deep clip stays deep throughout.  With a region of interest the pass is handed the
+        clip's view through it, so the detector and the pair statistics see the cropped frames."""
+        run, p, fr = self.run, self.run.detector, self.run._view()
+        feats, stats = detector.clip_pass(fr, run.device, p.kernel_size, DETECT_BATCH, features=self._labels is None,
+                                          pair_stats=self._cuts is None)
+        if feats is not None:
+            self._labels = detector.predict(feats, p)
+        if stats is not None:
+            self._cuts = find_cuts(*_host_stats(stats, fr.depth), fr.H * fr.W, **run.cut_params)
+
+    def has(self, k: int, home) -> bool:
+        return k < len(self.plan)
+
+
+class _ArrivingPlan:
+    """The plan source of a stream (`run.frames` is a `clip.StreamFrames`): a `StreamPlan` fed by the analysis of the frames as they
+    arrive; `labels`, `cuts` and `plan` hold what is known so far, `assumed` the frames planned under `StreamPlan`'s assumption."""
+
+    def __init__(self, run: "ClipRun", labels, cuts, horizon: int):
+        self.run, self.view = run, run._view()
+        self.sp = sp = StreamPlan(horizon, cuts="auto" if cuts is None else (cuts or None), labels=labels,
+                                  pixels=self.view.H * self.view.W, cut_params=run.cut_params)
+        # what is held at once: the look-ahead of the plan, the analysis batch in front of it and the windows behind (`ClipRun._run`)
+        run.frames.reserve(sp.horizon + 2 * DETECT_BATCH + PREFETCH + 4 + (run.cut_params.get("window", 2) - 2 if cuts is None else 0))
+        self.analysis = None if labels is not None and cuts is not None else detector.clip_analysis(
+            self.view, run.device, run.detector.kernel_size, DETECT_BATCH, features=labels is None, pair_stats=cuts is None)
+
+    labels = property(lambda self: np.asarray(self.sp.labels, dtype=np.int64))
+    cuts = property(lambda self: self.sp.cuts)
+    plan = property(lambda self: self.sp.plan)
+    assumed = property(lambda self: self.sp.assumed)
+
+    def _pump(self) -> None:
+        """One DETECT_BATCH of the stream into the plan, as soon as its frames have arrived: the batch `_WholePlan._analyse` would run."""
+        sp, analysis = self.sp, self.analysis
+        if analysis is not None:
+            item = next(analysis, None)
+            n = 0 if item is None else len(item[1] if item[1] is not None else item[2][1])
+        else:
+            n = self.view.upto(sp.fed + DETECT_BATCH) - sp.fed
+        if n <= 0:
+            if sp.fed < 2:
+                raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {sp.fed}")
+            sp.finish()
+        elif analysis is None:
+            sp.feed(count=n)
+        else:
+            _, feats, stats = item
+            sad, hist = (None, None) if stats is None else _host_stats(stats, self.view.depth)
+            sp.feed(None if feats is None else detector.predict(feats, self.run.detector), sad, hist, count=n)
+
+    def has(self, k: int, home) -> bool:
+        """Whether the clip has a frame k: analyses the stream (on the stream `home`) until entry k is planned (or the stream has
+        ended), and on until the plan is PREFETCH entries ahead while that takes no waiting.  Frames that neither a later window (its
+        references lie at most 7 behind its last frame) nor the analysis will ask for are given up."""
+        sp, plan, fr = self.sp, self.sp.plan, self.run.frames
+        fr.release(max(0, min(sp.fed, k - 8)))
+        while not sp.ended and (len(plan) <= k or (len(plan) <= k + PREFETCH and fr.ready(sp.fed + DETECT_BATCH) == sp.fed + DETECT_BATCH)):
+            with torch.no_grad(), torch.cuda.device(self.run.device), torch.cuda.stream(home):
+                self._pump()
+        return k < len(plan)
 
 
 class ClipRun:
@@ -573,8 +313,6 @@ class ClipRun:
         self.device = params[0].device if params else torch.device("cpu")
         if self.device.type != "cuda":
             raise RuntimeError("speinet_amd runs on MI355X only (HIP kernels): move the model to a ROCm device first")
-        self._labels = labels
-        self._cuts = cuts                # a list, or None while "auto" has not run
         self.cut_params = dict(cut_params or {})
         if out is not None and out.device != self.device:
             raise ValueError(f"out is on {out.device}, the model on {self.device}")
@@ -582,18 +320,10 @@ class ClipRun:
         self.recomputed = []         # frames whose 16-bit pass left a non-finite value and that were recomputed in bf16x3
         self.seconds = []
         self.numbers = numbers
-        self._plan = None
         self._it = None
-        self.assumed = []            # stream mode: the frames whose plan entry was handed out under `StreamPlan`'s assumption
         self.horizon = horizon       # None: the whole clip is known; a number: stream mode, with that look-ahead
-        self._stream = None
-        if horizon is not None:
-            view = self._view()
-            self._stream = StreamPlan(horizon, cuts="auto" if cuts is None else (cuts or None), labels=labels, pixels=view.H * view.W,
-                                      cut_params=self.cut_params)
-            self.assumed = self._stream.assumed
-            # what is held at once: the look-ahead of the plan, the analysis batch in front of it and the windows behind (`_run`)
-            frames.reserve(self._stream.horizon + 2 * DETECT_BATCH + PREFETCH + 4 + (self.cut_params.get("window", 2) - 2 if cuts is None else 0))
+        # labels, cuts (a list, or None for "auto") and the plan: known whole, or as the stream goes
+        self._source = _WholePlan(self, labels, cuts) if horizon is None else _ArrivingPlan(self, labels, cuts, horizon)
 
     @property
     def roi(self):
@@ -611,29 +341,10 @@ class ClipRun:
         """The clip the analysis pass sees: the frames cropped to the region of interest."""
         return self.frames if self.roi is None else self.frames.view(self.roi)
 
-    @property
-    def labels(self) -> np.ndarray:
-        if self._stream is not None:
-            return np.asarray(self._stream.labels, dtype=np.int64)
-        if self._labels is None:
-            self._analyse()
-        return self._labels
-
-    @property
-    def cuts(self) -> list:
-        if self._stream is not None:
-            return self._stream.cuts
-        if self._cuts is None:
-            self._analyse()
-        return self._cuts
-
-    @property
-    def plan(self) -> list:
-        if self._stream is not None:
-            return self._stream.plan
-        if self._plan is None:
-            self._plan = window_plan(self.labels, numbers=self.numbers, cuts=self.cuts)
-        return self._plan
+    labels = property(lambda self: self._source.labels)
+    cuts = property(lambda self: self._source.cuts)
+    plan = property(lambda self: self._source.plan)
+    assumed = property(lambda self: self._source.assumed)
 
     def __iter__(self):
         return self
@@ -642,19 +353,6 @@ class ClipRun:
         if self._it is None:
             self._it = self._run()
         return next(self._it)
-
-    def _analyse(self) -> None:
-        """Whatever is missing of the LD detector's labels and the scene cuts, in ONE pass over the clip, DETECT_BATCH frames at a time:
-        upload, then gray planes (spei_frames_u8_in / spei_frames_u16_in) and focus measures, pair statistics (spei_frame_pair_stats /
-        spei_frame_pair_stats_u16), or both.  A deep clip stays deep throughout.  With a region of interest the pass is handed the
-        clip's view through it, so the detector and the pair statistics see the cropped frames."""
-        p, fr = self.detector, self._view()
-        feats, stats = detector.clip_pass(fr, self.device, p.kernel_size, DETECT_BATCH, features=self._labels is None,
-                                          pair_stats=self._cuts is None)
-        if feats is not None:
-            self._labels = detector.predict(feats, p)
-        if stats is not None:
-            self._cuts = find_cuts(_sad_8bit(stats[0].cpu().numpy(), fr.depth), stats[1].cpu().numpy(), fr.H * fr.W, **self.cut_params)
 
     def _run(self):
         m, dev, fr = self.model, self.device, self.frames
@@ -667,45 +365,8 @@ class ClipRun:
         if roi is not None:
             Hp, Wp = padded_size(roi[2]), padded_size(roi[3])
         centres = {}                     # per window in flight: its centre input frame, whole, for the paste (and a recompute's)
-        sp = self._stream
-        plan = self.plan                 # the whole clip's; a stream's grows as `pump` analyses it
-        if sp is None:
-            def has(k):
-                return k < len(plan)
-        else:
-            p, view = self.detector, self._view()
-            analysis = None
-            if self._labels is None or self._cuts is None:
-                analysis = detector.clip_analysis(view, dev, p.kernel_size, DETECT_BATCH, features=self._labels is None,
-                                                  pair_stats=self._cuts is None)
-
-            def pump():
-                """One DETECT_BATCH of the stream into the plan, as soon as its frames have arrived: the batch `_analyse` would run."""
-                if analysis is not None:
-                    item = next(analysis, None)
-                    n = 0 if item is None else len(item[1] if item[1] is not None else item[2][1])
-                else:
-                    n = view.upto(sp.fed + DETECT_BATCH) - sp.fed
-                if n <= 0:
-                    if sp.fed < 2:
-                        raise ValueError(f"a clip needs at least 2 frames (its 3-frame windows reflect at the ends); got {sp.fed}")
-                    sp.finish()
-                elif analysis is None:
-                    sp.feed(count=n)
-                else:
-                    _, feats, stats = item
-                    sad, hist = (None, None) if stats is None else (_sad_8bit(stats[0].cpu().numpy(), view.depth), stats[1].cpu().numpy())
-                    sp.feed(None if feats is None else detector.predict(feats, p), sad, hist, count=n)
-
-            def has(k):
-                """Whether the clip has a frame k: analyses the stream until entry k is planned (or the stream has ended), and on
-                until the plan is PREFETCH entries ahead while that takes no waiting.  Frames that neither a later window (its
-                references lie at most 7 behind its last frame) nor the analysis will ask for are given up."""
-                fr.release(max(0, min(sp.fed, k - 8)))
-                while not sp.ended and (len(plan) <= k or (len(plan) <= k + PREFETCH and fr.ready(sp.fed + DETECT_BATCH) == sp.fed + DETECT_BATCH)):
-                    with torch.no_grad(), torch.cuda.device(dev), torch.cuda.stream(home):
-                        pump()
-                return k < len(plan)
+        src = self._source
+        plan = src.plan                  # the whole clip's; a stream's grows as `src.has` analyses it
         n = m.n_sequence
         pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
         # frames (uint8, or uint16 for a deep clip), decoded and uploaded once each; a y4m clip's as planar bytes, made RGB on the device
@@ -841,13 +502,13 @@ class ClipRun:
 
         # grad mode and the current device are set around each step, not across a `yield`: they are the caller's while it holds a frame
         try:
-            has(0)
+            src.has(0, home)
             with torch.no_grad(), torch.cuda.device(dev), torch.cuda.stream(home):
                 nxt = prepare(0)
             k = -1
             while nxt is not None:
                 k += 1
-                more = has(k + 1)
+                more = src.has(k + 1, home)
                 with torch.no_grad(), torch.cuda.device(dev):
                     with torch.cuda.stream(home):
                         x = nxt
@@ -864,8 +525,8 @@ class ClipRun:
                 yield got
         finally:
             pool.shutdown(wait=False, cancel_futures=True)
-            if sp is not None:
-                fr.close()
+            if self.horizon is not None:
+                fr.close()               # a stream: its reader thread ends
 
 
 def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = None, crop: bool = False, numbers=None,
@@ -994,10 +655,8 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
         if isinstance(roi, str) and roi == "auto":
             raise ValueError("roi=\"auto\" with stream=True: the active area is found from frames sampled over the whole clip; give "
                              "the rectangle (y0, x0, h, w)")
+    # a stream's `fr.T` is None: what is measured against the clip's length is then checked by `StreamPlan` as the stream goes
     fr = frames_of(frames, crop, yuv, depth)
-    if stream:
-        return _stream_run(model, fr, labels, detector, cuts, cut_params, out_depth, tiles, shave, feather, ensemble, roi, roi_feather,
-                           horizon)
     if roi is not None and not isinstance(roi, str):
         roi = roi_of(tuple(roi) if isinstance(roi, list) else roi, fr.H, fr.W)
         h, w = (fr.H, fr.W) if roi is None else roi[2:]
@@ -1021,40 +680,15 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
         if cuts != "auto":
             raise ValueError(f"cuts must be None, \"auto\" or a sequence of frame indices, got {cuts!r}")
         cuts = None
-    else:
-        cuts = cuts_of(cuts, fr.T)
-    if cut_params is not None and set(cut_params) - {"hist_min", "ratio", "min_delta", "window"}:
-        raise ValueError(f"cut_params holds {sorted(set(cut_params) - {'hist_min', 'ratio', 'min_delta', 'window'})}: "
-                         "find_cuts takes hist_min, ratio, min_delta and window")
+    elif cuts is None or fr.T is not None:
+        cuts = cuts_of(cuts, fr.T)       # a stream's list: `StreamPlan` checks it, its upper bound at the stream's end
+    if cut_params is not None and set(cut_params) - set(CUT_PARAMS):
+        raise ValueError(f"cut_params holds {sorted(set(cut_params) - set(CUT_PARAMS))}: find_cuts takes hist_min, ratio, min_delta and window")
     tp = None if tiles is None else tiling.tile_plan(fr.H, fr.W, tuple(tiles) if isinstance(tiles, list) else tiles, shave, feather)
     if tp is not None and tp.n == 1:
         tp = None                        # one tile that spans the frame: the untiled path
-    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp, ensemble, roi, int(roi_feather), bar_params)
-
-
-def _stream_run(model, fr, labels, detector, cuts, cut_params, out_depth, tiles, shave, feather, ensemble, roi, roi_feather, horizon) -> ClipRun:
-    """`deblur_clip`'s checks for a clip of unknown length, and its `ClipRun`: whatever is measured against the length is checked by
-    the incremental plan as the stream goes (`StreamPlan`)."""
-    if roi is not None:
-        roi = roi_of(tuple(roi) if isinstance(roi, list) else roi, fr.H, fr.W)
-        h, w = (fr.H, fr.W) if roi is None else roi[2:]
-        check_roi_feather(roi_feather, h, w, lambda bound: f"is outside 0..{bound}: at most {ROI_FEATHER_MAX} and half of the {w}x{h} rectangle")
-    if out_depth is not None and (isinstance(out_depth, bool) or out_depth not in y4m.DEPTHS):
-        raise ValueError(f"out_depth must be None, 8, 10 or 12, got {out_depth!r}")
-    if isinstance(cuts, str):
-        if cuts != "auto":
-            raise ValueError(f"cuts must be None, \"auto\" or a sequence of frame indices, got {cuts!r}")
-        cuts = None                      # `ClipRun`: found as the run goes
-    elif cuts is None:
-        cuts = []
-    if cut_params is not None and set(cut_params) - {"hist_min", "ratio", "min_delta", "window"}:
-        raise ValueError(f"cut_params holds {sorted(set(cut_params) - {'hist_min', 'ratio', 'min_delta', 'window'})}: "
-                         "find_cuts takes hist_min, ratio, min_delta and window")
-    tp = None if tiles is None else tiling.tile_plan(fr.H, fr.W, tuple(tiles) if isinstance(tiles, list) else tiles, shave, feather)
-    if tp is not None and tp.n == 1:
-        tp = None
-    return ClipRun(model, fr, labels, None, None, detector, cuts, cut_params, None if out_depth is None else int(out_depth), tp, ensemble,
-                   roi, int(roi_feather), None, horizon=horizon)
+    return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp, ensemble, roi, int(roi_feather), bar_params,
+                   horizon if stream else None)
 
 
 def _inputs(spec: str) -> list:

@@ -1,5 +1,5 @@
 """Reference side of the streaming tests (tests/test_stream_cpu.py, tests/test_gpu_stream.py): the two situations in which the
-incremental plan (`speinet_amd.video.StreamPlan`) may commit an entry under its assumption, stated from the reference's selection
+incremental plan (`speinet_amd.plan.StreamPlan`) may commit an entry under its assumption, stated from the reference's selection
 rule and NOT from the planner's code, the generator of the randomised plan cases, and y4m streams as bytes.
 
 The two situations, for entry j of a scene (j counted from the scene's start; its last window frame is f = j + 1, the frame the

@@ -1,9 +1,14 @@
-"""CPU suite for scene cuts in the clip API (speinet_amd/video.py): the cut rule `find_cuts` on hand-made statistics and on translated
-edge scenes (against a numpy restatement of the pair-statistics kernel), and the per-scene window plan `window_plan(..., cuts=)`."""
+"""CPU suite for scene cuts in the clip API (speinet_amd/plan.py, under its own name): the cut rule `find_cuts` on hand-made statistics
+and on translated edge scenes (against a numpy restatement of the pair-statistics kernel), the per-scene window plan
+`window_plan(..., cuts=)`, and that the plan module loads neither the HIP library nor the clip loop."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
-from speinet_amd import video as V
+from speinet_amd import plan as V, video
 from speinet_amd.synth import synth_scene_u8
 
 PIXELS = 6400
@@ -190,26 +195,39 @@ def test_cut_validation(cuts, message):
         V.window_plan([0] * 10, cuts=cuts)
     if cuts != "auto":
         with pytest.raises(ValueError, match=message):
-            V.deblur_clip(None, np.zeros((10, 30, 30, 3), np.uint8), [0] * 10, cuts=cuts)
+            video.deblur_clip(None, np.zeros((10, 30, 30, 3), np.uint8), [0] * 10, cuts=cuts)
 
 
 def test_deblur_clip_cut_arguments():
     frames = np.zeros((10, 30, 30, 3), np.uint8)
     with pytest.raises(ValueError, match='"auto"'):
-        V.deblur_clip(None, frames, [0] * 10, cuts="yes")
+        video.deblur_clip(None, frames, [0] * 10, cuts="yes")
     with pytest.raises(ValueError, match="find_cuts takes"):
-        V.deblur_clip(None, frames, [0] * 10, cuts="auto", cut_params={"threshold": 1})
+        video.deblur_clip(None, frames, [0] * 10, cuts="auto", cut_params={"threshold": 1})
 
 
 def test_read_cuts(tmp_path):
     np.save(tmp_path / "cuts.npy", np.asarray([6, 11]))
     (tmp_path / "cuts.txt").write_text("6\n11\n")
     (tmp_path / "none.txt").write_text("")
-    assert V.read_cuts(str(tmp_path / "cuts.npy")) == [6, 11] == V.read_cuts(str(tmp_path / "cuts.txt"))
-    assert V.read_cuts(str(tmp_path / "none.txt")) == []
+    assert video.read_cuts(str(tmp_path / "cuts.npy")) == [6, 11] == video.read_cuts(str(tmp_path / "cuts.txt"))
+    assert video.read_cuts(str(tmp_path / "none.txt")) == []
     with pytest.raises(ValueError):
         (tmp_path / "bad.txt").write_text("6 x")
-        V.read_cuts(str(tmp_path / "bad.txt"))
+        video.read_cuts(str(tmp_path / "bad.txt"))
+
+
+def test_plan_module_stands_alone():
+    """In a fresh interpreter (this one imported the clip loop long ago), importing the plan loads neither the HIP library's wrapper
+    nor the clip loop, and the clip loop hands out the plan's names as its own."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; import speinet_amd.plan as P; "
+            "bad = [m for m in ('ops', 'video', 'clip', 'detector', '_lib') if 'speinet_amd.' + m in sys.modules]; "
+            "assert not bad, bad; assert P.find_cuts and P.StreamPlan and P.CUT_PARAMS == ('hist_min', 'ratio', 'min_delta', 'window')")
+    done = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=120)
+    assert done.returncode == 0, done.stderr
+    for name in ("ZERO", "CUT_PARAMS", "ASSUMED_TAIL", "MIN_HORIZON", "labels_of", "cuts_of", "find_cuts", "StreamCuts", "window_plan", "StreamPlan"):
+        assert getattr(video, name) is getattr(V, name)
 
 
 def test_header_declares_pair_stats():
