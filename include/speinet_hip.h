@@ -630,6 +630,16 @@ int spei_roi_paste_u8(const float* src, const void* frame, int in_depth, unsigne
 int spei_roi_paste_u16(const float* src, const void* frame, int in_depth, uint16_t* dst, int* nonfinite, int H, int W, int y0, int x0,
                        int h, int w, int hp, int wp, int feather, int depth, spei_stream_t stream);
 
+/* A frame the clip API keeps (video.deblur_clip(..., sharp="keep"); an extension beyond the reference, which deblurs every frame):
+ * the packed input frame [H][W][3] at the output depth, dst[i] = requant(src[i]) as defined above for every one of the 3 * H * W
+ * samples; at equal depths a copy (a 16-bit word above D_in still reads as D_in).  src: in_depth 8 (bytes), 10 or 12 (little-endian
+ * 16-bit words, 2-byte aligned); dst: out_depth 8, 10 or 12 likewise.  The frame is a flat run of independent samples: where both
+ * bases are 16-byte aligned a thread moves the side with the wider samples as one 16-byte access and the other side as one access of
+ * the same samples (16 samples for 8 -> 8 bits, 8 otherwise); element by element otherwise and behind the last whole run.  One
+ * launch, no workspace, no atomics.  Non-zero before anything is launched: a null pointer; a depth outside {8, 10, 12}; H or W below
+ * 1, or a frame beyond the size bound of spei_frames_u8_in; a deep pointer on an odd address; a dst that overlaps src. */
+int spei_frame_requant(const void* src, int in_depth, void* dst, int out_depth, int H, int W, spei_stream_t stream);
+
 /* The extent of the picture in N packed uint8 [H][W][3] frames, frame_stride bytes apart (rows packed; the frame-size bound of
  * spei_frames_u8_in), for the clip API's bar rule (video.find_bars): on the integer luma of spei_frame_pair_stats,
  * Y = (77 R + 150 G + 29 B + 128) >> 8, rowmax[y] (H ints) is the maximum of Y over row y of all N frames and colmax[x] (W ints) the

@@ -130,6 +130,30 @@ class HostRing:
                 f.result()
 
 
+class RecordQueue:
+    """Host records handed to a pool of one thread, which writes them in the order queued: `put(fn, record)` copies the record (the
+    caller's buffer may be a view of a ring that moves on) and queues `fn(copy)`.  At most `n` writes are in flight: with `n` queued
+    `put` first waits for the oldest, as `HostRing.land` waits for the slot it used `n` frames earlier, so a producer that outruns the
+    sink holds `n` records, not the clip.  An error in a write is raised by the `put` or the `drain` that waits for it."""
+
+    def __init__(self, pool: ThreadPoolExecutor, n: int = 8):
+        self.pool, self.n, self.futs = pool, n, collections.deque()
+
+    @property
+    def in_flight(self) -> int:
+        """Writes queued and not yet waited for: an upper bound of those not yet done."""
+        return len(self.futs)
+
+    def put(self, fn, record: np.ndarray) -> None:
+        while len(self.futs) >= self.n:
+            self.futs.popleft().result()
+        self.futs.append(self.pool.submit(fn, np.array(record)))
+
+    def drain(self) -> None:
+        while self.futs:
+            self.futs.popleft().result()
+
+
 def reflect_index(n: int, n_pad: Optional[int] = None) -> np.ndarray:
     """Source row (or column) of each of the n_pad padded rows of a dimension of n: i < n reads i, n + j reads n - 2 - j (torch F.pad
     mode "reflect"; what spei_frames_u8_in computes in its pad band)."""

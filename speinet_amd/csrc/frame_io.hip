@@ -21,6 +21,11 @@
 //                        v * (float)(1 / D), the gray plane of v * (float)(255 / D), round_half_even(clamp(x * D, 0, D)), the luma
 //                        and its histogram at the depth of the samples (bins of Y >> (depth - 6)).
 //
+//   spei_frame_requant — a packed frame of in_depth 8, 10 or 12 -> the same frame at out_depth 8, 10 or 12, every sample requant(v) of
+//                        pixel_group.h (the value spei_roi_paste_* writes outside its rectangle; a copy at equal depths): the frame
+//                        the clip API hands out for a frame it keeps (video.deblur_clip(..., sharp="keep"); an extension, the
+//                        reference deblurs every frame).  One flat streaming launch.
+//
 // One kernel per entry-point pair, templated on the sample type T; the pixel group they stream is in pixel_group.h.  The mirrored
 // indices are computed in the pad band only.
 #include "pixel_group.h"
@@ -86,6 +91,47 @@ __global__ __launch_bounds__(256) void frame_out_kernel(const float* __restrict_
         store_group(dst + ((int64_t)y * W + x0) * 3, q, vec_out != 0, W - x0);
     }
     if (nonfinite && bad) atomicOr(nonfinite, 1);           // rare: one atomic per thread that met a non-finite value
+}
+
+// ---- a frame at another depth --------------------------------------------------------------------------------------------------
+// A packed frame is one run of independent samples, so this kernel has no pixel group.  A thread takes a run of samples at a time: the
+// side with the wider samples moves as one 16-byte access and the other side as one access of the same samples (16 bytes, or 8 where
+// uint8 meets uint16), so a wave reads and writes whole contiguous lines with one instruction each, where two 16-byte stores per
+// lane, 32 bytes apart, would fill every line in two halves.  This runs where both bases lie on 16-byte boundaries
+// (`vecs` whole runs; 0 otherwise); the samples behind the last whole run go one by one.  The two depths are template arguments:
+// `requant` then folds to one constant divisor (a multiply and a shift), or to nothing at equal depths.
+template <int DEPTH> struct SampleOf { typedef uint16_t type; };
+template <> struct SampleOf<8> { typedef unsigned char type; };
+constexpr int requant_run(int in_depth, int out_depth) { return in_depth == 8 && out_depth == 8 ? 16 : 8; }     // samples per thread
+
+template <int N> struct Words { typedef uint4 type; };                         // N dwords as one access
+template <> struct Words<2> { typedef uint2 type; };
+__device__ __forceinline__ void unpack_words(const uint4& v, uint32_t (&w)[4]) { w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+__device__ __forceinline__ void unpack_words(const uint2& v, uint32_t (&w)[2]) { w[0] = v.x; w[1] = v.y; }
+__device__ __forceinline__ uint4 pack_words(const uint32_t (&w)[4]) { return make_uint4(w[0], w[1], w[2], w[3]); }
+__device__ __forceinline__ uint2 pack_words(const uint32_t (&w)[2]) { return make_uint2(w[0], w[1]); }
+
+template <int IN, int OUT>
+__global__ __launch_bounds__(256) void frame_requant_kernel(const typename SampleOf<IN>::type* __restrict__ src,
+                                                            typename SampleOf<OUT>::type* __restrict__ dst, int64_t total, int64_t vecs) {
+    typedef typename SampleOf<IN>::type TI;
+    typedef typename SampleOf<OUT>::type TO;
+    constexpr int Din = (1 << IN) - 1, Dout = (1 << OUT) - 1, RUN = requant_run(IN, OUT);
+    constexpr int NI = RUN * (int)sizeof(TI) / 4, NO = RUN * (int)sizeof(TO) / 4, PI = 4 / (int)sizeof(TI), PO = 4 / (int)sizeof(TO);
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    for (int64_t i = t; i < vecs; i += step) {
+        uint32_t w[NI], o[NO];
+        unpack_words(reinterpret_cast<const typename Words<NI>::type*>(src)[i], w);
+#pragma unroll
+        for (int k = 0; k < NO; ++k) o[k] = 0u;
+#pragma unroll
+        for (int j = 0; j < RUN; ++j) {                    // sample j: PI of them per dword read, PO per dword written
+            const int v = sample_of((TI)(w[j / PI] >> (32 / PI * (j % PI))), Din);
+            o[j / PO] |= requant(v, Din, Dout) << (32 / PO * (j % PO));
+        }
+        reinterpret_cast<typename Words<NO>::type*>(dst)[i] = pack_words(o);
+    }
+    for (int64_t j = vecs * RUN + t; j < total; j += step) dst[j] = (TO)requant(sample_of(src[j], Din), Din, Dout);
 }
 
 // ---- pair statistics -----------------------------------------------------------------------------------------------------------
@@ -205,6 +251,34 @@ int frame_out(const char* name, const float* src, T* dst, int* nonfinite, int H,
     return 0;
 }
 
+int frame_requant(const char* name, const void* src, int in_depth, void* dst, int out_depth, int H, int W, hipStream_t stream) {
+    SPEI_REQUIRE(src && dst, "%s: null pointer", name);
+    SPEI_REQUIRE(in_depth == 8 || in_depth == 10 || in_depth == 12, "%s: unknown in_depth %d (8, 10 or 12)", name, in_depth);
+    SPEI_REQUIRE(out_depth == 8 || out_depth == 10 || out_depth == 12, "%s: unknown out_depth %d (8, 10 or 12)", name, out_depth);
+    SPEI_REQUIRE(H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
+    const int in_bytes = in_depth == 8 ? 1 : 2, out_bytes = out_depth == 8 ? 1 : 2;
+    SPEI_REQUIRE(((uintptr_t)src & (in_bytes - 1)) == 0 && ((uintptr_t)dst & (out_bytes - 1)) == 0,
+                 "%s: misaligned pointer (deep frames are 2-byte aligned)", name);
+    const int64_t total = (int64_t)H * W * 3;
+    SPEI_REQUIRE(!bytes_overlap(dst, total * out_bytes, src, total * in_bytes), "%s: dst overlaps src", name);
+    const int run = requant_run(in_depth, out_depth);
+    const int64_t vecs = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0 ? total / run : 0;
+    const dim3 grid(grid_for(vecs > total - vecs * run ? vecs : total - vecs * run));
+#define SPEI_REQUANT(IN, OUT)                                                                                               \
+    case IN * 16 + OUT:                                                                                                     \
+        hipLaunchKernelGGL((frame_requant_kernel<IN, OUT>), grid, dim3(256), 0, stream,                                     \
+                           static_cast<const SampleOf<IN>::type*>(src), static_cast<SampleOf<OUT>::type*>(dst), total, vecs); \
+        break
+    switch (in_depth * 16 + out_depth) {
+        SPEI_REQUANT(8, 8); SPEI_REQUANT(8, 10); SPEI_REQUANT(8, 12);
+        SPEI_REQUANT(10, 8); SPEI_REQUANT(10, 10); SPEI_REQUANT(10, 12);
+        SPEI_REQUANT(12, 8); SPEI_REQUANT(12, 10); SPEI_REQUANT(12, 12);
+    }
+#undef SPEI_REQUANT
+    SPEI_CHECK_LAUNCH(name);
+    return 0;
+}
+
 template <typename T>
 int frame_pair_stats(const char* name, const T* src, int64_t frame_stride, const T* prev, int N, int H, int W, int depth, int* hist,
                      int64_t* sad, hipStream_t stream) {
@@ -248,6 +322,10 @@ extern "C" int spei_frame_u8_out(const float* src, unsigned char* dst, int* nonf
 extern "C" int spei_frame_u16_out(const float* src, uint16_t* dst, int* nonfinite, int H, int W, int Hp, int Wp, int depth,
                                   spei_stream_t stream) {
     return frame_out<uint16_t>("spei_frame_u16_out", src, dst, nonfinite, H, W, Hp, Wp, depth, (hipStream_t)stream);
+}
+
+extern "C" int spei_frame_requant(const void* src, int in_depth, void* dst, int out_depth, int H, int W, spei_stream_t stream) {
+    return frame_requant("spei_frame_requant", src, in_depth, dst, out_depth, H, W, (hipStream_t)stream);
 }
 
 extern "C" int spei_frame_pair_stats(const unsigned char* src, int64_t frame_stride, const unsigned char* prev, int N, int H, int W,

@@ -99,6 +99,20 @@ __device__ __forceinline__ void ingest_group(const T* __restrict__ s, int x, int
     }
 }
 
+// the input sample at the output depth: v * Dout / Din rounded half up, in integers (at most 4095 * 8190 + 4095 < 2^26); v is a
+// sample as read, so at most Din.  The one definition behind spei_frame_requant and the outside of spei_roi_paste_*
+__device__ __forceinline__ uint32_t requant(int v, int Din, int Dout) {
+    if (Din == Dout) return (uint32_t)v;
+    const uint32_t n = (uint32_t)v * 2u * (uint32_t)Dout + (uint32_t)Din;
+    return Din == 255 ? n / 510u : Din == 1023 ? n / 2046u : n / 8190u;       // constant divisors: a multiply and a shift each
+}
+
+// do the byte ranges [a, a + na) and [b, b + nb) meet (host)
+inline bool bytes_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
+
 // mul(D).clamp(0, D).round() of tensor2numpy: half to even, as torch.  `round_sample` is for a value known to be finite;
 // `quantise` gives 0 for one that is not (rounded before the test: a select, no branch around the rounding)
 __device__ __forceinline__ float rounded(float v, float Df) { return rintf(fminf(fmaxf(v * Df, 0.0f), Df)); }

@@ -27,13 +27,6 @@ struct Rect {
     float r;
 };
 
-// the input sample at the output depth: v * Dout / Din rounded half up, in integers (at most 4095 * 8190 + 4095 < 2^26)
-__device__ __forceinline__ uint32_t requant(int v, int Din, int Dout) {
-    if (Din == Dout) return (uint32_t)v;
-    const uint32_t n = (uint32_t)v * 2u * (uint32_t)Dout + (uint32_t)Din;
-    return Din == 255 ? n / 510u : Din == 1023 ? n / 2046u : n / 8190u;       // constant divisors: a multiply and a shift each
-}
-
 // the weight of the model's output at place p of an axis of `len` pixels with ramps of lo / hi pixels at its two ends
 __device__ __forceinline__ float axis_weight(int p, int len, int lo, int hi, float r) {
     if (p < lo) return __fmul_rn((float)(2 * p + 1), r);
@@ -168,11 +161,6 @@ __global__ __launch_bounds__(256) void frame_extent_kernel(const T* __restrict__
     }
 }
 
-inline bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
-
 template <typename TO>
 int roi_paste(const char* name, const float* src, const void* frame, int in_depth, TO* dst, int* nonfinite, int H, int W, int y0, int x0,
               int h, int w, int hp, int wp, int feather, int depth, hipStream_t stream) {
@@ -192,8 +180,8 @@ int roi_paste(const char* name, const float* src, const void* frame, int in_dept
     SPEI_REQUIRE(((uintptr_t)frame & (in_bytes - 1)) == 0 && ((uintptr_t)dst & (sizeof(TO) - 1)) == 0 && ((uintptr_t)src & 3) == 0,
                  "%s: misaligned pointer (src 4-byte, deep frames 2-byte aligned)", name);
     const int64_t samples = (int64_t)H * W * 3;
-    SPEI_REQUIRE(!overlap(dst, samples * sizeof(TO), frame, samples * in_bytes), "%s: dst overlaps frame", name);
-    SPEI_REQUIRE(!overlap(dst, samples * sizeof(TO), src, (int64_t)3 * hp * wp * sizeof(float)), "%s: dst overlaps src", name);
+    SPEI_REQUIRE(!bytes_overlap(dst, samples * sizeof(TO), frame, samples * in_bytes), "%s: dst overlaps frame", name);
+    SPEI_REQUIRE(!bytes_overlap(dst, samples * sizeof(TO), src, (int64_t)3 * hp * wp * sizeof(float)), "%s: dst overlaps src", name);
     Rect rc = {y0, x0, h, w, 0, 0, 0, 0, feather, 0.0f};
     if (feather > 0) {                                     // a side on the frame's border has no seam: no ramp
         rc.top = y0 > 0 ? feather : 0;

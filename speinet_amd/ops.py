@@ -612,6 +612,34 @@ def roi_paste(x: torch.Tensor, frame: torch.Tensor, roi, out_depth: int = 8, fea
     return out
 
 
+def frame_requant(frame: torch.Tensor, out_depth: int, in_depth: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A packed frame at another depth: `frame` [H,W,3] on the device (contiguous), uint8 (`in_depth` None) or uint16 of `in_depth` 10
+    or 12 bits -> the frame at `out_depth`, uint8 [H,W,3] for 8 and uint16 for 10 and 12, every sample
+    (min(v, D_in) * 2 * D_out + D_in) // (2 * D_in) with D = 2^depth - 1: what `roi_paste` writes outside its rectangle, a copy at
+    equal depths (a word above D_in reads as D_in).  `out` (optional): the packed destination; it may not overlap `frame`.  One launch
+    on the current stream (csrc/frame_io.hip), no host sync."""
+    assert frame.is_cuda and frame.dtype in (torch.uint8, torch.uint16) and frame.dim() == 3 and frame.shape[2] == 3
+    assert frame.is_contiguous()
+    if frame.dtype == torch.uint16:
+        in_depth = _depth(in_depth)
+    elif in_depth not in (None, 8):
+        raise ValueError(f"in_depth= applies to uint16 frames only; the frame is {frame.dtype}")
+    else:
+        in_depth = 8
+    if isinstance(out_depth, bool) or out_depth not in y4m.DEPTHS:
+        raise ValueError(f"out_depth must be 8, 10 or 12, got {out_depth!r}")
+    h, w = (int(v) for v in frame.shape[:2])
+    dtype = torch.uint8 if out_depth == 8 else torch.uint16
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=dtype, device=frame.device)
+    assert out.device == frame.device and out.dtype == dtype and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
+    with torch.cuda.device(frame.device):
+        st = C.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)
+        _lib.check(_lib.lib().spei_frame_requant(_vp(frame.data_ptr()), in_depth, _vp(out.data_ptr()), int(out_depth), h, w, st),
+                   "spei_frame_requant")
+    return out
+
+
 def frame_extent(frames: torch.Tensor, depth: Optional[int] = None, out=None):
     """The extent of the picture in packed frames [N,H,W,3] on the device (any frame stride), uint8 (`depth` None) or uint16 of `depth`
     10 or 12 bits -> (rowmax int32 [H], colmax int32 [W]): the maximum over every row, and over every column, of all N frames of the

@@ -6,7 +6,7 @@
                                 [--matrix bt601|bt709] [--range full|limited] [--fps num:den]
                                 [--chroma 420jpeg|420mpeg2|422|444|mono] [--out_chroma 420jpeg|420mpeg2|422|444|mono]
                                 [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N] [--ensemble 1|2|4|8]
-                                [--roi none|auto|Y,X,H,W] [--roi_feather N] [--stream [--horizon N]]
+                                [--roi none|auto|Y,X,H,W] [--roi_feather N] [--stream [--horizon N]] [--sharp deblur|keep]
 
 (`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; by default stdin is spooled to a temporary
 file on disk before the first frame is deblurred, with `--stream` it is deblurred as it arrives, see `main`)
@@ -54,6 +54,14 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     asks its plan source whether frame k is planned yet (`_WholePlan`: always; `_ArrivingPlan`: after analysing as far as needed) and
     is otherwise the whole clip's, launch for launch: every frame outside `assumed` is bit-identical.  Host memory is bounded by
     the look-ahead.  Off by default.
+  * sharp frames kept (`sharp="keep"`, `--sharp keep`; csrc/frame_io.hip `spei_frame_requant`): no window runs for a frame labelled
+    sharp; it is handed out as the input frame at the output depth by one `ops.frame_requant` launch on the home stream and takes no
+    lane, launch slot or flag slot.  The other frames keep their plan entries and their bits: a sharp frame is still a neighbour and a
+    reference.  The window after a kept frame has no encoder prefetch and computes what it misses in `forward_window` (the same
+    values); the frame cache is asked for a kept frame itself.  The command line writes a kept y4m frame as the record it read, byte
+    for byte, when the output has the input's chroma layout, depth and range.  An extension beyond the reference, which deblurs every
+    frame; no trained checkpoint exists here, so nothing is claimed about quality, nor about a visible step between a kept frame and
+    its deblurred neighbours.  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -76,7 +84,7 @@ import numpy as np
 import torch
 
 from . import detector, engine, ensemble as ens, ops, tiles as tiling, y4m
-from .clip import IMAGE_EXTS, MIN_SIZE, FrameCache, Frames, HostRing, frames_of, imread, imwrite, padded_size, reflect_index  # noqa: F401
+from .clip import IMAGE_EXTS, MIN_SIZE, FrameCache, Frames, HostRing, RecordQueue, frames_of, imread, imwrite, padded_size, reflect_index  # noqa: F401
 from .plan import (ASSUMED_TAIL, CUT_PARAMS, MIN_HORIZON, ZERO, StreamCuts, StreamPlan, cuts_of, find_cuts, labels_of,  # noqa: F401
                    window_plan)
 from .speinet import EncoderCache
@@ -89,6 +97,7 @@ PREFETCH = 4                     # windows decoded ahead of the GPU
 LANES = 2                        # launch streams the windows alternate over (3 and 4 measured 8-25 % slower than 2 on 720p)
 LAG = 2                          # windows enqueued after a frame before it is handed out
 FLAG_RING = 8                    # non-finite flags in flight (> LAG + 1)
+READY_MAX = LAG + 2              # finished or queued frames held back at most (kept frames among them; < FLAG_RING, and a stream's look-back)
 
 
 def scene_stats(frames, device):
@@ -191,6 +200,15 @@ def check_roi_feather(roi_feather: int, h: int, w: int, tail) -> None:
         raise ValueError(f"roi_feather={roi_feather} " + tail(bound))
 
 
+SHARP = ("deblur", "keep")       # what becomes of a frame labelled sharp: a window of its own like any other, or the input frame
+
+
+def check_sharp(sharp) -> str:
+    if not isinstance(sharp, str) or sharp not in SHARP:
+        raise ValueError(f"sharp must be \"deblur\" or \"keep\", got {sharp!r}")
+    return sharp
+
+
 def _lanes(model, device, n: int) -> list:
     """The launch streams of the windows, one set per model and device: `forward_window` captures one graph per launch stream, so
     fresh streams per clip would capture fresh graphs per clip."""
@@ -233,6 +251,9 @@ class _WholePlan:
     def has(self, k: int, home) -> bool:
         return k < len(self.plan)
 
+    def label(self, k: int) -> int:
+        return int(self.labels[k])
+
 
 class _ArrivingPlan:
     """The plan source of a stream (`run.frames` is a `clip.StreamFrames`): a `StreamPlan` fed by the analysis of the frames as they
@@ -251,6 +272,10 @@ class _ArrivingPlan:
     cuts = property(lambda self: self.sp.cuts)
     plan = property(lambda self: self.sp.plan)
     assumed = property(lambda self: self.sp.assumed)
+
+    def label(self, k: int) -> int:
+        """The label of a frame whose entry is planned (its batch has been fed)."""
+        return self.sp.labels[k]
 
     def _pump(self) -> None:
         """One DETECT_BATCH of the stream into the plan, as soon as its frames have arrived: the batch `_WholePlan._analyse` would run."""
@@ -295,12 +320,17 @@ class ClipRun:
     clip that is deblurred whole (found on first access, by `active_area` + `find_bars`, when the caller asked for "auto"); labels,
     cuts and the plan are then those of the clip of cropped frames.  In stream mode (`horizon` set: the clip is a `clip.StreamFrames`)
     `labels`, `cuts` and `plan` hold what is known so far and are complete after the last frame, and `assumed` lists the frames whose
-    plan entry `StreamPlan` handed out under its assumption (empty in whole-clip mode)."""
+    plan entry `StreamPlan` handed out under its assumption (empty in whole-clip mode).  `sharp` is "deblur" or "keep"; with "keep"
+    no window runs for a frame whose label is 1: it is handed out as the input frame at `out_depth` (`ops.frame_requant`), `kept` is
+    the increasing list of those handed out so far, none of them is ever in `recomputed`, and `assumed` leaves them out (a kept frame's
+    plan entry is not used; `plan` itself is the same list either way)."""
 
     def __init__(self, model, frames: Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
                  out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None, ensemble: int = 1, roi=None,
-                 roi_feather: int = 0, bar_params: Optional[dict] = None, horizon: Optional[int] = None):
+                 roi_feather: int = 0, bar_params: Optional[dict] = None, horizon: Optional[int] = None, sharp: str = "deblur"):
         self.model, self.frames = model, frames
+        self.sharp = check_sharp(sharp)
+        self.kept = []                   # sharp="keep": the frames handed out as their input, in order
         self._roi = roi                  # None, a rectangle, or "auto" while the scan has not run
         self.roi_feather = roi_feather
         self.bar_params = dict(bar_params or {})
@@ -344,7 +374,11 @@ class ClipRun:
     labels = property(lambda self: self._source.labels)
     cuts = property(lambda self: self._source.cuts)
     plan = property(lambda self: self._source.plan)
-    assumed = property(lambda self: self._source.assumed)
+
+    @property
+    def assumed(self) -> list:
+        a = self._source.assumed
+        return a if self.sharp != "keep" else [i for i in a if self._source.label(i) != 1]
 
     def __iter__(self):
         return self
@@ -415,11 +449,44 @@ class ClipRun:
         def frame(i):
             return fr.device(i).to(dev).contiguous() if fr.on_device(i) else cache.get_dev(i)
 
+        keep = self.sharp == "keep"
+
+        def kept(k):
+            """Is frame k (planned already, so labelled) handed out as its input, with no window of its own?"""
+            return keep and src.label(k) == 1
+
+        def request(k):
+            """The frames that steps k .. k + PREFETCH will ask the cache for: a window's keys; a kept frame itself, which no running
+            window need hold (the middle of a run of sharp frames)."""
+            for j in range(k, min(k + 1 + PREFETCH, len(plan))):
+                keys = [j] if kept(j) else plan[j]["keys"]
+                cache.request([i for i in keys if i is not ZERO and not fr.on_device(i)])
+
+        def stage(k):
+            """What step k needs one step ahead: window k's input, or None (and the frame's `seconds` entry) for a kept frame."""
+            if not kept(k):
+                return prepare(k)
+            self.seconds.append([0.0, 0.0])
+            return None
+
+        def keep_frame(k):
+            """Frame k as its input at the output depth: one launch on the home stream, queued for the hand-out behind the windows
+            before it.  It takes no lane, no launch slot and no flag slot."""
+            t0 = time.time()
+            request(k)
+            f = frame(k)
+            t1 = time.time()
+            dst = self.out[k] if self.out is not None else torch.empty(H, W, 3, dtype=out_dtype, device=dev)
+            ops.frame_requant(f, out_depth, None if depth == 8 else depth, out=dst)
+            ev = torch.cuda.Event()
+            ev.record()
+            ready.append((k, dst, ev, None))
+            self.seconds[k] = [t1 - t0, time.time() - t1]
+
         def prepare(k):
             """Window k's input [nt, n + 2, 3, Hp, Wp] on the home stream (nt = 1 without tiles): one per ensemble member."""
             t0 = time.time()
-            for ahead in plan[k:k + 1 + PREFETCH]:
-                cache.request([i for i in ahead["keys"] if i is not ZERO and not fr.on_device(i)])
+            request(k)
             x = torch.empty(nt, n + 2, 3, Hp, Wp, device=dev)
             for j, key in enumerate(plan[k]["keys"]):
                 if key is ZERO:
@@ -433,7 +500,8 @@ class ClipRun:
             return xs
 
         def enqueue(k, xs, nxts):
-            """Window k on its lane (and window k + 1's encoder passes on the model's prefetch stream)."""
+            """Window k on its lane (and window k + 1's encoder passes on the model's prefetch stream; `nxts` is None where frame k + 1
+            is kept: the next window that runs then computes the encoder passes it misses itself, the same values)."""
             if len(inflight) >= max(2, len(lanes)):
                 inflight.popleft().synchronize()           # the host stays at most two windows ahead of the GPU
             t0 = time.time()
@@ -484,10 +552,21 @@ class ClipRun:
             warnings.warn(f"speinet_amd.video: frame {k} had a non-finite value in {keep[0]} arithmetic and was recomputed in bf16x3",
                           RuntimeWarning, stacklevel=3)
 
+        def due():
+            """Is the frame at the head of `ready` handed out now?"""
+            return bool(ready) and (ready[0][3] is None or sum(r[3] is not None for r in ready) > LAG or len(ready) > READY_MAX)
+
         def hand_out():
             k, t, e, x = ready.popleft()
-            e.synchronize()                                # done already: the limiter in `enqueue` waited for it (not so while draining)
             cur = torch.cuda.current_stream(dev)
+            if x is None:                                  # a kept frame: no window ran, so there is no flag to read
+                cur.wait_event(e)
+                self.kept.append(k)
+                if cur != home:
+                    t.record_stream(cur)
+                return k, t
+            e.synchronize()                                # done already: the limiter in `enqueue` waited for it (not so while draining,
+                                                           # nor for a window that READY_MAX sends out with kept frames behind it)
             if int(flags_host[k % FLAG_RING]):
                 with torch.cuda.stream(home):
                     home.wait_event(e)
@@ -502,23 +581,31 @@ class ClipRun:
 
         # grad mode and the current device are set around each step, not across a `yield`: they are the caller's while it holds a frame
         try:
-            src.has(0, home)
+            more = src.has(0, home)
             with torch.no_grad(), torch.cuda.device(dev), torch.cuda.stream(home):
-                nxt = prepare(0)
+                nxt = stage(0)
             k = -1
-            while nxt is not None:
+            while more:
                 k += 1
                 more = src.has(k + 1, home)
                 with torch.no_grad(), torch.cuda.device(dev):
                     with torch.cuda.stream(home):
                         x = nxt
-                        nxt = prepare(k + 1) if more else None
-                        enqueue(k, x, nxt)
-                    # frames are handed out LAG windows behind: by then the limiter has waited for that window, so its non-finite flag
-                    # is on the host without a stall, and the windows after it keep running
-                    got = hand_out() if len(ready) > LAG else None
-                if got is not None:
+                        nxt = stage(k + 1) if more else None
+                        if x is None:
+                            keep_frame(k)
+                        else:
+                            enqueue(k, x, nxt)
+                    # a window is handed out LAG windows behind: by then the limiter has waited for it, so its non-finite flag is on
+                    # the host without a stall, and the windows after it keep running.  Kept frames do not pass the limiter, so they
+                    # do not count towards LAG; a kept frame at the head has nothing to wait for and leaves at once, one behind a
+                    # window waits its turn, so the order is the frames'.  READY_MAX bounds the queue: a window with fewer than LAG
+                    # windows but that many frames behind it is handed out all the same, and `hand_out` then does wait for it
+                    got = hand_out() if due() else None
+                while got is not None:
                     yield got
+                    with torch.no_grad(), torch.cuda.device(dev):
+                        got = hand_out() if due() else None
             while ready:
                 with torch.no_grad(), torch.cuda.device(dev):
                     got = hand_out()
@@ -533,7 +620,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
                 detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None,
                 depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20, feather: int = 0,
                 ensemble: int = 1, roi=None, roi_feather: int = 0, bar_params: Optional[dict] = None, stream=False,
-                horizon: int = 48) -> ClipRun:
+                horizon: int = 48, sharp: str = "deblur") -> ClipRun:
     """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
     or uint16 frames when `out_depth` is 10 or 12.
 
@@ -615,11 +702,24 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              `stream="force"`.  `ClipRun.assumed` lists the frames that are not the whole-clip run's, see `StreamPlan`.
     horizon — with `stream`: the look-ahead in frames, at least 24, after which a plan entry is committed (`StreamPlan`).
 
+    sharp  — "deblur" (the default): every frame runs its window, as the reference does; launch for launch the path without this
+             argument.  "keep": a frame whose label is 1 (from `labels` or the detector; with `roi`, the cropped clip's label) is
+             KEPT: no window runs for it, and it is handed out as the input frame at the output depth, every sample
+             (min(v, D_in) * 2 * D_out + D_in) // (2 * D_in) with D = 2^depth - 1 (`ops.frame_requant`, one launch; the identity at
+             equal depths; for a y4m clip the input frame is the RGB frame made from it).  That is the whole frame under `tiles`,
+             `ensemble` and `roi` too: what the paste writes outside the rectangle, so a kept frame has no seam there.  Every frame
+             that is not kept has the same plan entry and is bit-identical to the "deblur" run's: sharp frames still enter the
+             neighbouring windows and serve as references, as inputs.  `ClipRun.kept` lists the kept frames handed out so far; none
+             is ever flagged non-finite or in `recomputed`; in a stream none is in `assumed`.  With every frame kept the model is never
+             called.  An extension beyond the reference.  No trained checkpoint exists here, so nothing is claimed about quality: in
+             particular not that the step from a kept frame to its deblurred neighbours is invisible.
+
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
     to `ClipRun.recomputed` with a RuntimeWarning, and FloatingPointError is raised if the frame is still not finite."""
     ensemble = ens.check_size(ensemble)                    # in front of everything else: no frame is looked at
+    sharp = check_sharp(sharp)
     if tiles is None and not (isinstance(feather, int) and not isinstance(feather, bool) and feather == 0):
         raise ValueError(f"feather={feather!r} needs tiles=: it blends the seams between tiles, and an untiled frame has none")
     if isinstance(roi_feather, bool) or not isinstance(roi_feather, (int, np.integer)) or roi_feather < 0:
@@ -688,7 +788,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     if tp is not None and tp.n == 1:
         tp = None                        # one tile that spans the frame: the untiled path
     return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp, ensemble, roi, int(roi_feather), bar_params,
-                   horizon if stream else None)
+                   horizon if stream else None, sharp)
 
 
 def _inputs(spec: str) -> list:
@@ -816,6 +916,10 @@ def main(argv=None) -> None:
                    "only that rectangle is deblurred, the rest of every frame is the input's")
     p.add_argument("--roi_feather", type=int, default=0, help="with --roi: blend the deblurred rectangle with the input over the N pixels "
                    "inside every side of it that is not a side of the frame (0..min(200, H/2, W/2); default 0: a hard edge)")
+    p.add_argument("--sharp", choices=SHARP, default="deblur", help="what becomes of a frame labelled sharp (by --labels or the detector): "
+                   "'deblur' (the default) runs its window like any other; 'keep' runs none and writes the input frame (y4m in and out "
+                   "with the input's chroma layout, depth and range: the input's record, byte for byte).  The blurry frames are the "
+                   "same either way; sharp frames still serve them as neighbours and references")
     p.add_argument("--stream", action="store_true", help="y4m input only: deblur the stream as it arrives, with a bounded look-ahead and "
                    "no spool ('--input -' reads stdin as a pipe; a .y4m file is read in order); the first frames leave before the "
                    "input has ended.  The window plan is exact except where it depends on the rest of a scene, however long: there it "
@@ -892,7 +996,7 @@ def main(argv=None) -> None:
         out_depth = 8
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
                       yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather, ensemble=a.ensemble,
-                      roi=roi, roi_feather=a.roi_feather, stream=a.stream, horizon=a.horizon)
+                      roi=roi, roi_feather=a.roi_feather, stream=a.stream, horizon=a.horizon, sharp=a.sharp)
     out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
@@ -922,38 +1026,53 @@ def main(argv=None) -> None:
             + (f", feather {run.tiles.feather}" if run.tiles.feather else ""))
     if run.ensemble > 1:
         say(f"# ensemble {run.ensemble}: members 0..{run.ensemble - 1}, {run.ensemble} forward passes per frame")
+    # a kept frame of a y4m clip leaves as the record it came in, when the output's layout, depth and range are the input's (the matrix
+    # is one for both sides): no colour conversion, no chroma resampling.  `run.frames.host(i)` is that record
+    as_read = (a.sharp == "keep" and writer is not None and reader is not None
+               and (writer.layout, writer.depth, writer.range, writer.frame_bytes) == (run.frames.yuv[0], reader.depth, reader.range,
+                                                                                     reader.frame_bytes))
+    if a.sharp == "keep":
+        say("# sharp keep: no window runs for a frame labelled sharp, it is written as "
+            + ("its input record, byte for byte" if as_read else "the input frame at the output depth"))
     t0 = t_prev = time.time()
     done = 0
 
     def write(buf) -> None:
-        writer.write(buf.numpy())
+        writer.write(buf.numpy() if torch.is_tensor(buf) else buf)
         if a.stream and to_stdout:                         # a live pipe: the frame leaves now, not when the buffer is full
             sys.stdout.buffer.flush()
     # PNGs are encoded on four threads; a y4m stream is written by ONE, so its frames land in the order they were queued
     with ThreadPoolExecutor(max_workers=1 if to_y4m else 4, thread_name_prefix="speinet-y4m" if to_y4m else "speinet-png") as writers:
         ring = HostRing(writers)
+        records = RecordQueue(writers, ring.n)             # input records on their way out: as many in flight as the ring has slots
         for i, frame in run:
             done = i + 1
             if a.stream:
                 for c in run.cuts[said:]:
                     say(f"# cut before {names[c]}")
                 said = len(run.cuts)
-            if to_y4m:
+            is_kept = bool(run.kept) and run.kept[-1] == i
+            if is_kept and as_read:                        # a copy: a stream gives the record up a few frames on; the one writer keeps order
+                records.put(write, run.frames.host(i))
+            elif to_y4m:
                 planar = (ops.rgb_u8_to_yuv(frame, layout, matrix, rng) if out_depth == 8 else
                           ops.rgb_u16_to_yuv(frame, layout, matrix, rng, out_depth))
                 ring.land(write, planar)
             else:
                 ring.land(lambda buf, path=os.path.join(a.output, names[i]): imwrite(path, buf.numpy()), frame)
             now = time.time()
-            branch = "no-reference" if run.plan[i]["zero_pre"] else "reference"
+            branch = "kept" if is_kept else "no-reference" if run.plan[i]["zero_pre"] else "reference"
             say(f"> {names[i]} {branch} {now - t_prev:.3f}s")
             if run.recomputed and run.recomputed[-1] == i:
                 say(f"# {names[i]}: non-finite value in the {a.precision} frame, recomputed in bf16x3 ({len(run.recomputed)} so far)")
             t_prev = now
         ring.drain()
+        records.drain()
     if writer is not None:
         writer.close()
     dt = time.time() - t0
+    if a.sharp == "keep":
+        say(f"# kept {len(run.kept)} of {done} frames")
     say(f"# {done} frames {W}x{H} in {dt:.2f}s: {done / dt:.2f} frames/s ({a.precision}"
         + (f", ensemble {run.ensemble}" if run.ensemble > 1 else "")
         + (f", streamed with horizon {a.horizon}: {len(run.assumed)} frames assumed" if a.stream else "") + ")")
