@@ -578,6 +578,30 @@ int spei_tiles_u16_blend(const float* const* tiles_host, uint16_t* dst, int* non
                          const int* x0_host, const int* yb_host, const int* xb_host, int rows, int cols, int thp, int twp, int th, int tw,
                          int feather, int depth, spei_stream_t stream);
 
+/* ---- field I/O of the clip API's interlaced mode (video.deblur_clip(..., fields="split"); an extension beyond the reference, which
+ * knows progressive frames only) ----
+ * A woven frame [H][W][3] of even height H holds two fields of H / 2 rows: field p (0 = top, 1 = bottom) is its rows p, p + 2, ...
+ * (f[p::2]), the same W, the same depth.  Each parity is deblurred as a clip of its own, so a window runs as two parts of one shape,
+ * hp x wp = H / 2 and W rounded up to multiples of 20.  Field order (top or bottom field first) does not enter.
+ * spei_fields_u8_in: src one packed uint8 [H][W][3] frame -> for p = 0, 1 the fp32 planes [3][hp][wp] at dst + p * field_stride
+ *   (floats; field_stride >= 3 * hp * wp and a multiple of 4, dst 16-byte aligned), bit-identical to spei_frames_u8_in on the packed
+ *   copy of field p, its reflect pad included: the pad is the FIELD's, padded field row H / 2 + j reads field row H / 2 - 2 - j
+ *   (frame row 2 (H / 2 - 2 - j) + p), which needs hp - H / 2 < H / 2 and wp - W < W.  One launch.
+ * spei_fields_u16_in: the same on a packed uint16 frame of `depth` 10 or 12, bit-identical to spei_frames_u16_in on the field.
+ * spei_fields_u8_out: top, bottom = the fp32 planes [3][hp][wp] of field 0 and field 1 -> dst packed uint8 [H][W][3]: row 2 r + p is
+ *   row r of spei_frame_u8_out's H / 2 x W crop of plane p.  nonfinite (or NULL): one int, cleared on the stream, then nonzero iff a
+ *   value of EITHER field's crop was a NaN or an infinity (that sample is 0); what a plane holds in its pad is never read.  One
+ *   launch, every sample of dst written once.
+ * spei_fields_u16_out: the same with spei_frame_u16_out's values for `depth` 10 or 12, dst packed uint16.
+ * Non-zero before anything is launched: a null pointer, an odd H, a frame beyond the size bound of spei_frames_u8_in, a field that
+ * cannot reflect-pad, planes smaller than the crop, a misaligned pointer or stride, an unknown depth. */
+int spei_fields_u8_in(const unsigned char* src, int H, int W, float* dst, int64_t field_stride, spei_stream_t stream);
+int spei_fields_u16_in(const uint16_t* src, int H, int W, float* dst, int64_t field_stride, int depth, spei_stream_t stream);
+int spei_fields_u8_out(const float* top, const float* bottom, unsigned char* dst, int* nonfinite, int H, int W, int hp, int wp,
+                       spei_stream_t stream);
+int spei_fields_u16_out(const float* top, const float* bottom, uint16_t* dst, int* nonfinite, int H, int W, int hp, int wp, int depth,
+                        spei_stream_t stream);
+
 /* ---- geometric self-ensemble of the clip API (speinet_amd/ensemble.py, video.deblur_clip(..., ensemble=); the reference's
  * forward_x8, util/network_utils.py:308-341, which it never calls) ----
  * Member `op` in 0..7, the reference's enumeration: bit 0 reverses the columns of a plane (a[:, ::-1], its 'v'), bit 1 reverses the
@@ -739,6 +763,25 @@ int spei_planar_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* 
                            int depth, spei_stream_t stream);
 int spei_rgb_u16_to_planar(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
                            spei_stream_t stream);
+
+/* Interlaced frames (the clip API's fields="split"): the conversions above on a woven frame, any of the five layouts, with the
+ * arguments and checks of the entries above.  Field p (0, 1) of a frame is a planar picture of its own: the Y rows p :: 2 and, for
+ * 4:2:0, the chroma-plane rows p :: 2 (chroma row j of the frame's plane belongs to field j & 1), so a field of a 4:2:0 frame has
+ * H / 2 luma and H / 4 chroma rows and H must be a multiple of 4 (anything else is refused with a message that names H).
+ * spei_yuv_fields_to_rgb_u8 / _u16: the woven RGB frame whose rows p :: 2 are spei_yuv_to_rgb_u8 / _u16 applied to field p's picture:
+ *   with r = y >> 1 the field row of frame row y, the 3 : 1 row rule takes field chroma rows j = r >> 1 and j - 1 (r even) or j + 1
+ *   (r odd), clamped to 0 .. H / 4 - 1, which are the plane's rows 2 j + p: no chroma of one field reaches a row of the other.
+ * spei_rgb_u8_to_yuv_fields / _u16: the planar frame whose field pictures are spei_rgb_u8_to_yuv / _u16 of the RGB rows p :: 2: Y per
+ *   pixel; chroma-plane row 2 j + p from RGB rows 4 j + p and 4 j + p + 2.
+ * 4:4:4, 4:2:2 and mono convert every row on its own: there the result is that of the progressive entries, bit for bit, any H. */
+int spei_yuv_fields_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W, int layout,
+                              int matrix, int range, spei_stream_t stream);
+int spei_rgb_u8_to_yuv_fields(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
+                              spei_stream_t stream);
+int spei_yuv_fields_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout, int matrix,
+                               int range, int depth, spei_stream_t stream);
+int spei_rgb_u16_to_yuv_fields(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
+                               spei_stream_t stream);
 
 /* ---- training on a dataset (speinet_amd/data.py, speinet_amd/fit.py) ---- */
 

@@ -1,6 +1,7 @@
 """The clip as a source, for the clip loop (speinet_amd.video), the labelling pass (speinet_amd.detector), the loaders (speinet_amd.data),
 blur synthesis (speinet_amd.blurset) and the harness (speinet_amd.inference).  `frames_of` validates a clip in any form the clip API takes
-and returns it as `Frames`: frame i on the host or on the device, a rectangle of every frame (`view`), a subset of the frames (`sample`);
+and returns it as `Frames`: frame i on the host or on the device, a rectangle of every frame (`view`), a subset of the frames (`sample`),
+one field of every interlaced frame (`woven`, `field`);
 a clip of unknown length (a `y4m.Y4MStream`, an iterator of frames) as `StreamFrames`, the same interface over a bounded ring of frames
 that one reader thread fills (`FrameRing`).
 Frames cross PCIe as uint8 (a deep clip's as its bytes) from page-locked staging buffers (`FrameCache`) and are decoded, for image paths, on
@@ -170,7 +171,9 @@ class Frames:
     (`yuv`: its (layout, matrix, range); `items` the `Y4MReader`) is the exception: `host` returns the frame's planar bytes as they
     are in the file, and `rgb` turns uploaded planar frames into the cropped RGB frames on the device.  `depth`: 8 (uint8 frames), or
     10 / 12 (uint16 frames: `dtype`; the planar bytes of a deep y4m clip are still uint8, two per sample).  `view` is the same clip
-    seen through a rectangle (the region of interest: the analysis pass is handed that view), `sample` a subset of its frames."""
+    seen through a rectangle (the region of interest: the analysis pass is handed that view), `sample` a subset of its frames.
+    `woven` is the same clip read as interlaced frames, two woven fields each (`interlaced`: the `rgb` of a y4m clip then goes through
+    the field-aware conversion), and `field(p)` its clip of the fields of parity p, frame rows p::2: a view with a row step of 2."""
 
     def __init__(self, items, T: int, H: int, W: int, paths: bool, crop: bool = False, yuv=None, depth: int = 8):
         self.items, self.T, self.paths, self.src, self.yuv, self.depth = items, T, paths, (H, W), yuv, depth
@@ -178,6 +181,8 @@ class Frames:
         self.H, self.W = (H - H % 20, W - W % 20) if crop else (H, W)
         self.y0 = self.x0 = 0            # the origin of the H x W view in the source frames (`view`: a rectangle)
         self.index = None                # the source frame of each of the T frames (`sample`: a subset); None: all, in order
+        self.ystep = 1                   # the rows of the view are the source rows y0, y0 + ystep, ... (`field`: 2)
+        self.interlaced = False          # the frames are two woven fields each (`woven`, `field`)
 
     def view(self, rect) -> "Frames":
         """The same clip seen through the rectangle (y0, x0, h, w) of this view: `device`, `host` and `rgb` hand out the cropped
@@ -186,6 +191,22 @@ class Frames:
         assert 0 <= y0 and 0 <= x0 and y0 + h <= self.H and x0 + w <= self.W
         v = copy.copy(self)
         v.y0, v.x0, v.H, v.W = self.y0 + y0, self.x0 + x0, h, w
+        return v
+
+    def woven(self) -> "Frames":
+        """The same clip with its frames read as two woven fields each (field p: rows p::2).  H and W are still the frame's; what
+        changes is `rgb`: the planar frames of a y4m clip go through `ops.yuv_to_rgb_u8(..., fields=True)` (or `_u16`), in which no
+        chroma row of one field reaches the other.  Nothing is copied."""
+        v = copy.copy(self)
+        v.interlaced = True
+        return v
+
+    def field(self, p: int) -> "Frames":
+        """The clip of the fields of parity p (0 = top, 1 = bottom) of this clip's frames: `device`, `host` and `rgb` hand out the
+        rows p::2, H is half the frame's (which must be even).  A strided view: nothing is copied on the host."""
+        assert p in (0, 1) and self.ystep == 1 and self.H % 2 == 0
+        v = self.woven()
+        v.y0, v.ystep, v.H = self.y0 + p, 2, self.H // 2
         return v
 
     def sample(self, index) -> "Frames":
@@ -199,7 +220,7 @@ class Frames:
         return i if self.index is None else self.index[i]
 
     def _crop(self, f):
-        return f[..., self.y0:self.y0 + self.H, self.x0:self.x0 + self.W, :]
+        return f[..., self.y0:self.y0 + self.H * self.ystep:self.ystep, self.x0:self.x0 + self.W, :]
 
     def upto(self, i: int) -> int:
         """How many of the first i frames exist: min(i, T).  A stream (`StreamFrames`) waits for frame i - 1 or its end."""
@@ -217,14 +238,17 @@ class Frames:
     def rgb(self, planar: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Planar frames [N, frame_bytes] (uint8: the file's bytes) of a y4m clip on the device -> uint8 [N,H,W,3] there
         (`ops.yuv_to_rgb_u8`), or uint16 for a deep clip (`ops.yuv_to_rgb_u16` on the bytes viewed as words); cropped after the
-        conversion, into the contiguous `out` if given."""
+        conversion, into the contiguous `out` if given.  An interlaced 4:2:0 clip (`woven`, `field`) goes through the field-aware
+        conversion; the other layouts convert row by row, so their progressive launch is the field-aware one."""
+        fields = self.interlaced and self.yuv[0] in (y4m.CENTER, y4m.LEFT)
         if self.depth == 8:
-            convert = ops.yuv_to_rgb_u8
+            def convert(p, h, w, *how, out=None):
+                return ops.yuv_to_rgb_u8(p, h, w, *how, out=out, fields=fields)
         else:
             planar = planar.view(torch.uint16)
 
             def convert(p, h, w, *how, out=None):
-                return ops.yuv_to_rgb_u16(p, h, w, *how, self.depth, out=out)
+                return ops.yuv_to_rgb_u16(p, h, w, *how, self.depth, out=out, fields=fields)
         if (self.H, self.W) == self.src:
             return convert(planar, self.H, self.W, *self.yuv, out=out)
         full = self._crop(convert(planar, *self.src, *self.yuv))
@@ -327,7 +351,7 @@ class StreamFrames(Frames):
     """A clip whose length is not known before its last frame: `Frames` over a `FrameRing`.  `T` is None until the stream has ended.
     `source`: a `y4m.Y4MStream` (`host(i)` is then the frame's planar bytes and `yuv` its (layout, matrix, range), as for a reader),
     or an iterator of uint8 [H,W,3] frames (uint16 with `depth`: arrays or host tensors), whose first frame `frames_of` has taken
-    already (`first`).  `host`, `rgb`, `view`, `depth`, `dtype` and `yuv` are `Frames`'; `upto(i)` waits for frame i - 1 (or the
+    already (`first`).  `host`, `rgb`, `view`, `woven`, `field`, `depth`, `dtype` and `yuv` are `Frames`'; `upto(i)` waits for frame i - 1 (or the
     end), `release(lo)` gives up every frame below `lo`, `ready(i)` does not wait.  `capacity`: the ring's slots; the clip loop sets
     it from its look-ahead (`reserve`) before the first frame is asked for, which is when the reader thread starts."""
 

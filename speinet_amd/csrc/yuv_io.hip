@@ -6,6 +6,10 @@
 //   spei_rgb_u8_to_yuv — one packed uint8 [H][W][3] RGB frame (what spei_frame_u8_out makes) -> one planar frame.
 //   spei_planar_to_rgb_u8, spei_rgb_u8_to_planar — the same two for 4:2:2 (U, V: [H][ceil(W/2)] each, co-sited with the even column
 //                        of their own row) and mono (the Y plane alone) frames: two more LAYOUT values of the same kernels.
+//   spei_yuv_fields_to_rgb_u8, spei_rgb_u8_to_yuv_fields (and _u16) — the same on an INTERLACED frame of any layout (the clip API's
+//                        fields="split"): the woven frame whose field p (rows p :: 2) is the conversion of field p's own planar
+//                        picture, Y rows p :: 2 and, for 4:2:0, chroma-plane rows p :: 2 (H % 4 == 0), so no chroma of one instant
+//                        reaches a row of the other.  The same kernels with a row pitch of 2 and the parity as offset (`fld`).
 //
 // Integer arithmetic only: the result is defined bit for bit and depends on neither the launch shape nor the access path.  `>>` is
 // an arithmetic shift (it floors).  Clipping is to [0,255] for RGB and full range, to [16,235] (Y) and [16,240] (U, V) for limited.
@@ -86,11 +90,22 @@ __host__ __device__ __forceinline__ int64_t chroma_size(int H, int W, int layout
     return (int64_t)(layout == SPEI_YUV_422 ? H : (H + 1) >> 1) * ((W + 1) >> 1);
 }
 
+// Rows of a 4:2:0 picture, progressive (fld = 0) or the two woven fields of an interlaced one (fld = 1; H % 4 == 0).  Field p = y & 1
+// of frame row y is a planar picture of its own: its Y rows are the frame's rows p :: 2 and its chroma rows the chroma plane's rows
+// p :: 2, so a row index of that picture has the pitch 1 << fld and the offset p in the frame's planes.  With fld = 0 every expression
+// below is the progressive one.
+//   chroma_rows — the chroma rows of the picture that the 3 : 1 row rule clamps to: ceil(H / 2), or H / 4 of a field
+//   chroma_row  — the chroma-plane row of chroma row j of the picture that frame row y belongs to
+//   next_row    — the frame row below frame row y in its picture, clamped to the picture's last row
+__host__ __device__ __forceinline__ int chroma_rows(int H, int fld) { return fld ? H >> 2 : (H + 1) >> 1; }
+__device__ __forceinline__ int chroma_row(int j, int y, int fld) { return (j << fld) + (y & fld); }
+__device__ __forceinline__ int next_row(int y, int H, int fld) { return y + 1 + fld < H ? y + 1 + fld : y; }
+
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const unsigned char* __restrict__ src, int64_t fstride,
                                                          unsigned char* __restrict__ dst, int H, int W, int64_t total, Coef k,
-                                                         int aligned) {
-    const int gw = (W + 3) >> 2, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
+                                                         int aligned, int fld) {
+    const int gw = (W + 3) >> 2, Hc = chroma_rows(H, fld), Wc = (W + 1) >> 1;
     const int64_t ysize = (int64_t)H * W, csize = chroma_size(H, W, LAYOUT);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / gw;                        // n * H + y
@@ -129,8 +144,8 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const unsigned char* __
             }
         } else {
             // chroma columns i0 - 1 .. i0 + 2 (clamped) serve the 4 pixels; rows first: 3 of row j, 1 of the other
-            const int j = y >> 1, jo = clip((y & 1) ? j + 1 : j - 1, 0, Hc - 1), i0 = x0 >> 1;
-            const int64_t rj = (int64_t)j * Wc, ro = (int64_t)jo * Wc;
+            const int fy = y >> fld, j = fy >> 1, jo = clip((fy & 1) ? j + 1 : j - 1, 0, Hc - 1), i0 = x0 >> 1;
+            const int64_t rj = (int64_t)chroma_row(j, y, fld) * Wc, ro = (int64_t)chroma_row(jo, y, fld) * Wc;
             int u[4], v[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -176,7 +191,8 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const unsigned char* __
 
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int H,
-                                                         int W, int64_t total, Coef k, int limited, int al_src, int al_y, int al_c) {
+                                                         int W, int64_t total, Coef k, int limited, int al_src, int al_y, int al_c,
+                                                         int fld) {
     const int gw = (W + 3) >> 2, Wc = (W + 1) >> 1;
     const int64_t ysize = (int64_t)H * W, csize = chroma_size(H, W, LAYOUT);
     constexpr bool TWO = LAYOUT != SPEI_YUV_422;           // a chroma sample spans two rows (4:2:0) or one
@@ -209,12 +225,12 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const unsigned char* __
         if (LAYOUT == SPEI_YUV_444) {
             store4(dst + ysize + (int64_t)y * W, x0, W, dword, U);
             store4(dst + 2 * ysize + (int64_t)y * W, x0, W, dword, V);
-        } else if (LAYOUT != SPEI_YUV_MONO && (!TWO || !(y & 1)) && !(g & 1)) {
+        } else if (LAYOUT != SPEI_YUV_MONO && (!TWO || !((y >> fld) & 1)) && !(g & 1)) {
             // chroma samples (j, i0 .. i0 + 3) of rows y, y + 1 (4:2:2: of row y alone) and columns x0 .. x0 + 7: s[ch][q] is the sum
             // over those rows of channel ch at column x0 - 1 + q, rows and columns clamped to the frame (q = 0 is the left neighbour
             // of LEFT and 4:2:2)
-            const int j = TWO ? y >> 1 : y, i0 = x0 >> 1;
-            const unsigned char* r1 = src + (int64_t)min(y + 1, H - 1) * W * 3;
+            const int j = TWO ? chroma_row(y >> fld >> 1, y, fld) : y, i0 = x0 >> 1;
+            const unsigned char* r1 = src + (int64_t)next_row(y, H, fld) * W * 3;
             int s[3][9];
             if (al_src && x0 + 8 <= W) {
                 const uint32_t* a = reinterpret_cast<const uint32_t*>(r0 + x0 * 3);
@@ -317,8 +333,8 @@ __device__ __forceinline__ int clip_deep(int64_t v, int D) { return (int)min(max
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void yuv_to_rgb_u16_kernel(const uint16_t* __restrict__ src, int64_t fstride,
                                                              uint16_t* __restrict__ dst, int H, int W, int64_t total, Coef k, int s,
-                                                             int aligned) {
-    const int gw = (W + 3) >> 2, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1, D = (256 << s) - 1;
+                                                             int aligned, int fld) {
+    const int gw = (W + 3) >> 2, Hc = chroma_rows(H, fld), Wc = (W + 1) >> 1, D = (256 << s) - 1;
     const int64_t ysize = (int64_t)H * W, csize = chroma_size(H, W, LAYOUT);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / gw;                        // n * H + y
@@ -355,8 +371,8 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_u16_kernel(const uint16_t* __r
                 V16[p] = (p & 1) ? 8 * (v[a] + v[a + 1]) : 16 * v[a];
             }
         } else {
-            const int j = y >> 1, jo = clip((y & 1) ? j + 1 : j - 1, 0, Hc - 1), i0 = x0 >> 1;
-            const int64_t rj = (int64_t)j * Wc, ro = (int64_t)jo * Wc;
+            const int fy = y >> fld, j = fy >> 1, jo = clip((fy & 1) ? j + 1 : j - 1, 0, Hc - 1), i0 = x0 >> 1;
+            const int64_t rj = (int64_t)chroma_row(j, y, fld) * Wc, ro = (int64_t)chroma_row(jo, y, fld) * Wc;
             int u[4], v[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -403,7 +419,8 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_u16_kernel(const uint16_t* __r
 
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void rgb_u16_to_yuv_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, int H, int W,
-                                                             int64_t total, Coef k, int limited, int s, int al_src, int al_y, int al_c) {
+                                                             int64_t total, Coef k, int limited, int s, int al_src, int al_y, int al_c,
+                                                             int fld) {
     const int gw = (W + 3) >> 2, Wc = (W + 1) >> 1, D = (256 << s) - 1, mid = 128 << s;
     const int64_t ysize = (int64_t)H * W, csize = chroma_size(H, W, LAYOUT);
     constexpr bool TWO = LAYOUT != SPEI_YUV_422;           // a chroma sample spans two rows (4:2:0) or one
@@ -428,12 +445,12 @@ __global__ __launch_bounds__(256) void rgb_u16_to_yuv_kernel(const uint16_t* __r
         if (LAYOUT == SPEI_YUV_444) {
             store4(dst + ysize + (int64_t)y * W, x0, W, wide, U);
             store4(dst + 2 * ysize + (int64_t)y * W, x0, W, wide, V);
-        } else if (LAYOUT != SPEI_YUV_MONO && (!TWO || !(y & 1)) && !(g & 1)) {
+        } else if (LAYOUT != SPEI_YUV_MONO && (!TWO || !((y >> fld) & 1)) && !(g & 1)) {
             // chroma samples (j, i0 .. i0 + 3) of rows y, y + 1 (4:2:2: of row y alone) and columns x0 .. x0 + 7: sm[ch][q] is the sum
             // over those rows of channel ch at column x0 - 1 + q, rows and columns clamped to the frame (q = 0 is the left neighbour
             // of LEFT and 4:2:2)
-            const int j = TWO ? y >> 1 : y, i0 = x0 >> 1;
-            const uint16_t* r1 = src + (int64_t)min(y + 1, H - 1) * W * 3;
+            const int j = TWO ? chroma_row(y >> fld >> 1, y, fld) : y, i0 = x0 >> 1;
+            const uint16_t* r1 = src + (int64_t)next_row(y, H, fld) * W * 3;
             int sm[3][9];
             if (al_src && x0 + 8 <= W) {
                 int a[12], b[12] = {};
@@ -486,6 +503,16 @@ inline bool known(int layout, int lo, int hi, int matrix, int range) {
            (range == SPEI_YUV_FULL || range == SPEI_YUV_LIMITED);
 }
 
+// `fields` of a call: 0 converts a progressive frame, 1 the woven fields of an interlaced one.  Only 4:2:0 has rows that depend on one
+// another, so only there do the kernels walk fields (fld = 1), and a field must have whole chroma rows: H % 4 == 0.  The other layouts
+// convert every row on its own: their fields are their rows, fld = 0
+inline int check_fields(const char* name, int fields, int layout, int H) {
+    SPEI_REQUIRE(!fields || layout > SPEI_YUV_420_LEFT || (H & 3) == 0, "%s: the fields of a 4:2:0 frame of H = %d rows have no whole "
+                 "chroma rows (H must be a multiple of 4: H / 2 rows per field, H / 4 chroma rows)", name, H);
+    return 0;
+}
+inline int field_pitch(int fields, int layout) { return fields && layout <= SPEI_YUV_420_LEFT ? 1 : 0; }
+
 inline Coef deep_coef(int depth, int matrix, int range) {
     return range == SPEI_YUV_FULL ? COEF[matrix][0] : COEF_DEEP[depth == 12][matrix];
 }
@@ -503,28 +530,32 @@ inline Coef deep_coef(int depth, int matrix, int range) {
 
 // The bodies of the entry points: `name` is the entry's, lo .. hi the layouts it takes.
 int to_rgb_u8(const char* name, int lo, int hi, const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W,
-              int layout, int matrix, int range, spei_stream_t stream) {
+              int layout, int matrix, int range, int fields, spei_stream_t stream) {
     SPEI_REQUIRE(src && dst, "%s: null pointer", name);
     SPEI_REQUIRE(N >= 1 && H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %d x %dx%d", name, N, H, W);
     SPEI_REQUIRE(known(layout, lo, hi, matrix, range), "%s: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", name, layout, matrix,
                  range);
+    if (check_fields(name, fields, layout, H)) return -1;
+    const int fld = field_pitch(fields, layout);
     SPEI_REQUIRE(N == 1 || frame_stride >= planar_bytes(H, W, layout), "%s: frame stride %lld < one %dx%d planar frame of %lld bytes", name,
                  (long long)frame_stride, H, W, (long long)planar_bytes(H, W, layout));
     const int aligned = (((uintptr_t)src | (uintptr_t)dst) & 3) == 0 && (N == 1 || (frame_stride & 3) == 0) && (W & 3) == 0;
     const int64_t total = (int64_t)N * H * ((W + 3) / 4);
     const Coef k = COEF[matrix][range];
     const dim3 grid(grid_for(total)), block(256);
-    SPEI_YUV_LAUNCH(yuv_to_rgb_kernel, layout, src, frame_stride, dst, H, W, total, k, aligned);
+    SPEI_YUV_LAUNCH(yuv_to_rgb_kernel, layout, src, frame_stride, dst, H, W, total, k, aligned, fld);
     SPEI_CHECK_LAUNCH(name);
     return 0;
 }
 
 int from_rgb_u8(const char* name, int lo, int hi, const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix,
-                int range, spei_stream_t stream) {
+                int range, int fields, spei_stream_t stream) {
     SPEI_REQUIRE(src && dst, "%s: null pointer", name);
     SPEI_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
     SPEI_REQUIRE(known(layout, lo, hi, matrix, range), "%s: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", name, layout, matrix,
                  range);
+    if (check_fields(name, fields, layout, H)) return -1;
+    const int fld = field_pitch(fields, layout);
     // rows of 3 W, W and ceil(W/2) bytes: 4-byte aligned when W % 4 == 0 (RGB, Y, and the 4:4:4 planes at H W and 2 H W) and, for
     // the 4:2:0 and 4:2:2 chroma planes, when W % 8 == 0
     const int al_src = ((uintptr_t)src & 3) == 0 && (W & 3) == 0;
@@ -534,17 +565,19 @@ int from_rgb_u8(const char* name, int lo, int hi, const unsigned char* src, unsi
     const Coef k = COEF[matrix][range];
     const int limited = range == SPEI_YUV_LIMITED;
     const dim3 grid(grid_for(total)), block(256);
-    SPEI_YUV_LAUNCH(rgb_to_yuv_kernel, layout, src, dst, H, W, total, k, limited, al_src, al_y, al_c);
+    SPEI_YUV_LAUNCH(rgb_to_yuv_kernel, layout, src, dst, H, W, total, k, limited, al_src, al_y, al_c, fld);
     SPEI_CHECK_LAUNCH(name);
     return 0;
 }
 
 int to_rgb_u16(const char* name, int lo, int hi, const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout,
-               int matrix, int range, int depth, spei_stream_t stream) {
+               int matrix, int range, int depth, int fields, spei_stream_t stream) {
     SPEI_REQUIRE(src && dst, "%s: null pointer", name);
     SPEI_REQUIRE(N >= 1 && H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %d x %dx%d", name, N, H, W);
     SPEI_REQUIRE(known(layout, lo, hi, matrix, range), "%s: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", name, layout, matrix,
                  range);
+    if (check_fields(name, fields, layout, H)) return -1;
+    const int fld = field_pitch(fields, layout);
     SPEI_REQUIRE(depth == 10 || depth == 12, "%s: unknown depth %d (10 or 12)", name, depth);
     SPEI_REQUIRE(N == 1 || frame_stride >= 2 * planar_bytes(H, W, layout), "%s: frame stride %lld < one %dx%d planar frame of %lld bytes",
                  name, (long long)frame_stride, H, W, (long long)(2 * planar_bytes(H, W, layout)));
@@ -555,17 +588,19 @@ int to_rgb_u16(const char* name, int lo, int hi, const uint16_t* src, int64_t fr
     const Coef k = deep_coef(depth, matrix, range);
     const int s = depth - 8;
     const dim3 grid(grid_for(total)), block(256);
-    SPEI_YUV_LAUNCH(yuv_to_rgb_u16_kernel, layout, src, fstride, dst, H, W, total, k, s, aligned);
+    SPEI_YUV_LAUNCH(yuv_to_rgb_u16_kernel, layout, src, fstride, dst, H, W, total, k, s, aligned, fld);
     SPEI_CHECK_LAUNCH(name);
     return 0;
 }
 
 int from_rgb_u16(const char* name, int lo, int hi, const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range,
-                 int depth, spei_stream_t stream) {
+                 int depth, int fields, spei_stream_t stream) {
     SPEI_REQUIRE(src && dst, "%s: null pointer", name);
     SPEI_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W * 3 < (1ll << 31), "%s: bad frame shape %dx%d", name, H, W);
     SPEI_REQUIRE(known(layout, lo, hi, matrix, range), "%s: unknown layout %d, matrix %d or range %d (SPEI_YUV_*)", name, layout, matrix,
                  range);
+    if (check_fields(name, fields, layout, H)) return -1;
+    const int fld = field_pitch(fields, layout);
     SPEI_REQUIRE(depth == 10 || depth == 12, "%s: unknown depth %d (10 or 12)", name, depth);
     SPEI_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 1) == 0, "%s: src and dst must be 2-byte aligned", name);
     // rows of 6 W, 2 W and 2 ceil(W/2) bytes: 8-byte aligned when W % 4 == 0 (RGB, Y, and the 4:4:4 planes) and, for the 4:2:0 and
@@ -577,7 +612,7 @@ int from_rgb_u16(const char* name, int lo, int hi, const uint16_t* src, uint16_t
     const Coef k = deep_coef(depth, matrix, range);
     const int limited = range == SPEI_YUV_LIMITED, s = depth - 8;
     const dim3 grid(grid_for(total)), block(256);
-    SPEI_YUV_LAUNCH(rgb_u16_to_yuv_kernel, layout, src, dst, H, W, total, k, limited, s, al_src, al_y, al_c);
+    SPEI_YUV_LAUNCH(rgb_u16_to_yuv_kernel, layout, src, dst, H, W, total, k, limited, s, al_src, al_y, al_c, fld);
     SPEI_CHECK_LAUNCH(name);
     return 0;
 }
@@ -586,43 +621,69 @@ int from_rgb_u16(const char* name, int lo, int hi, const uint16_t* src, uint16_t
 
 extern "C" int spei_yuv_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W, int layout,
                                   int matrix, int range, spei_stream_t stream) {
-    return to_rgb_u8("spei_yuv_to_rgb_u8", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, frame_stride, dst, N, H, W, layout, matrix, range, stream);
+    return to_rgb_u8("spei_yuv_to_rgb_u8", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, frame_stride, dst, N, H, W, layout, matrix, range, 0, stream);
 }
 
 extern "C" int spei_rgb_u8_to_yuv(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
                                   spei_stream_t stream) {
-    return from_rgb_u8("spei_rgb_u8_to_yuv", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, dst, H, W, layout, matrix, range, stream);
+    return from_rgb_u8("spei_rgb_u8_to_yuv", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, dst, H, W, layout, matrix, range, 0, stream);
 }
 
 extern "C" int spei_yuv_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout, int matrix,
                                    int range, int depth, spei_stream_t stream) {
     return to_rgb_u16("spei_yuv_to_rgb_u16", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, frame_stride, dst, N, H, W, layout, matrix, range,
-                      depth, stream);
+                      depth, 0, stream);
 }
 
 extern "C" int spei_rgb_u16_to_yuv(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
                                    spei_stream_t stream) {
-    return from_rgb_u16("spei_rgb_u16_to_yuv", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, dst, H, W, layout, matrix, range, depth, stream);
+    return from_rgb_u16("spei_rgb_u16_to_yuv", SPEI_YUV_420_CENTER, SPEI_YUV_444, src, dst, H, W, layout, matrix, range, depth, 0, stream);
 }
 
 // ---- 4:2:2 and mono: the same four bodies on SPEI_YUV_422 and SPEI_YUV_MONO ------------------------------------------------------
 extern "C" int spei_planar_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W, int layout,
                                      int matrix, int range, spei_stream_t stream) {
-    return to_rgb_u8("spei_planar_to_rgb_u8", SPEI_YUV_422, SPEI_YUV_MONO, src, frame_stride, dst, N, H, W, layout, matrix, range, stream);
+    return to_rgb_u8("spei_planar_to_rgb_u8", SPEI_YUV_422, SPEI_YUV_MONO, src, frame_stride, dst, N, H, W, layout, matrix, range, 0, stream);
 }
 
 extern "C" int spei_rgb_u8_to_planar(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
                                      spei_stream_t stream) {
-    return from_rgb_u8("spei_rgb_u8_to_planar", SPEI_YUV_422, SPEI_YUV_MONO, src, dst, H, W, layout, matrix, range, stream);
+    return from_rgb_u8("spei_rgb_u8_to_planar", SPEI_YUV_422, SPEI_YUV_MONO, src, dst, H, W, layout, matrix, range, 0, stream);
 }
 
 extern "C" int spei_planar_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout, int matrix,
                                       int range, int depth, spei_stream_t stream) {
     return to_rgb_u16("spei_planar_to_rgb_u16", SPEI_YUV_422, SPEI_YUV_MONO, src, frame_stride, dst, N, H, W, layout, matrix, range, depth,
-                      stream);
+                      0, stream);
 }
 
 extern "C" int spei_rgb_u16_to_planar(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
                                       spei_stream_t stream) {
-    return from_rgb_u16("spei_rgb_u16_to_planar", SPEI_YUV_422, SPEI_YUV_MONO, src, dst, H, W, layout, matrix, range, depth, stream);
+    return from_rgb_u16("spei_rgb_u16_to_planar", SPEI_YUV_422, SPEI_YUV_MONO, src, dst, H, W, layout, matrix, range, depth, 0, stream);
+}
+
+// ---- interlaced frames: the same four bodies on the woven fields, every layout ---------------------------------------------------
+// Field p of the result is the conversion above of field p's own planar picture (Y rows p :: 2 and, for 4:2:0, chroma-plane rows
+// p :: 2); 4:4:4, 4:2:2 and mono convert row by row, so there the result is the progressive one.
+extern "C" int spei_yuv_fields_to_rgb_u8(const unsigned char* src, int64_t frame_stride, unsigned char* dst, int N, int H, int W,
+                                         int layout, int matrix, int range, spei_stream_t stream) {
+    return to_rgb_u8("spei_yuv_fields_to_rgb_u8", SPEI_YUV_420_CENTER, SPEI_YUV_MONO, src, frame_stride, dst, N, H, W, layout, matrix, range,
+                     1, stream);
+}
+
+extern "C" int spei_rgb_u8_to_yuv_fields(const unsigned char* src, unsigned char* dst, int H, int W, int layout, int matrix, int range,
+                                         spei_stream_t stream) {
+    return from_rgb_u8("spei_rgb_u8_to_yuv_fields", SPEI_YUV_420_CENTER, SPEI_YUV_MONO, src, dst, H, W, layout, matrix, range, 1, stream);
+}
+
+extern "C" int spei_yuv_fields_to_rgb_u16(const uint16_t* src, int64_t frame_stride, uint16_t* dst, int N, int H, int W, int layout,
+                                          int matrix, int range, int depth, spei_stream_t stream) {
+    return to_rgb_u16("spei_yuv_fields_to_rgb_u16", SPEI_YUV_420_CENTER, SPEI_YUV_MONO, src, frame_stride, dst, N, H, W, layout, matrix,
+                      range, depth, 1, stream);
+}
+
+extern "C" int spei_rgb_u16_to_yuv_fields(const uint16_t* src, uint16_t* dst, int H, int W, int layout, int matrix, int range, int depth,
+                                          spei_stream_t stream) {
+    return from_rgb_u16("spei_rgb_u16_to_yuv_fields", SPEI_YUV_420_CENTER, SPEI_YUV_MONO, src, dst, H, W, layout, matrix, range, depth, 1,
+                        stream);
 }

@@ -534,6 +534,69 @@ def tiles_out(tiles, plan, out_depth: int = 8, out: Optional[torch.Tensor] = Non
     return out
 
 
+def fields_in(frame: torch.Tensor, out: torch.Tensor, depth: Optional[int] = None) -> torch.Tensor:
+    """One packed woven frame [H,W,3] on the device (H even), uint8 (`depth` None) or uint16 of `depth` 10 or 12 bits -> both fields
+    as fp32 planes in `out` [2, 3, hp, wp], hp / wp = H / 2 and W rounded up to multiples of 20: field p is bit-identical to
+    `frames_u8_in` / `frames_u16_in` on frame[p::2].contiguous(), the field's own reflect pad included.  `out` may be a view with any
+    field stride (a multiple of 4 floats) whose fields are contiguous, such as x[:, j] of the window inputs [2, n_seq + 2, 3, hp, wp]
+    of both fields.  One launch on the current stream (csrc/field_io.hip), no host sync."""
+    deep = frame.dtype == torch.uint16
+    assert frame.is_cuda and frame.dtype in (torch.uint8, torch.uint16) and frame.dim() == 3 and frame.shape[2] == 3 and frame.is_contiguous()
+    if deep:
+        depth = _depth(depth)
+    elif depth is not None:
+        raise ValueError(f"depth= applies to uint16 frames only; the frame is {frame.dtype}")
+    h, w = frame.shape[:2]
+    if h % 2:
+        raise ValueError(f"a frame of {h} rows does not split into two fields: H must be even")
+    hp, wp = padded_size(h // 2), padded_size(w)
+    assert out.is_cuda and out.device == frame.device and out.dtype == torch.float32 and tuple(out.shape) == (2, 3, hp, wp)
+    assert out.stride()[1:] == (hp * wp, wp, 1), "every field of out must be contiguous (any field stride)"
+    lib = _lib.lib()
+    with torch.cuda.device(frame.device):
+        st = C.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)
+        if deep:
+            _lib.check(lib.spei_fields_u16_in(_vp(frame.data_ptr()), h, w, _vp(out.data_ptr()), out.stride(0), depth, st), "spei_fields_u16_in")
+        else:
+            _lib.check(lib.spei_fields_u8_in(_vp(frame.data_ptr()), h, w, _vp(out.data_ptr()), out.stride(0), st), "spei_fields_u8_in")
+    return out
+
+
+def fields_out(fields, h: int, w: int, out_depth: int = 8, out: Optional[torch.Tensor] = None,
+               nonfinite: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The two fields of a frame (contiguous fp32 [3,hp,wp] tensors on one device: top, bottom) -> the woven frame, uint8 [h,w,3] for
+    `out_depth` 8 and uint16 for 10 and 12 (h even): row 2 r + p is row r of `frame_u8_out` / `frame_u16_out`'s h / 2 x w crop of
+    field p.  `out` (optional): the packed destination.  `nonfinite` (optional): an int32 device tensor whose first element becomes
+    nonzero iff either field's crop held a NaN or an infinity (that sample is 0).  One launch on the current stream
+    (csrc/field_io.hip), no host sync."""
+    top, bottom = fields
+    dev = top.device
+    for t in (top, bottom):
+        assert t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.dim() == 3 and t.shape == top.shape and t.shape[0] == 3
+        assert t.is_contiguous()
+    if out_depth not in y4m.DEPTHS:
+        raise ValueError(f"out_depth must be 8, 10 or 12, got {out_depth!r}")
+    if h % 2:
+        raise ValueError(f"a frame of {h} rows is not the weave of two fields: H must be even")
+    dtype = torch.uint8 if out_depth == 8 else torch.uint16
+    hp, wp = top.shape[1:]
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=dtype, device=dev)
+    assert out.device == dev and out.dtype == dtype and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
+    assert nonfinite is None or (nonfinite.device == dev and nonfinite.dtype == torch.int32 and nonfinite.numel() >= 1)
+    flag = _vp(nonfinite.data_ptr() if nonfinite is not None else 0)
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if out_depth == 8:
+            _lib.check(lib.spei_fields_u8_out(_vp(top.data_ptr()), _vp(bottom.data_ptr()), _vp(out.data_ptr()), flag, h, w, hp, wp, st),
+                       "spei_fields_u8_out")
+        else:
+            _lib.check(lib.spei_fields_u16_out(_vp(top.data_ptr()), _vp(bottom.data_ptr()), _vp(out.data_ptr()), flag, h, w, hp, wp,
+                                               out_depth, st), "spei_fields_u16_out")
+    return out
+
+
 ROI_FEATHER_MAX = 200
 
 
@@ -735,18 +798,23 @@ def yuv_frame_bytes(h: int, w: int, layout: int) -> int:
     return y4m.frame_bytes(h, w, layout)
 
 
-def _yuv_entry(layout: int, name: str, planar: str) -> str:
+def _yuv_entry(layout: int, name: str, planar: str, fields: bool = False) -> str:
     """The C-ABI entry of a conversion for a layout: `name` (spei_yuv_* / spei_*_to_yuv) takes 4:2:0 and 4:4:4, `planar` 4:2:2 and
-    mono (csrc/yuv_io.hip: one kernel template behind both)."""
+    mono (csrc/yuv_io.hip: one kernel template behind both).  `fields`: the entry for a woven interlaced frame, which takes every
+    layout (spei_yuv_fields_to_rgb_* / spei_rgb_*_to_yuv_fields: `name` with `yuv` read as `yuv_fields`)."""
+    if fields:
+        return name.replace("yuv", "yuv_fields")
     return planar if layout in (y4m.P422, y4m.MONO) else name
 
 
 def yuv_to_rgb_u8(planar: torch.Tensor, h: int, w: int, layout: int, matrix: int, range: int,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, fields: bool = False) -> torch.Tensor:
     """Planar uint8 YUV frames on the device, [N, frame_bytes] (rows any stride apart) or one [frame_bytes], as in a y4m FRAME payload
     -> packed RGB uint8 [N,h,w,3] (csrc/yuv_io.hip: integer arithmetic, defined bit for bit in include/speinet_hip.h).  `layout`,
     `matrix`, `range`: the constants of speinet_amd.y4m (SPEI_YUV_*; P422 and MONO go to spei_planar_to_rgb_u8).  `out` (optional): a contiguous uint8 [N,h,w,3] destination.
-    One launch on the current stream, no host sync."""
+    `fields`: the frames are interlaced, two woven fields each (spei_yuv_fields_to_rgb_u8): field p of the result, its rows p::2, is
+    this conversion of field p's own planar picture (Y rows p::2 and, for 4:2:0, chroma-plane rows p::2; h % 4 == 0 there); the other
+    layouts convert row by row and give the progressive result.  One launch on the current stream, no host sync."""
     assert planar.is_cuda and planar.dtype == torch.uint8 and planar.dim() in (1, 2)
     fr = planar if planar.dim() == 2 else planar.unsqueeze(0)
     n, nb = fr.shape
@@ -758,15 +826,17 @@ def yuv_to_rgb_u8(planar: torch.Tensor, h: int, w: int, layout: int, matrix: int
     lib = _lib.lib()
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        entry = _yuv_entry(layout, "spei_yuv_to_rgb_u8", "spei_planar_to_rgb_u8")
+        entry = _yuv_entry(layout, "spei_yuv_to_rgb_u8", "spei_planar_to_rgb_u8", fields)
         _lib.check(getattr(lib, entry)(_vp(fr.data_ptr()), fr.stride(0), _vp(out.data_ptr()), n, h, w, layout, matrix, range, st), entry)
     return out
 
 
-def rgb_u8_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def rgb_u8_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, out: Optional[torch.Tensor] = None,
+                  fields: bool = False) -> torch.Tensor:
     """One packed RGB uint8 frame [h,w,3] on the device -> its planar YUV frame, uint8 [frame_bytes], a y4m FRAME payload
     (csrc/yuv_io.hip; the inverse definition of `yuv_to_rgb_u8`).  `out` (optional): a contiguous uint8 [frame_bytes] destination.
-    One launch on the current stream, no host sync."""
+    `fields`: the frame is two woven fields (spei_rgb_u8_to_yuv_fields): field p of the planar frame is this conversion of the RGB
+    rows p::2, as in `yuv_to_rgb_u8`.  One launch on the current stream, no host sync."""
     assert rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.is_contiguous()
     h, w = rgb.shape[:2]
     nb = yuv_frame_bytes(h, w, layout)
@@ -777,17 +847,18 @@ def rgb_u8_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, out: 
     lib = _lib.lib()
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        entry = _yuv_entry(layout, "spei_rgb_u8_to_yuv", "spei_rgb_u8_to_planar")
+        entry = _yuv_entry(layout, "spei_rgb_u8_to_yuv", "spei_rgb_u8_to_planar", fields)
         _lib.check(getattr(lib, entry)(_vp(rgb.data_ptr()), _vp(out.data_ptr()), h, w, layout, matrix, range, st), entry)
     return out
 
 
 def yuv_to_rgb_u16(planar: torch.Tensor, h: int, w: int, layout: int, matrix: int, range: int, depth: int,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, fields: bool = False) -> torch.Tensor:
     """`yuv_to_rgb_u8` for deep frames: planar uint16 YUV frames of `depth` 10 or 12 bits on the device, [N, frame samples] (rows any
     stride apart) or one [frame samples] (`yuv_frame_bytes(h, w, layout)` samples: a deep y4m FRAME payload viewed as uint16) ->
     packed RGB uint16 [N,h,w,3] (csrc/yuv_io.hip; the deep rule of include/speinet_hip.h).  `out` (optional): a contiguous uint16
-    [N,h,w,3] destination.  One launch on the current stream, no host sync."""
+    [N,h,w,3] destination.  `fields`: as in `yuv_to_rgb_u8` (spei_yuv_fields_to_rgb_u16).  One launch on the current stream, no host
+    sync."""
     assert planar.is_cuda and planar.dtype == torch.uint16 and planar.dim() in (1, 2)
     depth = _depth(depth)
     fr = planar if planar.dim() == 2 else planar.unsqueeze(0)
@@ -800,16 +871,17 @@ def yuv_to_rgb_u16(planar: torch.Tensor, h: int, w: int, layout: int, matrix: in
     lib = _lib.lib()
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        entry = _yuv_entry(layout, "spei_yuv_to_rgb_u16", "spei_planar_to_rgb_u16")
+        entry = _yuv_entry(layout, "spei_yuv_to_rgb_u16", "spei_planar_to_rgb_u16", fields)
         _lib.check(getattr(lib, entry)(_vp(fr.data_ptr()), 2 * fr.stride(0), _vp(out.data_ptr()), n, h, w, layout, matrix, range, depth, st),
                    entry)
     return out
 
 
-def rgb_u16_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, depth: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def rgb_u16_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, depth: int, out: Optional[torch.Tensor] = None,
+                   fields: bool = False) -> torch.Tensor:
     """`rgb_u8_to_yuv` for deep frames: one packed RGB uint16 frame [h,w,3] of `depth` 10 or 12 bits on the device -> its planar YUV
     frame, uint16 [frame samples], whose bytes are a deep y4m FRAME payload.  `out` (optional): a contiguous uint16 destination.
-    One launch on the current stream, no host sync."""
+    `fields`: as in `rgb_u8_to_yuv` (spei_rgb_u16_to_yuv_fields).  One launch on the current stream, no host sync."""
     assert rgb.is_cuda and rgb.dtype == torch.uint16 and rgb.dim() == 3 and rgb.shape[2] == 3 and rgb.is_contiguous()
     depth = _depth(depth)
     h, w = rgb.shape[:2]
@@ -821,7 +893,7 @@ def rgb_u16_to_yuv(rgb: torch.Tensor, layout: int, matrix: int, range: int, dept
     lib = _lib.lib()
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        entry = _yuv_entry(layout, "spei_rgb_u16_to_yuv", "spei_rgb_u16_to_planar")
+        entry = _yuv_entry(layout, "spei_rgb_u16_to_yuv", "spei_rgb_u16_to_planar", fields)
         _lib.check(getattr(lib, entry)(_vp(rgb.data_ptr()), _vp(out.data_ptr()), h, w, layout, matrix, range, depth, st), entry)
     return out
 

@@ -7,6 +7,7 @@
                                 [--chroma 420jpeg|420mpeg2|422|444|mono] [--out_chroma 420jpeg|420mpeg2|422|444|mono]
                                 [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N] [--ensemble 1|2|4|8]
                                 [--roi none|auto|Y,X,H,W] [--roi_feather N] [--stream [--horizon N]] [--sharp deblur|keep]
+                                [--fields auto|progressive|split]
 
 (`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; by default stdin is spooled to a temporary
 file on disk before the first frame is deblurred, with `--stream` it is deblurred as it arrives, see `main`)
@@ -62,6 +63,16 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     for byte, when the output has the input's chroma layout, depth and range.  An extension beyond the reference, which deblurs every
     frame; no trained checkpoint exists here, so nothing is claimed about quality, nor about a visible step between a kept frame and
     its deblurred neighbours.  Off by default.
+  * interlaced clips (`fields="split"`, `--fields`; csrc/field_io.hip, the field entries of csrc/yuv_io.hip): a frame of even height
+    is two fields, field p its rows p::2, two different instants.  Each parity is deblurred as a clip of its own: frame k of the
+    result has, in its rows p::2, frame k of `deblur_clip` on the clip of the fields of parity p, bit for bit, both under ONE plan,
+    the top-field clip's labels and cuts (or the caller's).  A window runs as two parts of one shape (H / 2 x W, each field with its
+    own reflect pad), one launch splits a frame into both fields' planes (`ops.fields_in`) and one weaves the two outputs into the
+    frame (`ops.fields_out`); the analysis pass sees the top-field clip (`Frames.field(0)`), and a 4:2:0 y4m clip is converted field
+    by field (`ops.yuv_to_rgb_u8(..., fields=True)`), so no chroma of one instant reaches the other.  Same-parity windows have
+    frame-rate spacing and no half-line bob between neighbours (one clip of 2T alternating fields would bob: rejected); field order
+    therefore does not enter the result, `It` and `Ib` differ in the tag that is passed through; `Im` stays refused.  An extension
+    beyond the reference; no trained checkpoint exists here, so nothing is claimed about quality.  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -203,6 +214,13 @@ def check_roi_feather(roi_feather: int, h: int, w: int, tail) -> None:
 SHARP = ("deblur", "keep")       # what becomes of a frame labelled sharp: a window of its own like any other, or the input frame
 
 
+def check_fields(fields):
+    """How a frame is read: None, progressive; "split", as two woven fields that are deblurred as clips of their own."""
+    if fields is not None and not (isinstance(fields, str) and fields == "split"):
+        raise ValueError(f"fields must be None or \"split\", got {fields!r}")
+    return fields
+
+
 def check_sharp(sharp) -> str:
     if not isinstance(sharp, str) or sharp not in SHARP:
         raise ValueError(f"sharp must be \"deblur\" or \"keep\", got {sharp!r}")
@@ -323,11 +341,19 @@ class ClipRun:
     plan entry `StreamPlan` handed out under its assumption (empty in whole-clip mode).  `sharp` is "deblur" or "keep"; with "keep"
     no window runs for a frame whose label is 1: it is handed out as the input frame at `out_depth` (`ops.frame_requant`), `kept` is
     the increasing list of those handed out so far, none of them is ever in `recomputed`, and `assumed` leaves them out (a kept frame's
-    plan entry is not used; `plan` itself is the same list either way)."""
+    plan entry is not used; `plan` itself is the same list either way).  `fields` is None or "split"; with "split" every frame is
+    deblurred as its two fields (rows p::2), each parity a clip of its own, and `labels`, `cuts` and `plan` are the top-field clip's:
+    one plan for both parities."""
 
     def __init__(self, model, frames: Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
                  out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None, ensemble: int = 1, roi=None,
-                 roi_feather: int = 0, bar_params: Optional[dict] = None, horizon: Optional[int] = None, sharp: str = "deblur"):
+                 roi_feather: int = 0, bar_params: Optional[dict] = None, horizon: Optional[int] = None, sharp: str = "deblur",
+                 fields: Optional[str] = None):
+        self.fields = check_fields(fields)
+        if self.fields is not None:
+            if tiles is not None or roi is not None:
+                raise ValueError("fields= with tiles= or roi=: a window's table of parts is taken")
+            frames = frames.woven()          # a y4m clip's frames become RGB field by field
         self.model, self.frames = model, frames
         self.sharp = check_sharp(sharp)
         self.kept = []                   # sharp="keep": the frames handed out as their input, in order
@@ -368,7 +394,9 @@ class ClipRun:
         return self._roi
 
     def _view(self) -> Frames:
-        """The clip the analysis pass sees: the frames cropped to the region of interest."""
+        """The clip the analysis pass sees: the frames cropped to the region of interest; of an interlaced clip, the top-field clip."""
+        if self.fields is not None:
+            return self.frames.field(0)
         return self.frames if self.roi is None else self.frames.view(self.roi)
 
     labels = property(lambda self: self._source.labels)
@@ -392,8 +420,9 @@ class ClipRun:
         m, dev, fr = self.model, self.device, self.frames
         H, W = fr.H, fr.W
         tp = self.tiles
-        nt = 1 if tp is None else tp.n                 # tiles per frame: each is a window of its own, all of one shape
-        Hp, Wp = (padded_size(H), padded_size(W)) if tp is None else tp.padded
+        split = self.fields is not None                # the two fields of a frame: two parts of one shape, as two tiles are
+        nt = 2 if split else 1 if tp is None else tp.n     # parts per frame: each is a window of its own, all of one shape
+        Hp, Wp = (padded_size(H // 2 if split else H), padded_size(W)) if tp is None else tp.padded
         # a region of interest: the model sees the rectangle only, the cache keeps whole frames (the paste needs them)
         roi, roi_feather = self.roi, self.roi_feather
         if roi is not None:
@@ -421,7 +450,9 @@ class ClipRun:
         out_dtype = torch.uint8 if out_depth == 8 else torch.uint16
 
         def ingest(f, x, j):
-            """Frame f as frame j of the window's input: of its one sample, or of every tile's in one launch."""
+            """Frame f as frame j of the window's input: of its one sample, or of every tile's or both fields' in one launch."""
+            if split:
+                return ops.fields_in(f, x[:, j], None if depth == 8 else depth)
             if tp is not None:
                 return ops.tiles_in(f, tp, x[:, j], None if depth == 8 else depth)
             if roi is not None:          # the tile ingest with a table of one tile: bit-identical to the frame ingest on the crop
@@ -429,8 +460,10 @@ class ClipRun:
             return ops.frames_u8_in(f, out=x[0, j]) if depth == 8 else ops.frames_u16_in(f, depth, out=x[0, j])
 
         def egress(y, dst, flag, k):
-            """The model's output, a list of nt planes [3, Hp, Wp], as frame k: the crop, the tiles' bands stitched, or the rectangle
-            pasted into the input frame."""
+            """The model's output, a list of nt planes [3, Hp, Wp], as frame k: the crop, the tiles' bands stitched, the two fields
+            woven, or the rectangle pasted into the input frame."""
+            if split:
+                return ops.fields_out(y, H, W, out_depth, out=dst, nonfinite=flag)
             if tp is not None:
                 return ops.tiles_out(y, tp, out_depth, out=dst, nonfinite=flag)
             if roi is not None:
@@ -442,7 +475,7 @@ class ClipRun:
 
         def parts(run):
             """The nt planes of a window.  It runs as nt * K parts, one after the other: `run(t, g)` is the output plane of member g of
-            tile t on the input xs[g][t:t + 1]; one launch turns the K planes of a tile back and averages them (K = 1: none)."""
+            tile (or field) t on the input xs[g][t:t + 1]; one launch turns the K planes of a tile back and averages them (K = 1: none)."""
             mean = (lambda outs: outs[0]) if K == 1 else (lambda outs: ops.d4_mean(outs, members))
             return [mean([run(t, g) for g in members]) for t in range(nt)]
 
@@ -620,7 +653,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
                 detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None,
                 depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20, feather: int = 0,
                 ensemble: int = 1, roi=None, roi_feather: int = 0, bar_params: Optional[dict] = None, stream=False,
-                horizon: int = 48, sharp: str = "deblur") -> ClipRun:
+                horizon: int = 48, sharp: str = "deblur", fields: Optional[str] = None) -> ClipRun:
     """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
     or uint16 frames when `out_depth` is 10 or 12.
 
@@ -714,12 +747,33 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              called.  An extension beyond the reference.  No trained checkpoint exists here, so nothing is claimed about quality: in
              particular not that the step from a kept frame to its deblurred neighbours is invisible.
 
+    fields — None (the default): the frames are progressive; launch for launch the path without this argument.  "split": the frames
+             are INTERLACED.  A frame f of even height H is two fields, field p (0 = top, 1 = bottom) = f[p::2]: H / 2 rows, the same
+             W and depth, two different instants.  Frame k of the result has, in its rows p::2, frame k of
+             `deblur_clip(model, [f[p::2] for f in frames], labels=L, cuts=C, ...)` with every other argument the same, bit for bit,
+             for p = 0 and 1.  L and C are the caller's `labels` / `cuts` when given; otherwise the labels and, with `cuts="auto"`,
+             the cuts that the detector and `find_cuts` give the TOP-FIELD clip: one plan for both parities, and `ClipRun.labels`,
+             `.cuts` and `.plan` are the top-field clip's.  The reflect pad to multiples of 20 is each field's own (field row
+             H / 2 + j is field row H / 2 - 2 - j).  H must be even and H / 2 >= 20.  Design choices: each parity is its own clip, so a
+             window has frame-rate spacing and no half-line bob between its frames (one clip of 2T alternating fields bobs: rejected);
+             field order (top or bottom first) therefore does not enter the result, a y4m `It` and `Ib` clip differ in the tag only;
+             mixed-mode `Im` streams stay refused.  A y4m clip is made RGB field by field (4:2:0: chroma-plane row j belongs to field
+             j & 1, and H must be a multiple of 4; the other layouts convert row by row).  Composes with `cuts`, `ensemble`,
+             `sharp="keep"` (a kept frame is the whole input frame), deep clips, `out_depth`, every y4m layout, `out` and `stream`
+             (one plan stands behind both parts).  Not with `tiles` or `roi`: a window's table of parts is taken.  A y4m reader or
+             stream whose `interlace` is "t" or "b" needs `fields="split"` said: there is no silent default.  An extension beyond the
+             reference; no trained checkpoint exists here, so nothing is claimed about quality.
+
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
     to `ClipRun.recomputed` with a RuntimeWarning, and FloatingPointError is raised if the frame is still not finite."""
     ensemble = ens.check_size(ensemble)                    # in front of everything else: no frame is looked at
     sharp = check_sharp(sharp)
+    fields = check_fields(fields)
+    if fields is not None and (tiles is not None or roi is not None):
+        raise ValueError(f"fields={fields!r} with {'tiles=' if tiles is not None else 'roi='} is not built: the fields of a frame run as the "
+                         "two parts of its window, and the table of parts is taken by the tiles or the rectangle")
     if tiles is None and not (isinstance(feather, int) and not isinstance(feather, bool) and feather == 0):
         raise ValueError(f"feather={feather!r} needs tiles=: it blends the seams between tiles, and an untiled frame has none")
     if isinstance(roi_feather, bool) or not isinstance(roi_feather, (int, np.integer)) or roi_feather < 0:
@@ -736,7 +790,10 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     if stream not in (False, True, "force"):
         raise ValueError(f"stream must be False, True or \"force\", got {stream!r}")
     if isinstance(frames, (str, os.PathLike)) and os.fspath(frames).lower().endswith(".y4m"):
-        frames = (y4m.Y4MStream if stream else y4m.Y4MReader)(frames, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
+        frames = (y4m.Y4MStream if stream else y4m.Y4MReader)(frames, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS, interlace=y4m.INTERLACE)
+    if fields is None and getattr(frames, "interlace", "p") in ("t", "b") and isinstance(frames, (y4m.Y4MReader, y4m.Y4MStream)):
+        raise ValueError(f"the y4m clip is interlaced (I{frames.interlace}): pass fields=\"split\" to deblur its two fields as clips of "
+                         "their own, or open it as progressive on purpose; there is no silent default")
     unbounded = isinstance(frames, y4m.Y4MStream) or hasattr(frames, "__next__")
     if unbounded and not stream:
         raise ValueError("frames is a stream (a Y4MStream, or an iterator of frames): its length is not known, pass stream=True")
@@ -757,6 +814,13 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
                              "the rectangle (y0, x0, h, w)")
     # a stream's `fr.T` is None: what is measured against the clip's length is then checked by `StreamPlan` as the stream goes
     fr = frames_of(frames, crop, yuv, depth)
+    if fields is not None:
+        if fr.H % 2 or fr.H // 2 < MIN_SIZE:
+            raise ValueError(f"fields={fields!r}: a {fr.W}x{fr.H} frame does not split into two fields of at least {MIN_SIZE} rows "
+                             f"(H must be even and H / 2 >= {MIN_SIZE})")
+        if fr.yuv is not None and fr.yuv[0] in (y4m.CENTER, y4m.LEFT) and fr.src[0] % 4:
+            raise ValueError(f"fields={fields!r}: the fields of a 4:2:0 clip of H = {fr.src[0]} rows have no whole chroma rows (H must "
+                             "be a multiple of 4)")
     if roi is not None and not isinstance(roi, str):
         roi = roi_of(tuple(roi) if isinstance(roi, list) else roi, fr.H, fr.W)
         h, w = (fr.H, fr.W) if roi is None else roi[2:]
@@ -788,7 +852,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     if tp is not None and tp.n == 1:
         tp = None                        # one tile that spans the frame: the untiled path
     return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp, ensemble, roi, int(roi_feather), bar_params,
-                   horizon if stream else None, sharp)
+                   horizon if stream else None, sharp, fields)
 
 
 def _inputs(spec: str) -> list:
@@ -920,6 +984,11 @@ def main(argv=None) -> None:
                    "'deblur' (the default) runs its window like any other; 'keep' runs none and writes the input frame (y4m in and out "
                    "with the input's chroma layout, depth and range: the input's record, byte for byte).  The blurry frames are the "
                    "same either way; sharp frames still serve them as neighbours and references")
+    p.add_argument("--fields", choices=("auto", "progressive", "split"), default="auto", help="interlaced footage: 'split' deblurs the two "
+                   "fields of every frame (its even and its odd rows, two instants) as clips of their own under one plan, the top-field "
+                   "clip's, and weaves the results; 'progressive' treats the frames as they are, whatever the input's tag says; 'auto' "
+                   "(the default) splits iff the y4m input is tagged It or Ib.  The y4m output carries the input's I tag.  Needs an even "
+                   "height of at least 40 (a multiple of 4 for 4:2:0 y4m); not with --tiles or --roi")
     p.add_argument("--stream", action="store_true", help="y4m input only: deblur the stream as it arrives, with a bounded look-ahead and "
                    "no spool ('--input -' reads stdin as a pipe; a .y4m file is read in order); the first frames leave before the "
                    "input has ended.  The window plan is exact except where it depends on the rest of a scene, however long: there it "
@@ -944,6 +1013,9 @@ def main(argv=None) -> None:
         raise SystemExit(f"--roi: {e}")
     if roi is not None and tiles is not None:              # refused here, before the model is loaded
         raise SystemExit("--roi with --tiles is not built: the tile egress writes whole frames only")
+    if a.fields == "split" and (tiles is not None or roi is not None):
+        raise SystemExit(f"--fields split with {'--tiles' if tiles is not None else '--roi'} is not built: the two fields run as the parts "
+                         "of a window, and the table of parts is taken")
     if a.roi_feather != 0 and roi is None:
         raise SystemExit(f"--roi_feather {a.roi_feather}: needs --roi: it blends the edge of the region of interest")
     to_stdout = a.output == "-"
@@ -966,12 +1038,20 @@ def main(argv=None) -> None:
             raise SystemExit("--roi auto with --stream: the active area is found from the whole clip; give Y,X,H,W")
         if a.input != "-" and not (a.input.lower().endswith(".y4m") and os.path.isfile(a.input)):
             raise SystemExit(f"--stream: --input {a.input} is not '-' or a .y4m file (image files have a known length: nothing to stream)")
-        reader = y4m.Y4MStream(sys.stdin.buffer if a.input == "-" else a.input, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
+        reader = y4m.Y4MStream(sys.stdin.buffer if a.input == "-" else a.input, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS,
+                               interlace=y4m.INTERLACE)
     elif a.input == "-":
-        reader = y4m.Y4MReader(_spool(sys.stdin.buffer, a.spool_dir), depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
+        reader = y4m.Y4MReader(_spool(sys.stdin.buffer, a.spool_dir), depths=y4m.DEPTHS, layouts=y4m.LAYOUTS, interlace=y4m.INTERLACE)
     elif a.input.lower().endswith(".y4m") and os.path.isfile(a.input):
-        reader = y4m.Y4MReader(a.input, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS)
+        reader = y4m.Y4MReader(a.input, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS, interlace=y4m.INTERLACE)
+    tag = "p" if reader is None else reader.interlace      # the input's I tag: the y4m output carries it, whatever --fields says
+    fields = "split" if a.fields == "split" or (a.fields == "auto" and tag != "p") else None
+    if fields is not None and (tiles is not None or roi is not None):
+        raise SystemExit(f"--input {a.input} is interlaced (I{tag}) and --fields auto splits it, which is not built with "
+                         f"{'--tiles' if tiles is not None else '--roi'}: say --fields progressive to treat the frames as they are")
     if reader is not None:
+        if fields is None:
+            reader.interlace = "p"       # --fields progressive on an It / Ib input: the user's call, the frames as they are
         if reader.depth > 8 and reader.layout in (y4m.CENTER, y4m.LEFT) and a.chroma in ("420jpeg", "420mpeg2"):
             reader.layout = y4m.layout_of(a.chroma)
         if not a.stream and len(reader) < 2:
@@ -996,7 +1076,7 @@ def main(argv=None) -> None:
         out_depth = 8
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
                       yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather, ensemble=a.ensemble,
-                      roi=roi, roi_feather=a.roi_feather, stream=a.stream, horizon=a.horizon, sharp=a.sharp)
+                      roi=roi, roi_feather=a.roi_feather, stream=a.stream, horizon=a.horizon, sharp=a.sharp, fields=fields)
     out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
@@ -1010,11 +1090,16 @@ def main(argv=None) -> None:
             fps, aspect = a.fps or (25, 1), None
         if a.out_chroma is not None:
             layout = y4m.layout_of(a.out_chroma)
-        writer = y4m.Y4MWriter(sys.stdout.buffer if to_stdout else a.output, W, H, fps, layout, rng, aspect, depth=out_depth)
+        if fields is not None and layout in (y4m.CENTER, y4m.LEFT) and H % 4:
+            raise SystemExit(f"--fields split: a 4:2:0 y4m output of H = {H} rows has no whole chroma rows per field (H must be a multiple "
+                             "of 4); write --out_chroma 422 or 444")
+        writer = y4m.Y4MWriter(sys.stdout.buffer if to_stdout else a.output, W, H, fps, layout, rng, aspect, depth=out_depth, interlace=tag)
     else:
         os.makedirs(a.output, exist_ok=True)
     if reader is not None:
         say(f"# y4m input C{reader.chroma}" + (f", output C{writer.chroma}" if writer is not None and writer.chroma != reader.chroma else ""))
+    if fields is not None or tag != "p":
+        say(f"# fields: {'split' if fields is not None else 'progressive'} (I{tag})")
     if run.roi is not None:
         say("# roi " + ",".join(str(v) for v in run.roi))
     said = 0                                               # a stream's cuts are reported as they are found
@@ -1055,8 +1140,9 @@ def main(argv=None) -> None:
             if is_kept and as_read:                        # a copy: a stream gives the record up a few frames on; the one writer keeps order
                 records.put(write, run.frames.host(i))
             elif to_y4m:
-                planar = (ops.rgb_u8_to_yuv(frame, layout, matrix, rng) if out_depth == 8 else
-                          ops.rgb_u16_to_yuv(frame, layout, matrix, rng, out_depth))
+                woven = fields is not None and layout in (y4m.CENTER, y4m.LEFT)     # the other layouts convert row by row
+                planar = (ops.rgb_u8_to_yuv(frame, layout, matrix, rng, fields=woven) if out_depth == 8 else
+                          ops.rgb_u16_to_yuv(frame, layout, matrix, rng, out_depth, fields=woven))
                 ring.land(write, planar)
             else:
                 ring.land(lambda buf, path=os.path.join(a.output, names[i]): imwrite(path, buf.numpy()), frame)

@@ -7,8 +7,15 @@ Supported: progressive 8-bit 4:2:0 (`C420jpeg`, bare `C420`, `C420mpeg2`) and 4:
 `ops.yuv_to_rgb_u16` / `ops.rgb_u16_to_yuv` convert).  For a reader opened with `layouts=LAYOUTS`, also 4:2:2 (`C422`, `C422p10`,
 `C422p12`: chroma planes [H][ceil(W/2)], co-sited with the even column) and mono (`Cmono`, `Cmono10`, `Cmono12`: the Y plane alone) at
 the depths it was given; the same four `ops` functions convert them.  `Y4MReader` indexes a file; `Y4MStream` reads a pipe in order, with the same header
-parsing and error texts.  Not supported: interlaced streams, other depths (9, 14, 16
-bits), 4:1:1, 4:4:0, `C420paldv`."""
+parsing and error texts.
+
+Interlaced streams (`It`: top field first, `Ib`: bottom field first) are an opt-in as well: a reader opened with
+`interlace=("p", "t", "b")` accepts them and says which it met in `.interlace`; a record is then a WOVEN frame of `frame_bytes` bytes
+whose rows p::2 are field p, and for 4:2:0 chroma-plane row j belongs to field j & 1 (`ops.yuv_to_rgb_u8(..., fields=True)`; the clip
+API's `fields="split"`).  `Y4MWriter(..., interlace="t")` writes the tag.  The two tags differ in nothing but the tag.
+
+Not supported: mixed-mode streams (`Im`), interlaced streams without the opt-in, other depths (9, 14, 16 bits), 4:1:1, 4:4:0,
+`C420paldv`."""
 from __future__ import annotations
 
 import os
@@ -34,6 +41,7 @@ MATRIX_NAMES = {"bt601": BT601, "bt709": BT709}
 RANGE_NAMES = {"full": FULL, "limited": LIMITED}
 HINT = "convert it with `ffmpeg -i <in> -pix_fmt yuv420p -f yuv4mpegpipe <out.y4m>`"
 MAX_HEADER = 4096
+INTERLACE = ("p", "t", "b")            # the I tags a reader can take: progressive, top field first, bottom field first ("p" always)
 
 
 def _named(value, names: dict, what: str) -> int:
@@ -67,6 +75,14 @@ def depth_of(depth) -> int:
     return int(depth)
 
 
+def interlace_of(interlace) -> tuple:
+    """The I tags a reader takes, from a sequence of "p", "t", "b": "p" is always among them."""
+    tags = (interlace,) if isinstance(interlace, str) else tuple(interlace)
+    if any(not isinstance(t, str) or t not in INTERLACE for t in tags):
+        raise ValueError(f"interlace must hold \"p\", \"t\" or \"b\", got {interlace!r}")
+    return tuple(t for t in INTERLACE if t == "p" or t in tags)
+
+
 def frame_bytes(h: int, w: int, layout: int, depth: int = 8) -> int:
     """Bytes of one planar frame: Y [h][w], then U and V, [ceil(h/2)][ceil(w/2)] each for 4:2:0, [h][ceil(w/2)] each for 4:2:2 and
     [h][w] each for 4:4:4 (mono: the Y plane alone); one byte per sample at `depth` 8, two (a little-endian word) at 10 and 12."""
@@ -96,9 +112,10 @@ def _ratio(tag: str, text: str):
 class _Header:
     """What `Y4MReader` and `Y4MStream` share: the header line's tags, their validation and the error texts."""
 
-    def _open(self, path_or_file, depths, layouts, mode: str = "rb") -> None:
+    def _open(self, path_or_file, depths, layouts, interlace=("p",), mode: str = "rb") -> None:
         self.depths = tuple(depth_of(d) for d in depths)
         self.layouts = tuple(layout_of(v) for v in layouts)
+        self.interlaces = interlace_of(interlace)
         self._own = isinstance(path_or_file, (str, bytes, os.PathLike))
         self._f = open(path_or_file, mode) if self._own else path_or_file
         self.name = os.fspath(path_or_file) if self._own else getattr(path_or_file, "name", "<file>")
@@ -113,7 +130,7 @@ class _Header:
             raise ValueError(f"{self.name}: not a YUV4MPEG2 stream (no '{MAGIC.decode()} ...' header line)")
         tags = head[len(MAGIC):end].decode("ascii", "replace").split()
         self.width = self.height = None
-        self.fps, self.aspect, self.chroma, self.range = (25, 1), None, "420jpeg", LIMITED
+        self.fps, self.aspect, self.chroma, self.range, self.interlace = (25, 1), None, "420jpeg", LIMITED, "p"
         for t in tags:
             key, val = t[0], t[1:]
             if key == "W":
@@ -125,7 +142,11 @@ class _Header:
             elif key == "A":
                 self.aspect = _ratio(key, val)
             elif key == "I":
-                if val not in ("p", "?"):
+                if val == "m":
+                    self._fail("tag Im: mixed-mode streams (every frame with an interlacing flag of its own) are not supported")
+                if val in ("t", "b") and val in self.interlaces:
+                    self.interlace = val
+                elif val not in ("p", "?"):
                     self._fail(f"tag I{val}: interlaced streams are not supported (progressive Ip only)")
             elif key == "C":
                 self.chroma = val
@@ -203,17 +224,22 @@ class Y4MReader(_Header):
     and `Cmono*`, whatever `depths` says; with `layouts=LAYOUTS` the reader also accepts `C422` and `Cmono` and, at the depths it
     was given, `C422p10`, `C422p12`, `Cmono10` and `Cmono12` (`layout` is then P422 or MONO).
 
+    `interlace`: the I tags the caller can take, the third opt-in.  The default, ("p",), refuses `It` and `Ib`; with
+    `interlace=INTERLACE` (("p", "t", "b")) the reader accepts them and `interlace` is then "t" or "b" ("p" for `Ip`, `I?` and a
+    missing tag).  `frame_bytes` and `raw(i)` are unchanged: an interlaced record is a woven frame, rows p::2 its field p.  `Im`
+    (mixed mode) is refused either way.
+
     Attributes: `width`, `height`, `fps` and `aspect` ((num, den); 25:1 and None when absent), `layout` (CENTER / LEFT / P444; P422 /
     MONO for a reader that takes them),
     `depth` (8, 10 or 12), `chroma` (the C tag's text), `range` (from XCOLORRANGE=FULL|LIMITED; LIMITED when absent), `matrix`, `frame_bytes`.  y4m carries
     no matrix tag: `matrix` is BT709 when height >= 720 and BT601 otherwise, which is ffmpeg's usual guess for untagged video;
     assign `matrix` / `range`, or pass `yuv=dict(matrix=..., range=...)` to `deblur_clip`, to override.
 
-    Interlaced streams, depths outside `depths` (9, 14 and 16 bits always), layouts outside `layouts` (C422 and Cmono at any depth
+    Interlaced streams without the opt-in, depths outside `depths` (9, 14 and 16 bits always), layouts outside `layouts` (C422 and Cmono at any depth
     by default), C420paldv, C411 and C440 are rejected with a ValueError that names the tag."""
 
-    def __init__(self, path_or_file, depths=(8,), layouts=(CENTER, LEFT, P444)):
-        self._open(path_or_file, depths, layouts)
+    def __init__(self, path_or_file, depths=(8,), layouts=(CENTER, LEFT, P444), interlace=("p",)):
+        self._open(path_or_file, depths, layouts, interlace)
         self._lock = threading.Lock()
         try:
             self._parse()
@@ -268,15 +294,15 @@ class Y4MReader(_Header):
 
 class Y4MStream(_Header):
     """A y4m stream read in order from a binary file object that need not seek (a pipe, a socket's file, stdin), or from a path: what
-    `Y4MReader` is for a file, without a length.  The header line is read here, with `Y4MReader`'s tags, `depths=` / `layouts=`
+    `Y4MReader` is for a file, without a length.  The header line is read here, with `Y4MReader`'s tags, `depths=` / `layouts=` / `interlace=`
     opt-ins, attributes and error texts (the two share the code); then `read_into(buf)` fills `buf` (`frame_bytes` bytes: a uint8
     numpy array or any writable buffer) with the next frame's planar bytes and returns True, or returns False at a clean end of the
     stream (the end in front of a FRAME line).  Short reads are put together.  ValueError: a stream that ends inside a FRAME line or
     a frame, or a FRAME line that is not one of the first frame's length.  `frames` counts the frames read so far.  One reader at
     a time: the object keeps the bytes it read past a line."""
 
-    def __init__(self, path_or_file, depths=(8,), layouts=(CENTER, LEFT, P444)):
-        self._open(path_or_file, depths, layouts)
+    def __init__(self, path_or_file, depths=(8,), layouts=(CENTER, LEFT, P444), interlace=("p",)):
+        self._open(path_or_file, depths, layouts, interlace)
         self._rest, self._line, self.frames = b"", None, 0
         try:
             head = b""
@@ -343,14 +369,18 @@ class Y4MStream(_Header):
 
 
 class Y4MWriter:
-    """Write a progressive y4m stream: the header once, then `write(planar bytes)` per frame (`frame_bytes` bytes: a bytes-like
+    """Write a y4m stream, progressive unless `interlace` is "t" or "b" (the header then says `It` / `Ib`, top / bottom field first; a
+    frame is a woven frame of the same `frame_bytes`): the header once, then `write(planar bytes)` per frame (`frame_bytes` bytes: a bytes-like
     object or a contiguous numpy array, uint8, or uint16 for a deep stream).  `path_or_file`: a path, or a binary file object (a pipe
     will do), which `close` flushes and leaves open.  `depth` 10 or 12 writes `C420p10`, `C444p12`, `C422p10`, `Cmono12` and the like
     (little-endian words; the tag carries no siting, whatever `layout` says) and adds `XYSCSS=420P10`, `XYSCSS=422P12` and the like,
     as ffmpeg does (none for mono).  `layout` P422 / MONO writes `C422` / `Cmono` frames: Y, then U and V of [h][ceil(w/2)]; Y alone."""
 
     def __init__(self, path_or_file, w: int, h: int, fps=(25, 1), layout: int = CENTER, range: int = LIMITED, aspect=None,
-                 depth: int = 8):
+                 depth: int = 8, interlace: str = "p"):
+        if not isinstance(interlace, str) or interlace not in INTERLACE:
+            raise ValueError(f"y4m: interlace must be \"p\", \"t\" or \"b\", got {interlace!r}")
+        self.interlace = interlace
         self.width, self.height, self.fps, self.aspect = int(w), int(h), (int(fps[0]), int(fps[1])), aspect
         self.layout, self.range, self.depth = layout_of(layout), range_of(range), depth_of(depth)
         self.chroma = chroma_tag(self.layout, self.depth)
@@ -359,7 +389,7 @@ class Y4MWriter:
             raise ValueError(f"y4m: bad size {w}x{h} or frame rate {fps}")
         self._own = isinstance(path_or_file, (str, bytes, os.PathLike))
         self._f = open(path_or_file, "wb") if self._own else path_or_file
-        tags = [f"W{self.width}", f"H{self.height}", f"F{self.fps[0]}:{self.fps[1]}", "Ip"]
+        tags = [f"W{self.width}", f"H{self.height}", f"F{self.fps[0]}:{self.fps[1]}", "I" + interlace]
         if aspect is not None:
             tags.append(f"A{int(aspect[0])}:{int(aspect[1])}")
         tags += [f"C{self.chroma}"] + ([] if self.depth == 8 or self.layout == MONO else [f"XYSCSS={self.chroma.upper()}"])
