@@ -664,6 +664,26 @@ int spei_roi_paste_u16(const float* src, const void* frame, int in_depth, uint16
  * 1, or a frame beyond the size bound of spei_frames_u8_in; a deep pointer on an odd address; a dst that overlaps src. */
 int spei_frame_requant(const void* src, int in_depth, void* dst, int out_depth, int H, int W, spei_stream_t stream);
 
+/* A matte of the clip API (video.deblur_clip(..., matte=); an extension beyond the reference): an 8-bit mask [H][W] says how much of
+ * the deblurred frame every pixel gets.  frame = the packed input frame [H][W][3] of in_depth 8 (bytes), 10 or 12 (little-endian
+ * 16-bit words, 2-byte aligned; a word above D_in reads as D_in); deb = the packed deblurred frame [H][W][3] at the output depth (a
+ * 16-bit word above D_out reads as D_out); matte = H * W bytes, one per pixel, rows packed.  With a = requant(frame sample) as
+ * defined above, b = the sample of deb and m = the pixel's matte byte, or 255 - m where invert != 0, every one of the 3 * H * W
+ * samples of dst is
+ *     (a * (255 - m) + b * m + 127) / 255                                   (integer division; at most 4095 * 255 + 127)
+ * so m = 0 gives a (spei_frame_requant's value), m = 255 gives b, a == b gives a for every m, and swapping a with b under the
+ * inverted matte gives the same value.  dst == deb is allowed (in place: a thread reads the 4 pixels of its group from all three
+ * sources before it writes them).  A group's 12 samples move as three words where W % 4 == 0 and the frame's base lies on a 4-byte
+ * (8-byte for 16-bit samples) boundary, sample by sample otherwise; its 4 matte bytes as one dword where W % 4 == 0 and matte is
+ * 4-byte aligned, byte by byte otherwise.  One launch, no workspace, no atomics.  Non-zero before anything is launched: a null
+ * pointer; an in_depth outside {8, 10, 12}; H or W below 1, or 3 * H * W >= 2^31; 16-bit data on an odd address; a dst that overlaps
+ * deb other than dst == deb, or that overlaps frame or matte.
+ * spei_frame_matte_u16: the same with deb and dst packed uint16 of `depth` 10 or 12 (anything else is refused). */
+int spei_frame_matte_u8(const void* frame, int in_depth, const unsigned char* deb, const unsigned char* matte, int invert,
+                        unsigned char* dst, int H, int W, spei_stream_t stream);
+int spei_frame_matte_u16(const void* frame, int in_depth, const uint16_t* deb, const unsigned char* matte, int invert, uint16_t* dst,
+                         int H, int W, int depth, spei_stream_t stream);
+
 /* The extent of the picture in N packed uint8 [H][W][3] frames, frame_stride bytes apart (rows packed; the frame-size bound of
  * spei_frames_u8_in), for the clip API's bar rule (video.find_bars): on the integer luma of spei_frame_pair_stats,
  * Y = (77 R + 150 G + 29 B + 128) >> 8, rowmax[y] (H ints) is the maximum of Y over row y of all N frames and colmax[x] (W ints) the

@@ -6,7 +6,8 @@ a clip of unknown length (a `y4m.Y4MStream`, an iterator of frames) as `StreamFr
 that one reader thread fills (`FrameRing`).
 Frames cross PCIe as uint8 (a deep clip's as its bytes) from page-locked staging buffers (`FrameCache`) and are decoded, for image paths, on
 worker threads a few windows ahead; finished frames land in page-locked memory for worker threads (`HostRing`).  `imread` / `imwrite`: the
-image codec of every tool."""
+image codec of every tool.  `mattes_of` does for the mattes of a clip (`deblur_clip(..., matte=)`) what `frames_of` does for its frames:
+`Mattes`, matte i on the host or the device, whether it is empty, and the bounding box of them all."""
 from __future__ import annotations
 
 import collections
@@ -507,3 +508,222 @@ def frames_of(frames, crop: bool = False, yuv: Optional[dict] = None, depth: Opt
             raise ValueError(f"mixed frame sizes: frame 0 is {items[0].shape[1]}x{items[0].shape[0]}, frame {i} is {f.shape[1]}x{f.shape[0]}")
     return Frames(items, T, int(items[0].shape[0]), int(items[0].shape[1]), paths=False, crop=crop, depth=depth or 8)
 
+
+
+# ---- mattes ---------------------------------------------------------------------------------------------------------------------------
+MATTE_GROW = 20                          # pixels the matte's bounding box is grown by on every side: the clip API's `shave` default
+MATTE_MEMO = 32                          # decoded mattes held on the host at most (more than a window's look-ahead)
+
+
+def _matte_plane(a, what: str) -> np.ndarray:
+    """A host matte as uint8 (a bool matte is 0 / 255); ValueError for any other dtype."""
+    if a.dtype == np.bool_:
+        return a.astype(np.uint8) * np.uint8(255)
+    if a.dtype != np.uint8:
+        raise ValueError(f"a matte is uint8 or bool; {what} is {a.dtype}")
+    return a
+
+
+def grow_box(box, H: int, W: int, grow: int = MATTE_GROW, least: int = MIN_SIZE):
+    """The rectangle (y0, x0, h, w) of a bounding box (ya, yb, xa, xb) (half open) in an H x W frame: grown by `grow` pixels on every
+    side, then symmetrically to at least `least` per axis (an odd pixel goes to the far side), then clamped to the frame; an axis that
+    the clamp left shorter than `least` is extended back into the frame from the edge it lies on.  None for None (nothing to box)."""
+    if box is None:
+        return None
+
+    def axis(a: int, b: int, n: int):
+        a, b = a - grow, b + grow
+        if b - a < least:
+            d = least - (b - a)
+            a, b = a - d // 2, b + d - d // 2
+        a, b = max(a, 0), min(b, n)
+        if b - a < least:
+            a, b = (0, min(n, least)) if a == 0 else (max(0, b - least), b)
+        return a, b - a
+
+    (y0, h), (x0, w) = axis(box[0], box[1], H), axis(box[2], box[3], W)
+    return y0, x0, h, w
+
+
+class Mattes:
+    """The mattes of a clip behind one interface: matte i as a contiguous host uint8 [H,W] array (`host`) or a device tensor
+    (`device`, where `on_device`), cropped at the bottom and right as the frames are under `crop`.  `static`: one matte for every
+    frame (`T` is then None, and every index reads it).  The bytes are handed out as given; `invert` is applied by whoever reads them
+    (`ops.frame_matte(..., invert=)`), and by `empty` and `bbox`, which speak of the matte in effect, 255 - m under `invert`:
+    `empty(i)`, is it 0 everywhere; `bbox()`, the rectangle (y0, x0, h, w) around the non-zero samples of every matte, grown and
+    clamped by `grow_box`, or None when every matte is empty.  Host mattes are decided on the host (each decoded once while it is in
+    the memo; `prefetch` decodes ahead on a thread pool); device mattes with one reduction and one sync, on first use."""
+
+    def __init__(self, items, kind: str, T: Optional[int], H: int, W: int, crop: bool = False, invert: bool = False):
+        import threading
+        self.items, self.kind, self.T, self.src, self.invert = items, kind, T, (H, W), bool(invert)
+        self.static = T is None
+        self.H, self.W = (H - H % 20, W - W % 20) if crop else (H, W)
+        self._memo: "collections.OrderedDict[int, object]" = collections.OrderedDict()
+        self._empty, self._lock = {}, threading.Lock()
+
+    def describe(self) -> str:
+        return ("static" if self.static else f"per frame, {self.T} frames") + f", {self.W}x{self.H}" + (", inverted" if self.invert else "")
+
+    def key(self, i: int) -> int:
+        """What identifies matte i: 0 for a static matte."""
+        if self.static:
+            return 0
+        if not 0 <= i < self.T:
+            raise IndexError(f"matte {i} of {self.T}")
+        return i
+
+    def _item(self, k: int):
+        return self.items if self.static and self.kind != "paths" else self.items[k]
+
+    def on_device(self, i: int) -> bool:
+        return self.kind == "device" or (self.kind == "list" and torch.is_tensor(self._item(self.key(i))) and self._item(self.key(i)).is_cuda)
+
+    def device(self, i: int) -> torch.Tensor:
+        m = self._item(self.key(i))[:self.H, :self.W]
+        return (m.to(torch.uint8) * 255 if m.dtype == torch.bool else m).contiguous()
+
+    def _load(self, k: int) -> np.ndarray:
+        if self.kind == "y4m":
+            a = self.items.raw(k).reshape(self.src)
+        elif self.kind == "paths":
+            from PIL import Image
+            with Image.open(self.items[k]) as im:
+                a = np.asarray(im.convert("L"))
+            if a.shape != self.src:
+                raise ValueError(f"matte {k} ({self.items[k]}) is {a.shape[1]}x{a.shape[0]}, the frames are {self.src[1]}x{self.src[0]}")
+        else:
+            m = self._item(k)
+            a = _matte_plane(m.numpy() if torch.is_tensor(m) else np.asarray(m), f"matte {k}")
+        return np.ascontiguousarray(a[:self.H, :self.W])
+
+    def prefetch(self, pool: ThreadPoolExecutor, indices) -> None:
+        """Decode the host mattes `indices` on the pool, for the `host` and `empty` calls to come."""
+        with self._lock:
+            for i in indices:
+                k = self.key(i)
+                if k not in self._memo and not self.on_device(i):
+                    self._memo[k] = pool.submit(self._load, k)
+            while len(self._memo) > MATTE_MEMO:
+                self._memo.popitem(last=False)
+
+    def host(self, i: int) -> np.ndarray:
+        k = self.key(i)
+        with self._lock:
+            a = self._memo.get(k)
+        if a is None:                                      # not asked for ahead (or given up since): decoded by the caller
+            a = self._load(k)
+            with self._lock:
+                self._memo[k] = a
+                while len(self._memo) > MATTE_MEMO:
+                    self._memo.popitem(last=False)
+        return a.result() if isinstance(a, Future) else a
+
+    def _device_stack(self) -> Optional[torch.Tensor]:
+        return self.items[None] if self.static else self.items
+
+    def empty(self, i: int) -> bool:
+        k = self.key(i)
+        if k not in self._empty:
+            blank = 255 if self.invert else 0
+            if self.kind == "device":                      # one reduction over every matte, one sync
+                lit = (self._device_stack()[:, :self.H, :self.W] != (self.invert if self.items.dtype == torch.bool else blank))
+                for j, v in enumerate(lit.flatten(1).any(1).cpu().tolist()):
+                    self._empty[j] = not v
+            elif self.on_device(i):
+                self._empty[k] = not bool((self.device(i) != blank).any().item())
+            else:
+                self._empty[k] = not bool((self.host(i) != blank).any())
+        return self._empty[k]
+
+    def bbox(self, grow: int = MATTE_GROW):
+        """One pass over every matte (a static one: over it); host mattes on the host, device mattes with two reductions and one sync."""
+        blank = 255 if self.invert else 0
+        n = 1 if self.static else self.T
+        if self.kind == "device":
+            lit = (self._device_stack()[:, :self.H, :self.W] != (self.invert if self.items.dtype == torch.bool else blank)).any(0)
+            rows, cols = lit.any(1).cpu().numpy(), lit.any(0).cpu().numpy()
+        else:
+            rows, cols = np.zeros(self.H, bool), np.zeros(self.W, bool)
+            for i in range(n):
+                lit = (self.device(i).cpu().numpy() if self.on_device(i) else self.host(i)) != blank
+                rows |= lit.any(1)
+                cols |= lit.any(0)
+        ys, xs = np.flatnonzero(rows), np.flatnonzero(cols)
+        if not ys.size:
+            return None
+        return grow_box((int(ys[0]), int(ys[-1]) + 1, int(xs[0]), int(xs[-1]) + 1), self.H, self.W, grow)
+
+
+def _matte_shape(i, shape, dtype, H: int, W: int) -> None:
+    if dtype not in (np.uint8, np.bool_, torch.uint8, torch.bool):
+        raise ValueError(f"a matte is uint8 or bool; {'the matte' if i is None else f'matte {i}'} is {dtype}")
+    if tuple(shape) != (H, W):
+        raise ValueError(f"{'the matte' if i is None else f'matte {i}'} has shape {tuple(shape)}, the frames are {W}x{H}: a matte is [H,W] = "
+                         f"[{H},{W}], one byte per pixel")
+
+
+def mattes_of(matte, T: Optional[int], H: int, W: int, crop: bool = False, invert: bool = False) -> Mattes:
+    """Validate the mattes of a clip of T frames of H x W (T None: a stream, its length is not known; `crop`: the frames are cropped to
+    multiples of 20 as they are loaded, and so is the matte) and return them as `Mattes`.  Static: a uint8 or bool [H,W] numpy array or
+    torch tensor (host or device), or the path of an image file (decoded to one 8-bit channel, PIL `convert("L")`).  Per frame: a
+    [T,H,W] array or tensor, a list of [H,W] arrays / tensors or of image paths (only their headers are read here), a directory of
+    images (in file-name order), or an 8-bit `Cmono` y4m clip (a path ending in .y4m, or a `y4m.Y4MReader` opened with
+    `layouts=y4m.LAYOUTS`), whose luma bytes are the matte as stored: m = 255 needs full-range grey.  Raises ValueError naming what is
+    wrong: a size, a dtype, a length other than T, a y4m clip that is not `Cmono`."""
+    def length(n: int, what: str) -> None:
+        if T is not None and n != T:
+            raise ValueError(f"{what} holds {n} mattes for a clip of {T} frames: a per-frame matte has one per frame")
+
+    if isinstance(matte, (str, os.PathLike)):
+        path = os.fspath(matte)
+        if path.lower().endswith(".y4m"):
+            matte = y4m.Y4MReader(path, depths=y4m.DEPTHS, layouts=y4m.LAYOUTS, interlace=y4m.INTERLACE)
+        elif os.path.isdir(path):
+            matte = sorted(os.path.join(path, f) for f in os.listdir(path) if f.lower().endswith(IMAGE_EXTS))
+            if not matte:
+                raise ValueError(f"the matte directory {path} holds no image file ({', '.join(IMAGE_EXTS)})")
+        else:
+            from PIL import Image
+            with Image.open(path) as im:
+                if (im.size[1], im.size[0]) != (H, W):
+                    raise ValueError(f"the matte {path} is {im.size[0]}x{im.size[1]}, the frames are {W}x{H}")
+            return Mattes([path], "paths", None, H, W, crop, invert)
+    if isinstance(matte, y4m.Y4MReader):
+        if matte.layout != y4m.MONO or matte.depth != 8:
+            raise ValueError(f"a y4m matte is an 8-bit Cmono clip (its luma bytes are the matte); {matte.name} is C{matte.chroma}")
+        _matte_shape(None, (matte.height, matte.width), np.uint8, H, W)
+        length(len(matte), f"the y4m matte {matte.name}")
+        return Mattes(matte, "y4m", len(matte), H, W, crop, invert)
+    if isinstance(matte, (np.ndarray, torch.Tensor)):
+        device = torch.is_tensor(matte) and matte.is_cuda
+        if matte.ndim == 2:
+            _matte_shape(None, matte.shape, matte.dtype, H, W)
+            return Mattes(matte, "device" if device else "array", None, H, W, crop, invert)
+        if matte.ndim != 3:
+            raise ValueError(f"a matte array is [H,W] (static) or [T,H,W] (per frame); got shape {tuple(matte.shape)}")
+        _matte_shape(None, matte.shape[1:], matte.dtype, H, W)
+        length(int(matte.shape[0]), "the matte array")
+        return Mattes(matte, "device" if device else "array", int(matte.shape[0]), H, W, crop, invert)
+    if isinstance(matte, (bytes, bytearray)) or not hasattr(matte, "__len__") or not hasattr(matte, "__getitem__"):
+        raise ValueError(f"matte must be an [H,W] or [T,H,W] array or tensor, an image path, a list of either, a directory or a Cmono y4m "
+                         f"clip, got {type(matte).__name__} (an iterator of mattes is not built)")
+    items = list(matte)
+    length(len(items), "the matte list")
+    if not items:
+        raise ValueError("the matte list is empty")
+    is_path = [isinstance(m, (str, os.PathLike)) for m in items]
+    if any(is_path) and not all(is_path):
+        raise ValueError("matte mixes image paths and arrays")
+    if all(is_path):
+        from PIL import Image
+        for i, p in enumerate(items):
+            with Image.open(p) as im:                      # the header only: decoding happens later, on worker threads
+                if (im.size[1], im.size[0]) != (H, W):
+                    raise ValueError(f"matte {i} ({os.fspath(p)}) is {im.size[0]}x{im.size[1]}, the frames are {W}x{H}")
+        return Mattes([os.fspath(p) for p in items], "paths", len(items), H, W, crop, invert)
+    for i, m in enumerate(items):
+        if not isinstance(m, (np.ndarray, torch.Tensor)):
+            raise ValueError(f"matte {i} is a {type(m).__name__}, not an array, tensor or image path")
+        _matte_shape(i, m.shape, m.dtype, H, W)
+    return Mattes(items, "list", len(items), H, W, crop, invert)

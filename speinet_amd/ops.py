@@ -703,6 +703,46 @@ def frame_requant(frame: torch.Tensor, out_depth: int, in_depth: Optional[int] =
     return out
 
 
+def frame_matte(frame: torch.Tensor, deb: torch.Tensor, matte: torch.Tensor, out_depth: int, in_depth: Optional[int] = None,
+                invert: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The deblurred frame where a matte says, the input elsewhere: `frame` the packed input frame [H,W,3] on the device (contiguous),
+    uint8 (`in_depth` None) or uint16 of `in_depth` 10 or 12 bits; `deb` the deblurred frame [H,W,3] at `out_depth`, uint8 for 8 and
+    uint16 for 10 and 12 (a word above D_out reads as D_out); `matte` uint8 [H,W], contiguous -> the frame at `out_depth` with every
+    sample (a * (255 - m) + b * m + 127) // 255, a = `frame_requant`'s sample of `frame`, b = the sample of `deb`, m = the pixel's
+    matte byte, or 255 - m under `invert`: exact integers; m = 0 gives a, m = 255 gives b.  `out` (optional): the packed destination;
+    it may be `deb` itself (in place) and may not overlap anything otherwise.  One launch on the current stream (csrc/matte_io.hip),
+    no host sync."""
+    assert frame.is_cuda and frame.dtype in (torch.uint8, torch.uint16) and frame.dim() == 3 and frame.shape[2] == 3
+    assert frame.is_contiguous()
+    if frame.dtype == torch.uint16:
+        in_depth = _depth(in_depth)
+    elif in_depth not in (None, 8):
+        raise ValueError(f"in_depth= applies to uint16 frames only; the frame is {frame.dtype}")
+    else:
+        in_depth = 8
+    if isinstance(out_depth, bool) or out_depth not in y4m.DEPTHS:
+        raise ValueError(f"out_depth must be 8, 10 or 12, got {out_depth!r}")
+    h, w = (int(v) for v in frame.shape[:2])
+    dtype = torch.uint8 if out_depth == 8 else torch.uint16
+    if not (deb.device == frame.device and deb.dtype == dtype and tuple(deb.shape) == (h, w, 3) and deb.is_contiguous()):
+        raise ValueError(f"deb must be a contiguous {str(dtype).split('.')[-1]} [{h},{w},3] tensor on {frame.device} (out_depth {out_depth}), "
+                         f"got {deb.dtype} {tuple(deb.shape)}")
+    if not (matte.device == frame.device and matte.dtype == torch.uint8 and tuple(matte.shape) == (h, w) and matte.is_contiguous()):
+        raise ValueError(f"matte must be a contiguous uint8 [{h},{w}] tensor on {frame.device}, got {matte.dtype} {tuple(matte.shape)}")
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=dtype, device=frame.device)
+    assert out.device == frame.device and out.dtype == dtype and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
+    lib = _lib.lib()
+    with torch.cuda.device(frame.device):
+        st = C.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)
+        head = (_vp(frame.data_ptr()), in_depth, _vp(deb.data_ptr()), _vp(matte.data_ptr()), int(bool(invert)), _vp(out.data_ptr()), h, w)
+        if out_depth == 8:
+            _lib.check(lib.spei_frame_matte_u8(*head, st), "spei_frame_matte_u8")
+        else:
+            _lib.check(lib.spei_frame_matte_u16(*head, int(out_depth), st), "spei_frame_matte_u16")
+    return out
+
+
 def frame_extent(frames: torch.Tensor, depth: Optional[int] = None, out=None):
     """The extent of the picture in packed frames [N,H,W,3] on the device (any frame stride), uint8 (`depth` None) or uint16 of `depth`
     10 or 12 bits -> (rowmax int32 [H], colmax int32 [W]): the maximum over every row, and over every column, of all N frames of the

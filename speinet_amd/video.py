@@ -6,8 +6,8 @@
                                 [--matrix bt601|bt709] [--range full|limited] [--fps num:den]
                                 [--chroma 420jpeg|420mpeg2|422|444|mono] [--out_chroma 420jpeg|420mpeg2|422|444|mono]
                                 [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N] [--ensemble 1|2|4|8]
-                                [--roi none|auto|Y,X,H,W] [--roi_feather N] [--stream [--horizon N]] [--sharp deblur|keep]
-                                [--fields auto|progressive|split]
+                                [--roi none|auto|matte|Y,X,H,W] [--roi_feather N] [--stream [--horizon N]] [--sharp deblur|keep]
+                                [--fields auto|progressive|split] [--matte <image | dir | glob | matte.y4m> [--matte_invert]]
 
 (`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; by default stdin is spooled to a temporary
 file on disk before the first frame is deblurred, with `--stream` it is deblurred as it arrives, see `main`)
@@ -73,6 +73,14 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     frame-rate spacing and no half-line bob between neighbours (one clip of 2T alternating fields would bob: rejected); field order
     therefore does not enter the result, `It` and `Ib` differ in the tag that is passed through; `Im` stays refused.  An extension
     beyond the reference; no trained checkpoint exists here, so nothing is claimed about quality.  Off by default.
+  * mattes (`matte=`, `--matte`; csrc/matte_io.hip `spei_frame_matte_u8` / `_u16`): an 8-bit mask, one for the clip or one per frame
+    (`clip.mattes_of`), says how much of the deblurred frame every pixel gets: with a the input sample at the output depth, b the
+    sample the run without a matte hands out and m the matte byte, every sample is (a * (255 - m) + b * m + 127) // 255, exact
+    integers.  One more launch on the packed frame, in place, behind whichever egress ran (`ops.frame_matte`), also behind a bf16x3
+    recompute's; the window's centre input frame is kept for it as for the ROI paste, and the mattes are uploaded through a
+    `FrameCache` of their own.  A frame whose matte is empty takes the kept-frame path (`ClipRun.unmatted`), and `roi="matte"` is the
+    mattes' bounding box, grown by 20 pixels.  An extension beyond the reference; no trained checkpoint exists here, so nothing is
+    claimed about quality.  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -95,7 +103,8 @@ import numpy as np
 import torch
 
 from . import detector, engine, ensemble as ens, ops, tiles as tiling, y4m
-from .clip import IMAGE_EXTS, MIN_SIZE, FrameCache, Frames, HostRing, RecordQueue, frames_of, imread, imwrite, padded_size, reflect_index  # noqa: F401
+from .clip import (IMAGE_EXTS, MIN_SIZE, FrameCache, Frames, HostRing, Mattes, RecordQueue, frames_of, imread, imwrite, mattes_of,  # noqa: F401
+                   padded_size, reflect_index)
 from .plan import (ASSUMED_TAIL, CUT_PARAMS, MIN_HORIZON, ZERO, StreamCuts, StreamPlan, cuts_of, find_cuts, labels_of,  # noqa: F401
                    window_plan)
 from .speinet import EncoderCache
@@ -188,14 +197,14 @@ def active_area(frames, device, frames_max: Optional[int] = 64):
 
 
 def roi_of(roi, H: int, W: int):
-    """Validate a region of interest for H x W frames: None, "auto", or (y0, x0, h, w), four whole numbers (no bools) with
-    0 <= y0, y0 + h <= H, the same for x, and h, w >= 20.  Returns None, "auto", the tuple of ints, or None for the rectangle that is
+    """Validate a region of interest for H x W frames: None, "auto", "matte", or (y0, x0, h, w), four whole numbers (no bools) with
+    0 <= y0, y0 + h <= H, the same for x, and h, w >= 20.  Returns None, "auto", "matte", the tuple of ints, or None for the rectangle that is
     the whole frame (the path without a region).  Raises ValueError with the reason."""
-    if roi is None or (isinstance(roi, str) and roi == "auto"):
+    if roi is None or (isinstance(roi, str) and roi in ("auto", "matte")):
         return roi
     vals = tuple(roi) if isinstance(roi, (tuple, list)) else ()
     if len(vals) != 4 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in vals):
-        raise ValueError(f"roi must be None, \"auto\" or four whole numbers (y0, x0, h, w), got {roi!r}")
+        raise ValueError(f"roi must be None, \"auto\" or four whole numbers (y0, x0, h, w), or \"matte\" beside matte=, got {roi!r}")
     y0, x0, h, w = (int(v) for v in vals)
     if h < MIN_SIZE or w < MIN_SIZE:
         raise ValueError(f"roi {(y0, x0, h, w)}: the rectangle must be at least {MIN_SIZE}x{MIN_SIZE}, the smallest frame the clip API takes")
@@ -343,12 +352,15 @@ class ClipRun:
     the increasing list of those handed out so far, none of them is ever in `recomputed`, and `assumed` leaves them out (a kept frame's
     plan entry is not used; `plan` itself is the same list either way).  `fields` is None or "split"; with "split" every frame is
     deblurred as its two fields (rows p::2), each parity a clip of its own, and `labels`, `cuts` and `plan` are the top-field clip's:
-    one plan for both parities."""
+    one plan for both parities.  `matte` is the clip's `clip.Mattes` or None; with one, every frame handed out is the blend of the
+    input frame with the deblurred one that its matte says (`ops.frame_matte`), a frame whose matte is empty runs no window and is
+    handed out as the input frame at `out_depth`, `unmatted` is the increasing list of those handed out so far, none of them is ever
+    in `recomputed`, and `assumed` leaves them out.  `roi` may also be the mattes' bounding box (`roi="matte"`)."""
 
     def __init__(self, model, frames: Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
                  out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None, ensemble: int = 1, roi=None,
                  roi_feather: int = 0, bar_params: Optional[dict] = None, horizon: Optional[int] = None, sharp: str = "deblur",
-                 fields: Optional[str] = None):
+                 fields: Optional[str] = None, matte: Optional[Mattes] = None):
         self.fields = check_fields(fields)
         if self.fields is not None:
             if tiles is not None or roi is not None:
@@ -357,6 +369,8 @@ class ClipRun:
         self.model, self.frames = model, frames
         self.sharp = check_sharp(sharp)
         self.kept = []                   # sharp="keep": the frames handed out as their input, in order
+        self.matte = matte               # the clip's mattes (`clip.Mattes`), or None
+        self.unmatted = []               # matte=: the frames whose matte is empty, handed out as their input, in order
         self._roi = roi                  # None, a rectangle, or "auto" while the scan has not run
         self.roi_feather = roi_feather
         self.bar_params = dict(bar_params or {})
@@ -383,6 +397,12 @@ class ClipRun:
 
     @property
     def roi(self):
+        if isinstance(self._roi, str) and self._roi == "matte":     # the mattes' bounding box, grown and clamped; all empty: the path without
+            found = self.matte.bbox()
+            self._roi = None if found is None else roi_of(found, self.frames.H, self.frames.W)
+            if self._roi is not None:
+                check_roi_feather(self.roi_feather, *self._roi[2:], lambda _: f"does not fit the rectangle {self._roi} that "
+                                  f"roi=\"matte\" found: at most min({ROI_FEATHER_MAX}, h // 2, w // 2)")
         if isinstance(self._roi, str):   # "auto": the bar rule on the extent maxima of the sampled frames; no bars: the path without
             fr, bp = self.frames, self.bar_params
             ext = active_area(fr, self.device, bp.get("frames", 64))
@@ -406,7 +426,9 @@ class ClipRun:
     @property
     def assumed(self) -> list:
         a = self._source.assumed
-        return a if self.sharp != "keep" else [i for i in a if self._source.label(i) != 1]
+        if self.sharp == "keep":
+            a = [i for i in a if self._source.label(i) != 1]
+        return a if self.matte is None else [i for i in a if not self.matte.empty(i)]
 
     def __iter__(self):
         return self
@@ -434,6 +456,10 @@ class ClipRun:
         pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4), thread_name_prefix="speinet-video")
         # frames (uint8, or uint16 for a deep clip), decoded and uploaded once each; a y4m clip's as planar bytes, made RGB on the device
         cache = FrameCache(pool, fr.host, dev, convert=None if fr.yuv is None else (lambda planar: fr.rgb(planar)[0]))
+        # mattes, one byte per pixel, through a cache of their own (a static matte is uploaded once: its one key stays)
+        mt = self.matte
+        mcache = None if mt is None else FrameCache(pool, mt.host, dev)
+        mats = {}                        # per window in flight: its frame's matte on the device, for the blend (and a recompute's)
         K = self.ensemble
         members = ens.MEMBERS[K]         # every window runs once per member (and tile): K - 1 transformed copies of its input
         enc = EncoderCache(EncoderCache().capacity * nt * K)
@@ -484,16 +510,38 @@ class ClipRun:
 
         keep = self.sharp == "keep"
 
+        def unmatted(k):
+            """Is the matte of frame k empty?  A stream that has a frame k and no matte for it ends here."""
+            if mt is None:
+                return False
+            if not mt.static and k >= mt.T:
+                raise ValueError(f"frame {k} has no matte: the stream outruns its matte of {mt.T} frames")
+            return mt.empty(k)
+
         def kept(k):
-            """Is frame k (planned already, so labelled) handed out as its input, with no window of its own?"""
-            return keep and src.label(k) == 1
+            """Is frame k (planned already, so labelled) handed out as its input, with no window of its own: labelled sharp under
+            sharp="keep", or with an empty matte?"""
+            return (keep and src.label(k) == 1) or unmatted(k)
+
+        def matte(k):
+            return mt.device(k) if mt.on_device(k) else mcache.get_dev(mt.key(k))
+
+        def blend(k, dst):
+            """The deblurred frame where the matte says, the input elsewhere: one launch on the packed frame, in place, behind
+            whichever egress wrote it."""
+            ops.frame_matte(centres[k], dst, mats[k], out_depth, None if depth == 8 else depth, mt.invert, out=dst)
 
         def request(k):
             """The frames that steps k .. k + PREFETCH will ask the cache for: a window's keys; a kept frame itself, which no running
             window need hold (the middle of a run of sharp frames)."""
-            for j in range(k, min(k + 1 + PREFETCH, len(plan))):
+            ahead = range(k, min(k + 1 + PREFETCH, len(plan)))
+            if mt is not None and not mt.static:           # decoded on the worker threads, in front of the `empty` that `kept` asks for
+                mt.prefetch(pool, [j for j in ahead if j < mt.T])
+            for j in ahead:
                 keys = [j] if kept(j) else plan[j]["keys"]
                 cache.request([i for i in keys if i is not ZERO and not fr.on_device(i)])
+                if mt is not None and not kept(j) and not mt.on_device(j):
+                    mcache.request([mt.key(j)])
 
         def stage(k):
             """What step k needs one step ahead: window k's input, or None (and the frame's `seconds` entry) for a kept frame."""
@@ -526,8 +574,10 @@ class ClipRun:
                     x[:, j].zero_()
                 else:
                     ingest(frame(key), x, j)
-            if roi is not None:
+            if roi is not None or mt is not None:
                 centres[k] = frame(plan[k]["window"][n // 2])     # uploaded just now: the frame that window k deblurs
+            if mt is not None:
+                mats[k] = matte(k)
             xs = [x] + [ops.planes_d4(x, g) for g in members[1:]]     # T_g of all its planes, one launch each (a zeroed frame stays zero)
             self.seconds.append([time.time() - t0, 0.0])
             return xs
@@ -556,9 +606,12 @@ class ClipRun:
                     v.record_stream(lane)
                 dst.record_stream(lane)
                 y = parts(part)
-                if roi is not None:
+                if k in centres:
                     centres[k].record_stream(lane)
                 egress(y, dst, flags[slot:slot + 1], k)
+                if mt is not None:
+                    mats[k].record_stream(lane)
+                    blend(k, dst)
                 flags_host[slot:slot + 1].copy_(flags[slot:slot + 1], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
@@ -578,6 +631,8 @@ class ClipRun:
                 m.precision, m.corr_precision, m.use_graph = keep
             slot = k % FLAG_RING
             egress(y, dst, flags[slot:slot + 1], k)          # a region of interest: the same paste
+            if mt is not None:
+                blend(k, dst)                                # and the same blend behind it
             if int(flags[slot].item()):
                 raise FloatingPointError(f"non-finite values in deblurred frame {k} in bf16x3 arithmetic as well: the input or the "
                                          "checkpoint is at fault")
@@ -594,7 +649,10 @@ class ClipRun:
             cur = torch.cuda.current_stream(dev)
             if x is None:                                  # a kept frame: no window ran, so there is no flag to read
                 cur.wait_event(e)
-                self.kept.append(k)
+                if keep and src.label(k) == 1:
+                    self.kept.append(k)
+                if unmatted(k):
+                    self.unmatted.append(k)
                 if cur != home:
                     t.record_stream(cur)
                 return k, t
@@ -608,6 +666,7 @@ class ClipRun:
             else:
                 cur.wait_event(e)
             centres.pop(k, None)
+            mats.pop(k, None)
             if cur != home:
                 t.record_stream(cur)
             return k, t
@@ -643,6 +702,8 @@ class ClipRun:
                 with torch.no_grad(), torch.cuda.device(dev):
                     got = hand_out()
                 yield got
+            if mt is not None and not mt.static and mt.T != len(plan):       # a stream: its length is known now
+                raise ValueError(f"the matte holds {mt.T} mattes for a stream of {len(plan)} frames: a per-frame matte has one per frame")
         finally:
             pool.shutdown(wait=False, cancel_futures=True)
             if self.horizon is not None:
@@ -653,7 +714,8 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
                 detector=None, cuts=None, cut_params: Optional[dict] = None, yuv: Optional[dict] = None,
                 depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20, feather: int = 0,
                 ensemble: int = 1, roi=None, roi_feather: int = 0, bar_params: Optional[dict] = None, stream=False,
-                horizon: int = 48, sharp: str = "deblur", fields: Optional[str] = None) -> ClipRun:
+                horizon: int = 48, sharp: str = "deblur", fields: Optional[str] = None, matte=None,
+                matte_invert: bool = False) -> ClipRun:
     """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
     or uint16 frames when `out_depth` is 10 or 12.
 
@@ -764,6 +826,42 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              stream whose `interlace` is "t" or "b" needs `fields="split"` said: there is no silent default.  An extension beyond the
              reference; no trained checkpoint exists here, so nothing is claimed about quality.
 
+    matte  — None (the default): launch for launch the path without this argument.  Otherwise an 8-bit mask that says how much of the
+             deblurred result every pixel gets.  Write a for the input frame's sample at the output depth (what `sharp="keep"` and
+             the outside of `roi` hand out; for a y4m clip the input frame is the RGB frame made from it), b for the sample that the
+             same call without `matte=` hands out there, and m for the pixel's matte byte (255 - m under `matte_invert`).  Every
+             sample of the frame handed out is
+                 (a * (255 - m) + b * m + 127) // 255
+             in exact integers (at most 4095 * 255 + 127): m = 0 gives a, m = 255 gives b, a == b gives a for every m, and swapping
+             a with b under the inverted matte gives the same value.  So a matte of 255 everywhere is the run without a matte, bit
+             for bit, and a matte of 0 everywhere is the input.  The matte has the size of the frames as given and is cropped as
+             they are under `crop`.  Static (one for the clip): a uint8 or bool [H,W] numpy array or torch tensor (host or device; a
+             bool matte is 0 / 255), or the path of an image file, decoded to one 8-bit channel (PIL `convert("L")`).  Per frame
+             (T of them: any other length is a ValueError): a [T,H,W] array or tensor; a list of [H,W] arrays or of image paths
+             (decoded on the worker threads, prefetched as the frames are); a directory of images, in file-name order; an 8-bit
+             `Cmono` y4m file or `y4m.Y4MReader`, whose luma bytes are the matte AS STORED: m = 255 needs full-range grey (a
+             limited-range white is 235).  Mattes cross PCIe as 1 byte per pixel through a frame cache of their own.
+             A frame whose matte (in effect: after `matte_invert`) is 0 everywhere runs NO window: it takes the kept-frame path
+             (one `ops.frame_requant`, no lane, no flag slot), is never in `recomputed`, is left out of `assumed`, and is listed,
+             in order, in `ClipRun.unmatted` (`ClipRun.kept` stays what it is).  Every other frame keeps its plan entry; unmatted
+             frames still serve as neighbours and references, as inputs.  Emptiness is decided on the host for host mattes, and
+             with one reduction and one sync at the start for a device-resident [T,H,W] tensor.
+             The blend is one more launch on the packed frame (`ops.frame_matte`, in place) behind whichever egress ran, so it
+             composes: with `sharp="keep"` a kept frame is the input and the blend is skipped; with `roi` / `roi_feather` the paste
+             runs first, then the blend over the whole frame (outside the rectangle a == b); with `tiles` / `feather` it runs
+             behind the stitch; with `fields="split"` on the woven frame; `ensemble`, `out_depth`, deep input, `cuts`, `out`,
+             `crop` and every y4m layout are unchanged behind it.  A non-finite value anywhere in the egress's frame still sends the
+             window to the bf16x3 recompute, wherever the matte is 0 (conservative, simple), and the blend runs again behind the
+             recompute's egress.  With `stream=True` a static matte or an indexable per-frame matte is accepted (a stream that
+             outruns its matte is a ValueError naming the frame; an iterator of mattes is not built).
+             `roi="matte"`: the region of interest is the union bounding box of the non-zero matte samples of all frames, grown
+             by 20 pixels on every side (the `shave` default, so the rectangle's reflect pad does not sit on the subject's edge),
+             then symmetrically to at least 20x20, and clamped to the frame; `ClipRun.roi` holds it and everything `roi` says about
+             labels, cuts and the plan applies.  It needs every matte up front (one pass over them before the first window), so it is
+             refused with `stream=True` unless the matte is static.  An all-empty clip never calls the model.
+             An extension beyond the reference; no trained checkpoint exists here, so nothing is claimed about quality.
+    matte_invert — with `matte` only: the matte in effect is 255 - m.
+
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
     holds a NaN or an infinity (half operands do not saturate) is recomputed in bf16x3 arithmetic, as the harness does: its index goes
@@ -771,6 +869,10 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     ensemble = ens.check_size(ensemble)                    # in front of everything else: no frame is looked at
     sharp = check_sharp(sharp)
     fields = check_fields(fields)
+    if matte is None and matte_invert:
+        raise ValueError("matte_invert=True needs matte=: there is no matte to invert")
+    if matte is None and isinstance(roi, str) and roi == "matte":
+        raise ValueError("roi=\"matte\" needs matte=: the rectangle is the bounding box of the mattes")
     if fields is not None and (tiles is not None or roi is not None):
         raise ValueError(f"fields={fields!r} with {'tiles=' if tiles is not None else 'roi='} is not built: the fields of a frame run as the "
                          "two parts of its window, and the table of parts is taken by the tiles or the rectangle")
@@ -814,6 +916,10 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
                              "the rectangle (y0, x0, h, w)")
     # a stream's `fr.T` is None: what is measured against the clip's length is then checked by `StreamPlan` as the stream goes
     fr = frames_of(frames, crop, yuv, depth)
+    mt = None if matte is None else mattes_of(matte, fr.T, *fr.src, crop, matte_invert)
+    if stream and mt is not None and not mt.static and isinstance(roi, str) and roi == "matte":
+        raise ValueError("roi=\"matte\" with stream=True and a per-frame matte: the bounding box is found in one pass over every matte "
+                         "before the first window, and a stream's length is not known; give the rectangle (y0, x0, h, w) or a static matte")
     if fields is not None:
         if fr.H % 2 or fr.H // 2 < MIN_SIZE:
             raise ValueError(f"fields={fields!r}: a {fr.W}x{fr.H} frame does not split into two fields of at least {MIN_SIZE} rows "
@@ -826,7 +932,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
         h, w = (fr.H, fr.W) if roi is None else roi[2:]
         check_roi_feather(roi_feather, h, w, lambda bound: f"is outside 0..{bound}: at most {ROI_FEATHER_MAX} and half of the {w}x{h} rectangle")
     elif roi is not None:
-        roi = roi_of(roi, fr.H, fr.W)    # "auto", or a ValueError for any other string
+        roi = roi_of(roi, fr.H, fr.W)    # "auto" or "matte", or a ValueError for any other string
         check_roi_feather(roi_feather, fr.H, fr.W, lambda bound: f"is outside 0..{bound}: at most {ROI_FEATHER_MAX} and half of the "
                           f"rectangle, which lies inside the {fr.W}x{fr.H} frame")
     if out_depth is not None and (isinstance(out_depth, bool) or out_depth not in y4m.DEPTHS):
@@ -852,7 +958,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     if tp is not None and tp.n == 1:
         tp = None                        # one tile that spans the frame: the untiled path
     return ClipRun(model, fr, lab, out, numbers, detector, cuts, cut_params, out_depth, tp, ensemble, roi, int(roi_feather), bar_params,
-                   horizon if stream else None, sharp, fields)
+                   horizon if stream else None, sharp, fields, mt)
 
 
 def _inputs(spec: str) -> list:
@@ -861,12 +967,12 @@ def _inputs(spec: str) -> list:
 
 
 def parse_roi(text: str):
-    """`--roi`: 'none' -> None, 'auto' -> "auto", 'Y,X,H,W' -> (y0, x0, h, w).  Raises ValueError with the reason."""
-    if text in ("none", "auto"):
-        return None if text == "none" else "auto"
+    """`--roi`: 'none' -> None, 'auto' -> "auto", 'matte' -> "matte", 'Y,X,H,W' -> (y0, x0, h, w).  Raises ValueError with the reason."""
+    if text in ("none", "auto", "matte"):
+        return None if text == "none" else text
     parts = text.split(",")
     if len(parts) != 4 or not all(p.strip().lstrip("+").isdigit() for p in parts):
-        raise ValueError(f"{text!r} is not none, auto or Y,X,H,W (four whole numbers: top, left, height, width)")
+        raise ValueError(f"{text!r} is not none, auto, matte or Y,X,H,W (four whole numbers: top, left, height, width)")
     return tuple(int(p) for p in parts)
 
 
@@ -976,10 +1082,17 @@ def main(argv=None) -> None:
                    "and its mirror), 4 (the flips) or 8 (flips and transpositions) transformed copies and average the results; K times "
                    "the work (default 1: off)")
     p.add_argument("--roi", default="none", help="region of interest: 'none' (the default: whole frames), 'auto' (the active picture area "
-                   "of letterboxed or pillarboxed footage, found from the clip) or Y,X,H,W (top, left, height, width; at least 20x20): "
+                   "of letterboxed or pillarboxed footage, found from the clip), 'matte' (with --matte: the bounding box of the mattes, "
+                   "grown by 20 pixels) or Y,X,H,W (top, left, height, width; at least 20x20): "
                    "only that rectangle is deblurred, the rest of every frame is the input's")
     p.add_argument("--roi_feather", type=int, default=0, help="with --roi: blend the deblurred rectangle with the input over the N pixels "
                    "inside every side of it that is not a side of the frame (0..min(200, H/2, W/2); default 0: a hard edge)")
+    p.add_argument("--matte", default=None, help="an 8-bit matte that says how much of the deblurred frame every pixel gets (255: all of "
+                   "it, 0: the input frame): an image file (one matte for the clip), or one matte per frame as a directory of images, a "
+                   "glob (both in file-name order) or an 8-bit Cmono .y4m file, whose luma bytes are used as stored (255 needs full-range "
+                   "grey).  Images are read as one 8-bit channel.  A frame whose matte is empty runs no window and is written as the "
+                   "input frame (y4m in and out with the input's chroma layout, depth and range: the input's record, byte for byte)")
+    p.add_argument("--matte_invert", action="store_true", help="with --matte: use 255 - m, deblur where the matte is black")
     p.add_argument("--sharp", choices=SHARP, default="deblur", help="what becomes of a frame labelled sharp (by --labels or the detector): "
                    "'deblur' (the default) runs its window like any other; 'keep' runs none and writes the input frame (y4m in and out "
                    "with the input's chroma layout, depth and range: the input's record, byte for byte).  The blurry frames are the "
@@ -1018,6 +1131,18 @@ def main(argv=None) -> None:
                          "of a window, and the table of parts is taken")
     if a.roi_feather != 0 and roi is None:
         raise SystemExit(f"--roi_feather {a.roi_feather}: needs --roi: it blends the edge of the region of interest")
+    if a.matte is None and a.matte_invert:
+        raise SystemExit("--matte_invert: needs --matte: there is no matte to invert")
+    if a.matte is None and a.roi == "matte":
+        raise SystemExit("--roi matte: needs --matte: the rectangle is the bounding box of the mattes")
+    matte = None
+    if a.matte is not None:                                # a file (an image or a .y4m clip), a directory, or a glob of images
+        matte = a.matte if os.path.isfile(a.matte) or os.path.isdir(a.matte) else _inputs(a.matte)
+        if not matte or (os.path.isdir(a.matte) and not _inputs(a.matte)):
+            raise SystemExit(f"--matte {a.matte}: no image file, directory of images, glob or .y4m file of that name")
+        if a.stream and a.roi == "matte" and not (isinstance(matte, str) and os.path.isfile(matte) and not matte.lower().endswith(".y4m")):
+            raise SystemExit("--roi matte with --stream: the bounding box is found from every matte before the first window; give "
+                             "Y,X,H,W, or one image as the matte of the whole clip")
     to_stdout = a.output == "-"
     to_y4m = to_stdout or a.output.lower().endswith(".y4m")
     log = sys.stderr if to_stdout else sys.stdout
@@ -1076,7 +1201,8 @@ def main(argv=None) -> None:
         out_depth = 8
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
                       yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather, ensemble=a.ensemble,
-                      roi=roi, roi_feather=a.roi_feather, stream=a.stream, horizon=a.horizon, sharp=a.sharp, fields=fields)
+                      roi=roi, roi_feather=a.roi_feather, stream=a.stream, horizon=a.horizon, sharp=a.sharp, fields=fields,
+                      **({} if matte is None else dict(matte=matte, matte_invert=a.matte_invert)))
     out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
@@ -1100,6 +1226,8 @@ def main(argv=None) -> None:
         say(f"# y4m input C{reader.chroma}" + (f", output C{writer.chroma}" if writer is not None and writer.chroma != reader.chroma else ""))
     if fields is not None or tag != "p":
         say(f"# fields: {'split' if fields is not None else 'progressive'} (I{tag})")
+    if run.matte is not None:
+        say(f"# matte {a.matte}: {run.matte.describe()}")
     if run.roi is not None:
         say("# roi " + ",".join(str(v) for v in run.roi))
     said = 0                                               # a stream's cuts are reported as they are found
@@ -1111,9 +1239,9 @@ def main(argv=None) -> None:
             + (f", feather {run.tiles.feather}" if run.tiles.feather else ""))
     if run.ensemble > 1:
         say(f"# ensemble {run.ensemble}: members 0..{run.ensemble - 1}, {run.ensemble} forward passes per frame")
-    # a kept frame of a y4m clip leaves as the record it came in, when the output's layout, depth and range are the input's (the matrix
+    # a kept frame of a y4m clip (labelled sharp under --sharp keep, or with an empty matte) leaves as the record it came in, when the output's layout, depth and range are the input's (the matrix
     # is one for both sides): no colour conversion, no chroma resampling.  `run.frames.host(i)` is that record
-    as_read = (a.sharp == "keep" and writer is not None and reader is not None
+    as_read = ((a.sharp == "keep" or run.matte is not None) and writer is not None and reader is not None
                and (writer.layout, writer.depth, writer.range, writer.frame_bytes) == (run.frames.yuv[0], reader.depth, reader.range,
                                                                                      reader.frame_bytes))
     if a.sharp == "keep":
@@ -1137,7 +1265,8 @@ def main(argv=None) -> None:
                     say(f"# cut before {names[c]}")
                 said = len(run.cuts)
             is_kept = bool(run.kept) and run.kept[-1] == i
-            if is_kept and as_read:                        # a copy: a stream gives the record up a few frames on; the one writer keeps order
+            is_unmatted = bool(run.unmatted) and run.unmatted[-1] == i
+            if (is_kept or is_unmatted) and as_read:                        # a copy: a stream gives the record up a few frames on; the one writer keeps order
                 records.put(write, run.frames.host(i))
             elif to_y4m:
                 woven = fields is not None and layout in (y4m.CENTER, y4m.LEFT)     # the other layouts convert row by row
@@ -1147,7 +1276,7 @@ def main(argv=None) -> None:
             else:
                 ring.land(lambda buf, path=os.path.join(a.output, names[i]): imwrite(path, buf.numpy()), frame)
             now = time.time()
-            branch = "kept" if is_kept else "no-reference" if run.plan[i]["zero_pre"] else "reference"
+            branch = "kept" if is_kept else "unmatted" if is_unmatted else "no-reference" if run.plan[i]["zero_pre"] else "reference"
             say(f"> {names[i]} {branch} {now - t_prev:.3f}s")
             if run.recomputed and run.recomputed[-1] == i:
                 say(f"# {names[i]}: non-finite value in the {a.precision} frame, recomputed in bf16x3 ({len(run.recomputed)} so far)")
@@ -1159,6 +1288,8 @@ def main(argv=None) -> None:
     dt = time.time() - t0
     if a.sharp == "keep":
         say(f"# kept {len(run.kept)} of {done} frames")
+    if run.matte is not None:
+        say(f"# unmatted {len(run.unmatted)} of {done} frames")
     say(f"# {done} frames {W}x{H} in {dt:.2f}s: {done / dt:.2f} frames/s ({a.precision}"
         + (f", ensemble {run.ensemble}" if run.ensemble > 1 else "")
         + (f", streamed with horizon {a.horizon}: {len(run.assumed)} frames assumed" if a.stream else "") + ")")
