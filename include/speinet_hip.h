@@ -684,6 +684,42 @@ int spei_frame_matte_u8(const void* frame, int in_depth, const unsigned char* de
 int spei_frame_matte_u16(const void* frame, int in_depth, const uint16_t* deb, const unsigned char* matte, int invert, uint16_t* dst,
                          int H, int W, int depth, spei_stream_t stream);
 
+/* Automatic blur mattes of the clip API (video.deblur_clip(..., matte="auto"), speinet_amd/blurmap.py; an extension beyond the
+ * reference, so no reference code is cited): where in a frame is the picture blurred?  Integers throughout; tests/blurmap_ref.py is
+ * the numpy statement.  src = N packed uint8 [H][W][3] frames, frame_stride bytes apart (rows packed), 1 <= N <= 65535.  The frame
+ * is cut into cells of 16x16 pixels, ch = ceil(H / 16) by cw = ceil(W / 16); the edge cells are partial, n < 256 pixels.  On the
+ * luma Y = (77 R + 150 G + 29 B + 128) >> 8 of spei_frame_pair_stats, taken at the clamped index outside the frame, per pixel
+ *     horizontally  d = 9 * (Y(y,x) - Y(y,x-1)),  b = Y(y,x+4) - Y(y,x-5)    (b: the adjacent difference of two 9-tap box sums)
+ *     vertically    d = 9 * (Y(y,x) - Y(y-1,x)),  b = Y(y+4,x) - Y(y-5,x)
+ *     D = d * d,  V = max(0, d * d - b * b)
+ * and per cell the four sums over its pixels, sums[N][ch][cw][4] = (sum D_h, sum V_h, sum D_v, sum V_v) as int64 (sums may be NULL).
+ * A direction is textured iff sum D >= (81 * flat^2 * n) << (2 * (depth - 8)) and blurred iff textured and 256 * sum V < thr * sum D;
+ * cells[N][ch][cw] is 255 where either direction is blurred and 0 elsewhere.  thr = 0 lights nothing; thr = 257 lights every
+ * textured direction with sum D > 0.  One launch: a workgroup stages the luma of a strip of four cells and its halo in LDS, one wave
+ * reduces one cell; no workspace, no atomics, exact whatever the launch order.  A group's 12 samples move as three words where
+ * W % 4 == 0 and the base and the stride lie on a 4-byte (8-byte for 16-bit samples) boundary, sample by sample otherwise.
+ * Non-zero before anything is launched: src or cells NULL; N outside 1..65535; H or W below 1, 3 * H * W >= 2^31 or more than 65535
+ * rows of cells; N > 1 with a stride below one frame; thr outside 0..257; flat outside 0..255; sums off an 8-byte boundary; cells
+ * or sums overlapping src or each other.
+ * spei_blur_cells_u16: the same on uint16 frames of `depth` 10 or 12 (anything else is refused; frame_stride in BYTES and even, src
+ * 2-byte aligned, a word above D reads as D), on the depth-bit luma.
+ * spei_blur_matte: cells = n verdict maps [n][ch][cw] (1 <= n <= 8) for H x W frames -> matte[H][W], one byte per pixel.  The maps
+ * are joined by their maximum, cell by cell (the hold over a window's frames), dilated by `grow` cells (0..4: the maximum over a
+ * (2 * grow + 1)^2 neighbourhood, zeros outside the grid; cell_out[ch][cw], or NULL, receives this map), and interpolated between
+ * cell centres: with u = 2 * y + 17, i0 = u / 32 - 1, i1 = i0 + 1 (both clamped into 0..ch-1), wy = u % 32, and j0, j1, wx from x
+ * alike,
+ *     m = ((32-wy) * (32-wx) * c[i0][j0] + (32-wy) * wx * c[i0][j1] + wy * (32-wx) * c[i1][j0] + wy * wx * c[i1][j1] + 512) / 1024
+ * so an all-255 map gives 255 everywhere, an all-0 map 0, and the ramp between a lit and an unlit cell is 16 pixels wide.  One
+ * launch (a workgroup first puts the dilated cells its 16x64 pixel tile needs into LDS); dword stores where W % 4 == 0 and matte is
+ * 4-byte aligned, byte stores otherwise.  Non-zero before anything is launched: cells or matte NULL; n outside 1..8; grow outside
+ * 0..4; H or W below 1 or H * W >= 2^31; matte or cell_out overlapping cells or each other. */
+int spei_blur_cells_u8(const unsigned char* src, int64_t frame_stride, int N, int H, int W, int thr, int flat, unsigned char* cells,
+                       int64_t* sums, spei_stream_t stream);
+int spei_blur_cells_u16(const uint16_t* src, int64_t frame_stride, int N, int H, int W, int depth, int thr, int flat,
+                        unsigned char* cells, int64_t* sums, spei_stream_t stream);
+int spei_blur_matte(const unsigned char* cells, int n, int grow, int H, int W, unsigned char* matte, unsigned char* cell_out,
+                    spei_stream_t stream);
+
 /* The extent of the picture in N packed uint8 [H][W][3] frames, frame_stride bytes apart (rows packed; the frame-size bound of
  * spei_frames_u8_in), for the clip API's bar rule (video.find_bars): on the integer luma of spei_frame_pair_stats,
  * Y = (77 R + 150 G + 29 B + 128) >> 8, rowmax[y] (H ints) is the maximum of Y over row y of all N frames and colmax[x] (W ints) the

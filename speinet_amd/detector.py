@@ -161,14 +161,19 @@ def clip_batches(fr, device, batch: int = DETECT_BATCH):
             b, i0, done = b + 1, i0 + n, i0 + n
 
 
-def clip_analysis(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, features: bool = True, pair_stats: bool = False):
+def clip_analysis(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, features: bool = True, pair_stats: bool = False,
+                  blur=None):
     """The analysis of a clip batch by batch, for a whole clip (`clip_pass`) and for a stream (speinet_amd.video, as its frames
     arrive): per `clip_batches` batch, yields (first frame index, the six focus measures [n,6] float32 or None when not `features`,
     the batch's `ops.frame_pair_stats` (sad [n] int64, or [n-1] for the first batch; hist [n,64] int64) or None when not
     `pair_stats`), on the current stream of `device`.  A deep clip goes through `ops.frames_u16_in` and `ops.frame_pair_stats_u16`
     (its sad is in units of the clip's own depth).  The last frame of a batch is kept as `prev` of the next, so a pair that straddles
     two batches is counted like any other: device memory is bounded by one batch plus one frame.  The consumer sets grad mode and the
-    current device around every `next`."""
+    current device around every `next`.
+    `blur` (a `blurmap.BlurParams`; None: what is yielded is exactly the above): every yield carries a fourth item, the batch's blur
+    verdict maps, uint8 [n,ch,cw] on the device (`ops.blur_cells` with the parameters' `thr` and `flat`: one more launch per batch on
+    the frames as this pass sees them), for `deblur_clip(..., matte="auto")`.  With neither `features` nor `pair_stats` the pass
+    measures the cells alone: for a clip whose labels and cuts were given that is one more upload of a host clip."""
     from . import ops
     dev = torch.device(device)
     if pair_stats and batch < 2:
@@ -190,17 +195,24 @@ def clip_analysis(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, 
             if fr.T is None or i0 + len(frames) < fr.T:      # a stream that has not ended may have a next batch
                 prev = torch.empty_like(frames[-1]) if prev is None else prev
                 prev.copy_(frames[-1])
-        yield i0, feats, stats
+        if blur is None:
+            yield i0, feats, stats
+        else:
+            yield i0, feats, stats, ops.blur_cells(frames, None if fr.depth == 8 else fr.depth, blur.thr, blur.flat)
 
 
-def clip_pass(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, features: bool = True, pair_stats: bool = False):
+def clip_pass(fr, device, kernel_size: int = 11, batch: int = DETECT_BATCH, features: bool = True, pair_stats: bool = False, blur=None,
+              cells=None):
     """One `clip_analysis` pass over a whole clip: the six focus measures of every frame ([T,6] float32, or None when not `features`),
     the pair statistics of `ops.frame_pair_stats` over the whole clip ((sad int64 [T-1], hist int64 [T,64]), or None when not
-    `pair_stats`), or both, all on `device`."""
+    `pair_stats`), or both, all on `device`.  With `blur` (a `blurmap.BlurParams`) the pass also measures the blur cells, and
+    `cells(first frame index, verdict maps)` is called with every batch's."""
     dev = torch.device(device)
     feats, sads, hists = [], [], []
     with torch.no_grad(), torch.cuda.device(dev):
-        for _, f, st in clip_analysis(fr, dev, kernel_size, batch, features, pair_stats):
+        for i0, f, st, *maps in clip_analysis(fr, dev, kernel_size, batch, features, pair_stats, blur):
+            if maps:
+                cells(i0, maps[0])
             if features:
                 feats.append(f)
             if pair_stats:

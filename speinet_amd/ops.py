@@ -743,6 +743,80 @@ def frame_matte(frame: torch.Tensor, deb: torch.Tensor, matte: torch.Tensor, out
     return out
 
 
+BLUR_CELL = 16                  # the cell of the blur map: 16x16 pixels (csrc/blur_map.hip)
+BLUR_MAPS_MAX = 8               # verdict maps one `blur_matte` launch joins
+BLUR_GROW_MAX = 4
+
+
+def blur_cell_shape(h: int, w: int) -> tuple:
+    """(ch, cw) = (ceil(h / 16), ceil(w / 16)): the cell grid of an h x w frame."""
+    return (int(h) + BLUR_CELL - 1) // BLUR_CELL, (int(w) + BLUR_CELL - 1) // BLUR_CELL
+
+
+def blur_cells(frames: torch.Tensor, depth: Optional[int] = None, thr: int = 192, flat: int = 2, sums: bool = False):
+    """The blur verdict of every 16x16 cell of packed frames [N,H,W,3] on the device (any frame stride), uint8 (`depth` None) or uint16
+    of `depth` 10 or 12 bits (a word above D = 2^depth - 1 reads as D) -> cells uint8 [N,ch,cw], 255 = blurred, with ch = ceil(H / 16),
+    cw = ceil(W / 16) (edge cells are partial: n < 256 pixels); with `sums` -> (cells, int64 [N,ch,cw,4]), the cell's four sums
+    (sum D_h, sum V_h, sum D_v, sum V_v).  Integers throughout, on the luma Y = (77 R + 150 G + 29 B + 128) >> 8 at the frame's
+    depth, taken at the clamped index outside the frame.  Per pixel, horizontally: d = 9 (Y(y,x) - Y(y,x-1)),
+    b = Y(y,x+4) - Y(y,x-5) (the adjacent difference of the 9-tap box sums centred on x and x - 1), D_h = d d,
+    V_h = max(0, d d - b b): how much of the adjacent-pixel variation a 9-tap box removes.  Vertically the same with y and x exchanged.
+    A direction is textured iff sum D >= 81 flat^2 n << 2 (depth - 8) (its RMS adjacent difference is at least `flat` 8-bit levels)
+    and blurred iff textured and 256 sum V < thr sum D; a cell is lit iff either direction is blurred.  `thr` 0..257 (0 lights
+    nothing, 257 every textured direction with sum D > 0), `flat` 0..255.  One launch on the current stream (csrc/blur_map.hip), no
+    host sync."""
+    assert frames.is_cuda and frames.dtype in (torch.uint8, torch.uint16) and frames.dim() == 4
+    deep = frames.dtype == torch.uint16
+    if deep:
+        depth = _depth(depth)
+    elif depth not in (None, 8):
+        raise ValueError(f"depth= applies to uint16 frames only; the frames are {frames.dtype}")
+    n, h, w, c = frames.shape
+    assert c == 3 and frames.stride()[1:] == (w * 3, 3, 1), "frames must be packed [H,W,3] (any frame stride)"
+    dev = frames.device
+    ch, cw = blur_cell_shape(h, w)
+    cells = torch.empty(n, ch, cw, dtype=torch.uint8, device=dev)
+    s = torch.empty(n, ch, cw, 4, dtype=torch.int64, device=dev) if sums else None
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        head = (_vp(frames.data_ptr()), frames.element_size() * frames.stride(0), n, h, w)
+        tail = (int(thr), int(flat), _vp(cells.data_ptr()), _vp(s.data_ptr() if sums else 0), st)
+        if deep:
+            _lib.check(lib.spei_blur_cells_u16(*head, depth, *tail), "spei_blur_cells_u16")
+        else:
+            _lib.check(lib.spei_blur_cells_u8(*head, *tail), "spei_blur_cells_u8")
+    return (cells, s) if sums else cells
+
+
+def blur_matte(cells: torch.Tensor, H: int, W: int, grow: int = 1, out: Optional[torch.Tensor] = None,
+               cell_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The pixel matte of verdict maps: `cells` uint8 [n,ch,cw] on the device (contiguous; n = 1..8, (ch, cw) the cell grid of an
+    H x W frame) -> uint8 [H,W].  The maps are joined by their maximum, cell by cell (the hold), dilated by `grow` cells (0..4: the
+    maximum over a (2 grow + 1)^2 neighbourhood, zeros outside), and interpolated bilinearly between cell centres in exact integers:
+    u = 2 y + 17, i0 = u // 32 - 1, i1 = i0 + 1 (both clamped into 0..ch-1), wy = u % 32, the same for x with j0, j1, wx, and
+    m = ((32-wy)(32-wx) c[i0][j0] + (32-wy) wx c[i0][j1] + wy (32-wx) c[i1][j0] + wy wx c[i1][j1] + 512) // 1024: all-255 gives 255,
+    all-0 gives 0, the ramp between a lit and an unlit cell is 16 pixels wide.  `out` (optional): the matte's destination, contiguous;
+    `cell_out` (optional): uint8 [ch,cw], receives the held and dilated cell map.  One launch on the current stream
+    (csrc/blur_map.hip), no host sync."""
+    assert cells.is_cuda and cells.dtype == torch.uint8 and cells.dim() == 3 and cells.is_contiguous()
+    H, W = int(H), int(W)
+    n, (ch, cw) = cells.shape[0], blur_cell_shape(H, W)
+    if tuple(cells.shape[1:]) != (ch, cw):
+        raise ValueError(f"cells has shape {tuple(cells.shape)}; a {W}x{H} frame has {ch}x{cw} cells")
+    dev = cells.device
+    if out is None:
+        out = torch.empty(H, W, dtype=torch.uint8, device=dev)
+    assert out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (H, W) and out.is_contiguous()
+    assert cell_out is None or (cell_out.device == dev and cell_out.dtype == torch.uint8 and tuple(cell_out.shape) == (ch, cw)
+                                and cell_out.is_contiguous())
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().spei_blur_matte(_vp(cells.data_ptr()), n, int(grow), H, W, _vp(out.data_ptr()),
+                                              _vp(cell_out.data_ptr() if cell_out is not None else 0), st), "spei_blur_matte")
+    return out
+
+
 def frame_extent(frames: torch.Tensor, depth: Optional[int] = None, out=None):
     """The extent of the picture in packed frames [N,H,W,3] on the device (any frame stride), uint8 (`depth` None) or uint16 of `depth`
     10 or 12 bits -> (rowmax int32 [H], colmax int32 [W]): the maximum over every row, and over every column, of all N frames of the

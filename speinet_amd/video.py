@@ -8,6 +8,7 @@
                                 [--out_depth 8|10|12] [--tiles none|auto|RxC] [--shave N] [--feather N] [--ensemble 1|2|4|8]
                                 [--roi none|auto|matte|Y,X,H,W] [--roi_feather N] [--stream [--horizon N]] [--sharp deblur|keep]
                                 [--fields auto|progressive|split] [--matte <image | dir | glob | matte.y4m> [--matte_invert]]
+                                [--matte auto [--matte_params thr=192,flat=2,grow=1,hold=1]] [--matte_out <matte.y4m>]
 
 (`-`: a YUV4MPEG2 stream on stdin / stdout, as `ffmpeg -f yuv4mpegpipe` writes and reads it; by default stdin is spooled to a temporary
 file on disk before the first frame is deblurred, with `--stream` it is deblurred as it arrives, see `main`)
@@ -81,6 +82,13 @@ and the dataset harness (speinet_amd.inference) runs every clip through `deblur_
     `FrameCache` of their own.  A frame whose matte is empty takes the kept-frame path (`ClipRun.unmatted`), and `roi="matte"` is the
     mattes' bounding box, grown by 20 pixels.  An extension beyond the reference; no trained checkpoint exists here, so nothing is
     claimed about quality.  Off by default.
+  * automatic blur mattes (`matte="auto"`, `--matte auto`; csrc/blur_map.hip, speinet_amd/blurmap.py): the mattes are measured, one per
+    frame, on the device.  Per cell of 16x16 pixels and per direction the re-blur measure says how much of the adjacent-pixel variation
+    a 9-tap box removes (`ops.blur_cells`, one launch per analysis batch, in the labelling pass where that sees the full frames); frame
+    k's cell map is the maximum over the frames of plan entry k's window, dilated, and its matte the bilinear interpolation between cell
+    centres (`ops.blur_matte`, one launch per matted frame).  `blurmap.AutoMattes` stands where a `clip.Mattes` does, so everything
+    behind the matte is the given matte's.  Four untuned design parameters (`matte_params=`).  An extension beyond the reference; no
+    trained checkpoint exists here, so nothing is claimed about quality.  Off by default.
 A frame whose size is not a multiple of 20 is padded at the bottom and right by reflection (torch F.pad mode "reflect", the padding
 SwinIR's `check_image_size` uses for window multiples) and the result is cropped back: csrc/frame_io.hip does both, the padding on
 the way in (with `numpy2tensor`'s values) and the crop on the way out (with `tensor2numpy`'s rounding).  The reference cannot run
@@ -102,7 +110,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import detector, engine, ensemble as ens, ops, tiles as tiling, y4m
+from . import blurmap, detector, engine, ensemble as ens, ops, tiles as tiling, y4m
+from .blurmap import MATTE_PARAMS, BlurParams  # noqa: F401
 from .clip import (IMAGE_EXTS, MIN_SIZE, FrameCache, Frames, HostRing, Mattes, RecordQueue, frames_of, imread, imwrite, mattes_of,  # noqa: F401
                    padded_size, reflect_index)
 from .plan import (ASSUMED_TAIL, CUT_PARAMS, MIN_HORIZON, ZERO, StreamCuts, StreamPlan, cuts_of, find_cuts, labels_of,  # noqa: F401
@@ -266,10 +275,12 @@ class _WholePlan:
         """Whatever is missing of the LD detector's labels and the scene cuts, in ONE pass over the clip, DETECT_BATCH frames at a time:
         upload, then gray planes (spei_frames_u8_in / spei_frames_u16_in) and focus measures, pair statistics (spei_frame_pair_stats /
         spei_frame_pair_stats_u16), or both.  A deep clip stays deep throughout.  With a region of interest the pass is handed the
-        clip's view through it, so the detector and the pair statistics see the cropped frames."""
+        clip's view through it, so the detector and the pair statistics see the cropped frames.  Under matte="auto" the pass also
+        measures the blur cells (one more launch per batch), when it sees the full frames and nobody has measured them yet."""
         run, p, fr = self.run, self.run.detector, self.run._view()
+        am = run.matte if isinstance(run.matte, blurmap.AutoMattes) and fr is run.frames and not run.matte.fed else None
         feats, stats = detector.clip_pass(fr, run.device, p.kernel_size, DETECT_BATCH, features=self._labels is None,
-                                          pair_stats=self._cuts is None)
+                                          pair_stats=self._cuts is None, **({} if am is None else dict(blur=am.params, cells=am.feed)))
         if feats is not None:
             self._labels = detector.predict(feats, p)
         if stats is not None:
@@ -292,8 +303,16 @@ class _ArrivingPlan:
                                   pixels=self.view.H * self.view.W, cut_params=run.cut_params)
         # what is held at once: the look-ahead of the plan, the analysis batch in front of it and the windows behind (`ClipRun._run`)
         run.frames.reserve(sp.horizon + 2 * DETECT_BATCH + PREFETCH + 4 + (run.cut_params.get("window", 2) - 2 if cuts is None else 0))
-        self.analysis = None if labels is not None and cuts is not None else detector.clip_analysis(
-            self.view, run.device, run.detector.kernel_size, DETECT_BATCH, features=labels is None, pair_stats=cuts is None)
+        # matte="auto": the blur cells are measured on the full frames, in the analysis pass when that sees them (also when labels
+        # and cuts were given: the pass then measures the cells alone), in a pass of its own beside it otherwise (a fixed roi), which
+        # reads the same frames of the ring in the same batches
+        am = self.am = run.matte if isinstance(run.matte, blurmap.AutoMattes) else None
+        shared = am is not None and self.view is run.frames
+        self.analysis = None if labels is not None and cuts is not None and not shared else detector.clip_analysis(
+            self.view, run.device, run.detector.kernel_size, DETECT_BATCH, features=labels is None, pair_stats=cuts is None,
+            **(dict(blur=am.params) if shared else {}))
+        self.cells = None if am is None or shared else detector.clip_analysis(
+            run.frames, run.device, run.detector.kernel_size, DETECT_BATCH, features=False, pair_stats=False, blur=am.params)
 
     labels = property(lambda self: np.asarray(self.sp.labels, dtype=np.int64))
     cuts = property(lambda self: self.sp.cuts)
@@ -307,9 +326,16 @@ class _ArrivingPlan:
     def _pump(self) -> None:
         """One DETECT_BATCH of the stream into the plan, as soon as its frames have arrived: the batch `_WholePlan._analyse` would run."""
         sp, analysis = self.sp, self.analysis
+        own = None if self.cells is None else next(self.cells, None)
+        if own is not None:
+            self.am.feed(own[0], own[3])
         if analysis is not None:
             item = next(analysis, None)
-            n = 0 if item is None else len(item[1] if item[1] is not None else item[2][1])
+            if item is not None and len(item) > 3:         # the batch's blur cells: they exist before its entries are planned
+                self.am.feed(item[0], item[3])
+            n = 0 if item is None else len(item[3] if len(item) > 3 else item[1] if item[1] is not None else item[2][1])
+        elif self.cells is not None:
+            n = 0 if own is None else len(own[3])
         else:
             n = self.view.upto(sp.fed + DETECT_BATCH) - sp.fed
         if n <= 0:
@@ -319,7 +345,7 @@ class _ArrivingPlan:
         elif analysis is None:
             sp.feed(count=n)
         else:
-            _, feats, stats = item
+            feats, stats = item[1], item[2]
             sad, hist = (None, None) if stats is None else _host_stats(stats, self.view.depth)
             sp.feed(None if feats is None else detector.predict(feats, self.run.detector), sad, hist, count=n)
 
@@ -355,7 +381,10 @@ class ClipRun:
     one plan for both parities.  `matte` is the clip's `clip.Mattes` or None; with one, every frame handed out is the blend of the
     input frame with the deblurred one that its matte says (`ops.frame_matte`), a frame whose matte is empty runs no window and is
     handed out as the input frame at `out_depth`, `unmatted` is the increasing list of those handed out so far, none of them is ever
-    in `recomputed`, and `assumed` leaves them out.  `roi` may also be the mattes' bounding box (`roi="matte"`)."""
+    in `recomputed`, and `assumed` leaves them out.  `roi` may also be the mattes' bounding box (`roi="matte"`).  Under `matte="auto"`
+    `matte` is a `blurmap.AutoMattes`, which measures the mattes on the device and whose `cells` holds the verdict maps on the host.
+    `handed_matte` is the device matte [H,W] (as given, before `matte_invert`) that the frame handed out last was blended with, or None
+    where it left as its input."""
 
     def __init__(self, model, frames: Frames, labels, out, numbers=None, detector_params=None, cuts=None, cut_params=None,
                  out_depth: Optional[int] = None, tiles: Optional[tiling.TilePlan] = None, ensemble: int = 1, roi=None,
@@ -369,7 +398,10 @@ class ClipRun:
         self.model, self.frames = model, frames
         self.sharp = check_sharp(sharp)
         self.kept = []                   # sharp="keep": the frames handed out as their input, in order
-        self.matte = matte               # the clip's mattes (`clip.Mattes`), or None
+        self.matte = matte               # the clip's mattes (`clip.Mattes`, or `blurmap.AutoMattes` under matte="auto"), or None
+        if isinstance(matte, blurmap.AutoMattes):
+            matte.bind(self)             # it measures this run's frames, and its plan entries name the windows it holds over
+        self.handed_matte = None         # the matte (device uint8 [H,W], as given: before `matte_invert`) that the frame handed out last was blended with; None: none was
         self.unmatted = []               # matte=: the frames whose matte is empty, handed out as their input, in order
         self._roi = roi                  # None, a rectangle, or "auto" while the scan has not run
         self.roi_feather = roi_feather
@@ -647,6 +679,8 @@ class ClipRun:
         def hand_out():
             k, t, e, x = ready.popleft()
             cur = torch.cuda.current_stream(dev)
+            if mt is not None:
+                self.handed_matte = None if x is None else mats.get(k)
             if x is None:                                  # a kept frame: no window ran, so there is no flag to read
                 cur.wait_event(e)
                 if keep and src.label(k) == 1:
@@ -715,7 +749,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
                 depth: Optional[int] = None, out_depth: Optional[int] = None, tiles=None, shave: int = 20, feather: int = 0,
                 ensemble: int = 1, roi=None, roi_feather: int = 0, bar_params: Optional[dict] = None, stream=False,
                 horizon: int = 48, sharp: str = "deblur", fields: Optional[str] = None, matte=None,
-                matte_invert: bool = False) -> ClipRun:
+                matte_invert: bool = False, matte_params: Optional[dict] = None) -> ClipRun:
     """Deblur a clip: an iterator of (index, [H,W,3] frame on the model's device), in frame order, one per input frame: uint8 frames,
     or uint16 frames when `out_depth` is 10 or 12.
 
@@ -860,7 +894,29 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
              labels, cuts and the plan applies.  It needs every matte up front (one pass over them before the first window), so it is
              refused with `stream=True` unless the matte is static.  An all-empty clip never calls the model.
              An extension beyond the reference; no trained checkpoint exists here, so nothing is claimed about quality.
+             matte="auto" (the string; a file of that name is "./auto"): the mattes are MEASURED, one per frame, on the device: where
+             is the picture blurred?  The frames as given (after `crop`) are cut into cells of 16x16 pixels; per cell and direction
+             the re-blur measure says how much of the adjacent-pixel variation a 9-tap box removes (`ops.blur_cells`, one launch per
+             analysis batch of 16 frames, in the labelling / cut pass when that sees the full frames; in one more pass over the clip,
+             one more upload of a host clip, when that pass sees a region of interest or does not run because `labels` and `cuts`
+             were given); a cell is lit where either direction has texture and a box removes little of it.  Frame k's cell map is the
+             maximum of the verdict maps of the frames of plan entry k's window (`hold`: it never crosses a cut and needs no frame
+             that a stream has not delivered by the time the window runs), dilated by `grow` cells, and its matte the bilinear
+             interpolation between cell centres, exact integers (`ops.blur_matte`, one launch per matted frame): a ramp of 16 pixels
+             between a lit and an unlit cell.  Everything behind the matte is what it is for a given one, and the result is that of
+             `matte=M` with M the [T,H,W] mattes so made, bit for bit: the blend, `ClipRun.unmatted` for a frame whose cell map is
+             empty (decided from the cell bytes on the host; no window runs), `sharp="keep"`, tiles, ensemble, deep clips, `out`,
+             `crop`, cuts, every y4m layout, the bf16x3 recompute, `roi` as a rectangle, "auto" or "matte" (the rectangle around
+             every lit cell of every frame's cell map, moved out by the 8 pixels the ramp reaches, then grown as above), and
+             `stream=True` (an all-sharp stream never calls the model).  `ClipRun.matte` is then a `blurmap.AutoMattes`, whose
+             `cells` holds the verdict maps [T,ch,cw] on the host.  Refused: with `fields=` (the rows of a frame are two instants,
+             so the vertical measure is meaningless: not built), with `matte_invert=True`, and `roi="matte"` with `stream=True`.
+             The definition in full, its four parameters (design parameters, not measurements: nobody has tuned them) and its
+             blind spots (grain on top of a blurred region reads as sharp; a defocused background is "blurred"; a cell below
+             `flat` is never lit): speinet_amd/blurmap.py.
     matte_invert — with `matte` only: the matte in effect is 255 - m.
+    matte_params — with matte="auto" only: a dict over `MATTE_PARAMS`: thr (0..257, default 192), flat (0..255, default 2), grow
+             (0..4, default 1), hold (0 or 1, default 1); an unknown key or a value out of range is a ValueError.
 
     The frames are validated here (ValueError with the reason); the GPU work starts with the first `next`.  A yielded frame is
     complete in the order of the stream that is current at that `next`: use it there, or synchronise first.  A window whose frame
@@ -871,6 +927,20 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
     fields = check_fields(fields)
     if matte is None and matte_invert:
         raise ValueError("matte_invert=True needs matte=: there is no matte to invert")
+    auto = isinstance(matte, str) and matte == "auto"
+    if matte_params is not None and not auto:
+        raise ValueError("matte_params= needs matte=\"auto\": they are the parameters of the measured matte, a given one has none")
+    if auto:
+        if fields is not None:
+            raise ValueError(f"matte=\"auto\" with fields={fields!r} is not built: the rows of an interlaced frame are two instants, so the "
+                             "vertical blur measure is meaningless")
+        if matte_invert:
+            raise ValueError("matte=\"auto\" with matte_invert=True: the measured matte is lit where the picture is blurred, and deblurring "
+                             "where it is sharp instead serves nothing")
+        if stream and isinstance(roi, str) and roi == "matte":
+            raise ValueError("roi=\"matte\" with stream=True and matte=\"auto\": the bounding box is found from the mattes of every frame "
+                             "before the first window, and a stream's length is not known; give the rectangle (y0, x0, h, w)")
+        blur_params = BlurParams.of(matte_params)
     if matte is None and isinstance(roi, str) and roi == "matte":
         raise ValueError("roi=\"matte\" needs matte=: the rectangle is the bounding box of the mattes")
     if fields is not None and (tiles is not None or roi is not None):
@@ -916,7 +986,7 @@ def deblur_clip(model, frames, labels=None, *, out: Optional[torch.Tensor] = Non
                              "the rectangle (y0, x0, h, w)")
     # a stream's `fr.T` is None: what is measured against the clip's length is then checked by `StreamPlan` as the stream goes
     fr = frames_of(frames, crop, yuv, depth)
-    mt = None if matte is None else mattes_of(matte, fr.T, *fr.src, crop, matte_invert)
+    mt = None if matte is None else blurmap.AutoMattes(blur_params, fr.H, fr.W) if auto else mattes_of(matte, fr.T, *fr.src, crop, matte_invert)
     if stream and mt is not None and not mt.static and isinstance(roi, str) and roi == "matte":
         raise ValueError("roi=\"matte\" with stream=True and a per-frame matte: the bounding box is found in one pass over every matte "
                          "before the first window, and a stream's length is not known; give the rectangle (y0, x0, h, w) or a static matte")
@@ -1093,6 +1163,14 @@ def main(argv=None) -> None:
                    "grey).  Images are read as one 8-bit channel.  A frame whose matte is empty runs no window and is written as the "
                    "input frame (y4m in and out with the input's chroma layout, depth and range: the input's record, byte for byte)")
     p.add_argument("--matte_invert", action="store_true", help="with --matte: use 255 - m, deblur where the matte is black")
+    p.add_argument("--matte_params", default=None, help="with --matte auto ('auto' measures the mattes: deblur where the picture is blurred; "
+                   "a file of that name is ./auto): NAME=N,... over thr (0..257, default 192: a cell is blurred where a 9-tap box removes "
+                   "less than thr/256 of its adjacent-pixel variation), flat (0..255, default 2: 8-bit levels of RMS difference below "
+                   "which a cell is not judged), grow (0..4, default 1: cells of dilation) and hold (0 | 1, default 1: join the cells of "
+                   "the frames of a window).  Untuned design parameters")
+    p.add_argument("--matte_out", default=None, help="with --matte: write the matte in effect of every frame to this file as an 8-bit Cmono "
+                   "y4m record, full range as stored, zeros for a frame that was written as its input; inspect it, repair it in a paint "
+                   "tool and feed it back through --matte FILE.y4m")
     p.add_argument("--sharp", choices=SHARP, default="deblur", help="what becomes of a frame labelled sharp (by --labels or the detector): "
                    "'deblur' (the default) runs its window like any other; 'keep' runs none and writes the input frame (y4m in and out "
                    "with the input's chroma layout, depth and range: the input's record, byte for byte).  The blurry frames are the "
@@ -1135,8 +1213,28 @@ def main(argv=None) -> None:
         raise SystemExit("--matte_invert: needs --matte: there is no matte to invert")
     if a.matte is None and a.roi == "matte":
         raise SystemExit("--roi matte: needs --matte: the rectangle is the bounding box of the mattes")
-    matte = None
-    if a.matte is not None:                                # a file (an image or a .y4m clip), a directory, or a glob of images
+    matte, matte_params = None, None
+    if a.matte_params is not None:
+        if a.matte != "auto":
+            raise SystemExit("--matte_params: needs --matte auto: they are the parameters of the measured matte")
+        try:
+            matte_params = blurmap.parse_params(a.matte_params)
+            BlurParams.of(matte_params)
+        except ValueError as e:
+            raise SystemExit(f"--matte_params: {e}")
+    if a.matte_out is not None and a.matte is None:
+        raise SystemExit("--matte_out: needs --matte: there is no matte to write")
+    if a.matte_out is not None and not a.matte_out.lower().endswith(".y4m"):
+        raise SystemExit(f"--matte_out {a.matte_out}: the mattes are written as one Cmono .y4m file")
+    if a.matte == "auto":                                  # measured, not read: a file of that name is ./auto
+        if a.matte_invert:
+            raise SystemExit("--matte auto with --matte_invert: the measured matte is lit where the picture is blurred")
+        if a.fields == "split":
+            raise SystemExit("--matte auto with --fields split is not built: the rows of an interlaced frame are two instants")
+        if a.stream and a.roi == "matte":
+            raise SystemExit("--roi matte with --stream: the bounding box is found from every matte before the first window; give Y,X,H,W")
+        matte = "auto"
+    elif a.matte is not None:                              # a file (an image or a .y4m clip), a directory, or a glob of images
         matte = a.matte if os.path.isfile(a.matte) or os.path.isdir(a.matte) else _inputs(a.matte)
         if not matte or (os.path.isdir(a.matte) and not _inputs(a.matte)):
             raise SystemExit(f"--matte {a.matte}: no image file, directory of images, glob or .y4m file of that name")
@@ -1202,7 +1300,8 @@ def main(argv=None) -> None:
     run = deblur_clip(net, files, labels, detector=detector.DetectorParams.load(a.detector) if a.detector else None, cuts=cuts,
                       yuv=yuv or None, out_depth=out_depth, tiles=tiles, shave=a.shave, feather=a.feather, ensemble=a.ensemble,
                       roi=roi, roi_feather=a.roi_feather, stream=a.stream, horizon=a.horizon, sharp=a.sharp, fields=fields,
-                      **({} if matte is None else dict(matte=matte, matte_invert=a.matte_invert)))
+                      **({} if matte is None else dict(matte=matte, matte_invert=a.matte_invert)),
+                      **({} if matte_params is None else dict(matte_params=matte_params)))
     out_depth = run.out_depth
     H, W = run.frames.H, run.frames.W
     writer = None
@@ -1228,6 +1327,9 @@ def main(argv=None) -> None:
         say(f"# fields: {'split' if fields is not None else 'progressive'} (I{tag})")
     if run.matte is not None:
         say(f"# matte {a.matte}: {run.matte.describe()}")
+    matte_writer = None
+    if a.matte_out is not None:
+        matte_writer = y4m.Y4MWriter(a.matte_out, W, H, a.fps or (reader.fps if reader is not None else (25, 1)), y4m.MONO, y4m.FULL)
     if run.roi is not None:
         say("# roi " + ",".join(str(v) for v in run.roi))
     said = 0                                               # a stream's cuts are reported as they are found
@@ -1255,6 +1357,9 @@ def main(argv=None) -> None:
         if a.stream and to_stdout:                         # a live pipe: the frame leaves now, not when the buffer is full
             sys.stdout.buffer.flush()
     # PNGs are encoded on four threads; a y4m stream is written by ONE, so its frames land in the order they were queued
+    # the mattes of --matte_out (only then): a ring and one writer of their own, so that they land in frame order
+    matte_writers = None if matte_writer is None else ThreadPoolExecutor(max_workers=1, thread_name_prefix="speinet-matte")
+    matte_ring, blank = None if matte_writer is None else HostRing(matte_writers), None
     with ThreadPoolExecutor(max_workers=1 if to_y4m else 4, thread_name_prefix="speinet-y4m" if to_y4m else "speinet-png") as writers:
         ring = HostRing(writers)
         records = RecordQueue(writers, ring.n)             # input records on their way out: as many in flight as the ring has slots
@@ -1266,6 +1371,13 @@ def main(argv=None) -> None:
                 said = len(run.cuts)
             is_kept = bool(run.kept) and run.kept[-1] == i
             is_unmatted = bool(run.unmatted) and run.unmatted[-1] == i
+            if matte_writer is not None:                   # the matte in effect: 255 - m under --matte_invert, zeros where none was used
+                m = run.handed_matte
+                if m is None:
+                    m = blank = torch.zeros(H, W, dtype=torch.uint8, device=frame.device) if blank is None else blank
+                elif run.matte.invert:
+                    m = 255 - m
+                matte_ring.land(lambda buf: matte_writer.write(buf.numpy()), m)
             if (is_kept or is_unmatted) and as_read:                        # a copy: a stream gives the record up a few frames on; the one writer keeps order
                 records.put(write, run.frames.host(i))
             elif to_y4m:
@@ -1285,6 +1397,10 @@ def main(argv=None) -> None:
         records.drain()
     if writer is not None:
         writer.close()
+    if matte_writer is not None:
+        matte_ring.drain()
+        matte_writers.shutdown()
+        matte_writer.close()
     dt = time.time() - t0
     if a.sharp == "keep":
         say(f"# kept {len(run.kept)} of {done} frames")
